@@ -13,15 +13,18 @@ reference generator emits it, random-init (ortho) weights.
 
     value = agents x env instances (all ranks) x simulated seconds / wall time     [env-steps/s]
 
-The timed region carries no profiling; a second pass of the same loop, HIP events around every launch on the launch
-stream, gives the per-kernel table.  `--config c2 | c3 | c5` select BASELINE.json configs[1], [2] (default), [4].
+`--config c2 | c3 | c5` select BASELINE.json configs[1], [2] (default), [4].  A plain run sets up, warms up, times the
+`--steps` iterations and prints the result line; `--dump-outputs DIR` also writes what the last timed iteration computed
+(dump_outputs), so that two builds can be compared output for output.
 
-Adds `roofline` (dominant kernel, timed live with HIP events on the launch stream) and
-`cpu_baseline` (the CPU oracle -- C microsim + NumPy env wrapper + torch-CPU nets, float32 like the reference and float64
-like the checker -- on a bounded sample of the same workload, rank 0, N = 1 only; it also quotes the committed timing of the
-reference's own env class over the fake TraCI backend, which exists in the build container only).  The plain driver
-line (`python bench.py`, N = 1) also carries short runs of the other single-GPU configurations, BASELINE.json configs[1]
-(c2) and configs[4]'s per-GPU share (c5), under `extra.configs`.
+Everything else the line can carry is measured only with `--full`.  The timed region carries no profiling; a second pass of
+the same loop, HIP events around every launch on the launch stream, gives the per-kernel table and `roofline` (dominant
+kernel).  `cpu_baseline` is the CPU oracle -- C microsim + NumPy env wrapper + torch-CPU nets, float32 like the reference
+and float64 like the checker -- on a bounded sample of the same workload, rank 0, N = 1 only; it also quotes the committed
+timing of the reference's own env class over the fake TraCI backend.  The full driver line (`python bench.py --full`,
+N = 1, default workload) also carries the sim-only / sim + forward lines and short runs of the other single-GPU
+configurations, BASELINE.json configs[1] (c2) and configs[4]'s per-GPU share (c5), under `extra.configs`, and the IQL-DNN
+learner under `extra.iql`.
 """
 import argparse
 import json
@@ -426,7 +429,40 @@ def rank_table(rank, world, local, backend):
             'rccl_version': ver, 'distinct_devices': len({(r['host'], r['device_id'] or r['device_index']) for r in rows}), 'ranks': rows}
 
 
-def run_config(args, rank, world, local, scenario, agent, policy, E, steps, warmup, want_extra, want_cpu, want_profile):
+DUMP_INSTANCES = 256                    # --dump-outputs: per-instance arrays keep this many env instances (fixed seeded sample)
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(tr, path):
+    """--dump-outputs: what the last timed iteration computed, as a caller of the trainer reads it, one DIR/<name>.npy each:
+    `params` (the learner's flat parameters after the update), `grad` (the flat gradient buffer of that update), `obs` (the
+    observation the next iteration starts from) and, for the A2C agents, the on-policy rollout the update consumed: `action`,
+    `value`, `reward` (float64, as stored in the buffer) and `done` (after each control step), [n_step, instances, ...].
+    Per-instance arrays keep a fixed, seeded sample of DUMP_INSTANCES env instances (the same ones on every run with the same
+    arguments), which keeps the files of every preset under 64 MB.  Integer arrays are written as float32."""
+    parts = getattr(tr, 'parts', [tr])
+    model = parts[0].model
+    out = {'params': model.get_flat(), 'grad': model.grad_tensor().cpu().numpy(),
+           'obs': torch.cat([p.ob for p in parts], 0).cpu().numpy()}
+    E = out['obs'].shape[0]
+    idx = np.sort(np.random.RandomState(0).choice(E, min(E, DUMP_INSTANCES), replace=False))
+    out['obs'] = out['obs'][idx]
+    if all(p.agent.endswith('a2c') for p in parts):
+        sl = [p.model.rollout_slots() for p in parts]
+        for k in ('action', 'value', 'reward'):
+            out[k] = torch.cat([s[k] for s in sl], 1).cpu().numpy()[:, idx]
+        out['done'] = torch.cat([s['done'][1:] for s in sl], 1).cpu().numpy()[:, idx]
+    out = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float32) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit('bench.py: --dump-outputs would write %.1f MB, more than %d MB' % (total / 2 ** 20, DUMP_LIMIT >> 20))
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + '.npy'), v)
+
+
+def run_config(args, rank, world, local, scenario, agent, policy, E, steps, warmup, want_extra, want_cpu, want_profile,
+               dump=None):
     """Build the env instances and the learner of one configuration on this rank's GPU, time `steps` A2C iterations after
     `warmup` (barrier + device synchronisation on both sides, MAX over ranks) and return the JSON line as a dict (rank 0)."""
     from deeprl_signal_control_amd import _lib
@@ -482,6 +518,8 @@ def run_config(args, rank, world, local, scenario, agent, policy, E, steps, warm
     # window mean over the timed region of the vehicles in the network per env instance (SURVEY 8d's V)
     live = float(np.mean([e_.live_vehicle_mean(steps * model.n_step) for e_ in envs]))
     msr = tr.mean_step_reward()
+    if dump and rank == 0:
+        dump_outputs(tr, dump)                      # before any further iteration (the profiled passes) moves the state on
     # ---- a second, profiled pass of the same loop: HIP events on the launch stream around every kernel -------------
     # a profiled pass covers one whole episode (T / n_step iterations, whatever its phase): its vehicle count is the episode mean,
     # the figure the committed PMC summaries were collected at
@@ -683,9 +721,14 @@ def main():
     ap.add_argument('--scenario', default='large_grid', choices=['large_grid', 'real_net'])
     ap.add_argument('--policy', default='lstm', choices=['lstm', 'fc', 'dqn', 'lr'], help='fc = FcACPolicy (BASELINE configs[1], ia2c only); dqn / lr: the IQL agents\' Q nets')
     ap.add_argument('--batches', type=int, default=1, help='independent half-batches per GPU on separate HIP streams')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the sim-only / sim+forward lines (SURVEY 8d) and the other single-GPU configs')
-    ap.add_argument('--no-profile', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: the profiled passes (kernels, roofline), the CPU baseline, '
+                         'and on the default workload the sim-only / sim+forward lines and the other single-GPU configurations')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed iteration computed as DIR/<name>.npy (float32 / float64, at most 64 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='--full without the sim-only / sim+forward lines (SURVEY 8d) and the other single-GPU configs')
+    ap.add_argument('--no-profile', action='store_true', help='--full without the profiled passes')
     ap.add_argument('--no-lane-change', action='store_true', help='large_grid without MICROSIM_SPEC.md rule 10 (the rounds 1 - 4 spec): A/B measurement only')
     ap.add_argument('--profile-stride', type=int, default=1,
                     help='profiled pass: HIP-event timing of every n-th launch of the per-control-step kernels (1 = all)')
@@ -708,8 +751,10 @@ def main():
         args.steps = 2 * ipe
     if args.warmup is None:
         args.warmup = warmup_iterations(ipe)
-    # the plain driver line (no --config / --envs ... given) also carries the other single-GPU configurations of BASELINE.json
-    plain = (args.config is None and (args.scenario, args.agent, args.policy, args.envs, args.batches) == ('large_grid', 'ma2c', 'lstm', 1024, 1))
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    # the full driver line (no --config / --envs ... given) also carries the other single-GPU configurations of BASELINE.json
+    default_workload = (args.config is None and (args.scenario, args.agent, args.policy, args.envs, args.batches) == ('large_grid', 'ma2c', 'lstm', 1024, 1))
 
     rank = int(os.environ.get('RANK', 0))
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -726,8 +771,9 @@ def main():
     torch.cuda.set_device(local)
 
     out = run_config(args, rank, world, local, args.scenario, args.agent, args.policy, args.envs, args.steps, args.warmup,
-                     want_extra=not args.no_extra, want_cpu=False, want_profile=not args.no_profile)
-    if rank == 0 and world == 1 and plain and not args.no_extra:
+                     want_extra=args.full and not args.no_extra, want_cpu=False, want_profile=args.full and not args.no_profile,
+                     dump=args.dump_outputs)
+    if rank == 0 and world == 1 and default_workload and args.full and not args.no_extra:
         # BASELINE.json configs[1] and configs[4] (per-GPU share), same method, short runs: value, iteration time, window-mean
         # vehicles and the dominant kernel's roofline fraction of each -- one driver-run line evidences c2 / c3 / c5
         cfgs = {}
@@ -754,7 +800,7 @@ def main():
                                                                               'share_of_kernel_time', 'algorithmic')}
             out['extra']['iql']['kernels'] = o['kernels']
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
         print(json.dumps(out))
     if world > 1:

@@ -90,3 +90,49 @@ def test_default_window_is_two_whole_episodes_after_whole_warm_up_episodes():
     from deeprl_signal_control_amd.iql import IQL_DEFAULTS
     assert 720 // A2C_DEFAULTS['batch_size'] == b.iterations_per_episode('large_grid', 'ma2c')
     assert 720 // IQL_DEFAULTS['batch_size'] == b.iterations_per_episode('large_grid', 'iqld')
+
+
+def test_dump_outputs_writes_floats_of_one_fixed_instance_sample(tmp_path):
+    """--dump-outputs: every array a float32 / float64 .npy, the per-instance arrays cut to the same seeded sample of instances
+    (rows of `obs` line up with the instance axis of the rollout), the same sample on every call, and nothing over 64 MB."""
+    import numpy as np
+    import pytest
+    import torch
+    b = _bench()
+    T, E, A, S = 4, b.DUMP_INSTANCES + 44, 3, 5
+    inst = torch.arange(E, dtype=torch.float32)
+    slots = {'obs': torch.zeros(T + 1, E, A, S), 'action': inst.to(torch.int32)[None, :, None].repeat(T, 1, A),
+             'value': inst[None, :, None].repeat(T, 1, A), 'reward': inst.double()[None, :, None].repeat(T, 1, A),
+             'done': torch.ones(T + 1, E, dtype=torch.uint8)}
+
+    class Model:
+        n = 10
+
+        def get_flat(self):
+            return np.arange(self.n, dtype=np.float32)
+
+        def grad_tensor(self):
+            return torch.full((self.n,), 0.5)
+
+        def rollout_slots(self):
+            return slots
+
+    class Trainer:
+        agent, model, ob = 'ma2c', Model(), inst[:, None, None].repeat(1, A, S)
+
+    got = []
+    for run in ('a', 'b'):
+        b.dump_outputs(Trainer(), str(tmp_path / run))
+        got.append({f[:-4]: np.load(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))})
+    d = got[0]
+    assert set(d) == {'params', 'grad', 'obs', 'action', 'value', 'reward', 'done'}
+    assert all(v.dtype in (np.float32, np.float64) for v in d.values()) and d['reward'].dtype == np.float64
+    n = b.DUMP_INSTANCES
+    assert d['obs'].shape == (n, A, S) and d['action'].shape == (T, n, A) and d['done'].shape == (T, n)
+    picked = d['obs'][:, 0, 0]
+    assert len(set(picked)) == n and (np.diff(picked) > 0).all()
+    assert (d['action'][0, :, 0] == picked).all() and (d['reward'][-1, :, -1] == picked).all()
+    assert all(np.array_equal(v, got[1][k]) for k, v in d.items())
+    Trainer.model.n = (b.DUMP_LIMIT >> 2) + 1
+    with pytest.raises(SystemExit):
+        b.dump_outputs(Trainer(), str(tmp_path / 'big'))

@@ -1,5 +1,5 @@
 """Reads a bench.py JSON line on stdin and prints value, iteration time and the per-launch averages of the largest kernels
-(A/B runs on the GPU box: `TSC_ENV_KF=3 python bench.py --no-extra --no-cpu-baseline | python tools/bench_brief.py kf3`)."""
+(A/B runs on an MI355X: `TSC_ENV_KF=3 python bench.py --full --no-extra --no-cpu-baseline | python tools/bench_brief.py kf3`)."""
 import json
 import sys
 

@@ -2,7 +2,7 @@
 # Profiles of one round, on the GPU box (run through gpurun from the repo root):
 #   tools/profile_round.sh r06 [cal c2 c5 q1 c3]
 # per configuration (c3 = the default workload; suffix "" / _c2 / _c5 / _q1):
-# 1. (run last, see below) the bench line (c3: the driver line `python bench.py` with extra.configs and cpu_baseline)
+# 1. (run last, see below) the bench line with --full (c3: the driver line `python bench.py --full` with extra.configs and cpu_baseline)
 # 2. rocprofv3 --kernel-trace --stats of the same command (every launch timed by the profiler; bench.py's default window = whole
 #    episodes, so the per-kernel averages are episode averages like the live HIP-event figures)
 # 3. PMC passes, each in its own run without any trace (MI355X_MICROARCH.md "HBM / rocprofv3"): FETCH_SIZE, WRITE_SIZE, SQ.
@@ -56,9 +56,9 @@ for C in $CFGS; do
   cp $RES/${TAG}_kernel_stats${SUF}.csv $ROOT/profiles/ 2>/dev/null
   [ -f $RES/${TAG}_pmc${SUF}.json ] && cp $RES/${TAG}_pmc${SUF}.json $ROOT/profiles/
   if [ $C = c3 ]; then
-    python $ROOT/bench.py > $RES/${TAG}_bench.json 2> $OUT/${TAG}_bench.err           # the driver line
+    python $ROOT/bench.py --full > $RES/${TAG}_bench.json 2> $OUT/${TAG}_bench.err    # the driver line
   else
-    python $ROOT/bench.py --config $C --no-cpu-baseline > $RES/${TAG}_bench${SUF}.json 2> $OUT/${TAG}_bench${SUF}.err
+    python $ROOT/bench.py --config $C --full --no-cpu-baseline > $RES/${TAG}_bench${SUF}.json 2> $OUT/${TAG}_bench${SUF}.err
   fi
 done
 ls -la $RES
