@@ -239,6 +239,7 @@ def _setup_lib(L):
     L.tsc_model_destroy.argtypes = [vp]
     L.tsc_model_set_stream.argtypes = [vp, vp]
     L.tsc_model_layout.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.tsc_model_path.argtypes = [vp, C.POINTER(C.c_int32)]
     for f in ('tsc_model_set_params', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state'):
         getattr(L, f).argtypes = [vp, vp]
     L.tsc_model_reset_opt_state.argtypes = [vp]
@@ -268,9 +269,7 @@ class VecA2C:
             raise RuntimeError('VecA2C needs a GPU (MI355X); there is no CPU fallback')
         cfg = coerce_config(model_config, A2C_DEFAULTS)
         self.cfg, self.name = cfg, name
-        self.policy = policy                    # 'lstm' (what the reference instantiates) or 'fc' (FcACPolicy)
-        if policy == 'fc' and name == 'ma2c':
-            raise ValueError('FcACPolicy has no working fingerprint variant in the reference (policies.py:259-282)')
+        self.policy = policy                    # 'lstm' (what the reference instantiates) or 'fc' (FcACPolicy; MA2C: FPFcACPolicy)
         self.n_agent, self.E = len(n_s_ls), int(n_env)
         self.n_s_ls, self.n_a_ls, self.n_w_ls, self.n_f_ls = map(list, (n_s_ls, n_a_ls, n_w_ls, n_f_ls))
         if name != 'ma2c':
@@ -305,6 +304,11 @@ class VecA2C:
         self.layout = ParamLayout(self.n_wave_ls, self.n_w_ls, self.n_f_ls, self.n_a_ls, self.s_max, self.n_fc,
                                   self.Lh, self.out_pad, policy)
         assert self.layout.as_tuple() == tuple(int(x) for x in lay), 'host / device parameter layouts disagree'
+        path = (C.c_int32 * 2)()
+        _lib.check(L.tsc_model_path(h, path))
+        # FC policy: (rollout forward 2 = policy_fwd_fc_mfma_kernel / 1 = policy_fwd_fc_kernel / 0 = dense GEMMs,
+        # update 1 = fused fc_bwd_kernel / 0 = grouped GEMMs); (-1, -1) for the LSTM policy (include/tsc.h tsc_model_path)
+        self.fc_path = (int(path[0]), int(path[1]))
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream(self.device)
             _lib.check(L.tsc_model_set_stream(h, C.c_void_p(self.stream.cuda_stream)))

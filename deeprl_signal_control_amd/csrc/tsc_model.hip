@@ -2156,7 +2156,7 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     constexpr int LDX = H + 16;                                 // X1 chunk rows: (LDX % 32) == 16 -> the four k rows of an MFMA step sit on two bank halves
     constexpr int NF = NCU / 2;                                 // dWfc tiles per wave
     constexpr int XQ = H / 4, NXQ = 32 * XQ, NXL = (NXQ + 511) / 512;
-    static_assert(NXL <= 3, "X1 staging slots");
+    static_assert(NXL <= 4, "X1 staging slots");             // 4 at H = 224 (MA2C-FC, large_grid): 32 x 56 quads
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float *Az = (float *)smem_raw;                              // [2][32][kFbLdz]
     float *Ob = Az + 2 * 32 * kFbLdz;                           // [2][32][kObLd]
@@ -2203,7 +2203,7 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
 #pragma unroll
     for (int j = 0; j < NF; ++j) accF[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bsumF = 0.f;
-    // ---- staging: thread -> one dZ float4 (row tid >> 4, 16-byte column tid & 15), one obs float4, up to three X1 float4s.
+    // ---- staging: thread -> one dZ float4 (row tid >> 4, 16-byte column tid & 15), one obs float4, up to four X1 float4s.
     // Rows past the split are stored as ZERO dZ rows: they then contribute nothing to either layer.
     const int zr = tid >> 4, zc = tid & 15;
     struct XSlot { int row, col; bool ok; };
@@ -2215,8 +2215,8 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
         o.row = idx / XQ; o.col = 4 * (idx % XQ);
         return o;
     };
-    const XSlot x0 = xslot(0), x1s = xslot(1), x2s = xslot(2);
-    float4 sz, so, sx0, sx1, sx2;
+    const XSlot x0 = xslot(0), x1s = xslot(1), x2s = xslot(2), x3s = xslot(3);
+    float4 sz, so, sx0, sx1, sx2, sx3;
     auto fetch = [&](long long row0) {
         auto rowc = [&](long long r) { return r < n1 ? r : n1 - 1; };
         const float4 z = *reinterpret_cast<const float4 *>(dz + rowc(row0 + zr) * kL + 4 * zc);
@@ -2226,6 +2226,7 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
         sx0 = *reinterpret_cast<const float4 *>(x1 + rowc(row0 + x0.row) * H + x0.col);
         if (NXL > 1) sx1 = *reinterpret_cast<const float4 *>(x1 + rowc(row0 + x1s.row) * H + x1s.col);
         if (NXL > 2) sx2 = *reinterpret_cast<const float4 *>(x1 + rowc(row0 + x2s.row) * H + x2s.col);
+        if (NXL > 3) sx3 = *reinterpret_cast<const float4 *>(x1 + rowc(row0 + x3s.row) * H + x3s.col);
     };
     auto put = [&](int buf) {
         *reinterpret_cast<float4 *>(Az + ((long long)buf * 32 + zr) * kFbLdz + 4 * zc) = sz;
@@ -2234,6 +2235,7 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
         if (x0.ok) *reinterpret_cast<float4 *>(xb + x0.row * LDX + x0.col) = sx0;
         if (NXL > 1 && x1s.ok) *reinterpret_cast<float4 *>(xb + x1s.row * LDX + x1s.col) = sx1;
         if (NXL > 2 && x2s.ok) *reinterpret_cast<float4 *>(xb + x2s.row * LDX + x2s.col) = sx2;
+        if (NXL > 3 && x3s.ok) *reinterpret_cast<float4 *>(xb + x3s.row * LDX + x3s.col) = sx3;
     };
     // one column unit of the chunk in LDS buffer `buf`: both / one of its row tiles
     auto unit = [&](int buf, long long row, const float (&bw)[16], int col, bool r0, bool r1, f32x4 (&aw)[4], float &bs, int fm) {
@@ -2552,11 +2554,13 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
     if (const char *ev = getenv("TSC_UNFUSED_DW")) if (atoi(ev)) m->fused_dw = 0;
     m->fused_dx = !L.fc && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128) && L.SMAX <= 64 && L.SMAX % 4 == 0;
     if (const char *ev = getenv("TSC_UNFUSED_DX")) if (atoi(ev)) m->fused_dx = 0;
-    m->fused_fc = L.fc && (L.H == 160 || L.H == 128) && L.SMAX <= 64 && L.SMAX % 4 == 0;
+    m->fused_fc = L.fc && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128) && L.SMAX <= 64 && L.SMAX % 4 == 0;
     if (const char *ev = getenv("TSC_UNFUSED_DX")) if (atoi(ev)) m->fused_fc = 0;
     if (m->fused_fc) {
         const int lds = (int)(sizeof(float) * (2 * 32 * kFbLdz + 2 * 32 * kObLd + 2 * 32 * (L.H + 16)));
+        TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<14>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
     }
     if (m->fused_dx) {
@@ -2649,6 +2653,39 @@ int tsc_model_reset(tsc_model *m) {
     return 0;
 }
 
+// FcACPolicy rollout forward on the matrix cores: the widths policy_fwd_fc_mfma_kernel is instantiated for (H = 32 NCT,
+// NCT = 4..7; LDS 64 x 33 + 2 x 32 x (H + 1) + 8 x 32 x 33 + 2 x 32 x kFcLdo floats = 114 KiB at H = 224, under 160 KiB)
+static bool fc_mfma_path(const tsc_model *m) {
+    const Layout &L = m->lay;
+    return L.fc && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128) && L.SMAX <= 64 && L.AMAX <= kOut && m->fc_mfma;
+}
+
+// the per-thread FcACPolicy forward (policy_fwd_fc_kernel) and its LDS: 161 KiB at H = 224 does not fit, so MA2C-FC on
+// large_grid with TSC_FC_MFMA=0 takes the dense GEMMs + head_fwd_kernel instead (H = 192, Monaco: 145 KiB, fits)
+static size_t fc_thread_lds(int H) { return sizeof(float) * ((size_t)64 * kFcLdo + (size_t)2 * 64 * (H + 1) + (size_t)2 * 64 * kFcLdo); }
+static bool fc_thread_path(const tsc_model *m) {
+    const Layout &L = m->lay;
+    return L.fc && L.H % 16 == 0 && L.SMAX <= 64 && L.AMAX <= kOut && fc_thread_lds(L.H) <= 160 * 1024;
+}
+
+// split-K factor of the FcACPolicy update (~ one workgroup per CU) and whether it runs as fc_bwd_kernel: the fused widths,
+// a workspace of (2 x 65 H + (H + 1) x 64) floats per split x tower that fits, and b1 / bfc where the reduce expects them
+static int fc_bwd_splits(const tsc_model *m) { const int S = 256 / m->lay.G; return S < 1 ? 1 : S; }
+static bool fc_fused_bwd_path(const tsc_model *m) {
+    const Layout &L = m->lay;
+    const long long perfc = (long long)2 * 65 * L.H + (long long)(L.H + 1) * kL;
+    return m->fused_fc && (size_t)((long long)fc_bwd_splits(m) * L.G * perfc) <= m->ws_floats &&
+           L.ob1 == L.oW1 + (long long)L.SMAX * L.H && L.obl == L.oWx + (long long)L.H * kL;
+}
+
+int tsc_model_path(tsc_model *m, int32_t out[2]) {
+    if (!m || !out) return tsc::fail("tsc_model_path: bad arguments");
+    const bool fc = m->lay.fc != 0;
+    out[0] = !fc ? -1 : fc_mfma_path(m) ? 2 : fc_thread_path(m) ? 1 : 0;
+    out[1] = !fc ? -1 : fc_fused_bwd_path(m) ? 1 : 0;
+    return 0;
+}
+
 static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, float *pi, float *v, int32_t advance,
                          int32_t *action, uint64_t seed, uint64_t step, int32_t tslot) {
     if (!m || !obs || !done || !pi || !v) return tsc::fail("tsc_model_forward: bad arguments");
@@ -2657,7 +2694,7 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
     // activation cache: valid only if slots 0..T-1 are filled in order by advancing forwards
     if (advance) {
         if (tslot == 0) m->cached_next = 0;         // slot 0 opens a rollout: whatever invalidated the cache before is history
-        const bool fc_cache = L.fc && (L.H == 160 || L.H == 128) && L.SMAX <= 64 && L.AMAX <= kOut && m->fc_mfma;   // policy_fwd_fc_mfma_kernel
+        const bool fc_cache = fc_mfma_path(m);                                                                       // policy_fwd_fc_mfma_kernel
         if ((m->fused_fwd || fc_cache) && tslot >= 0 && tslot == m->cached_next && tslot < m->T) m->cached_next = tslot + 1;
         else { m->cached_next = -1; tslot = -1; }
     } else {
@@ -2721,38 +2758,38 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
         TSC_HIP(hipGetLastError());
         return 0;
     }
-    if (L.fc && (L.H == 160 || L.H == 128) && L.SMAX <= 64 && L.AMAX <= kOut && m->fc_mfma) {   // FcACPolicy (IA2C: large_grid / Monaco) on the matrix cores
+    if (fc_mfma_path(m)) {      // FcACPolicy on the matrix cores (IA2C H = 160 / 128, MA2C H = 224 / 192: large_grid / Monaco)
         const size_t lds = sizeof(float) * ((size_t)64 * kFmLd + (size_t)2 * 32 * (L.H + 1) + (size_t)8 * 32 * kFmLd + (size_t)2 * 32 * kFcLdo);
         static bool attr_set2 = false;
         if (!attr_set2) {
             TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_set2 = true;
         }
         tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
 #define TSC_FCM(NCT) hipLaunchKernelGGL(policy_fwd_fc_mfma_kernel<NCT>, dim3((unsigned)((E + 31) / 32), (unsigned)L.A), dim3(512), lds, m->stream, m->params, L, \
                                         m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step, (int)tslot, (long long)m->T * E, m->X1, m->Hh)
-        if (L.H == 128) TSC_FCM(4); else TSC_FCM(5);
+        if (L.H == 224) TSC_FCM(7); else if (L.H == 160) TSC_FCM(5); else if (L.H == 192) TSC_FCM(6); else TSC_FCM(4);
 #undef TSC_FCM
         ps.stop();
         TSC_HIP(hipGetLastError());
         return 0;
     }
-    if (L.fc && L.H % 16 == 0 && L.SMAX <= 64 && L.AMAX <= kOut) {     // FcACPolicy: one launch (policy_fwd_fc_kernel)
-        const size_t lds = sizeof(float) * ((size_t)64 * kFcLdo + (size_t)2 * 64 * (L.H + 1) + (size_t)2 * 64 * kFcLdo);
+    if (fc_thread_path(m)) {     // FcACPolicy: one launch (policy_fwd_fc_kernel)
+        const size_t lds = fc_thread_lds(L.H);
         static bool attr_set = false;
         if (!attr_set) {
             TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_set = true;
         }
-        if (lds <= 160 * 1024) {
-            tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
-            hipLaunchKernelGGL(policy_fwd_fc_kernel, dim3((unsigned)((E + 63) / 64), (unsigned)L.A), dim3(512), lds, m->stream, m->params, L,
-                               m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step);
-            ps.stop();
-            TSC_HIP(hipGetLastError());
-            return 0;
-        }
+        tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
+        hipLaunchKernelGGL(policy_fwd_fc_kernel, dim3((unsigned)((E + 63) / 64), (unsigned)L.A), dim3(512), lds, m->stream, m->params, L,
+                           m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step);
+        ps.stop();
+        TSC_HIP(hipGetLastError());
+        return 0;
     }
     // unfused path (shapes the fused kernels do not cover): the training kernels with T = 1
     if (dense_forward(m, obs, E, m->X1, L.fc ? m->Hh : m->Z)) return tsc::fail("tsc_model_forward: gemm launch failed");
@@ -2871,11 +2908,8 @@ int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
         hipLaunchKernelGGL(transpose_wx_kernel, dim3((unsigned)((G * L.H * L.NZ + 255) / 256)), dim3(256), 0, st, m->params, L, m->WxT);
         ps9.stop();
         TSC_HIP(hipGetLastError());
-        int S = 256 / (int)G;                       // ~ one workgroup per CU
-        if (S < 1) S = 1;
-        const long long perfc = (long long)2 * 65 * L.H + (long long)(L.H + 1) * kL;
-        if (m->fused_fc && (size_t)((long long)S * G * perfc) <= m->ws_floats && L.ob1 == L.oW1 + (long long)L.SMAX * L.H &&
-            L.obl == L.oWx + (long long)L.H * kL) {
+        const int S = fc_bwd_splits(m);             // ~ one workgroup per CU
+        if (fc_fused_bwd_path(m)) {
             // both layers' weight gradients in one pass, dX1 never leaves the registers (fc_bwd_kernel)
             long long rps = (N + S - 1) / S;
             rps = (rps + 31) / 32 * 32;                  // whole 32-row chunks
@@ -2883,7 +2917,7 @@ int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
             {
                 tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
 #define TSC_FCB(NCU) hipLaunchKernelGGL(fc_bwd_kernel<NCU>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->dHh, m->X1, m->WxT, m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask)
-                if (L.H == 160) TSC_FCB(10); else TSC_FCB(8);
+                if (L.H == 224) TSC_FCB(14); else if (L.H == 160) TSC_FCB(10); else if (L.H == 192) TSC_FCB(12); else TSC_FCB(8);
 #undef TSC_FCB
             }
             {

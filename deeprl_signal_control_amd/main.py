@@ -99,14 +99,28 @@ class GreedyPolicy:
         pass
 
 
+A2C_POLICIES = ('lstm', 'fc')
+
+
+def a2c_policy(model_config):
+    """[MODEL_CONFIG] policy = lstm | fc: the actor-critic net of IA2C / MA2C.  The key is the one the reference's
+    config/config_greedy_large.ini:13 carries (and nothing there reads); absent means lstm, the policy the reference's
+    agents/models.py builds.  fc is the feed-forward FcACPolicy (agents/policies.py:214-256), for MA2C its fingerprint
+    variant FPFcACPolicy (agents/policies.py:259-282)."""
+    policy = model_config.get('policy', 'lstm').strip()
+    if policy not in A2C_POLICIES:
+        raise ValueError('[MODEL_CONFIG] policy = %r: allowed values are %s' % (policy, ' | '.join(A2C_POLICIES)))
+    return policy
+
+
 def init_model(env, config, total_step, n_env, seed, device=0):
-    """main.py:102-118: the learner for env.agent."""
+    """main.py:102-118: the learner for env.agent (IA2C / MA2C with the [MODEL_CONFIG] policy, a2c_policy)."""
     from .agents import VecA2C
     from .iql import VecIQL
     a_max = int(env.scn.green_tab.shape[1])
     if env.agent in ('ia2c', 'ma2c'):
         return VecA2C(env.n_s_ls, env.n_a_ls, env.n_w_ls, env.n_f_ls, n_env, env.scn.s_max, a_max, config['MODEL_CONFIG'],
-                      total_step, device=device, seed=seed, name=env.agent)
+                      total_step, device=device, seed=seed, name=env.agent, policy=a2c_policy(config['MODEL_CONFIG']))
     if env.agent in ('iqld', 'iqll'):
         return VecIQL(env.n_s_ls, env.n_a_ls, env.n_w_ls, n_env, env.scn.s_max, a_max, config['MODEL_CONFIG'], total_step,
                       device=device, seed=0, model_type='dqn' if env.agent == 'iqld' else 'lr')

@@ -98,7 +98,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -244,6 +244,11 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
 int tsc_model_destroy(tsc_model *m);
 int tsc_model_set_stream(tsc_model *m, void *hip_stream);
 int tsc_model_layout(tsc_model *m, int64_t out[12]);
+/* Which kernels the FC policy (policy_kind 1) runs, fixed at create time: out[0] = rollout forward, 2 for
+ * policy_fwd_fc_mfma_kernel (H = 128 / 160 / 192 / 224, s_max <= 64; not with TSC_FC_MFMA=0 in the environment), 1 for the
+ * per-thread policy_fwd_fc_kernel, 0 for the dense GEMMs + head kernel; out[1] = update, 1 for the fused fc_bwd_kernel (same
+ * widths; not with TSC_UNFUSED_DX=1), 0 for the grouped split-K GEMMs.  Both -1 for the LSTM policy. */
+int tsc_model_path(tsc_model *m, int32_t out[2]);
 int tsc_model_set_params(tsc_model *m, const float *params_host);     /* optimizer state untouched */
 int tsc_model_reset_opt_state(tsc_model *m);                         /* RMSProp ms <- 1 (TF1 slot init) */
 int tsc_model_get_params(tsc_model *m, float *params_host);
