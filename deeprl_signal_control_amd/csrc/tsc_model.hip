@@ -26,6 +26,10 @@
 //                     registers, chained into dW1 | db1) -> grad_norm -> rmsprop; the FcACPolicy update: head_bwd2 ->
 //                     fc_bwd_kernel (dWfc | dbfc | dW1 | db1 in one pass over the X1 / Hh rows its rollout forward cached;
 //                     the grouped split-K GEMMs of tsc_gemm.h behind TSC_UNFUSED_DX and for other shapes)
+// Which of these a handle runs is decided once, in tsc_model_create: its Plan (forward kernel, the three one-pass update
+// kernels, split counts) follows from the shapes, the LDS and workspace fits and the knobs of INTEGRATION.md section 5, which
+// are read there and nowhere else.  The forward and the update only switch on the plan; tsc_model_path reports it.  The fused
+// kernels exist for the hidden widths of with_fused_width, and each launch derives its template argument from H.
 #include "tsc_common.h"
 #include "tsc_gemm.h"
 #include "../../include/tsc.h"
@@ -429,12 +433,6 @@ __global__ void __launch_bounds__(64) head_fwd_kernel(const float *__restrict__ 
     for (int k = 0; k < lay.AMAX; ++k) pi_out[idx * lay.AMAX + k] = k < kOut ? pi[k] : 0.f;
     v_out[idx] = v;
 }
-
-// Loss (agents/policies.py:41-52) and its gradient w.r.t. logits / v, then back through the head:
-//   L = -mean(log_pi[a] Adv) + 0.5 v_coef mean((R - v)^2) - beta mean(entropy), mean over the
-//   T*E samples of one agent.  Writes dL [G][N][8] (pi tower: dlogits, v tower: dv in col 0)
-//   and dH [G][N][64].
-
 
 // ------------------------------------------------------------------------------------------------
 // head_bwd, second form: loss gradient + dH + dWo / dbo of BOTH towers of an agent in one persistent pass.
@@ -2379,36 +2377,64 @@ __global__ void fc_bwd_reduce_kernel(const float *__restrict__ ws, int G, int S,
     }
 }
 
+namespace {
+
+constexpr size_t kLdsMax = 160 * 1024;      // LDS of one workgroup on gfx950
+
+// The hidden widths H = n_fc_wave + n_fc_fp + n_fc_wait the fused kernels are instantiated for.  with_fused_width calls
+// f(std::integral_constant<int, H>{}) for one of them and returns false for any other H; every launch site derives its
+// template argument from H.  bench.py:fused_update_kernels mirrors this list: change both together.
+template <int... W, class F> bool with_width(int H, F &&f) { return ((H == W && (f(std::integral_constant<int, W>{}), true)) || ...); }
+template <class F> bool with_fused_width(int H, F &&f) { return with_width<128, 160, 192, 224>(H, f); }
+
+// Which kernels a handle runs: decided once in tsc_model_create from its shapes and the knobs.
+enum class Fwd : int8_t {
+    Dense,      // grouped GEMMs + lstm_fwd (LSTM) + head_fwd: the shapes no fused forward covers
+    Tile,       // LSTM: policy_fwd_fused_kernel, one 64-instance tile per workgroup
+    Ws,         // LSTM: policy_fwd_ws_kernel<(H + kL) / 2>, [Wx ; Wh] stationary in registers
+    FcThread,   // FcACPolicy: policy_fwd_fc_kernel
+    FcMfma      // FcACPolicy: policy_fwd_fc_mfma_kernel<H / 32>
+};
+// the rollout forwards that also fill the activation cache the update reads
+inline bool fills_cache(Fwd f) { return f == Fwd::Tile || f == Fwd::Ws || f == Fwd::FcMfma; }
+
+struct Plan {
+    Fwd fwd;
+    bool dwxh;      // LSTM: dWx | dWh | dbl in one pass (dwxh_kernel<(H + kL) / 32>), else two grouped GEMMs
+    bool dx1w1;     // LSTM: dX1 in registers, dW1 | db1 in the same pass (dx1w1_kernel2<H / 16>), else two grouped GEMMs
+    bool fc_bwd;    // FcACPolicy: dWfc | dbfc | dW1 | db1 in one pass, dX1 in registers (fc_bwd_kernel<H / 16>)
+    int s_fwd;      // Ws: workgroups per tower
+    int s_upd;      // dwxh / dx1w1 / fc_bwd: row splits per tower (~ one workgroup per CU)
+};
+
+}  // namespace
+
 struct tsc_model {
     Layout lay;
+    Plan plan;
     int E, T, device;
     double gamma, rnorm, rclip, vcoef, max_norm, alpha, eps;
     hipStream_t stream;
     std::vector<void *> allocs;
     int *n_act;
     int16_t *rowrange;          // [A][SMAX][2]
-    int *wgmap; int wgmap_S, wgmap_n, xcd_map_on;   // ws forward: blockIdx -> (tower << 8 | split), XCD-affine (TSC_FWD_XCD=0: off)
+    int *wgmap; unsigned fwd_wgs;   // Ws forward: blockIdx -> (tower << 8 | split), XCD-affine (null: TSC_FWD_XCD=0); workgroups
     int dbg_tid;                // thread of workgroup 0 that writes the clock stamps (TSC_DBG_THREAD)
     int *ftmask;                // [A][H / 16]: 16-feature tiles of dW1 with a structural non-zero in column unit U (dx1w1_kernel2)
     int *krange;                // [A][8][2]: first-layer MFMA steps (2 obs rows each) that feed hidden column tile w (ws forward)
     float *params, *grads, *ms, *WxT;
-    float *Wg;                  // gate-interleaved copy of [Wx ; Wh] for the fused forward (interleave_gates_kernel)
+    float *Wg;                  // [Wx ; Wh] re-laid out for the Tile (gate-interleaved) or Ws (register order) forward
     int wg_dirty;
-    float *state_fw, *state_bw, *state_tmp;     // [G][E][128]
+    float *state_fw, *state_bw;     // [G][E][128]
     // rollout (on-policy buffer)
     float *r_obs; int *r_act; double *r_rew; float *r_val; uint8_t *r_done;   // done [T+1][E]
     float *Rs, *Advs;
     // activations
-    float *X1, *Z, *Hh, *Cc, *Hp, *dHh, *dL;
+    float *X1, *Z, *Hh, *Cc, *Hp, *dHh;
     double *norm2, *stats, *norm_part;
     float *ws, *wsc;            // split-K workspace
     size_t ws_floats, wsc_floats;
     size_t lds_fwd, lds_fused, lds_ws;
-    int fused_fwd;
-    int fused_dw;               // dWx | dWh | dbl in one pass (dwxh_kernel)
-    int fc_mfma;                // FcACPolicy rollout forward on the matrix cores (TSC_FC_MFMA=0: the per-thread kernel)
-    int fused_dx;               // dX1 in registers, dW1 | db1 in the same pass (dx1w1_kernel2)
-    int fused_fc;               // FcACPolicy: dWfc | dbfc | dW1 | db1 in one pass, dX1 in registers (fc_bwd_kernel)
     int inplace;                // the running rollout is written straight into the buffer's slots (tsc_model_rollout_slot): slot T -> 0 carry
     int cached_next;            // next rollout slot whose activations the fused forward will cache; T = all cached
     long long *dbg;
@@ -2444,6 +2470,9 @@ int dense_forward(tsc_model *m, const float *obs, long long rows, float *X1, flo
         return 1;
     return 0;
 }
+
+// dynamic LDS of the per-thread FcACPolicy forward (policy_fwd_fc_kernel), bytes
+size_t fc_thread_lds(int H) { return sizeof(float) * ((size_t)64 * kFcLdo + (size_t)2 * 64 * (H + 1) + (size_t)2 * 64 * kFcLdo); }
 
 }  // namespace
 
@@ -2524,7 +2553,6 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
     MALLOC(m->Wg, float, G * (L.H + kL) * kG4);
     m->wg_dirty = 1;
     MALLOC(m->state_fw, float, G * E * 2 * kL); MALLOC(m->state_bw, float, G * E * 2 * kL);
-    MALLOC(m->state_tmp, float, G * E * 2 * kL);
     MALLOC(m->r_obs, float, (N + E) * A * L.SMAX);          // T + 1 slots: slot t + 1 receives the obs the env returns at step t
     MALLOC(m->r_act, int, N * A); MALLOC(m->r_rew, double, N * A);
     MALLOC(m->r_val, float, N * A); MALLOC(m->r_done, uint8_t, (T + 1) * E);
@@ -2532,56 +2560,78 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
     MALLOC(m->X1, float, G * N * L.H + 32 * L.H);        // + one tile nobody reads: the ws forward's branch-free X1 store when the cache is off
     MALLOC(m->Z, float, G * N * kG4);
     MALLOC(m->Hh, float, G * N * kL); MALLOC(m->Cc, float, G * N * kL); MALLOC(m->Hp, float, G * N * kL);
-    MALLOC(m->dHh, float, G * N * kL); MALLOC(m->dL, float, G * N * kOut);
+    MALLOC(m->dHh, float, G * N * kL);
     MALLOC(m->norm2, double, A); MALLOC(m->stats, double, A * 4); MALLOC(m->norm_part, double, A * kNormParts);
     m->ws_floats = (size_t)48 << 20; m->wsc_floats = (size_t)1 << 20;      // 192 MiB + 4 MiB
     MALLOC(m->ws, float, m->ws_floats); MALLOC(m->wsc, float, m->wsc_floats);
     m->lds_fwd = sizeof(float) * (64 * kWhLd + 64 * kHsLd);
-    TSC_HIP(hipFuncSetAttribute((const void *)lstm_bwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * 32 * (kDz2Ld + kDh3Ld))));
-    TSC_HIP(hipFuncSetAttribute((const void *)lstm_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_fwd));
-    TSC_HIP(hipFuncSetAttribute((const void *)lstm_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_fwd));
+    m->lds_fused = sizeof(float) * ((size_t)(L.H + 64) * kXLd + kL * kOut + kOut + 8);   // activations + head weights
+    m->lds_ws = sizeof(float) * ((size_t)32 * (L.H + 64 + 4) + 64 * kWsLdx + (size_t)kL * kWsLdg + (size_t)kG4 * kWsLdg + 528 + (kWsBuf + 2) * 32 * kOut + (size_t)L.SMAX * L.H);
     m->dbg = nullptr;
     m->cached_next = 0;
     m->inplace = 0;
-    m->lds_fused = sizeof(float) * ((size_t)(L.H + 64) * kXLd + kL * kOut + kOut + 8);   // activations + head weights
-    m->fused_fwd = !L.fc && (L.H % 32 == 0) && (L.SMAX <= 64) && (L.SMAX % 4 == 0) && ((L.H + 64) % 8 == 0) && m->lds_fused <= 160 * 1024;
-    if (const char *ev = getenv("TSC_DBG_THREAD")) m->dbg_tid = atoi(ev);
-    m->fc_mfma = 1;
-    if (const char *ev = getenv("TSC_FC_MFMA")) m->fc_mfma = atoi(ev);
-    m->xcd_map_on = 1;
-    if (const char *ev = getenv("TSC_FWD_XCD")) m->xcd_map_on = atoi(ev);
-    m->fused_dw = !L.fc && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128);
-    if (const char *ev = getenv("TSC_UNFUSED_DW")) if (atoi(ev)) m->fused_dw = 0;
-    m->fused_dx = !L.fc && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128) && L.SMAX <= 64 && L.SMAX % 4 == 0;
-    if (const char *ev = getenv("TSC_UNFUSED_DX")) if (atoi(ev)) m->fused_dx = 0;
-    m->fused_fc = L.fc && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128) && L.SMAX <= 64 && L.SMAX % 4 == 0;
-    if (const char *ev = getenv("TSC_UNFUSED_DX")) if (atoi(ev)) m->fused_fc = 0;
-    if (m->fused_fc) {
-        const int lds = (int)(sizeof(float) * (2 * 32 * kFbLdz + 2 * 32 * kObLd + 2 * 32 * (L.H + 16)));
-        TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<14>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        TSC_HIP(hipFuncSetAttribute((const void *)fc_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+
+    // The plan: the only place that reads the knobs and checks what fits (s_max % 4 == 0 and a_max <= kOut hold from above).
+    const auto env_int = [](const char *name, int unset) { const char *ev = getenv(name); return ev ? atoi(ev) : unset; };
+    const char *fwd_ws = getenv("TSC_FWD_WS");
+    const bool unfused_dx = env_int("TSC_UNFUSED_DX", 0) != 0;
+    m->dbg_tid = env_int("TSC_DBG_THREAD", 0);
+    Plan &P = m->plan;
+    P.s_upd = 256 / (int)G;                                 // ~ one workgroup per CU
+    if (P.s_upd < 1) P.s_upd = 1;
+    P.s_fwd = P.s_upd < (E + 31) / 32 ? P.s_upd : (int)((E + 31) / 32);
+    const bool wide = with_fused_width(L.H, [](auto) {}), narrow_obs = L.SMAX <= 64;
+    const auto ws_fits = [&](long long per_split) { return (size_t)(P.s_upd * G * per_split) <= m->ws_floats; };
+    if (!L.fc) {
+        const bool tile = L.H % 32 == 0 && narrow_obs && m->lds_fused <= kLdsMax;
+        P.fwd = !tile ? Fwd::Dense : wide && m->lds_ws <= kLdsMax && !(fwd_ws && fwd_ws[0] == '0') ? Fwd::Ws : Fwd::Tile;
+        P.dwxh = wide && !env_int("TSC_UNFUSED_DW", 0) && ws_fits((long long)(L.H + kL + 1) * kG4);
+        P.dx1w1 = wide && narrow_obs && !unfused_dx && ws_fits((long long)2 * 65 * L.H);
+    } else {
+        // policy_fwd_fc_mfma_kernel fits every fused width (114 KiB of LDS at H = 224); the per-thread kernel does not fit at
+        // H = 224 (161 KiB), so MA2C-FC on large_grid with TSC_FC_MFMA=0 takes the dense GEMMs + head_fwd_kernel
+        P.fwd = wide && narrow_obs && env_int("TSC_FC_MFMA", 1) ? Fwd::FcMfma
+              : L.H % 16 == 0 && narrow_obs && fc_thread_lds(L.H) <= kLdsMax ? Fwd::FcThread : Fwd::Dense;
+        P.fc_bwd = wide && narrow_obs && !unfused_dx && ws_fits((long long)2 * 65 * L.H + (long long)(L.H + 1) * kL);
     }
-    if (m->fused_dx) {
-        const int lds = (int)(sizeof(float) * (2 * 32 * kD1Ld + 2 * 32 * kObLd));
-        TSC_HIP(hipFuncSetAttribute((const void *)dx1w1_kernel2<14>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        TSC_HIP(hipFuncSetAttribute((const void *)dx1w1_kernel2<10>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        TSC_HIP(hipFuncSetAttribute((const void *)dx1w1_kernel2<12>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        TSC_HIP(hipFuncSetAttribute((const void *)dx1w1_kernel2<8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    m->fwd_wgs = (unsigned)(G * P.s_fwd);
+    if (P.fwd == Fwd::Ws && env_int("TSC_FWD_XCD", 1) && P.s_fwd > 1 && P.s_fwd < 256) {
+        // XCD-affine numbering: towers are placed whole on the XCD with the most free slots (cap = ceil(G S / 8) per XCD), the
+        // last ones are split over what is left; ids without work exit at once
+        const int S = P.s_fwd, cap = (L.G * S + 7) / 8;
+        std::vector<int> tab((size_t)8 * cap, -1), used(8, 0);
+        for (int gg = 0; gg < L.G; ++gg) {
+            int left = S, spn = 0;
+            while (left > 0) {
+                int x = 0;
+                for (int k = 1; k < 8; ++k) if (cap - used[k] > cap - used[x]) x = k;
+                const int take = left < cap - used[x] ? left : cap - used[x];
+                for (int q = 0; q < take; ++q) tab[(size_t)(used[x] + q) * 8 + x] = (gg << 8) | (spn + q);
+                used[x] += take; spn += take; left -= take;
+            }
+        }
+        TSC_HIP(tsc::upload<int>(&m->wgmap, tab.data(), tab.size())); m->allocs.push_back(m->wgmap);
+        m->fwd_wgs = (unsigned)tab.size();
     }
-    m->lds_ws = sizeof(float) * ((size_t)32 * (L.H + 64 + 4) + 64 * kWsLdx + (size_t)kL * kWsLdg + (size_t)kG4 * kWsLdg + 528 + (kWsBuf + 2) * 32 * kOut + (size_t)L.SMAX * L.H);
-    if (m->fused_fwd && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128) && m->lds_ws <= 160 * 1024) {
-        // weight-stationary variant (TSC_FWD_WS=0 falls back to the tile-per-workgroup kernel)
-        const char *ev = getenv("TSC_FWD_WS");
-        if (!(ev && ev[0] == '0')) m->fused_fwd = 2;
-        TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_ws_kernel<144>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_ws));
-        TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_ws_kernel<112>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_ws));
-        TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_ws_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_ws));
-        TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_ws_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_ws));
-    }
-    if (m->fused_fwd)
-        TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_fused));
+    // Every kernel this handle launches with dynamic LDS may use the 160 KiB the plan checked each launch against: the same
+    // value for every handle, so one handle's create never lowers what another one's launches need.
+    hipError_t attr = hipSuccess;
+    const auto allow_lds = [&attr](const void *k) {
+        if (attr == hipSuccess) attr = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
+    };
+    allow_lds((const void *)lstm_bwd2_kernel);
+    allow_lds((const void *)lstm_fwd_kernel<true>);
+    allow_lds((const void *)lstm_fwd_kernel<false>);
+    if (P.fwd == Fwd::Tile) allow_lds((const void *)policy_fwd_fused_kernel);
+    if (P.fwd == Fwd::FcThread) allow_lds((const void *)policy_fwd_fc_kernel);
+    with_fused_width(L.H, [&](auto w) {
+        constexpr int H = decltype(w)::value;
+        if (P.fwd == Fwd::Ws) allow_lds((const void *)policy_fwd_ws_kernel<(H + kL) / 2>);
+        if (P.fwd == Fwd::FcMfma) allow_lds((const void *)policy_fwd_fc_mfma_kernel<H / 32>);
+        if (P.dx1w1) allow_lds((const void *)dx1w1_kernel2<H / 16>);
+        if (P.fc_bwd) allow_lds((const void *)fc_bwd_kernel<H / 16>);
+    });
+    TSC_HIP(attr);
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((m->nparam + 255) / 256)), dim3(256), 0, 0, m->ms, m->nparam, 1.0f);
     TSC_HIP(hipDeviceSynchronize());
     *out = guard.release();
@@ -2592,7 +2642,6 @@ int tsc_model_destroy(tsc_model *m) {
     if (!m) return 0;
     (void)hipSetDevice(m->device);
     for (void *p : m->allocs) (void)hipFree(p);
-    if (m->wgmap) (void)hipFree(m->wgmap);
     delete m;
     return 0;
 }
@@ -2653,36 +2702,12 @@ int tsc_model_reset(tsc_model *m) {
     return 0;
 }
 
-// FcACPolicy rollout forward on the matrix cores: the widths policy_fwd_fc_mfma_kernel is instantiated for (H = 32 NCT,
-// NCT = 4..7; LDS 64 x 33 + 2 x 32 x (H + 1) + 8 x 32 x 33 + 2 x 32 x kFcLdo floats = 114 KiB at H = 224, under 160 KiB)
-static bool fc_mfma_path(const tsc_model *m) {
-    const Layout &L = m->lay;
-    return L.fc && (L.H == 224 || L.H == 160 || L.H == 192 || L.H == 128) && L.SMAX <= 64 && L.AMAX <= kOut && m->fc_mfma;
-}
-
-// the per-thread FcACPolicy forward (policy_fwd_fc_kernel) and its LDS: 161 KiB at H = 224 does not fit, so MA2C-FC on
-// large_grid with TSC_FC_MFMA=0 takes the dense GEMMs + head_fwd_kernel instead (H = 192, Monaco: 145 KiB, fits)
-static size_t fc_thread_lds(int H) { return sizeof(float) * ((size_t)64 * kFcLdo + (size_t)2 * 64 * (H + 1) + (size_t)2 * 64 * kFcLdo); }
-static bool fc_thread_path(const tsc_model *m) {
-    const Layout &L = m->lay;
-    return L.fc && L.H % 16 == 0 && L.SMAX <= 64 && L.AMAX <= kOut && fc_thread_lds(L.H) <= 160 * 1024;
-}
-
-// split-K factor of the FcACPolicy update (~ one workgroup per CU) and whether it runs as fc_bwd_kernel: the fused widths,
-// a workspace of (2 x 65 H + (H + 1) x 64) floats per split x tower that fits, and b1 / bfc where the reduce expects them
-static int fc_bwd_splits(const tsc_model *m) { const int S = 256 / m->lay.G; return S < 1 ? 1 : S; }
-static bool fc_fused_bwd_path(const tsc_model *m) {
-    const Layout &L = m->lay;
-    const long long perfc = (long long)2 * 65 * L.H + (long long)(L.H + 1) * kL;
-    return m->fused_fc && (size_t)((long long)fc_bwd_splits(m) * L.G * perfc) <= m->ws_floats &&
-           L.ob1 == L.oW1 + (long long)L.SMAX * L.H && L.obl == L.oWx + (long long)L.H * kL;
-}
-
 int tsc_model_path(tsc_model *m, int32_t out[2]) {
     if (!m || !out) return tsc::fail("tsc_model_path: bad arguments");
     const bool fc = m->lay.fc != 0;
-    out[0] = !fc ? -1 : fc_mfma_path(m) ? 2 : fc_thread_path(m) ? 1 : 0;
-    out[1] = !fc ? -1 : fc_fused_bwd_path(m) ? 1 : 0;
+    const Fwd f = m->plan.fwd;
+    out[0] = !fc ? -1 : f == Fwd::FcMfma ? 2 : f == Fwd::FcThread ? 1 : 0;
+    out[1] = !fc ? -1 : m->plan.fc_bwd ? 1 : 0;
     return 0;
 }
 
@@ -2690,66 +2715,41 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
                          int32_t *action, uint64_t seed, uint64_t step, int32_t tslot) {
     if (!m || !obs || !done || !pi || !v) return tsc::fail("tsc_model_forward: bad arguments");
     const Layout &L = m->lay;
+    const Plan &P = m->plan;
     const int E = m->E;
     // activation cache: valid only if slots 0..T-1 are filled in order by advancing forwards
     if (advance) {
         if (tslot == 0) m->cached_next = 0;         // slot 0 opens a rollout: whatever invalidated the cache before is history
-        const bool fc_cache = fc_mfma_path(m);                                                                       // policy_fwd_fc_mfma_kernel
-        if ((m->fused_fwd || fc_cache) && tslot >= 0 && tslot == m->cached_next && tslot < m->T) m->cached_next = tslot + 1;
+        if (fills_cache(P.fwd) && tslot >= 0 && tslot == m->cached_next && tslot < m->T) m->cached_next = tslot + 1;
         else { m->cached_next = -1; tslot = -1; }
     } else {
         tslot = -1;
     }
-    if (m->fused_fwd) {
-        const int n_tiles = (E + 63) / 64, per_xcd = (L.G + 7) / 8;
-        if (m->wg_dirty) {                                  // parameters changed since the re-laid-out copy was made
-            const long long tot = (long long)L.G * (L.H + kL) * kG4;
-            if (m->fused_fwd == 1)
-                hipLaunchKernelGGL(interleave_gates_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, m->stream, m->params, L, m->Wg);
-            else
-                hipLaunchKernelGGL(register_order_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, m->stream, m->params, L, m->Wg);
-            m->wg_dirty = 0;
-        }
+    if ((P.fwd == Fwd::Tile || P.fwd == Fwd::Ws) && m->wg_dirty) {     // parameters changed since the re-laid-out copy was made
+        const long long tot = (long long)L.G * (L.H + kL) * kG4;
+        if (P.fwd == Fwd::Tile)
+            hipLaunchKernelGGL(interleave_gates_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, m->stream, m->params, L, m->Wg);
+        else
+            hipLaunchKernelGGL(register_order_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, m->stream, m->params, L, m->Wg);
+        m->wg_dirty = 0;
+    }
+    switch (P.fwd) {
+    case Fwd::Ws: {
         tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
-        if (m->fused_fwd == 2) {
-            int S = 256 / L.G;
-            if (S < 1) S = 1;
-            if (S > (E + 31) / 32) S = (E + 31) / 32;
-            // XCD-affine numbering: towers are placed whole on the XCD with the most free slots (cap = ceil(G S / 8) per XCD), the
-            // last ones are split over what is left; built once per (S), ids without work exit at once
-            const int *wgm = nullptr;
-            unsigned nwg = (unsigned)(L.G * S);
-            if (m->xcd_map_on && S > 1 && S < 256) {
-                if (m->wgmap_S != S) {
-                    const int cap = (L.G * S + 7) / 8;
-                    std::vector<int> tab((size_t)8 * cap, -1), used(8, 0);
-                    for (int gg = 0; gg < L.G; ++gg) {
-                        int left = S, spn = 0;
-                        while (left > 0) {
-                            int x = 0;
-                            for (int k = 1; k < 8; ++k) if (cap - used[k] > cap - used[x]) x = k;
-                            const int take = left < cap - used[x] ? left : cap - used[x];
-                            for (int q = 0; q < take; ++q) tab[(size_t)(used[x] + q) * 8 + x] = (gg << 8) | (spn + q);
-                            used[x] += take; spn += take; left -= take;
-                        }
-                    }
-                    if (m->wgmap) { (void)hipFree(m->wgmap); m->wgmap = nullptr; }
-                    TSC_HIP(hipMalloc((void **)&m->wgmap, tab.size() * sizeof(int)));
-                    TSC_HIP(hipMemcpyAsync(m->wgmap, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
-                    TSC_HIP(hipStreamSynchronize(m->stream));
-                    m->wgmap_S = S; m->wgmap_n = (int)tab.size();
-                }
-                wgm = m->wgmap; nwg = (unsigned)m->wgmap_n;
-            }
-#define TSC_WS(KS2) hipLaunchKernelGGL(policy_fwd_ws_kernel<KS2>, dim3(nwg), dim3(512), m->lds_ws, m->stream, m->params, \
-                                       L, m->n_act, obs, done, m->state_fw, (int)advance, E, S, pi, v, action, (unsigned long long)seed,     \
-                                       (unsigned long long)step, (int)tslot, (long long)m->T * E, m->X1, m->Z, m->Hh, m->Cc, m->Hp, m->dbg, m->Wg, m->krange, m->dbg_tid, wgm)
-            if (L.H == 224) TSC_WS(144); else if (L.H == 160) TSC_WS(112); else if (L.H == 192) TSC_WS(128); else TSC_WS(96);
-#undef TSC_WS
-            ps.stop();
-            TSC_HIP(hipGetLastError());
-            return 0;
-        }
+        with_fused_width(L.H, [&](auto w) {
+            constexpr int H = decltype(w)::value;
+            hipLaunchKernelGGL(policy_fwd_ws_kernel<(H + kL) / 2>, dim3(m->fwd_wgs), dim3(512), m->lds_ws, m->stream, m->params, L,
+                               m->n_act, obs, done, m->state_fw, (int)advance, E, P.s_fwd, pi, v, action, (unsigned long long)seed,
+                               (unsigned long long)step, (int)tslot, (long long)m->T * E, m->X1, m->Z, m->Hh, m->Cc, m->Hp, m->dbg, m->Wg,
+                               m->krange, m->dbg_tid, m->wgmap);
+        });
+        ps.stop();
+        TSC_HIP(hipGetLastError());
+        return 0;
+    }
+    case Fwd::Tile: {
+        const int n_tiles = (E + 63) / 64, per_xcd = (L.G + 7) / 8;
+        tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
         hipLaunchKernelGGL(policy_fwd_fused_kernel, dim3(8 * per_xcd * n_tiles), dim3(256), m->lds_fused, m->stream, m->params,
                            L, m->n_act, obs, done, m->state_fw, (int)advance, E, n_tiles, pi, v, action,
                            (unsigned long long)seed, (unsigned long long)step, m->dbg, (int)tslot, (long long)m->T * E,
@@ -2758,40 +2758,31 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
         TSC_HIP(hipGetLastError());
         return 0;
     }
-    if (fc_mfma_path(m)) {      // FcACPolicy on the matrix cores (IA2C H = 160 / 128, MA2C H = 224 / 192: large_grid / Monaco)
+    case Fwd::FcMfma: {     // FcACPolicy on the matrix cores (IA2C H = 160 / 128, MA2C H = 224 / 192: large_grid / Monaco)
         const size_t lds = sizeof(float) * ((size_t)64 * kFmLd + (size_t)2 * 32 * (L.H + 1) + (size_t)8 * 32 * kFmLd + (size_t)2 * 32 * kFcLdo);
-        static bool attr_set2 = false;
-        if (!attr_set2) {
-            TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_mfma_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set2 = true;
-        }
         tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
-#define TSC_FCM(NCT) hipLaunchKernelGGL(policy_fwd_fc_mfma_kernel<NCT>, dim3((unsigned)((E + 31) / 32), (unsigned)L.A), dim3(512), lds, m->stream, m->params, L, \
-                                        m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step, (int)tslot, (long long)m->T * E, m->X1, m->Hh)
-        if (L.H == 224) TSC_FCM(7); else if (L.H == 160) TSC_FCM(5); else if (L.H == 192) TSC_FCM(6); else TSC_FCM(4);
-#undef TSC_FCM
+        with_fused_width(L.H, [&](auto w) {
+            constexpr int H = decltype(w)::value;
+            hipLaunchKernelGGL(policy_fwd_fc_mfma_kernel<H / 32>, dim3((unsigned)((E + 31) / 32), (unsigned)L.A), dim3(512), lds, m->stream,
+                               m->params, L, m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step,
+                               (int)tslot, (long long)m->T * E, m->X1, m->Hh);
+        });
         ps.stop();
         TSC_HIP(hipGetLastError());
         return 0;
     }
-    if (fc_thread_path(m)) {     // FcACPolicy: one launch (policy_fwd_fc_kernel)
-        const size_t lds = fc_thread_lds(L.H);
-        static bool attr_set = false;
-        if (!attr_set) {
-            TSC_HIP(hipFuncSetAttribute((const void *)policy_fwd_fc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set = true;
-        }
+    case Fwd::FcThread: {   // FcACPolicy: one launch
         tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
-        hipLaunchKernelGGL(policy_fwd_fc_kernel, dim3((unsigned)((E + 63) / 64), (unsigned)L.A), dim3(512), lds, m->stream, m->params, L,
-                           m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step);
+        hipLaunchKernelGGL(policy_fwd_fc_kernel, dim3((unsigned)((E + 63) / 64), (unsigned)L.A), dim3(512), fc_thread_lds(L.H), m->stream,
+                           m->params, L, m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step);
         ps.stop();
         TSC_HIP(hipGetLastError());
         return 0;
     }
-    // unfused path (shapes the fused kernels do not cover): the training kernels with T = 1
+    case Fwd::Dense:
+        break;
+    }
+    // the training kernels with T = 1
     if (dense_forward(m, obs, E, m->X1, L.fc ? m->Hh : m->Z)) return tsc::fail("tsc_model_forward: gemm launch failed");
     if (L.fc) {                                   // stateless: FcACPolicy.forward (agents/policies.py:237-240)
         tsc::ProfScope psh(tsc::KID_HEAD_FWD, m->stream);
@@ -2890,8 +2881,9 @@ int tsc_model_rollout_slot(tsc_model *m, int32_t t, void *ptrs[6]) {
 int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
     if (!m || !R_boot) return tsc::fail("tsc_model_compute_grads: bad arguments");
     const Layout &L = m->lay;
+    const Plan &P = m->plan;
     const long long E = m->E, T = m->T, N = E * T, A = L.A, G = L.G;
-    const int AS = L.A * L.SMAX;
+    const int AS = L.A * L.SMAX, S = P.s_upd;
     hipStream_t st = m->stream;
     TSC_HIP(hipMemsetAsync(m->stats, 0, sizeof(double) * A * 4, st));
     tsc::ProfScope ps6(tsc::KID_RETURNS, m->stream);
@@ -2908,17 +2900,17 @@ int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
         hipLaunchKernelGGL(transpose_wx_kernel, dim3((unsigned)((G * L.H * L.NZ + 255) / 256)), dim3(256), 0, st, m->params, L, m->WxT);
         ps9.stop();
         TSC_HIP(hipGetLastError());
-        const int S = fc_bwd_splits(m);             // ~ one workgroup per CU
-        if (fc_fused_bwd_path(m)) {
+        if (P.fc_bwd) {
             // both layers' weight gradients in one pass, dX1 never leaves the registers (fc_bwd_kernel)
             long long rps = (N + S - 1) / S;
             rps = (rps + 31) / 32 * 32;                  // whole 32-row chunks
             const size_t lds = sizeof(float) * (2 * 32 * kFbLdz + 2 * 32 * kObLd + 2 * 32 * (L.H + 16));
             {
                 tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
-#define TSC_FCB(NCU) hipLaunchKernelGGL(fc_bwd_kernel<NCU>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->dHh, m->X1, m->WxT, m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask)
-                if (L.H == 224) TSC_FCB(14); else if (L.H == 160) TSC_FCB(10); else if (L.H == 192) TSC_FCB(12); else TSC_FCB(8);
-#undef TSC_FCB
+                with_fused_width(L.H, [&](auto w) {
+                    hipLaunchKernelGGL(fc_bwd_kernel<decltype(w)::value / 16>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->dHh, m->X1,
+                                       m->WxT, m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask);
+                });
             }
             {
                 tsc::ProfScope ps(tsc::KID_DW1_GEMM, m->stream);
@@ -2955,19 +2947,16 @@ int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
     ps9.stop();
     TSC_HIP(hipGetLastError());
     // dWh = Hp^T dZ (+ dbl) ; dWx = X1^T dZ        (dWo = Hh^T dL and dbo came out of head_bwd)
-    const int NT = (L.H + kL) / 32;
-    int S = 256 / (int)G;                       // ~ one workgroup per CU
-    if (S < 1) S = 1;
-    const long long per = (long long)(NT * 32 + 1) * kG4;
-    if (m->fused_dw && (size_t)((long long)S * G * per) <= m->ws_floats && L.oWh == L.oWx + (long long)L.H * kG4 &&
-        L.obl == L.oWh + (long long)kL * kG4) {
+    if (P.dwxh) {
+        const long long per = (long long)(L.H + kL + 1) * kG4;      // a split's [dWx ; dWh ; dbl] partial
         long long rps = (N + S - 1) / S;
         rps += rps & 1;                           // a k-step is two rows
         {
             tsc::ProfScope ps(tsc::KID_DWX_GEMM, m->stream);
-#define TSC_DWXH(NT_) hipLaunchKernelGGL(dwxh_kernel<NT_>, dim3((unsigned)(S * G)), dim3(512), 0, st, m->X1, m->Hp, m->Z, N, (int)G, S, rps, m->ws)
-            if (NT == 9) TSC_DWXH(9); else if (NT == 7) TSC_DWXH(7); else if (NT == 8) TSC_DWXH(8); else TSC_DWXH(6);
-#undef TSC_DWXH
+            with_fused_width(L.H, [&](auto w) {
+                hipLaunchKernelGGL(dwxh_kernel<(decltype(w)::value + kL) / 32>, dim3((unsigned)(S * G)), dim3(512), 0, st, m->X1, m->Hp,
+                                   m->Z, N, (int)G, S, rps, m->ws);
+            });
         }
         {
             tsc::ProfScope ps(tsc::KID_DWH_GEMM, m->stream);
@@ -2981,16 +2970,17 @@ int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
     if (gemm(m, tsc::KID_DWX_GEMM, true, tsc::EPI_NONE, (int)G, L.H, kG4, (int)N, m->X1, N * L.H, L.H, 1, m->Z, N * kG4, kG4, g + L.oWx, L.stride,
              kG4, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0)) return tsc::fail("gemm failed");
     }
-    if (m->fused_dx && L.ob1 == L.oW1 + (long long)L.SMAX * L.H && (size_t)((long long)S * G * 2 * 65 * L.H) <= m->ws_floats) {
+    if (P.dx1w1) {
         // dX1 stays in registers: dW1 | db1 come out of the same pass (dx1w1_kernel2)
         long long rps = (N + S - 1) / S;
         rps = (rps + 31) / 32 * 32;                  // whole 32-row chunks
         const size_t lds = sizeof(float) * (2 * 32 * kD1Ld + 2 * 32 * kObLd);
         {
             tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
-#define TSC_DX2(NCU) hipLaunchKernelGGL(dx1w1_kernel2<NCU>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->Z, m->X1, m->WxT, m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask)
-            if (L.H == 224) TSC_DX2(14); else if (L.H == 160) TSC_DX2(10); else if (L.H == 192) TSC_DX2(12); else TSC_DX2(8);
-#undef TSC_DX2
+            with_fused_width(L.H, [&](auto w) {
+                hipLaunchKernelGGL(dx1w1_kernel2<decltype(w)::value / 16>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->Z, m->X1, m->WxT,
+                                   m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask);
+            });
         }
         {
             tsc::ProfScope ps(tsc::KID_DW1_GEMM, m->stream);
