@@ -79,6 +79,8 @@ struct EnvDev {
     const uint32_t *lane_routes;   // [NL][2] the (<= kMaxEntry) routes whose entry lane this is, one byte each, 0xFF = none
     const uint8_t *emit_tab;       // [NS][emit_len] vehicles each stream's flows emit at second t
     int emit_len;
+    float sigma;                   // Krauss dawdling in force (tsc_env_set_car_following; 0: none).  In the padding behind emit_len: the
+                                   // layout and size of EnvDev, i.e. every kernel's arguments, are those of the IDM-only build
     const int *agent_lanes, *agent_nlane, *agent_nlink, *agent_nphase;
     const uint8_t *green_tab, *yellow_tab;
     const int *nbr, *obs_kind, *obs_src;
@@ -103,6 +105,7 @@ struct EnvDev {
     int trip_cap;                  // trip records per instance
     const float *lane_origin;      // [NL] start of the SUMO lane inside the compiled lane (lane.* getters count from here)
     uint32_t *R0, *R1;             // per vehicle, indexed like X: depart_sec | serial << 16 ; waiting seconds | waiting count << 16
+                                   // (R0 also under Krauss: the serial within the insertion stream travels with the vehicle)
     long long *rec_int;            // [E][8 sec][4]: vehicles, departed, arrived, sum of waiting times
     double *rec_speed;             // [E][8 sec]: sum of speeds (per-lane partial sums added in lane order)
     int *rec_queue;                // [E][8 sec][A * LMAX]: halting vehicles on every incoming lane (whole SUMO lane)
@@ -158,8 +161,23 @@ __device__ __forceinline__ void wave_seg_scan_min(float &v, int &f) {
 #undef TSC_SEG_STEP
 }
 
-// one car-following evaluation against one leader (MICROSIM_SPEC.md rule 3)
+// one car-following evaluation against one leader (MICROSIM_SPEC.md rule 3; KR: the Krauss alternative, v_des = min(v + a,
+// v_safe, v0) with the same safe speed -- tsc_env_set_car_following)
+template <bool KR = false>
 __device__ __forceinline__ float follow(float v, float v0, bool has_lead, float g, float vl, float s0gap) {
+    if constexpr (KR) {
+        float vsafe = INFINITY;
+        if (has_lead) {
+            float gs = g - s0gap;
+            if (gs < 0.0f) gs = 0.0f;
+            vsafe = sqrtf((kDec * kDec + vl * vl) + (2.0f * kDec) * gs) - kDec;
+        }
+        float vn = v + kAcc;
+        if (vn > vsafe) vn = vsafe;
+        if (vn > v0) vn = v0;
+        if (vn < 0.0f) vn = 0.0f;
+        return vn;
+    }
     float ratio = v / v0;
     float r2 = ratio * ratio;
     float acc = kAcc * (1.0f - r2 * r2);
@@ -178,6 +196,15 @@ __device__ __forceinline__ float follow(float v, float v0, bool has_lead, float 
     float vn = v + acc;
     if (vn > vsafe) vn = vsafe;
     if (vn > v0 && v <= v0) vn = v0;
+    if (vn < 0.0f) vn = 0.0f;
+    return vn;
+}
+
+// SUMO's dawdling (Krauss, sigma > 0): v' = v_des - (sigma * min(v_des, a)) * u, u uniform per vehicle (route, serial within its
+// insertion stream) and second t, floored at 0 -- applied to the minimum over the leaders, before the queue clamp
+__device__ __forceinline__ float dawdle(float vn, float sigma, uint32_t seed, uint32_t route, uint32_t serial, uint32_t t) {
+    const float u = u01(hash32(seed ^ 0x9E3779B9u, route, serial, t));
+    vn = vn - (sigma * (vn < kAcc ? vn : kAcc)) * u;
     if (vn < 0.0f) vn = 0.0f;
     return vn;
 }
@@ -201,6 +228,7 @@ __device__ __forceinline__ bool sig_open(int tl, int k, int a, int w, float x, f
 // Table dimensions of the reference's scenarios as compile-time constants (SPEC of step_kernel; matched against the
 // scenario at create time): 1 = large_grid (5x5), 2 = real_net (Monaco, lane chains contracted)
 struct SpecDims { int NLP, NLA, NU, NR, A, KMAX, PMAX, LMAX, NBR, ctrl, yellow, teleport; };
+constexpr int kSpecKrauss = -1;        // SPEC of the Krauss instantiations (runtime dimensions, tsc_env_set_car_following)
 constexpr SpecDims kSpec[3] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
                                {192, 128, 88, 12, 25, 12, 5, 6, 4, 5, 2, 600},     // NU: 81 lanes carry vehicles (83 with lane changing); the rest stay empty
                                {192, 128, 113, 16, 28, 22, 6, 11, 5, 5, 2, 300}};
@@ -229,7 +257,8 @@ struct Smem {
 };
 
 // One layout for the step and the reset kernel.
-template <class Take>
+// KR: the Krauss kernels also hand the vehicles' R0 words over through the outbox (or0), recording or not.
+template <bool KR = false, class Take>
 __host__ __device__ __forceinline__ void smem_layout(Smem &s, const EnvDev &P, Take take) {
     s.r = (double *)take(sizeof(double) * (P.A + 1));
     s.mv = (int *)take(sizeof(int) * P.NU * P.NR);
@@ -254,20 +283,23 @@ __host__ __device__ __forceinline__ void smem_layout(Smem &s, const EnvDev &P, T
         s.rq = (int *)take(4 * P.NLA); s.rsp = (double *)take(8 * P.NLA); s.rint = (long long *)take(8 * 4);
     } else {
         s.or0 = s.or1 = nullptr; s.rq = nullptr; s.rsp = nullptr; s.rint = nullptr;
+        if constexpr (KR) s.or0 = (uint32_t *)take(4 * kMaxCross * P.NLA);
     }
 }
 
+template <bool KR = false>
 __device__ __forceinline__ Smem carve(char *base, const EnvDev &P) {
     Smem s;
     char *p = base;
-    smem_layout(s, P, [&](size_t bytes) { char *q = p; p += (bytes + 15) & ~size_t(15); return q; });
+    smem_layout<KR>(s, P, [&](size_t bytes) { char *q = p; p += (bytes + 15) & ~size_t(15); return q; });
     return s;
 }
 
+template <bool KR = false>
 size_t smem_bytes(const EnvDev &P) {
     Smem s;
     size_t tot = 0;
-    smem_layout(s, P, [&](size_t bytes) { tot += (bytes + 15) & ~size_t(15); return (char *)nullptr; });
+    smem_layout<KR>(s, P, [&](size_t bytes) { tot += (bytes + 15) & ~size_t(15); return (char *)nullptr; });
     return tot;
 }
 
@@ -385,10 +417,15 @@ __global__ void __launch_bounds__(256) greedy_kernel(EnvDev P, const float *__re
 // (tools/bench_env.py, tsc_env_debug_clock).  The cap costs ~120 B of scratch per lane and 8 % in isolation.
 // SPEC 1: the table dimensions of the reference's large_grid are compile-time constants (LDS offsets and index products
 // fold into immediates: the kernel holds > 100 scalar values otherwise and reloads the spilled ones with v_readlane)
+// SPEC = kSpecKrauss (tsc_env_set_car_following): runtime table dimensions and the Krauss car following with SUMO's dawdling
+// instead of rule 3's IDM (KR); the vehicles' R0 words (depart | serial << 16) then travel with them on every path (SER), recording
+// or not.  (A sentinel of SPEC rather than one more template parameter: the IDM kernels keep their symbols and their code.)
 template <int MAXT, bool HELP, bool REC = false, int KF = 4, int SPEC = 0>      // REC: evaluation recording (plain walk only); KF: vehicles per thread and super-round of the flat phase
 __global__ void __launch_bounds__(MAXT, MAXT <= 512 ? 4 : 1)      // (HIP: the second figure is wavefronts per SIMD) 128 VGPRs whatever the workgroup size
 step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, double *__restrict__ reward,
             double *__restrict__ greward, uint8_t *__restrict__ done, int train_mode) {
+    constexpr bool KR = SPEC == kSpecKrauss;
+    constexpr bool SER = REC || KR;         // R0 (depart | serial << 16) is kept per slot
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     if constexpr (SPEC > 0) {
         constexpr SpecDims D = kSpec[SPEC];
@@ -396,7 +433,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         P.PMAX = D.PMAX; P.LMAX = D.LMAX; P.NBR = D.NBR; P.ctrl = D.ctrl; P.yellow = D.yellow; P.teleport = D.teleport;
         P.NS = D.NR;                            // the reference's configurations: every route is its own stream
     }
-    Smem s = carve(smem_raw, P);
+    Smem s = carve<KR>(smem_raw, P);
     const int e = P.order ? P.order[blockIdx.x] : (int)blockIdx.x, l = threadIdx.x, NLP = P.NLP, NLA = P.NLA, NR = P.NR, NS = P.NS;
     const bool lane = l < P.NU;             // lanes >= NU are never entered by any route: always empty
     const bool lthr = l < NLA;              // threads >= NLA only help in phase A1 and in the strided loops
@@ -422,7 +459,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     if (P.dbg && threadIdx.x == 0) P.dbg[64 + 2 * blockIdx.x] = wall_clock64();
     float4 *S = P.S + (size_t)e * kCap * NLP;
     static_assert(!(HELP && REC), "recording uses the plain walk");
-    uint32_t *R0 = REC ? P.R0 + (size_t)e * kCap * NLP : nullptr, *R1 = REC ? P.R1 + (size_t)e * kCap * NLP : nullptr;
+    uint32_t *R0 = SER ? P.R0 + (size_t)e * kCap * NLP : nullptr, *R1 = REC ? P.R1 + (size_t)e * kCap * NLP : nullptr;
     const float origin = REC && lane ? P.lane_origin[l] : 0.0f;
     if (REC && l < 4) s.rint[l] = 0;
 
@@ -549,7 +586,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         int kept = 0, nsent = 0;
         bool has_first = false;                        // HELP: the first stayer is written in phase B (its old slot is
         float fxn = 0.0f, fvn = 0.0f, fsf = 0.0f;      // still read by the flat phase)
-        uint32_t fmeta = 0u;
+        uint32_t fmeta = 0u, fr0 = 0u;
         int i0 = 0;
         // recording: this lane's share of the per-second network statistics (envs/env.py:409-437)
         int rq_halt = 0, rq_wait = 0, rq_arr = 0, rq_dep = 0;
@@ -595,6 +632,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 const unsigned ob = (unsigned)vslot(kept, l, NLP) * 4u;
                 stg(S, 4u * ob, make_float4(xn, vn, sf, __uint_as_float(nmeta)));
                 if constexpr (REC) { stg(R0, ob, r0); stg(R1, ob, r1); tally(xn, vn, nmeta); }
+                else if constexpr (KR) stg(R0, ob, r0);
                 if (kept == 0) { hx = xn; hv = vn; hsf = sf; hm = nmeta; }
                 tx = xn; tv = vn;
                 ++kept;
@@ -612,13 +650,17 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 Raw r; r.x = a4.x; r.v = a4.y; r.sf = a4.z; r.m = __float_as_uint(a4.w);
                 r.r0 = 0u; r.r1 = 0u;
                 if constexpr (REC) { r.r0 = ldg(R0, ob); r.r1 = ldg(R1, ob); }
+                else if constexpr (KR) r.r0 = ldg(R0, ob);
                 return r;
             };
             int i = 0;
             // the head's record is what this thread wrote last (hx / hv / hsf / hm track slot 0): with HELP the walk starts from the
             // registers instead of waiting for a load of it -- one memory round trip less on the second's critical path
             Raw cur;
-            if constexpr (HELP && !REC) { cur.x = hx; cur.v = hv; cur.sf = hsf; cur.m = hm; cur.r0 = 0u; cur.r1 = 0u; }
+            if constexpr (HELP && !REC) {
+                cur.x = hx; cur.v = hv; cur.sf = hsf; cur.m = hm; cur.r0 = 0u; cur.r1 = 0u;
+                if constexpr (KR) cur.r0 = ldg(R0, (unsigned)vslot(0, l, NLP) * 4u);
+            }
             else cur = load_raw(0);
             for (; i < n; ++i) {
                 if (HELP && !all_crossed) break;
@@ -723,9 +765,9 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 const bool has_lead = i > 0 || tgt_lead;
                 const float lg = i > 0 ? (pox - kLen) - x : (Lq - x) + (s.tx[tq] - kLen);
                 const float lvl = i > 0 ? pov : s.tv[tq];
-                float vn = follow(v, v0, has_lead, lg, lvl, kS0);
+                float vn = follow<KR>(v, v0, has_lead, lg, lvl, kS0);
                 if (line_block) {
-                    const float v2 = follow(v, v0, true, L - x, 0.0f, 0.0f);
+                    const float v2 = follow<KR>(v, v0, true, L - x, 0.0f, 0.0f);
                     if (v2 < vn) vn = v2;
                 }
                 // rule 10: the head of a lane that has to move over lines up BEHIND the sibling's queue instead of driving past
@@ -733,9 +775,12 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 if (sb >= 0 && !lc && i == 0 && s.n[sb] > 0) {
                     const float g3 = (s.tx[sb] - kLen) - x;
                     if (g3 >= 0.0f) {
-                        const float v3 = follow(v, v0, true, g3, s.tv[sb], kS0);
+                        const float v3 = follow<KR>(v, v0, true, g3, s.tv[sb], kS0);
                         if (v3 < vn) vn = v3;
                     }
+                }
+                if constexpr (KR) {
+                    if (P.sigma > 0.0f) vn = dawdle(vn, P.sigma, seed, (uint32_t)r, cur.r0 >> 16, (uint32_t)t);
                 }
                 float xn = x + vn;
                 if (!HELP && !all_crossed) {
@@ -776,6 +821,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     const int o = nsent * NLA + l;
                     s.ox[o] = xn; s.ov[o] = vn; s.osf[o] = sf; s.om[o] = nmeta; s.oto[o] = sb;
                     if constexpr (REC) { s.or0[o] = cur.r0; s.or1[o] = r1n; }
+                    else if constexpr (KR) s.or0[o] = cur.r0;
                     ++nsent; ++ncross;
                 } else if (can_cross && xn >= L) {
                     if (!sink) {
@@ -783,6 +829,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         const float ex = xn - L, Lt = s.len[tl];          // rounding of (L + Lt) - L
                         s.ox[o] = ex > Lt ? Lt : ex; s.ov[o] = vn; s.osf[o] = sf; s.om[o] = nmeta; s.oto[o] = tl;
                         if constexpr (REC) { s.or0[o] = cur.r0; s.or1[o] = r1n; }
+                        else if constexpr (KR) s.or0[o] = cur.r0;
                         ++nsent;
                     } else {
                         ++arrived;
@@ -801,7 +848,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     if (all_crossed) K = xn + (float)(5 * i);      // the first vehicle that stays seeds the chain
                     all_crossed = false;
                     if constexpr (HELP) {
-                        has_first = true; i0 = i; fxn = xn; fvn = vn; fsf = sf; fmeta = nmeta;
+                        has_first = true; i0 = i; fxn = xn; fvn = vn; fsf = sf; fmeta = nmeta; fr0 = cur.r0;
                         if (last && xn >= det) { ++d_wave; if (vn < kHalt) ++d_halt; }
                     } else {
                         keep(xn, vn, sf, nmeta, cur.r0, r1n);
@@ -846,7 +893,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 const bool wave_on = base + kF * (int)((unsigned)lf & ~63u) < total;
                 int eq[kF], ei[kF];
                 float x[kF], v[kF], sf[kF], px[kF], pv[kF];
-                uint32_t m[kF];
+                uint32_t m[kF], sr[kF];
                 bool act[kF];
                 float vn[kF], a[kF], key[kF], loc[kF];
                 bool run0[kF];
@@ -854,7 +901,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 int pfs = 1;
 #pragma unroll
                 for (int u = 0; u < kF; ++u) {
-                    eq[u] = 0; ei[u] = 0; x[u] = v[u] = sf[u] = px[u] = pv[u] = 0.0f; m[u] = 0u; act[u] = false;
+                    eq[u] = 0; ei[u] = 0; x[u] = v[u] = sf[u] = px[u] = pv[u] = 0.0f; m[u] = 0u; sr[u] = 0u; act[u] = false;
                     vn[u] = a[u] = 0.0f; key[u] = loc[u] = INFINITY; run0[u] = true;
                 }
                 if (wave_on) {
@@ -893,6 +940,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         const float2 p2 = ldg((const float2 *)S, 4u * pb);
                         x[u] = a4.x; v[u] = a4.y; sf[u] = a4.z; m[u] = __float_as_uint(a4.w);
                         px[u] = p2.x; pv[u] = p2.y;
+                        if constexpr (KR) sr[u] = ldg(R0, ob);
                     }
                     if (round > 0 && lf == 0 && ei[0] > 1) { px[0] = s.hz[0]; pv[0] = s.hz[1]; }   // overwritten by the previous super-round
     #pragma unroll
@@ -902,10 +950,13 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         const int mvp = s.mv[q * NR + (int)(m[u] >> 16)];
                         const float v0 = s.vmax[q] * sf[u];
                         const bool open = sig_open(mv_tl(mvp), mv_k(mvp), s.node[q], (int)(m[u] & 0xFFFFu), x[u], v[u], Lq, link, P.KMAX, P.teleport);
-                        float vv = follow(v[u], v0, true, (px[u] - kLen) - x[u], pv[u], kS0);
+                        float vv = follow<KR>(v[u], v0, true, (px[u] - kLen) - x[u], pv[u], kS0);
                         if (!open) {
-                            const float v2 = follow(v[u], v0, true, Lq - x[u], 0.0f, 0.0f);
+                            const float v2 = follow<KR>(v[u], v0, true, Lq - x[u], 0.0f, 0.0f);
                             if (v2 < vv) vv = v2;
+                        }
+                        if constexpr (KR) {
+                            if (P.sigma > 0.0f) vv = dawdle(vv, P.sigma, seed, m[u] >> 16, sr[u] >> 16, (uint32_t)t);
                         }
                         vn[u] = vv;
                         float aa = x[u] + vv;
@@ -958,6 +1009,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     const int shift = s.nc[q];
                     const unsigned ob = (unsigned)vslot(i - shift, q, NLP) * 4u;
                     stg(S, 4u * ob, make_float4(xn, vv, sf[u], __uint_as_float(nmeta)));
+                    if constexpr (KR) stg(R0, ob, sr[u]);
                     if (i == s.n[q] - 1) { s.tx[q] = xn; s.tv[q] = vv; }
                     if (last && xn >= P.lane_det[q]) { atomicAdd(&s.wave[q], 1); if (vv < kHalt) atomicAdd(&s.halt[q], 1); }
                 }
@@ -980,6 +1032,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 if (has_first) {
                     const unsigned ob0 = (unsigned)vslot(0, l, NLP) * 4u;
                     stg(S, 4u * ob0, make_float4(fxn, fvn, fsf, __uint_as_float(fmeta)));
+                    if constexpr (KR) stg(R0, ob0, fr0);
                     hx = fxn; hv = fvn; hsf = fsf; hm = fmeta;
                     if (kept >= 2) { tx = s.tx[l]; tv = s.tv[l]; } else { tx = fxn; tv = fvn; }
                 }
@@ -1006,6 +1059,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         }
                         S[d] = make_float4(ax, av, s.osf[o], __uint_as_float(am));
                         if constexpr (REC) { R0[d] = s.or0[o]; R1[d] = s.or1[o]; tally(ax, av, am); }
+                        else if constexpr (KR) R0[d] = s.or0[o];
                         if (n == 0) { hx = ax; hv = av; hsf = s.osf[o]; hm = am; }
                         tx = ax; tv = av;
                         ++n;
@@ -1036,7 +1090,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         const float ax = xlo + u0 * (xmax - xlo);
                         const float asf = 1.0f + 0.2f * ((u1 + u2) - 1.0f);
                         int rt = r;                                  // the vehicle's route: the stream itself, ...
-                        if (SPEC == 0 && P.sroute) {                 // (the specialised instantiations have one-to-one streams)
+                        if (SPEC <= 0 && P.sroute) {                 // (the specialised instantiations have one-to-one streams)
                             const int md = P.smode[r];
                             rt = P.sroute[r];                        // ... the stream's fixed route, ...
                             if (md == 2) rt = P.iroute[(size_t)e * NS + r];      // ... this episode's draw of the host, ...
@@ -1056,6 +1110,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         const int d = vslot(n, l, NLP);
                         S[d] = make_float4(ax, 0.0f, asf, __uint_as_float(am));
                         if constexpr (REC) { R0[d] = (uint32_t)t | ((uint32_t)ser << 16); R1[d] = 0u; tally(ax, 0.0f, am); ++rq_dep; }
+                        else if constexpr (KR) R0[d] = (uint32_t)t | ((uint32_t)ser << 16);
                         if (n == 0) { hx = ax; hv = 0.0f; hsf = asf; hm = am; }
                         tx = ax; tv = 0.0f;
                         ++n;
@@ -1236,6 +1291,11 @@ struct tsc_env {
     int *order_buf = nullptr;       // tsc_env_set_block_order
     bool auto_threads;              // the workgroup size follows the number of instances resident on the device (pick_workgroup)
     int kf_default;
+    // car following (tsc_env_set_car_following): the model in force (P.sigma its dawdling) and the one the next reset installs
+    int cf = TSC_CF_IDM, cf_next = TSC_CF_IDM;
+    float sigma_next = 0.0f;
+    size_t smem_kr = 0;             // LDS of the Krauss kernels (the R0 outbox on top)
+    int threads_kr = 256, kf_kr = 1;
 };
 
 // Workgroup size / flat-phase width of the specialised step kernels for `n_resident` env instances on the device (this handle's
@@ -1306,7 +1366,7 @@ const char *tsc_profile_name(int32_t id) {
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 106; }      // 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 107; }      // 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \
@@ -1323,6 +1383,26 @@ int tsc_version(void) { return 106; }      // 1.06: tsc_model_path; 1.05: round 
         h->allocs.push_back(d_);                                                 \
         P.field = d_;                                                            \
     } while (0)
+
+// LDS of the Krauss kernels for the current recording state; their launch geometry (runtime table dimensions: the flat phase at
+// 256 threads unless TSC_ENV_THREADS says otherwise, KF 1 unless TSC_ENV_KF, as with TSC_ENV_SPEC=0)
+static int krauss_attrs(tsc_env *h) {
+    const EnvDev &P = h->P;
+    h->smem_kr = smem_bytes<true>(P);
+    if (h->smem_kr > 160 * 1024) return tsc::fail("tsc_env_set_car_following: LDS need %zu B > 160 KiB", h->smem_kr);
+    h->threads_kr = (P.help && P.NLA < 256) ? 256 : P.NLA;
+    if (const char *ev = getenv("TSC_ENV_THREADS")) {
+        const int tv = atoi(ev);
+        if (tv >= P.NLA && tv <= 1024 && tv % 64 == 0) h->threads_kr = tv;
+    }
+    h->kf_kr = 1;
+    if (const char *ev = getenv("TSC_ENV_KF")) { const int kv = atoi(ev); h->kf_kr = (kv == 2 || kv == 4) ? kv : 1; }
+#define TSC_ATTR_KR(MT, HELP, REC, KF) TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<MT, HELP, REC, KF, kSpecKrauss>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr))
+    TSC_ATTR_KR(256, true, false, 1); TSC_ATTR_KR(256, true, false, 2); TSC_ATTR_KR(256, true, false, 4); TSC_ATTR_KR(1024, true, false, 1);
+    TSC_ATTR_KR(256, false, false, 1); TSC_ATTR_KR(1024, false, false, 1); TSC_ATTR_KR(256, false, true, 1); TSC_ATTR_KR(1024, false, true, 1);
+#undef TSC_ATTR_KR
+    return 0;
+}
 
 int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_env **out) {
     if (!sc || !out || n_env <= 0) return tsc::fail("tsc_env_create: bad arguments");
@@ -1595,9 +1675,10 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     if (!h || trip_cap < 0) return tsc::fail("tsc_env_record: bad arguments");
     EnvDev &P = h->P;
     TSC_HIP(hipStreamSynchronize(h->stream));
-    if (enable && !P.R0) {
+    if (enable && !P.R1) {
         const size_t slots = (size_t)P.E * kCap * P.NLP;
-        ALLOC(R0, uint32_t, slots); ALLOC(R1, uint32_t, slots);
+        if (!P.R0) ALLOC(R0, uint32_t, slots);          // (a Krauss handle has it already: one word per slot for both)
+        ALLOC(R1, uint32_t, slots);
         ALLOC(rec_int, long long, (size_t)P.E * 8 * 4); ALLOC(rec_speed, double, (size_t)P.E * 8);
         ALLOC(rec_queue, int, (size_t)P.E * 8 * P.A * P.LMAX);
         P.trip_cap = trip_cap > 0 ? trip_cap : 8192;
@@ -1615,6 +1696,7 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
+    if ((h->cf == TSC_CF_KRAUSS || h->cf_next == TSC_CF_KRAUSS) && krauss_attrs(h)) return 1;
     return 0;
 }
 
@@ -1684,10 +1766,34 @@ int tsc_env_set_stream(tsc_env *h, void *hip_stream) {
 int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
     if (!h || !seeds_host || !obs_dev) return tsc::fail("tsc_env_reset: bad arguments");
     h->P.fp_bound = nullptr;                     // reset(): fingerprints <- uniform policy (envs/env.py:556-557)
+    h->cf = h->cf_next;                          // tsc_env_set_car_following takes effect here
+    h->P.sigma = h->cf == TSC_CF_KRAUSS ? h->sigma_next : 0.0f;
     TSC_HIP(hipMemcpyAsync(h->d_seeds, seeds_host, sizeof(uint32_t) * h->P.E, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(reset_kernel, dim3(h->P.E), dim3(h->P.NLP), h->smem, h->stream, h->P, h->d_seeds, obs_dev);
     TSC_HIP(hipGetLastError());
     TSC_HIP(hipStreamSynchronize(h->stream));          // seeds_host may be reused by the caller
+    return 0;
+}
+
+int tsc_env_set_car_following(tsc_env *h, int32_t model, double sigma) {
+    if (!h) return tsc::fail("tsc_env_set_car_following: null handle");
+    if (model != TSC_CF_IDM && model != TSC_CF_KRAUSS) return tsc::fail("tsc_env_set_car_following: model %d is neither TSC_CF_IDM (0) nor TSC_CF_KRAUSS (1)", model);
+    if (!(sigma >= 0.0 && sigma <= 1.0)) return tsc::fail("tsc_env_set_car_following: sigma %g outside [0, 1]", sigma);
+    EnvDev &P = h->P;
+    if (model == TSC_CF_KRAUSS && !P.R0) {       // the vehicles' serials (R0), shared with the recording path
+        TSC_HIP(hipStreamSynchronize(h->stream));
+        ALLOC(R0, uint32_t, (size_t)P.E * kCap * P.NLP);
+    }
+    if (model == TSC_CF_KRAUSS && krauss_attrs(h)) return 1;
+    h->cf_next = model;
+    h->sigma_next = (float)sigma;
+    return 0;
+}
+
+int tsc_env_car_following(tsc_env *h, int32_t *model, double *sigma) {
+    if (!h || !model || !sigma) return tsc::fail("tsc_env_car_following: bad arguments");
+    *model = h->cf;
+    *sigma = (double)h->P.sigma;
     return 0;
 }
 
@@ -1785,6 +1891,21 @@ int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *
     if (!h || !action_dev || !obs_dev || !reward_dev || !global_reward_dev || !done_dev)
         return tsc::fail("tsc_env_step: bad arguments");
     tsc::ProfScope ps(tsc::KID_ENV_STEP, h->stream);
+    if (h->cf == TSC_CF_KRAUSS) {
+#define TSC_STEP_KR(MAXT, HELP, REC, KF)                                                                                \
+    hipLaunchKernelGGL((step_kernel<MAXT, HELP, REC, KF, kSpecKrauss>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr, h->stream, h->P, \
+                       action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
+        const bool narrow = h->threads_kr <= 256;
+        if (h->P.rec) { if (narrow) TSC_STEP_KR(256, false, true, 1); else TSC_STEP_KR(1024, false, true, 1); }
+        else if (!h->P.help) { if (narrow) TSC_STEP_KR(256, false, false, 1); else TSC_STEP_KR(1024, false, false, 1); }
+        else if (!narrow) TSC_STEP_KR(1024, true, false, 1);
+        else if (h->kf_kr == 2) TSC_STEP_KR(256, true, false, 2);
+        else if (h->kf_kr == 4) TSC_STEP_KR(256, true, false, 4);
+        else TSC_STEP_KR(256, true, false, 1);
+#undef TSC_STEP_KR
+        TSC_HIP(hipGetLastError());
+        return 0;
+    }
 #define TSC_STEP(MAXT, HELP)                                                                                       \
     hipLaunchKernelGGL((step_kernel<MAXT, HELP>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
                        obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)

@@ -52,6 +52,10 @@ class VecTrafficEnv:
         h = C.c_void_p()
         _lib.check(L.tsc_env_create(C.byref(sc), self.E, self.device.index or 0, C.byref(h)))
         self._h = h
+        model = getattr(scn, 'car_following', 'idm')
+        if model != 'idm':                  # (IDM handles never call it: they run exactly the kernels they always ran)
+            car_following_kw(model, scn.krauss_sigma)
+            _lib.check(L.tsc_env_set_car_following(h, CAR_FOLLOWING_MODELS.index(model), float(scn.krauss_sigma)))
         if resident is not None:        # env instances sharing the device with these (other handles / ranks), these included
             _lib.check(L.tsc_env_set_resident_instances(h, int(resident)))
         with torch.cuda.device(self.device):
@@ -278,6 +282,12 @@ class VecTrafficEnv:
             out['pending'].ctypes.data_as(ip), out['serial'].ctypes.data_as(ip), out['t'].ctypes.data_as(ip)))
         return out
 
+    def car_following(self):
+        """(model, sigma) in force since the last reset(): ('idm', 0.0) or ('krauss', sigma)."""
+        m, sg = C.c_int32(), C.c_double()
+        _lib.check(self._L.tsc_env_car_following(self._h, C.byref(m), C.byref(sg)))
+        return CAR_FOLLOWING_MODELS[m.value], sg.value
+
     def mean_live_vehicles(self):
         v = C.c_double()
         _lib.check(self._L.tsc_env_live_vehicles(self._h, C.byref(v)))
@@ -286,7 +296,25 @@ class VecTrafficEnv:
 
 ENV_CONFIG_KEYS = dict(control_interval_sec=int, yellow_interval_sec=int, episode_length_sec=int, coop_gamma=float,
                        norm_wave=float, norm_wait=float, clip_wave=float, clip_wait=float, coef_wait=float,
-                       objective=str)
+                       objective=str, car_following=str, krauss_sigma=float)
+CAR_FOLLOWING_MODELS = ('idm', 'krauss')                 # include/tsc.h TSC_CF_IDM / TSC_CF_KRAUSS
+
+
+def car_following_kw(model, sigma=None):
+    """[ENV_CONFIG] car_following / krauss_sigma -> Scenario keywords.  A missing model means idm (MICROSIM_SPEC.md rule 3);
+    krauss_sigma is SUMO's dawdling sigma in [0, 1] (default 0.5) and only means something under krauss."""
+    model = 'idm' if model is None else str(model).strip()
+    if model not in CAR_FOLLOWING_MODELS:
+        raise ValueError('[ENV_CONFIG] car_following = %r: allowed values are %s' % (model, ' | '.join(CAR_FOLLOWING_MODELS)))
+    kw = dict(car_following=model)
+    if sigma is not None:
+        sigma = float(sigma)
+        if model != 'krauss':
+            raise ValueError('[ENV_CONFIG] krauss_sigma = %r needs car_following = krauss (the %s model has no dawdling)' % (sigma, model))
+        if not 0.0 <= sigma <= 1.0:
+            raise ValueError('[ENV_CONFIG] krauss_sigma = %r: must lie in [0, 1]' % sigma)
+        kw['krauss_sigma'] = sigma
+    return kw
 SCENARIO_KEYS = {'large_grid': dict(peak_flow1=int, peak_flow2=int, init_density=float),
                  'real_net': dict(flow_rate=int), 'small_grid': dict(num_extra_car_per_hour=int)}
 
@@ -301,8 +329,9 @@ def scenario_from_config(config):
     kw = {}
     for k, typ in list(ENV_CONFIG_KEYS.items()) + list(SCENARIO_KEYS.get(name, {}).items()):
         v = get(k)
-        if v is not None:
+        if v is not None and k not in ('car_following', 'krauss_sigma'):
             kw[k] = typ(float(v)) if typ is int else typ(v)
+    kw.update(car_following_kw(get('car_following'), get('krauss_sigma')))
     seed = int(get('seed'))
     test_seeds = tuple(int(x) for x in str(get('test_seeds')).split(','))
     return build_scenario(name, agent, **kw), seed, test_seeds

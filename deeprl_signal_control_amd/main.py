@@ -127,6 +127,10 @@ def init_model(env, config, total_step, n_env, seed, device=0):
     raise ValueError('agent %r has no learner (main.py:102-118 knows ia2c, ma2c, iqld, iqll)' % env.agent)
 
 
+def car_following_label(scn):
+    return 'krauss (sigma %g)' % scn.krauss_sigma if scn.car_following == 'krauss' else scn.car_following
+
+
 def train(args):
     """main.py:82-155 + utils.py:255-308 (Trainer.run)."""
     from .env import VecTrafficEnv, scenario_from_config
@@ -139,6 +143,7 @@ def train(args):
     in_test, post_test = init_test_flag(args.test_mode)
     scn, seed, test_seeds = scenario_from_config(config['ENV_CONFIG'])
     env = VecTrafficEnv(scn, args.envs, device=args.device, seed=seed, test_seeds=test_seeds)
+    logging.info('Training: car following %s' % car_following_label(scn))
     logging.info('Training: s dim: %d, a dim %d, s dim ls: %r, a dim ls: %r' % (env.n_s, env.n_a, env.n_s_ls, env.n_a_ls))
     total_step = int(config.getfloat('TRAIN_CONFIG', 'total_step'))
     test_step = int(config.getfloat('TRAIN_CONFIG', 'test_interval'))
@@ -185,6 +190,7 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
     scn, seed, _ = scenario_from_config(config['ENV_CONFIG'])
     E = len(seeds)
     env = VecTrafficEnv(scn, E, device=device, seed=seed, test_seeds=seeds)
+    logging.info('Evaluation: car following %s' % car_following_label(scn))
     logging.info('Evaluation: s dim: %d, a dim %d, s dim ls: %r, a dim ls: %r' % (env.n_s, env.n_a, env.n_s_ls, env.n_a_ls))
     if agent != 'greedy':
         model = init_model(env, config, 0, E, seed, device)

@@ -99,6 +99,8 @@ class Scenario:
     queue_cap: int = -1              # real_net: min(10, halting)   (env.py:332-333)
     reward_scale_realnet: bool = False
     teleport_sec: int = 600          # --time-to-teleport (env.py:281-284)
+    car_following: str = 'idm'       # 'idm' (MICROSIM_SPEC.md rule 3, the default) | 'krauss' (SUMO's default model, with dawdling)
+    krauss_sigma: float = 0.5        # Krauss dawdling sigma in [0, 1] (SUMO's default 0.5; 0 = none); unused under 'idm'
     extra: Dict = field(default_factory=dict)
     link_foes: np.ndarray = None     # u32 [A, KMAX] bit k2 of row (a, k): the path of signal link k2 crosses or joins the path of link k
                                      # inside the junction (junction interiors, MICROSIM_SPEC.md rule 10); None = no junction has foes

@@ -35,6 +35,7 @@ extern "C" {
 
 enum { TSC_AGENT_GREEDY = 0, TSC_AGENT_GLOBAL = 1 /* ia2c, iql */, TSC_AGENT_MA2C = 2 };
 enum { TSC_OBJ_QUEUE = 0, TSC_OBJ_WAIT = 1, TSC_OBJ_HYBRID = 2 };
+enum { TSC_CF_IDM = 0, TSC_CF_KRAUSS = 1 };        /* car-following model (tsc_env_set_car_following) */
 
 /* Dense scenario tables (host pointers, copied at create time).  Produced by
  * deeprl_signal_control_amd/scenario.py; meaning and reference provenance of every
@@ -98,7 +99,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -125,6 +126,15 @@ int tsc_env_set_stream(tsc_env *h, void *hip_stream);
  * load, not the handle's: with fewer instances than workgroup slots an instance is spread over 512 / 1024 threads, with a full
  * device it runs 256.  Default: the handle's own n_env.  (No reference counterpart: one SUMO process per env, main.py:93.) */
 int tsc_env_set_resident_instances(tsc_env *h, int32_t n_resident);
+
+/* Car-following model of the vehicles (MICROSIM_SPEC.md rule 3): TSC_CF_IDM (the default: IDM acceleration clamped by the Krauss
+ * safe speed, no dawdling) or TSC_CF_KRAUSS (SUMO's default model: v = min(v + a, v_safe, v0), then dawdling by sigma in [0, 1],
+ * SUMO's default 0.5; 0 = none).  Takes effect at the next tsc_env_reset; the first Krauss call allocates a serial word per vehicle
+ * slot (4 B x n_env x 28 x lanes rounded up to 64; shared with tsc_env_record).  Krauss handles run the kernels with runtime
+ * table dimensions.  An out-of-range model or sigma is an error (tsc_last_error). */
+int tsc_env_set_car_following(tsc_env *h, int32_t model, double sigma);
+/* The model and sigma in force (those of the last reset; sigma 0 under TSC_CF_IDM). */
+int tsc_env_car_following(tsc_env *h, int32_t *model, double *sigma);
 
 /* reset(), envs/env.py:544-561.  seeds: host [E] (the caller does the reference's
  * `seed += 1` bookkeeping); obs: dev float32 [E, A, SMAX] = float32(state) at t = 0. */
