@@ -57,8 +57,12 @@ __host__ __device__ __forceinline__ int mv_k(int w) { const int k = (w >> 12) & 
 __host__ __device__ __forceinline__ int mv_yield(int w) { const int y = (w >> 18) & 0xFFF; return y == 0xFFF ? -1 : y; }
 __host__ __device__ __forceinline__ bool mv_prio(int w) { return (w >> 30) & 1; }
 
+// Trace fields (tsc_env_trace) sit where three flow / entry tables and the flow count were, which no kernel read: the layout and
+// size of EnvDev, i.e. every kernel's arguments, stay those of the untraced build.
 struct EnvDev {
-    int NL, NLP, NR, A, NF, KMAX, PMAX, LMAX, SMAX, NBR, E;
+    int NL, NLP, NR, A;
+    int trace_cap;                 // rows per traced instance (tsc_env_trace)
+    int KMAX, PMAX, LMAX, SMAX, NBR, E;
     int NS, KC;                    // insertion streams (= NR when every route is its own stream), route choices per stream
     int NU, NLA;                   // lanes that can ever hold a vehicle (prefix after load sorting), rounded up to wavefronts
     int help;                      // phase A1 enabled (step_kernel)
@@ -67,15 +71,15 @@ struct EnvDev {
     const int *lane_sib;           // [NL] sibling lane of a two-lane street or -1; null = no lane changing (rule 10)
     const int *mv;                 // [NL*NR] packed movement word, see mv_* helpers
     const uint8_t *zip;            // [NL*NR] zipper-merge slot: rank | count << 4 (0 = none)
-    const int *route_entry;        // [NS] entry lane of every stream
-    const int *flow_ptr;           // [NS+1] CSR over flows sorted by stream
+    const int *trace_slot;         // [E] trace buffer of an instance, -1 = untraced; null = no trace armed (tsc_env_trace)
+    int *trace_cnt;                // [n_trace][1 + episode]: rows counted so far (dropped ones too: the cursor), then rows per second
     const int *sroute;             // [NS] route of a stream's vehicles (-1: drawn); null = the stream index itself
     const int *smode;              // [NS] 0 fixed, 1 per-vehicle draw from schoice, 2 per-instance route (iroute)
     const int *schoice;            // [NS][KC][2] (route, cumulative weight of 65536)
     const float *sorigin;          // [NS][2] the stretch of the entry lane vehicles are inserted on, or null (whole lane)
     int NI, ilen;                  // choice intervals per stream and their length in seconds
     int *iroute;                   // [E][NS] routes of the mode-2 streams of the running episode
-    const int *flows;              // [NF*4] begin,end,vph,route (sorted by route, stable)
+    uint4 *trace_rows;             // [n_trace][trace_cap] one row per live vehicle and second: {lane | route << 16, R0, x, v}
     const uint32_t *lane_routes;   // [NL][2] the (<= kMaxEntry) routes whose entry lane this is, one byte each, 0xFF = none
     const uint8_t *emit_tab;       // [NS][emit_len] vehicles each stream's flows emit at second t
     int emit_len;
@@ -229,6 +233,7 @@ __device__ __forceinline__ bool sig_open(int tl, int k, int a, int w, float x, f
 // scenario at create time): 1 = large_grid (5x5), 2 = real_net (Monaco, lane chains contracted)
 struct SpecDims { int NLP, NLA, NU, NR, A, KMAX, PMAX, LMAX, NBR, ctrl, yellow, teleport; };
 constexpr int kSpecKrauss = -1;        // SPEC of the Krauss instantiations (runtime dimensions, tsc_env_set_car_following)
+constexpr int kSpecTrace = -2, kSpecKraussTrace = -3;   // the recording walk that also writes per-vehicle rows (tsc_env_trace): IDM / Krauss
 constexpr SpecDims kSpec[3] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
                                {192, 128, 88, 12, 25, 12, 5, 6, 4, 5, 2, 600},     // NU: 81 lanes carry vehicles (83 with lane changing); the rest stay empty
                                {192, 128, 113, 16, 28, 22, 6, 11, 5, 5, 2, 300}};
@@ -420,12 +425,16 @@ __global__ void __launch_bounds__(256) greedy_kernel(EnvDev P, const float *__re
 // SPEC = kSpecKrauss (tsc_env_set_car_following): runtime table dimensions and the Krauss car following with SUMO's dawdling
 // instead of rule 3's IDM (KR); the vehicles' R0 words (depart | serial << 16) then travel with them on every path (SER), recording
 // or not.  (A sentinel of SPEC rather than one more template parameter: the IDM kernels keep their symbols and their code.)
+// SPEC = kSpecTrace / kSpecKraussTrace (tsc_env_trace, recording walk only): after every simulated second a workgroup whose instance
+// is traced writes one row per live vehicle, in (lane, slot) order, behind its running cursor (TR; see the end of the second loop).
 template <int MAXT, bool HELP, bool REC = false, int KF = 4, int SPEC = 0>      // REC: evaluation recording (plain walk only); KF: vehicles per thread and super-round of the flat phase
 __global__ void __launch_bounds__(MAXT, MAXT <= 512 ? 4 : 1)      // (HIP: the second figure is wavefronts per SIMD) 128 VGPRs whatever the workgroup size
 step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, double *__restrict__ reward,
             double *__restrict__ greward, uint8_t *__restrict__ done, int train_mode) {
-    constexpr bool KR = SPEC == kSpecKrauss;
+    constexpr bool KR = SPEC == kSpecKrauss || SPEC == kSpecKraussTrace;
+    constexpr bool TR = SPEC == kSpecTrace || SPEC == kSpecKraussTrace;
     constexpr bool SER = REC || KR;         // R0 (depart | serial << 16) is kept per slot
+    static_assert(!TR || (REC && !HELP), "the trace rides on the recording walk");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     if constexpr (SPEC > 0) {
         constexpr SpecDims D = kSpec[SPEC];
@@ -462,6 +471,11 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     uint32_t *R0 = SER ? P.R0 + (size_t)e * kCap * NLP : nullptr, *R1 = REC ? P.R1 + (size_t)e * kCap * NLP : nullptr;
     const float origin = REC && lane ? P.lane_origin[l] : 0.0f;
     if (REC && l < 4) s.rint[l] = 0;
+    int tslot = -1, tcur = 0;               // TR: this instance's trace buffer (-1: untraced, the same for the whole workgroup), its cursor
+    if constexpr (TR) {
+        tslot = P.trace_slot[e];
+        if (tslot >= 0) tcur = P.trace_cnt[(size_t)tslot * (P.episode + 1)];
+    }
 
     // ---- prologue.  Everything is requested in two levels -- first all loads that depend on nothing, then (under
     // the table copies) the ones that need a first-level value -- and unconditionally (lane index clamped), so
@@ -1147,6 +1161,40 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 const int ln = P.agent_lanes[p2];
                 P.rec_queue[row * (P.A * P.LMAX) + p2] = (ln >= 0 && ln < P.NU) ? s.rq[ln] : 0;
             }
+            if constexpr (TR) {
+                if (tslot >= 0 && t < P.episode) {
+                    // per-vehicle rows of second t (tsc_env_trace).  The lanes' first rows: an exclusive prefix sum of the lane counts
+                    // (wavefront scan, one LDS word per wavefront; s.pre / s.wtot belong to the flat phase, which the recording walk
+                    // does not run), then the rows flat over all threads -- consecutive threads write consecutive 16-byte rows.
+                    if (lthr) {
+                        const int c = lane ? n : 0;
+                        const int inc = wave_scan_add(c);
+                        s.pre[l] = inc - c;
+                        if ((l & 63) == 63) s.wtot[l >> 6] = inc;
+                    }
+                    __syncthreads();
+                    int before = 0, tot = 0;
+                    for (int w = 0; w < NLA / 64; ++w) { const int c = s.wtot[w]; if (w < (l >> 6)) before += c; tot += c; }
+                    if (lthr) s.pre[l] += before;
+                    __syncthreads();
+                    uint4 *rows = P.trace_rows + (size_t)tslot * P.trace_cap;
+                    for (int k = l; k < tot; k += blockDim.x) {
+                        int lo = 0, hi = NLA - 1;            // the lane of row k: the last lane whose first row is <= k
+                        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s.pre[mid] <= k) lo = mid; else hi = mid - 1; }
+                        const unsigned ob = (unsigned)vslot(k - s.pre[lo], lo, NLP) * 4u;
+                        const float4 a = ldg(S, 4u * ob);
+                        const uint32_t r0 = ldg(R0, ob);
+                        if (tcur + k < P.trace_cap)        // rows past the buffer are dropped, but counted (the cursor)
+                            rows[tcur + k] = make_uint4((uint32_t)lo | (__float_as_uint(a.w) & 0xFFFF0000u), r0, __float_as_uint(a.x), __float_as_uint(a.y));
+                    }
+                    tcur += tot;
+                    if (l == 0) {
+                        int *cnt = P.trace_cnt + (size_t)tslot * (P.episode + 1);
+                        cnt[1 + t] = tot;
+                        cnt[0] = tcur;
+                    }
+                }
+            }
             __syncthreads();
             if (l < 4) s.rint[l] = 0;
         }
@@ -1296,6 +1344,7 @@ struct tsc_env {
     float sigma_next = 0.0f;
     size_t smem_kr = 0;             // LDS of the Krauss kernels (the R0 outbox on top)
     int threads_kr = 256, kf_kr = 1;
+    int n_trace = 0;                // traced instances (tsc_env_trace); their buffers are P.trace_*
 };
 
 // Workgroup size / flat-phase width of the specialised step kernels for `n_resident` env instances on the device (this handle's
@@ -1366,7 +1415,7 @@ const char *tsc_profile_name(int32_t id) {
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 107; }      // 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 108; }      // 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \
@@ -1401,6 +1450,8 @@ static int krauss_attrs(tsc_env *h) {
     TSC_ATTR_KR(256, true, false, 1); TSC_ATTR_KR(256, true, false, 2); TSC_ATTR_KR(256, true, false, 4); TSC_ATTR_KR(1024, true, false, 1);
     TSC_ATTR_KR(256, false, false, 1); TSC_ATTR_KR(1024, false, false, 1); TSC_ATTR_KR(256, false, true, 1); TSC_ATTR_KR(1024, false, true, 1);
 #undef TSC_ATTR_KR
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 1, kSpecKraussTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr));
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 1, kSpecKraussTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr));
     return 0;
 }
 
@@ -1415,7 +1466,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     h->stream = nullptr;
     EnvDev &P = h->P;
     P.NL = sc->n_lane; P.NLP = (sc->n_lane + 63) / 64 * 64; P.NR = sc->n_route; P.A = sc->n_agent;
-    P.NF = sc->n_flow; P.KMAX = sc->k_max; P.PMAX = sc->p_max; P.LMAX = sc->l_max; P.SMAX = sc->s_max;
+    P.KMAX = sc->k_max; P.PMAX = sc->p_max; P.LMAX = sc->l_max; P.SMAX = sc->s_max;
     P.NBR = sc->nbr_max; P.E = n_env;
     P.ctrl = sc->control_interval_sec; P.yellow = sc->yellow_interval_sec; P.episode = sc->episode_length_sec;
     P.teleport = sc->teleport_sec; P.queue_cap = sc->queue_cap; P.objective = sc->objective;
@@ -1500,11 +1551,6 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
         if (any_zip && NL > 255)
             return tsc::fail("tsc_env_create: zipper merges need lane indices < 255 (feeders are bytes on the device), the scenario has %d lanes", NL);
     }
-    {
-        std::vector<int> se(NS);
-        for (int s_ = 0; s_ < NS; ++s_) se[s_] = stream_entry(s_);
-        UP(route_entry, int, se.data(), NS);
-    }
     P.sroute = nullptr; P.smode = nullptr; P.schoice = nullptr; P.sorigin = nullptr; P.iroute = nullptr;
     if (streams) {
         std::vector<int> sr(NS);
@@ -1537,16 +1583,6 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
             UP(sorigin, float, so.data(), so.size());
         }
     }
-    // flows sorted by stream (stable) + CSR
-    std::vector<int> fl; std::vector<int> ptr(NS + 1, 0);
-    for (int r = 0; r < NS; ++r) {
-        ptr[r] = (int)fl.size() / 4;
-        for (int f = 0; f < sc->n_flow; ++f)
-            if (sc->flows[f * 4 + 3] == r) fl.insert(fl.end(), sc->flows + f * 4, sc->flows + f * 4 + 4);
-    }
-    ptr[NS] = (int)fl.size() / 4;
-    UP(flows, int, fl.data(), fl.size());
-    UP(flow_ptr, int, ptr.data(), NS + 1);
     {   // per-lane entry routes (<= 2) and per-route emission table (MICROSIM_SPEC.md, rule 6)
         std::vector<int> lr((size_t)NL * kMaxEntry, -1);
         for (int r = 0; r < NS; ++r) {
@@ -1614,6 +1650,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     }
     P.rec = 0; P.trip_cap = 0; P.R0 = P.R1 = nullptr; P.rec_int = nullptr; P.rec_speed = nullptr; P.rec_queue = nullptr;
     P.trips = nullptr;
+    P.trace_cap = 0; P.trace_slot = nullptr; P.trace_cnt = nullptr; P.trace_rows = nullptr;
     P.fp_bound = nullptr;
     P.dbg = nullptr;
     P.order = nullptr;
@@ -1689,6 +1726,8 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     if (h->smem > 160 * 1024) return tsc::fail("tsc_env_record: LDS need %zu B > 160 KiB", h->smem);
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 4, kSpecTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 4, kSpecTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
@@ -1697,6 +1736,59 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     if ((h->cf == TSC_CF_KRAUSS || h->cf_next == TSC_CF_KRAUSS) && krauss_attrs(h)) return 1;
+    return 0;
+}
+
+// Frees a buffer this handle allocated (P.* = nullptr afterwards is the caller's)
+static void free_alloc(tsc_env *h, const void *p) {
+    if (!p) return;
+    for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
+        if (*it == p) { (void)hipFree(*it); h->allocs.erase(it); return; }
+}
+
+int tsc_env_trace(tsc_env *h, int32_t n_trace, const int32_t *instances_host, int32_t row_cap) {
+    if (!h || n_trace < 0) return tsc::fail("tsc_env_trace: bad arguments");
+    EnvDev &P = h->P;
+    if (n_trace > 0) {
+        if (!P.rec) return tsc::fail("tsc_env_trace: recording is off (call tsc_env_record(h, 1, ...) first: the trace rides on the recording walk)");
+        if (!instances_host) return tsc::fail("tsc_env_trace: no instance list");
+        if (n_trace > P.E) return tsc::fail("tsc_env_trace: %d instances traced, the handle has %d", n_trace, P.E);
+        if (row_cap < 1) return tsc::fail("tsc_env_trace: row_cap %d < 1", row_cap);
+    }
+    std::vector<int> slot((size_t)P.E, -1);
+    for (int k = 0; k < n_trace; ++k) {
+        const int e = instances_host[k];
+        if (e < 0 || e >= P.E) return tsc::fail("tsc_env_trace: instance %d of %d", e, P.E);
+        if (slot[e] >= 0) return tsc::fail("tsc_env_trace: instance %d listed twice", e);
+        slot[e] = k;
+    }
+    (void)hipSetDevice(h->device);
+    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running step may still write the old buffers
+    free_alloc(h, P.trace_slot); free_alloc(h, P.trace_cnt); free_alloc(h, P.trace_rows);
+    P.trace_slot = nullptr; P.trace_cnt = nullptr; P.trace_rows = nullptr; P.trace_cap = 0;
+    h->n_trace = 0;
+    if (n_trace == 0) return 0;                                 // detached: the untraced recording kernels run again
+    UP(trace_slot, int, slot.data(), P.E);
+    ALLOC(trace_cnt, int, (size_t)n_trace * (P.episode + 1));
+    ALLOC(trace_rows, uint4, (size_t)n_trace * row_cap);
+    P.trace_cap = row_cap;
+    h->n_trace = n_trace;
+    return 0;
+}
+
+int tsc_env_read_trace(tsc_env *h, int32_t k, int32_t *counts_host, uint32_t *rows_host, int32_t max_rows, int32_t *n_rows) {
+    if (!h || !n_rows || !counts_host || (max_rows > 0 && !rows_host)) return tsc::fail("tsc_env_read_trace: bad arguments");
+    const EnvDev &P = h->P;
+    if (k < 0 || k >= h->n_trace) return tsc::fail("tsc_env_read_trace: trace %d of %d", k, h->n_trace);
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    std::vector<int> cnt((size_t)P.episode + 1);
+    TSC_HIP(hipMemcpy(cnt.data(), P.trace_cnt + (size_t)k * (P.episode + 1), sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+    memcpy(counts_host, cnt.data() + 1, sizeof(int) * (size_t)P.episode);
+    *n_rows = cnt[0];
+    int n = cnt[0];
+    if (n > P.trace_cap) n = P.trace_cap;
+    if (n > max_rows) n = max_rows;
+    if (n > 0) TSC_HIP(hipMemcpy(rows_host, P.trace_rows + (size_t)k * P.trace_cap, sizeof(uint4) * (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1769,6 +1861,8 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
     h->cf = h->cf_next;                          // tsc_env_set_car_following takes effect here
     h->P.sigma = h->cf == TSC_CF_KRAUSS ? h->sigma_next : 0.0f;
     TSC_HIP(hipMemcpyAsync(h->d_seeds, seeds_host, sizeof(uint32_t) * h->P.E, hipMemcpyHostToDevice, h->stream));
+    if (h->P.trace_cnt)                                // tsc_env_trace: cursors and per-second counts start over
+        TSC_HIP(hipMemsetAsync(h->P.trace_cnt, 0, sizeof(int) * (size_t)h->n_trace * (h->P.episode + 1), h->stream));
     hipLaunchKernelGGL(reset_kernel, dim3(h->P.E), dim3(h->P.NLP), h->smem, h->stream, h->P, h->d_seeds, obs_dev);
     TSC_HIP(hipGetLastError());
     TSC_HIP(hipStreamSynchronize(h->stream));          // seeds_host may be reused by the caller
@@ -1896,7 +1990,12 @@ int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *
     hipLaunchKernelGGL((step_kernel<MAXT, HELP, REC, KF, kSpecKrauss>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr, h->stream, h->P, \
                        action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
         const bool narrow = h->threads_kr <= 256;
-        if (h->P.rec) { if (narrow) TSC_STEP_KR(256, false, true, 1); else TSC_STEP_KR(1024, false, true, 1); }
+#define TSC_STEP_KRT(MAXT)                                                                                             \
+    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 1, kSpecKraussTrace>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr, h->stream, h->P, \
+                       action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
+        if (h->P.rec && h->P.trace_slot) { if (narrow) TSC_STEP_KRT(256); else TSC_STEP_KRT(1024); }
+#undef TSC_STEP_KRT
+        else if (h->P.rec) { if (narrow) TSC_STEP_KR(256, false, true, 1); else TSC_STEP_KR(1024, false, true, 1); }
         else if (!h->P.help) { if (narrow) TSC_STEP_KR(256, false, false, 1); else TSC_STEP_KR(1024, false, false, 1); }
         else if (!narrow) TSC_STEP_KR(1024, true, false, 1);
         else if (h->kf_kr == 2) TSC_STEP_KR(256, true, false, 2);
@@ -1912,7 +2011,12 @@ int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *
 #define TSC_STEP_REC(MAXT)                                                                                         \
     hipLaunchKernelGGL((step_kernel<MAXT, false, true>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
                        obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-    if (h->P.rec) { if (h->threads <= 256) TSC_STEP_REC(256); else TSC_STEP_REC(1024); }
+#define TSC_STEP_TRACE(MAXT)                                                                                       \
+    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 4, kSpecTrace>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
+                       obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
+    if (h->P.rec && h->P.trace_slot) { if (h->threads <= 256) TSC_STEP_TRACE(256); else TSC_STEP_TRACE(1024); }
+#undef TSC_STEP_TRACE
+    else if (h->P.rec) { if (h->threads <= 256) TSC_STEP_REC(256); else TSC_STEP_REC(1024); }
 #define TSC_STEP_KF(KF)                                                                                           \
     hipLaunchKernelGGL((step_kernel<256, true, false, KF>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
                        obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)

@@ -18,6 +18,9 @@ import torch
 from . import _lib
 from .scenario import LANE_CAP, Scenario, build_scenario
 
+TRACE_ROW_CAP = 1 << 22           # default trajectory rows per traced instance (64 MiB; large_grid's busiest episodes need ~2 M)
+FCD_COLUMNS = ('episode', 'time_sec', 'id', 'lane', 'pos', 'speed')
+
 
 class VecTrafficEnv:
     """E instances of TrafficSimulator.  Seeds follow the reference's bookkeeping
@@ -111,6 +114,44 @@ class VecTrafficEnv:
             self.teleported_trips = [0] * self.E     # trips of the episode the teleport surrogate truncated (not in trip_data)
             self.truncated_trip_data = [[] for _ in range(self.E)]     # ... their rows (own table, see collect_tripinfo)
 
+    def set_trace(self, instances, row_cap=TRACE_ROW_CAP):
+        """Per-vehicle trajectories of the listed instances (SUMO's --fcd-output without coordinates, tsc_env_trace): from the next
+        reset() on, every simulated second keeps each live vehicle's lane, position and speed.  Needs set_record(True); an empty
+        list detaches the trace.  row_cap: rows kept per instance and episode (16 bytes each; collect_trajectories raises when an
+        episode needed more)."""
+        instances = [int(e) for e in instances]
+        if instances and not getattr(self, 'is_record', False):
+            raise ValueError('set_trace: recording is off -- call set_record(True) before set_trace (the trace rides on the '
+                             'recording path)')
+        if instances and int(row_cap) < 1:
+            raise ValueError('set_trace: row_cap = %r must be >= 1' % row_cap)
+        arr = np.ascontiguousarray(instances, np.int32)
+        _lib.check(self._L.tsc_env_trace(self._h, len(arr), arr.ctypes.data_as(C.POINTER(C.c_int32)), int(row_cap)))
+        self.trace_instances, self.trace_cap = instances, int(row_cap)
+        self.trajectory_data = {e: None for e in instances}
+
+    def collect_trajectories(self):
+        """The traced instances' trajectories of the running episode (set_trace): {instance: dict of columns} with time_sec (the
+        traffic table's convention: the end of simulated second t is t + 1), id (the trip table's f_<route>.<serial>), lane and pos
+        (the SUMO lane and the position on it, Scenario.sumo_lane_pos) and speed, one row per live vehicle and second, in (second,
+        simulator lane, queue position) order; also the simulator's own view of each row: sim_lane, x, route, serial.  Also kept for
+        output_data."""
+        T = int(self.scn.episode_length_sec)
+        counts = np.zeros(T, np.int32)
+        out = {}
+        for k, e in enumerate(getattr(self, 'trace_instances', [])):
+            n = C.c_int32()
+            _lib.check(self._L.tsc_env_read_trace(self._h, k, counts.ctypes.data_as(C.POINTER(C.c_int32)), None, 0, C.byref(n)))
+            if n.value > self.trace_cap:
+                raise RuntimeError('instance %d: the episode needed %d trajectory rows, the trace holds %d: call set_trace(..., '
+                                   'row_cap=%d) or larger' % (e, n.value, self.trace_cap, n.value))
+            rows = np.zeros((n.value, 4), np.uint32)
+            _lib.check(self._L.tsc_env_read_trace(self._h, k, counts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  rows.ctypes.data_as(C.c_void_p), len(rows), C.byref(n)))
+            out[e] = decode_trace(self.scn, counts, rows)
+        self.trajectory_data = out
+        return out
+
     def counters(self):
         """Per-instance counters of the running episode: (arrived, teleported), int64 [E] each.  `arrived` is the episode sum
         of simulation.getArrivedNumber (envs/env.py:413); `teleported` counts the heads the teleport surrogate removed after
@@ -186,6 +227,11 @@ class VecTrafficEnv:
             df = pd.DataFrame(rows)
             df = df[sorted(df.columns)] if len(df.columns) else df
             df.to_csv(output_path + ('%s_%s_%s.csv' % (name, self.agent, kind)))
+        if e in getattr(self, 'trace_instances', []):         # set_trace: the trajectories, <name>_<agent>_fcd.csv
+            tr = self.trajectory_data.get(e)
+            if tr is None:
+                tr = self.collect_trajectories()[e]
+            pd.DataFrame(dict(tr, episode=self.cur_episode))[list(FCD_COLUMNS)].to_csv(output_path + ('%s_%s_fcd.csv' % (name, self.agent)))
 
     def live_vehicle_mean(self, steps, reset=True):
         """Window mean of the vehicles in the network per env instance over the last `steps` control steps."""
@@ -292,6 +338,21 @@ class VecTrafficEnv:
         v = C.c_double()
         _lib.check(self._L.tsc_env_live_vehicles(self._h, C.byref(v)))
         return v.value
+
+
+def decode_trace(scn, counts, rows):
+    """tsc_env_read_trace's output -> trajectory columns (VecTrafficEnv.collect_trajectories): counts [T] rows per simulated second,
+    rows [n, 4] uint32 {lane | route << 16, depart | serial << 16, x bits, v bits}."""
+    rows = np.asarray(rows, np.uint32).reshape(-1, 4)
+    counts = np.asarray(counts, np.int64)
+    n = len(rows)
+    time_sec = np.repeat(np.arange(1, len(counts) + 1), counts)[:n]
+    lane, route, serial = rows[:, 0] & 0xFFFF, rows[:, 0] >> 16, rows[:, 1] >> 16
+    x, v = rows[:, 2].view(np.float32), rows[:, 3].view(np.float32)
+    ids = np.array(['f_%d.%d' % (r, s) for r, s in zip(route.tolist(), serial.tolist())], dtype=object)
+    sumo_lane, pos = scn.sumo_lane_pos(lane.astype(np.int64), x.astype(np.float64))
+    return dict(time_sec=time_sec, id=ids, lane=sumo_lane, pos=pos, speed=v.astype(np.float64),
+                sim_lane=lane.astype(np.int32), x=x, route=route.astype(np.int32), serial=serial.astype(np.int32))
 
 
 ENV_CONFIG_KEYS = dict(control_interval_sec=int, yellow_interval_sec=int, episode_length_sec=int, coop_gamma=float,

@@ -116,12 +116,43 @@ class Scenario:
     stream_mode: np.ndarray = None          # i32 [NS] 0 fixed route, 1 per-vehicle draw (turn ratios), 2 per-episode route from the host
     stream_choice: np.ndarray = None        # i32 [NS, NI, KC, 2] (route, cumulative weight of 65536) per choice interval, route -1 pads
     choice_interval_sec: int = 1 << 30      # length of a choice interval (time-variant turn ratios); NI = stream_choice.shape[1]
+    # SUMO lanes of every lane, in driving order: [(SUMO lane id, where the piece starts on that SUMO lane, its length)].  A lane is
+    # one whole SUMO lane of its own name unless small_grid cut a long SUMO lane into pieces or contract_chains merged a chain
+    # (sumo_lane_pos; the device never sees this)
+    lane_pieces: List = None
 
     def __post_init__(self):
         if self.lane_origin is None:
             self.lane_origin = np.zeros(len(self.lane_names), np.float32)
+        if self.lane_pieces is None:
+            self.lane_pieces = [[(nm, 0.0, float(ln))] for nm, ln in zip(self.lane_names, self.lane_len)]
         if self.link_foes is None:
             self.link_foes = np.zeros(np.asarray(self.link_lane).shape, np.uint32)
+
+    def sumo_lane_pos(self, lane, x):
+        """Simulator (lane, x from the start of the lane) -> (SUMO lane id, position on that SUMO lane), vectorised: object array of
+        ids and float64 positions, shaped like the broadcast inputs.  A position past a piece's end (x beyond the lane) stays at
+        that end."""
+        lane, x = np.broadcast_arrays(np.asarray(lane, np.int64), np.asarray(x, np.float64))
+        cache = getattr(self, '_piece_tables', None)       # (the lane_pieces list it was built from, tables)
+        if cache is None or cache[0] is not self.lane_pieces:
+            names, start_sim, start_sumo, length, first, last = [], [], [], [], [], []
+            for ps in self.lane_pieces:
+                first.append(len(names))
+                off = 0.0
+                for nm, st, ln in ps:
+                    names.append(nm); start_sim.append(off); start_sumo.append(st); length.append(ln)
+                    off += ln
+                last.append(len(names) - 1)
+            pl = np.repeat(np.arange(len(self.lane_pieces)), [len(p) for p in self.lane_pieces])
+            span = 2.0 * (max(sum(p[2] for p in ps) for ps in self.lane_pieces) + 1.0)
+            cache = (self.lane_pieces, (pl * span + np.array(start_sim), span, np.array(names, dtype=object), np.array(start_sim),
+                                        np.array(start_sumo), np.array(length), np.array(first), np.array(last)))
+            self._piece_tables = cache
+        pkey, span, names, start_sim, start_sumo, length, first, last = cache[1]
+        idx = np.searchsorted(pkey, lane * span + np.clip(x, 0.0, None), side='right') - 1
+        idx = np.clip(idx, first[lane], last[lane])
+        return names[idx], start_sumo[idx] + np.clip(x - start_sim[idx], 0.0, length[idx])
 
     @property
     def n_stream(self) -> int:
@@ -945,6 +976,7 @@ def contract_chains(scn: Scenario) -> Scenario:
     # lanes only said "go to the next piece"
     scn.extra['contracted'] = {scn.lane_names[a]: scn.lane_names[resolve(a)[-1]] for a in into}
     scn.lane_names = [scn.lane_names[l] for l in keep]
+    scn.lane_pieces = [[p for c in resolve(first_of[l]) for p in scn.lane_pieces[c]] for l in keep]     # the chain's SUMO lanes, in order
     scn.lane_len, scn.lane_det_start = lane_len, det
     scn.lane_origin = np.array([np.float32(offset[l]) + scn.lane_origin[l] for l in keep], np.float32)
     scn.lane_vmax, scn.lane_node = scn.lane_vmax[keep], scn.lane_node[keep]
@@ -1103,6 +1135,10 @@ def build_small_grid(agent: str = 'greedy', num_extra_car_per_hour: int = 1000, 
         lane_len += [elen[e] / k] * k
     NL = len(lane_names)
     lane_len = np.array(lane_len, np.float32)
+    lane_pieces = []                                              # every piece is a stretch of the SUMO lane <edge>_0
+    for e in ['%s_%s' % x for x in edge_list]:
+        k = piece_last[e] - piece_first[e] + 1
+        lane_pieces += [[('%s_0' % e, float(i * lane_len[piece_first[e]]), float(lane_len[piece_first[e]]))] for i in range(k)]
     # signal links: per TL node, incoming edges clockwise from north, their out-edges in the same sense
     link_edges, phases = {}, []
     for n in node_names:
@@ -1222,6 +1258,7 @@ def build_small_grid(agent: str = 'greedy', num_extra_car_per_hour: int = 1000, 
         link_lane=link_lane, phases=phases, green_tab=green, yellow_tab=yellow,
         neighbors=neighbors, n_s_ls=n_s, n_w_ls=n_w, n_f_ls=n_f, n_a_ls=n_a_ls,
         obs_kind=obs_kind, obs_src=obs_src, flows=flows, obs_len=lens,
+        lane_pieces=lane_pieces,
         extra={'num_extra_car_per_hour': num_extra_car_per_hour, 'routes': route_paths, 'demand': demand,
                'state_phase_map': SMALL_GRID_STATE_PHASE_MAP}, **stream_kw, **env_kw)
     return sort_lanes_by_load(scn) if sort_lanes else scn
@@ -1272,6 +1309,7 @@ def permute_lanes(scn: Scenario, order) -> Scenario:
         out[m] = new_of[v[m]]
         return out.astype(v.dtype)
     scn.lane_names = [scn.lane_names[i] for i in order]
+    scn.lane_pieces = [scn.lane_pieces[i] for i in order]
     for k in ('lane_len', 'lane_vmax', 'lane_node', 'lane_det_start', 'lane_origin'):
         setattr(scn, k, getattr(scn, k)[order])
     if scn.lane_sib is not None:

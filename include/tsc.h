@@ -99,7 +99,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -225,6 +225,17 @@ int tsc_env_read_record(tsc_env *h, int64_t *ints_host, double *speed_host, int3
  * would have moved that vehicle on and written its tripinfo later, so collect_tripinfo (envs/env.py:498-515) must not
  * count it as a finished trip. */
 int tsc_env_read_trips(tsc_env *h, int32_t e, int32_t *trips_host, int32_t max_trips, int32_t *count);
+/* Per-vehicle trajectories (SUMO's --fcd-output without coordinates) of n_trace instances, instances_host[k] going to trace k:
+ * after every simulated second t < episode_length_sec the recording walk of a traced instance appends one 16-byte row per
+ * live vehicle, in (lane, slot) order: {lane | route << 16, depart_sec | serial << 16 (the trip log's ids), x, v} (x, v: the
+ * float bits; x from the start of the simulator's lane).  row_cap rows per trace; rows beyond it are dropped but counted.
+ * Needs tsc_env_record on; call before reset(), which clears the cursors.  n_trace = 0 detaches the trace (the untraced
+ * recording kernels run again).  Rejects out-of-range or repeated instances and row_cap < 1.  Synchronises. */
+int tsc_env_trace(tsc_env *h, int32_t n_trace, const int32_t *instances_host, int32_t row_cap);
+/* Trace k since reset(): counts_host[episode_length_sec] = rows of every second; rows_host [max_rows][4] = the first
+ * min(*n_rows, row_cap, max_rows) rows; *n_rows = rows written and dropped (> row_cap: the buffer overflowed).  Host pointers.
+ * Synchronises. */
+int tsc_env_read_trace(tsc_env *h, int32_t k, int32_t *counts_host, uint32_t *rows_host, int32_t max_rows, int32_t *n_rows);
 
 /* ---- model: replaces IA2C / MA2C (agents/models.py:132-262) + LstmACPolicy / FPLstmACPolicy
  *      (agents/policies.py:75-211) + OnPolicyBuffer (agents/utils.py:182-228) + the TF1 runtime ---- */
