@@ -121,7 +121,19 @@ struct EnvDev {
     const int *g_ncand;            // [A]
     const int8_t *g_term;          // [A][GC][GT] observation index of a term, -1 = end
     const int *g_action;           // [A][GC] action a winning candidate stands for
+    // ---- lane data (tsc_env_lane_data; SUMO's laneData): per slot -- one (lane, SUMO lane it is a piece of) pair -- and interval,
+    // kept by the recording walk of kSpecLaneData / kSpecKraussLaneData.  Behind every other field: the offsets of those stay put.
+    int ld_period;                 // interval length in seconds (a multiple of ctrl: a launch lies in one interval)
+    int ld_nslot;                  // slots of the lanes < NU (a prefix of the slot table)
+    const int *ld_slot0;           // [NL + 1] first slot of every lane (its pieces in driving order)
+    const float4 *ld_bound;        // [NU] where a lane's pieces 2..5 start on it: the smallest float position on the piece (INFINITY: none)
+    const int *ld_sumo;            // [ld_nslot] SUMO lane of the slot (an index)
+    int *ld_int;                   // [E][n_interval][kLdInts][ld_nslot] sums, see kLdSampled...
+    double *ld_speed;              // [E][n_interval][ld_nslot] sums of speeds (per-second sums in slot order, added in second order)
 };
+// Integer fields of the lane data, in the order of tsc_env_read_lane_data
+enum { kLdSampled, kLdWaiting, kLdDeparted, kLdArrived, kLdEntered, kLdLeft, kLdLcFrom, kLdLcTo, kLdTeleported, kLdInts };
+constexpr int kLdMaxPieces = 5;        // slots per lane (Monaco's longest contracted chain): the lookup is four compares, no loop
 
 __device__ __forceinline__ uint32_t hash32(uint32_t seed, uint32_t route, uint32_t serial, uint32_t stream) {
     uint32_t h = seed * 0x9E3779B1u + route * 0x85EBCA77u + serial * 0xC2B2AE3Du + stream * 0x27D4EB2Fu;
@@ -234,6 +246,7 @@ __device__ __forceinline__ bool sig_open(int tl, int k, int a, int w, float x, f
 struct SpecDims { int NLP, NLA, NU, NR, A, KMAX, PMAX, LMAX, NBR, ctrl, yellow, teleport; };
 constexpr int kSpecKrauss = -1;        // SPEC of the Krauss instantiations (runtime dimensions, tsc_env_set_car_following)
 constexpr int kSpecTrace = -2, kSpecKraussTrace = -3;   // the recording walk that also writes per-vehicle rows (tsc_env_trace): IDM / Krauss
+constexpr int kSpecLaneData = -4, kSpecKraussLaneData = -5;   // ... that keeps the lane data (tsc_env_lane_data), the trace optional
 constexpr SpecDims kSpec[3] = {{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0},
                                {192, 128, 88, 12, 25, 12, 5, 6, 4, 5, 2, 600},     // NU: 81 lanes carry vehicles (83 with lane changing); the rest stay empty
                                {192, 128, 113, 16, 28, 22, 6, 11, 5, 5, 2, 300}};
@@ -259,11 +272,15 @@ struct Smem {
     float *wtail, *hz;                          // wave tails of the chain scan [2][16]; old (x, v) across super-rounds [2]
     uint32_t *or0, *or1;                        // outbox of the trip records [kMaxCross*NLA]      (recording only)
     int *rq; double *rsp; long long *rint;      // per-lane halting [NLA], speed partial sums [NLA], counters [4]  (recording only)
+    int *ldi; double *ldsp, *ldsec;             // lane data of the launch's interval [kLdInts][ld_nslot], speed sums [ld_nslot], this
+                                                // second's speed sums [ld_nslot]                                   (LD only)
+    float4 *ldb; int *ldsu;                     // copies of ld_bound [NU] / ld_sumo [ld_nslot]                     (LD only)
 };
 
 // One layout for the step and the reset kernel.
 // KR: the Krauss kernels also hand the vehicles' R0 words over through the outbox (or0), recording or not.
-template <bool KR = false, class Take>
+// LD: the lane-data kernels (a recording walk: no flat phase) hold the lane data where the flat phase's arrays are otherwise.
+template <bool KR = false, bool LD = false, class Take>
 __host__ __device__ __forceinline__ void smem_layout(Smem &s, const EnvDev &P, Take take) {
     s.r = (double *)take(sizeof(double) * (P.A + 1));
     s.mv = (int *)take(sizeof(int) * P.NU * P.NR);
@@ -281,8 +298,14 @@ __host__ __device__ __forceinline__ void smem_layout(Smem &s, const EnvDev &P, T
     s.zip = (uint8_t *)take((P.NU * P.NR + 3) / 4 * 4);
     s.up4 = (uint32_t *)take(4 * P.NLA);
     s.pre = (int *)take(4 * P.NLA); s.wtot = (int *)take(4 * 16);
-    s.mark = (uint8_t *)take((size_t)P.NLA * (kCap - 1) + 8); s.bound = (uint16_t *)take(2 * ((size_t)P.NLA * (kCap - 1) / 64 + 8));
-    s.nc = (int *)take(4 * P.NLA); s.seed = (float *)take(4 * P.NLA); s.wtail = (float *)take(4 * 32); s.hz = (float *)take(4 * 4);
+    if constexpr (LD) {
+        s.mark = nullptr; s.bound = nullptr; s.nc = nullptr; s.seed = nullptr; s.wtail = nullptr; s.hz = nullptr;
+        s.ldi = (int *)take(4 * kLdInts * (size_t)P.ld_nslot); s.ldsp = (double *)take(8 * (size_t)P.ld_nslot);
+        s.ldsec = (double *)take(8 * (size_t)P.ld_nslot); s.ldb = (float4 *)take(16 * (size_t)P.NU); s.ldsu = (int *)take(4 * (size_t)P.ld_nslot);
+    } else {
+        s.mark = (uint8_t *)take((size_t)P.NLA * (kCap - 1) + 8); s.bound = (uint16_t *)take(2 * ((size_t)P.NLA * (kCap - 1) / 64 + 8));
+        s.nc = (int *)take(4 * P.NLA); s.seed = (float *)take(4 * P.NLA); s.wtail = (float *)take(4 * 32); s.hz = (float *)take(4 * 4);
+    }
     if (P.rec) {
         s.or0 = (uint32_t *)take(4 * kMaxCross * P.NLA); s.or1 = (uint32_t *)take(4 * kMaxCross * P.NLA);
         s.rq = (int *)take(4 * P.NLA); s.rsp = (double *)take(8 * P.NLA); s.rint = (long long *)take(8 * 4);
@@ -292,19 +315,19 @@ __host__ __device__ __forceinline__ void smem_layout(Smem &s, const EnvDev &P, T
     }
 }
 
-template <bool KR = false>
+template <bool KR = false, bool LD = false>
 __device__ __forceinline__ Smem carve(char *base, const EnvDev &P) {
     Smem s;
     char *p = base;
-    smem_layout<KR>(s, P, [&](size_t bytes) { char *q = p; p += (bytes + 15) & ~size_t(15); return q; });
+    smem_layout<KR, LD>(s, P, [&](size_t bytes) { char *q = p; p += (bytes + 15) & ~size_t(15); return q; });
     return s;
 }
 
-template <bool KR = false>
+template <bool KR = false, bool LD = false>
 size_t smem_bytes(const EnvDev &P) {
     Smem s;
     size_t tot = 0;
-    smem_layout<KR>(s, P, [&](size_t bytes) { tot += (bytes + 15) & ~size_t(15); return (char *)nullptr; });
+    smem_layout<KR, LD>(s, P, [&](size_t bytes) { tot += (bytes + 15) & ~size_t(15); return (char *)nullptr; });
     return tot;
 }
 
@@ -427,12 +450,18 @@ __global__ void __launch_bounds__(256) greedy_kernel(EnvDev P, const float *__re
 // or not.  (A sentinel of SPEC rather than one more template parameter: the IDM kernels keep their symbols and their code.)
 // SPEC = kSpecTrace / kSpecKraussTrace (tsc_env_trace, recording walk only): after every simulated second a workgroup whose instance
 // is traced writes one row per live vehicle, in (lane, slot) order, behind its running cursor (TR; see the end of the second loop).
+// SPEC = kSpecLaneData / kSpecKraussLaneData (tsc_env_lane_data, recording walk only): the same, the trace optional (null
+// trace_slot: none), and the lane thread also keeps its slots' lane data (LD): it finds every vehicle's slot at the end of the
+// second from its position, and counts the vehicles, the halting ones, the speeds and the events on it; a hand-off carries the
+// vehicle's old slot in the upper half of its outbox target, so that the gathering thread counts `entered` / `laneChangedTo` on
+// its own slot and `left` / `laneChangedFrom` (LDS atomics) on the source's.  The interval's sums stay in LDS for the launch.
 template <int MAXT, bool HELP, bool REC = false, int KF = 4, int SPEC = 0>      // REC: evaluation recording (plain walk only); KF: vehicles per thread and super-round of the flat phase
 __global__ void __launch_bounds__(MAXT, MAXT <= 512 ? 4 : 1)      // (HIP: the second figure is wavefronts per SIMD) 128 VGPRs whatever the workgroup size
 step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, double *__restrict__ reward,
             double *__restrict__ greward, uint8_t *__restrict__ done, int train_mode) {
-    constexpr bool KR = SPEC == kSpecKrauss || SPEC == kSpecKraussTrace;
-    constexpr bool TR = SPEC == kSpecTrace || SPEC == kSpecKraussTrace;
+    constexpr bool KR = SPEC == kSpecKrauss || SPEC == kSpecKraussTrace || SPEC == kSpecKraussLaneData;
+    constexpr bool LD = SPEC == kSpecLaneData || SPEC == kSpecKraussLaneData;
+    constexpr bool TR = SPEC == kSpecTrace || SPEC == kSpecKraussTrace || LD;
     constexpr bool SER = REC || KR;         // R0 (depart | serial << 16) is kept per slot
     static_assert(!TR || (REC && !HELP), "the trace rides on the recording walk");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -442,7 +471,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         P.PMAX = D.PMAX; P.LMAX = D.LMAX; P.NBR = D.NBR; P.ctrl = D.ctrl; P.yellow = D.yellow; P.teleport = D.teleport;
         P.NS = D.NR;                            // the reference's configurations: every route is its own stream
     }
-    Smem s = carve<KR>(smem_raw, P);
+    Smem s = carve<KR, LD>(smem_raw, P);
     const int e = P.order ? P.order[blockIdx.x] : (int)blockIdx.x, l = threadIdx.x, NLP = P.NLP, NLA = P.NLA, NR = P.NR, NS = P.NS;
     const bool lane = l < P.NU;             // lanes >= NU are never entered by any route: always empty
     const bool lthr = l < NLA;              // threads >= NLA only help in phase A1 and in the strided loops
@@ -473,7 +502,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     if (REC && l < 4) s.rint[l] = 0;
     int tslot = -1, tcur = 0;               // TR: this instance's trace buffer (-1: untraced, the same for the whole workgroup), its cursor
     if constexpr (TR) {
-        tslot = P.trace_slot[e];
+        tslot = (LD && !P.trace_slot) ? -1 : P.trace_slot[e];
         if (tslot >= 0) tcur = P.trace_cnt[(size_t)tslot * (P.episode + 1)];
     }
 
@@ -586,6 +615,31 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         s.up4[l] = b8(up0) | b8(up1) << 8 | b8(up2) << 16 | b8(up3) << 24;
         s.nout[l] = 0;
     }
+    // LD: the sums of the interval this launch lies in, into LDS (stored back once, behind the last second); my lane's slots
+    const int nds = LD ? P.ld_nslot : 0;
+    const bool ldon = LD && t < P.episode;
+    int *ld_gi = nullptr; double *ld_gs = nullptr;
+    int ld_k0 = 0, ld_k1 = 0;
+    if constexpr (LD) {
+        if (ldon) {
+            const int nint = (P.episode + P.ld_period - 1) / P.ld_period;
+            const size_t row = (size_t)e * nint + t / P.ld_period;
+            ld_gi = P.ld_int + row * kLdInts * nds; ld_gs = P.ld_speed + row * nds;
+            if (lane) { ld_k0 = P.ld_slot0[l]; ld_k1 = P.ld_slot0[l + 1]; }
+            copy_words((uint32_t *)s.ldi, (const uint32_t *)ld_gi, kLdInts * nds);          // (four loads in flight per thread)
+            copy_words((uint32_t *)s.ldsp, (const uint32_t *)ld_gs, 2 * nds);
+            copy_words((uint32_t *)s.ldsu, (const uint32_t *)P.ld_sumo, nds);
+            copy_words((uint32_t *)s.ldb, (const uint32_t *)P.ld_bound, 4 * P.NU);
+            for (int i = l; i < nds; i += blockDim.x) s.ldsec[i] = 0.0;
+        }
+    }
+    // the slot of position x on my lane: the last piece that starts at or before x (the first one for any x before it).  A lane of
+    // one piece (every lane of large_grid) has it without a look; otherwise four compares against the lane's piece starts.
+    auto ld_slot = [&](float x) {
+        if (ld_k1 == ld_k0 + 1) return ld_k0;
+        const float4 b = s.ldb[l];
+        return ld_k0 + (int)(x >= b.x) + (int)(x >= b.y) + (int)(x >= b.z) + (int)(x >= b.w);
+    };
     unsigned arrived = 0, tele = 0;
     __syncthreads();
     TSC_STAMP();
@@ -611,6 +665,28 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 rq_speed += (double)vn;
                 if (vn < kHalt && xn >= origin) ++rq_halt;
             }
+        };
+        // LD: a vehicle of my lane at the end of this second, at xn with speed vn -> its slot, where it is counted.  The counts and
+        // the speed sum of the slot the last vehicle was on stay in registers (a lane's vehicles come in queue order, so its slot
+        // changes at most once per piece); a change of slot moves them to LDS, and the speed sum continues from the new slot's
+        // partial sum of this second, so the sum is the one of the slot's speeds in queue order whatever the order of slots.
+        // The run starts on the lane's first slot with a sum of 0.0 (what every slot's sum of the second starts from): on a lane of one
+        // piece the slot never changes, and the walk never touches LDS for it.
+        const bool ldsec = ldon && t < P.episode;
+        int ld_cur = ld_k0, ld_ns = 0, ld_nw = 0;
+        double ld_acc = 0.0;
+        auto ld_flush = [&]() {
+            s.ldsec[ld_cur] = ld_acc;
+            s.ldi[kLdSampled * nds + ld_cur] += ld_ns; s.ldi[kLdWaiting * nds + ld_cur] += ld_nw;
+            ld_ns = 0; ld_nw = 0;
+        };
+        auto ld_sample = [&](float xn, float vn) {
+            const int k = ld_slot(xn);
+            if (k != ld_cur) { ld_flush(); ld_cur = k; ld_acc = s.ldsec[k]; }
+            ++ld_ns;
+            if (vn < kHalt) ++ld_nw;
+            ld_acc += (double)vn;
+            return k;
         };
         if constexpr (HELP) {
             // flat order of the queued vehicles (slots >= 1) of the instance, lane after lane: this lane's first flat index P0
@@ -754,6 +830,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 // as a teleport, not as an arrival, and its trip row carries a negative arrival second
                 if (i == 0 && !can_cross && !lc && (tl >= 0 || sb >= 0) && w >= P.teleport) {
                     ++tele;
+                    if constexpr (LD) { if (ldsec) ++s.ldi[kLdTeleported * nds + ld_slot(x)]; }
                     if constexpr (REC) {
                         const int k = atomicAdd(&P.n_trips[e], 1);
                         if (k < P.trip_cap) {
@@ -834,6 +911,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 if (lc) {                                   // rule 10: over to the sibling lane, position kept
                     const int o = nsent * NLA + l;
                     s.ox[o] = xn; s.ov[o] = vn; s.osf[o] = sf; s.om[o] = nmeta; s.oto[o] = sb;
+                    if constexpr (LD) { if (ldsec) s.oto[o] = sb | 0x8000 | ld_slot(x) << 16; }   // LD: lane change (bit 15) from the old slot
                     if constexpr (REC) { s.or0[o] = cur.r0; s.or1[o] = r1n; }
                     else if constexpr (KR) s.or0[o] = cur.r0;
                     ++nsent; ++ncross;
@@ -842,11 +920,13 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         const int o = nsent * NLA + l;
                         const float ex = xn - L, Lt = s.len[tl];          // rounding of (L + Lt) - L
                         s.ox[o] = ex > Lt ? Lt : ex; s.ov[o] = vn; s.osf[o] = sf; s.om[o] = nmeta; s.oto[o] = tl;
+                        if constexpr (LD) { if (ldsec) s.oto[o] = tl | ld_slot(x) << 16; }
                         if constexpr (REC) { s.or0[o] = cur.r0; s.or1[o] = r1n; }
                         else if constexpr (KR) s.or0[o] = cur.r0;
                         ++nsent;
                     } else {
                         ++arrived;
+                        if constexpr (LD) { if (ldsec) ++s.ldi[kLdArrived * nds + ld_slot(x)]; }
                         if constexpr (REC) {
                             ++rq_arr;
                             const int k = atomicAdd(&P.n_trips[e], 1);
@@ -866,6 +946,12 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         if (last && xn >= det) { ++d_wave; if (vn < kHalt) ++d_halt; }
                     } else {
                         keep(xn, vn, sf, nmeta, cur.r0, r1n);
+                        if constexpr (LD) {
+                            if (ldsec) {                           // onto the next piece of a contracted lane: left / entered
+                                const int ko = ld_slot(x), kn = ld_sample(xn, vn);
+                                if (ko != kn && s.ldsu[ko] != s.ldsu[kn]) { ++s.ldi[kLdLeft * nds + ko]; ++s.ldi[kLdEntered * nds + kn]; }
+                            }
+                        }
                     }
                 }
                 cur = nxt;
@@ -1062,7 +1148,8 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 const int cnt = s.nout[src];
                 for (int j = 0; j < cnt; ++j) {
                     const int o = j * NLA + src;
-                    if (s.oto[o] == l && n < kCap) {
+                    const int to = s.oto[o];
+                    if ((LD ? (to & 0x7FFF) : to) == l && n < kCap) {
                         const int d = vslot(n, l, NLP);
                         float ax = s.ox[o];
                         const float av = s.ov[o];
@@ -1074,6 +1161,13 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         S[d] = make_float4(ax, av, s.osf[o], __uint_as_float(am));
                         if constexpr (REC) { R0[d] = s.or0[o]; R1[d] = s.or1[o]; tally(ax, av, am); }
                         else if constexpr (KR) R0[d] = s.or0[o];
+                        if constexpr (LD) {
+                            if (ldsec) {                           // the source's old slot rode in the upper half of `to`
+                                const int kn = ld_sample(ax, av), ko = to >> 16;
+                                if (to & 0x8000) { ++s.ldi[kLdLcTo * nds + kn]; atomicAdd(&s.ldi[kLdLcFrom * nds + ko], 1); }
+                                else if (s.ldsu[ko] != s.ldsu[kn]) { ++s.ldi[kLdEntered * nds + kn]; atomicAdd(&s.ldi[kLdLeft * nds + ko], 1); }
+                            }
+                        }
                         if (n == 0) { hx = ax; hv = av; hsf = s.osf[o]; hm = am; }
                         tx = ax; tv = av;
                         ++n;
@@ -1125,6 +1219,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         S[d] = make_float4(ax, 0.0f, asf, __uint_as_float(am));
                         if constexpr (REC) { R0[d] = (uint32_t)t | ((uint32_t)ser << 16); R1[d] = 0u; tally(ax, 0.0f, am); ++rq_dep; }
                         else if constexpr (KR) R0[d] = (uint32_t)t | ((uint32_t)ser << 16);
+                        if constexpr (LD) { if (ldsec) ++s.ldi[kLdDeparted * nds + ld_sample(ax, 0.0f)]; }
                         if (n == 0) { hx = ax; hv = 0.0f; hsf = asf; hm = am; }
                         tx = ax; tv = 0.0f;
                         ++n;
@@ -1134,6 +1229,12 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     }
                 }
                 s.pend[r] = pend; s.ser[r] = ser;               // a route has exactly one entry lane: no race
+            }
+            if constexpr (LD) {                                  // this second's speed sums into the interval's, second after second
+                if (ldsec) {
+                    ld_flush();
+                    for (int k = ld_k0; k < ld_k1; ++k) { s.ldsp[k] += s.ldsec[k]; s.ldsec[k] = 0.0; }
+                }
             }
         }
         publish();
@@ -1216,6 +1317,12 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     for (int r = l; r < NS; r += blockDim.x) { P.pending[(size_t)e * NS + r] = s.pend[r]; P.serial[(size_t)e * NS + r] = s.ser[r]; }
     if (arrived) atomicAdd(&P.arrived[e], (unsigned long long)arrived);
     if (tele) atomicAdd(&P.teleported[e], (unsigned long long)tele);
+    if constexpr (LD) {                 // the interval's sums back (the barrier that ended the last second orders the LDS)
+        if (ldon) {
+            for (int i = l; i < kLdInts * nds; i += blockDim.x) ld_gi[i] = s.ldi[i];
+            for (int i = l; i < nds; i += blockDim.x) ld_gs[i] = s.ldsp[i];
+        }
+    }
     if (l == 0) { P.tsec[e] = t; done[e] = t >= P.episode ? 1 : 0; }
     TSC_STAMP();
     __syncthreads();
@@ -1345,6 +1452,11 @@ struct tsc_env {
     size_t smem_kr = 0;             // LDS of the Krauss kernels (the R0 outbox on top)
     int threads_kr = 256, kf_kr = 1;
     int n_trace = 0;                // traced instances (tsc_env_trace); their buffers are P.trace_*
+    // lane data (tsc_env_lane_data): buffers P.ld_*, live from the reset after arming on; the caller's slot count (P.ld_nslot:
+    // the prefix of it the device keeps), intervals per episode, LDS of the IDM / Krauss lane-data kernels
+    bool ld_live = false;
+    int ld_nslot_all = 0, ld_nint = 0;
+    size_t smem_ld = 0, smem_kr_ld = 0;
 };
 
 // Workgroup size / flat-phase width of the specialised step kernels for `n_resident` env instances on the device (this handle's
@@ -1415,7 +1527,7 @@ const char *tsc_profile_name(int32_t id) {
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 108; }      // 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 109; }      // 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \
@@ -1452,6 +1564,20 @@ static int krauss_attrs(tsc_env *h) {
 #undef TSC_ATTR_KR
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 1, kSpecKraussTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr));
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 1, kSpecKraussTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr));
+    return 0;
+}
+
+// LDS of the lane-data kernels (recording on, P.ld_nslot set): the flat phase's arrays make room for the lane data
+static int lane_data_attrs(tsc_env *h) {
+    const EnvDev &P = h->P;
+    h->smem_ld = smem_bytes<false, true>(P);
+    h->smem_kr_ld = smem_bytes<true, true>(P);
+    const size_t need = h->smem_ld > h->smem_kr_ld ? h->smem_ld : h->smem_kr_ld;
+    if (need > 160 * 1024) return tsc::fail("tsc_env_lane_data: LDS need %zu B > 160 KiB (%d slots)", need, P.ld_nslot);
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 4, kSpecLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_ld));
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 4, kSpecLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_ld));
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 1, kSpecKraussLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr_ld));
+    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 1, kSpecKraussLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr_ld));
     return 0;
 }
 
@@ -1651,6 +1777,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     P.rec = 0; P.trip_cap = 0; P.R0 = P.R1 = nullptr; P.rec_int = nullptr; P.rec_speed = nullptr; P.rec_queue = nullptr;
     P.trips = nullptr;
     P.trace_cap = 0; P.trace_slot = nullptr; P.trace_cnt = nullptr; P.trace_rows = nullptr;
+    P.ld_period = 0; P.ld_nslot = 0; P.ld_slot0 = nullptr; P.ld_bound = nullptr; P.ld_sumo = nullptr; P.ld_int = nullptr; P.ld_speed = nullptr;
     P.fp_bound = nullptr;
     P.dbg = nullptr;
     P.order = nullptr;
@@ -1736,6 +1863,7 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     TSC_HIP(hipFuncSetAttribute((const void *)reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     if ((h->cf == TSC_CF_KRAUSS || h->cf_next == TSC_CF_KRAUSS) && krauss_attrs(h)) return 1;
+    if (P.ld_int && P.rec && lane_data_attrs(h)) return 1;
     return 0;
 }
 
@@ -1744,6 +1872,78 @@ static void free_alloc(tsc_env *h, const void *p) {
     if (!p) return;
     for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
         if (*it == p) { (void)hipFree(*it); h->allocs.erase(it); return; }
+}
+
+int tsc_env_lane_data(tsc_env *h, int32_t period_sec, int32_t n_slot, const int32_t *lane_slot0_host, const float *slot_start_host,
+                      const int32_t *slot_sumo_host) {
+    if (!h) return tsc::fail("tsc_env_lane_data: bad arguments");
+    EnvDev &P = h->P;
+    const int NL = P.NL;
+    if (period_sec > 0) {
+        if (!P.rec) return tsc::fail("tsc_env_lane_data: recording is off (call tsc_env_record(h, 1, ...) first: the lane data rides on the recording walk)");
+        if (period_sec % P.ctrl) return tsc::fail("tsc_env_lane_data: period %d s is not a multiple of the control interval (%d s)", period_sec, P.ctrl);
+        if (!lane_slot0_host || !slot_start_host || !slot_sumo_host || n_slot < NL) return tsc::fail("tsc_env_lane_data: bad slot tables");
+        if (lane_slot0_host[0] != 0 || lane_slot0_host[NL] != n_slot) return tsc::fail("tsc_env_lane_data: lane_slot0 must run from 0 to n_slot = %d", n_slot);
+        for (int l = 0; l < NL; ++l) {
+            const int k0 = lane_slot0_host[l], k1 = lane_slot0_host[l + 1];
+            if (k1 <= k0) return tsc::fail("tsc_env_lane_data: lane %d has no slot", l);
+            if (k1 - k0 > kLdMaxPieces) return tsc::fail("tsc_env_lane_data: lane %d has %d pieces, at most %d", l, k1 - k0, kLdMaxPieces);
+            for (int k = k0 + 1; k < k1; ++k)
+                if (!(slot_start_host[k] >= slot_start_host[k - 1])) return tsc::fail("tsc_env_lane_data: the pieces of lane %d are out of order", l);
+        }
+        for (int k = 0; k < n_slot; ++k)
+            if (slot_sumo_host[k] < 0) return tsc::fail("tsc_env_lane_data: slot %d has SUMO lane %d", k, slot_sumo_host[k]);
+        if (lane_slot0_host[P.NU] >= 0x8000) return tsc::fail("tsc_env_lane_data: %d slots on the live lanes, at most 32767", lane_slot0_host[P.NU]);
+    }
+    (void)hipSetDevice(h->device);
+    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running step may still write the old buffers
+    free_alloc(h, P.ld_slot0); free_alloc(h, P.ld_bound); free_alloc(h, P.ld_sumo); free_alloc(h, P.ld_int); free_alloc(h, P.ld_speed);
+    P.ld_slot0 = nullptr; P.ld_bound = nullptr; P.ld_sumo = nullptr; P.ld_int = nullptr; P.ld_speed = nullptr;
+    P.ld_period = 0; P.ld_nslot = 0;
+    h->ld_live = false; h->ld_nslot_all = 0; h->ld_nint = 0;
+    if (period_sec <= 0) return 0;                              // detached: the recording kernels without lane data run again
+    const int nds = lane_slot0_host[P.NU];
+    P.ld_period = period_sec; P.ld_nslot = nds;
+    h->ld_nslot_all = n_slot; h->ld_nint = (P.episode + period_sec - 1) / period_sec;
+    if (lane_data_attrs(h)) { P.ld_period = 0; P.ld_nslot = 0; return 1; }
+    UP(ld_slot0, int, lane_slot0_host, NL + 1);
+    {   // a lane's piece starts 2..5 as one 16-byte LDS word per lane (the lookup: four compares)
+        std::vector<float4> b((size_t)P.NU);
+        for (int l = 0; l < P.NU; ++l) {
+            float v[4];
+            for (int j = 0; j < 4; ++j) {
+                const int k = lane_slot0_host[l] + 1 + j;
+                v[j] = k < lane_slot0_host[l + 1] ? slot_start_host[k] : INFINITY;
+            }
+            b[l] = make_float4(v[0], v[1], v[2], v[3]);
+        }
+        UP(ld_bound, float4, b.data(), P.NU);
+    }
+    UP(ld_sumo, int, slot_sumo_host, nds);
+    ALLOC(ld_int, int, (size_t)P.E * h->ld_nint * kLdInts * nds);
+    ALLOC(ld_speed, double, (size_t)P.E * h->ld_nint * nds);
+    return 0;                                                   // (ld_live: from the next reset on)
+}
+
+int tsc_env_read_lane_data(tsc_env *h, int32_t *ints_host, double *speed_host) {
+    if (!h || !ints_host || !speed_host) return tsc::fail("tsc_env_read_lane_data: bad arguments");
+    const EnvDev &P = h->P;
+    if (!P.ld_int) return tsc::fail("tsc_env_read_lane_data: no lane data armed (tsc_env_lane_data)");
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    const int nds = P.ld_nslot, ns = h->ld_nslot_all;
+    const size_t rows = (size_t)P.E * h->ld_nint;
+    std::vector<int> gi(rows * kLdInts * nds);
+    std::vector<double> gs(rows * nds);
+    TSC_HIP(hipMemcpy(gi.data(), P.ld_int, sizeof(int) * gi.size(), hipMemcpyDeviceToHost));
+    TSC_HIP(hipMemcpy(gs.data(), P.ld_speed, sizeof(double) * gs.size(), hipMemcpyDeviceToHost));
+    memset(ints_host, 0, sizeof(int32_t) * rows * kLdInts * ns);       // slots of lanes >= NU: never a vehicle
+    memset(speed_host, 0, sizeof(double) * rows * ns);
+    for (size_t r = 0; r < rows; ++r) {
+        for (int f = 0; f < kLdInts; ++f)
+            memcpy(ints_host + (r * kLdInts + f) * ns, gi.data() + (r * kLdInts + f) * nds, sizeof(int) * nds);
+        memcpy(speed_host + r * ns, gs.data() + r * nds, sizeof(double) * nds);
+    }
+    return 0;
 }
 
 int tsc_env_trace(tsc_env *h, int32_t n_trace, const int32_t *instances_host, int32_t row_cap) {
@@ -1863,6 +2063,12 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
     TSC_HIP(hipMemcpyAsync(h->d_seeds, seeds_host, sizeof(uint32_t) * h->P.E, hipMemcpyHostToDevice, h->stream));
     if (h->P.trace_cnt)                                // tsc_env_trace: cursors and per-second counts start over
         TSC_HIP(hipMemsetAsync(h->P.trace_cnt, 0, sizeof(int) * (size_t)h->n_trace * (h->P.episode + 1), h->stream));
+    h->ld_live = h->P.ld_int != nullptr;               // tsc_env_lane_data takes effect here; its sums start over
+    if (h->ld_live) {
+        const size_t rows = (size_t)h->P.E * h->ld_nint;
+        TSC_HIP(hipMemsetAsync(h->P.ld_int, 0, sizeof(int) * rows * kLdInts * h->P.ld_nslot, h->stream));
+        TSC_HIP(hipMemsetAsync(h->P.ld_speed, 0, sizeof(double) * rows * h->P.ld_nslot, h->stream));
+    }
     hipLaunchKernelGGL(reset_kernel, dim3(h->P.E), dim3(h->P.NLP), h->smem, h->stream, h->P, h->d_seeds, obs_dev);
     TSC_HIP(hipGetLastError());
     TSC_HIP(hipStreamSynchronize(h->stream));          // seeds_host may be reused by the caller
@@ -1993,7 +2199,12 @@ int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *
 #define TSC_STEP_KRT(MAXT)                                                                                             \
     hipLaunchKernelGGL((step_kernel<MAXT, false, true, 1, kSpecKraussTrace>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr, h->stream, h->P, \
                        action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-        if (h->P.rec && h->P.trace_slot) { if (narrow) TSC_STEP_KRT(256); else TSC_STEP_KRT(1024); }
+#define TSC_STEP_KRL(MAXT)                                                                                             \
+    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 1, kSpecKraussLaneData>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr_ld, h->stream, \
+                       h->P, action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
+        if (h->P.rec && h->ld_live) { if (narrow) TSC_STEP_KRL(256); else TSC_STEP_KRL(1024); }
+#undef TSC_STEP_KRL
+        else if (h->P.rec && h->P.trace_slot) { if (narrow) TSC_STEP_KRT(256); else TSC_STEP_KRT(1024); }
 #undef TSC_STEP_KRT
         else if (h->P.rec) { if (narrow) TSC_STEP_KR(256, false, true, 1); else TSC_STEP_KR(1024, false, true, 1); }
         else if (!h->P.help) { if (narrow) TSC_STEP_KR(256, false, false, 1); else TSC_STEP_KR(1024, false, false, 1); }
@@ -2014,7 +2225,12 @@ int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *
 #define TSC_STEP_TRACE(MAXT)                                                                                       \
     hipLaunchKernelGGL((step_kernel<MAXT, false, true, 4, kSpecTrace>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
                        obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-    if (h->P.rec && h->P.trace_slot) { if (h->threads <= 256) TSC_STEP_TRACE(256); else TSC_STEP_TRACE(1024); }
+#define TSC_STEP_LD(MAXT)                                                                                          \
+    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 4, kSpecLaneData>), dim3(h->P.E), dim3(h->threads), h->smem_ld, h->stream, h->P, \
+                       action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
+    if (h->P.rec && h->ld_live) { if (h->threads <= 256) TSC_STEP_LD(256); else TSC_STEP_LD(1024); }
+#undef TSC_STEP_LD
+    else if (h->P.rec && h->P.trace_slot) { if (h->threads <= 256) TSC_STEP_TRACE(256); else TSC_STEP_TRACE(1024); }
 #undef TSC_STEP_TRACE
     else if (h->P.rec) { if (h->threads <= 256) TSC_STEP_REC(256); else TSC_STEP_REC(1024); }
 #define TSC_STEP_KF(KF)                                                                                           \

@@ -20,6 +20,12 @@ from .scenario import LANE_CAP, Scenario, build_scenario
 
 TRACE_ROW_CAP = 1 << 22           # default trajectory rows per traced instance (64 MiB; large_grid's busiest episodes need ~2 M)
 FCD_COLUMNS = ('episode', 'time_sec', 'id', 'lane', 'pos', 'speed')
+# tsc_env_read_lane_data's integer fields, in its order, under SUMO's laneData attribute names; the lanedata table's columns
+LANEDATA_INTS = ('sampledSeconds', 'waitingTime', 'departed', 'arrived', 'entered', 'left', 'laneChangedFrom', 'laneChangedTo',
+                 'teleported')
+LANEDATA_COLUMNS = ('episode', 'begin', 'end', 'id', 'sampledSeconds', 'density', 'occupancy', 'waitingTime', 'speed', 'traveltime',
+                    'departed', 'arrived', 'entered', 'left', 'laneChangedFrom', 'laneChangedTo', 'teleported')
+VEHICLE_LENGTH = 5.0              # m (MICROSIM_SPEC.md; kLen of the kernels): SUMO's occupancy counts it
 
 
 class VecTrafficEnv:
@@ -152,6 +158,47 @@ class VecTrafficEnv:
         self.trajectory_data = out
         return out
 
+    def set_lane_data(self, period):
+        """Per-lane traffic statistics of every instance over intervals of `period` seconds (SUMO's laneData / edgeData
+        meandata, tsc_env_lane_data): from the next reset() on, the recording walk sums per SUMO lane and interval the sampled
+        vehicle-seconds, halting vehicle-seconds, speeds and the departed / arrived / entered / left / lane-changing / teleported
+        vehicles.  Needs set_record(True); `period` must be a positive multiple of control_interval_sec, 0
+        detaches."""
+        period = check_lane_data_period(period, self.scn.control_interval_sec)
+        if period and not getattr(self, 'is_record', False):
+            raise ValueError('set_lane_data: recording is off -- call set_record(True) before set_lane_data (the lane data rides '
+                             'on the recording path)')
+        tabs = self.scn.lane_data_slots()
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        _lib.check(self._L.tsc_env_lane_data(self._h, period, len(tabs['start']), tabs['slot0'].ctypes.data_as(ip),
+                                             tabs['start'].ctypes.data_as(fp), tabs['sumo'].ctypes.data_as(ip)))
+        self.lane_data_period, self._lane_slots = period, tabs
+        self.lane_data = None
+
+    def read_lane_data(self):
+        """The raw sums since reset() (set_lane_data): ints int64 [E, n_interval, 9, n_slot] (LANEDATA_INTS order) and speed_sum
+        float64 [E, n_interval, n_slot], per slot (a piece of a simulator lane, Scenario.lane_data_slots)."""
+        if not getattr(self, 'lane_data_period', 0):
+            raise RuntimeError('read_lane_data: no lane data armed (set_lane_data)')
+        tabs = self._lane_slots
+        n_int = -(-int(self.scn.episode_length_sec) // self.lane_data_period)
+        ints = np.zeros((self.E, n_int, len(LANEDATA_INTS), len(tabs['start'])), np.int32)
+        speed = np.zeros((self.E, n_int, len(tabs['start'])), np.float64)
+        _lib.check(self._L.tsc_env_read_lane_data(self._h, ints.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  speed.ctypes.data_as(C.POINTER(C.c_double))))
+        return ints.astype(np.int64), speed
+
+    def collect_lane_data(self):
+        """Every instance's lane data of the running episode (set_lane_data), merged onto SUMO lanes: {instance: dict of columns}
+        with one row per (interval, SUMO lane), zeros included (merge_lane_data).  Also kept for output_data."""
+        if not getattr(self, 'lane_data_period', 0):
+            return {}
+        ints, speed = self.read_lane_data()
+        cols = merge_lane_data(self._lane_slots, self.lane_data_period, int(self.scn.episode_length_sec), ints, speed)
+        self.lane_data = {e: {k: v[e] if isinstance(v, np.ndarray) and v.ndim == 2 else v for k, v in cols.items()}
+                          for e in range(self.E)}
+        return self.lane_data
+
     def counters(self):
         """Per-instance counters of the running episode: (arrived, teleported), int64 [E] each.  `arrived` is the episode sum
         of simulation.getArrivedNumber (envs/env.py:413); `teleported` counts the heads the teleport surrogate removed after
@@ -232,6 +279,9 @@ class VecTrafficEnv:
             if tr is None:
                 tr = self.collect_trajectories()[e]
             pd.DataFrame(dict(tr, episode=self.cur_episode))[list(FCD_COLUMNS)].to_csv(output_path + ('%s_%s_fcd.csv' % (name, self.agent)))
+        if getattr(self, 'lane_data_period', 0):               # set_lane_data: <name>_<agent>_lanedata.csv
+            ld = self.lane_data if self.lane_data is not None else self.collect_lane_data()
+            lanedata_frame(ld[e], self.cur_episode).to_csv(output_path + ('%s_%s_lanedata.csv' % (name, self.agent)))
 
     def live_vehicle_mean(self, steps, reset=True):
         """Window mean of the vehicles in the network per env instance over the last `steps` control steps."""
@@ -261,6 +311,7 @@ class VecTrafficEnv:
                                          C.c_void_p(self.obs.data_ptr())))
         self.cur_sec = 0
         self.cur_episode += 1
+        self.lane_data = None                                   # (collect_lane_data: the sums start over)
         return self.obs
 
     def update_fingerprint(self, pi, zero_copy=False):
@@ -353,6 +404,65 @@ def decode_trace(scn, counts, rows):
     sumo_lane, pos = scn.sumo_lane_pos(lane.astype(np.int64), x.astype(np.float64))
     return dict(time_sec=time_sec, id=ids, lane=sumo_lane, pos=pos, speed=v.astype(np.float64),
                 sim_lane=lane.astype(np.int32), x=x, route=route.astype(np.int32), serial=serial.astype(np.int32))
+
+
+def check_lane_data_period(period, control_interval_sec):
+    """A lane-data period in seconds (set_lane_data, evaluate --lane-data): 0 = off, else a positive multiple of the control
+    interval, so that one control step never straddles two intervals."""
+    p = int(period)
+    if p != period or p < 0 or p % int(control_interval_sec):
+        raise ValueError('lane data period %r: must be 0 (off) or a positive multiple of the control interval (%d s)'
+                         % (period, control_interval_sec))
+    return p
+
+
+def merge_lane_data(tabs, period, episode_sec, ints, speed):
+    """Raw per-slot sums (VecTrafficEnv.read_lane_data: ints [E, n_interval, 9, n_slot], speed [E, n_interval, n_slot]) ->
+    columns per SUMO lane (tabs: Scenario.lane_data_slots), rows in (interval, SUMO lane) order: begin, end, id, the integer
+    columns of LANEDATA_INTS, speed_sum (a SUMO lane's slots added in slot order, i.e. (simulator lane, piece) order, from 0.0) and
+    the derived columns of SUMO's laneData: density (vehicles / km), occupancy (%, vehicle length 5 m), speed (m/s) and traveltime
+    (s), the last two NaN (an empty field) without samples or at speed 0.  Arrays [E, n_interval * n_sumo_lane]; begin / end / id
+    are shared."""
+    ints, speed = np.asarray(ints), np.asarray(speed, np.float64)
+    E, n_int, _, n_slot = ints.shape
+    names, sumo, length = tabs['names'], np.asarray(tabs['sumo']), np.asarray(tabs['length'], np.float64)
+    n_sumo = len(names)
+    m = np.zeros((n_sumo, n_slot), np.int64)
+    m[sumo, np.arange(n_slot)] = 1
+    isum = np.einsum('eifs,ns->eifn', ints.astype(np.int64), m)
+    # the floats in slot order: a SUMO lane's k-th slot added in round k (a padding column of zeros for the shorter lists)
+    order = [np.flatnonzero(sumo == j) for j in range(n_sumo)]
+    depth = max(len(o) for o in order)
+    pick = np.full((n_sumo, depth), n_slot, np.int64)
+    for j, o in enumerate(order):
+        pick[j, :len(o)] = o
+    sp = np.concatenate([speed, np.zeros((E, n_int, 1))], axis=2)
+    ssum = np.zeros((E, n_int, n_sumo))
+    for k in range(depth):
+        ssum = ssum + sp[:, :, pick[:, k]]
+    begin = np.arange(n_int) * period
+    end = np.minimum(begin + period, episode_sec)
+    P = (end - begin).astype(np.float64)[None, :, None]
+    L = length[None, None, :]
+    samp = isum[:, :, 0, :].astype(np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean = np.where((samp > 0) & (ssum > 0), ssum / samp, np.nan)
+        ttime = L / mean
+    out = dict(begin=np.repeat(begin, n_sumo), end=np.repeat(end, n_sumo),
+               id=np.array(list(names) * n_int, dtype=object),
+               density=(samp / P / (L / 1000.0)).reshape(E, -1),
+               occupancy=(100.0 * samp * VEHICLE_LENGTH / (P * L)).reshape(E, -1),
+               speed=mean.reshape(E, -1), traveltime=ttime.reshape(E, -1), speed_sum=ssum.reshape(E, -1))
+    for f, k in enumerate(LANEDATA_INTS):
+        out[k] = isum[:, :, f, :].reshape(E, -1)
+    return out
+
+
+def lanedata_frame(cols, episode):
+    """One instance's lane-data columns (VecTrafficEnv.collect_lane_data) -> the lanedata table (LANEDATA_COLUMNS)."""
+    import pandas as pd
+    n = len(cols['id'])
+    return pd.DataFrame({k: (np.full(n, episode) if k == 'episode' else cols[k]) for k in LANEDATA_COLUMNS})
 
 
 ENV_CONFIG_KEYS = dict(control_interval_sec=int, yellow_interval_sec=int, episode_length_sec=int, coop_gamma=float,

@@ -6,7 +6,7 @@
     python -m deeprl_signal_control_amd.main --base-dir DIR evaluate --agents ma2c,greedy
                                                                   [--evaluation-policy-type default|stochastic|deterministic]
                                                                   [--evaluation-seeds 10000,20000,...]
-                                                                  [--trajectories N]
+                                                                  [--trajectories N] [--lane-data PERIOD]
 
 Same sub-commands, flags, INI sections ([MODEL_CONFIG] [TRAIN_CONFIG] [ENV_CONFIG], config/config_*.ini of the
 reference are read unchanged) and on-disk layout as the reference: ``DIR/{log,data,model}`` with the config copied
@@ -15,6 +15,9 @@ into ``data/`` (main.py:84-87), ``data/train_reward.csv`` (utils.py:299-308), ``
 <scenario>_<agent>_{control,traffic,trip}.csv`` out (main.py:158-222, utils.py:366-388, envs/env.py:534-542).
 ``--trajectories N`` also writes ``<scenario>_<agent>_fcd.csv``: every vehicle's SUMO lane, position and speed at every second
 (SUMO's --fcd-output without coordinates) for the first N evaluation seeds, with an ``episode`` column.
+``--lane-data PERIOD`` also writes ``<scenario>_<agent>_lanedata.csv``: per SUMO lane and PERIOD-second interval, SUMO's laneData
+statistics (sampled vehicle-seconds, density, occupancy, waiting time, speed, travel time, vehicle counts) for every evaluation
+seed.  PERIOD is a multiple of the control interval; 0 (the default) is off.
 
 What differs: ``--envs E`` trains on E parallel env instances per GPU (the reference has one); `total_step`,
 `test_interval`, `log_interval` keep counting control steps of ONE instance, so a run is E times the experience.
@@ -51,6 +54,9 @@ def parse_args(argv=None):
     sp.add_argument('--demo', action='store_true', help='accepted for compatibility (there is no gui)')
     sp.add_argument('--trajectories', type=int, default=0,
                     help='record per-second vehicle trajectories of the first N evaluation seeds (eva_data/<scenario>_<agent>_fcd.csv)')
+    sp.add_argument('--lane-data', type=int, default=0, metavar='PERIOD',
+                    help='record per-lane statistics over PERIOD-second intervals for every evaluation seed, a multiple of the '
+                         'control interval (eva_data/<scenario>_<agent>_lanedata.csv); 0 = off')
     sp.add_argument('--device', type=int, default=0)
     args = parser.parse_args(argv)
     if not args.option:
@@ -60,6 +66,8 @@ def parse_args(argv=None):
         n_seeds = len([s for s in args.evaluation_seeds.split(',') if s]) if args.evaluation_seeds else 0
         if not 0 <= args.trajectories <= n_seeds:
             parser.error('--trajectories %d: must lie in [0, %d], the number of evaluation seeds' % (args.trajectories, n_seeds))
+        if args.lane_data < 0:
+            parser.error('--lane-data %d: must be 0 (off) or a positive multiple of the control interval' % args.lane_data)
     return args
 
 
@@ -181,9 +189,9 @@ def write_reward_csv(rows, path):
     df.to_csv(path)
 
 
-def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0, trajectories=0):
+def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0, trajectories=0, lane_data=0):
     """main.py:158-198 + Evaluator.run (utils.py:366-388): all evaluation seeds as ONE batched, recorded episode."""
-    from .env import VecTrafficEnv, scenario_from_config
+    from .env import VecTrafficEnv, check_lane_data_period, scenario_from_config
     from .trainer import VecTrainer
     agent = agent_dir.rstrip('/').split('/')[-1]
     if not os.path.isdir(agent_dir):
@@ -197,6 +205,7 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
     if agent == 'greedy':
         config['ENV_CONFIG']['agent'] = 'greedy'
     scn, seed, _ = scenario_from_config(config['ENV_CONFIG'])
+    lane_data = check_lane_data_period(lane_data, scn.control_interval_sec)     # (before any work on the device)
     E = len(seeds)
     env = VecTrafficEnv(scn, E, device=device, seed=seed, test_seeds=seeds)
     logging.info('Evaluation: car following %s' % car_following_label(scn))
@@ -212,11 +221,15 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
     env.set_record(True)
     if trajectories:
         env.set_trace(range(trajectories))
+    if lane_data:
+        env.set_lane_data(lane_data)
     trainer = VecTrainer(env, model)
     mean, std = trainer.perform(np.arange(E), policy_type)
     env.collect_tripinfo()
     if trajectories:
         env.collect_trajectories()
+    if lane_data:
+        env.collect_lane_data()
     for e in range(E):
         logging.info('test %i, avg reward %.2f' % (e, mean[e]))
     write_eval_tables(env, output_dir)
@@ -252,6 +265,10 @@ def write_eval_tables(env, output_dir):
         from .env import FCD_COLUMNS
         df = pd.concat([pd.DataFrame(dict(env.trajectory_data[e], episode=e + 1)) for e in env.trace_instances], ignore_index=True)
         df[list(FCD_COLUMNS)].to_csv(output_dir + ('%s_%s_fcd.csv' % (env.scn.name, env.agent)))
+    if getattr(env, 'lane_data', None):                     # --lane-data: every instance, episode e + 1
+        from .env import lanedata_frame
+        df = pd.concat([lanedata_frame(env.lane_data[e], e + 1) for e in range(env.E)], ignore_index=True)
+        df.to_csv(output_dir + ('%s_%s_lanedata.csv' % (env.scn.name, env.agent)))
 
 
 def evaluate(args):
@@ -263,7 +280,7 @@ def evaluate(args):
     out = {}
     for agent in args.agents.split(','):
         out[agent] = evaluate_agent(args.base_dir + '/' + agent, dirs['eva_data'], seeds, args.evaluation_policy_type, args.device,
-                                    getattr(args, 'trajectories', 0))
+                                    getattr(args, 'trajectories', 0), getattr(args, 'lane_data', 0))
     return out
 
 

@@ -154,6 +154,33 @@ class Scenario:
         idx = np.clip(idx, first[lane], last[lane])
         return names[idx], start_sumo[idx] + np.clip(x - start_sim[idx], 0.0, length[idx])
 
+    def lane_data_slots(self):
+        """The slot tables of the lane data (tsc_env_lane_data; VecTrafficEnv.set_lane_data): one slot per piece of every lane, lane
+        after lane, pieces in driving order.  Returns a dict: slot0 i32 [NL + 1] (a lane's first slot), start f32 [n_slot] (the
+        smallest float32 position on the lane that lies on the piece, i.e. float32(x) >= start exactly when x >= the piece's
+        start in float64, as in sumo_lane_pos), sumo i32 [n_slot] (the slot's SUMO lane, an index into names), names (the SUMO
+        lanes in order of first appearance) and length f64 [len(names)] (a SUMO lane's length: the largest start + length over
+        its pieces)."""
+        slot0, start, sumo, names, index, length = [0], [], [], [], {}, []
+        for ps in self.lane_pieces:
+            off = 0.0
+            for nm, st, ln in ps:
+                if nm not in index:
+                    index[nm] = len(names)
+                    names.append(nm)
+                    length.append(0.0)
+                j = index[nm]
+                length[j] = max(length[j], float(st) + float(ln))
+                start.append(off)
+                sumo.append(j)
+                off += ln
+            slot0.append(len(start))
+        start = np.array(start, np.float64)
+        f = start.astype(np.float32)
+        f = np.where(f.astype(np.float64) < start, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+        return dict(slot0=np.array(slot0, np.int32), start=f, sumo=np.array(sumo, np.int32), names=names,
+                    length=np.array(length, np.float64))
+
     @property
     def n_stream(self) -> int:
         return self.n_route if self.stream_entry_lane is None else len(self.stream_entry_lane)

@@ -99,7 +99,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -236,6 +236,24 @@ int tsc_env_trace(tsc_env *h, int32_t n_trace, const int32_t *instances_host, in
  * min(*n_rows, row_cap, max_rows) rows; *n_rows = rows written and dropped (> row_cap: the buffer overflowed).  Host pointers.
  * Synchronises. */
 int tsc_env_read_trace(tsc_env *h, int32_t k, int32_t *counts_host, uint32_t *rows_host, int32_t max_rows, int32_t *n_rows);
+/* Per-lane traffic statistics (SUMO's laneData) of every instance, over intervals of period_sec seconds: second t < episode_length_sec
+ * counts in interval t / period_sec (n_interval = ceil(episode_length_sec / period_sec)).  A slot is one piece of a lane: the
+ * lane_slot0_host[NL + 1] table gives every lane's first slot (a lane's pieces in driving order, one to five; lane_slot0_host[NL]
+ * = n_slot), slot_start_host[n_slot] the smallest float position on the lane that lies on the piece (a lane's first piece also takes
+ * everything before it), slot_sumo_host[n_slot] the SUMO lane it is a piece of (an index >= 0).  A vehicle belongs to the slot of
+ * its lane and position at the end of a second.  Per slot and interval the recording walk sums (in this order): vehicle-seconds,
+ * vehicle-seconds with v < 0.1, departed (inserted onto the slot), arrived and teleported (left the network from it), entered / left
+ * (a move between slots of different SUMO lanes, other than a lane change: counted on the new / the old slot), laneChangedFrom /
+ * laneChangedTo (a rule-10 move to the sibling lane: on the old / the new slot); the speeds as a double: per slot and second a sum
+ * of the float speeds in queue order, added up second after second.  period_sec must be a multiple of control_interval_sec, so
+ * that a control step lies in one interval.  Needs tsc_env_record on; takes effect at the next reset(), which clears the sums.
+ * period_sec <= 0 detaches (the recording kernels without lane data run again).  Works together with tsc_env_trace.
+ * Synchronises. */
+int tsc_env_lane_data(tsc_env *h, int32_t period_sec, int32_t n_slot, const int32_t *lane_slot0_host, const float *slot_start_host,
+                      const int32_t *slot_sumo_host);
+/* The sums since reset(), every instance: ints_host [E][n_interval][9][n_slot] in the order above, speed_host
+ * [E][n_interval][n_slot].  Host pointers.  Synchronises. */
+int tsc_env_read_lane_data(tsc_env *h, int32_t *ints_host, double *speed_host);
 
 /* ---- model: replaces IA2C / MA2C (agents/models.py:132-262) + LstmACPolicy / FPLstmACPolicy
  *      (agents/policies.py:75-211) + OnPolicyBuffer (agents/utils.py:182-228) + the TF1 runtime ---- */
