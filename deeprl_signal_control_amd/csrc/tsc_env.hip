@@ -33,6 +33,7 @@
 #include "tsc_common.h"
 #include "../../include/tsc.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -81,10 +82,10 @@ struct EnvDev {
     int *iroute;                   // [E][NS] routes of the mode-2 streams of the running episode
     uint4 *trace_rows;             // [n_trace][trace_cap] one row per live vehicle and second: {lane | route << 16, R0, x, v}
     const uint32_t *lane_routes;   // [NL][2] the (<= kMaxEntry) routes whose entry lane this is, one byte each, 0xFF = none
-    const uint8_t *emit_tab;       // [NS][emit_len] vehicles each stream's flows emit at second t
+    const uint8_t *emit_tab;       // [NS][emit_len] vehicles each stream's flows emit at second t (per instance: see emit_inst)
     int emit_len;
     float sigma;                   // Krauss dawdling in force (tsc_env_set_car_following; 0: none).  In the padding behind emit_len: the
-                                   // layout and size of EnvDev, i.e. every kernel's arguments, are those of the IDM-only build
+                                   // offsets of the other fields are those of the IDM-only build
     const int *agent_lanes, *agent_nlane, *agent_nlink, *agent_nphase;
     const uint8_t *green_tab, *yellow_tab;
     const int *nbr, *obs_kind, *obs_src;
@@ -130,6 +131,9 @@ struct EnvDev {
     const int *ld_sumo;            // [ld_nslot] SUMO lane of the slot (an index)
     int *ld_int;                   // [E][n_interval][kLdInts][ld_nslot] sums, see kLdSampled...
     double *ld_speed;              // [E][n_interval][ld_nslot] sums of speeds (per-second sums in slot order, added in second order)
+    // ---- per-instance demand (tsc_env_set_demand): emit_tab then holds one [NS][emit_len] table per instance, emit_inst bytes
+    // apart (demand_kernel writes them at the reset); 0 = every instance reads the scenario's one table.  Behind every other field.
+    int emit_inst;
 };
 // Integer fields of the lane data, in the order of tsc_env_read_lane_data
 enum { kLdSampled, kLdWaiting, kLdDeparted, kLdArrived, kLdEntered, kLdLeft, kLdLcFrom, kLdLcTo, kLdTeleported, kLdInts };
@@ -389,6 +393,39 @@ __global__ void reset_kernel(EnvDev P, const uint32_t *seeds, float *obs) {
     emit_obs(P, s, e, obs);
 }
 
+// Per-instance demand (tsc_env_set_demand): the emission tables of all instances, [E][NS][emit_len] bytes, from each instance's
+// veh/h column.  The flow elements' windows and streams are the scenario's (fl: {begin, end, flow index} per element, grouped by
+// stream, off[r] .. off[r + 1] those of stream r); the counts follow tsc_env_create's integer rule: second t of an element that
+// starts at b emits ceil((t - b + 1) vph / 3600) - ceil((t - b) vph / 3600).  One workgroup per (stream, instance), one thread
+// per four seconds: five ceilings give the four counts, one 32-bit store writes them (emit_len is a multiple of 4).
+__global__ void __launch_bounds__(256) demand_kernel(uint8_t *__restrict__ rows, const int *__restrict__ vph, const int *__restrict__ off,
+                                                     const int *__restrict__ fl, int NS, int emit_len, int n_flow) {
+    const int r = blockIdx.x, e = blockIdx.y;
+    const int f0 = off[r], f1 = off[r + 1];
+    uint32_t *row = (uint32_t *)(rows + ((size_t)e * NS + r) * emit_len);
+    const int *rate = vph + (size_t)e * n_flow;
+    for (int w = threadIdx.x; w < emit_len / 4; w += blockDim.x) {
+        const int t0 = 4 * w;
+        uint32_t c[4] = {0u, 0u, 0u, 0u};
+        for (int f = f0; f < f1; ++f) {
+            const int b = fl[3 * f], en = fl[3 * f + 1];
+            if (t0 + 4 <= b || t0 >= en) continue;
+            const unsigned long long v = (unsigned long long)rate[fl[3 * f + 2]];
+            // vehicles the element has emitted before second t: ceil(clamp(t - b, 0, en - b) v / 3600)
+            unsigned long long cum[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                int tau = t0 + k - b;
+                tau = tau < 0 ? 0 : tau > en - b ? en - b : tau;
+                cum[k] = ((unsigned long long)tau * v + 3599ull) / 3600ull;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[k] += (uint32_t)(cum[k + 1] - cum[k]);
+        }
+        row[w] = c[0] | c[1] << 8 | c[2] << 16 | c[3] << 24;       // (each <= 255: tsc_env_set_demand checked the column)
+    }
+}
+
 __global__ void fingerprint_kernel(EnvDev P, const float *pi) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t tot = (size_t)P.E * P.A * P.PMAX;
@@ -524,6 +561,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     const uint32_t seed = P.seed[e];
     const int rc = l < NS ? l : NS - 1;
     const int pend0 = P.pending[(size_t)e * NS + rc], ser0 = P.serial[(size_t)e * NS + rc];
+    const uint8_t *const emit_tab = P.emit_tab + (size_t)e * P.emit_inst;    // the instance's own table under tsc_env_set_demand
     if (!lane) {
         n = 0; L_ = 1.0f; vmax_ = 1.0f; det = 0.0f; my_node = -1; up0 = up1 = up2 = up3 = -1;
         myr_lo = myr_hi = 0xFFFFFFFFu;
@@ -574,11 +612,11 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     // per-route insertion state and this step's emissions live in LDS for the duration of the launch
     if (l < NS) {
         s.pend[l] = pend0; s.ser[l] = ser0;
-        for (int q = 0; q < 8; ++q) s.emit[l * 8 + q] = q < P.ctrl ? P.emit_tab[(size_t)l * P.emit_len + t + q] : 0;
+        for (int q = 0; q < 8; ++q) s.emit[l * 8 + q] = q < P.ctrl ? emit_tab[(size_t)l * P.emit_len + t + q] : 0;
     }
     for (int r = blockDim.x + l; r < NS; r += blockDim.x) {              // more streams than threads (not on the reference scenarios)
         s.pend[r] = P.pending[(size_t)e * NS + r]; s.ser[r] = P.serial[(size_t)e * NS + r];
-        for (int q = 0; q < 8; ++q) s.emit[r * 8 + q] = q < P.ctrl ? P.emit_tab[(size_t)r * P.emit_len + t + q] : 0;
+        for (int q = 0; q < 8; ++q) s.emit[r * 8 + q] = q < P.ctrl ? emit_tab[(size_t)r * P.emit_len + t + q] : 0;
     }
     for (int a2 = blockDim.x + l; a2 < P.A; a2 += blockDim.x) {          // more agents than threads (ditto)
         const int act2 = action[(size_t)e * P.A + a2], prev2 = P.prev_action[(size_t)e * P.A + a2];
@@ -1457,6 +1495,15 @@ struct tsc_env {
     bool ld_live = false;
     int ld_nslot_all = 0, ld_nint = 0;
     size_t smem_ld = 0, smem_kr_ld = 0;
+    // per-instance demand (tsc_env_set_demand): the scenario's flow table; the [E][n_flow] veh/h columns in force and those the next
+    // reset installs (empty: the scenario's own for every instance); the scenario's table and, from the first set_demand on, the
+    // instances' tables, the uploaded columns and the flow elements grouped by stream (demand_kernel)
+    int n_flow = 0;
+    std::vector<int> h_flows, dem_cur, dem_next;
+    bool dem_dirty = false;
+    const uint8_t *emit_shared = nullptr;
+    uint8_t *dem_rows = nullptr;
+    int *dem_vph = nullptr, *dem_off = nullptr, *dem_fl = nullptr;
 };
 
 // Workgroup size / flat-phase width of the specialised step kernels for `n_resident` env instances on the device (this handle's
@@ -1522,12 +1569,12 @@ const char *tsc_profile_name(int32_t id) {
     static const char *names[] = {"env_step", "fc_gemm", "zx_gemm", "lstm_fwd", "head_fwd", "sample", "add_transition",
                                   "returns", "head_bwd", "lstm_bwd", "dwo_gemm", "dwh_gemm", "dwx_gemm", "dx1_gemm",
                                   "dw1_gemm", "grad_norm", "rmsprop", "transpose_wx", "fingerprint", "policy_fwd_fused",
-                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam"};
+                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "demand"};
     static_assert(sizeof(names) / sizeof(names[0]) == tsc::KID_COUNT, "one name per kernel id");
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 109; }      // 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 110; }      // 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \
@@ -1725,7 +1772,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
                 if (lr[l * kMaxEntry + q] >= 0)
                     lrp[l * 2 + q / 4] = (lrp[l * 2 + q / 4] & ~(0xFFu << (8 * (q % 4)))) | ((uint32_t)lr[l * kMaxEntry + q] << (8 * (q % 4)));
         UP(lane_routes, uint32_t, lrp.data(), lrp.size());
-        P.emit_len = sc->episode_length_sec + 64;
+        P.emit_len = (sc->episode_length_sec + 64 + 3) / 4 * 4;       // (whole words: demand_kernel stores four seconds at once)
         std::vector<uint8_t> em((size_t)NS * P.emit_len, 0);
         for (int f = 0; f < sc->n_flow; ++f) {
             const long long b = sc->flows[f * 4], en = sc->flows[f * 4 + 1], vph = sc->flows[f * 4 + 2];
@@ -1740,6 +1787,10 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
             }
         }
         UP(emit_tab, uint8_t, em.data(), em.size());
+        P.emit_inst = 0;
+        h->emit_shared = P.emit_tab;
+        h->n_flow = sc->n_flow;
+        h->h_flows.assign(sc->flows, sc->flows + (size_t)sc->n_flow * 4);
     }
     if (sc->control_interval_sec > 8) return tsc::fail("tsc_env_create: control interval > 8 s unsupported");
     UP(agent_lanes, int, sc->agent_lanes, A * P.LMAX);
@@ -2063,6 +2114,23 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
     TSC_HIP(hipMemcpyAsync(h->d_seeds, seeds_host, sizeof(uint32_t) * h->P.E, hipMemcpyHostToDevice, h->stream));
     if (h->P.trace_cnt)                                // tsc_env_trace: cursors and per-second counts start over
         TSC_HIP(hipMemsetAsync(h->P.trace_cnt, 0, sizeof(int) * (size_t)h->n_trace * (h->P.episode + 1), h->stream));
+    if (h->dem_dirty) {                                // tsc_env_set_demand takes effect here
+        EnvDev &P = h->P;
+        if (h->dem_next.empty()) { P.emit_tab = h->emit_shared; P.emit_inst = 0; }
+        else {
+            h->dem_cur = h->dem_next;                  // (the copy reads the vector that no set_demand reassigns)
+            TSC_HIP(hipMemcpyAsync(h->dem_vph, h->dem_cur.data(), sizeof(int) * h->dem_cur.size(), hipMemcpyHostToDevice, h->stream));
+            {
+                tsc::ProfScope ps(tsc::KID_DEMAND, h->stream);
+                hipLaunchKernelGGL(demand_kernel, dim3(P.NS, P.E), dim3(256), 0, h->stream, h->dem_rows, h->dem_vph, h->dem_off, h->dem_fl,
+                                   P.NS, P.emit_len, h->n_flow);
+            }
+            TSC_HIP(hipGetLastError());
+            P.emit_tab = h->dem_rows; P.emit_inst = P.NS * P.emit_len;
+        }
+        h->dem_cur = h->dem_next;
+        h->dem_dirty = false;
+    }
     h->ld_live = h->P.ld_int != nullptr;               // tsc_env_lane_data takes effect here; its sums start over
     if (h->ld_live) {
         const size_t rows = (size_t)h->P.E * h->ld_nint;
@@ -2094,6 +2162,108 @@ int tsc_env_car_following(tsc_env *h, int32_t *model, double *sigma) {
     if (!h || !model || !sigma) return tsc::fail("tsc_env_car_following: bad arguments");
     *model = h->cf;
     *sigma = (double)h->P.sigma;
+    return 0;
+}
+
+int tsc_env_set_demand(tsc_env *h, const int32_t *vph_host) {
+    if (!h) return tsc::fail("tsc_env_set_demand: null handle");
+    const EnvDev &P = h->P;
+    const int NF = h->n_flow, NS = P.NS;
+    if (!vph_host) {                             // back to the scenario's column at the next reset
+        h->dem_dirty = h->dem_dirty || !h->dem_next.empty() || !h->dem_cur.empty();
+        h->dem_next.clear();
+        return 0;
+    }
+    if (NF < 1) return tsc::fail("tsc_env_set_demand: the scenario has no flows");
+    for (int f = 0; f < NF; ++f)                 // (the tables' seconds start at 0: demand_kernel counts an element's seconds from its begin)
+        if (h->h_flows[f * 4] < 0) return tsc::fail("tsc_env_set_demand: flow %d begins at second %d < 0", f, h->h_flows[f * 4]);
+    // Everything is checked before anything changes.  The flow windows are the scenario's, so the seconds of a stream split into
+    // a few segments with one set of overlapping elements each (cut at every begin / end); an element emits at most ceil(vph / 3600)
+    // vehicles in a second, so a segment whose elements' bounds add up to <= 255 needs no look at its seconds.
+    struct Seg { int r, t0, t1; std::vector<int> fs; };
+    std::vector<Seg> segs;
+    for (int r = 0; r < NS; ++r) {
+        std::vector<int> cuts;
+        for (int f = 0; f < NF; ++f)
+            if (h->h_flows[f * 4 + 3] == r) {
+                cuts.push_back(std::min(std::max(h->h_flows[f * 4], 0), P.emit_len));
+                cuts.push_back(std::min(std::max(h->h_flows[f * 4 + 1], 0), P.emit_len));
+            }
+        std::sort(cuts.begin(), cuts.end());
+        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+        for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+            Seg sg{r, cuts[c], cuts[c + 1], {}};
+            for (int f = 0; f < NF; ++f)
+                if (h->h_flows[f * 4 + 3] == r && h->h_flows[f * 4] <= sg.t0 && h->h_flows[f * 4 + 1] >= sg.t1) sg.fs.push_back(f);
+            if (!sg.fs.empty()) segs.push_back(std::move(sg));
+        }
+    }
+    for (int e = 0; e < P.E; ++e) {
+        const int32_t *v = vph_host + (size_t)e * NF;
+        for (int f = 0; f < NF; ++f)
+            if (v[f] < 0) return tsc::fail("tsc_env_set_demand: instance %d flow %d: negative rate %d veh/h", e, f, v[f]);
+        for (const Seg &sg : segs) {
+            long long bound = 0;
+            for (int f : sg.fs) bound += ((long long)v[f] + 3599) / 3600;
+            if (bound <= 255) continue;
+            for (int t = sg.t0; t < sg.t1; ++t) {
+                long long sum = 0;
+                for (int f : sg.fs) {
+                    const long long tau = t - h->h_flows[f * 4], vph = v[f];
+                    sum += (((tau + 1) * vph + 3599) / 3600) - ((tau * vph + 3599) / 3600);
+                    if (sum > 255)
+                        return tsc::fail("tsc_env_set_demand: instance %d flow %d (%d veh/h): stream %d emits more than 255 vehicles in second %d",
+                                         e, f, v[f], sg.r, t);
+                }
+            }
+        }
+    }
+    if (!h->dem_rows) {                          // first use: the instances' tables and what demand_kernel reads
+        (void)hipSetDevice(h->device);
+        std::vector<int> off(NS + 1, 0), fl;
+        for (int r = 0; r < NS; ++r) {
+            for (int f = 0; f < NF; ++f)
+                if (h->h_flows[f * 4 + 3] == r) {
+                    const int b = std::min(std::max(h->h_flows[f * 4], 0), P.emit_len);
+                    const int en = std::min(std::max(h->h_flows[f * 4 + 1], b), P.emit_len);
+                    fl.push_back(b); fl.push_back(en); fl.push_back(f);
+                }
+            off[r + 1] = (int)fl.size() / 3;
+        }
+        if (fl.empty()) fl.assign(3, 0);
+        // (each buffer is the handle's as soon as it exists: a call that fails half way is completed by the next one)
+        const size_t bytes = (size_t)P.E * NS * P.emit_len;
+        if (!h->dem_vph) { TSC_HIP(hipMalloc((void **)&h->dem_vph, sizeof(int) * (size_t)P.E * NF)); h->allocs.push_back(h->dem_vph); }
+        auto up = [&](int **field, const std::vector<int> &v) {      // the handle's only once it is filled; freed with it either way
+            int *d = nullptr;
+            const hipError_t e = tsc::upload<int>(&d, v.data(), v.size());
+            if (d) h->allocs.push_back(d);
+            if (e == hipSuccess) *field = d;
+            return e;
+        };
+        if (!h->dem_off) TSC_HIP(up(&h->dem_off, off));
+        if (!h->dem_fl) TSC_HIP(up(&h->dem_fl, fl));
+        uint8_t *rows = nullptr;
+        if (hipMalloc((void **)&rows, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return tsc::fail("tsc_env_set_demand: no device memory for %zu B of per-instance emission tables (%d instances x %d streams x %d s)",
+                             bytes, P.E, NS, P.emit_len);
+        }
+        h->allocs.push_back(rows);
+        h->dem_rows = rows;
+    }
+    h->dem_next.assign(vph_host, vph_host + (size_t)P.E * NF);
+    h->dem_dirty = true;
+    return 0;
+}
+
+int tsc_env_demand(tsc_env *h, int32_t *vph_host) {
+    if (!h || !vph_host) return tsc::fail("tsc_env_demand: bad arguments");
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    const size_t NF = (size_t)h->n_flow;
+    for (size_t e = 0; e < (size_t)h->P.E; ++e)
+        for (size_t f = 0; f < NF; ++f)
+            vph_host[e * NF + f] = h->dem_cur.empty() ? h->h_flows[f * 4 + 2] : h->dem_cur[e * NF + f];
     return 0;
 }
 

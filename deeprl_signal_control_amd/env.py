@@ -31,10 +31,13 @@ VEHICLE_LENGTH = 5.0              # m (MICROSIM_SPEC.md; kLen of the kernels): S
 class VecTrafficEnv:
     """E instances of TrafficSimulator.  Seeds follow the reference's bookkeeping
     (envs/env.py:547-560): instance e starts at ``seed + e`` and every ``reset()`` in train
-    mode advances its seed by ``seed_stride`` (1 for E = 1, like the reference)."""
+    mode advances its seed by ``seed_stride`` (1 for E = 1, like the reference).
+
+    demand: a scenario.DemandSampler -- every ``reset()`` in train mode then draws each instance's veh/h column from its episode
+    seed (set_demand); test mode runs the scenario's own demand unless set_demand is called by hand."""
 
     def __init__(self, scn: Scenario, n_env: int, device=0, seed=12, test_seeds=(10000, 20000),
-                 seed_stride=None, resident=None):
+                 seed_stride=None, resident=None, demand=None):
         if not torch.cuda.is_available():
             raise RuntimeError('VecTrafficEnv needs a GPU (MI355X); there is no CPU fallback')
         self.scn = scn
@@ -54,6 +57,9 @@ class VecTrafficEnv:
         self.seed_stride = self.E if seed_stride is None else seed_stride
         self.cur_episode = 0
         self.cur_sec = 0
+        self.demand_sampler = demand
+        self.demand_scale = np.ones(self.E)                   # the scales the sampler drew for the running episode
+        self._sampled_demand = False                          # a sampled demand is installed (a test-mode reset takes it out)
         self._draws_routes = scn.stream_mode is not None and bool((np.asarray(scn.stream_mode) == 2).any())
         L = _lib.lib()
         self._L = L
@@ -98,6 +104,31 @@ class VecTrafficEnv:
     def use_stream(self, stream):
         self.stream = stream
         _lib.check(self._L.tsc_env_set_stream(self._h, C.c_void_p(stream.cuda_stream)))
+
+    def set_demand(self, vph):
+        """Per-instance traffic demand (tsc_env_set_demand): vph int [E, n_flow], the veh/h of flow element f for instance e in
+        place of scn.flows[f, 2]; None returns to the scenario's own column.  Takes effect at the next reset() and stays in force
+        until changed; a running episode is not touched.  Raises (and changes nothing) on a negative rate or one that makes a
+        stream emit more than 255 vehicles in a second."""
+        if vph is None:
+            _lib.check(self._L.tsc_env_set_demand(self._h, None))
+            return
+        arr = np.asarray(vph)
+        want = (self.E, len(self.scn.flows))
+        if arr.shape != want or not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError('set_demand: vph must be an integer array of shape [E, n_flow] = %r, got %s %r'
+                             % (want, arr.dtype, arr.shape))
+        if arr.size and (arr.min() < np.iinfo(np.int32).min or arr.max() > np.iinfo(np.int32).max):
+            raise ValueError('set_demand: rates outside the int32 range')
+        arr = np.ascontiguousarray(arr, np.int32)
+        _lib.check(self._L.tsc_env_set_demand(self._h, arr.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def demand(self):
+        """The veh/h column in force since the last reset(), int32 [E, n_flow] (the scenario's own, repeated, without
+        set_demand)."""
+        out = np.zeros((self.E, len(self.scn.flows)), np.int32)
+        _lib.check(self._L.tsc_env_demand(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
 
     def set_record(self, on, trip_cap=8192):
         """init_data(is_record=True) (envs/env.py:517-528): the following steps keep, per simulated second, the network
@@ -307,6 +338,16 @@ class VecTrafficEnv:
             from .scenario import draw_stream_routes
             routes = np.ascontiguousarray(np.stack([draw_stream_routes(self.scn, int(sd)) for sd in seeds]), np.int32)
             _lib.check(self._L.tsc_env_set_stream_routes(self._h, routes.ctypes.data_as(C.POINTER(C.c_int32))))
+        if self.demand_sampler is not None:
+            if self.train_mode:          # every instance's demand of this episode, from its seed
+                draws = [self.demand_sampler.draw(int(sd)) for sd in seeds]
+                self.demand_scale = np.array([d[0] for d in draws], np.float64)
+                self.set_demand(np.stack([d[1] for d in draws]))
+                self._sampled_demand = True
+            elif self._sampled_demand:     # test episodes run the nominal demand
+                self.demand_scale = np.ones(self.E)
+                self.set_demand(None)
+                self._sampled_demand = False
         _lib.check(self._L.tsc_env_reset(self._h, s32.ctypes.data_as(C.POINTER(C.c_uint32)),
                                          C.c_void_p(self.obs.data_ptr())))
         self.cur_sec = 0
@@ -468,6 +509,7 @@ def lanedata_frame(cols, episode):
 ENV_CONFIG_KEYS = dict(control_interval_sec=int, yellow_interval_sec=int, episode_length_sec=int, coop_gamma=float,
                        norm_wave=float, norm_wait=float, clip_wave=float, clip_wait=float, coef_wait=float,
                        objective=str, car_following=str, krauss_sigma=float)
+DEMAND_CONFIG_KEYS = ('demand_scales', 'demand_jitter')
 CAR_FOLLOWING_MODELS = ('idm', 'krauss')                 # include/tsc.h TSC_CF_IDM / TSC_CF_KRAUSS
 
 
@@ -506,6 +548,19 @@ def scenario_from_config(config):
     seed = int(get('seed'))
     test_seeds = tuple(int(x) for x in str(get('test_seeds')).split(','))
     return build_scenario(name, agent, **kw), seed, test_seeds
+
+
+def demand_from_config(config, scn):
+    """[ENV_CONFIG] demand_scales = 0.6,0.8,1.0,1.2 / demand_jitter = 0.15 -> the scenario.DemandSampler of a training run, or
+    None with both keys absent (nothing is built then, and no demand call is ever made).  scales > 0, jitter in [0, 1)."""
+    from .scenario import DemandSampler, demand_kw
+    kw = demand_kw(config.get('demand_scales'), config.get('demand_jitter'))
+    if kw is None:
+        return None
+    try:
+        return DemandSampler(scn, *kw)
+    except ValueError as ex:
+        raise ValueError('[ENV_CONFIG] demand_scales / demand_jitter: %s' % ex) from None
 
 
 class NodeView:

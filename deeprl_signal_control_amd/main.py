@@ -7,6 +7,7 @@
                                                                   [--evaluation-policy-type default|stochastic|deterministic]
                                                                   [--evaluation-seeds 10000,20000,...]
                                                                   [--trajectories N] [--lane-data PERIOD]
+                                                                  [--demand-scales 0.8,1.0,1.2]
 
 Same sub-commands, flags, INI sections ([MODEL_CONFIG] [TRAIN_CONFIG] [ENV_CONFIG], config/config_*.ini of the
 reference are read unchanged) and on-disk layout as the reference: ``DIR/{log,data,model}`` with the config copied
@@ -18,6 +19,10 @@ into ``data/`` (main.py:84-87), ``data/train_reward.csv`` (utils.py:299-308), ``
 ``--lane-data PERIOD`` also writes ``<scenario>_<agent>_lanedata.csv``: per SUMO lane and PERIOD-second interval, SUMO's laneData
 statistics (sampled vehicle-seconds, density, occupancy, waiting time, speed, travel time, vehicle counts) for every evaluation
 seed.  PERIOD is a multiple of the control interval; 0 (the default) is off.
+``--demand-scales S1,S2,...`` evaluates every seed under every demand scale (the scenario's demand keys times S, as
+scenario.DemandSampler builds it) as one batched episode of seeds x scales instances -- episode numbers run over the seeds of the
+first scale, then the second ... -- and adds a ``demand_scale`` column to every table.  Training draws its demand per episode from
+``[ENV_CONFIG] demand_scales`` / ``demand_jitter``; the evaluation runs the nominal demand without the flag.
 
 What differs: ``--envs E`` trains on E parallel env instances per GPU (the reference has one); `total_step`,
 `test_interval`, `log_interval` keep counting control steps of ONE instance, so a run is E times the experience.
@@ -57,6 +62,9 @@ def parse_args(argv=None):
     sp.add_argument('--lane-data', type=int, default=0, metavar='PERIOD',
                     help='record per-lane statistics over PERIOD-second intervals for every evaluation seed, a multiple of the '
                          'control interval (eva_data/<scenario>_<agent>_lanedata.csv); 0 = off')
+    sp.add_argument('--demand-scales', type=str, default=None, metavar='S1,S2,...',
+                    help='evaluate every seed under each of these multiples of the scenario\'s demand (one batched episode of seeds '
+                         'x scales instances); every table gets a demand_scale column')
     sp.add_argument('--device', type=int, default=0)
     args = parser.parse_args(argv)
     if not args.option:
@@ -68,6 +76,12 @@ def parse_args(argv=None):
             parser.error('--trajectories %d: must lie in [0, %d], the number of evaluation seeds' % (args.trajectories, n_seeds))
         if args.lane_data < 0:
             parser.error('--lane-data %d: must be 0 (off) or a positive multiple of the control interval' % args.lane_data)
+        if args.demand_scales is not None:
+            from .scenario import demand_kw
+            try:
+                args.demand_scales = list(demand_kw(args.demand_scales)[0])
+            except ValueError as ex:
+                parser.error('--%s' % str(ex).replace('_', '-', 1))
     return args
 
 
@@ -150,7 +164,7 @@ def car_following_label(scn):
 
 def train(args):
     """main.py:82-155 + utils.py:255-308 (Trainer.run)."""
-    from .env import VecTrafficEnv, scenario_from_config
+    from .env import VecTrafficEnv, demand_from_config, scenario_from_config
     from .trainer import Counter, VecTrainer
     dirs = init_dir(args.base_dir)
     init_log(dirs['log'])
@@ -159,8 +173,11 @@ def train(args):
     config.read(args.config_dir)
     in_test, post_test = init_test_flag(args.test_mode)
     scn, seed, test_seeds = scenario_from_config(config['ENV_CONFIG'])
-    env = VecTrafficEnv(scn, args.envs, device=args.device, seed=seed, test_seeds=test_seeds)
+    sampler = demand_from_config(config['ENV_CONFIG'], scn)
+    env = VecTrafficEnv(scn, args.envs, device=args.device, seed=seed, test_seeds=test_seeds, demand=sampler)
     logging.info('Training: car following %s' % car_following_label(scn))
+    if sampler is not None:
+        logging.info('Training: per-instance demand, %s' % sampler.describe())
     logging.info('Training: s dim: %d, a dim %d, s dim ls: %r, a dim ls: %r' % (env.n_s, env.n_a, env.n_s_ls, env.n_a_ls))
     total_step = int(config.getfloat('TRAIN_CONFIG', 'total_step'))
     test_step = int(config.getfloat('TRAIN_CONFIG', 'test_interval'))
@@ -189,8 +206,10 @@ def write_reward_csv(rows, path):
     df.to_csv(path)
 
 
-def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0, trajectories=0, lane_data=0):
-    """main.py:158-198 + Evaluator.run (utils.py:366-388): all evaluation seeds as ONE batched, recorded episode."""
+def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0, trajectories=0, lane_data=0, demand_scales=None):
+    """main.py:158-198 + Evaluator.run (utils.py:366-388): all evaluation seeds as ONE batched, recorded episode.  demand_scales:
+    every seed under each of these demand scales (instance k * len(seeds) + i runs seed i at scale k); the tables then carry a
+    demand_scale column."""
     from .env import VecTrafficEnv, check_lane_data_period, scenario_from_config
     from .trainer import VecTrainer
     agent = agent_dir.rstrip('/').split('/')[-1]
@@ -206,8 +225,18 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
         config['ENV_CONFIG']['agent'] = 'greedy'
     scn, seed, _ = scenario_from_config(config['ENV_CONFIG'])
     lane_data = check_lane_data_period(lane_data, scn.control_interval_sec)     # (before any work on the device)
+    n_seed = len(seeds)
+    scale_of = None
+    if demand_scales:
+        from .scenario import DemandSampler
+        sampler = DemandSampler(scn, demand_scales)
+        scale_of = [float(s_) for s_ in demand_scales for _ in seeds]
+        seeds = list(seeds) * len(demand_scales)
     E = len(seeds)
     env = VecTrafficEnv(scn, E, device=device, seed=seed, test_seeds=seeds)
+    if scale_of is not None:
+        env.set_demand(np.stack([sampler.column(s_) for s_ in scale_of]))
+        logging.info('Evaluation: demand scales %s x %d seeds' % (','.join('%g' % s_ for s_ in demand_scales), n_seed))
     logging.info('Evaluation: car following %s' % car_following_label(scn))
     logging.info('Evaluation: s dim: %d, a dim %d, s dim ls: %r, a dim ls: %r' % (env.n_s, env.n_a, env.n_s_ls, env.n_a_ls))
     if agent != 'greedy':
@@ -219,8 +248,8 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
         model = GreedyPolicy(env)
     env.train_mode = False
     env.set_record(True)
-    if trajectories:
-        env.set_trace(range(trajectories))
+    if trajectories:                 # the first N seeds, under every scale
+        env.set_trace([k * n_seed + i for k in range(E // max(n_seed, 1)) for i in range(trajectories)])
     if lane_data:
         env.set_lane_data(lane_data)
     trainer = VecTrainer(env, model)
@@ -232,22 +261,26 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
         env.collect_lane_data()
     for e in range(E):
         logging.info('test %i, avg reward %.2f' % (e, mean[e]))
-    write_eval_tables(env, output_dir)
+    write_eval_tables(env, output_dir, scale_of)
     env.close()
     if hasattr(model, 'close'):
         model.close()
     return mean, std
 
 
-def write_eval_tables(env, output_dir):
+def write_eval_tables(env, output_dir, scale_of=None):
     """envs/env.py:534-542 over all evaluated instances: instance e is episode e + 1 (the reference runs the seeds one
-    after the other and numbers them by cur_episode)."""
+    after the other and numbers them by cur_episode).  scale_of: the demand scale of every instance (evaluate --demand-scales), a
+    demand_scale column of every table."""
     import pandas as pd
+
+    def scaled(cols, e):
+        return cols if scale_of is None else dict(cols, demand_scale=scale_of[e])
     for kind, per_env in (('control', env.control_data), ('traffic', env.traffic_data), ('trip', env.trip_data),
                           ('trip_truncated', getattr(env, 'truncated_trip_data', []))):
         rows = []
         for e, rs in enumerate(per_env):
-            rows += [dict(r, episode=e + 1) for r in rs]
+            rows += [scaled(dict(r, episode=e + 1), e) for r in rs]
         if kind == 'trip_truncated':
             if not rows:
                 continue
@@ -263,11 +296,12 @@ def write_eval_tables(env, output_dir):
         df.to_csv(output_dir + ('%s_%s_%s.csv' % (env.scn.name, env.agent, kind)))
     if getattr(env, 'trace_instances', None):               # --trajectories: instance e is episode e + 1 here too
         from .env import FCD_COLUMNS
-        df = pd.concat([pd.DataFrame(dict(env.trajectory_data[e], episode=e + 1)) for e in env.trace_instances], ignore_index=True)
-        df[list(FCD_COLUMNS)].to_csv(output_dir + ('%s_%s_fcd.csv' % (env.scn.name, env.agent)))
+        df = pd.concat([pd.DataFrame(scaled(dict(env.trajectory_data[e], episode=e + 1), e)) for e in env.trace_instances], ignore_index=True)
+        df[list(FCD_COLUMNS) + ['demand_scale'] * (scale_of is not None)].to_csv(output_dir + ('%s_%s_fcd.csv' % (env.scn.name, env.agent)))
     if getattr(env, 'lane_data', None):                     # --lane-data: every instance, episode e + 1
         from .env import lanedata_frame
-        df = pd.concat([lanedata_frame(env.lane_data[e], e + 1) for e in range(env.E)], ignore_index=True)
+        df = pd.concat([lanedata_frame(env.lane_data[e], e + 1) if scale_of is None else
+                        lanedata_frame(env.lane_data[e], e + 1).assign(demand_scale=scale_of[e]) for e in range(env.E)], ignore_index=True)
         df.to_csv(output_dir + ('%s_%s_lanedata.csv' % (env.scn.name, env.agent)))
 
 
@@ -280,7 +314,7 @@ def evaluate(args):
     out = {}
     for agent in args.agents.split(','):
         out[agent] = evaluate_agent(args.base_dir + '/' + agent, dirs['eva_data'], seeds, args.evaluation_policy_type, args.device,
-                                    getattr(args, 'trajectories', 0), getattr(args, 'lane_data', 0))
+                                    getattr(args, 'trajectories', 0), getattr(args, 'lane_data', 0), getattr(args, 'demand_scales', None))
     return out
 
 

@@ -22,6 +22,8 @@ spec"); they are this repo's spec, not SUMO's.
 """
 from __future__ import annotations
 
+import copy
+import dataclasses
 from dataclasses import dataclass, field
 from fractions import Fraction
 from typing import Dict, List, Tuple
@@ -1370,6 +1372,123 @@ def sort_lanes_by_load(scn: Scenario) -> Scenario:
     load = lane_load(scn)
     order = sorted(range(scn.n_lane), key=lambda i: (-load[i], i))
     return permute_lanes(scn, order)
+
+
+# the keys of a scenario that set its demand (what DemandSampler scales)
+DEMAND_KEYS = {'large_grid': ('peak_flow1', 'peak_flow2'), 'real_net': ('flow_rate',), 'small_grid': ('num_extra_car_per_hour',)}
+_ENV_FIELDS = ('control_interval_sec', 'yellow_interval_sec', 'episode_length_sec', 'coop_gamma', 'norm_wave', 'norm_wait',
+               'clip_wave', 'clip_wait', 'coef_wait', 'objective', 'car_following', 'krauss_sigma')
+
+
+def demand_kw(scales=None, jitter=None):
+    """[ENV_CONFIG] demand_scales / demand_jitter -> (scales, jitter) of a DemandSampler, or None with both absent.  scales: a
+    comma-separated list (or a sequence) of multipliers > 0, default 1.0 alone; jitter in [0, 1), default 0."""
+    if scales is None and jitter is None:
+        return None
+    if scales is None:
+        scales = (1.0,)
+    if isinstance(scales, str):
+        try:
+            scales = tuple(float(x) for x in scales.split(',') if x.strip())
+        except ValueError:
+            raise ValueError('demand_scales = %r: a comma-separated list of numbers' % scales) from None
+    scales = tuple(float(x) for x in scales)
+    if not scales or not all(np.isfinite(x) and x > 0 for x in scales):
+        raise ValueError('demand_scales = %r: every scale must be > 0 (and there must be one)' % (scales,))
+    try:
+        jitter = 0.0 if jitter is None else float(jitter)
+    except ValueError:
+        raise ValueError('demand_jitter = %r: a number in [0, 1)' % jitter) from None
+    if not 0.0 <= jitter < 1.0:
+        raise ValueError('demand_jitter = %r: must lie in [0, 1)' % jitter)
+    return scales, jitter
+
+
+class DemandSampler:
+    """Per-instance traffic demand for domain-randomised training (VecTrafficEnv(..., demand=sampler), tsc_env_set_demand): an
+    episode's veh/h column, drawn from its seed.
+
+    scales multiply the scenario's demand keys (DEMAND_KEYS: peak_flow1 / peak_flow2, flow_rate, num_extra_car_per_hour); the
+    column of scale s is flows[:, 2] of build_scenario(name, agent, <keys x s>, ...), so the reference generator's %d truncation
+    comes after the scaling.  Only the rates may differ between instances of a handle: every other table of the scaled scenario
+    (brought to the base's lane order, matched by lane name; the free-form `extra` aside) must equal the base's, or the constructor
+    raises ValueError.  jitter = j then multiplies every flow element's rate by an independent u in [1 - j, 1 + j] and truncates.
+
+    build_kw: builder keywords the base scenario was built with that its tables do not show (e.g. contract=False for real_net);
+    the env constants, init_density and lane_change are read from the scenario itself."""
+
+    def __init__(self, scn: Scenario, scales=(1.0,), jitter: float = 0.0, build_kw=None):
+        self.scales, self.jitter = demand_kw(scales, jitter)
+        if scn.name not in DEMAND_KEYS:
+            raise ValueError('DemandSampler: scenario %r has no demand keys (%s)' % (scn.name, ', '.join(DEMAND_KEYS)))
+        self.scn = scn
+        self.keys = {k: scn.extra[k] for k in DEMAND_KEYS[scn.name]}
+        kw = {k: getattr(scn, k) for k in _ENV_FIELDS}
+        if scn.name == 'large_grid':
+            kw.update(init_density=scn.extra.get('init_density', 0.0), lane_change=scn.extra.get('lane_change', LANE_CHANGE_DEFAULT))
+        kw.update(build_kw or {})
+        self._build_kw = kw
+        self.base = np.asarray(scn.flows, np.int32)[:, 2].copy()
+        self._col = {}
+        if not np.array_equal(self.column(1.0), self.base):       # (rates set by hand, or a builder keyword build_kw does not name)
+            raise ValueError('DemandSampler: the rates of %s are not the ones build_scenario gives for its keys %r: scaled columns '
+                             'would not be multiples of this scenario (pass the missing builder keywords as build_kw)'
+                             % (scn.name, self.keys))
+        for s_ in self.scales:
+            self.column(s_)
+
+    def column(self, scale):
+        """int32 [n_flow]: the veh/h column of the scenario built with its demand keys times `scale`."""
+        scale = float(scale)
+        if scale not in self._col:
+            keys = {k: v * scale for k, v in self.keys.items()}
+            other = build_scenario(self.scn.name, self.scn.agent, sort_lanes=False, **keys, **self._build_kw)
+            diff = scenario_table_diff(self.scn, other)
+            if diff:
+                raise ValueError('DemandSampler: scale %g changes more than the rates of %s: %s differ%s from the base scenario '
+                                 '(only the veh/h column may vary between the instances of a handle)'
+                                 % (scale, self.scn.name, ', '.join(diff), 's' if len(diff) == 1 else ''))
+            self._col[scale] = np.asarray(other.flows, np.int32)[:, 2].copy()
+        return self._col[scale].copy()
+
+    def draw(self, seed):
+        """(scale, vph int32 [n_flow]) of the episode with this seed: a pure function of the seed, on a RandomState of its own
+        (seeded with the pair (seed, tag), not with the seed alone: draw_stream_routes' stream is not touched)."""
+        rs = np.random.RandomState([int(seed) & 0xFFFFFFFF, 0x64656D64])
+        scale = self.scales[int(rs.randint(len(self.scales)))]
+        vph = self.column(scale)
+        if self.jitter > 0.0:
+            u = rs.uniform(1.0 - self.jitter, 1.0 + self.jitter, size=len(vph))
+            vph = (vph.astype(np.float64) * u).astype(np.int32)              # truncation, as the generator's %d
+        return scale, vph
+
+    def describe(self):
+        return 'scales %s, jitter %g' % (','.join('%g' % s_ for s_ in self.scales), self.jitter)
+
+
+def scenario_table_diff(base: Scenario, other: Scenario):
+    """Names of the Scenario fields in which `other` differs from `base`, the flows' veh/h column and `extra` aside, after
+    bringing `other` (built with sort_lanes=False) to the lane order of `base`, matched by lane name."""
+    if sorted(base.lane_names) != sorted(other.lane_names) or len(set(base.lane_names)) != len(base.lane_names):
+        return ['lane_names']
+    if list(other.lane_names) != list(base.lane_names):
+        at = {nm: i for i, nm in enumerate(other.lane_names)}
+        other = permute_lanes(copy.copy(other), [at[nm] for nm in base.lane_names])
+    diff = []
+    for f in dataclasses.fields(Scenario):
+        a, b = getattr(base, f.name), getattr(other, f.name)
+        if f.name == 'extra':
+            continue
+        if f.name == 'flows':
+            a, b = np.asarray(a), np.asarray(b)
+            same = a.shape == b.shape and np.array_equal(a[:, [0, 1, 3]], b[:, [0, 1, 3]])
+        elif isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+            same = a is not None and b is not None and np.asarray(a).shape == np.asarray(b).shape and np.array_equal(a, b)
+        else:
+            same = a == b
+        if not same:
+            diff.append(f.name)
+    return diff
 
 
 def build_scenario(name: str, agent: str = 'ma2c', **kw) -> Scenario:

@@ -187,6 +187,8 @@ class VecTrainer:
             mean, std = float(r.mean(0).mean().item()), float(r.std(0, unbiased=False).mean().item())
             data.append({'agent': self.agent, 'step': self.global_counter.cur_step, 'test_id': -1, 'avg_reward': mean, 'std_reward': std})
             logging.info('Training: global step %d, episode %d, avg R: %.2f' % (self.global_counter.cur_step, self.env.cur_episode, mean))
+            if getattr(self.env, 'demand_sampler', None) is not None:
+                logging.info('Training: episode %d, mean demand scale %.3f' % (self.env.cur_episode, float(np.mean(self.env.demand_scale))))
             self.ob = None
         self.log_rewards = was
         return data

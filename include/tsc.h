@@ -99,7 +99,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -144,6 +144,19 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev);
  * what gen_rou_file(seed) would write for every instance's episode seed (the caller draws them; env.py does it with
  * numpy's RandomState(seed), the generator the reference's np.random.seed(seed) + np.random.choice uses). */
 int tsc_env_set_stream_routes(tsc_env *h, const int32_t *routes_host);
+
+/* Per-instance traffic demand.  vph: host int32 [E, n_flow], the veh/h of flow element f for env instance e in place of
+ * flows[f][2]; the elements' windows and streams stay the scenario's.  Takes effect at the NEXT reset() -- a running episode is
+ * never touched -- and stays in force until changed; NULL returns the handle to the scenario's own column at the next reset.
+ * Checked on the host before anything changes: no negative rate, and no second in which the overlapping elements of a stream
+ * emit more than 255 vehicles (the limit of tsc_env_create).  On error the call returns non-zero, tsc_last_error names the
+ * instance and the flow, and the handle keeps the demand it had.  The first call allocates the instances' emission tables
+ * (E x n_stream x (episode + 64) bytes, written on the device at each reset that installs a new demand: only the E x n_flow
+ * rates cross the bus); a handle that never calls it allocates and launches nothing. */
+int tsc_env_set_demand(tsc_env *h, const int32_t *vph_host);
+/* The [E, n_flow] veh/h column in force since the last reset (the scenario's own, repeated, without tsc_env_set_demand).
+ * Synchronises. */
+int tsc_env_demand(tsc_env *h, int32_t *vph_host);
 
 /* update_fingerprint(policy), envs/env.py:633-635.  pi: dev float32 [E, A, AMAX];
  * entries k >= n_a - 1 are ignored. */
