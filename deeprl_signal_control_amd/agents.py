@@ -23,6 +23,24 @@ A2C_DEFAULTS = dict(rmsp_alpha=0.99, rmsp_epsilon=1e-5, max_grad_norm=40.0, gamm
                     entropy_decay='constant', entropy_ratio=0.5, value_coef=0.5, num_fw=128, num_ft=32,
                     num_lstm=64, num_fp=64, batch_size=120, reward_norm=2000.0, reward_clip=2.0,
                     lr_min=0.0)     # config/config_ma2c_large.ini [MODEL_CONFIG]
+# The opt-in PPO update (no reference counterpart; include/tsc.h tsc_model_compute_grads_ppo): `algo = ppo` runs ppo_epochs epochs
+# per rollout under the clipped surrogate (ppo_clip) with GAE(gae_lambda) advantages; `algo = a2c`, the default, ignores the rest.
+PPO_DEFAULTS = dict(algo='a2c', ppo_epochs=4, ppo_clip=0.2, gae_lambda=0.95)
+
+
+def check_algo_config(cfg):
+    """Validate the [MODEL_CONFIG] keys of PPO_DEFAULTS in a coerced config; returns (algo, epochs, clip, lambda)."""
+    algo = str(cfg['algo']).strip().lower()
+    if algo not in ('a2c', 'ppo'):
+        raise ValueError("MODEL_CONFIG algo = %r: expected 'a2c' or 'ppo'" % (cfg['algo'],))
+    epochs, clip, lam = cfg['ppo_epochs'], cfg['ppo_clip'], cfg['gae_lambda']
+    if not isinstance(epochs, int) or isinstance(epochs, bool) or epochs < 1:
+        raise ValueError('MODEL_CONFIG ppo_epochs = %r: expected an integer >= 1' % (epochs,))
+    if not (isinstance(clip, (int, float)) and clip > 0):
+        raise ValueError('MODEL_CONFIG ppo_clip = %r: expected a number > 0' % (clip,))
+    if not (isinstance(lam, (int, float)) and 0 < lam <= 1):
+        raise ValueError('MODEL_CONFIG gae_lambda = %r: expected a number in (0, 1]' % (lam,))
+    return algo, int(epochs), float(clip), float(lam)
 
 
 class TscModelCfg(C.Structure):
@@ -253,6 +271,9 @@ def _setup_lib(L):
     L.tsc_model_compute_grads.argtypes = [vp, vp, C.c_double]
     L.tsc_model_grad_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int64)]
     L.tsc_model_apply_grads.argtypes = [vp, C.c_double, C.c_double, vp]
+    L.tsc_model_compute_grads_ppo.argtypes = [vp, vp, C.c_double, C.c_double, C.c_double, C.c_int32]
+    L.tsc_model_apply_grads_ex.argtypes = [vp, C.c_double, C.c_double, vp, C.c_int32]
+    L.tsc_model_ppo_stats.argtypes = [vp, vp]
     L.tsc_model_get_returns.argtypes = [vp, vp, vp]
     L.tsc_model_debug_clock.argtypes = [vp, C.c_int32, vp, C.c_int32]
     L.tsc_gemm_grouped_f32.argtypes = [C.c_int32] * 6 + [vp, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32,
@@ -267,7 +288,9 @@ class VecA2C:
                  total_step=0, device=0, seed=None, name='ma2c', process_group=None, policy='lstm', replica=0):
         if not torch.cuda.is_available():
             raise RuntimeError('VecA2C needs a GPU (MI355X); there is no CPU fallback')
-        cfg = coerce_config(model_config, A2C_DEFAULTS)
+        cfg = coerce_config(model_config, {**A2C_DEFAULTS, **PPO_DEFAULTS})
+        self.algo, self.ppo_epochs, self.ppo_clip, self.gae_lambda = check_algo_config(cfg)
+        self.n_epoch = self.ppo_epochs if self.algo == 'ppo' else 1       # updates per rollout
         self.cfg, self.name = cfg, name
         self.policy = policy                    # 'lstm' (what the reference instantiates) or 'fc' (FcACPolicy; MA2C: FPFcACPolicy)
         self.n_agent, self.E = len(n_s_ls), int(n_env)
@@ -281,6 +304,8 @@ class VecA2C:
         self.pg = process_group
         self.total_step = total_step
         self._init_scheduler()
+        self._cur_lr, self._cur_beta = self.lr_scheduler.val, self.beta_scheduler.val      # of the running rollout (compute_grads, epoch 0)
+        self._next_epoch, self._pending_epoch = 0, None     # the update of the rollout that comes next / whose gradients await apply_grads
         L = _lib.lib()
         _setup_lib(L)
         self._L = L
@@ -468,8 +493,13 @@ class VecA2C:
         self.sample_step += 1
         return self.pi, v, act
 
+    def _rollout_open(self):
+        assert self._next_epoch == 0 and self._pending_epoch is None, \
+            'the previous rollout still has updates left (algo = ppo: %d of %d epochs ran)' % (self._next_epoch, self.n_epoch)
+
     def commit_transition(self):
         """The transition of slot cur_t was written in place (rollout_slots): only the slot counter moves."""
+        self._rollout_open()
         self.cur_t += 1
 
     def sample(self, pi=None):
@@ -484,6 +514,7 @@ class VecA2C:
         """agents/models.py:222-229 (+ the pre-step done the LSTM saw, agents/utils.py:225-226)."""
         if not torch.is_tensor(done_pre):
             done_pre = torch.full((self.E,), int(bool(done_pre)), dtype=torch.uint8, device=self.device)
+        self._rollout_open()
         _lib.check(self._L.tsc_model_add_transition(
             self._h, self.cur_t, C.c_void_p(obs.data_ptr()), C.c_void_p(done_pre.data_ptr()),
             C.c_void_p(actions.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(values.data_ptr()),
@@ -494,31 +525,62 @@ class VecA2C:
         self.stream = stream
         _lib.check(self._L.tsc_model_set_stream(self._h, C.c_void_p(stream.cuda_stream)))
 
-    def compute_grads(self, R):
-        """First half of IA2C.backward (agents/models.py:174-183): returns + loss + BPTT -> flat gradient buffer."""
+    def compute_grads(self, R, epoch=None):
+        """First half of IA2C.backward (agents/models.py:174-183): returns + loss + BPTT -> flat gradient buffer.
+        algo = ppo: the next of the rollout's n_epoch updates (the lr / beta schedulers advance at epoch 0 only: once per
+        rollout).  The object counts the epochs: compute_grads / apply_grads alternate, n_epoch pairs per rollout; `epoch`, if
+        given, must be the one that is due."""
         assert self.cur_t == self.n_step, 'backward() needs a full n_step buffer (T %% n_step == 0, utils.py:121)'
-        self._cur_lr = self.lr_scheduler.get(self.n_step)
-        self._cur_beta = cur_beta = self.beta_scheduler.get(self.n_step)
-        _lib.check(self._L.tsc_model_compute_grads(self._h, C.c_void_p(R.data_ptr()), float(cur_beta)))
+        assert self._pending_epoch is None, 'compute_grads twice without apply_grads'
+        assert epoch is None or epoch == self._next_epoch, 'epoch %r given, epoch %d of %d is due' % (epoch, self._next_epoch, self.n_epoch)
+        epoch = self._pending_epoch = self._next_epoch
+        if epoch == 0:
+            self._cur_lr = self.lr_scheduler.get(self.n_step)
+            self._cur_beta = self.beta_scheduler.get(self.n_step)
+        if self.algo == 'ppo':
+            _lib.check(self._L.tsc_model_compute_grads_ppo(self._h, C.c_void_p(R.data_ptr()), float(self._cur_beta), self.ppo_clip,
+                                                           self.gae_lambda, int(epoch)))
+        else:
+            _lib.check(self._L.tsc_model_compute_grads(self._h, C.c_void_p(R.data_ptr()), float(self._cur_beta)))
 
-    def apply_grads(self, scale=1.0, want_stats=False):
-        """Second half: per-agent clip on grad * scale, TF1 RMSProp, states_bw <- states_fw, buffer reset."""
+    def apply_grads(self, scale=1.0, want_stats=False, epoch=None):
+        """Second half, of the epoch compute_grads just ran: per-agent clip on grad * scale, TF1 RMSProp; after the rollout's last
+        epoch (the only one under algo = a2c) also states_bw <- states_fw and the buffer reset.  Stats: [A,4] losses and
+        gradient norm; algo = ppo appends the clipped share and the approximate KL of the epoch ([A,6])."""
+        due = self._next_epoch if self._pending_epoch is None else self._pending_epoch      # None: the caller filled the gradient buffer itself
+        assert epoch is None or epoch == due, 'epoch %r given, the gradients are epoch %d\'s' % (epoch, due)
+        epoch, self._pending_epoch = due, None
         stats = np.zeros((self.n_agent, 4), np.float64) if want_stats else None
-        _lib.check(self._L.tsc_model_apply_grads(self._h, float(self._cur_lr), float(scale),
-                                                 stats.ctypes.data_as(C.c_void_p) if want_stats else None))
-        self.cur_t = 0
+        last = epoch == self.n_epoch - 1
+        self._next_epoch = 0 if last else epoch + 1
+        _lib.check(self._L.tsc_model_apply_grads_ex(self._h, float(self._cur_lr), float(scale),
+                                                    stats.ctypes.data_as(C.c_void_p) if want_stats else None, int(last)))
+        if last:
+            self.cur_t = 0
+        if want_stats and self.algo == 'ppo':
+            stats = np.concatenate([stats, self.ppo_stats()], 1)
         return stats
 
+    def ppo_stats(self):
+        """Per agent {clipped share, mean(logp_old - logp)} of the last PPO epoch, float64 [A,2]."""
+        out = np.zeros((self.n_agent, 2), np.float64)
+        _lib.check(self._L.tsc_model_ppo_stats(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def backward(self, R, summary_writer=None, global_step=None, want_stats=False):
-        """agents/models.py:174-183.  R: bootstrap values f32 [E,A] (zeros where terminal)."""
-        self.compute_grads(R)
-        scale = 1.0
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            # the gradient kernels run on self.stream: issue the collective there too, so that it starts after
-            # compute_grads and apply_grads starts after it, whatever torch's current stream is
-            with torch.cuda.stream(self.stream):
-                scale = allreduce_grads_(self.grad_tensor(), self.pg)   # RCCL over xGMI, one flat buffer
-        return self.apply_grads(scale, want_stats)
+        """agents/models.py:174-183.  R: bootstrap values f32 [E,A] (zeros where terminal).  algo = ppo: n_epoch rounds of
+        compute -> all-reduce -> apply over the same rollout; returns the last epoch's stats."""
+        stats = None
+        for epoch in range(self.n_epoch):
+            self.compute_grads(R, epoch)
+            scale = 1.0
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                # the gradient kernels run on self.stream: issue the collective there too, so that it starts after
+                # compute_grads and apply_grads starts after it, whatever torch's current stream is
+                with torch.cuda.stream(self.stream):
+                    scale = allreduce_grads_(self.grad_tensor(), self.pg)   # RCCL over xGMI, one flat buffer
+            stats = self.apply_grads(scale, want_stats and epoch == self.n_epoch - 1, epoch)
+        return stats
 
     # ---- checkpoints (agents/models.py:83-108: `checkpoint-<step>`, highest step wins) -------
     def save(self, model_dir, global_step):

@@ -1569,12 +1569,13 @@ const char *tsc_profile_name(int32_t id) {
     static const char *names[] = {"env_step", "fc_gemm", "zx_gemm", "lstm_fwd", "head_fwd", "sample", "add_transition",
                                   "returns", "head_bwd", "lstm_bwd", "dwo_gemm", "dwh_gemm", "dwx_gemm", "dx1_gemm",
                                   "dw1_gemm", "grad_norm", "rmsprop", "transpose_wx", "fingerprint", "policy_fwd_fused",
-                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "demand"};
+                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "demand",
+                                  "gae", "head_bwd_ppo"};
     static_assert(sizeof(names) / sizeof(names[0]) == tsc::KID_COUNT, "one name per kernel id");
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 110; }      // 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 111; }      // 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \

@@ -443,6 +443,8 @@ __global__ void __launch_bounds__(64) head_fwd_kernel(const float *__restrict__ 
 // added in slice order by head_bwd2_reduce_kernel (deterministic), which replaces the separate split-K dWo GEMM and
 // its second pass over h and dL.  grid = (slices, agents), 256 threads.
 // ------------------------------------------------------------------------------------------------
+// head_bwd_ppo_kernel below is this pass with PPO's policy term; the two bodies are kept apart because sharing one (a templated
+// device function) changed this kernel's register allocation.  A fix to the shared part goes into BOTH.
 constexpr int kHbPer = kL * kOut + kOut + kL + 1;      // partial record of a slice: dWo [64][8] | dbo [8] | dWv [64] | dbv
 
 __global__ void __launch_bounds__(256, 3)
@@ -617,6 +619,205 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
         double a0 = 0, a1 = 0, a2 = 0;
         for (int w = 0; w < 4; ++w) { a0 += redl[w][0]; a1 += redl[w][1]; a2 += redl[w][2]; }
         atomicAdd(&stats[a * 4 + 0], a0); atomicAdd(&stats[a * 4 + 1], a1); atomicAdd(&stats[a * 4 + 2], a2);
+    }
+}
+
+// head_bwd for the PPO update (tsc_model_compute_grads_ppo): a copy of head_bwd2_kernel above (keep the two in step: what differs
+// is the block between `logpm` and `dot`, the lp / lc / lk sums and redl's width) -- same decomposition, same partial records
+// for head_bwd2_reduce_kernel, same value and entropy terms -- with the clipped-surrogate policy term
+//   -mean(min(ratio A, clip(ratio, 1 - eps, 1 + eps) A)),   ratio = exp(logp - logp_old).
+// A sample's policy gradient is -A ratio / N through logp, and zero where the clipped branch is the smaller one (A > 0 and
+// ratio > 1 + eps, or A < 0 and ratio < 1 - eps) or pi sits below the 1e-10 clamp.  logp_old [N][A] holds log(clip(pi_old(a_n),
+// 1e-10, 1)), one more 4-byte stream per (sample, agent): record != 0 (epoch 0) writes it from this very evaluation, record == 0
+// reads it.  stats[a][0] is the surrogate loss; ppo_stats [A][2] += {clipped share, mean(logp_old - logp)}.
+__global__ void __launch_bounds__(256, 3)
+head_bwd_ppo_kernel(const float *__restrict__ params, Layout lay, const int *__restrict__ n_act, const float *__restrict__ Hh,
+                    const int *__restrict__ act, const float *__restrict__ Rs, const float *__restrict__ Advs, long long N,
+                    long long rows_per_slice, float v_coef, float beta, float *__restrict__ dH, float *__restrict__ part,
+                    double *stats, float *__restrict__ logp_old, int record, float clip_eps, double *ppo_stats) {
+    __shared__ float red[4][16][36];
+    const int a = blockIdx.y, sp = blockIdx.x, na = n_act[a];
+    const int tid = threadIdx.x, c = tid & 15, grp = tid >> 4;          // 16 sample groups per workgroup
+    const float *Pp = params + (long long)(2 * a) * lay.stride, *Pv = params + (long long)(2 * a + 1) * lay.stride;
+    float wo[4][kOut], wv[4], bo[kOut];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) wo[u][k] = Pp[lay.oWo + (4 * c + u) * kOut + k];
+        wv[u] = Pv[lay.oWo + (4 * c + u) * kOut];
+    }
+#pragma unroll
+    for (int k = 0; k < kOut; ++k) bo[k] = Pp[lay.obo + k];
+    const float bv = Pv[lay.obo];
+    float aw[4][kOut], awv[4], ab[kOut], abv = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        awv[u] = 0.f;
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) aw[u][k] = 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < kOut; ++k) ab[k] = 0.f;
+    float lp = 0.f, lv = 0.f, le = 0.f, lc = 0.f, lk = 0.f;       // lc, lk: clipped share and approximate KL
+    const long long n0 = (long long)sp * rows_per_slice;
+    long long n1 = n0 + rows_per_slice;
+    if (n1 > N) n1 = N;
+    const float *hp = Hh + (long long)(2 * a) * N * kL + 4 * c, *hq = Hh + (long long)(2 * a + 1) * N * kL + 4 * c;
+    float *dp = dH + (long long)(2 * a) * N * kL + 4 * c, *dq = dH + (long long)(2 * a + 1) * N * kL + 4 * c;
+    const float invN = 1.0f / (float)N;
+    for (long long nb = n0; nb < n1; nb += 16) {
+        const long long n = nb + grp;
+        const bool in = n < n1;
+        const long long nc = in ? n : n1 - 1;                           // clamped: unconditional loads
+        const float4 h4 = *reinterpret_cast<const float4 *>(hp + nc * kL);
+        const float4 g4 = *reinterpret_cast<const float4 *>(hq + nc * kL);
+        const long long idx = nc * lay.A + a;
+        const int ac = act[idx];
+        const float adv = Advs[idx], R = Rs[idx];
+        const float hh[4] = {h4.x, h4.y, h4.z, h4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
+        float lg[kOut], vv = 0.f;
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) lg[k] = 0.f;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) lg[k] += hh[u] * wo[u][k];
+            vv += gg[u] * wv[u];
+        }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {                              // the 16 lanes of a sample are one shuffle row
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) lg[k] += __shfl_xor(lg[k], o, 64);
+            vv += __shfl_xor(vv, o, 64);
+        }
+        const float v = vv + bv;
+        // softmax / loss gradient: lane c of the sample's 16 handles action k = c & 7 (one exp, one log, one division per
+        // lane instead of eight of each), sums go over the 8-lane row by xor-shuffles, then every lane collects all dl[k]
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) { lg[k] += bo[k]; if (k < na && lg[k] > mx) mx = lg[k]; }
+        const int km = c & 7;
+        float lgm = lg[0];
+#pragma unroll
+        for (int k = 1; k < kOut; ++k) lgm = km == k ? lg[k] : lgm;
+        const bool valid = km < na;
+        const float pk = valid ? expf(lgm - mx) : 0.f;
+        float sum = pk;
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) sum += __shfl_xor(sum, o, 64);
+        const float pim = pk / sum;
+        const bool inr = pim >= 1e-10f;                                  // tf.clip_by_value(pi, 1e-10, 1)
+        const float logpm = valid ? logf(fminf(fmaxf(pim, 1e-10f), 1.0f)) : 0.f;
+        float gpi = 0.f;
+        float lpa = (km == (ac < na ? ac : 0)) ? logpm : 0.f;
+        // the surrogate needs log pi(a_n) before the gradient: one nonzero term per 8-lane row, so the sum is exact
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) lpa += __shfl_xor(lpa, o, 64);
+        const float lpo = record ? lpa : logp_old[idx];
+        const float ratio = expf(lpa - lpo);                            // record: exp(0) = 1, the A2C gradient bit for bit
+        const bool clipped = (adv > 0.f && ratio > 1.0f + clip_eps) || (adv < 0.f && ratio < 1.0f - clip_eps);
+        if (record && in && c == 0) logp_old[idx] = lpa;
+        if (valid) {
+            if (km == ac && inr && !clipped) gpi += -adv * ratio * invN / fmaxf(pim, 1e-10f);
+            gpi += beta * invN * (logpm + (inr ? 1.0f : 0.f));
+        }
+        float dot = pim * gpi, ent = valid ? -pim * logpm : 0.f;
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) {
+            dot += __shfl_xor(dot, o, 64); ent += __shfl_xor(ent, o, 64);
+        }
+        const float dlm = (in && valid) ? pim * (gpi - dot) : 0.f;
+        float dl[kOut];
+        const int row0 = (tid & 63) & ~15;
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) dl[k] = __shfl(dlm, row0 + k, 64);
+        const float dv = in ? v_coef * (v - R) * invN : 0.f;
+        // dH of my quad (FC policy: the head input is relu(.), fold its derivative in), dWo / dWv accumulation
+        float o4[4], q4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float sacc = 0.f;
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) { sacc += dl[k] * wo[u][k]; aw[u][k] += hh[u] * dl[k]; }
+            o4[u] = (lay.fc && !(hh[u] > 0.f)) ? 0.f : sacc;
+            q4[u] = (lay.fc && !(gg[u] > 0.f)) ? 0.f : dv * wv[u];
+            awv[u] += gg[u] * dv;
+        }
+        if (in) {
+            *reinterpret_cast<float4 *>(dp + n * kL) = make_float4(o4[0], o4[1], o4[2], o4[3]);
+            *reinterpret_cast<float4 *>(dq + n * kL) = make_float4(q4[0], q4[1], q4[2], q4[3]);
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) ab[k] += dl[k];
+            abv += dv;
+            if (in) {
+                const float rc = fminf(fmaxf(ratio, 1.0f - clip_eps), 1.0f + clip_eps);
+                lp += -fminf(ratio * adv, rc * adv) * invN;
+                lc += clipped ? invN : 0.f;
+                lk += (lpo - lpa) * invN;
+                lv += 0.5f * v_coef * (R - v) * (R - v) * invN;
+                le += -beta * ent * invN;
+            }
+        }
+    }
+    // fold the 16 sample groups: across the wave's four groups by shuffles, across the four waves through LDS
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int o = 16; o < 64; o <<= 1) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) aw[u][k] += __shfl_xor(aw[u][k], o, 64);
+            awv[u] += __shfl_xor(awv[u], o, 64);
+        }
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) ab[k] += __shfl_xor(ab[k], o, 64);
+        abv += __shfl_xor(abv, o, 64);
+        lp += __shfl_xor(lp, o, 64); lv += __shfl_xor(lv, o, 64); le += __shfl_xor(le, o, 64);
+        lc += __shfl_xor(lc, o, 64); lk += __shfl_xor(lk, o, 64);
+    }
+    if ((tid & 63) < 16) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int k = 0; k < kOut; ++k) red[wave][c][u * kOut + k] = aw[u][k];
+            red[wave][c][32 + u] = awv[u];
+        }
+    }
+    __shared__ float redb[4][kOut + 1];
+    __shared__ float redl[4][5];
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kOut; ++k) redb[wave][k] = ab[k];
+        redb[wave][kOut] = abv;
+        redl[wave][0] = lp; redl[wave][1] = lv; redl[wave][2] = le;
+        redl[wave][3] = lc; redl[wave][4] = lk;
+    }
+    __syncthreads();
+    float *out = part + ((long long)sp * lay.A + a) * kHbPer;
+    for (int j = tid; j < kHbPer; j += 256) {
+        float acc = 0.f;
+        if (j < kL * kOut) {                       // dWo[jj][k]: jj = 4 c + u
+            const int jj = j / kOut, k = j % kOut;
+            for (int w = 0; w < 4; ++w) acc += red[w][jj >> 2][(jj & 3) * kOut + k];
+        } else if (j < kL * kOut + kOut) {
+            for (int w = 0; w < 4; ++w) acc += redb[w][j - kL * kOut];
+        } else if (j < kL * kOut + kOut + kL) {
+            const int jj = j - (kL * kOut + kOut);
+            for (int w = 0; w < 4; ++w) acc += red[w][jj >> 2][32 + (jj & 3)];
+        } else {
+            for (int w = 0; w < 4; ++w) acc += redb[w][kOut];
+        }
+        out[j] = acc;
+    }
+    if (stats && tid == 0) {     // logging only (policies.py:63-72)
+        double a0 = 0, a1 = 0, a2 = 0;
+        for (int w = 0; w < 4; ++w) { a0 += redl[w][0]; a1 += redl[w][1]; a2 += redl[w][2]; }
+        atomicAdd(&stats[a * 4 + 0], a0); atomicAdd(&stats[a * 4 + 1], a1); atomicAdd(&stats[a * 4 + 2], a2);
+        double a3 = 0, a4 = 0;
+        for (int w = 0; w < 4; ++w) { a3 += redl[w][3]; a4 += redl[w][4]; }
+        atomicAdd(&ppo_stats[a * 2 + 0], a3); atomicAdd(&ppo_stats[a * 2 + 1], a4);
     }
 }
 
@@ -1667,6 +1868,29 @@ __global__ void returns_kernel(const double *rew, const float *val, const uint8_
     }
 }
 
+// GAE(lambda) (Schulman et al. 2016), the sibling of returns_kernel: the same float64 reverse scan per (e, a) over the same
+// normalised / clipped rewards and POST-step dones, with the rollout's stored values and v_T = Rboot:
+//   delta_t = r_t + gamma v_{t+1} (1 - d_{t+1}) - v_t;   A_t = delta_t + gamma lambda (1 - d_{t+1}) A_{t+1};   R_t = A_t + v_t
+__global__ void gae_kernel(const double *rew, const float *val, const uint8_t *done_all, const float *Rboot, int T, int E, int A,
+                           double gamma, double lambda, double rnorm, double rclip, float *Rs, float *Advs) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= E * A) return;
+    const int e = idx / A;
+    double vnext = (double)Rboot[idx], adv = 0.0;
+    for (int t = T - 1; t >= 0; --t) {
+        const double d = (double)done_all[(long long)(t + 1) * E + e];
+        double r = rew[(long long)t * E * A + idx];
+        if (rnorm != 0.0) r = r / rnorm;
+        if (rclip != 0.0) r = fmin(fmax(r, -rclip), rclip);
+        const double v = (double)val[(long long)t * E * A + idx];
+        const double delta = r + gamma * vnext * (1.0 - d) - v;
+        adv = delta + gamma * lambda * (1.0 - d) * adv;
+        Rs[(long long)t * E * A + idx] = (float)(adv + v);
+        Advs[(long long)t * E * A + idx] = (float)adv;
+        vnext = v;
+    }
+}
+
 __global__ void add_transition_kernel(int E, int A, int SMAX, const float *obs, const uint8_t *done_pre,
                                       const int *action, const double *reward, const float *value,
                                       const uint8_t *done_post, float *obs_t,
@@ -2429,6 +2653,8 @@ struct tsc_model {
     // rollout (on-policy buffer)
     float *r_obs; int *r_act; double *r_rew; float *r_val; uint8_t *r_done;   // done [T+1][E]
     float *Rs, *Advs;
+    float *logp_old;            // [T E][A] log(clip(pi_old(a_n), 1e-10, 1)) of the rollout's policy (PPO; allocated by the first PPO update)
+    int ppo_ready;              // epoch 0 of tsc_model_compute_grads_ppo ran on the rollout in the buffer: Rs / Advs / logp_old are its own
     // activations
     float *X1, *Z, *Hh, *Cc, *Hp, *dHh;
     double *norm2, *stats, *norm_part;
@@ -2561,7 +2787,9 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
     MALLOC(m->Z, float, G * N * kG4);
     MALLOC(m->Hh, float, G * N * kL); MALLOC(m->Cc, float, G * N * kL); MALLOC(m->Hp, float, G * N * kL);
     MALLOC(m->dHh, float, G * N * kL);
-    MALLOC(m->norm2, double, A); MALLOC(m->stats, double, A * 4); MALLOC(m->norm_part, double, A * kNormParts);
+    MALLOC(m->norm2, double, A); MALLOC(m->stats, double, A * 6);        // [A][4] losses | [A][2] PPO: clipped share, approximate KL
+    MALLOC(m->norm_part, double, A * kNormParts);
+    m->logp_old = nullptr; m->ppo_ready = 0;
     m->ws_floats = (size_t)48 << 20; m->wsc_floats = (size_t)1 << 20;      // 192 MiB + 4 MiB
     MALLOC(m->ws, float, m->ws_floats); MALLOC(m->wsc, float, m->wsc_floats);
     m->lds_fwd = sizeof(float) * (64 * kWhLd + 64 * kHsLd);
@@ -2663,6 +2891,7 @@ int tsc_model_layout(tsc_model *m, int64_t out[12]) {
 int tsc_model_set_params(tsc_model *m, const float *h) {
     if (!m || !h) return tsc::fail("tsc_model_set_params: bad arguments");
     m->cached_next = -1;                              // activations cached under the old parameters are stale
+    m->ppo_ready = 0;                                 // ... and so is logp_old: a PPO epoch > 0 needs a new epoch 0
     m->wg_dirty = 1;
     TSC_HIP(hipStreamSynchronize(m->stream));
     TSC_HIP(hipMemcpy(m->params, h, sizeof(float) * m->nparam, hipMemcpyHostToDevice));
@@ -2699,6 +2928,7 @@ int tsc_model_reset(tsc_model *m) {
     const size_t b = sizeof(float) * (size_t)m->lay.G * m->E * 2 * kL;
     TSC_HIP(hipMemsetAsync(m->state_fw, 0, b, m->stream));
     TSC_HIP(hipMemsetAsync(m->state_bw, 0, b, m->stream));
+    m->ppo_ready = 0;                                 // the re-forward of a PPO epoch > 0 would start from another state than epoch 0 did
     return 0;
 }
 
@@ -2843,7 +3073,10 @@ int tsc_model_add_transition(tsc_model *m, int32_t t, const float *obs, const ui
     return 0;
 }
 
-static int launch_head_bwd(tsc_model *m, long long N, double beta) {
+// The PPO arguments of an update (tsc_model_compute_grads_ppo); null = the A2C update.
+struct PpoArgs { double clip_eps, lambda; int epoch; };
+
+static int launch_head_bwd(tsc_model *m, long long N, double beta, const PpoArgs *ppo) {
     const Layout &L = m->lay;
     hipStream_t st = m->stream;
     int S = (int)((8 * 256 + L.A - 1) / L.A);        // ~8 workgroups per CU
@@ -2851,7 +3084,12 @@ static int launch_head_bwd(tsc_model *m, long long N, double beta) {
     rps = (rps + 15) / 16 * 16;
     S = (int)((N + rps - 1) / rps);
     if ((size_t)((long long)S * L.A * kHbPer) > m->ws_floats) return tsc::fail("head_bwd: workspace too small");
-    {
+    if (ppo) {
+        tsc::ProfScope ps7(tsc::KID_HEAD_BWD_PPO, m->stream);
+        hipLaunchKernelGGL(head_bwd_ppo_kernel, dim3((unsigned)S, (unsigned)L.A), dim3(256), 0, st, m->params, L, m->n_act, m->Hh, m->r_act,
+                           m->Rs, m->Advs, N, rps, (float)m->vcoef, (float)beta, m->dHh, m->ws, m->stats, m->logp_old,
+                           ppo->epoch == 0 ? 1 : 0, (float)ppo->clip_eps, m->stats + 4 * L.A);
+    } else {
         tsc::ProfScope ps7(tsc::KID_HEAD_BWD, m->stream);
         hipLaunchKernelGGL(head_bwd2_kernel, dim3((unsigned)S, (unsigned)L.A), dim3(256), 0, st, m->params, L, m->n_act, m->Hh, m->r_act,
                            m->Rs, m->Advs, N, rps, (float)m->vcoef, (float)beta, m->dHh, m->ws, m->stats);
@@ -2878,24 +3116,31 @@ int tsc_model_rollout_slot(tsc_model *m, int32_t t, void *ptrs[6]) {
     return 0;
 }
 
-int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
-    if (!m || !R_boot) return tsc::fail("tsc_model_compute_grads: bad arguments");
+// The update's first half.  ppo == null: the A2C update.  Otherwise epoch ppo->epoch of a PPO update: the returns / advantages are
+// taken at epoch 0 only (from the rollout's stored values), epoch 0 reads the rollout's activation cache when it is valid, and every
+// later epoch finds the cache consumed (cached_next == 0) and takes the re-forward branch from state_bw with the current parameters.
+static int compute_grads_impl(tsc_model *m, const float *R_boot, double beta, const PpoArgs *ppo) {
     const Layout &L = m->lay;
     const Plan &P = m->plan;
     const long long E = m->E, T = m->T, N = E * T, A = L.A, G = L.G;
     const int AS = L.A * L.SMAX, S = P.s_upd;
     hipStream_t st = m->stream;
-    TSC_HIP(hipMemsetAsync(m->stats, 0, sizeof(double) * A * 4, st));
-    tsc::ProfScope ps6(tsc::KID_RETURNS, m->stream);
-    hipLaunchKernelGGL(returns_kernel, dim3((unsigned)((E * A + 255) / 256)), dim3(256), 0, st, m->r_rew, m->r_val, m->r_done,
-                       R_boot, (int)T, (int)E, (int)A, m->gamma, m->rnorm, m->rclip, m->Rs, m->Advs);
-    ps6.stop();
+    TSC_HIP(hipMemsetAsync(m->stats, 0, sizeof(double) * A * (ppo ? 6 : 4), st));
+    if (!ppo || (ppo->epoch == 0 && ppo->lambda == 1.0)) {
+        tsc::ProfScope ps6(tsc::KID_RETURNS, m->stream);
+        hipLaunchKernelGGL(returns_kernel, dim3((unsigned)((E * A + 255) / 256)), dim3(256), 0, st, m->r_rew, m->r_val, m->r_done,
+                           R_boot, (int)T, (int)E, (int)A, m->gamma, m->rnorm, m->rclip, m->Rs, m->Advs);
+    } else if (ppo->epoch == 0) {
+        tsc::ProfScope ps6(tsc::KID_GAE, m->stream);
+        hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((E * A + 255) / 256)), dim3(256), 0, st, m->r_rew, m->r_val, m->r_done, R_boot,
+                           (int)T, (int)E, (int)A, m->gamma, ppo->lambda, m->rnorm, m->rclip, m->Rs, m->Advs);
+    }
     float *g = m->grads;
     if (L.fc) {
         // FcACPolicy (agents/policies.py:214-256): Hh = relu(X1 Wfc + bfc); dZ = dH * (Hh > 0) comes out of head_bwd
         // (skipped when the rollout forward cached X1 / Hh of all n_step slots under these very parameters)
         if (m->cached_next != (int)T && dense_forward(m, m->r_obs, N, m->X1, m->Hh)) return tsc::fail("gemm launch failed");
-        if (launch_head_bwd(m, N, beta)) return tsc::fail("head_bwd failed");       // + dWo, dbo
+        if (launch_head_bwd(m, N, beta, ppo)) return tsc::fail("head_bwd failed");       // + dWo, dbo
         tsc::ProfScope ps9(tsc::KID_TRANSPOSE, m->stream);
         hipLaunchKernelGGL(transpose_wx_kernel, dim3((unsigned)((G * L.H * L.NZ + 255) / 256)), dim3(256), 0, st, m->params, L, m->WxT);
         ps9.stop();
@@ -2937,7 +3182,7 @@ int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
                            m->Z, m->state_bw, (float *)nullptr, m->Hh, m->Cc, m->Hp, m->r_done, (int)T, (int)E, 1);
         ps2.stop();
     }
-    if (launch_head_bwd(m, N, beta)) return tsc::fail("head_bwd failed");           // + dWo, dbo
+    if (launch_head_bwd(m, N, beta, ppo)) return tsc::fail("head_bwd failed");           // + dWo, dbo
     tsc::ProfScope ps8(tsc::KID_LSTM_BWD, m->stream);
     hipLaunchKernelGGL(lstm_bwd2_kernel, dim3((unsigned)G, (unsigned)((E + 31) / 32)), dim3(256), sizeof(float) * 32 * (kDz2Ld + kDh3Ld), st,
                        m->params, L, m->Z, m->Cc, m->state_bw, m->dHh, m->r_done, (int)T, (int)E);
@@ -3004,6 +3249,36 @@ int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
     return 0;
 }
 
+int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {
+    if (!m || !R_boot) return tsc::fail("tsc_model_compute_grads: bad arguments");
+    m->ppo_ready = 0;                                 // Rs / Advs become the n-step ones: no PPO epoch > 0 may follow on them
+    return compute_grads_impl(m, R_boot, beta, nullptr);
+}
+
+int tsc_model_compute_grads_ppo(tsc_model *m, const float *R_boot, double beta, double clip_eps, double gae_lambda, int32_t epoch) {
+    if (!m || epoch < 0 || (epoch == 0 && !R_boot)) return tsc::fail("tsc_model_compute_grads_ppo: bad arguments");
+    if (!(clip_eps > 0.0)) return tsc::fail("tsc_model_compute_grads_ppo: clip_eps %g must be positive", clip_eps);
+    if (!(gae_lambda > 0.0 && gae_lambda <= 1.0)) return tsc::fail("tsc_model_compute_grads_ppo: gae_lambda %g outside (0, 1]", gae_lambda);
+    if (epoch > 0 && !m->ppo_ready)
+        return tsc::fail("tsc_model_compute_grads_ppo: epoch %d without epoch 0 on this rollout (advantages and logp_old are taken there)", epoch);
+    if (!m->logp_old) {
+        TSC_HIP(hipSetDevice(m->device));
+        MALLOC(m->logp_old, float, (size_t)m->T * m->E * m->lay.A);
+    }
+    const PpoArgs ppo = {clip_eps, gae_lambda, epoch};
+    if (epoch == 0) m->ppo_ready = 0;                 // until this epoch 0 is through
+    if (compute_grads_impl(m, R_boot, beta, &ppo)) return 1;
+    m->ppo_ready = 1;
+    return 0;
+}
+
+int tsc_model_ppo_stats(tsc_model *m, double *out_host) {
+    if (!m || !out_host) return tsc::fail("tsc_model_ppo_stats: bad arguments");
+    TSC_HIP(hipStreamSynchronize(m->stream));
+    TSC_HIP(hipMemcpy(out_host, m->stats + 4 * m->lay.A, sizeof(double) * 2 * m->lay.A, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int tsc_model_grad_buffer(tsc_model *m, float **grad, int64_t *count) {
     if (!m || !grad || !count) return tsc::fail("tsc_model_grad_buffer: bad arguments");
     *grad = m->grads; *count = m->nparam;
@@ -3011,6 +3286,10 @@ int tsc_model_grad_buffer(tsc_model *m, float **grad, int64_t *count) {
 }
 
 int tsc_model_apply_grads(tsc_model *m, double lr, double grad_scale, double *stats_host) {
+    return tsc_model_apply_grads_ex(m, lr, grad_scale, stats_host, 1);
+}
+
+int tsc_model_apply_grads_ex(tsc_model *m, double lr, double grad_scale, double *stats_host, int32_t end_of_rollout) {
     if (!m) return tsc::fail("null handle");
     const Layout &L = m->lay;
     const long long per_agent = 2 * L.stride;
@@ -3026,6 +3305,9 @@ int tsc_model_apply_grads(tsc_model *m, double lr, double grad_scale, double *st
     ps11.stop();
     m->wg_dirty = 1;
     TSC_HIP(hipGetLastError());
+    // The end-of-rollout bookkeeping.  A PPO epoch that is not the last one leaves all three alone: the next epoch's re-forward
+    // starts from state_bw over obs[0 .. T) and done[0 .. T) of THIS rollout.
+    if (end_of_rollout) {
     // states_bw <- states_fw (policies.py:153); buffer.reset(dones[-1]) (utils.py:227)
     TSC_HIP(hipMemcpyAsync(m->state_bw, m->state_fw, sizeof(float) * (size_t)L.G * m->E * 2 * kL, hipMemcpyDeviceToDevice, st));
     TSC_HIP(hipMemcpyAsync(m->r_done, m->r_done + (size_t)m->T * m->E, m->E, hipMemcpyDeviceToDevice, st));
@@ -3034,6 +3316,8 @@ int tsc_model_apply_grads(tsc_model *m, double lr, double grad_scale, double *st
     if (m->inplace)
         TSC_HIP(hipMemcpyAsync(m->r_obs, m->r_obs + (size_t)m->T * m->E * L.A * L.SMAX, sizeof(float) * (size_t)m->E * L.A * L.SMAX,
                                hipMemcpyDeviceToDevice, st));
+    m->ppo_ready = 0;
+    }
     if (stats_host) {
         std::vector<double> s(L.A * 4), n2(L.A);
         TSC_HIP(hipStreamSynchronize(st));

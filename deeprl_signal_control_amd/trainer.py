@@ -323,25 +323,29 @@ class MultiBatchTrainer:
         for p, st, s in zip(self.parts, self.streams, state):
             with torch.cuda.stream(st):
                 p.ob, p.done = s['ob'], s['done']
-                R = p.zero_R if s['fin'] else p.model.forward(s['ob'], False, 'v')
-                p.model.compute_grads(R)
-        # gradient exchange between the half-batches (and, with several GPUs, between ranks)
-        g0 = self.models[0].grad_tensor()
-        main = self.streams[0]
-        for m, st in zip(self.models[1:], self.streams[1:]):
-            main.wait_stream(st)
-        with torch.cuda.stream(main):
-            for m in self.models[1:]:
-                g0.add_(m.grad_tensor())
-            scale = 1.0 / len(self.models)
-            if torch.distributed.is_available() and torch.distributed.is_initialized():
-                from .agents import allreduce_grads_
-                scale *= allreduce_grads_(g0, self.models[0].pg)
-            for m in self.models[1:]:
-                m.grad_tensor().copy_(g0)
-        for st in self.streams[1:]:
-            st.wait_stream(main)
-        self._each(lambda p: p.model.apply_grads(scale))
+                s['R'] = p.zero_R if s['fin'] else p.model.forward(s['ob'], False, 'v')
+        # one update per rollout; algo = ppo: n_epoch of them over the same rollouts, the replicas exchanging every epoch's gradient
+        for epoch in range(self.models[0].n_epoch):
+            for p, st, s in zip(self.parts, self.streams, state):
+                with torch.cuda.stream(st):
+                    p.model.compute_grads(s['R'], epoch)
+            # gradient exchange between the half-batches (and, with several GPUs, between ranks)
+            g0 = self.models[0].grad_tensor()
+            main = self.streams[0]
+            for m, st in zip(self.models[1:], self.streams[1:]):
+                main.wait_stream(st)
+            with torch.cuda.stream(main):
+                for m in self.models[1:]:
+                    g0.add_(m.grad_tensor())
+                scale = 1.0 / len(self.models)
+                if torch.distributed.is_available() and torch.distributed.is_initialized():
+                    from .agents import allreduce_grads_
+                    scale *= allreduce_grads_(g0, self.models[0].pg)
+                for m in self.models[1:]:
+                    m.grad_tensor().copy_(g0)
+            for st in self.streams[1:]:
+                st.wait_stream(main)
+            self._each(lambda p: p.model.apply_grads(scale, epoch=epoch))
         if finished:
             def restart(p):
                 p.env.terminate()

@@ -99,7 +99,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -355,6 +355,36 @@ int tsc_model_grad_buffer(tsc_model *m, float **grad_dev, int64_t *count);
  * buffer reset carrying the last done (utils.py:227).  stats_host (nullable): per agent
  * {policy_loss, value_loss, entropy_loss, grad_norm} float64 [A,4]. */
 int tsc_model_apply_grads(tsc_model *m, double lr, double grad_scale, double *stats_host);
+
+/* The PPO update (opt-in; no reference counterpart: the reference takes one RMSProp step per rollout): K epochs over the rollout in
+ * the buffer under the clipped surrogate (Schulman et al. 2017) with GAE(lambda) advantages (Schulman et al. 2016).  Epoch k of a
+ * rollout is  tsc_model_compute_grads_ppo(.., epoch = k) -> [all-reduce of the gradient buffer] -> tsc_model_apply_grads_ex(..,
+ * end_of_rollout = (k == K - 1)).
+ *   epoch 0: advantages and returns from the rollout's stored values, once per rollout -- gae_lambda = 1: the n-step returns of
+ *     tsc_model_compute_grads, bit for bit; otherwise, in float64 with r the normalised / clipped reward, d the POST-step done and
+ *     v_T = R_boot:  delta_t = r_t + gamma v_{t+1} (1 - d_{t+1}) - v_t,  A_t = delta_t + gamma lambda (1 - d_{t+1}) A_{t+1},
+ *     R_t = A_t + v_t, both cast to float32; no advantage normalisation.  The epoch also records logp_old[n][a] =
+ *     log(clip(pi(a_n), 1e-10, 1)) (float32 [n_step * E][A], allocated by the first call).  The parameters are the rollout's, so
+ *     ratio = 1 and the gradient is that of tsc_model_compute_grads; the rollout's activation cache is used when it is valid.
+ *   epoch k > 0: re-evaluates the forward from the saved backward state over the stored obs / done with the CURRENT parameters
+ *     (the LSTM start state stays the rollout-time one); R_boot is ignored (may be null).  Fails (tsc_last_error) unless epoch 0
+ *     ran on the same rollout, i.e. since the last end-of-rollout apply, tsc_model_compute_grads, tsc_model_reset or
+ *     tsc_model_set_params (each of them invalidates the advantages, the start state or logp_old of the rollout).
+ *   loss, per agent over its N = n_step * E samples:  -mean(min(ratio A, clip(ratio, 1 - clip_eps, 1 + clip_eps) A))
+ *     + 0.5 value_coef mean((R - v)^2) - entropy_beta mean(entropy),  ratio = exp(logp - logp_old); value and entropy terms as in
+ *     tsc_model_compute_grads, with the current parameters.  A sample's policy gradient is -A ratio / N through logp, and zero
+ *     where the clipped branch is the smaller one (A > 0 and ratio > 1 + clip_eps, or A < 0 and ratio < 1 - clip_eps) or pi is
+ *     below the 1e-10 clamp.  No minibatches, no value clipping, no KL early stopping.
+ * clip_eps > 0, 0 < gae_lambda <= 1.  stats_host of the following apply: policy_loss is the surrogate term. */
+int tsc_model_compute_grads_ppo(tsc_model *m, const float *R_boot_dev, double entropy_beta, double clip_eps, double gae_lambda,
+                                int32_t epoch);
+/* tsc_model_apply_grads with the end-of-rollout bookkeeping (states_bw <- states_fw, done[0] <- done[n_step], obs[0] <-
+ * obs[n_step] of a zero-copy rollout) only when end_of_rollout != 0: a PPO epoch that is not the last one must leave them
+ * alone, the next epoch's re-forward reads all three.  tsc_model_apply_grads is the end_of_rollout = 1 case. */
+int tsc_model_apply_grads_ex(tsc_model *m, double lr, double grad_scale, double *stats_host, int32_t end_of_rollout);
+/* Per agent, of the last tsc_model_compute_grads_ppo: {share of the samples whose policy gradient the clip removed,
+ * mean(logp_old - logp) (the approximate KL divergence from the rollout's policy)} float64 [A,2].  Host pointer.  Synchronises. */
+int tsc_model_ppo_stats(tsc_model *m, double *out_host);
 
 /* Tuning aid for the fused rollout forward: like tsc_env_debug_clock (phase stamps of one workgroup in
  * [0,63), per-workgroup 100 MHz start / end from index 64). */

@@ -1,0 +1,216 @@
+"""Float64 restatement of the opt-in PPO update (include/tsc.h tsc_model_compute_grads_ppo) -- TEST INFRASTRUCTURE ONLY, never
+the code under test.  PPOOracle extends oracle.nets_oracle.OracleA2C (its towers, buffer, n-step returns, clip + RMSProp) with
+
+  * GAE(lambda) advantages from the rollout's stored values, taken once per rollout at epoch 0 (lambda = 1: returns_advs itself);
+  * logp_old = log(clip(pi_old(a_n), 1e-10, 1)), recorded at epoch 0;
+  * the clipped surrogate  -mean(min(ratio A, clip(ratio, 1 - eps, 1 + eps) A)),  ratio = exp(logp - logp_old), next to the value
+    and entropy terms of OracleA2C.compute_grads, all through torch float64 autograd;
+  * epochs: every epoch re-evaluates the towers from s_bw with the current parameters; the end-of-rollout bookkeeping of
+    apply_grads (s_bw <- s_fw, buffer reset) happens only when the caller says so.
+
+For the parity tests it also reports, per epoch, the clipped share, the approximate KL, and the AMBIGUOUS samples: those whose
+float64 ratio lies within relative 1e-4 of the bound that applies for the sign of their advantage (a float32 evaluation may
+land on the other side of the bound, like a hidden unit on a ReLU kink), with each one's absolute contribution to every
+gradient entry (`amb_slack`, same structure as the gradients)."""
+import numpy as np
+import torch
+
+from oracle.nets_oracle import OracleA2C, t64, to_torch, tower
+
+AMBIGUOUS_REL = 1e-4
+
+
+class PPOOracle(OracleA2C):
+    def __init__(self, *args, clip_eps=0.2, gae_lambda=0.95, **kw):
+        super().__init__(*args, **kw)
+        self.clip_eps, self.lam = float(clip_eps), float(gae_lambda)
+        self.logp_old = None
+
+    @staticmethod
+    def gae(rs, vs, dones, R, gamma, lam):
+        """rs, vs [T,...] float64 (rs normalised / clipped), dones [T+1,...] (index t + 1 = post-step done), R = v_T.
+        -> (Rs, Advs) float32.  lam = 1 is OracleA2C.returns_advs (the same arithmetic as the n-step recursion)."""
+        if lam == 1.0:
+            return OracleA2C.returns_advs(rs, vs, dones, R, gamma)
+        T = len(rs)
+        Rs, Advs = [None] * T, [None] * T
+        vnext, adv = np.asarray(R, np.float64), 0.0
+        for t in range(T - 1, -1, -1):
+            nd = 1. - dones[t + 1]
+            delta = rs[t] + gamma * vnext * nd - vs[t]
+            adv = delta + gamma * lam * nd * adv
+            Rs[t], Advs[t] = adv + vs[t], adv
+            vnext = vs[t]
+        return np.array(Rs, np.float64).astype(np.float32), np.array(Advs, np.float64).astype(np.float32)
+
+    def _kinks(self, obs):
+        """OracleA2C.compute_grads' ReLU-kink columns (|pre-activation| < 1e-5 for some sample) under the current parameters."""
+        out = []
+        with torch.no_grad():
+            for g_, p in enumerate(self.p):
+                a = g_ // 2
+                ob = self._ob(obs, a)
+                nw, nt, nf = self.nw[a], self.nt[a], self.nf[a]
+                parts = [('fcw', ob[..., :nw])]
+                if nf:
+                    parts.append(('fcf', ob[..., nw + nt:nw + nt + nf]))
+                if nt:
+                    parts.append(('fct', ob[..., nw:nw + nt]))
+                kc, hs = {}, []
+                for name, x in parts:
+                    z = x @ p[name + '_w'] + p[name + '_b']
+                    kc[name] = (z.abs() < 1e-5).reshape(-1, z.shape[-1]).any(0).numpy()
+                    hs.append(torch.relu(z))
+                if 'fc_w' in p:
+                    z = torch.cat(hs, -1) @ p['fc_w'] + p['fc_b']
+                    kc['fc'] = (z.abs() < 1e-5).reshape(-1, z.shape[-1]).any(0).numpy()
+                out.append(kc)
+        return out
+
+    def compute_grads(self, R_boot, beta, epoch=0, slack=True):
+        """Epoch `epoch` of the rollout in the buffer -> (grads list[2A] of dicts, stats [A,3] = surrogate / value / entropy loss).
+        Also sets Rs, Advs (epoch 0), kink_cols, clip_share [A], approx_kl [A], amb_share [A] and -- with slack -- amb_slack."""
+        b = self.buf
+        T = len(b['obs'])
+        obs = np.stack(b['obs'])
+        dones = np.stack(b['dones'])
+        if epoch == 0:
+            dpost = dones[:, :, None] * np.ones((1, 1, self.A))
+            self.Rs, self.Advs = self.gae(np.stack(b['rs']), np.stack(b['vs']), dpost, R_boot, self.gamma, self.lam)
+            self.logp_old = [None] * self.A
+        else:
+            assert self.logp_old is not None and self.logp_old[0] is not None, 'epoch > 0 needs epoch 0 on the same rollout'
+        acts = np.stack(b['acts'])
+        dpre = t64(dones[:-1])
+        N = T * self.E
+        eps = self.clip_eps
+        P = to_torch([{k: v.numpy() for k, v in p.items()} for p in self.p], requires_grad=True)
+        self.kink_cols = self._kinks(obs)
+        stats, self.clip_share, self.approx_kl, self.amb_share = [], [], [], []
+        self.amb_slack = [{k: torch.zeros_like(v) for k, v in p.items()} for p in self.p]
+        for a in range(self.A):
+            ob = self._ob(obs, a)
+            lo, _ = tower(P[2 * a], ob, dpre, self.s_bw[2 * a], self.nw[a], self.nt[a], self.nf[a])
+            vo, _ = tower(P[2 * a + 1], ob, dpre, self.s_bw[2 * a + 1], self.nw[a], self.nt[a], self.nf[a])
+            pi = torch.softmax(lo, -1).reshape(N, -1)
+            v = vo.reshape(N)
+            A_ = torch.as_tensor(acts[:, :, a].reshape(-1), dtype=torch.long)
+            ADV, R = t64(self.Advs[:, :, a].reshape(-1)), t64(self.Rs[:, :, a].reshape(-1))
+            log_pi = torch.log(torch.clamp(pi, 1e-10, 1.0))
+            logp = log_pi.gather(1, A_[:, None])[:, 0]
+            if epoch == 0:
+                self.logp_old[a] = logp.detach().clone()
+            lpo = self.logp_old[a]
+            ratio = torch.exp(logp - lpo)
+            rd = ratio.detach()
+            clipped = ((ADV > 0) & (rd > 1 + eps)) | ((ADV < 0) & (rd < 1 - eps))
+            # min(ratio A, clip(ratio) A): where the clipped branch is the smaller one it is a constant, elsewhere it is ratio A
+            surr = torch.where(clipped, torch.clamp(rd, 1 - eps, 1 + eps) * ADV, ratio * ADV)
+            assert torch.equal(surr.detach(), torch.minimum(rd * ADV, torch.clamp(rd, 1 - eps, 1 + eps) * ADV))
+            policy_loss = -surr.mean()
+            entropy = -(pi * log_pi).sum(1)
+            entropy_loss = -entropy.mean() * beta
+            value_loss = ((R - v) ** 2).mean() * 0.5 * self.vcoef
+            (policy_loss + value_loss + entropy_loss).backward()
+            stats.append([policy_loss.item(), value_loss.item(), entropy_loss.item()])
+            self.clip_share.append(clipped.double().mean().item())
+            self.approx_kl.append((lpo - logp.detach()).mean().item())
+            bound = torch.where(ADV > 0, torch.full_like(rd, 1 + eps), torch.full_like(rd, 1 - eps))
+            amb = (ADV != 0) & ((rd - bound).abs() <= AMBIGUOUS_REL * bound)
+            self.amb_share.append(amb.double().mean().item())
+            if slack:
+                for n in torch.nonzero(amb)[:, 0].tolist():
+                    self._add_slack(a, n, obs, dones, acts, N)
+        grads = [{k: (v.grad if v.grad is not None else torch.zeros_like(v)).detach() for k, v in q.items()} for q in P]
+        self.clip_share, self.approx_kl, self.amb_share = map(np.array, (self.clip_share, self.approx_kl, self.amb_share))
+        return grads, np.array(stats)
+
+    def _add_slack(self, a, n, obs, dones, acts, N):
+        """|d(-A ratio / N)/d theta| of sample n = t E + e of agent a, added to amb_slack of its pi tower: what the gradient moves
+        by if a float32 evaluation puts the sample on the other side of its clip bound.  The towers are per-instance, so only
+        instance e is evaluated."""
+        t, e = divmod(n, self.E)
+        q = {k: v.detach().clone().requires_grad_(True) for k, v in self.p[2 * a].items()}
+        ob = self._ob(obs[:, e:e + 1], a)
+        lo, _ = tower(q, ob, t64(dones[:-1, e:e + 1]), self.s_bw[2 * a][e:e + 1], self.nw[a], self.nt[a], self.nf[a])
+        logp = torch.log(torch.clamp(torch.softmax(lo[t, 0], -1), 1e-10, 1.0))[int(acts[t, e, a])]
+        term = -float(self.Advs[t, e, a]) * torch.exp(logp - self.logp_old[a][n]) / N
+        term.backward()
+        for k, v in q.items():
+            if v.grad is not None:
+                self.amb_slack[2 * a][k] += v.grad.abs()
+
+    def apply_grads(self, grads, lr, grad_scale=1.0, end_of_rollout=True):
+        """OracleA2C.apply_grads; an epoch that is not the rollout's last keeps s_bw and the buffer for the next one."""
+        keep = (self.s_bw, self.buf)
+        norms = super().apply_grads(grads, lr, grad_scale)
+        if not end_of_rollout:
+            self.s_bw, self.buf = keep
+        else:
+            self.logp_old = None
+        return norms
+
+
+# ---- shared fixtures of tests/test_ppo_oracle.py (CPU) and tests/test_ppo_gpu.py ------------------------------------------------
+def make_oracle(scn, agent, policy, E, seed, clip_eps=0.2, gae_lambda=0.95, cfg=None, towers=None, sel=None):
+    """PPOOracle over the towers VecA2C(seed=seed) starts from (agents.init_tower_params with RandomState(seed)), or over
+    `towers`; sel = the agents to keep (the benchmarked shape affords three)."""
+    from deeprl_signal_control_amd.agents import A2C_DEFAULTS, init_tower_params
+    c = dict(A2C_DEFAULTS)
+    c.update(cfg or {})
+    n_f = list(scn.n_f_ls) if agent == 'ma2c' else [0] * scn.n_agent
+    n_wave = [s - w - f for s, w, f in zip(scn.n_s_ls, scn.n_w_ls, n_f)]
+    n_fc = (int(c['num_fw']), int(c['num_fp']) if agent == 'ma2c' else 0, int(c['num_ft']) if max(scn.n_w_ls) > 0 else 0)
+    if towers is None:
+        towers = init_tower_params(n_wave, scn.n_w_ls, n_f, scn.n_a_ls, n_fc, int(c['num_lstm']), policy, np.random.RandomState(seed))
+    sel = list(range(scn.n_agent)) if sel is None else list(sel)
+    pick = lambda ls: [ls[a] for a in sel]                                  # noqa: E731
+    return PPOOracle([towers[2 * a + k] for a in sel for k in (0, 1)], pick(n_wave), pick(scn.n_w_ls), pick(n_f), pick(scn.n_a_ls), E,
+                     gamma=c['gamma'], reward_norm=c['reward_norm'], reward_clip=c['reward_clip'], value_coef=c['value_coef'],
+                     max_grad_norm=c['max_grad_norm'], clip_eps=clip_eps, gae_lambda=gae_lambda)
+
+
+def rand_obs(scn, E, rng):
+    obs = np.zeros((E, scn.n_agent, scn.s_max), np.float32)
+    for a, n in enumerate(scn.n_s_ls):
+        obs[:, a, :n] = rng.rand(E, n).astype(np.float32) * 2
+    return obs
+
+
+def fill(scn, o, E, T, rng, reward_norm, obs=None, done=None, p_done=0.1, done_at=(), put=None, sel=None):
+    """One rollout of random observations, uniform random actions and rewards in [-3 reward_norm, 0] into the oracle -- and, through
+    put(t, obs, done, act, rew, dpost) -> v [E,A] float32, into the code under test, whose forward then supplies the stored values
+    (without it the oracle's own, rounded to float32).  done_at: steps whose post-step done is 1 for every instance (terminal
+    steps in the middle / at the end of the window).  Returns (next obs, carried done)."""
+    sel = list(range(scn.n_agent)) if sel is None else list(sel)
+    obs = rand_obs(scn, E, rng) if obs is None else obs
+    done = np.ones(E, np.uint8) if done is None else done
+    for t in range(T):
+        act = np.stack([rng.randint(0, n, E) for n in scn.n_a_ls], 1).astype(np.int32)
+        rew = -rng.rand(E, scn.n_agent) * 3.0 * reward_norm
+        dpost = (rng.rand(E) < p_done).astype(np.uint8)
+        if t in done_at:
+            dpost[:] = 1
+        _, ov = o.forward(obs[:, sel], done, 'pv')
+        v = put(t, obs, done, act, rew, dpost) if put is not None else ov.astype(np.float32)
+        o.add_transition(obs[:, sel], done, act[:, sel], rew[:, sel], v[:, sel] if put is not None else v, dpost)
+        obs, done = rand_obs(scn, E, rng), dpost
+    return obs, done
+
+
+# K = 3 parity cases (tests/test_ppo_gpu.py::test_k3_epochs_match_oracle; the oracle-only conditions are also pinned without a
+# GPU by tests/test_ppo_oracle.py): (agent, policy, E, T, oracle / init seed, rollout seed, lr).  Chosen on the CPU so that the
+# clipped share of all samples at epochs 1 and 2 lies in [5 %, 50 %] and the ambiguous share is at most 0.5 %.
+K3_SMALL = [('ma2c', 'lstm', 16, 8, 5, 7, 5e-2), ('ia2c', 'lstm', 16, 8, 5, 7, 5e-2),
+            ('ma2c', 'fc', 16, 8, 5, 7, 5e-3), ('ia2c', 'fc', 16, 8, 5, 7, 5e-3)]
+K3_REWARD_NORM = 2000.0
+
+
+def k3_conditions(o, epoch):
+    """The oracle-only preconditions of the K = 3 comparison at this epoch: -> (clipped share, ambiguous share) over all samples
+    of all agents (every agent has the same number of samples)."""
+    clip, amb = float(o.clip_share.mean()), float(o.amb_share.mean())
+    if epoch >= 1:
+        assert 0.05 <= clip <= 0.50, 'epoch %d: clipped share %.3f outside [5 %%, 50 %%]: the clip branch is not exercised' % (epoch, clip)
+    assert amb <= 0.005, 'epoch %d: %.4f of the samples sit on a clip bound' % (epoch, amb)
+    return clip, amb

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Time the A2C update's kernels alone (no simulator): fill one rollout of the benchmark shape through the fused forward
 (random observations, E env instances, T = n_step), then run compute_grads `--reps` times with HIP-event timing on.
-    python tools/bench_update.py [--envs 1024] [--agent ma2c] [--reps 3]
+    python tools/bench_update.py [--envs 1024] [--agent ma2c] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]]
+--algo ppo times `--ppo-epochs` epochs per rollout and also prints the wall time (stream-synchronised, profiling off) of an epoch-0
+update and of a later epoch (re-forward + update); --algo a2c prints the wall time of its one update the same way.
 Environment knobs of the library (TSC_UNFUSED_DW, TSC_UNFUSED_DX) select kernel variants for A/B runs."""
 import argparse
 import os
@@ -19,6 +21,9 @@ def main():
     ap.add_argument('--agent', default='ma2c')
     ap.add_argument('--scenario', default='large_grid')
     ap.add_argument('--reps', type=int, default=3)
+    ap.add_argument('--algo', default='a2c', choices=['a2c', 'ppo'])
+    ap.add_argument('--ppo-epochs', type=int, default=2)
+    ap.add_argument('--json', action='store_true', help='one JSON line with the wall times (ms) of the updates, per epoch index')
     args = ap.parse_args()
     from deeprl_signal_control_amd import _lib
     from deeprl_signal_control_amd.agents import VecA2C
@@ -26,7 +31,8 @@ def main():
     scn = build_scenario(args.scenario, args.agent)
     T = 120 if args.scenario == 'large_grid' else 40
     m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, args.envs, scn.s_max, int(scn.green_tab.shape[1]),
-               dict(batch_size=T), device=0, seed=0, name=args.agent)
+               dict(batch_size=T, **(dict(algo='ppo', ppo_epochs=args.ppo_epochs) if args.algo == 'ppo' else {})), device=0, seed=0,
+               name=args.agent)
     sl = m.rollout_slots()
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     out = {}
@@ -55,6 +61,35 @@ def main():
         tot += per
         print('%-18s %8.3f ms per update  (%d launches)' % (k, per, cnt))
     print('%-18s %8.3f ms' % ('update total', tot))
+
+    # wall time per update without the event pairs: epoch by epoch, the stream drained before and after
+    import json
+    import time
+    # (getattr: the file also runs against a checkout from before `algo` existed, for A/B runs of the A2C update across commits)
+    n_epoch = getattr(m, 'n_epoch', 1)
+    wall = [[] for _ in range(n_epoch)]
+    for rep in range(args.reps):
+        m.reset()
+        sl['obs'].copy_(torch.rand(sl['obs'].shape, generator=g, device='cuda') * 2)
+        sl['done'].zero_(); sl['done'][0].fill_(1)
+        m.cur_t = 0
+        for t in range(T):
+            m.forward_sample(sl['obs'][t], sl['done'][t], v_out=sl['value'][t], action_out=sl['action'][t])
+            m.commit_transition()
+        R = m.forward(sl['obs'][T], False, 'v')
+        for k in range(n_epoch):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if n_epoch > 1 or getattr(m, 'algo', 'a2c') == 'ppo':
+                m.compute_grads(R, k); m.apply_grads(1.0, epoch=k)
+            else:
+                m.compute_grads(R); m.apply_grads(1.0)
+            torch.cuda.synchronize()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+    for k, w in enumerate(wall):
+        print('wall: %s update, epoch %d: %s ms (median %.3f)' % (args.algo, k, ' '.join('%.3f' % x for x in w), float(np.median(w))))
+    if args.json:
+        print(json.dumps(dict(algo=args.algo, envs=args.envs, agent=args.agent, scenario=args.scenario, n_step=T, wall_ms_per_epoch=wall)))
 
 
 if __name__ == '__main__':

@@ -23,7 +23,8 @@ import numpy as np          # noqa: E402
 import torch                # noqa: E402
 
 
-def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, log=None, policy='lstm', scn_kw=None, test_seeds=None):
+def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, log=None, policy='lstm', scn_kw=None, test_seeds=None,
+        algo='a2c', ppo_epochs=None, ppo_clip=None, gae_lambda=None):
     from deeprl_signal_control_amd.agents import VecA2C
     from deeprl_signal_control_amd.env import VecTrafficEnv
     from deeprl_signal_control_amd.scenario import build_scenario
@@ -35,6 +36,8 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
         mcfg, seed0 = dict(reward_norm=1.0, batch_size=40), 42
     if lr is not None:
         mcfg['lr_init'] = lr
+    # the update rule ([MODEL_CONFIG] algo and its keys; unset ones keep agents.PPO_DEFAULTS)
+    mcfg.update({k: v for k, v in dict(algo=algo, ppo_epochs=ppo_epochs, ppo_clip=ppo_clip, gae_lambda=gae_lambda).items() if v is not None})
     env = VecTrafficEnv(scn, n_env, device=0, seed=seed0, **({'test_seeds': tuple(test_seeds)} if test_seeds else {}))
     is_q = agent in ('iqld', 'iqll')
     if is_q:
@@ -89,6 +92,8 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
     ev['greedy'] = [dict(test_id=int(k), avg_reward=float(np.mean(gm[np.arange(n_env) % env.test_num == k]))) for k in range(env.test_num)]
     if log:
         log('greedy controller: %s' % ', '.join('seed %d: %.1f' % (r['test_id'], r['avg_reward']) for r in ev['greedy']))
+    # the update rule in force, defaults resolved (the A2C agents; IQL has none of these)
+    run.algo_in_force = {} if is_q else dict(algo=model.algo, ppo_epochs=model.n_epoch, ppo_clip=model.ppo_clip, gae_lambda=model.gae_lambda)
     env.close(); model.close()
     return rows, ev
 
@@ -103,13 +108,18 @@ def main():
     ap.add_argument('--policy', default='lstm', choices=['lstm', 'fc'], help='fc = FcACPolicy (ia2c only; BASELINE configs[1])')
     ap.add_argument('--lane-change', type=int, default=None, help='large_grid: 1 / 0 = with / without MICROSIM_SPEC.md rule 10 (default: the scenario default)')
     ap.add_argument('--test-seeds', default=None, help='comma-separated evaluation seeds (default: the config\'s test_seeds)')
+    ap.add_argument('--algo', default='a2c', choices=['a2c', 'ppo'], help='update rule of the A2C agents ([MODEL_CONFIG] algo)')
+    ap.add_argument('--ppo-epochs', type=int, default=None, help='algo ppo: epochs per rollout (default 4)')
+    ap.add_argument('--ppo-clip', type=float, default=None, help='algo ppo: clip range of the probability ratio (default 0.2)')
+    ap.add_argument('--gae-lambda', type=float, default=None, help='algo ppo: GAE lambda (default 0.95)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     kw = {} if args.lane_change is None else {'lane_change': bool(args.lane_change)}
     rows, ev = run(args.episodes, args.envs, args.scenario, args.agent, lr=args.lr, log=print, policy=args.policy, scn_kw=kw,
-                   test_seeds=[int(x) for x in args.test_seeds.split(',')] if args.test_seeds else None)
+                   test_seeds=[int(x) for x in args.test_seeds.split(',')] if args.test_seeds else None,
+                   algo=args.algo, ppo_epochs=args.ppo_epochs, ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda)
     first, last = np.mean([r['avg_reward'] for r in rows[:5]]), np.mean([r['avg_reward'] for r in rows[-5:]])
-    out = dict(scenario=args.scenario, agent=args.agent, policy=args.policy, envs=args.envs, episodes=args.episodes, scenario_options=kw,
+    out = dict(scenario=args.scenario, agent=args.agent, policy=args.policy, **run.algo_in_force, envs=args.envs, episodes=args.episodes, scenario_options=kw,
                control_steps_per_episode=rows[0]['step'], first5_mean=first, last5_mean=last, rows=rows, evaluation=ev,
                note='mean over env instances of the per-episode mean global step reward (train_reward.csv avg_reward); '
                     'this repo\'s microsim spec underneath, not SUMO')
