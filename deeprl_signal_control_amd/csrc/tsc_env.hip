@@ -466,6 +466,116 @@ __global__ void __launch_bounds__(256) greedy_kernel(EnvDev P, const float *__re
     action[i] = P.g_action[a * P.GC + arg];
 }
 
+// Tables and state of the max-pressure controller (tsc_env_set_pressure), a kernel argument of their own: EnvDev -- every other
+// kernel's argument -- keeps its layout and size.  Lanes are the scenario's (= the device's, load-sorted) lanes.
+struct PressDev {
+    int n_mov, n_walk;             // movements; lanes that appear in one, as its incoming or its downstream lane
+    int measure, min_green;        // TSC_PRESSURE_*; control steps a chosen phase is held at least
+    const short *walk;             // [n_walk] the walked lanes, ascending
+    const short *mov_of;           // [NL * NR] movement of (lane, route), -1 = none
+    const short *mov_dn;           // [n_mov] index into walk of the movement's downstream lane
+    const int *srv_off;            // [A * PMAX + 1] phase (a, p) serves the movements srv[srv_off[a * PMAX + p] .. srv_off[.. + 1])
+    const short *srv;
+    int *hold;                     // [E][A][2] {cur, age}: the phase being held and the control steps it has been
+};
+constexpr int kPressT = 256;       // threads per instance
+
+// Max-pressure (Varaiya 2013), the rule of INTEGRATION.md "Baseline controllers": with q(vehicle) = 1 (count) or v < kHalt (queue),
+// up(movement) = sum of q over the vehicles on its incoming lane whose route takes the movement, down(lane) = sum of q over ALL
+// vehicles of the lane; the pressure of phase p is the int32 sum over the movements it serves of up - down(downstream lane); the
+// action is the first maximum over p < n_phase, subject to the hold (min_green).  Integers only: the result is exact.
+// One workgroup per instance.  (a) The live records of the walked lanes are visited in one flat (lane, slot) order -- exclusive
+// prefix sum of the lanes' counts in LDS, a record's lane by binary search in it -- so a wavefront loads 64 consecutive live
+// records, contiguous within a lane, and never a dead slot; the sums are LDS integer atomics (addition order cannot change an
+// integer sum).  (b) One thread per (agent, phase) adds up its list.  (c) One thread per agent: argmax, hold, stores.
+// Reads EnvDev, writes only action / pressure / Q.hold.  One call per control step: a call advances the hold state.
+__global__ void __launch_bounds__(kPressT) pressure_kernel(EnvDev P, PressDev Q, int *__restrict__ action, int *__restrict__ pressure) {
+    extern __shared__ int psm[];
+    int *start = psm;                          // [n_walk + 1] flat index of a walked lane's first record
+    int *down = start + Q.n_walk + 1;          // [n_walk]
+    int *up = down + Q.n_walk;                 // [n_mov]
+    int *prs = up + Q.n_mov;                   // [A * PMAX]
+    int *part = prs + P.A * P.PMAX;            // [kPressT] scan scratch
+    const int e = blockIdx.x, t = threadIdx.x;
+    const int *N = P.N + (size_t)e * P.NLP;
+    const float4 *S = P.S + (size_t)e * kCap * P.NLP;
+    const bool queue = Q.measure == TSC_PRESSURE_QUEUE;
+    // counts of this thread's run of walked lanes, their exclusive prefix sum over the workgroup
+    const int chunk = (Q.n_walk + kPressT - 1) / kPressT, w0 = t * chunk;
+    int local = 0;
+    for (int w = w0; w < w0 + chunk && w < Q.n_walk; ++w) {
+        const int n = N[Q.walk[w]];
+        local += n < 0 ? 0 : n > kCap ? kCap : n;
+    }
+    part[t] = local;
+    __syncthreads();
+    for (int d = 1; d < kPressT; d <<= 1) {
+        const int v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - local;
+    for (int w = w0; w < w0 + chunk && w < Q.n_walk; ++w) {
+        int n = N[Q.walk[w]];
+        n = n < 0 ? 0 : n > kCap ? kCap : n;
+        start[w] = run;
+        down[w] = queue ? 0 : n;               // count: every vehicle of the lane
+        run += n;
+    }
+    if (t == kPressT - 1) start[Q.n_walk] = part[t];
+    for (int m = t; m < Q.n_mov; m += kPressT) up[m] = 0;
+    __syncthreads();
+    const int total = start[Q.n_walk];
+    for (int f = t; f < total; f += kPressT) {
+        int lo = 0, hi = Q.n_walk;             // the last walked lane whose first record is at or before f (empty lanes repeat a start)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (start[mid] <= f) lo = mid; else hi = mid;
+        }
+        const int lane = Q.walk[lo];
+        const float4 rec = S[vslot(f - start[lo], lane, P.NLP)];
+        if (queue && !(rec.y < kHalt)) continue;
+        const int route = (int)(__float_as_uint(rec.w) >> 16);
+        const int mv = route < P.NR ? Q.mov_of[lane * P.NR + route] : -1;
+        if (mv >= 0) atomicAdd(&up[mv], 1);
+        if (queue) atomicAdd(&down[lo], 1);
+    }
+    __syncthreads();
+    for (int i = t; i < P.A * P.PMAX; i += kPressT) {
+        int sum = 0;
+        for (int j = Q.srv_off[i]; j < Q.srv_off[i + 1]; ++j) {
+            const int mv = Q.srv[j];
+            sum += up[mv] - down[Q.mov_dn[mv]];
+        }
+        prs[i] = sum;                          // (padded phases serve nothing: 0)
+        if (pressure) pressure[(size_t)e * P.A * P.PMAX + i] = sum;
+    }
+    __syncthreads();
+    for (int a = t; a < P.A; a += kPressT) {
+        int2 *hold = (int2 *)Q.hold + (size_t)e * P.A + a;
+        int2 h = *hold;                        // {cur, age}
+        if (h.y < Q.min_green) h.y += 1;
+        else {
+            int arg = 0;
+            for (int p = 1; p < P.agent_nphase[a]; ++p)
+                if (prs[a * P.PMAX + p] > prs[a * P.PMAX + arg]) arg = p;
+            if (arg != h.x) { h.x = arg; h.y = 1; }
+            else h.y = Q.min_green;            // (held long enough: the count need not run on)
+        }
+        *hold = h;
+        action[(size_t)e * P.A + a] = h.x;
+    }
+}
+
+// Fixed-time cycle: phase (t / steps) % n_phase at control step t = tsec / control interval.  One thread per (instance, agent).
+__global__ void __launch_bounds__(256) fixed_time_kernel(EnvDev P, int steps, int *__restrict__ action) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P.E * P.A) return;
+    const int t = P.tsec[i / P.A] / P.ctrl;
+    action[i] = (t / steps) % P.agent_nphase[i % P.A];
+}
+
 // Work decomposition of one workgroup (= one env instance):
 //   * lane threads (l < NLA) own one lane each: the head walk (phase H), the gather (phase B);
 //   * with HELP, phase F evaluates the car-following law of every queued vehicle behind the first one that stays with
@@ -1504,6 +1614,10 @@ struct tsc_env {
     const uint8_t *emit_shared = nullptr;
     uint8_t *dem_rows = nullptr;
     int *dem_vph = nullptr, *dem_off = nullptr, *dem_fl = nullptr;
+    // max-pressure controller (tsc_env_set_pressure): its tables and hold state, null until armed; LDS of pressure_kernel
+    PressDev Q = {};
+    size_t smem_press = 0;
+    std::vector<int> h_nphase;      // host copy of agent_nphase (tsc_env_set_pressure checks the served lists against it)
 };
 
 // Workgroup size / flat-phase width of the specialised step kernels for `n_resident` env instances on the device (this handle's
@@ -1569,13 +1683,13 @@ const char *tsc_profile_name(int32_t id) {
     static const char *names[] = {"env_step", "fc_gemm", "zx_gemm", "lstm_fwd", "head_fwd", "sample", "add_transition",
                                   "returns", "head_bwd", "lstm_bwd", "dwo_gemm", "dwh_gemm", "dwx_gemm", "dx1_gemm",
                                   "dw1_gemm", "grad_norm", "rmsprop", "transpose_wx", "fingerprint", "policy_fwd_fused",
-                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "demand",
+                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "pressure", "demand",
                                   "gae", "head_bwd_ppo"};
     static_assert(sizeof(names) / sizeof(names[0]) == tsc::KID_COUNT, "one name per kernel id");
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 111; }      // 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 112; }      // 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \
@@ -1797,6 +1911,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     UP(agent_lanes, int, sc->agent_lanes, A * P.LMAX);
     UP(agent_nlane, int, sc->agent_nlane, A); UP(agent_nlink, int, sc->agent_nlink, A);
     UP(agent_nphase, int, sc->agent_nphase, A);
+    h->h_nphase.assign(sc->agent_nphase, sc->agent_nphase + A);
     UP(green_tab, uint8_t, sc->green_tab, (size_t)A * P.PMAX * P.KMAX);
     UP(yellow_tab, uint8_t, sc->yellow_tab, (size_t)A * P.PMAX * P.PMAX * P.KMAX);
     UP(nbr, int, sc->nbr, A * P.NBR);
@@ -2132,6 +2247,8 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
         h->dem_cur = h->dem_next;
         h->dem_dirty = false;
     }
+    if (h->Q.hold)                                     // max-pressure hold: age >= min_green, the first decision is free
+        TSC_HIP(hipMemsetAsync(h->Q.hold, 0x7F, sizeof(int) * 2 * (size_t)h->P.E * h->P.A, h->stream));
     h->ld_live = h->P.ld_int != nullptr;               // tsc_env_lane_data takes effect here; its sums start over
     if (h->ld_live) {
         const size_t rows = (size_t)h->P.E * h->ld_nint;
@@ -2353,6 +2470,94 @@ int tsc_env_greedy_actions(tsc_env *h, const float *obs_dev, int32_t *action_dev
     if (!h->P.g_ncand) return tsc::fail("tsc_env_greedy_actions: no controller tables (tsc_env_set_greedy)");
     const int tot = h->P.E * h->P.A;
     hipLaunchKernelGGL(greedy_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->P, obs_dev, action_dev);
+    TSC_HIP(hipGetLastError());
+    return 0;
+}
+
+int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov,
+                         int32_t srv_max, const int32_t *served) {
+    if (!h || !mov || !lane_route_mov || !served || n_mov < 0 || srv_max <= 0) return tsc::fail("tsc_env_set_pressure: bad arguments");
+    if (measure != TSC_PRESSURE_COUNT && measure != TSC_PRESSURE_QUEUE)
+        return tsc::fail("tsc_env_set_pressure: measure %d is neither TSC_PRESSURE_COUNT (0) nor TSC_PRESSURE_QUEUE (1)", measure);
+    if (min_green < 1) return tsc::fail("tsc_env_set_pressure: min_green %d must be >= 1", min_green);
+    const EnvDev &P = h->P;
+    if (n_mov > 4096 || P.A * P.PMAX > 4096)
+        return tsc::fail("tsc_env_set_pressure: %d movements, %d (agent, phase) pairs: at most 4096 each", n_mov, P.A * P.PMAX);
+    std::vector<int> widx((size_t)P.NL, -1);
+    for (int i = 0; i < n_mov; ++i) {
+        const int a = mov[4 * i], l = mov[4 * i + 1], m = mov[4 * i + 2], k = mov[4 * i + 3];
+        if (a < 0 || a >= P.A) return tsc::fail("tsc_env_set_pressure: movement %d names agent %d of %d", i, a, P.A);
+        if (l < 0 || l >= P.NL || m < 0 || m >= P.NL) return tsc::fail("tsc_env_set_pressure: movement %d names lanes %d -> %d of %d", i, l, m, P.NL);
+        if (k < 0 || k >= P.KMAX) return tsc::fail("tsc_env_set_pressure: movement %d names signal link %d of %d", i, k, P.KMAX);
+        widx[l] = widx[m] = 0;
+    }
+    std::vector<short> walk, mov_of((size_t)P.NL * P.NR), mov_dn((size_t)n_mov), srv;
+    for (int l = 0; l < P.NL; ++l)
+        if (widx[l] == 0) { widx[l] = (int)walk.size(); walk.push_back((short)l); }
+    for (int i = 0; i < n_mov; ++i) mov_dn[i] = (short)widx[mov[4 * i + 2]];
+    for (int l = 0; l < P.NL; ++l)
+        for (int r = 0; r < P.NR; ++r) {
+            const int i = lane_route_mov[(size_t)l * P.NR + r];
+            if (i < -1 || i >= n_mov || (i >= 0 && mov[4 * i + 1] != l))
+                return tsc::fail("tsc_env_set_pressure: lane %d route %d names movement %d of %d (or one of another lane)", l, r, i, n_mov);
+            mov_of[(size_t)l * P.NR + r] = (short)i;
+        }
+    std::vector<int> off((size_t)P.A * P.PMAX + 1, 0);
+    for (int a = 0; a < P.A; ++a)
+        for (int p = 0; p < P.PMAX; ++p) {
+            for (int j = 0; j < srv_max; ++j) {
+                const int i = served[((size_t)a * P.PMAX + p) * srv_max + j];
+                if (i < 0) break;
+                if (p >= h->h_nphase[a]) return tsc::fail("tsc_env_set_pressure: agent %d phase %d of %d serves a movement", a, p, h->h_nphase[a]);
+                if (i >= n_mov || mov[4 * i] != a) return tsc::fail("tsc_env_set_pressure: agent %d phase %d serves movement %d of %d (or another agent's)", a, p, i, n_mov);
+                srv.push_back((short)i);
+            }
+            off[(size_t)a * P.PMAX + p + 1] = (int)srv.size();
+        }
+    const size_t smem = sizeof(int) * (2 * walk.size() + 1 + (size_t)n_mov + (size_t)P.A * P.PMAX + kPressT);
+    if (smem > 48 * 1024) return tsc::fail("tsc_env_set_pressure: LDS need %zu B > 48 KiB (%zu walked lanes, %d movements)", smem, walk.size(), n_mov);
+    (void)hipSetDevice(h->device);
+    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running pressure_kernel may still read the old tables
+    PressDev &Q = h->Q;
+    for (const void *old : {(const void *)Q.walk, (const void *)Q.mov_of, (const void *)Q.mov_dn, (const void *)Q.srv_off, (const void *)Q.srv}) {
+        if (!old) continue;
+        for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
+            if (*it == old) { (void)hipFree(*it); h->allocs.erase(it); break; }
+    }
+    Q.walk = nullptr; Q.mov_of = nullptr; Q.mov_dn = nullptr; Q.srv_off = nullptr; Q.srv = nullptr;
+#define UPQ(field, T, vec)                                                       \
+    do {                                                                         \
+        T *d_ = nullptr;                                                         \
+        TSC_HIP(tsc::upload<T>(&d_, (vec).data(), (vec).size()));                \
+        h->allocs.push_back(d_);                                                 \
+        Q.field = d_;                                                            \
+    } while (0)
+    UPQ(walk, short, walk); UPQ(mov_of, short, mov_of); UPQ(mov_dn, short, mov_dn); UPQ(srv_off, int, off); UPQ(srv, short, srv);
+#undef UPQ
+    if (!Q.hold) {
+        TSC_HIP(hipMalloc((void **)&Q.hold, sizeof(int) * 2 * (size_t)P.E * P.A));
+        h->allocs.push_back(Q.hold);
+    }
+    TSC_HIP(hipMemset(Q.hold, 0x7F, sizeof(int) * 2 * (size_t)P.E * P.A));      // age >= min_green: the next decision is free
+    Q.n_mov = n_mov; Q.n_walk = (int)walk.size(); Q.measure = measure; Q.min_green = min_green;
+    h->smem_press = smem;
+    return 0;
+}
+
+int tsc_env_pressure_actions(tsc_env *h, int32_t *action_dev, int32_t *pressure_dev) {
+    if (!h || !action_dev) return tsc::fail("tsc_env_pressure_actions: bad arguments");
+    if (!h->Q.hold) return tsc::fail("tsc_env_pressure_actions: no controller tables (tsc_env_set_pressure)");
+    tsc::ProfScope ps(tsc::KID_PRESSURE, h->stream);
+    hipLaunchKernelGGL(pressure_kernel, dim3(h->P.E), dim3(kPressT), h->smem_press, h->stream, h->P, h->Q, action_dev, pressure_dev);
+    TSC_HIP(hipGetLastError());
+    return 0;
+}
+
+int tsc_env_fixed_time_actions(tsc_env *h, int32_t steps_per_phase, int32_t *action_dev) {
+    if (!h || !action_dev) return tsc::fail("tsc_env_fixed_time_actions: bad arguments");
+    if (steps_per_phase < 1) return tsc::fail("tsc_env_fixed_time_actions: steps_per_phase %d must be >= 1", steps_per_phase);
+    const int tot = h->P.E * h->P.A;
+    hipLaunchKernelGGL(fixed_time_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->P, (int)steps_per_phase, action_dev);
     TSC_HIP(hipGetLastError());
     return 0;
 }

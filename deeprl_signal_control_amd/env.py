@@ -381,6 +381,39 @@ class VecTrafficEnv:
         _lib.check(self._L.tsc_env_greedy_actions(self._h, C.c_void_p(obs.data_ptr()), C.c_void_p(out.data_ptr())))
         return out
 
+    def max_pressure_actions(self, out=None, measure='count', min_green=1, return_pressure=False):
+        """The max-pressure controller's actions for every instance, from the vehicle state on the device (pressure_kernel,
+        csrc/tsc_env.hip; the rule: INTEGRATION.md "Baseline controllers") -> int32 [E, A]; with return_pressure also the phase
+        pressures int32 [E, A, AMAX] (padded phases 0).  measure 'count' | 'queue'; min_green >= 1 control steps a chosen phase is
+        held at least.  Arms the tables at the first call and again when measure / min_green change (which frees the next
+        decision, as reset() does).  ONE CALL PER CONTROL STEP: with min_green > 1 a call advances the hold state."""
+        key = (measure, min_green)
+        if getattr(self, '_pressure_key', None) != key:
+            kw = pressure_kw(measure, min_green)
+            tabs = self.scn.pressure_tables()
+            ip = C.POINTER(C.c_int32)
+            mov, lrm, served = (np.ascontiguousarray(tabs[k], np.int32) for k in ('mov', 'lane_route_mov', 'served'))
+            _lib.check(self._L.tsc_env_set_pressure(self._h, PRESSURE_MEASURES.index(kw['pressure_measure']), kw['pressure_min_green'],
+                                                    len(mov), mov.ctypes.data_as(ip), lrm.ctypes.data_as(ip), served.shape[2],
+                                                    served.ctypes.data_as(ip)))
+            self._pressure_key = key
+        if out is None:
+            out = torch.empty(self.E, self.A, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (self.E, self.A)
+        prs = torch.empty(self.E, self.A, self.AMAX, dtype=torch.int32, device=self.device) if return_pressure else None
+        _lib.check(self._L.tsc_env_pressure_actions(self._h, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(prs.data_ptr()) if return_pressure else None))
+        return (out, prs) if return_pressure else out
+
+    def fixed_time_actions(self, steps_per_phase, out=None):
+        """The fixed-time cycle for every instance (fixed_time_kernel): action[e, a] = (t // steps_per_phase) % n_phase[a] with t
+        the control steps taken since reset() -> int32 [E, A]."""
+        if out is None:
+            out = torch.empty(self.E, self.A, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (self.E, self.A)
+        _lib.check(self._L.tsc_env_fixed_time_actions(self._h, int(steps_per_phase), C.c_void_p(out.data_ptr())))
+        return out
+
     def reward_sum(self, reset=False):
         """Sum of the global reward over instances and control steps since the accumulator was reset."""
         v = C.c_double()
@@ -528,6 +561,40 @@ def car_following_kw(model, sigma=None):
             raise ValueError('[ENV_CONFIG] krauss_sigma = %r: must lie in [0, 1]' % sigma)
         kw['krauss_sigma'] = sigma
     return kw
+
+
+CONTROLLERS = ('greedy', 'maxpressure', 'fixedtime')     # evaluate --agents names that need no learner (main.py)
+PRESSURE_MEASURES = ('count', 'queue')                   # include/tsc.h TSC_PRESSURE_COUNT / TSC_PRESSURE_QUEUE
+
+
+def pressure_kw(measure=None, min_green=None):
+    """[ENV_CONFIG] pressure_measure = count | queue (default count) / pressure_min_green = 1 -> checked values."""
+    measure = 'count' if measure is None else str(measure).strip()
+    if measure not in PRESSURE_MEASURES:
+        raise ValueError('[ENV_CONFIG] pressure_measure = %r: allowed values are %s' % (measure, ' | '.join(PRESSURE_MEASURES)))
+    return dict(pressure_measure=measure, pressure_min_green=_positive_int('pressure_min_green', 1 if min_green is None else min_green))
+
+
+def _positive_int(key, v):
+    try:
+        n = int(str(v).strip()) if not isinstance(v, (int, np.integer)) else int(v)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise ValueError('[ENV_CONFIG] %s = %r: must be an integer >= 1' % (key, v))
+    return n
+
+
+def controller_kw(config):
+    """The baseline controllers' keys of an [ENV_CONFIG] section (SectionProxy or dict of strings): pressure_measure = count | queue
+    (default count), pressure_min_green = 1, fixed_time_steps = 6 (control steps per phase).  Unknown values are refused with the
+    allowed ones named."""
+    kw = pressure_kw(config.get('pressure_measure'), config.get('pressure_min_green'))
+    steps = config.get('fixed_time_steps')
+    kw['fixed_time_steps'] = _positive_int('fixed_time_steps', 6 if steps is None else steps)
+    return kw
+
+
 SCENARIO_KEYS = {'large_grid': dict(peak_flow1=int, peak_flow2=int, init_density=float),
                  'real_net': dict(flow_rate=int), 'small_grid': dict(num_extra_car_per_hour=int)}
 

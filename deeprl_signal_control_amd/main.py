@@ -3,7 +3,7 @@
     python -m deeprl_signal_control_amd.main --base-dir DIR train --config-dir config/config_ma2c_large.ini
                                                                   [--test-mode no_test|in_train_test|after_train_test|all_test]
                                                                   [--envs E]
-    python -m deeprl_signal_control_amd.main --base-dir DIR evaluate --agents ma2c,greedy
+    python -m deeprl_signal_control_amd.main --base-dir DIR evaluate --agents ma2c,greedy,maxpressure,fixedtime
                                                                   [--evaluation-policy-type default|stochastic|deterministic]
                                                                   [--evaluation-seeds 10000,20000,...]
                                                                   [--trajectories N] [--lane-data PERIOD]
@@ -23,6 +23,10 @@ seed.  PERIOD is a multiple of the control interval; 0 (the default) is off.
 scenario.DemandSampler builds it) as one batched episode of seeds x scales instances -- episode numbers run over the seeds of the
 first scale, then the second ... -- and adds a ``demand_scale`` column to every table.  Training draws its demand per episode from
 ``[ENV_CONFIG] demand_scales`` / ``demand_jitter``; the evaluation runs the nominal demand without the flag.
+
+``greedy``, ``maxpressure`` (Varaiya 2013) and ``fixedtime`` are controllers without a learner: ``DIR/<name>/data/*.ini`` supplies the
+config ([ENV_CONFIG] ``pressure_measure = count | queue``, ``pressure_min_green = 1``, ``fixed_time_steps = 6``), no checkpoint is read,
+and ``train`` refuses them.
 
 What differs: ``--envs E`` trains on E parallel env instances per GPU (the reference has one); `total_step`,
 `test_interval`, `log_interval` keep counting control steps of ONE instance, so a run is E times the experience.
@@ -130,6 +134,38 @@ class GreedyPolicy:
         pass
 
 
+class MaxPressurePolicy:
+    """The max-pressure controller (Varaiya 2013) on the device's vehicle state: VecTrafficEnv.max_pressure_actions ->
+    tsc_env_pressure_actions; [ENV_CONFIG] pressure_measure / pressure_min_green.  The observation is not read."""
+    name = 'maxpressure'
+    n_step = 1
+
+    def __init__(self, env, measure='count', min_green=1):
+        self.env, self.measure, self.min_green = env, measure, min_green
+
+    def forward(self, ob, *_a, **_k):
+        return self.env.max_pressure_actions(measure=self.measure, min_green=self.min_green)
+
+    def reset(self):
+        pass
+
+
+class FixedTimePolicy:
+    """A fixed-time cycle, [ENV_CONFIG] fixed_time_steps control steps per phase: VecTrafficEnv.fixed_time_actions ->
+    tsc_env_fixed_time_actions."""
+    name = 'fixedtime'
+    n_step = 1
+
+    def __init__(self, env, steps_per_phase=6):
+        self.env, self.steps = env, steps_per_phase
+
+    def forward(self, ob, *_a, **_k):
+        return self.env.fixed_time_actions(self.steps)
+
+    def reset(self):
+        pass
+
+
 A2C_POLICIES = ('lstm', 'fc')
 
 
@@ -172,6 +208,10 @@ def train(args):
     config = configparser.ConfigParser()
     config.read(args.config_dir)
     in_test, post_test = init_test_flag(args.test_mode)
+    from .env import CONTROLLERS
+    if config['ENV_CONFIG'].get('agent') in CONTROLLERS:          # (before any work on the device)
+        raise ValueError('agent %r has no learner to train (main.py:102-118 knows ia2c, ma2c, iqld, iqll); evaluate it with '
+                         '`evaluate --agents %s`' % (config['ENV_CONFIG'].get('agent'), config['ENV_CONFIG'].get('agent')))
     scn, seed, test_seeds = scenario_from_config(config['ENV_CONFIG'])
     sampler = demand_from_config(config['ENV_CONFIG'], scn)
     env = VecTrafficEnv(scn, args.envs, device=args.device, seed=seed, test_seeds=test_seeds, demand=sampler)
@@ -210,7 +250,7 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
     """main.py:158-198 + Evaluator.run (utils.py:366-388): all evaluation seeds as ONE batched, recorded episode.  demand_scales:
     every seed under each of these demand scales (instance k * len(seeds) + i runs seed i at scale k); the tables then carry a
     demand_scale column."""
-    from .env import VecTrafficEnv, check_lane_data_period, scenario_from_config
+    from .env import CONTROLLERS, VecTrafficEnv, check_lane_data_period, controller_kw, scenario_from_config
     from .trainer import VecTrainer
     agent = agent_dir.rstrip('/').split('/')[-1]
     if not os.path.isdir(agent_dir):
@@ -221,8 +261,9 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
         return None
     config = configparser.ConfigParser()
     config.read(config_dir)
-    if agent == 'greedy':
+    if agent in CONTROLLERS:                  # the controllers share the greedy observation layout (none but greedy reads it)
         config['ENV_CONFIG']['agent'] = 'greedy'
+        ctl = controller_kw(config['ENV_CONFIG']) if agent != 'greedy' else {}   # (refusals before any work on the device)
     scn, seed, _ = scenario_from_config(config['ENV_CONFIG'])
     lane_data = check_lane_data_period(lane_data, scn.control_interval_sec)     # (before any work on the device)
     n_seed = len(seeds)
@@ -234,12 +275,19 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
         seeds = list(seeds) * len(demand_scales)
     E = len(seeds)
     env = VecTrafficEnv(scn, E, device=device, seed=seed, test_seeds=seeds)
+    env.agent = agent if agent in CONTROLLERS else env.agent                     # every table is named and labelled with it
     if scale_of is not None:
         env.set_demand(np.stack([sampler.column(s_) for s_ in scale_of]))
         logging.info('Evaluation: demand scales %s x %d seeds' % (','.join('%g' % s_ for s_ in demand_scales), n_seed))
     logging.info('Evaluation: car following %s' % car_following_label(scn))
     logging.info('Evaluation: s dim: %d, a dim %d, s dim ls: %r, a dim ls: %r' % (env.n_s, env.n_a, env.n_s_ls, env.n_a_ls))
-    if agent != 'greedy':
+    if agent == 'maxpressure':
+        model = MaxPressurePolicy(env, ctl['pressure_measure'], ctl['pressure_min_green'])
+        logging.info('Evaluation: max-pressure, measure %s, min green %d control steps' % (model.measure, model.min_green))
+    elif agent == 'fixedtime':
+        model = FixedTimePolicy(env, ctl['fixed_time_steps'])
+        logging.info('Evaluation: fixed-time, %d control steps per phase' % model.steps)
+    elif agent != 'greedy':
         model = init_model(env, config, 0, E, seed, device)
         if not model.load(agent_dir + '/model/'):
             logging.error('Evaluation: no checkpoint under %s/model/' % agent_dir)

@@ -232,6 +232,49 @@ class Scenario:
                 action[a, c] = acts[a][c]
         return n_cand, term, action
 
+    def pressure_tables(self):
+        """The movement tables of the max-pressure controller (tsc_env_set_pressure; INTEGRATION.md states the rule).  A movement
+        of agent a is a distinct triple (l, m, k) over the routes r with lane_node[l] == a, m = mv_next[l, r] >= 0 and k =
+        mv_link[l, r] >= 0; phase p < agent_nphase[a] serves it when green_tab[a, p, k] is 'G' or 'g'.  A vehicle whose mv_next
+        entry on its lane is negative (end of the route, or the wrong lane of a two-lane street) belongs to no movement.  Lanes are
+        the simulator's, in the scenario's (load-sorted) order, which is the device's.  Returns a dict: mov i32 [n_mov, 4] rows
+        (agent, l, m, k) ordered by agent, l, m, k; lane_route_mov i32 [NL, NR] the movement of (lane, route) or -1; n_served i32
+        [A, PMAX] and served i32 [A, PMAX, SRV] (-1 padded) the movements every phase serves, ascending; walk i32 the lanes that
+        appear in a movement as l or m, ascending.  The device keeps movement indices as 16-bit values and its sums in 48 KiB of LDS:
+        a scenario that does not fit is refused here."""
+        A, PMAX = self.n_agent, int(self.green_tab.shape[1])
+        node, nxt, link = np.asarray(self.lane_node), np.asarray(self.mv_next), np.asarray(self.mv_link)
+        ls, rs = np.nonzero((node[:, None] >= 0) & (nxt >= 0) & (link >= 0))
+        keys = sorted({(int(node[l]), int(l), int(nxt[l, r]), int(link[l, r])) for l, r in zip(ls, rs)})
+        index = {k: i for i, k in enumerate(keys)}
+        mov = np.array(keys, np.int32).reshape(-1, 4)
+        lane_route_mov = np.full(nxt.shape, -1, np.int32)
+        for l, r in zip(ls, rs):
+            lane_route_mov[l, r] = index[(int(node[l]), int(l), int(nxt[l, r]), int(link[l, r]))]
+        lists = [[[] for _ in range(PMAX)] for _ in range(A)]
+        for i, (a, _l, _m, k) in enumerate(keys):
+            if k >= self.green_tab.shape[2]:
+                raise ValueError('movement %d of agent %d uses signal link %d, the phase table has %d' % (i, a, k, self.green_tab.shape[2]))
+            for p in range(int(self.agent_nphase[a])):
+                if self.green_tab[a, p, k] in (ord('G'), ord('g')):
+                    lists[a][p].append(i)
+        SRV = max(1, max(len(s) for row in lists for s in row))
+        served = np.full((A, PMAX, SRV), -1, np.int32)
+        n_served = np.zeros((A, PMAX), np.int32)
+        for a in range(A):
+            for p in range(PMAX):
+                served[a, p, :len(lists[a][p])] = lists[a][p]
+                n_served[a, p] = len(lists[a][p])
+        walk = np.array(sorted(set(mov[:, 1].tolist()) | set(mov[:, 2].tolist())), np.int32)
+        if len(mov) > 4096 or A * PMAX > 4096:
+            raise ValueError('max-pressure tables: %d movements, %d (agent, phase) pairs: the device keeps at most 4096 of each in LDS'
+                             % (len(mov), A * PMAX))
+        lds = 4 * (2 * len(walk) + 1 + len(mov) + A * PMAX + 256)
+        if lds > 48 * 1024:
+            raise ValueError('max-pressure tables: %d walked lanes, %d movements and %d (agent, phase) pairs need %d B of LDS, the '
+                             'kernel has 48 KiB' % (len(walk), len(mov), A * PMAX, lds))
+        return dict(mov=mov, lane_route_mov=lane_route_mov, served=served, n_served=n_served, walk=walk)
+
     def streams_ready(self):
         """Fill the optional stream tables (whole-lane insertion window) once streams are declared."""
         if self.stream_entry_lane is not None:

@@ -206,7 +206,7 @@ class VecTrainer:
         model.reset()
         rewards = []
         while True:
-            if self.agent == 'greedy':                           # utils.py:202-203
+            if self.agent in ('greedy', 'maxpressure', 'fixedtime'):     # utils.py:202-203 (controllers: no learner)
                 action = model.forward(ob)
             elif not self.agent.endswith('a2c'):                 # value-based (utils.py:221-226)
                 action, _ = model.forward(ob, stochastic=policy_type == 'stochastic')
@@ -386,3 +386,43 @@ def greedy_actions(scn, wave):
             flows.append(f)
         out[..., a] = action[a][np.argmax(np.stack(flows, -1), -1)]
     return out
+
+
+def max_pressure_actions(scn, state, measure='count', return_pressure=False):
+    """HOST restatement of the max-pressure rule (INTEGRATION.md "Baseline controllers") over one instance's vehicle state, a
+    VecTrafficEnv.get_state dict (n [NL], v and r [NL, LANE_CAP]) and Scenario.pressure_tables -- the tables the device kernel reads
+    (VecTrafficEnv.max_pressure_actions -> tsc_env_pressure_actions, the product path).  For host arrays only: CPU tools and tests.
+    q(vehicle) = 1 ('count') or 1 only if v < float32(0.1) ('queue'); up(movement) = sum of q over the vehicles on its lane whose
+    route takes it, down(m) = sum of q over all vehicles on m; pressure[a, p] = sum over the movements phase p serves of up -
+    down(m), int32, padded phases 0; the action is the first maximum over p < n_phase (no hold: min_green = 1)."""
+    if any(torch.is_tensor(v) for v in state.values()):
+        raise TypeError('max_pressure_actions is the host restatement; device state goes through VecTrafficEnv.max_pressure_actions (HIP)')
+    if measure not in ('count', 'queue'):
+        raise ValueError('measure = %r: allowed values are count | queue' % (measure,))
+    tabs = scn.pressure_tables()
+    n = np.asarray(state['n'])
+    live = np.arange(np.asarray(state['v']).shape[1])[None, :] < n[:, None]
+    q = live & (np.asarray(state['v'], np.float32) < np.float32(0.1)) if measure == 'queue' else live
+    down = q.sum(1)
+    up = np.zeros(len(tabs['mov']), np.int64)
+    lanes, slots = np.nonzero(q)
+    mv = tabs['lane_route_mov'][lanes, np.asarray(state['r'])[lanes, slots]]
+    np.add.at(up, mv[mv >= 0], 1)
+    A, PMAX = tabs['n_served'].shape
+    pressure = np.zeros((A, PMAX), np.int32)
+    for a in range(A):
+        for p in range(PMAX):
+            for i in tabs['served'][a, p, :tabs['n_served'][a, p]]:
+                pressure[a, p] += up[i] - down[tabs['mov'][i, 2]]
+    action = np.array([int(np.argmax(pressure[a, :int(scn.agent_nphase[a])])) for a in range(A)], np.int32)
+    return (action, pressure) if return_pressure else action
+
+
+def pressure_hold(cur, age, p_star, min_green):
+    """The max-pressure hold (min_green = g >= 1 control steps) for one agent: (cur, age) and this step's argmax p* -> (action, cur,
+    age).  age < g: the phase is held; otherwise p* is taken, a change restarting the count.  reset() sets age = g."""
+    if age < min_green:
+        return cur, cur, age + 1
+    if p_star != cur:
+        return p_star, p_star, 1
+    return cur, cur, age + 1

@@ -36,6 +36,7 @@ extern "C" {
 enum { TSC_AGENT_GREEDY = 0, TSC_AGENT_GLOBAL = 1 /* ia2c, iql */, TSC_AGENT_MA2C = 2 };
 enum { TSC_OBJ_QUEUE = 0, TSC_OBJ_WAIT = 1, TSC_OBJ_HYBRID = 2 };
 enum { TSC_CF_IDM = 0, TSC_CF_KRAUSS = 1 };        /* car-following model (tsc_env_set_car_following) */
+enum { TSC_PRESSURE_COUNT = 0, TSC_PRESSURE_QUEUE = 1 };   /* what a vehicle counts for under max-pressure (tsc_env_set_pressure) */
 
 /* Dense scenario tables (host pointers, copied at create time).  Produced by
  * deeprl_signal_control_amd/scenario.py; meaning and reference provenance of every
@@ -99,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -181,6 +182,27 @@ int tsc_env_set_greedy(tsc_env *h, int32_t n_cand_max, int32_t n_term_max, const
  * step() wrote it, action dev int32 [E, A].  The controllers read the env's float64 state; the kernel recovers it from the
  * float32 entries (a wave entry is a vehicle count / norm_wave, clipped: envs/env.py:439-442), so ties fall as in numpy. */
 int tsc_env_greedy_actions(tsc_env *h, const float *obs_dev, int32_t *action_dev);
+
+/* The max-pressure controller (Varaiya 2013; no reference counterpart; INTEGRATION.md "Baseline controllers" states the rule).  A
+ * movement is a row of mov [n_mov, 4] = {agent, incoming lane l, downstream lane m, signal link k}; lane_route_mov [n_lane, n_route]
+ * names the movement a vehicle of that route takes from that lane, -1 = none (end of the route, or the wrong lane of a two-lane
+ * street); served [A, p_max, srv_max] lists, -1 padded, the movements a phase serves (none for p >= n_phase).  Host pointers, int32,
+ * copied; deeprl_signal_control_amd/scenario.py:Scenario.pressure_tables compiles them.  With q(vehicle) = 1 (TSC_PRESSURE_COUNT) or
+ * 1 only if v < 0.1 m/s (TSC_PRESSURE_QUEUE): up(movement) = sum of q over the vehicles on l whose route takes it, down(m) = sum of
+ * q over ALL vehicles on m, pressure(p) = int32 sum over the served movements of up - down(m); p* = the FIRST maximum over p <
+ * n_phase.  min_green = g >= 1 control steps: per (instance, agent) the device keeps cur and age; age < g: the action is cur, age += 1;
+ * otherwise p* != cur: cur = p*, age = 1; p* == cur: age += 1.  tsc_env_reset and this call set age = g (the next decision is free); g = 1
+ * is stateless.  Rejects a bad measure, min_green < 1 and out-of-range agents, lanes, links, movements or phases (tsc_last_error),
+ * before anything changes.  Synchronises before replacing tables.  A handle that never calls it allocates and launches nothing. */
+int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov,
+                         int32_t srv_max, const int32_t *served);
+/* The controller's actions from the vehicle state as it stands (pressure_kernel, one workgroup per instance): action dev int32
+ * [E, A]; pressure (nullable) dev int32 [E, A, p_max], padded phases 0.  ONE CALL PER CONTROL STEP: a call advances the hold state
+ * (cur, age) whenever min_green > 1.  Changes nothing of the simulation. */
+int tsc_env_pressure_actions(tsc_env *h, int32_t *action_dev, int32_t *pressure_dev);
+/* Fixed-time cycle: action[e, a] = (t / steps_per_phase) % n_phase[a], t = simulated seconds of instance e / control_interval_sec at
+ * the time of the call.  action dev int32 [E, A]; steps_per_phase >= 1.  Needs no tables. */
+int tsc_env_fixed_time_actions(tsc_env *h, int32_t steps_per_phase, int32_t *action_dev);
 
 /* Sum over instances and control steps of the global reward since the last reset of the accumulator
  * (what Trainer logs per episode, utils.py:161,296-305).  Synchronises. */

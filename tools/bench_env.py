@@ -1,6 +1,10 @@
 #!/usr/bin/env python
 """Sim-only timing of the env kernel (tsc_env_step) at a realistic traffic state.
-    python tools/bench_env.py [E] [steps]"""
+    python tools/bench_env.py [E] [steps] [--controller random|greedy|maxpressure|fixedtime]
+
+--controller: what chooses the actions of the warm-up and timed loops.  random (the default) replays 16 precomputed random action
+tensors, so the loop times tsc_env_step alone; the others launch that controller's kernel in front of every step, as an evaluation
+does (greedy_kernel on the observation, pressure_kernel on the vehicle state, fixed_time_kernel on the clock)."""
 import os
 import sys
 import time
@@ -23,6 +27,13 @@ def phase_names(n):
     return names + ['?'] * max(0, n - len(names))
 
 
+controller = 'random'
+if '--controller' in sys.argv:
+    k = sys.argv.index('--controller')
+    controller = sys.argv[k + 1] if k + 1 < len(sys.argv) else ''
+    del sys.argv[k:k + 2]
+    if controller not in ('random', 'greedy', 'maxpressure', 'fixedtime'):
+        sys.exit('--controller %r: allowed values are random | greedy | maxpressure | fixedtime' % controller)
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 scn = build_large_grid('ma2c')
@@ -34,8 +45,18 @@ for chunk in ('1',):
     for phase, n in (('warm-up to t=1500s (random actions)', 300), ('timed', steps)):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         for i in range(n):
-            obs, r, d, gr = env.step(acts[i % 16])
+            if controller == 'random':
+                act = acts[i % 16]
+            elif controller == 'greedy':
+                act = env.greedy_actions(obs, out=acts[0])
+            elif controller == 'maxpressure':
+                act = env.max_pressure_actions(out=acts[0])
+            else:
+                act = env.fixed_time_actions(6, out=acts[0])
+            obs, r, d, gr = env.step(act)
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
+        if controller != 'random':
+            print('controller %s in front of every step' % controller)
         print('chunk=%s %s: %.1f us/control-step, %.0f live veh/env, %.3g env-steps/s (sim only)'
               % (chunk, phase, 1e6 * dt / n, env.mean_live_vehicles(), 25 * E * 5 * n / dt))
     import ctypes as C
