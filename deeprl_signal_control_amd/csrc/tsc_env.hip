@@ -23,9 +23,26 @@
 // simulated second: phase H (lane threads: the platoon that crosses and the first vehicle that stays), phase F (all
 // threads: every other queued vehicle in a flat, load-balanced order -- car-following from the old state, the queue
 // constraint as a segmented prefix-min scan on the wavefront's DPP path; its first half runs on the helper wavefronts
-// WHILE the lane wavefronts are in phase H), phase B (gather + demand) (see step_kernel).  The reference's large_grid
-// and Monaco run instantiations whose table dimensions are compile-time constants (kSpec), with 256, 512 or 1024
-// threads per instance depending on how many instances share a CU (tsc_env_create).
+// WHILE the lane wavefronts are in phase H), phase B (gather + demand) (see step_kernel).
+//
+// Which kernel runs.  step_kernel<MAXT, HELP, REC, KF, SPEC> has one instantiation per row of kStepVariants (MAXT: workgroup
+// bound; HELP: flat phase; REC: recording walk; KF: flat-phase vehicles per thread; SPEC: 0 runtime table dimensions, 1 / 2
+// large_grid's / Monaco's as compile-time constants (kSpec), < 0 the kSpec* sentinels).  plan_step turns the handle's state into
+// a row, a workgroup size and an LDS size (StepPlan; tsc_env_step_plan reports it) whenever an input changes -- create, record,
+// trace, lane_data, set_resident_instances, reset -- and tsc_env_step only launches the plan.  The rules, first match wins:
+//   recording on ........ <256 | 1024, false, true, 4 (Krauss: 1), S>: S = lane data (live from the reset after arming), else
+//                         trace (from the call that attaches it), else none; IDM 0 / -2 / -4, Krauss -1 / -3 / -5
+//   Krauss .............. <256 | 1024, HELP, false, KF, -1>: KF = TSC_ENV_KF only up to 256 threads with the flat phase, else 1
+//   IDM, spec ........... <threads, true, false, kf, spec> when the scenario matches a kSpec row (not with TSC_ENV_SPEC=0 or
+//                         kf 4), the flat phase is on, kf is 1 or 2 and threads is 256, 512 or 1024
+//   IDM, runtime dims ... <256, true, false, kf, 0> up to 256 threads with the flat phase and kf 1 or 2; otherwise
+//                         <256 | 1024, HELP, false, 4, 0>: every wider workgroup runs the 4-wide flat phase whatever kf says
+// 256 | 1024 is by threads <= 256.  Threads: 256 with the flat phase when the live lanes fit (else NLA, the live lanes rounded
+// up to 64; TSC_ENV_HELP=0: NLA); a spec handle follows the device's load (pick_workgroup: 1024 threads and kf 1 up to one instance
+// per CU, 512 and kf 2 up to two, else 256 and kf 2 on large_grid / 1 on Monaco; tsc_env_set_resident_instances); a Krauss handle
+// does not.  TSC_ENV_THREADS (a multiple of 64 in [NLA, 1024]) and TSC_ENV_KF (1 | 2 | 4) override either.  The recording rows keep
+// that workgroup size.  Krauss is in force from the reset after tsc_env_set_car_following.  LDS is smem_bytes<KR, LD> of the
+// handle's tables (at most kLdsMax); a setter whose effect waits for the reset checks the size it will need when it is called.
 //
 // Arithmetic is fp32 with one rounding per operation (-ffp-contract=off, IEEE div/sqrt) so the
 // vehicle state is bit-identical to the CPU oracle; obs/reward are computed in float64 exactly
@@ -1580,15 +1597,43 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
+// Every instantiation of step_kernel, one row each: the only place their template arguments are written.  plan_step picks a row.
+using StepFn = void (*)(EnvDev, const int *, float *, double *, double *, uint8_t *, int);
+struct StepVariant { int maxt, help, rec, kf, spec; StepFn fn; };
+#define TSC_ROW(MAXT, HELP, REC, KF, SPEC) {MAXT, HELP, REC, KF, SPEC, step_kernel<MAXT, HELP, REC, KF, SPEC>}
+constexpr StepVariant kStepVariants[] = {
+    // compile-time table dimensions (large_grid 1, Monaco 2): workgroup 256 / 512 / 1024, flat phase 1 or 2 wide
+    TSC_ROW(256, true, false, 1, 1),  TSC_ROW(256, true, false, 2, 1),  TSC_ROW(256, true, false, 1, 2),  TSC_ROW(256, true, false, 2, 2),
+    TSC_ROW(512, true, false, 1, 1),  TSC_ROW(512, true, false, 2, 1),  TSC_ROW(512, true, false, 1, 2),  TSC_ROW(512, true, false, 2, 2),
+    TSC_ROW(1024, true, false, 1, 1), TSC_ROW(1024, true, false, 2, 1), TSC_ROW(1024, true, false, 1, 2), TSC_ROW(1024, true, false, 2, 2),
+    // runtime dimensions, IDM: the flat phase 1 / 2 / 4 wide up to 256 threads, 4 wide above; the plain walk (TSC_ENV_HELP=0)
+    TSC_ROW(256, true, false, 1, 0),  TSC_ROW(256, true, false, 2, 0),  TSC_ROW(256, true, false, 4, 0),  TSC_ROW(1024, true, false, 4, 0),
+    TSC_ROW(256, false, false, 4, 0), TSC_ROW(1024, false, false, 4, 0),
+    // the recording walk; with the trace; with the lane data
+    TSC_ROW(256, false, true, 4, 0),             TSC_ROW(1024, false, true, 4, 0),
+    TSC_ROW(256, false, true, 4, kSpecTrace),    TSC_ROW(1024, false, true, 4, kSpecTrace),
+    TSC_ROW(256, false, true, 4, kSpecLaneData), TSC_ROW(1024, false, true, 4, kSpecLaneData),
+    // Krauss (runtime dimensions): the same families, the flat phase 1 wide except up to 256 threads
+    TSC_ROW(256, true, false, 1, kSpecKrauss),  TSC_ROW(256, true, false, 2, kSpecKrauss),  TSC_ROW(256, true, false, 4, kSpecKrauss),
+    TSC_ROW(1024, true, false, 1, kSpecKrauss), TSC_ROW(256, false, false, 1, kSpecKrauss), TSC_ROW(1024, false, false, 1, kSpecKrauss),
+    TSC_ROW(256, false, true, 1, kSpecKrauss),         TSC_ROW(1024, false, true, 1, kSpecKrauss),
+    TSC_ROW(256, false, true, 1, kSpecKraussTrace),    TSC_ROW(1024, false, true, 1, kSpecKraussTrace),
+    TSC_ROW(256, false, true, 1, kSpecKraussLaneData), TSC_ROW(1024, false, true, 1, kSpecKraussLaneData),
+};
+#undef TSC_ROW
+struct StepPlan { const StepVariant *v = nullptr; int threads = 0; size_t lds = 0; };
+constexpr size_t kLdsMax = 160 * 1024;     // LDS of a CU (gfx950): what one workgroup may ask for
+
 struct tsc_env {
     EnvDev P;
     int device;
     hipStream_t stream;
     std::vector<void *> allocs;
-    size_t smem;
-    int threads;                    // workgroup size of step_kernel
-    int kf;                         // flat-phase vehicles per thread (measurement knob TSC_ENV_KF)
-    int spec;                       // 1: the scenario has the large_grid table dimensions -> specialised step_kernel (TSC_ENV_SPEC=0: off)
+    size_t smem;                    // LDS of reset_kernel (the IDM layout for the recording state)
+    int threads;                    // IDM workgroup size (pick_workgroup)
+    int kf;                         // IDM flat-phase vehicles per thread (measurement knob TSC_ENV_KF)
+    int spec;                       // kSpec row the scenario's table dimensions match -> specialised step_kernel (TSC_ENV_SPEC=0: off)
+    StepPlan plan;                  // what tsc_env_step launches (plan_step)
     uint32_t *d_seeds;
     std::vector<int> h_mode, h_sroute;      // host copies of the stream tables (tsc_env_set_stream_routes)
     int *order_buf = nullptr;       // tsc_env_set_block_order
@@ -1597,14 +1642,11 @@ struct tsc_env {
     // car following (tsc_env_set_car_following): the model in force (P.sigma its dawdling) and the one the next reset installs
     int cf = TSC_CF_IDM, cf_next = TSC_CF_IDM;
     float sigma_next = 0.0f;
-    size_t smem_kr = 0;             // LDS of the Krauss kernels (the R0 outbox on top)
-    int threads_kr = 256, kf_kr = 1;
     int n_trace = 0;                // traced instances (tsc_env_trace); their buffers are P.trace_*
     // lane data (tsc_env_lane_data): buffers P.ld_*, live from the reset after arming on; the caller's slot count (P.ld_nslot:
-    // the prefix of it the device keeps), intervals per episode, LDS of the IDM / Krauss lane-data kernels
+    // the prefix of it the device keeps), intervals per episode
     bool ld_live = false;
     int ld_nslot_all = 0, ld_nint = 0;
-    size_t smem_ld = 0, smem_kr_ld = 0;
     // per-instance demand (tsc_env_set_demand): the scenario's flow table; the [E][n_flow] veh/h columns in force and those the next
     // reset installs (empty: the scenario's own for every instance); the scenario's table and, from the first set_demand on, the
     // instances' tables, the uploaded columns and the flow elements grouped by stream (demand_kernel)
@@ -1620,8 +1662,21 @@ struct tsc_env {
     std::vector<int> h_nphase;      // host copy of agent_nphase (tsc_env_set_pressure checks the served lists against it)
 };
 
-// Workgroup size / flat-phase width of the specialised step kernels for `n_resident` env instances on the device (this handle's
-// and whatever shares the GPU with it); TSC_ENV_THREADS / TSC_ENV_KF override (measurement / test knobs).
+// TSC_ENV_THREADS / TSC_ENV_KF (measurement / test knobs) over the library's own choice
+static int env_threads(const EnvDev &P, int threads) {
+    const char *ev = getenv("TSC_ENV_THREADS");
+    const int tv = ev ? atoi(ev) : 0;
+    return (tv >= P.NLA && tv <= 1024 && tv % 64 == 0) ? tv : threads;
+}
+static int env_kf(int kf) {
+    const char *ev = getenv("TSC_ENV_KF");
+    if (!ev) return kf;
+    const int kv = atoi(ev);
+    return (kv == 2 || kv == 4) ? kv : 1;
+}
+
+// IDM workgroup size / flat-phase width for `n_resident` env instances on the device (this handle's and whatever shares the GPU
+// with it): the specialised kernels follow the device's load, everything else keeps what tsc_env_create chose.
 static void pick_workgroup(tsc_env *h, int n_resident) {
     if (h->auto_threads) {
         int dev_cus = 256;
@@ -1631,11 +1686,45 @@ static void pick_workgroup(tsc_env *h, int n_resident) {
         if (n_resident <= dev_cus) { h->threads = 1024; h->kf = 1; }
         else if (n_resident <= 2 * dev_cus) { h->threads = 512; h->kf = 2; }  // (Monaco, E = 512, saturated: 59.6 us with 2, 67.1 with 1)
     }
-    if (const char *ev = getenv("TSC_ENV_THREADS")) {
-        const int tv = atoi(ev);
-        if (tv >= h->P.NLA && tv <= 1024 && tv % 64 == 0) h->threads = tv;
+    h->threads = env_threads(h->P, h->threads);
+    h->kf = env_kf(h->kf);
+}
+
+// LDS of the step kernels of one family for the handle's current tables and recording state.  KR: the R0 outbox on top when
+// recording is off; LD: the flat phase's arrays make room for the lane data.
+static size_t step_lds(const EnvDev &P, bool kr, bool ld) {
+    return kr ? (ld ? smem_bytes<true, true>(P) : smem_bytes<true>(P)) : (ld ? smem_bytes<false, true>(P) : smem_bytes(P));
+}
+
+// The one place that turns the handle's state into a kernel, a workgroup size and an LDS size (header comment: "Which kernel
+// runs").  Called by every entry point that changes one of its inputs (`who`), never per step.
+static int plan_step(tsc_env *h, const char *who) {
+    const EnvDev &P = h->P;
+    const bool kr = h->cf == TSC_CF_KRAUSS, help = P.help != 0, ld = P.rec && h->ld_live;
+    // Krauss: runtime table dimensions, so the workgroup of TSC_ENV_SPEC=0 whatever shares the device
+    const int threads = kr ? env_threads(P, (help && P.NLA < 256) ? 256 : P.NLA) : h->threads;
+    const int kf = kr ? env_kf(1) : h->kf;
+    const bool narrow = threads <= 256;
+    const int wide = narrow ? 256 : 1024;
+    StepVariant k;
+    if (P.rec) {
+        const int what = ld ? (kr ? kSpecKraussLaneData : kSpecLaneData) : P.trace_slot ? (kr ? kSpecKraussTrace : kSpecTrace) : (kr ? kSpecKrauss : 0);
+        k = {wide, false, true, kr ? 1 : 4, what, nullptr};
     }
-    if (const char *ev = getenv("TSC_ENV_KF")) { const int kv = atoi(ev); h->kf = (kv == 2 || kv == 4) ? kv : 1; }
+    else if (kr) k = {wide, help, false, (narrow && help) ? kf : 1, kSpecKrauss, nullptr};
+    else if (h->spec && help && kf != 4 && (threads == 256 || threads == 512 || threads == 1024)) k = {threads, true, false, kf, h->spec, nullptr};
+    else if (narrow && help && kf != 4) k = {256, true, false, kf, 0, nullptr};
+    else k = {wide, help, false, 4, 0, nullptr};      // (any wider workgroup with runtime dimensions: the 4-wide flat phase)
+    h->plan = StepPlan();                              // a failure below leaves no plan: tsc_env_step refuses
+    const StepVariant *v = nullptr;
+    for (const StepVariant &r : kStepVariants)
+        if (r.maxt == k.maxt && r.help == k.help && r.rec == k.rec && r.kf == k.kf && r.spec == k.spec) v = &r;
+    if (!v) return tsc::fail("tsc_env_step: no instantiation for %d threads, kf %d, spec %d", threads, kf, k.spec);
+    const size_t lds = step_lds(P, kr, ld);
+    if (lds > kLdsMax) return tsc::fail("%s: LDS need %zu B > 160 KiB", who, lds);
+    TSC_HIP(hipFuncSetAttribute((const void *)v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    h->plan.v = v; h->plan.threads = threads; h->plan.lds = lds;
+    return 0;
 }
 
 namespace tsc {
@@ -1689,7 +1778,7 @@ const char *tsc_profile_name(int32_t id) {
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 112; }      // 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 113; }      // 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \
@@ -1706,42 +1795,6 @@ int tsc_version(void) { return 112; }      // 1.12: tsc_env_set_pressure / tsc_e
         h->allocs.push_back(d_);                                                 \
         P.field = d_;                                                            \
     } while (0)
-
-// LDS of the Krauss kernels for the current recording state; their launch geometry (runtime table dimensions: the flat phase at
-// 256 threads unless TSC_ENV_THREADS says otherwise, KF 1 unless TSC_ENV_KF, as with TSC_ENV_SPEC=0)
-static int krauss_attrs(tsc_env *h) {
-    const EnvDev &P = h->P;
-    h->smem_kr = smem_bytes<true>(P);
-    if (h->smem_kr > 160 * 1024) return tsc::fail("tsc_env_set_car_following: LDS need %zu B > 160 KiB", h->smem_kr);
-    h->threads_kr = (P.help && P.NLA < 256) ? 256 : P.NLA;
-    if (const char *ev = getenv("TSC_ENV_THREADS")) {
-        const int tv = atoi(ev);
-        if (tv >= P.NLA && tv <= 1024 && tv % 64 == 0) h->threads_kr = tv;
-    }
-    h->kf_kr = 1;
-    if (const char *ev = getenv("TSC_ENV_KF")) { const int kv = atoi(ev); h->kf_kr = (kv == 2 || kv == 4) ? kv : 1; }
-#define TSC_ATTR_KR(MT, HELP, REC, KF) TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<MT, HELP, REC, KF, kSpecKrauss>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr))
-    TSC_ATTR_KR(256, true, false, 1); TSC_ATTR_KR(256, true, false, 2); TSC_ATTR_KR(256, true, false, 4); TSC_ATTR_KR(1024, true, false, 1);
-    TSC_ATTR_KR(256, false, false, 1); TSC_ATTR_KR(1024, false, false, 1); TSC_ATTR_KR(256, false, true, 1); TSC_ATTR_KR(1024, false, true, 1);
-#undef TSC_ATTR_KR
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 1, kSpecKraussTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 1, kSpecKraussTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr));
-    return 0;
-}
-
-// LDS of the lane-data kernels (recording on, P.ld_nslot set): the flat phase's arrays make room for the lane data
-static int lane_data_attrs(tsc_env *h) {
-    const EnvDev &P = h->P;
-    h->smem_ld = smem_bytes<false, true>(P);
-    h->smem_kr_ld = smem_bytes<true, true>(P);
-    const size_t need = h->smem_ld > h->smem_kr_ld ? h->smem_ld : h->smem_kr_ld;
-    if (need > 160 * 1024) return tsc::fail("tsc_env_lane_data: LDS need %zu B > 160 KiB (%d slots)", need, P.ld_nslot);
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 4, kSpecLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_ld));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 4, kSpecLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_ld));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 1, kSpecKraussLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr_ld));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 1, kSpecKraussLaneData>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_kr_ld));
-    return 0;
-}
 
 int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_env **out) {
     if (!sc || !out || n_env <= 0) return tsc::fail("tsc_env_create: bad arguments");
@@ -1957,7 +2010,6 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     if (kMaxCross * P.NLA < P.NLP || kMaxCross * P.NLA < 2 * P.A)
         return tsc::fail("tsc_env_create: too few live lanes (%d of %d) for the observation scratch", P.NU, P.NL);
     h->smem = smem_bytes(P);
-    if (h->smem > 160 * 1024) return tsc::fail("tsc_env_create: LDS need %zu B > 160 KiB", h->smem);
     h->threads = (P.help && P.NLA < 256) ? 256 : P.NLA;
     // the reference's large_grid / Monaco get the instantiation with compile-time table dimensions (TSC_ENV_SPEC=0: off)
     h->spec = 0;
@@ -1973,16 +2025,8 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     // 1 is best (296 M env-steps/s; 2: 294, 4: 284 -- fewer barriers do not pay for the registers); the specialised kernel
     // has the registers for 2 (env step 11.5 -> 10.7 ms per rollout; 4 spills: 11.4; round 5, rule-10 traffic, episode average:
     // 3 -- 128 VGPRs, 8 spilled dwords, bit-exact -- 94.9 / 95.3 us per control step against 92.7 / 92.8 with 2)
-    h->kf = h->spec == 1 ? 2 : 1;                            // (Monaco, spec 2: 330 M env-steps/s with 1, 323 M with 2)
-    if (const char *ev = getenv("TSC_ENV_KF")) { const int kv = atoi(ev); h->kf = (kv == 2 || kv == 4) ? kv : 1; }
+    h->kf = env_kf(h->spec == 1 ? 2 : 1);                    // (Monaco, spec 2: 330 M env-steps/s with 1, 323 M with 2)
     if (h->spec && h->kf == 4) h->spec = 0;                  // (no specialised instantiation of the 4-wide variant)
-#define TSC_ATTR(MT, KF, SP) TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<MT, true, false, KF, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem))
-    TSC_ATTR(256, 1, 1); TSC_ATTR(256, 2, 1); TSC_ATTR(256, 1, 2); TSC_ATTR(256, 2, 2);
-    TSC_ATTR(512, 1, 1); TSC_ATTR(512, 2, 1); TSC_ATTR(512, 1, 2); TSC_ATTR(512, 2, 2);
-    TSC_ATTR(1024, 1, 1); TSC_ATTR(1024, 2, 1); TSC_ATTR(1024, 1, 2); TSC_ATTR(1024, 2, 2);
-#undef TSC_ATTR
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     // Workgroup size of the specialised kernels: a CU holds 16 wavefronts of this kernel (128 VGPRs), i.e. four workgroups of 256
     // threads.  With fewer instances than that the flat phase -- a latency chain per wavefront -- is spread over more wavefronts of
     // the same instance instead of leaving the slots idle (sim only, saturated large_grid: E = 256: 63.0 -> 52.5 us per control
@@ -1993,10 +2037,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     h->auto_threads = h->spec && P.help && h->threads == 256;
     h->kf_default = h->kf;
     pick_workgroup(h, n_env);
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
+    if (plan_step(h, "tsc_env_create")) return 1;            // (checks h->smem, the LDS of a fresh handle's kernels, against kLdsMax)
     TSC_HIP(hipFuncSetAttribute((const void *)reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     *out = guard.release();
     return 0;
@@ -2017,21 +2058,11 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     }
     P.rec = enable ? 1 : 0;
     h->smem = smem_bytes(P);
-    if (h->smem > 160 * 1024) return tsc::fail("tsc_env_record: LDS need %zu B > 160 KiB", h->smem);
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false, true, 4, kSpecTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false, true, 4, kSpecTrace>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true, false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, true, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    TSC_HIP(hipFuncSetAttribute((const void *)step_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
+    if (h->smem > kLdsMax) { h->plan = StepPlan(); return tsc::fail("tsc_env_record: LDS need %zu B > 160 KiB", h->smem); }
     TSC_HIP(hipFuncSetAttribute((const void *)reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
-    if ((h->cf == TSC_CF_KRAUSS || h->cf_next == TSC_CF_KRAUSS) && krauss_attrs(h)) return 1;
-    if (P.ld_int && P.rec && lane_data_attrs(h)) return 1;
-    return 0;
+    // (the Krauss and lane-data layouts need no check of their own here: with recording on a Krauss kernel takes what the IDM one
+    // takes, without it what tsc_env_set_car_following checked; lane data was checked, recording on, when it was armed)
+    return plan_step(h, "tsc_env_record");
 }
 
 // Frees a buffer this handle allocated (P.* = nullptr afterwards is the caller's)
@@ -2068,11 +2099,18 @@ int tsc_env_lane_data(tsc_env *h, int32_t period_sec, int32_t n_slot, const int3
     P.ld_slot0 = nullptr; P.ld_bound = nullptr; P.ld_sumo = nullptr; P.ld_int = nullptr; P.ld_speed = nullptr;
     P.ld_period = 0; P.ld_nslot = 0;
     h->ld_live = false; h->ld_nslot_all = 0; h->ld_nint = 0;
-    if (period_sec <= 0) return 0;                              // detached: the recording kernels without lane data run again
+    if (plan_step(h, "tsc_env_lane_data")) return 1;            // until the next reset the recording kernels without lane data run
+    if (period_sec <= 0) return 0;                              // detached
     const int nds = lane_slot0_host[P.NU];
     P.ld_period = period_sec; P.ld_nslot = nds;
     h->ld_nslot_all = n_slot; h->ld_nint = (P.episode + period_sec - 1) / period_sec;
-    if (lane_data_attrs(h)) { P.ld_period = 0; P.ld_nslot = 0; return 1; }
+    // what the reset will install, checked here (IDM and Krauss: either may be in force by then)
+    const size_t need = std::max(step_lds(P, false, true), step_lds(P, true, true));
+    if (need > kLdsMax) {
+        tsc::fail("tsc_env_lane_data: LDS need %zu B > 160 KiB (%d slots)", need, P.ld_nslot);
+        P.ld_period = 0; P.ld_nslot = 0;
+        return 1;
+    }
     UP(ld_slot0, int, lane_slot0_host, NL + 1);
     {   // a lane's piece starts 2..5 as one 16-byte LDS word per lane (the lookup: four compares)
         std::vector<float4> b((size_t)P.NU);
@@ -2134,13 +2172,13 @@ int tsc_env_trace(tsc_env *h, int32_t n_trace, const int32_t *instances_host, in
     free_alloc(h, P.trace_slot); free_alloc(h, P.trace_cnt); free_alloc(h, P.trace_rows);
     P.trace_slot = nullptr; P.trace_cnt = nullptr; P.trace_rows = nullptr; P.trace_cap = 0;
     h->n_trace = 0;
-    if (n_trace == 0) return 0;                                 // detached: the untraced recording kernels run again
+    if (n_trace == 0) return plan_step(h, "tsc_env_trace");     // detached: the untraced recording kernels run again
     UP(trace_slot, int, slot.data(), P.E);
     ALLOC(trace_cnt, int, (size_t)n_trace * (P.episode + 1));
     ALLOC(trace_rows, uint4, (size_t)n_trace * row_cap);
     P.trace_cap = row_cap;
     h->n_trace = n_trace;
-    return 0;
+    return plan_step(h, "tsc_env_trace");                       // the tracing kernels from the next step on
 }
 
 int tsc_env_read_trace(tsc_env *h, int32_t k, int32_t *counts_host, uint32_t *rows_host, int32_t max_rows, int32_t *n_rows) {
@@ -2213,7 +2251,7 @@ int tsc_env_destroy(tsc_env *h) {
 int tsc_env_set_resident_instances(tsc_env *h, int32_t n_resident) {
     if (!h || n_resident <= 0) return tsc::fail("tsc_env_set_resident_instances: bad arguments");
     pick_workgroup(h, n_resident > h->P.E ? n_resident : h->P.E);
-    return 0;
+    return plan_step(h, "tsc_env_set_resident_instances");
 }
 
 int tsc_env_set_stream(tsc_env *h, void *hip_stream) {
@@ -2255,6 +2293,7 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
         TSC_HIP(hipMemsetAsync(h->P.ld_int, 0, sizeof(int) * rows * kLdInts * h->P.ld_nslot, h->stream));
         TSC_HIP(hipMemsetAsync(h->P.ld_speed, 0, sizeof(double) * rows * h->P.ld_nslot, h->stream));
     }
+    if (plan_step(h, "tsc_env_reset")) return 1;       // the model and the lane data now in force (their setters checked the LDS)
     hipLaunchKernelGGL(reset_kernel, dim3(h->P.E), dim3(h->P.NLP), h->smem, h->stream, h->P, h->d_seeds, obs_dev);
     TSC_HIP(hipGetLastError());
     TSC_HIP(hipStreamSynchronize(h->stream));          // seeds_host may be reused by the caller
@@ -2270,7 +2309,9 @@ int tsc_env_set_car_following(tsc_env *h, int32_t model, double sigma) {
         TSC_HIP(hipStreamSynchronize(h->stream));
         ALLOC(R0, uint32_t, (size_t)P.E * kCap * P.NLP);
     }
-    if (model == TSC_CF_KRAUSS && krauss_attrs(h)) return 1;
+    // what the reset will install, checked here
+    if (model == TSC_CF_KRAUSS && step_lds(P, true, false) > kLdsMax)
+        return tsc::fail("tsc_env_set_car_following: LDS need %zu B > 160 KiB", step_lds(P, true, false));
     h->cf_next = model;
     h->sigma_next = (float)sigma;
     return 0;
@@ -2566,78 +2607,20 @@ int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *
                  double *global_reward_dev, uint8_t *done_dev, int32_t train_mode) {
     if (!h || !action_dev || !obs_dev || !reward_dev || !global_reward_dev || !done_dev)
         return tsc::fail("tsc_env_step: bad arguments");
+    const StepPlan &pl = h->plan;
+    if (!pl.v) return tsc::fail("tsc_env_step: the call that last changed the handle's configuration failed");
     tsc::ProfScope ps(tsc::KID_ENV_STEP, h->stream);
-    if (h->cf == TSC_CF_KRAUSS) {
-#define TSC_STEP_KR(MAXT, HELP, REC, KF)                                                                                \
-    hipLaunchKernelGGL((step_kernel<MAXT, HELP, REC, KF, kSpecKrauss>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr, h->stream, h->P, \
-                       action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-        const bool narrow = h->threads_kr <= 256;
-#define TSC_STEP_KRT(MAXT)                                                                                             \
-    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 1, kSpecKraussTrace>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr, h->stream, h->P, \
-                       action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-#define TSC_STEP_KRL(MAXT)                                                                                             \
-    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 1, kSpecKraussLaneData>), dim3(h->P.E), dim3(h->threads_kr), h->smem_kr_ld, h->stream, \
-                       h->P, action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-        if (h->P.rec && h->ld_live) { if (narrow) TSC_STEP_KRL(256); else TSC_STEP_KRL(1024); }
-#undef TSC_STEP_KRL
-        else if (h->P.rec && h->P.trace_slot) { if (narrow) TSC_STEP_KRT(256); else TSC_STEP_KRT(1024); }
-#undef TSC_STEP_KRT
-        else if (h->P.rec) { if (narrow) TSC_STEP_KR(256, false, true, 1); else TSC_STEP_KR(1024, false, true, 1); }
-        else if (!h->P.help) { if (narrow) TSC_STEP_KR(256, false, false, 1); else TSC_STEP_KR(1024, false, false, 1); }
-        else if (!narrow) TSC_STEP_KR(1024, true, false, 1);
-        else if (h->kf_kr == 2) TSC_STEP_KR(256, true, false, 2);
-        else if (h->kf_kr == 4) TSC_STEP_KR(256, true, false, 4);
-        else TSC_STEP_KR(256, true, false, 1);
-#undef TSC_STEP_KR
-        TSC_HIP(hipGetLastError());
-        return 0;
-    }
-#define TSC_STEP(MAXT, HELP)                                                                                       \
-    hipLaunchKernelGGL((step_kernel<MAXT, HELP>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
-                       obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-#define TSC_STEP_REC(MAXT)                                                                                         \
-    hipLaunchKernelGGL((step_kernel<MAXT, false, true>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
-                       obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-#define TSC_STEP_TRACE(MAXT)                                                                                       \
-    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 4, kSpecTrace>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
-                       obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-#define TSC_STEP_LD(MAXT)                                                                                          \
-    hipLaunchKernelGGL((step_kernel<MAXT, false, true, 4, kSpecLaneData>), dim3(h->P.E), dim3(h->threads), h->smem_ld, h->stream, h->P, \
-                       action_dev, obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-    if (h->P.rec && h->ld_live) { if (h->threads <= 256) TSC_STEP_LD(256); else TSC_STEP_LD(1024); }
-#undef TSC_STEP_LD
-    else if (h->P.rec && h->P.trace_slot) { if (h->threads <= 256) TSC_STEP_TRACE(256); else TSC_STEP_TRACE(1024); }
-#undef TSC_STEP_TRACE
-    else if (h->P.rec) { if (h->threads <= 256) TSC_STEP_REC(256); else TSC_STEP_REC(1024); }
-#define TSC_STEP_KF(KF)                                                                                           \
-    hipLaunchKernelGGL((step_kernel<256, true, false, KF>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
-                       obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-#define TSC_STEP_SPEC(MT, KF, SP)                                                                                   \
-    hipLaunchKernelGGL((step_kernel<MT, true, false, KF, SP>), dim3(h->P.E), dim3(h->threads), h->smem, h->stream, h->P, action_dev, \
-                       obs_dev, reward_dev, global_reward_dev, done_dev, (int)train_mode)
-    // specialised instantiations: workgroup size 256 (four workgroups per CU: E > 512), 512 or 1024 (fewer instances than
-    // workgroup slots: the flat phase spreads over more wavefronts instead of leaving the CU idle)
-    else if (h->P.help && h->spec && (h->kf == 1 || h->kf == 2) && (h->threads == 256 || h->threads == 512 || h->threads == 1024)) {
-        const int key = h->threads * 100 + h->kf * 10 + h->spec;
-        switch (key) {
-            case 25611: TSC_STEP_SPEC(256, 1, 1); break;   case 25621: TSC_STEP_SPEC(256, 2, 1); break;
-            case 25612: TSC_STEP_SPEC(256, 1, 2); break;   case 25622: TSC_STEP_SPEC(256, 2, 2); break;
-            case 51211: TSC_STEP_SPEC(512, 1, 1); break;   case 51221: TSC_STEP_SPEC(512, 2, 1); break;
-            case 51212: TSC_STEP_SPEC(512, 1, 2); break;   case 51222: TSC_STEP_SPEC(512, 2, 2); break;
-            case 102411: TSC_STEP_SPEC(1024, 1, 1); break; case 102421: TSC_STEP_SPEC(1024, 2, 1); break;
-            case 102412: TSC_STEP_SPEC(1024, 1, 2); break; case 102422: TSC_STEP_SPEC(1024, 2, 2); break;
-            default: return tsc::fail("tsc_env_step: no instantiation for %d threads, kf %d, spec %d", h->threads, h->kf, h->spec);
-        }
-    }
-#undef TSC_STEP_SPEC
-    else if (h->threads <= 256 && h->P.help && h->kf == 1) TSC_STEP_KF(1);
-    else if (h->threads <= 256 && h->P.help && h->kf == 2) TSC_STEP_KF(2);
-#undef TSC_STEP_KF
-    else if (h->threads <= 256) { if (h->P.help) TSC_STEP(256, true); else TSC_STEP(256, false); }
-    else { if (h->P.help) TSC_STEP(1024, true); else TSC_STEP(1024, false); }
-#undef TSC_STEP_REC
-#undef TSC_STEP
+    hipLaunchKernelGGL(pl.v->fn, dim3(h->P.E), dim3(pl.threads), pl.lds, h->stream, h->P, action_dev, obs_dev, reward_dev,
+                       global_reward_dev, done_dev, (int)train_mode);
     TSC_HIP(hipGetLastError());
+    return 0;
+}
+
+int tsc_env_step_plan(tsc_env *h, int32_t out[7]) {
+    if (!h || !out || !h->plan.v) return tsc::fail("tsc_env_step_plan: bad arguments");
+    const StepVariant &v = *h->plan.v;
+    const int32_t r[7] = {v.maxt, v.help, v.rec, v.kf, v.spec, h->plan.threads, (int32_t)h->plan.lds};
+    std::copy(r, r + 7, out);
     return 0;
 }
 

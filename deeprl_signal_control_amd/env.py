@@ -440,6 +440,13 @@ class VecTrafficEnv:
         return self.obs, reward, self.done, self.global_reward
 
     # -- debug / parity ---------------------------------------------------------------------
+    def step_plan(self):
+        """What step() launches right now (tsc_env_step_plan): the step_kernel instantiation as `row` = (MAXT, HELP, REC, KF, SPEC)
+        -- SPEC codes in include/tsc.h -- plus `threads` per workgroup and `lds_bytes`."""
+        out = (C.c_int32 * 7)()
+        _lib.check(self._L.tsc_env_step_plan(self._h, out))
+        return dict(row=tuple(out[:5]), threads=out[5], lds_bytes=out[6])
+
     def get_state(self, e=0):
         NL, NR = self.scn.n_lane, self.scn.n_stream          # pending / serial are per insertion stream
         out = dict(n=np.zeros(NL, np.int32), x=np.zeros((NL, LANE_CAP), np.float32),
@@ -727,6 +734,9 @@ class TrafficEnv:
         if self.agent in ('a2c', 'greedy') and self.train_mode:
             r = float(r[0])                                    # scalar for greedy/a2c (envs/env.py:593-594)
         return self._split(obs), r, bool(done[0].item()), float(g[0].item())
+
+    def step_plan(self):
+        return self.vec.step_plan()
 
     def terminate(self):
         pass

@@ -100,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -214,6 +214,14 @@ int tsc_env_reward_sum(tsc_env *h, double *sum_host, int32_t reset);
  * done: dev uint8 [E].  train_mode = 0 returns local rewards (envs/env.py:590-592). */
 int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *reward_dev,
                  double *global_reward_dev, uint8_t *done_dev, int32_t train_mode);
+/* Which step_kernel instantiation tsc_env_step launches right now, and how: out[] = {MAXT (workgroup bound), HELP (flat phase),
+ * REC (recording walk), KF (flat-phase vehicles per thread), SPEC, threads per workgroup, bytes of LDS}.  SPEC: 0 runtime table
+ * dimensions, 1 large_grid's and 2 Monaco's as compile-time constants, -1 Krauss, -2 trace, -3 Krauss + trace, -4 lane data,
+ * -5 Krauss + lane data (the negative ones: runtime dimensions).  Chosen when the handle is created and again by every call that
+ * changes an input of the choice (tsc_env_record, tsc_env_trace, tsc_env_lane_data, tsc_env_set_resident_instances,
+ * tsc_env_reset -- where a new car-following model and armed lane data take effect), never per step; the rules are in the header
+ * comment of csrc/tsc_env.hip and in INTEGRATION.md section 5. */
+int tsc_env_step_plan(tsc_env *h, int32_t out[7]);
 
 /* Debug / parity access: vehicle state of env `e` as dense host arrays [n_lane, TSC_LANE_CAP]
  * (front vehicle first) + counts [n_lane] + per-stream pending/serial [n_stream, = n_route without stream tables].

@@ -229,6 +229,8 @@ def test_resident_instances_hint_changes_the_launch_shape_not_the_results():
     scn = build_large_grid('ma2c')
     E = 64
     envs = [VecTrafficEnv(scn, E, seed=31), VecTrafficEnv(scn, E, seed=31, resident=2048)]
+    assert 64 <= torch.cuda.get_device_properties(0).multi_processor_count < 1024
+    assert [e_.step_plan()['threads'] for e_ in envs] == [1024, 256]
     rng = np.random.RandomState(4)
     for e_ in envs:
         e_.reset()
