@@ -44,7 +44,7 @@ _LIB = None
 # every symbol include/tsc.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = ['tsc_last_error', 'tsc_version', 'tsc_profile_enable', 'tsc_profile_select', 'tsc_profile_reset', 'tsc_profile_read',
            'tsc_profile_name', 'tsc_env_create', 'tsc_env_destroy', 'tsc_env_set_stream', 'tsc_env_set_resident_instances',
-           'tsc_env_reset', 'tsc_env_set_stream_routes', 'tsc_env_set_demand', 'tsc_env_demand', 'tsc_env_set_greedy', 'tsc_env_greedy_actions', 'tsc_env_set_pressure', 'tsc_env_pressure_actions', 'tsc_env_fixed_time_actions', 'tsc_env_set_fingerprint', 'tsc_env_bind_fingerprint', 'tsc_env_reward_sum', 'tsc_env_step', 'tsc_env_step_plan', 'tsc_env_get_state',
+           'tsc_env_reset', 'tsc_env_set_stream_routes', 'tsc_env_set_demand', 'tsc_env_demand', 'tsc_env_set_greedy', 'tsc_env_greedy_actions', 'tsc_env_set_pressure', 'tsc_env_pressure_actions', 'tsc_env_set_reward_pressure', 'tsc_env_fixed_time_actions', 'tsc_env_set_fingerprint', 'tsc_env_bind_fingerprint', 'tsc_env_reward_sum', 'tsc_env_step', 'tsc_env_step_plan', 'tsc_env_get_state',
            'tsc_env_live_vehicles', 'tsc_env_vehicle_counts', 'tsc_env_set_block_order', 'tsc_env_counters', 'tsc_env_debug_clock', 'tsc_env_live_sum', 'tsc_env_record', 'tsc_env_read_record', 'tsc_env_read_trips', 'tsc_env_trace', 'tsc_env_read_trace', 'tsc_env_lane_data', 'tsc_env_read_lane_data', 'tsc_env_set_car_following', 'tsc_env_car_following',
            'tsc_model_create', 'tsc_model_destroy', 'tsc_model_set_stream', 'tsc_model_layout', 'tsc_model_path',
            'tsc_model_set_params', 'tsc_model_reset_opt_state', 'tsc_model_debug_read', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state',
@@ -87,6 +87,7 @@ def lib():
     L.tsc_env_greedy_actions.argtypes = [vp, vp, vp]
     L.tsc_env_set_pressure.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _ip, _ip, C.c_int32, _ip]
     L.tsc_env_pressure_actions.argtypes = [vp, vp, vp]
+    L.tsc_env_set_reward_pressure.argtypes = [vp, C.c_int32, C.c_int32, _ip, _ip]
     L.tsc_env_fixed_time_actions.argtypes = [vp, C.c_int32, vp]
     L.tsc_env_bind_fingerprint.argtypes = [vp, vp]
     L.tsc_env_reward_sum.argtypes = [vp, C.POINTER(C.c_double), C.c_int32]
@@ -112,6 +113,16 @@ def lib():
     return L
 
 
+# [ENV_CONFIG] objective -> the struct's field.  'pressure' is not one of the step kernel's objectives: VecTrafficEnv arms the pressure
+# reward (tsc_env_set_reward_pressure), which overwrites whatever the step kernel computed, so the field carries TSC_OBJ_QUEUE, unused.
+OBJECTIVES = {'queue': 0, 'wait': 1, 'hybrid': 2, 'pressure': 0}
+
+
+def agent_kind(agent):
+    """include/tsc.h TSC_AGENT_*: 0 greedy / a2c (the global reward), 2 ma2c (neighbour discount), 1 everything else (IA2C / IQL)."""
+    return {'greedy': 0, 'a2c': 0, 'ma2c': 2}.get(agent, 1)
+
+
 def check(rc):
     if rc != 0:
         raise RuntimeError('libtsc: ' + lib().tsc_last_error().decode())
@@ -131,7 +142,6 @@ def scenario_struct(scn):
     nbr = np.full((A, nbr_max), -1, np.int32)
     for a, ns in enumerate(scn.neighbors):
         nbr[a, :len(ns)] = ns
-    agent_kind = {'greedy': 0, 'a2c': 0, 'ma2c': 2}.get(scn.agent, 1)
     s = TscScenario(
         n_lane=scn.n_lane, n_route=scn.n_route, n_agent=A, n_flow=len(scn.flows),
         k_max=scn.green_tab.shape[2], p_max=scn.green_tab.shape[1], l_max=scn.agent_lanes.shape[1],
@@ -150,8 +160,8 @@ def scenario_struct(scn):
         obs_src=arr(scn.obs_src, np.int32, _ip),
         control_interval_sec=scn.control_interval_sec, yellow_interval_sec=scn.yellow_interval_sec,
         episode_length_sec=scn.episode_length_sec, teleport_sec=scn.teleport_sec,
-        queue_cap=scn.queue_cap, objective={'queue': 0, 'wait': 1, 'hybrid': 2}[scn.objective],
-        agent_kind=agent_kind, realnet_scale=int(scn.reward_scale_realnet),
+        queue_cap=scn.queue_cap, objective=OBJECTIVES[scn.objective],
+        agent_kind=agent_kind(scn.agent), realnet_scale=int(scn.reward_scale_realnet),
         coop_gamma=scn.coop_gamma, norm_wave=scn.norm_wave, norm_wait=scn.norm_wait,
         clip_wave=scn.clip_wave, clip_wait=scn.clip_wait, coef_wait=scn.coef_wait,
         lane_origin=arr(scn.lane_origin, np.float32, _fp))

@@ -497,6 +497,58 @@ struct PressDev {
 };
 constexpr int kPressT = 256;       // threads per instance
 
+// The flat walk of pressure_kernel and pressure_reward_kernel (step (a) of pressure_kernel's comment): fills start / down / up for
+// instance e from the live records of the walked lanes; `part` is [kPressT] scan scratch.  Every thread of the workgroup calls it;
+// the sums are complete when it returns (it ends on a barrier).
+__device__ __forceinline__ void pressure_walk(const EnvDev &P, int e, int n_walk, int n_mov, bool queue, const short *__restrict__ walk,
+                                              const short *__restrict__ mov_of, int *start, int *down, int *up, int *part) {
+    const int t = threadIdx.x;
+    const int *N = P.N + (size_t)e * P.NLP;
+    const float4 *S = P.S + (size_t)e * kCap * P.NLP;
+    // counts of this thread's run of walked lanes, their exclusive prefix sum over the workgroup
+    const int chunk = (n_walk + kPressT - 1) / kPressT, w0 = t * chunk;
+    int local = 0;
+    for (int w = w0; w < w0 + chunk && w < n_walk; ++w) {
+        const int n = N[walk[w]];
+        local += n < 0 ? 0 : n > kCap ? kCap : n;
+    }
+    part[t] = local;
+    __syncthreads();
+    for (int d = 1; d < kPressT; d <<= 1) {
+        const int v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - local;
+    for (int w = w0; w < w0 + chunk && w < n_walk; ++w) {
+        int n = N[walk[w]];
+        n = n < 0 ? 0 : n > kCap ? kCap : n;
+        start[w] = run;
+        down[w] = queue ? 0 : n;               // count: every vehicle of the lane
+        run += n;
+    }
+    if (t == kPressT - 1) start[n_walk] = part[t];
+    for (int m = t; m < n_mov; m += kPressT) up[m] = 0;
+    __syncthreads();
+    const int total = start[n_walk];
+    for (int f = t; f < total; f += kPressT) {
+        int lo = 0, hi = n_walk;               // the last walked lane whose first record is at or before f (empty lanes repeat a start)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (start[mid] <= f) lo = mid; else hi = mid;
+        }
+        const int lane = walk[lo];
+        const float4 rec = S[vslot(f - start[lo], lane, P.NLP)];
+        if (queue && !(rec.y < kHalt)) continue;
+        const int route = (int)(__float_as_uint(rec.w) >> 16);
+        const int mv = route < P.NR ? mov_of[lane * P.NR + route] : -1;
+        if (mv >= 0) atomicAdd(&up[mv], 1);
+        if (queue) atomicAdd(&down[lo], 1);
+    }
+    __syncthreads();
+}
+
 // Max-pressure (Varaiya 2013), the rule of INTEGRATION.md "Baseline controllers": with q(vehicle) = 1 (count) or v < kHalt (queue),
 // up(movement) = sum of q over the vehicles on its incoming lane whose route takes the movement, down(lane) = sum of q over ALL
 // vehicles of the lane; the pressure of phase p is the int32 sum over the movements it serves of up - down(downstream lane); the
@@ -514,51 +566,7 @@ __global__ void __launch_bounds__(kPressT) pressure_kernel(EnvDev P, PressDev Q,
     int *prs = up + Q.n_mov;                   // [A * PMAX]
     int *part = prs + P.A * P.PMAX;            // [kPressT] scan scratch
     const int e = blockIdx.x, t = threadIdx.x;
-    const int *N = P.N + (size_t)e * P.NLP;
-    const float4 *S = P.S + (size_t)e * kCap * P.NLP;
-    const bool queue = Q.measure == TSC_PRESSURE_QUEUE;
-    // counts of this thread's run of walked lanes, their exclusive prefix sum over the workgroup
-    const int chunk = (Q.n_walk + kPressT - 1) / kPressT, w0 = t * chunk;
-    int local = 0;
-    for (int w = w0; w < w0 + chunk && w < Q.n_walk; ++w) {
-        const int n = N[Q.walk[w]];
-        local += n < 0 ? 0 : n > kCap ? kCap : n;
-    }
-    part[t] = local;
-    __syncthreads();
-    for (int d = 1; d < kPressT; d <<= 1) {
-        const int v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - local;
-    for (int w = w0; w < w0 + chunk && w < Q.n_walk; ++w) {
-        int n = N[Q.walk[w]];
-        n = n < 0 ? 0 : n > kCap ? kCap : n;
-        start[w] = run;
-        down[w] = queue ? 0 : n;               // count: every vehicle of the lane
-        run += n;
-    }
-    if (t == kPressT - 1) start[Q.n_walk] = part[t];
-    for (int m = t; m < Q.n_mov; m += kPressT) up[m] = 0;
-    __syncthreads();
-    const int total = start[Q.n_walk];
-    for (int f = t; f < total; f += kPressT) {
-        int lo = 0, hi = Q.n_walk;             // the last walked lane whose first record is at or before f (empty lanes repeat a start)
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (start[mid] <= f) lo = mid; else hi = mid;
-        }
-        const int lane = Q.walk[lo];
-        const float4 rec = S[vslot(f - start[lo], lane, P.NLP)];
-        if (queue && !(rec.y < kHalt)) continue;
-        const int route = (int)(__float_as_uint(rec.w) >> 16);
-        const int mv = route < P.NR ? Q.mov_of[lane * P.NR + route] : -1;
-        if (mv >= 0) atomicAdd(&up[mv], 1);
-        if (queue) atomicAdd(&down[lo], 1);
-    }
-    __syncthreads();
+    pressure_walk(P, e, Q.n_walk, Q.n_mov, Q.measure == TSC_PRESSURE_QUEUE, Q.walk, Q.mov_of, start, down, up, part);
     for (int i = t; i < P.A * P.PMAX; i += kPressT) {
         int sum = 0;
         for (int j = Q.srv_off[i]; j < Q.srv_off[i + 1]; ++j) {
@@ -582,6 +590,73 @@ __global__ void __launch_bounds__(kPressT) pressure_kernel(EnvDev P, PressDev Q,
         }
         *hold = h;
         action[(size_t)e * P.A + a] = h.x;
+    }
+}
+
+// Tables and accumulator of the pressure reward (tsc_env_set_reward_pressure), a kernel argument of their own like PressDev and
+// independent of it: the controller and the reward may be armed with different measures, or one without the other.
+struct PressRewDev {
+    int n_mov, n_walk;             // as in PressDev
+    int measure;                   // TSC_PRESSURE_*
+    const short *walk;             // [n_walk]
+    const short *mov_of;           // [NL * NR]
+    const short *mov_dn;           // [n_mov]
+    const int *agt_off;            // [A + 1] agent a owns the movements agt_mov[agt_off[a] .. agt_off[a + 1])
+    const short *agt_mov;
+    double *acc;                   // [E] running sum of the global pressure reward (tsc_env_reward_sum while armed)
+};
+
+// The pressure reward, the rule of INTEGRATION.md "Pressure reward": P[a] = int32 sum over the agent's movements of up - down(downstream
+// lane) on the state step_kernel left, r[a] = -|P[a]|, g = sum of r; the returned reward is shaped as step_kernel shapes its own
+// (K6).  Runs behind step_kernel on the same stream and overwrites reward / greward; reads EnvDev, writes nothing else but R.acc.
+// One workgroup per instance: the walk of pressure_kernel, then one thread per agent sums its movements, one thread forms g, one
+// thread per agent shapes and stores.  r and g are integers in float64: no order of addition can change them.
+__global__ void __launch_bounds__(kPressT) pressure_reward_kernel(EnvDev P, PressRewDev R, double *__restrict__ reward,
+                                                                  double *__restrict__ greward, int train_mode) {
+    extern __shared__ __attribute__((aligned(16))) char prw_raw[];
+    double *r = (double *)prw_raw;             // [A + 1] local rewards, then g
+    int *start = (int *)(r + P.A + 1);         // [n_walk + 1]
+    int *down = start + R.n_walk + 1;          // [n_walk]
+    int *up = down + R.n_walk;                 // [n_mov]
+    int *part = up + R.n_mov;                  // [kPressT]
+    const int e = blockIdx.x, t = threadIdx.x;
+    pressure_walk(P, e, R.n_walk, R.n_mov, R.measure == TSC_PRESSURE_QUEUE, R.walk, R.mov_of, start, down, up, part);
+    for (int a = t; a < P.A; a += kPressT) {
+        int sum = 0;
+        for (int j = R.agt_off[a]; j < R.agt_off[a + 1]; ++j) {
+            const int mv = R.agt_mov[j];
+            sum += up[mv] - down[R.mov_dn[mv]];
+        }
+        r[a] = (double)(sum < 0 ? sum : -sum);
+    }
+    __syncthreads();
+    if (t == 0) {
+        double g = 0.0;
+        for (int a = 0; a < P.A; ++a) g += r[a];
+        r[P.A] = g; greward[e] = g; R.acc[e] += g;
+    }
+    __syncthreads();
+    for (int a = t; a < P.A; a += kPressT) {
+        const double g = r[P.A];
+        double out;
+        if (!train_mode) {
+            out = r[a];
+        } else if (P.agent_kind == TSC_AGENT_GREEDY) {
+            out = g;
+        } else if (P.agent_kind == TSC_AGENT_GLOBAL) {
+            out = P.realnet_scale ? g / (double)(P.A * 20) : g;
+        } else {
+            double cur = r[a];
+            int deg = 0;
+            for (int j = 0; j < P.NBR; ++j) {
+                const int nb = P.nbr[a * P.NBR + j];
+                if (nb < 0) break;
+                cur += P.coop_gamma * r[nb];
+                ++deg;
+            }
+            out = P.realnet_scale ? cur / (double)((1 + deg) * 20) : cur;
+        }
+        reward[(size_t)e * P.A + a] = out;
     }
 }
 
@@ -1660,6 +1735,9 @@ struct tsc_env {
     PressDev Q = {};
     size_t smem_press = 0;
     std::vector<int> h_nphase;      // host copy of agent_nphase (tsc_env_set_pressure checks the served lists against it)
+    // pressure reward (tsc_env_set_reward_pressure): its tables and accumulator, R.acc null until armed; LDS of pressure_reward_kernel
+    PressRewDev R = {};
+    size_t smem_prew = 0;
 };
 
 // TSC_ENV_THREADS / TSC_ENV_KF (measurement / test knobs) over the library's own choice
@@ -1772,13 +1850,13 @@ const char *tsc_profile_name(int32_t id) {
     static const char *names[] = {"env_step", "fc_gemm", "zx_gemm", "lstm_fwd", "head_fwd", "sample", "add_transition",
                                   "returns", "head_bwd", "lstm_bwd", "dwo_gemm", "dwh_gemm", "dwx_gemm", "dx1_gemm",
                                   "dw1_gemm", "grad_norm", "rmsprop", "transpose_wx", "fingerprint", "policy_fwd_fused",
-                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "pressure", "demand",
+                                  "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "pressure", "pressure_reward", "demand",
                                   "gae", "head_bwd_ppo"};
     static_assert(sizeof(names) / sizeof(names[0]) == tsc::KID_COUNT, "one name per kernel id");
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 113; }      // 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 114; }      // 1.14: tsc_env_set_reward_pressure; 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 #define UP(field, T, src, count)                                                 \
     do {                                                                         \
@@ -2455,11 +2533,15 @@ int tsc_env_reward_sum(tsc_env *h, double *sum_host, int32_t reset) {
     if (!h || !sum_host) return tsc::fail("tsc_env_reward_sum: bad arguments");
     TSC_HIP(hipStreamSynchronize(h->stream));
     std::vector<double> acc(h->P.E);
-    TSC_HIP(hipMemcpy(acc.data(), h->P.reward_acc, sizeof(double) * h->P.E, hipMemcpyDeviceToHost));
+    // armed pressure reward: its own accumulator (step_kernel keeps adding the built-in reward to reward_acc, which nobody reads then)
+    TSC_HIP(hipMemcpy(acc.data(), h->R.acc ? h->R.acc : h->P.reward_acc, sizeof(double) * h->P.E, hipMemcpyDeviceToHost));
     double t = 0;
     for (double v : acc) t += v;
     *sum_host = t;
-    if (reset) TSC_HIP(hipMemset(h->P.reward_acc, 0, sizeof(double) * h->P.E));
+    if (reset) {
+        TSC_HIP(hipMemset(h->P.reward_acc, 0, sizeof(double) * h->P.E));
+        if (h->R.acc) TSC_HIP(hipMemset(h->R.acc, 0, sizeof(double) * h->P.E));
+    }
     return 0;
 }
 
@@ -2515,24 +2597,24 @@ int tsc_env_greedy_actions(tsc_env *h, const float *obs_dev, int32_t *action_dev
     return 0;
 }
 
-int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov,
-                         int32_t srv_max, const int32_t *served) {
-    if (!h || !mov || !lane_route_mov || !served || n_mov < 0 || srv_max <= 0) return tsc::fail("tsc_env_set_pressure: bad arguments");
+// The range checks and the compiled movement tables that tsc_env_set_pressure and tsc_env_set_reward_pressure share: walk = the
+// lanes that appear in a movement, ascending; mov_of = lane_route_mov as 16-bit values; mov_dn = a movement's downstream lane as an
+// index into walk.  `who` names the caller in the error.  Changes nothing of the handle.
+static int compile_movements(const char *who, const EnvDev &P, int measure, int n_mov, const int32_t *mov, const int32_t *lane_route_mov,
+                             std::vector<short> &walk, std::vector<short> &mov_of, std::vector<short> &mov_dn) {
     if (measure != TSC_PRESSURE_COUNT && measure != TSC_PRESSURE_QUEUE)
-        return tsc::fail("tsc_env_set_pressure: measure %d is neither TSC_PRESSURE_COUNT (0) nor TSC_PRESSURE_QUEUE (1)", measure);
-    if (min_green < 1) return tsc::fail("tsc_env_set_pressure: min_green %d must be >= 1", min_green);
-    const EnvDev &P = h->P;
+        return tsc::fail("%s: measure %d is neither TSC_PRESSURE_COUNT (0) nor TSC_PRESSURE_QUEUE (1)", who, measure);
     if (n_mov > 4096 || P.A * P.PMAX > 4096)
-        return tsc::fail("tsc_env_set_pressure: %d movements, %d (agent, phase) pairs: at most 4096 each", n_mov, P.A * P.PMAX);
+        return tsc::fail("%s: %d movements, %d (agent, phase) pairs: at most 4096 each", who, n_mov, P.A * P.PMAX);
     std::vector<int> widx((size_t)P.NL, -1);
     for (int i = 0; i < n_mov; ++i) {
         const int a = mov[4 * i], l = mov[4 * i + 1], m = mov[4 * i + 2], k = mov[4 * i + 3];
-        if (a < 0 || a >= P.A) return tsc::fail("tsc_env_set_pressure: movement %d names agent %d of %d", i, a, P.A);
-        if (l < 0 || l >= P.NL || m < 0 || m >= P.NL) return tsc::fail("tsc_env_set_pressure: movement %d names lanes %d -> %d of %d", i, l, m, P.NL);
-        if (k < 0 || k >= P.KMAX) return tsc::fail("tsc_env_set_pressure: movement %d names signal link %d of %d", i, k, P.KMAX);
+        if (a < 0 || a >= P.A) return tsc::fail("%s: movement %d names agent %d of %d", who, i, a, P.A);
+        if (l < 0 || l >= P.NL || m < 0 || m >= P.NL) return tsc::fail("%s: movement %d names lanes %d -> %d of %d", who, i, l, m, P.NL);
+        if (k < 0 || k >= P.KMAX) return tsc::fail("%s: movement %d names signal link %d of %d", who, i, k, P.KMAX);
         widx[l] = widx[m] = 0;
     }
-    std::vector<short> walk, mov_of((size_t)P.NL * P.NR), mov_dn((size_t)n_mov), srv;
+    walk.clear(); mov_of.assign((size_t)P.NL * P.NR, 0); mov_dn.assign((size_t)n_mov, 0);
     for (int l = 0; l < P.NL; ++l)
         if (widx[l] == 0) { widx[l] = (int)walk.size(); walk.push_back((short)l); }
     for (int i = 0; i < n_mov; ++i) mov_dn[i] = (short)widx[mov[4 * i + 2]];
@@ -2540,9 +2622,30 @@ int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t
         for (int r = 0; r < P.NR; ++r) {
             const int i = lane_route_mov[(size_t)l * P.NR + r];
             if (i < -1 || i >= n_mov || (i >= 0 && mov[4 * i + 1] != l))
-                return tsc::fail("tsc_env_set_pressure: lane %d route %d names movement %d of %d (or one of another lane)", l, r, i, n_mov);
+                return tsc::fail("%s: lane %d route %d names movement %d of %d (or one of another lane)", who, l, r, i, n_mov);
             mov_of[(size_t)l * P.NR + r] = (short)i;
         }
+    return 0;
+}
+
+// frees the listed device tables of the handle (a second arming call replaces them)
+static void free_tables(tsc_env *h, std::initializer_list<const void *> olds) {
+    for (const void *old : olds) {
+        if (!old) continue;
+        for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
+            if (*it == old) { (void)hipFree(*it); h->allocs.erase(it); break; }
+    }
+}
+
+int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov,
+                         int32_t srv_max, const int32_t *served) {
+    if (!h || !mov || !lane_route_mov || !served || n_mov < 0 || srv_max <= 0) return tsc::fail("tsc_env_set_pressure: bad arguments");
+    if (measure != TSC_PRESSURE_COUNT && measure != TSC_PRESSURE_QUEUE)
+        return tsc::fail("tsc_env_set_pressure: measure %d is neither TSC_PRESSURE_COUNT (0) nor TSC_PRESSURE_QUEUE (1)", measure);
+    if (min_green < 1) return tsc::fail("tsc_env_set_pressure: min_green %d must be >= 1", min_green);
+    const EnvDev &P = h->P;
+    std::vector<short> walk, mov_of, mov_dn, srv;
+    if (compile_movements("tsc_env_set_pressure", P, measure, n_mov, mov, lane_route_mov, walk, mov_of, mov_dn)) return 1;
     std::vector<int> off((size_t)P.A * P.PMAX + 1, 0);
     for (int a = 0; a < P.A; ++a)
         for (int p = 0; p < P.PMAX; ++p) {
@@ -2560,11 +2663,7 @@ int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t
     (void)hipSetDevice(h->device);
     TSC_HIP(hipStreamSynchronize(h->stream));                  // a running pressure_kernel may still read the old tables
     PressDev &Q = h->Q;
-    for (const void *old : {(const void *)Q.walk, (const void *)Q.mov_of, (const void *)Q.mov_dn, (const void *)Q.srv_off, (const void *)Q.srv}) {
-        if (!old) continue;
-        for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
-            if (*it == old) { (void)hipFree(*it); h->allocs.erase(it); break; }
-    }
+    free_tables(h, {Q.walk, Q.mov_of, Q.mov_dn, Q.srv_off, Q.srv});
     Q.walk = nullptr; Q.mov_of = nullptr; Q.mov_dn = nullptr; Q.srv_off = nullptr; Q.srv = nullptr;
 #define UPQ(field, T, vec)                                                       \
     do {                                                                         \
@@ -2594,6 +2693,57 @@ int tsc_env_pressure_actions(tsc_env *h, int32_t *action_dev, int32_t *pressure_
     return 0;
 }
 
+int tsc_env_set_reward_pressure(tsc_env *h, int32_t measure, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov) {
+    if (!h) return tsc::fail("tsc_env_set_reward_pressure: null handle");
+    PressRewDev &R = h->R;
+    const EnvDev &P = h->P;
+    if (measure == -1) {                                       // disarm: tsc_env_step and tsc_env_reward_sum return to the built-in reward
+        if (!R.acc) return 0;
+        (void)hipSetDevice(h->device);
+        TSC_HIP(hipStreamSynchronize(h->stream));              // a running pressure_reward_kernel still reads the tables
+        free_tables(h, {R.walk, R.mov_of, R.mov_dn, R.agt_off, R.agt_mov, R.acc});
+        R = PressRewDev();
+        h->smem_prew = 0;
+        // the built-in sum starts over: what step_kernel added to it while the pressure reward was returned is no part of either sum
+        TSC_HIP(hipMemset(P.reward_acc, 0, sizeof(double) * P.E));
+        return 0;
+    }
+    if (!mov || !lane_route_mov || n_mov < 0) return tsc::fail("tsc_env_set_reward_pressure: bad arguments (null tables with measure %d)", measure);
+    std::vector<short> walk, mov_of, mov_dn, agt_mov;
+    if (compile_movements("tsc_env_set_reward_pressure", P, measure, n_mov, mov, lane_route_mov, walk, mov_of, mov_dn)) return 1;
+    std::vector<int> off((size_t)P.A + 1, 0);                  // agent -> movements, each agent's in ascending order
+    for (int a = 0; a < P.A; ++a) {
+        for (int i = 0; i < n_mov; ++i)
+            if (mov[4 * i] == a) agt_mov.push_back((short)i);
+        off[(size_t)a + 1] = (int)agt_mov.size();
+    }
+    const size_t smem = sizeof(double) * ((size_t)P.A + 1) + sizeof(int) * (2 * walk.size() + 1 + (size_t)n_mov + kPressT);
+    if (smem > 48 * 1024) return tsc::fail("tsc_env_set_reward_pressure: LDS need %zu B > 48 KiB (%zu walked lanes, %d movements)", smem, walk.size(), n_mov);
+    (void)hipSetDevice(h->device);
+    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running pressure_reward_kernel may still read the old tables
+    free_tables(h, {R.walk, R.mov_of, R.mov_dn, R.agt_off, R.agt_mov});
+    R.walk = nullptr; R.mov_of = nullptr; R.mov_dn = nullptr; R.agt_off = nullptr; R.agt_mov = nullptr;
+#define UPR(field, T, vec)                                                       \
+    do {                                                                         \
+        T *d_ = nullptr;                                                         \
+        TSC_HIP(tsc::upload<T>(&d_, (vec).data(), (vec).size()));                \
+        h->allocs.push_back(d_);                                                 \
+        R.field = d_;                                                            \
+    } while (0)
+    UPR(walk, short, walk); UPR(mov_of, short, mov_of); UPR(mov_dn, short, mov_dn); UPR(agt_off, int, off); UPR(agt_mov, short, agt_mov);
+#undef UPR
+    R.n_mov = n_mov; R.n_walk = (int)walk.size(); R.measure = measure;
+    h->smem_prew = smem;
+    if (!R.acc) {                                              // armed from here on: the pressure sum starts at zero
+        double *acc = nullptr;
+        TSC_HIP(hipMalloc((void **)&acc, sizeof(double) * (size_t)P.E));
+        h->allocs.push_back(acc);
+        TSC_HIP(hipMemset(acc, 0, sizeof(double) * (size_t)P.E));
+        R.acc = acc;
+    }
+    return 0;
+}
+
 int tsc_env_fixed_time_actions(tsc_env *h, int32_t steps_per_phase, int32_t *action_dev) {
     if (!h || !action_dev) return tsc::fail("tsc_env_fixed_time_actions: bad arguments");
     if (steps_per_phase < 1) return tsc::fail("tsc_env_fixed_time_actions: steps_per_phase %d must be >= 1", steps_per_phase);
@@ -2609,10 +2759,20 @@ int tsc_env_step(tsc_env *h, const int32_t *action_dev, float *obs_dev, double *
         return tsc::fail("tsc_env_step: bad arguments");
     const StepPlan &pl = h->plan;
     if (!pl.v) return tsc::fail("tsc_env_step: the call that last changed the handle's configuration failed");
-    tsc::ProfScope ps(tsc::KID_ENV_STEP, h->stream);
-    hipLaunchKernelGGL(pl.v->fn, dim3(h->P.E), dim3(pl.threads), pl.lds, h->stream, h->P, action_dev, obs_dev, reward_dev,
-                       global_reward_dev, done_dev, (int)train_mode);
+    {
+        tsc::ProfScope ps(tsc::KID_ENV_STEP, h->stream);
+        hipLaunchKernelGGL(pl.v->fn, dim3(h->P.E), dim3(pl.threads), pl.lds, h->stream, h->P, action_dev, obs_dev, reward_dev,
+                           global_reward_dev, done_dev, (int)train_mode);
+    }
     TSC_HIP(hipGetLastError());
+    if (h->R.acc) {                                    // tsc_env_set_reward_pressure: the rewards of the state the step left
+        {
+            tsc::ProfScope ps(tsc::KID_PRESSURE_REWARD, h->stream);
+            hipLaunchKernelGGL(pressure_reward_kernel, dim3(h->P.E), dim3(kPressT), h->smem_prew, h->stream, h->P, h->R, reward_dev,
+                               global_reward_dev, (int)train_mode);
+        }
+        TSC_HIP(hipGetLastError());
+    }
     return 0;
 }
 

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scenario import LANE_CAP, Scenario, build_scenario
+from .scenario import LANE_CAP, OBJECTIVES, PRESSURE_MEASURES, Scenario, build_scenario
 
 TRACE_ROW_CAP = 1 << 22           # default trajectory rows per traced instance (64 MiB; large_grid's busiest episodes need ~2 M)
 FCD_COLUMNS = ('episode', 'time_sec', 'id', 'lane', 'pos', 'speed')
@@ -71,6 +71,9 @@ class VecTrafficEnv:
         if model != 'idm':                  # (IDM handles never call it: they run exactly the kernels they always ran)
             car_following_kw(model, scn.krauss_sigma)
             _lib.check(L.tsc_env_set_car_following(h, CAR_FOLLOWING_MODELS.index(model), float(scn.krauss_sigma)))
+        self.reward_pressure = None         # the measure of the armed pressure reward (set_reward_pressure), None = the built-in reward
+        if scn.objective == 'pressure':     # (the other objectives never call it: they run exactly what they always ran)
+            self.set_reward_pressure(scn.pressure_measure)
         if resident is not None:        # env instances sharing the device with these (other handles / ranks), these included
             _lib.check(L.tsc_env_set_resident_instances(h, int(resident)))
         with torch.cuda.device(self.device):
@@ -405,6 +408,25 @@ class VecTrafficEnv:
                                                     C.c_void_p(prs.data_ptr()) if return_pressure else None))
         return (out, prs) if return_pressure else out
 
+    def set_reward_pressure(self, measure):
+        """The pressure reward (tsc_env_set_reward_pressure, pressure_reward_kernel; the rule: INTEGRATION.md "Pressure reward"):
+        measure 'count' | 'queue' arms it -- from the next step() on, reward and global_reward are r[a] = -|P[a]| over the state the step
+        left, shaped like the built-in reward, and reward_sum() sums its g from zero; None disarms, back to the scenario's built-in
+        objective, whose reward_sum() starts over.  Neither sum spans the change: do not switch mid-episode if the sum matters.
+        A scenario with objective = 'pressure' is armed at construction with its pressure_measure.  Independent of
+        max_pressure_actions."""
+        if measure is None:
+            _lib.check(self._L.tsc_env_set_reward_pressure(self._h, -1, 0, None, None))
+            self.reward_pressure = None
+            return
+        kw = pressure_kw(measure)
+        tabs = self.scn.pressure_tables()
+        ip = C.POINTER(C.c_int32)
+        mov, lrm = (np.ascontiguousarray(tabs[k], np.int32) for k in ('mov', 'lane_route_mov'))
+        _lib.check(self._L.tsc_env_set_reward_pressure(self._h, PRESSURE_MEASURES.index(kw['pressure_measure']), len(mov),
+                                                       mov.ctypes.data_as(ip), lrm.ctypes.data_as(ip)))
+        self.reward_pressure = kw['pressure_measure']
+
     def fixed_time_actions(self, steps_per_phase, out=None):
         """The fixed-time cycle for every instance (fixed_time_kernel): action[e, a] = (t // steps_per_phase) % n_phase[a] with t
         the control steps taken since reset() -> int32 [E, A]."""
@@ -571,7 +593,6 @@ def car_following_kw(model, sigma=None):
 
 
 CONTROLLERS = ('greedy', 'maxpressure', 'fixedtime')     # evaluate --agents names that need no learner (main.py)
-PRESSURE_MEASURES = ('count', 'queue')                   # include/tsc.h TSC_PRESSURE_COUNT / TSC_PRESSURE_QUEUE
 
 
 def pressure_kw(measure=None, min_green=None):
@@ -590,6 +611,21 @@ def _positive_int(key, v):
     if n < 1:
         raise ValueError('[ENV_CONFIG] %s = %r: must be an integer >= 1' % (key, v))
     return n
+
+
+def objective_kw(objective=None, measure=None):
+    """[ENV_CONFIG] objective = queue | wait | hybrid | pressure -> Scenario keywords; a missing key keeps the scenario's own default.
+    Under pressure the measure is pressure_measure = count | queue (default count), the key the max-pressure controller reads, so one
+    config trains and evaluates on the same measure."""
+    kw = {}
+    if objective is not None:
+        objective = str(objective).strip()
+        if objective not in OBJECTIVES:
+            raise ValueError('[ENV_CONFIG] objective = %r: allowed values are %s' % (objective, ' | '.join(OBJECTIVES)))
+        kw['objective'] = objective
+    if measure is not None:
+        kw['pressure_measure'] = pressure_kw(measure)['pressure_measure']
+    return kw
 
 
 def controller_kw(config):
@@ -616,9 +652,10 @@ def scenario_from_config(config):
     kw = {}
     for k, typ in list(ENV_CONFIG_KEYS.items()) + list(SCENARIO_KEYS.get(name, {}).items()):
         v = get(k)
-        if v is not None and k not in ('car_following', 'krauss_sigma'):
+        if v is not None and k not in ('car_following', 'krauss_sigma', 'objective'):
             kw[k] = typ(float(v)) if typ is int else typ(v)
     kw.update(car_following_kw(get('car_following'), get('krauss_sigma')))
+    kw.update(objective_kw(get('objective'), get('pressure_measure')))
     seed = int(get('seed'))
     test_seeds = tuple(int(x) for x in str(get('test_seeds')).split(','))
     return build_scenario(name, agent, **kw), seed, test_seeds
@@ -737,6 +774,10 @@ class TrafficEnv:
 
     def step_plan(self):
         return self.vec.step_plan()
+
+    def set_reward_pressure(self, measure):
+        """VecTrafficEnv.set_reward_pressure: 'count' | 'queue' arms the pressure reward, None returns to the built-in one."""
+        self.vec.set_reward_pressure(measure)
 
     def terminate(self):
         pass

@@ -44,6 +44,10 @@ DET_LEN = 50.0       # lane-area detector covers the last 50 m
 NO_LANE = -1
 
 
+OBJECTIVES = ('queue', 'wait', 'hybrid', 'pressure')      # [ENV_CONFIG] objective: the reference's three and the pressure reward
+PRESSURE_MEASURES = ('count', 'queue')                   # include/tsc.h TSC_PRESSURE_COUNT / TSC_PRESSURE_QUEUE
+
+
 @dataclass
 class Scenario:
     name: str
@@ -96,7 +100,8 @@ class Scenario:
     clip_wave: float = 2.0
     clip_wait: float = 2.0
     coef_wait: float = 0.2
-    objective: str = 'hybrid'
+    objective: str = 'hybrid'        # queue | wait | hybrid (the reference's, envs/env.py:325-367) | pressure (INTEGRATION.md "Pressure reward")
+    pressure_measure: str = 'count'  # count | queue: what a vehicle counts for under objective = pressure (and the max-pressure controller)
     has_wait_state: bool = True
     queue_cap: int = -1              # real_net: min(10, halting)   (env.py:332-333)
     reward_scale_realnet: bool = False
@@ -124,6 +129,10 @@ class Scenario:
     lane_pieces: List = None
 
     def __post_init__(self):
+        if self.objective not in OBJECTIVES:
+            raise ValueError('[ENV_CONFIG] objective = %r: allowed values are %s' % (self.objective, ' | '.join(OBJECTIVES)))
+        if self.pressure_measure not in PRESSURE_MEASURES:
+            raise ValueError('[ENV_CONFIG] pressure_measure = %r: allowed values are %s' % (self.pressure_measure, ' | '.join(PRESSURE_MEASURES)))
         if self.lane_origin is None:
             self.lane_origin = np.zeros(len(self.lane_names), np.float32)
         if self.lane_pieces is None:
@@ -1420,7 +1429,7 @@ def sort_lanes_by_load(scn: Scenario) -> Scenario:
 # the keys of a scenario that set its demand (what DemandSampler scales)
 DEMAND_KEYS = {'large_grid': ('peak_flow1', 'peak_flow2'), 'real_net': ('flow_rate',), 'small_grid': ('num_extra_car_per_hour',)}
 _ENV_FIELDS = ('control_interval_sec', 'yellow_interval_sec', 'episode_length_sec', 'coop_gamma', 'norm_wave', 'norm_wait',
-               'clip_wave', 'clip_wait', 'coef_wait', 'objective', 'car_following', 'krauss_sigma')
+               'clip_wave', 'clip_wait', 'coef_wait', 'objective', 'pressure_measure', 'car_following', 'krauss_sigma')
 
 
 def demand_kw(scales=None, jitter=None):

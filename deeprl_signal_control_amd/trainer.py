@@ -418,6 +418,62 @@ def max_pressure_actions(scn, state, measure='count', return_pressure=False):
     return (action, pressure) if return_pressure else action
 
 
+def shape_reward(scn, r, agent_kind=None, train_mode=True):
+    """The reference's reward shaping (envs/env.py:589-631; step_kernel K6) over one instance's local rewards r float64 [A] ->
+    (reward float64 [A], g).  g = sum of r; train_mode off returns r; agent kind greedy returns g; global (IA2C / IQL) returns g,
+    on Monaco (reward_scale_realnet) g / (A * 20); otherwise (MA2C) cur = r[a], then cur += coop_gamma * r[nb] per neighbour in
+    list order, on Monaco cur / ((1 + deg) * 20).  agent_kind: an agent name ('greedy', 'a2c', 'ia2c', 'iqld', 'iqll', 'ma2c'),
+    default scn.agent.  Plain float64 operations in this order, the device's."""
+    from ._lib import agent_kind as kind_of
+    kind = kind_of(scn.agent if agent_kind is None else agent_kind)
+    r = np.asarray(r, np.float64)
+    A = len(r)
+    g = np.float64(0.0)
+    for a in range(A):
+        g = g + r[a]
+    if not train_mode:
+        return r.copy(), g
+    out = np.zeros(A, np.float64)
+    for a in range(A):
+        if kind == 0:
+            out[a] = g
+        elif kind == 1:
+            out[a] = g / np.float64(A * 20) if scn.reward_scale_realnet else g
+        else:
+            cur = r[a]
+            for nb in scn.neighbors[a]:
+                cur = cur + np.float64(scn.coop_gamma) * r[int(nb)]
+            out[a] = cur / np.float64((1 + len(scn.neighbors[a])) * 20) if scn.reward_scale_realnet else cur
+    return out, g
+
+
+def pressure_reward(scn, state, measure='count', agent_kind=None, train_mode=True):
+    """HOST restatement of the pressure reward (INTEGRATION.md "Pressure reward") over one instance's vehicle state, a
+    VecTrafficEnv.get_state dict taken after the step, and Scenario.pressure_tables -- what pressure_reward_kernel computes on the
+    device (VecTrafficEnv.set_reward_pressure / objective = pressure, the product path).  For host arrays only: CPU tools and tests.
+    up / down and the measure as in max_pressure_actions; P[a] = int32 sum over the movements of agent a of up - down(downstream
+    lane), r[a] = -|P[a]| as float64, g = sum of r; the returned reward is r shaped by shape_reward.  -> (reward float64 [A], g, P
+    int32 [A])."""
+    if any(torch.is_tensor(v) for v in state.values()):
+        raise TypeError('pressure_reward is the host restatement; device state goes through VecTrafficEnv.set_reward_pressure (HIP)')
+    if measure not in ('count', 'queue'):
+        raise ValueError('measure = %r: allowed values are count | queue' % (measure,))
+    tabs = scn.pressure_tables()
+    n = np.asarray(state['n'])
+    live = np.arange(np.asarray(state['v']).shape[1])[None, :] < n[:, None]
+    q = live & (np.asarray(state['v'], np.float32) < np.float32(0.1)) if measure == 'queue' else live
+    down = q.sum(1)
+    up = np.zeros(len(tabs['mov']), np.int64)
+    lanes, slots = np.nonzero(q)
+    mv = tabs['lane_route_mov'][lanes, np.asarray(state['r'])[lanes, slots]]
+    np.add.at(up, mv[mv >= 0], 1)
+    P = np.zeros(scn.n_agent, np.int32)
+    for i, (a, _l, m, _k) in enumerate(tabs['mov'].tolist()):
+        P[a] += up[i] - down[m]
+    reward, g = shape_reward(scn, (-np.abs(P)).astype(np.float64), agent_kind, train_mode)
+    return reward, g, P
+
+
 def pressure_hold(cur, age, p_star, min_green):
     """The max-pressure hold (min_green = g >= 1 control steps) for one agent: (cur, age) and this step's argmax p* -> (action, cur,
     age).  age < g: the phase is held; otherwise p* is taken, a change restarting the count.  reset() sets age = g."""

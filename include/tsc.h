@@ -36,7 +36,7 @@ extern "C" {
 enum { TSC_AGENT_GREEDY = 0, TSC_AGENT_GLOBAL = 1 /* ia2c, iql */, TSC_AGENT_MA2C = 2 };
 enum { TSC_OBJ_QUEUE = 0, TSC_OBJ_WAIT = 1, TSC_OBJ_HYBRID = 2 };
 enum { TSC_CF_IDM = 0, TSC_CF_KRAUSS = 1 };        /* car-following model (tsc_env_set_car_following) */
-enum { TSC_PRESSURE_COUNT = 0, TSC_PRESSURE_QUEUE = 1 };   /* what a vehicle counts for under max-pressure (tsc_env_set_pressure) */
+enum { TSC_PRESSURE_COUNT = 0, TSC_PRESSURE_QUEUE = 1 };   /* what a vehicle counts for under max-pressure (tsc_env_set_pressure, tsc_env_set_reward_pressure) */
 
 /* Dense scenario tables (host pointers, copied at create time).  Produced by
  * deeprl_signal_control_amd/scenario.py; meaning and reference provenance of every
@@ -100,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -200,12 +200,28 @@ int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t
  * [E, A]; pressure (nullable) dev int32 [E, A, p_max], padded phases 0.  ONE CALL PER CONTROL STEP: a call advances the hold state
  * (cur, age) whenever min_green > 1.  Changes nothing of the simulation. */
 int tsc_env_pressure_actions(tsc_env *h, int32_t *action_dev, int32_t *pressure_dev);
+/* The pressure reward (PressLight / MPLight; no reference counterpart; INTEGRATION.md "Pressure reward" states the rule).  mov and
+ * lane_route_mov are tsc_env_set_pressure's (host pointers, int32, copied), up / down and the two measures as there.  While armed,
+ * tsc_env_step launches step_kernel exactly as otherwise and then pressure_reward_kernel on the same stream, which OVERWRITES
+ * reward_dev and global_reward_dev from the state the step left: P[a] = int32 sum over the movements of agent a of up - down(m),
+ * r[a] = -|P[a]|, global_reward[e] = g = sum of r; reward[e, a] is r shaped by the call's train_mode, the agent kind, coop_gamma and
+ * realnet_scale exactly as the built-in reward is (queue_cap, coef_wait, norm_wait and clip_wait play no part).  Observations, done,
+ * the vehicle state, counters, recording, trace and lane data are untouched.  tsc_env_reward_sum then returns the sum of g, kept in an
+ * accumulator of its own that starts at zero when the handle is armed.  measure = -1 disarms (the pointers may be NULL): rewards and
+ * tsc_env_reward_sum return to the built-in reward, whose sum starts over at zero.  Arming and disarming take effect at the next
+ * tsc_env_step; neither sum spans the change, so arm before an episode if the sum matters.  Independent of tsc_env_set_pressure:
+ * tables, measure and hold state of the controller are separate, either may be armed without the other.  Runs the range checks of
+ * tsc_env_set_pressure before anything changes (non-zero and tsc_last_error on a bad measure, agent, lane, link or movement, or NULL
+ * tables with measure >= 0; the handle keeps what it had).  Synchronises before replacing tables.  A handle that never calls it
+ * allocates nothing and launches nothing more. */
+int tsc_env_set_reward_pressure(tsc_env *h, int32_t measure, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov);
 /* Fixed-time cycle: action[e, a] = (t / steps_per_phase) % n_phase[a], t = simulated seconds of instance e / control_interval_sec at
  * the time of the call.  action dev int32 [E, A]; steps_per_phase >= 1.  Needs no tables. */
 int tsc_env_fixed_time_actions(tsc_env *h, int32_t steps_per_phase, int32_t *action_dev);
 
 /* Sum over instances and control steps of the global reward since the last reset of the accumulator
- * (what Trainer logs per episode, utils.py:161,296-305).  Synchronises. */
+ * (what Trainer logs per episode, utils.py:161,296-305): the per-instance sums, each accumulated in step order, added in instance
+ * order.  Of the pressure reward's g while tsc_env_set_reward_pressure is armed.  Synchronises. */
 int tsc_env_reward_sum(tsc_env *h, double *sum_host, int32_t reset);
 
 /* step(action), envs/env.py:566-631: yellow FSM -> 2 sim-steps -> green -> 3 sim-steps

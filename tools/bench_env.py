@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """Sim-only timing of the env kernel (tsc_env_step) at a realistic traffic state.
-    python tools/bench_env.py [E] [steps] [--controller random|greedy|maxpressure|fixedtime]
+    python tools/bench_env.py [E] [steps] [--controller random|greedy|maxpressure|fixedtime] [--reward-pressure count|queue]
 
 --controller: what chooses the actions of the warm-up and timed loops.  random (the default) replays 16 precomputed random action
 tensors, so the loop times tsc_env_step alone; the others launch that controller's kernel in front of every step, as an evaluation
-does (greedy_kernel on the observation, pressure_kernel on the vehicle state, fixed_time_kernel on the clock)."""
+does (greedy_kernel on the observation, pressure_kernel on the vehicle state, fixed_time_kernel on the clock).
+--reward-pressure: arm the pressure reward with that measure on every handle (pressure_reward_kernel behind every step)."""
 import os
 import sys
 import time
@@ -34,11 +35,21 @@ if '--controller' in sys.argv:
     del sys.argv[k:k + 2]
     if controller not in ('random', 'greedy', 'maxpressure', 'fixedtime'):
         sys.exit('--controller %r: allowed values are random | greedy | maxpressure | fixedtime' % controller)
+reward_pressure = None
+if '--reward-pressure' in sys.argv:
+    k = sys.argv.index('--reward-pressure')
+    reward_pressure = sys.argv[k + 1] if k + 1 < len(sys.argv) else ''
+    del sys.argv[k:k + 2]
+    if reward_pressure not in ('count', 'queue'):
+        sys.exit('--reward-pressure %r: allowed values are count | queue' % reward_pressure)
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 scn = build_large_grid('ma2c')
 for chunk in ('1',):
     env = VecTrafficEnv(scn, E, seed=12)
+    if reward_pressure:
+        env.set_reward_pressure(reward_pressure)
+        print('pressure reward armed (%s)' % reward_pressure)
     obs = env.reset()
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     acts = [torch.randint(0, 5, (E, 25), generator=g, device='cuda', dtype=torch.int32) for _ in range(16)]
@@ -75,6 +86,8 @@ for chunk in ('1',):
 # --- cache / interference experiment: how much slower is env_step when other kernels run in between?
 from deeprl_signal_control_amd import _lib as _l
 env = VecTrafficEnv(scn, E, seed=12)
+if reward_pressure:
+    env.set_reward_pressure(reward_pressure)
 env.reset()
 for i in range(300):
     env.step(acts[i % 16])

@@ -112,9 +112,14 @@ def main():
     ap.add_argument('--ppo-epochs', type=int, default=None, help='algo ppo: epochs per rollout (default 4)')
     ap.add_argument('--ppo-clip', type=float, default=None, help='algo ppo: clip range of the probability ratio (default 0.2)')
     ap.add_argument('--gae-lambda', type=float, default=None, help='algo ppo: GAE lambda (default 0.95)')
+    ap.add_argument('--objective', default=None, choices=['queue', 'wait', 'hybrid', 'pressure'],
+                    help='[ENV_CONFIG] objective of the scenario (default: the scenario\'s own); pressure = the pressure reward, whose '
+                         'levels are not comparable with the others\'')
+    ap.add_argument('--pressure-measure', default=None, choices=['count', 'queue'], help='objective pressure: its measure (default count)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     kw = {} if args.lane_change is None else {'lane_change': bool(args.lane_change)}
+    kw.update({k: v for k, v in dict(objective=args.objective, pressure_measure=args.pressure_measure).items() if v is not None})
     rows, ev = run(args.episodes, args.envs, args.scenario, args.agent, lr=args.lr, log=print, policy=args.policy, scn_kw=kw,
                    test_seeds=[int(x) for x in args.test_seeds.split(',')] if args.test_seeds else None,
                    algo=args.algo, ppo_epochs=args.ppo_epochs, ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda)
