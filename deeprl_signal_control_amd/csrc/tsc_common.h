@@ -1,9 +1,10 @@
-// Shared host-side helpers for the tsc C-ABI library (error plumbing only).
+// Shared host-side helpers for the tsc C-ABI library: error plumbing, the owner of a handle's device buffers, kernel timing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace tsc {
@@ -40,14 +41,49 @@ struct CreateGuard {
     H *release() { H *t = h; h = nullptr; return t; }
 };
 
-template <typename T>
-inline hipError_t upload(T **dst, const T *src, size_t count) {
-    hipError_t e = hipMalloc((void **)dst, sizeof(T) * (count ? count : 1));
-    if (e != hipSuccess) return e;
-    if (count) e = hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice);
-    return e;
-}
+// The device allocations of one handle (tsc_env, tsc_model, tsc_iql): every buffer is registered the moment it exists and freed
+// with the handle, or earlier by release().  A call that fails frees what it allocated and leaves *field as it was.  `Mem` is the
+// four device calls; tests/device_bufs_check.cpp runs the bookkeeping over host stubs.
+struct HipMem {
+    static hipError_t malloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t zero(void *p, size_t bytes) { return hipMemset(p, 0, bytes); }
+    static hipError_t copy(void *dst, const void *src, size_t bytes) { return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); }
+    static void free(void *p) { (void)hipFree(p); }
+};
 
+template <class Mem>
+struct DeviceBufsT {
+    std::vector<void *> owned;
+    DeviceBufsT() = default;
+    DeviceBufsT(const DeviceBufsT &) = delete;
+    DeviceBufsT &operator=(const DeviceBufsT &) = delete;
+    ~DeviceBufsT() { for (void *p : owned) Mem::free(p); }
+
+    template <class T> hipError_t alloc(T **field, size_t count, bool zero) {
+        return make(field, count, [&](void *d) { return zero ? Mem::zero(d, sizeof(T) * count) : hipSuccess; });
+    }
+    // count == 0: one element, nothing copied (a kernel argument that is never read, but not null)
+    template <class T> hipError_t upload(T **field, const std::remove_const_t<T> *src, size_t count) {
+        return make(field, count ? count : 1, [&](void *d) { return count ? Mem::copy(d, src, sizeof(T) * count) : hipSuccess; });
+    }
+    void release(const void *p) {               // null, or not one of ours: nothing
+        for (auto it = owned.begin(); p && it != owned.end(); ++it)
+            if (*it == p) { Mem::free(*it); owned.erase(it); return; }
+    }
+
+private:
+    template <class T, class Fill> hipError_t make(T **field, size_t count, Fill fill) {
+        void *d = nullptr;
+        hipError_t e = Mem::malloc(&d, sizeof(T) * count);
+        if (e != hipSuccess) return e;
+        owned.push_back(d);
+        e = fill(d);
+        if (e != hipSuccess) release(d);
+        else *field = (T *)d;
+        return e;
+    }
+};
+using DeviceBufs = DeviceBufsT<HipMem>;
 
 // ---- per-kernel timing with HIP events (bench.py's live roofline figure) -------------------------
 // Off by default.  When on, launch sites bracket their kernel with two events on the launch stream;

@@ -483,14 +483,21 @@ __global__ void __launch_bounds__(256) greedy_kernel(EnvDev P, const float *__re
     action[i] = P.g_action[a * P.GC + arg];
 }
 
-// Tables and state of the max-pressure controller (tsc_env_set_pressure), a kernel argument of their own: EnvDev -- every other
-// kernel's argument -- keeps its layout and size.  Lanes are the scenario's (= the device's, load-sorted) lanes.
-struct PressDev {
+// The movement tables that the max-pressure controller and the pressure reward each hold a set of (upload_movements).  Lanes are
+// the scenario's (= the device's, load-sorted) lanes.
+struct MovDev {
     int n_mov, n_walk;             // movements; lanes that appear in one, as its incoming or its downstream lane
-    int measure, min_green;        // TSC_PRESSURE_*; control steps a chosen phase is held at least
+    int measure;                   // TSC_PRESSURE_*
     const short *walk;             // [n_walk] the walked lanes, ascending
     const short *mov_of;           // [NL * NR] movement of (lane, route), -1 = none
     const short *mov_dn;           // [n_mov] index into walk of the movement's downstream lane
+};
+
+// Tables and state of the max-pressure controller (tsc_env_set_pressure), a kernel argument of their own: EnvDev -- every other
+// kernel's argument -- keeps its layout and size.
+struct PressDev {
+    MovDev M;
+    int min_green;                 // control steps a chosen phase is held at least
     const int *srv_off;            // [A * PMAX + 1] phase (a, p) serves the movements srv[srv_off[a * PMAX + p] .. srv_off[.. + 1])
     const short *srv;
     int *hold;                     // [E][A][2] {cur, age}: the phase being held and the control steps it has been
@@ -500,9 +507,10 @@ constexpr int kPressT = 256;       // threads per instance
 // The flat walk of pressure_kernel and pressure_reward_kernel (step (a) of pressure_kernel's comment): fills start / down / up for
 // instance e from the live records of the walked lanes; `part` is [kPressT] scan scratch.  Every thread of the workgroup calls it;
 // the sums are complete when it returns (it ends on a barrier).
-__device__ __forceinline__ void pressure_walk(const EnvDev &P, int e, int n_walk, int n_mov, bool queue, const short *__restrict__ walk,
-                                              const short *__restrict__ mov_of, int *start, int *down, int *up, int *part) {
-    const int t = threadIdx.x;
+__device__ __forceinline__ void pressure_walk(const EnvDev &P, const MovDev &M, int e, int *start, int *down, int *up, int *part) {
+    const int t = threadIdx.x, n_walk = M.n_walk, n_mov = M.n_mov;
+    const bool queue = M.measure == TSC_PRESSURE_QUEUE;
+    const short *__restrict__ walk = M.walk, *__restrict__ mov_of = M.mov_of;
     const int *N = P.N + (size_t)e * P.NLP;
     const float4 *S = P.S + (size_t)e * kCap * P.NLP;
     // counts of this thread's run of walked lanes, their exclusive prefix sum over the workgroup
@@ -561,17 +569,17 @@ __device__ __forceinline__ void pressure_walk(const EnvDev &P, int e, int n_walk
 __global__ void __launch_bounds__(kPressT) pressure_kernel(EnvDev P, PressDev Q, int *__restrict__ action, int *__restrict__ pressure) {
     extern __shared__ int psm[];
     int *start = psm;                          // [n_walk + 1] flat index of a walked lane's first record
-    int *down = start + Q.n_walk + 1;          // [n_walk]
-    int *up = down + Q.n_walk;                 // [n_mov]
-    int *prs = up + Q.n_mov;                   // [A * PMAX]
+    int *down = start + Q.M.n_walk + 1;        // [n_walk]
+    int *up = down + Q.M.n_walk;               // [n_mov]
+    int *prs = up + Q.M.n_mov;                 // [A * PMAX]
     int *part = prs + P.A * P.PMAX;            // [kPressT] scan scratch
     const int e = blockIdx.x, t = threadIdx.x;
-    pressure_walk(P, e, Q.n_walk, Q.n_mov, Q.measure == TSC_PRESSURE_QUEUE, Q.walk, Q.mov_of, start, down, up, part);
+    pressure_walk(P, Q.M, e, start, down, up, part);
     for (int i = t; i < P.A * P.PMAX; i += kPressT) {
         int sum = 0;
         for (int j = Q.srv_off[i]; j < Q.srv_off[i + 1]; ++j) {
             const int mv = Q.srv[j];
-            sum += up[mv] - down[Q.mov_dn[mv]];
+            sum += up[mv] - down[Q.M.mov_dn[mv]];
         }
         prs[i] = sum;                          // (padded phases serve nothing: 0)
         if (pressure) pressure[(size_t)e * P.A * P.PMAX + i] = sum;
@@ -593,50 +601,10 @@ __global__ void __launch_bounds__(kPressT) pressure_kernel(EnvDev P, PressDev Q,
     }
 }
 
-// Tables and accumulator of the pressure reward (tsc_env_set_reward_pressure), a kernel argument of their own like PressDev and
-// independent of it: the controller and the reward may be armed with different measures, or one without the other.
-struct PressRewDev {
-    int n_mov, n_walk;             // as in PressDev
-    int measure;                   // TSC_PRESSURE_*
-    const short *walk;             // [n_walk]
-    const short *mov_of;           // [NL * NR]
-    const short *mov_dn;           // [n_mov]
-    const int *agt_off;            // [A + 1] agent a owns the movements agt_mov[agt_off[a] .. agt_off[a + 1])
-    const short *agt_mov;
-    double *acc;                   // [E] running sum of the global pressure reward (tsc_env_reward_sum while armed)
-};
-
-// The pressure reward, the rule of INTEGRATION.md "Pressure reward": P[a] = int32 sum over the agent's movements of up - down(downstream
-// lane) on the state step_kernel left, r[a] = -|P[a]|, g = sum of r; the returned reward is shaped as step_kernel shapes its own
-// (K6).  Runs behind step_kernel on the same stream and overwrites reward / greward; reads EnvDev, writes nothing else but R.acc.
-// One workgroup per instance: the walk of pressure_kernel, then one thread per agent sums its movements, one thread forms g, one
-// thread per agent shapes and stores.  r and g are integers in float64: no order of addition can change them.
-__global__ void __launch_bounds__(kPressT) pressure_reward_kernel(EnvDev P, PressRewDev R, double *__restrict__ reward,
-                                                                  double *__restrict__ greward, int train_mode) {
-    extern __shared__ __attribute__((aligned(16))) char prw_raw[];
-    double *r = (double *)prw_raw;             // [A + 1] local rewards, then g
-    int *start = (int *)(r + P.A + 1);         // [n_walk + 1]
-    int *down = start + R.n_walk + 1;          // [n_walk]
-    int *up = down + R.n_walk;                 // [n_mov]
-    int *part = up + R.n_mov;                  // [kPressT]
-    const int e = blockIdx.x, t = threadIdx.x;
-    pressure_walk(P, e, R.n_walk, R.n_mov, R.measure == TSC_PRESSURE_QUEUE, R.walk, R.mov_of, start, down, up, part);
-    for (int a = t; a < P.A; a += kPressT) {
-        int sum = 0;
-        for (int j = R.agt_off[a]; j < R.agt_off[a + 1]; ++j) {
-            const int mv = R.agt_mov[j];
-            sum += up[mv] - down[R.mov_dn[mv]];
-        }
-        r[a] = (double)(sum < 0 ? sum : -sum);
-    }
-    __syncthreads();
-    if (t == 0) {
-        double g = 0.0;
-        for (int a = 0; a < P.A; ++a) g += r[a];
-        r[P.A] = g; greward[e] = g; R.acc[e] += g;
-    }
-    __syncthreads();
-    for (int a = t; a < P.A; a += kPressT) {
+// The reward shaping of envs/env.py:580,:590-631, float64: r is [A + 1], the agents' local rewards and then their sum g.  Thread
+// `first` of `stride` stores the returned reward of agents first, first + stride, ...  (The same loop ends step_kernel's K6.)
+__device__ __forceinline__ void shape_rewards(const EnvDev &P, const double *r, int e, double *reward, int train_mode, int first, int stride) {
+    for (int a = first; a < P.A; a += stride) {
         const double g = r[P.A];
         double out;
         if (!train_mode) {
@@ -658,6 +626,48 @@ __global__ void __launch_bounds__(kPressT) pressure_reward_kernel(EnvDev P, Pres
         }
         reward[(size_t)e * P.A + a] = out;
     }
+}
+
+// Tables and accumulator of the pressure reward (tsc_env_set_reward_pressure), a kernel argument of their own like PressDev and
+// independent of it: the controller and the reward may be armed with different measures, or one without the other.
+struct PressRewDev {
+    MovDev M;
+    const int *agt_off;            // [A + 1] agent a owns the movements agt_mov[agt_off[a] .. agt_off[a + 1])
+    const short *agt_mov;
+    double *acc;                   // [E] running sum of the global pressure reward (tsc_env_reward_sum while armed)
+};
+
+// The pressure reward, the rule of INTEGRATION.md "Pressure reward": P[a] = int32 sum over the agent's movements of up - down(downstream
+// lane) on the state step_kernel left, r[a] = -|P[a]|, g = sum of r; the returned reward is shaped as step_kernel shapes its own
+// (K6).  Runs behind step_kernel on the same stream and overwrites reward / greward; reads EnvDev, writes nothing else but R.acc.
+// One workgroup per instance: the walk of pressure_kernel, then one thread per agent sums its movements, one thread forms g, one
+// thread per agent shapes and stores.  r and g are integers in float64: no order of addition can change them.
+__global__ void __launch_bounds__(kPressT) pressure_reward_kernel(EnvDev P, PressRewDev R, double *__restrict__ reward,
+                                                                  double *__restrict__ greward, int train_mode) {
+    extern __shared__ __attribute__((aligned(16))) char prw_raw[];
+    double *r = (double *)prw_raw;             // [A + 1] local rewards, then g
+    int *start = (int *)(r + P.A + 1);         // [n_walk + 1]
+    int *down = start + R.M.n_walk + 1;        // [n_walk]
+    int *up = down + R.M.n_walk;               // [n_mov]
+    int *part = up + R.M.n_mov;                // [kPressT]
+    const int e = blockIdx.x, t = threadIdx.x;
+    pressure_walk(P, R.M, e, start, down, up, part);
+    for (int a = t; a < P.A; a += kPressT) {
+        int sum = 0;
+        for (int j = R.agt_off[a]; j < R.agt_off[a + 1]; ++j) {
+            const int mv = R.agt_mov[j];
+            sum += up[mv] - down[R.M.mov_dn[mv]];
+        }
+        r[a] = (double)(sum < 0 ? sum : -sum);
+    }
+    __syncthreads();
+    if (t == 0) {
+        double g = 0.0;
+        for (int a = 0; a < P.A; ++a) g += r[a];
+        r[P.A] = g; greward[e] = g; R.acc[e] += g;
+    }
+    __syncthreads();
+    shape_rewards(P, r, e, reward, train_mode, t, kPressT);
 }
 
 // Fixed-time cycle: phase (t / steps) % n_phase at control step t = tsec / control interval.  One thread per (instance, agent).
@@ -1629,6 +1639,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     __syncthreads();
     if (l == 0) { double g = np_sum(s.r, P.A); s.r[P.A] = g; greward[e] = g; P.reward_acc[e] += g; }
     __syncthreads();
+    // (the loop of shape_rewards, kept in place: calling it here changes the scalar register allocation of the whole kernel)
     for (int a = l; a < P.A; a += blockDim.x) {
         const double g = s.r[P.A];
         double out;
@@ -1703,7 +1714,7 @@ struct tsc_env {
     EnvDev P;
     int device;
     hipStream_t stream;
-    std::vector<void *> allocs;
+    tsc::DeviceBufs bufs;           // every device buffer of the handle
     size_t smem;                    // LDS of reset_kernel (the IDM layout for the recording state)
     int threads;                    // IDM workgroup size (pick_workgroup)
     int kf;                         // IDM flat-phase vehicles per thread (measurement knob TSC_ENV_KF)
@@ -1858,22 +1869,6 @@ const char *tsc_profile_name(int32_t id) {
 
 int tsc_version(void) { return 114; }      // 1.14: tsc_env_set_reward_pressure; 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
-#define UP(field, T, src, count)                                                 \
-    do {                                                                         \
-        T *d_ = nullptr;                                                         \
-        TSC_HIP(tsc::upload<T>(&d_, (const T *)(src), (size_t)(count)));         \
-        h->allocs.push_back(d_);                                                 \
-        P.field = d_;                                                            \
-    } while (0)
-#define ALLOC(field, T, count)                                                   \
-    do {                                                                         \
-        T *d_ = nullptr;                                                         \
-        TSC_HIP(hipMalloc((void **)&d_, sizeof(T) * (size_t)(count)));           \
-        TSC_HIP(hipMemset(d_, 0, sizeof(T) * (size_t)(count)));                  \
-        h->allocs.push_back(d_);                                                 \
-        P.field = d_;                                                            \
-    } while (0)
-
 int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_env **out) {
     if (!sc || !out || n_env <= 0) return tsc::fail("tsc_env_create: bad arguments");
     if (sc->n_lane > 1024) return tsc::fail("tsc_env_create: n_lane %d > 1024 unsupported", sc->n_lane);
@@ -1929,18 +1924,18 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
         P.NU = nu < 1 ? 1 : nu;
         P.NLA = (P.NU + 63) / 64 * 64;
     }
-    UP(lane_len, float, sc->lane_len, NL); UP(lane_vmax, float, sc->lane_vmax, NL);
-    UP(lane_det, float, sc->lane_det_start, NL);
-    UP(lane_node, int, sc->lane_node, NL);
+    TSC_HIP(h->bufs.upload(&P.lane_len, sc->lane_len, NL)); TSC_HIP(h->bufs.upload(&P.lane_vmax, sc->lane_vmax, NL));
+    TSC_HIP(h->bufs.upload(&P.lane_det, sc->lane_det_start, NL));
+    TSC_HIP(h->bufs.upload(&P.lane_node, sc->lane_node, NL));
     if (sc->lane_sib) {
         for (int l = 0; l < NL; ++l)
             if (sc->lane_sib[l] >= NL || sc->lane_sib[l] == l) return tsc::fail("tsc_env_create: lane %d names sibling lane %d of %d", l, sc->lane_sib[l], NL);
-        UP(lane_sib, int, sc->lane_sib, NL);
+        TSC_HIP(h->bufs.upload(&P.lane_sib, sc->lane_sib, NL));
     }
     {
         std::vector<int> up(sc->lane_up, sc->lane_up + (size_t)NL * kMaxUp);
         for (int &u : up) if (u >= 0 && (u >= NL || !reach[u])) u = -1;        // a feeder that is never occupied never sends
-        UP(lane_up, int, up.data(), up.size());
+        TSC_HIP(h->bufs.upload(&P.lane_up, up.data(), up.size()));
     }
     if (NL > 0xFFD) return tsc::fail("tsc_env_create: n_lane %d > 4093 unsupported", NL);
     std::vector<int> mv((size_t)NL * NR);
@@ -1955,7 +1950,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
         if (mv_tl(mv[i]) != (nx < -1 ? -2 : nx) || mv_k(mv[i]) != (lk < 0 ? -1 : lk) || mv_yield(mv[i]) != yl)
             return tsc::fail("tsc_env_create: movement table overflow");
     }
-    UP(mv, int, mv.data(), NL * NR);
+    TSC_HIP(h->bufs.upload(&P.mv, mv.data(), NL * NR));
     {
         std::vector<uint8_t> zp(((size_t)NL * NR + 3) / 4 * 4, 0);
         for (int i = 0; i < NL * NR; ++i) {
@@ -1963,7 +1958,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
             if (rank > 15 || cnt > 15) return tsc::fail("tsc_env_create: zipper slot overflow");
             zp[i] = (uint8_t)(rank | (cnt << 4));
         }
-        UP(zip, uint8_t, zp.data(), zp.size());
+        TSC_HIP(h->bufs.upload(&P.zip, zp.data(), zp.size()));
         for (uint8_t v : zp) if (v >> 4 > 1) any_zip = true;
         // the merge arbitration packs a lane's feeders into bytes (Smem::up4, 0xFF = none): a feeder index >= 255 would be
         // left out of the winner search and wait for the teleport
@@ -1985,10 +1980,10 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
         }
         h->h_mode.assign(sc->stream_mode, sc->stream_mode + NS); h->h_sroute = sr;
         if (!identity) {                              // fixed one-to-one streams keep the round-2 fast path (sroute == null)
-            UP(sroute, int, sr.data(), NS);
-            UP(smode, int, sc->stream_mode, NS);
-            UP(schoice, int, sc->stream_choice, (size_t)NS * NI * KC * 2);
-            ALLOC(iroute, int, (size_t)n_env * NS);
+            TSC_HIP(h->bufs.upload(&P.sroute, sr.data(), NS));
+            TSC_HIP(h->bufs.upload(&P.smode, sc->stream_mode, NS));
+            TSC_HIP(h->bufs.upload(&P.schoice, sc->stream_choice, (size_t)NS * NI * KC * 2));
+            TSC_HIP(h->bufs.alloc(&P.iroute, (size_t)n_env * NS, true));
             std::vector<int> ir((size_t)n_env * NS);
             for (size_t i = 0; i < ir.size(); ++i) ir[i] = sr[i % NS];
             TSC_HIP(hipMemcpy(P.iroute, ir.data(), sizeof(int) * ir.size(), hipMemcpyHostToDevice));
@@ -1999,7 +1994,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
                 so[2 * s_] = sc->stream_origin ? sc->stream_origin[s_] : 0.0f;
                 so[2 * s_ + 1] = sc->stream_limit ? sc->stream_limit[s_] : INFINITY;
             }
-            UP(sorigin, float, so.data(), so.size());
+            TSC_HIP(h->bufs.upload(&P.sorigin, so.data(), so.size()));
         }
     }
     {   // per-lane entry routes (<= 2) and per-route emission table (MICROSIM_SPEC.md, rule 6)
@@ -2017,7 +2012,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
             for (int q = 0; q < kMaxEntry; ++q)
                 if (lr[l * kMaxEntry + q] >= 0)
                     lrp[l * 2 + q / 4] = (lrp[l * 2 + q / 4] & ~(0xFFu << (8 * (q % 4)))) | ((uint32_t)lr[l * kMaxEntry + q] << (8 * (q % 4)));
-        UP(lane_routes, uint32_t, lrp.data(), lrp.size());
+        TSC_HIP(h->bufs.upload(&P.lane_routes, lrp.data(), lrp.size()));
         P.emit_len = (sc->episode_length_sec + 64 + 3) / 4 * 4;       // (whole words: demand_kernel stores four seconds at once)
         std::vector<uint8_t> em((size_t)NS * P.emit_len, 0);
         for (int f = 0; f < sc->n_flow; ++f) {
@@ -2032,45 +2027,45 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
                 em[(size_t)r * P.emit_len + t] = (uint8_t)v;
             }
         }
-        UP(emit_tab, uint8_t, em.data(), em.size());
+        TSC_HIP(h->bufs.upload(&P.emit_tab, em.data(), em.size()));
         P.emit_inst = 0;
         h->emit_shared = P.emit_tab;
         h->n_flow = sc->n_flow;
         h->h_flows.assign(sc->flows, sc->flows + (size_t)sc->n_flow * 4);
     }
     if (sc->control_interval_sec > 8) return tsc::fail("tsc_env_create: control interval > 8 s unsupported");
-    UP(agent_lanes, int, sc->agent_lanes, A * P.LMAX);
-    UP(agent_nlane, int, sc->agent_nlane, A); UP(agent_nlink, int, sc->agent_nlink, A);
-    UP(agent_nphase, int, sc->agent_nphase, A);
+    TSC_HIP(h->bufs.upload(&P.agent_lanes, sc->agent_lanes, A * P.LMAX));
+    TSC_HIP(h->bufs.upload(&P.agent_nlane, sc->agent_nlane, A)); TSC_HIP(h->bufs.upload(&P.agent_nlink, sc->agent_nlink, A));
+    TSC_HIP(h->bufs.upload(&P.agent_nphase, sc->agent_nphase, A));
     h->h_nphase.assign(sc->agent_nphase, sc->agent_nphase + A);
-    UP(green_tab, uint8_t, sc->green_tab, (size_t)A * P.PMAX * P.KMAX);
-    UP(yellow_tab, uint8_t, sc->yellow_tab, (size_t)A * P.PMAX * P.PMAX * P.KMAX);
-    UP(nbr, int, sc->nbr, A * P.NBR);
-    UP(obs_kind, int, sc->obs_kind, A * P.SMAX); UP(obs_src, int, sc->obs_src, A * P.SMAX);
+    TSC_HIP(h->bufs.upload(&P.green_tab, sc->green_tab, (size_t)A * P.PMAX * P.KMAX));
+    TSC_HIP(h->bufs.upload(&P.yellow_tab, sc->yellow_tab, (size_t)A * P.PMAX * P.PMAX * P.KMAX));
+    TSC_HIP(h->bufs.upload(&P.nbr, sc->nbr, A * P.NBR));
+    TSC_HIP(h->bufs.upload(&P.obs_kind, sc->obs_kind, A * P.SMAX)); TSC_HIP(h->bufs.upload(&P.obs_src, sc->obs_src, A * P.SMAX));
     {
         std::vector<int> ks((size_t)A * P.SMAX);
         for (size_t i = 0; i < ks.size(); ++i) {
             if (sc->obs_src[i] < 0 || sc->obs_src[i] > 0xFFFF) { ks[i] = 0; continue; }
             ks[i] = (sc->obs_kind[i] << 16) | sc->obs_src[i];
         }
-        UP(obs_ks, int, ks.data(), ks.size());
+        TSC_HIP(h->bufs.upload(&P.obs_ks, ks.data(), ks.size()));
     }
 
     const size_t slots = (size_t)n_env * kCap * P.NLP;
-    ALLOC(S, float4, slots);
-    ALLOC(N, int, (size_t)n_env * P.NLP);
-    ALLOC(pending, int, (size_t)n_env * NS); ALLOC(serial, int, (size_t)n_env * NS);
-    ALLOC(tsec, int, n_env); ALLOC(seed, uint32_t, n_env);
-    ALLOC(prev_action, int, (size_t)n_env * A);
-    ALLOC(fp, float, (size_t)n_env * A * P.PMAX);
-    ALLOC(arrived, unsigned long long, n_env);
-    ALLOC(teleported, unsigned long long, n_env);
-    ALLOC(reward_acc, double, n_env);
-    ALLOC(n_trips, int, n_env); ALLOC(live_acc, unsigned long long, n_env);
+    TSC_HIP(h->bufs.alloc(&P.S, slots, true));
+    TSC_HIP(h->bufs.alloc(&P.N, (size_t)n_env * P.NLP, true));
+    TSC_HIP(h->bufs.alloc(&P.pending, (size_t)n_env * NS, true)); TSC_HIP(h->bufs.alloc(&P.serial, (size_t)n_env * NS, true));
+    TSC_HIP(h->bufs.alloc(&P.tsec, n_env, true)); TSC_HIP(h->bufs.alloc(&P.seed, n_env, true));
+    TSC_HIP(h->bufs.alloc(&P.prev_action, (size_t)n_env * A, true));
+    TSC_HIP(h->bufs.alloc(&P.fp, (size_t)n_env * A * P.PMAX, true));
+    TSC_HIP(h->bufs.alloc(&P.arrived, n_env, true));
+    TSC_HIP(h->bufs.alloc(&P.teleported, n_env, true));
+    TSC_HIP(h->bufs.alloc(&P.reward_acc, n_env, true));
+    TSC_HIP(h->bufs.alloc(&P.n_trips, n_env, true)); TSC_HIP(h->bufs.alloc(&P.live_acc, n_env, true));
     {
         std::vector<float> org((size_t)NL, 0.0f);
         if (sc->lane_origin) org.assign(sc->lane_origin, sc->lane_origin + NL);
-        UP(lane_origin, float, org.data(), NL);
+        TSC_HIP(h->bufs.upload(&P.lane_origin, org.data(), NL));
     }
     P.rec = 0; P.trip_cap = 0; P.R0 = P.R1 = nullptr; P.rec_int = nullptr; P.rec_speed = nullptr; P.rec_queue = nullptr;
     P.trips = nullptr;
@@ -2079,8 +2074,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     P.fp_bound = nullptr;
     P.dbg = nullptr;
     P.order = nullptr;
-    TSC_HIP(hipMalloc((void **)&h->d_seeds, sizeof(uint32_t) * n_env));
-    h->allocs.push_back(h->d_seeds);
+    TSC_HIP(h->bufs.alloc(&h->d_seeds, n_env, false));
     {   // phase A1 (helper threads) unless switched off for A/B measurements
         const char *ev = getenv("TSC_ENV_HELP");
         P.help = (ev && ev[0] == '0') ? 0 : 1;
@@ -2127,12 +2121,12 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     TSC_HIP(hipStreamSynchronize(h->stream));
     if (enable && !P.R1) {
         const size_t slots = (size_t)P.E * kCap * P.NLP;
-        if (!P.R0) ALLOC(R0, uint32_t, slots);          // (a Krauss handle has it already: one word per slot for both)
-        ALLOC(R1, uint32_t, slots);
-        ALLOC(rec_int, long long, (size_t)P.E * 8 * 4); ALLOC(rec_speed, double, (size_t)P.E * 8);
-        ALLOC(rec_queue, int, (size_t)P.E * 8 * P.A * P.LMAX);
+        if (!P.R0) TSC_HIP(h->bufs.alloc(&P.R0, slots, true));          // (a Krauss handle has it already: one word per slot for both)
+        TSC_HIP(h->bufs.alloc(&P.R1, slots, true));
+        TSC_HIP(h->bufs.alloc(&P.rec_int, (size_t)P.E * 8 * 4, true)); TSC_HIP(h->bufs.alloc(&P.rec_speed, (size_t)P.E * 8, true));
+        TSC_HIP(h->bufs.alloc(&P.rec_queue, (size_t)P.E * 8 * P.A * P.LMAX, true));
         P.trip_cap = trip_cap > 0 ? trip_cap : 8192;
-        ALLOC(trips, int, (size_t)P.E * P.trip_cap * 6);
+        TSC_HIP(h->bufs.alloc(&P.trips, (size_t)P.E * P.trip_cap * 6, true));
     }
     P.rec = enable ? 1 : 0;
     h->smem = smem_bytes(P);
@@ -2143,11 +2137,18 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     return plan_step(h, "tsc_env_record");
 }
 
-// Frees a buffer this handle allocated (P.* = nullptr afterwards is the caller's)
-static void free_alloc(tsc_env *h, const void *p) {
-    if (!p) return;
-    for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
-        if (*it == p) { (void)hipFree(*it); h->allocs.erase(it); return; }
+// Build, then swap (tsc_env_lane_data, tsc_env_trace): the caller has built new tables into D, a copy of the handle's EnvDev.  Waits
+// for the stream (a running step may still write the old buffers), installs D and plans the step for it.  On return D holds what
+// the handle does not use, for the caller to release: the old tables, or on failure the new ones -- the handle, its plan and
+// ld_live are then as they were.
+static int swap_and_plan(tsc_env *h, EnvDev &D, bool ld_live, const char *who) {
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    const StepPlan plan0 = h->plan;
+    const bool live0 = h->ld_live;
+    std::swap(h->P, D); h->ld_live = ld_live;
+    if (!plan_step(h, who)) return 0;
+    std::swap(h->P, D); h->ld_live = live0; h->plan = plan0;
+    return 1;
 }
 
 int tsc_env_lane_data(tsc_env *h, int32_t period_sec, int32_t n_slot, const int32_t *lane_slot0_host, const float *slot_start_host,
@@ -2172,25 +2173,22 @@ int tsc_env_lane_data(tsc_env *h, int32_t period_sec, int32_t n_slot, const int3
         if (lane_slot0_host[P.NU] >= 0x8000) return tsc::fail("tsc_env_lane_data: %d slots on the live lanes, at most 32767", lane_slot0_host[P.NU]);
     }
     (void)hipSetDevice(h->device);
-    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running step may still write the old buffers
-    free_alloc(h, P.ld_slot0); free_alloc(h, P.ld_bound); free_alloc(h, P.ld_sumo); free_alloc(h, P.ld_int); free_alloc(h, P.ld_speed);
-    P.ld_slot0 = nullptr; P.ld_bound = nullptr; P.ld_sumo = nullptr; P.ld_int = nullptr; P.ld_speed = nullptr;
-    P.ld_period = 0; P.ld_nslot = 0;
-    h->ld_live = false; h->ld_nslot_all = 0; h->ld_nint = 0;
-    if (plan_step(h, "tsc_env_lane_data")) return 1;            // until the next reset the recording kernels without lane data run
-    if (period_sec <= 0) return 0;                              // detached
-    const int nds = lane_slot0_host[P.NU];
-    P.ld_period = period_sec; P.ld_nslot = nds;
-    h->ld_nslot_all = n_slot; h->ld_nint = (P.episode + period_sec - 1) / period_sec;
-    // what the reset will install, checked here (IDM and Krauss: either may be in force by then)
-    const size_t need = std::max(step_lds(P, false, true), step_lds(P, true, true));
-    if (need > kLdsMax) {
-        tsc::fail("tsc_env_lane_data: LDS need %zu B > 160 KiB (%d slots)", need, P.ld_nslot);
-        P.ld_period = 0; P.ld_nslot = 0;
-        return 1;
-    }
-    UP(ld_slot0, int, lane_slot0_host, NL + 1);
-    {   // a lane's piece starts 2..5 as one 16-byte LDS word per lane (the lookup: four compares)
+    EnvDev D = P;                                               // with the new lane-data tables (none: detached)
+    D.ld_slot0 = nullptr; D.ld_bound = nullptr; D.ld_sumo = nullptr; D.ld_int = nullptr; D.ld_speed = nullptr;
+    D.ld_period = 0; D.ld_nslot = 0;
+    const int nds = period_sec > 0 ? lane_slot0_host[P.NU] : 0;
+    const int nint = period_sec > 0 ? (P.episode + period_sec - 1) / period_sec : 0;
+    const auto drop = [h](const EnvDev &d) {
+        h->bufs.release(d.ld_slot0); h->bufs.release(d.ld_bound); h->bufs.release(d.ld_sumo); h->bufs.release(d.ld_int); h->bufs.release(d.ld_speed);
+    };
+    const auto build = [&]() {
+        if (period_sec <= 0) return 0;
+        D.ld_period = period_sec; D.ld_nslot = nds;
+        // what the reset will install, checked here (IDM and Krauss: either may be in force by then)
+        const size_t need = std::max(step_lds(D, false, true), step_lds(D, true, true));
+        if (need > kLdsMax) return tsc::fail("tsc_env_lane_data: LDS need %zu B > 160 KiB (%d slots)", need, nds);
+        TSC_HIP(h->bufs.upload(&D.ld_slot0, lane_slot0_host, NL + 1));
+        // a lane's piece starts 2..5 as one 16-byte LDS word per lane (the lookup: four compares)
         std::vector<float4> b((size_t)P.NU);
         for (int l = 0; l < P.NU; ++l) {
             float v[4];
@@ -2200,11 +2198,17 @@ int tsc_env_lane_data(tsc_env *h, int32_t period_sec, int32_t n_slot, const int3
             }
             b[l] = make_float4(v[0], v[1], v[2], v[3]);
         }
-        UP(ld_bound, float4, b.data(), P.NU);
-    }
-    UP(ld_sumo, int, slot_sumo_host, nds);
-    ALLOC(ld_int, int, (size_t)P.E * h->ld_nint * kLdInts * nds);
-    ALLOC(ld_speed, double, (size_t)P.E * h->ld_nint * nds);
+        TSC_HIP(h->bufs.upload(&D.ld_bound, b.data(), P.NU));
+        TSC_HIP(h->bufs.upload(&D.ld_sumo, slot_sumo_host, nds));
+        TSC_HIP(h->bufs.alloc(&D.ld_int, (size_t)P.E * nint * kLdInts * nds, true));
+        TSC_HIP(h->bufs.alloc(&D.ld_speed, (size_t)P.E * nint * nds, true));
+        return 0;
+    };
+    // (ld_live false: until the next reset the recording kernels without lane data run)
+    const int rc = build() || swap_and_plan(h, D, false, "tsc_env_lane_data");
+    drop(D);
+    if (rc) return 1;
+    h->ld_nslot_all = period_sec > 0 ? n_slot : 0; h->ld_nint = nint;
     return 0;                                                   // (ld_live: from the next reset on)
 }
 
@@ -2246,17 +2250,23 @@ int tsc_env_trace(tsc_env *h, int32_t n_trace, const int32_t *instances_host, in
         slot[e] = k;
     }
     (void)hipSetDevice(h->device);
-    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running step may still write the old buffers
-    free_alloc(h, P.trace_slot); free_alloc(h, P.trace_cnt); free_alloc(h, P.trace_rows);
-    P.trace_slot = nullptr; P.trace_cnt = nullptr; P.trace_rows = nullptr; P.trace_cap = 0;
-    h->n_trace = 0;
-    if (n_trace == 0) return plan_step(h, "tsc_env_trace");     // detached: the untraced recording kernels run again
-    UP(trace_slot, int, slot.data(), P.E);
-    ALLOC(trace_cnt, int, (size_t)n_trace * (P.episode + 1));
-    ALLOC(trace_rows, uint4, (size_t)n_trace * row_cap);
-    P.trace_cap = row_cap;
+    EnvDev D = P;                                               // with the new trace buffers (none: detached)
+    D.trace_slot = nullptr; D.trace_cnt = nullptr; D.trace_rows = nullptr; D.trace_cap = 0;
+    const auto drop = [h](const EnvDev &d) { h->bufs.release(d.trace_slot); h->bufs.release(d.trace_cnt); h->bufs.release(d.trace_rows); };
+    const auto build = [&]() {
+        if (n_trace == 0) return 0;
+        TSC_HIP(h->bufs.upload(&D.trace_slot, slot.data(), P.E));
+        TSC_HIP(h->bufs.alloc(&D.trace_cnt, (size_t)n_trace * (P.episode + 1), true));
+        TSC_HIP(h->bufs.alloc(&D.trace_rows, (size_t)n_trace * row_cap, true));
+        D.trace_cap = row_cap;
+        return 0;
+    };
+    // the tracing kernels from the next step on (detached: the untraced recording kernels again)
+    const int rc = build() || swap_and_plan(h, D, h->ld_live, "tsc_env_trace");
+    drop(D);
+    if (rc) return 1;
     h->n_trace = n_trace;
-    return plan_step(h, "tsc_env_trace");                       // the tracing kernels from the next step on
+    return 0;
 }
 
 int tsc_env_read_trace(tsc_env *h, int32_t k, int32_t *counts_host, uint32_t *rows_host, int32_t max_rows, int32_t *n_rows) {
@@ -2321,8 +2331,7 @@ int tsc_env_live_sum(tsc_env *h, double *sum_host, int32_t reset) {
 int tsc_env_destroy(tsc_env *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
-    for (void *p : h->allocs) (void)hipFree(p);
-    delete h;
+    delete h;                                    // (h->bufs frees the device buffers)
     return 0;
 }
 
@@ -2385,7 +2394,7 @@ int tsc_env_set_car_following(tsc_env *h, int32_t model, double sigma) {
     EnvDev &P = h->P;
     if (model == TSC_CF_KRAUSS && !P.R0) {       // the vehicles' serials (R0), shared with the recording path
         TSC_HIP(hipStreamSynchronize(h->stream));
-        ALLOC(R0, uint32_t, (size_t)P.E * kCap * P.NLP);
+        TSC_HIP(h->bufs.alloc(&P.R0, (size_t)P.E * kCap * P.NLP, true));
     }
     // what the reset will install, checked here
     if (model == TSC_CF_KRAUSS && step_lds(P, true, false) > kLdsMax)
@@ -2468,26 +2477,16 @@ int tsc_env_set_demand(tsc_env *h, const int32_t *vph_host) {
             off[r + 1] = (int)fl.size() / 3;
         }
         if (fl.empty()) fl.assign(3, 0);
-        // (each buffer is the handle's as soon as it exists: a call that fails half way is completed by the next one)
+        // (a call that fails half way is completed by the next one)
         const size_t bytes = (size_t)P.E * NS * P.emit_len;
-        if (!h->dem_vph) { TSC_HIP(hipMalloc((void **)&h->dem_vph, sizeof(int) * (size_t)P.E * NF)); h->allocs.push_back(h->dem_vph); }
-        auto up = [&](int **field, const std::vector<int> &v) {      // the handle's only once it is filled; freed with it either way
-            int *d = nullptr;
-            const hipError_t e = tsc::upload<int>(&d, v.data(), v.size());
-            if (d) h->allocs.push_back(d);
-            if (e == hipSuccess) *field = d;
-            return e;
-        };
-        if (!h->dem_off) TSC_HIP(up(&h->dem_off, off));
-        if (!h->dem_fl) TSC_HIP(up(&h->dem_fl, fl));
-        uint8_t *rows = nullptr;
-        if (hipMalloc((void **)&rows, bytes) != hipSuccess) {
+        if (!h->dem_vph) TSC_HIP(h->bufs.alloc(&h->dem_vph, (size_t)P.E * NF, false));
+        if (!h->dem_off) TSC_HIP(h->bufs.upload(&h->dem_off, off.data(), off.size()));
+        if (!h->dem_fl) TSC_HIP(h->bufs.upload(&h->dem_fl, fl.data(), fl.size()));
+        if (h->bufs.alloc(&h->dem_rows, bytes, false) != hipSuccess) {
             (void)hipGetLastError();
             return tsc::fail("tsc_env_set_demand: no device memory for %zu B of per-instance emission tables (%d instances x %d streams x %d s)",
                              bytes, P.E, NS, P.emit_len);
         }
-        h->allocs.push_back(rows);
-        h->dem_rows = rows;
     }
     h->dem_next.assign(vph_host, vph_host + (size_t)P.E * NF);
     h->dem_dirty = true;
@@ -2574,17 +2573,20 @@ int tsc_env_set_greedy(tsc_env *h, int32_t n_cand_max, int32_t n_term_max, const
         }
     }
     (void)hipSetDevice(h->device);
-    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running greedy_kernel may still read the old tables
-    for (const void *old : {(const void *)P.g_ncand, (const void *)P.g_term, (const void *)P.g_action}) {      // a second call replaces them
-        if (!old) continue;
-        for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
-            if (*it == old) { (void)hipFree(*it); h->allocs.erase(it); break; }
-    }
-    P.g_ncand = nullptr; P.g_term = nullptr; P.g_action = nullptr;
-    UP(g_ncand, int, n_cand, P.A);
-    UP(g_term, int8_t, t8.data(), t8.size());
-    UP(g_action, int, cand_action, (size_t)P.A * n_cand_max);
-    P.GC = n_cand_max; P.GT = n_term_max;
+    EnvDev G = P;                                              // the new tables; a second call replaces the old ones
+    G.g_ncand = nullptr; G.g_term = nullptr; G.g_action = nullptr;
+    G.GC = n_cand_max; G.GT = n_term_max;
+    const auto drop = [h](const EnvDev &D) { h->bufs.release(D.g_ncand); h->bufs.release(D.g_term); h->bufs.release(D.g_action); };
+    const auto build = [&]() {
+        TSC_HIP(h->bufs.upload(&G.g_ncand, n_cand, P.A));
+        TSC_HIP(h->bufs.upload(&G.g_term, t8.data(), t8.size()));
+        TSC_HIP(h->bufs.upload(&G.g_action, cand_action, (size_t)P.A * n_cand_max));
+        TSC_HIP(hipStreamSynchronize(h->stream));              // a running greedy_kernel may still read the old tables
+        return 0;
+    };
+    if (build()) { drop(G); return 1; }
+    drop(P);
+    P = G;
     return 0;
 }
 
@@ -2628,58 +2630,66 @@ static int compile_movements(const char *who, const EnvDev &P, int measure, int 
     return 0;
 }
 
-// frees the listed device tables of the handle (a second arming call replaces them)
-static void free_tables(tsc_env *h, std::initializer_list<const void *> olds) {
-    for (const void *old : olds) {
-        if (!old) continue;
-        for (auto it = h->allocs.begin(); it != h->allocs.end(); ++it)
-            if (*it == old) { (void)hipFree(*it); h->allocs.erase(it); break; }
-    }
+// compile_movements, then its three tables on the device: fills M through the handle's buffers and *lds with the LDS bytes of
+// pressure_walk's arrays (start, down, up, scan scratch).  Changes nothing else of the handle; on failure M holds what was uploaded,
+// for the caller to release.
+static int upload_movements(const char *who, tsc_env *h, int measure, int n_mov, const int32_t *mov, const int32_t *lane_route_mov,
+                            MovDev &M, size_t *lds) {
+    std::vector<short> walk, mov_of, mov_dn;
+    if (compile_movements(who, h->P, measure, n_mov, mov, lane_route_mov, walk, mov_of, mov_dn)) return 1;
+    M.n_mov = n_mov; M.n_walk = (int)walk.size(); M.measure = measure;
+    *lds = sizeof(int) * (2 * walk.size() + 1 + (size_t)n_mov + kPressT);
+    TSC_HIP(h->bufs.upload(&M.walk, walk.data(), walk.size()));
+    TSC_HIP(h->bufs.upload(&M.mov_of, mov_of.data(), mov_of.size()));
+    TSC_HIP(h->bufs.upload(&M.mov_dn, mov_dn.data(), mov_dn.size()));
+    return 0;
 }
+static void release_movements(tsc_env *h, const MovDev &M) { h->bufs.release(M.walk); h->bufs.release(M.mov_of); h->bufs.release(M.mov_dn); }
 
 int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov,
                          int32_t srv_max, const int32_t *served) {
     if (!h || !mov || !lane_route_mov || !served || n_mov < 0 || srv_max <= 0) return tsc::fail("tsc_env_set_pressure: bad arguments");
-    if (measure != TSC_PRESSURE_COUNT && measure != TSC_PRESSURE_QUEUE)
-        return tsc::fail("tsc_env_set_pressure: measure %d is neither TSC_PRESSURE_COUNT (0) nor TSC_PRESSURE_QUEUE (1)", measure);
     if (min_green < 1) return tsc::fail("tsc_env_set_pressure: min_green %d must be >= 1", min_green);
     const EnvDev &P = h->P;
-    std::vector<short> walk, mov_of, mov_dn, srv;
-    if (compile_movements("tsc_env_set_pressure", P, measure, n_mov, mov, lane_route_mov, walk, mov_of, mov_dn)) return 1;
-    std::vector<int> off((size_t)P.A * P.PMAX + 1, 0);
-    for (int a = 0; a < P.A; ++a)
-        for (int p = 0; p < P.PMAX; ++p) {
-            for (int j = 0; j < srv_max; ++j) {
-                const int i = served[((size_t)a * P.PMAX + p) * srv_max + j];
-                if (i < 0) break;
-                if (p >= h->h_nphase[a]) return tsc::fail("tsc_env_set_pressure: agent %d phase %d of %d serves a movement", a, p, h->h_nphase[a]);
-                if (i >= n_mov || mov[4 * i] != a) return tsc::fail("tsc_env_set_pressure: agent %d phase %d serves movement %d of %d (or another agent's)", a, p, i, n_mov);
-                srv.push_back((short)i);
-            }
-            off[(size_t)a * P.PMAX + p + 1] = (int)srv.size();
-        }
-    const size_t smem = sizeof(int) * (2 * walk.size() + 1 + (size_t)n_mov + (size_t)P.A * P.PMAX + kPressT);
-    if (smem > 48 * 1024) return tsc::fail("tsc_env_set_pressure: LDS need %zu B > 48 KiB (%zu walked lanes, %d movements)", smem, walk.size(), n_mov);
     (void)hipSetDevice(h->device);
-    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running pressure_kernel may still read the old tables
-    PressDev &Q = h->Q;
-    free_tables(h, {Q.walk, Q.mov_of, Q.mov_dn, Q.srv_off, Q.srv});
-    Q.walk = nullptr; Q.mov_of = nullptr; Q.mov_dn = nullptr; Q.srv_off = nullptr; Q.srv = nullptr;
-#define UPQ(field, T, vec)                                                       \
-    do {                                                                         \
-        T *d_ = nullptr;                                                         \
-        TSC_HIP(tsc::upload<T>(&d_, (vec).data(), (vec).size()));                \
-        h->allocs.push_back(d_);                                                 \
-        Q.field = d_;                                                            \
-    } while (0)
-    UPQ(walk, short, walk); UPQ(mov_of, short, mov_of); UPQ(mov_dn, short, mov_dn); UPQ(srv_off, int, off); UPQ(srv, short, srv);
-#undef UPQ
-    if (!Q.hold) {
-        TSC_HIP(hipMalloc((void **)&Q.hold, sizeof(int) * 2 * (size_t)P.E * P.A));
-        h->allocs.push_back(Q.hold);
+    // Build, then swap: the handle's Q changes only when every table of the new one, N, is on the device.
+    PressDev N = {};
+    size_t smem = 0;
+    const auto drop = [h](const PressDev &q) { release_movements(h, q.M); h->bufs.release(q.srv_off); h->bufs.release(q.srv); h->bufs.release(q.hold); };
+    const auto build = [&]() {
+        if (upload_movements("tsc_env_set_pressure", h, measure, n_mov, mov, lane_route_mov, N.M, &smem)) return 1;
+        std::vector<short> srv;
+        std::vector<int> off((size_t)P.A * P.PMAX + 1, 0);
+        for (int a = 0; a < P.A; ++a)
+            for (int p = 0; p < P.PMAX; ++p) {
+                for (int j = 0; j < srv_max; ++j) {
+                    const int i = served[((size_t)a * P.PMAX + p) * srv_max + j];
+                    if (i < 0) break;
+                    if (p >= h->h_nphase[a]) return tsc::fail("tsc_env_set_pressure: agent %d phase %d of %d serves a movement", a, p, h->h_nphase[a]);
+                    if (i >= n_mov || mov[4 * i] != a) return tsc::fail("tsc_env_set_pressure: agent %d phase %d serves movement %d of %d (or another agent's)", a, p, i, n_mov);
+                    srv.push_back((short)i);
+                }
+                off[(size_t)a * P.PMAX + p + 1] = (int)srv.size();
+            }
+        smem += sizeof(int) * (size_t)P.A * P.PMAX;
+        if (smem > 48 * 1024) return tsc::fail("tsc_env_set_pressure: LDS need %zu B > 48 KiB (%d walked lanes, %d movements)", smem, N.M.n_walk, n_mov);
+        TSC_HIP(h->bufs.upload(&N.srv_off, off.data(), off.size()));
+        TSC_HIP(h->bufs.upload(&N.srv, srv.data(), srv.size()));
+        N.min_green = min_green;
+        N.hold = h->Q.hold;                                    // the hold state: the handle's from the first arming on
+        if (!N.hold) TSC_HIP(h->bufs.alloc(&N.hold, 2 * (size_t)P.E * P.A, false));
+        TSC_HIP(hipStreamSynchronize(h->stream));              // a running pressure_kernel may still read the old tables
+        TSC_HIP(hipMemset(N.hold, 0x7F, sizeof(int) * 2 * (size_t)P.E * P.A));      // age >= min_green: the next decision is free
+        return 0;
+    };
+    if (build()) {                                             // refused: the handle is as it was
+        if (N.hold == h->Q.hold) N.hold = nullptr;             // (an armed handle's hold state stays its own)
+        drop(N);
+        return 1;
     }
-    TSC_HIP(hipMemset(Q.hold, 0x7F, sizeof(int) * 2 * (size_t)P.E * P.A));      // age >= min_green: the next decision is free
-    Q.n_mov = n_mov; Q.n_walk = (int)walk.size(); Q.measure = measure; Q.min_green = min_green;
+    h->Q.hold = nullptr;                                       // (N's now)
+    drop(h->Q);
+    h->Q = N;
     h->smem_press = smem;
     return 0;
 }
@@ -2695,52 +2705,51 @@ int tsc_env_pressure_actions(tsc_env *h, int32_t *action_dev, int32_t *pressure_
 
 int tsc_env_set_reward_pressure(tsc_env *h, int32_t measure, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov) {
     if (!h) return tsc::fail("tsc_env_set_reward_pressure: null handle");
-    PressRewDev &R = h->R;
     const EnvDev &P = h->P;
+    const auto drop = [h](const PressRewDev &r) { release_movements(h, r.M); h->bufs.release(r.agt_off); h->bufs.release(r.agt_mov); h->bufs.release(r.acc); };
     if (measure == -1) {                                       // disarm: tsc_env_step and tsc_env_reward_sum return to the built-in reward
-        if (!R.acc) return 0;
+        if (!h->R.acc) return 0;
         (void)hipSetDevice(h->device);
         TSC_HIP(hipStreamSynchronize(h->stream));              // a running pressure_reward_kernel still reads the tables
-        free_tables(h, {R.walk, R.mov_of, R.mov_dn, R.agt_off, R.agt_mov, R.acc});
-        R = PressRewDev();
+        drop(h->R);
+        h->R = PressRewDev();
         h->smem_prew = 0;
         // the built-in sum starts over: what step_kernel added to it while the pressure reward was returned is no part of either sum
         TSC_HIP(hipMemset(P.reward_acc, 0, sizeof(double) * P.E));
         return 0;
     }
     if (!mov || !lane_route_mov || n_mov < 0) return tsc::fail("tsc_env_set_reward_pressure: bad arguments (null tables with measure %d)", measure);
-    std::vector<short> walk, mov_of, mov_dn, agt_mov;
-    if (compile_movements("tsc_env_set_reward_pressure", P, measure, n_mov, mov, lane_route_mov, walk, mov_of, mov_dn)) return 1;
-    std::vector<int> off((size_t)P.A + 1, 0);                  // agent -> movements, each agent's in ascending order
-    for (int a = 0; a < P.A; ++a) {
-        for (int i = 0; i < n_mov; ++i)
-            if (mov[4 * i] == a) agt_mov.push_back((short)i);
-        off[(size_t)a + 1] = (int)agt_mov.size();
-    }
-    const size_t smem = sizeof(double) * ((size_t)P.A + 1) + sizeof(int) * (2 * walk.size() + 1 + (size_t)n_mov + kPressT);
-    if (smem > 48 * 1024) return tsc::fail("tsc_env_set_reward_pressure: LDS need %zu B > 48 KiB (%zu walked lanes, %d movements)", smem, walk.size(), n_mov);
     (void)hipSetDevice(h->device);
-    TSC_HIP(hipStreamSynchronize(h->stream));                  // a running pressure_reward_kernel may still read the old tables
-    free_tables(h, {R.walk, R.mov_of, R.mov_dn, R.agt_off, R.agt_mov});
-    R.walk = nullptr; R.mov_of = nullptr; R.mov_dn = nullptr; R.agt_off = nullptr; R.agt_mov = nullptr;
-#define UPR(field, T, vec)                                                       \
-    do {                                                                         \
-        T *d_ = nullptr;                                                         \
-        TSC_HIP(tsc::upload<T>(&d_, (vec).data(), (vec).size()));                \
-        h->allocs.push_back(d_);                                                 \
-        R.field = d_;                                                            \
-    } while (0)
-    UPR(walk, short, walk); UPR(mov_of, short, mov_of); UPR(mov_dn, short, mov_dn); UPR(agt_off, int, off); UPR(agt_mov, short, agt_mov);
-#undef UPR
-    R.n_mov = n_mov; R.n_walk = (int)walk.size(); R.measure = measure;
-    h->smem_prew = smem;
-    if (!R.acc) {                                              // armed from here on: the pressure sum starts at zero
-        double *acc = nullptr;
-        TSC_HIP(hipMalloc((void **)&acc, sizeof(double) * (size_t)P.E));
-        h->allocs.push_back(acc);
-        TSC_HIP(hipMemset(acc, 0, sizeof(double) * (size_t)P.E));
-        R.acc = acc;
+    // Build, then swap: the handle's R changes only when every table of the new one, N, is on the device.
+    PressRewDev N = {};
+    size_t smem = 0;
+    const auto build = [&]() {
+        if (upload_movements("tsc_env_set_reward_pressure", h, measure, n_mov, mov, lane_route_mov, N.M, &smem)) return 1;
+        std::vector<short> agt_mov;
+        std::vector<int> off((size_t)P.A + 1, 0);              // agent -> movements, each agent's in ascending order
+        for (int a = 0; a < P.A; ++a) {
+            for (int i = 0; i < n_mov; ++i)
+                if (mov[4 * i] == a) agt_mov.push_back((short)i);
+            off[(size_t)a + 1] = (int)agt_mov.size();
+        }
+        smem += sizeof(double) * ((size_t)P.A + 1);
+        if (smem > 48 * 1024) return tsc::fail("tsc_env_set_reward_pressure: LDS need %zu B > 48 KiB (%d walked lanes, %d movements)", smem, N.M.n_walk, n_mov);
+        TSC_HIP(h->bufs.upload(&N.agt_off, off.data(), off.size()));
+        TSC_HIP(h->bufs.upload(&N.agt_mov, agt_mov.data(), agt_mov.size()));
+        N.acc = h->R.acc;                                      // the pressure sum: kept across a re-arm, from zero on first arming
+        if (!N.acc) TSC_HIP(h->bufs.alloc(&N.acc, (size_t)P.E, true));
+        TSC_HIP(hipStreamSynchronize(h->stream));              // a running pressure_reward_kernel may still read the old tables
+        return 0;
+    };
+    if (build()) {                                             // refused: the handle is as it was
+        if (N.acc == h->R.acc) N.acc = nullptr;                // (an armed handle's accumulator stays its own)
+        drop(N);
+        return 1;
     }
+    h->R.acc = nullptr;                                        // (N's now)
+    drop(h->R);
+    h->R = N;
+    h->smem_prew = smem;
     return 0;
 }
 
@@ -2815,11 +2824,7 @@ int tsc_env_debug_clock(tsc_env *h, int32_t enable, int64_t *stamps64_host) {
     if (!h) return tsc::fail("null handle");
     TSC_HIP(hipStreamSynchronize(h->stream));
     if (enable && !h->P.dbg) {
-        long long *d = nullptr;
-        TSC_HIP(hipMalloc((void **)&d, (64 + 7 * (size_t)h->P.E) * sizeof(long long)));
-        TSC_HIP(hipMemset(d, 0, (64 + 7 * (size_t)h->P.E) * sizeof(long long)));
-        h->allocs.push_back(d);
-        h->P.dbg = d;
+        TSC_HIP(h->bufs.alloc(&h->P.dbg, 64 + 7 * (size_t)h->P.E, true));
     }
     if (stamps64_host && h->P.dbg)
         TSC_HIP(hipMemcpy(stamps64_host, h->P.dbg, (enable == 3 ? 64 + 7 * (size_t)h->P.E : enable == 2 ? 64 + 2 * (size_t)h->P.E : 64) * sizeof(long long), hipMemcpyDeviceToHost));
@@ -2850,10 +2855,7 @@ int tsc_env_set_block_order(tsc_env *h, const int32_t *order_host) {
         if (e < 0 || e >= h->P.E || seen[e]) return tsc::fail("tsc_env_set_block_order: not a permutation of the %d instances", h->P.E);
         seen[e] = 1;
     }
-    if (!h->order_buf) {
-        TSC_HIP(hipMalloc((void **)&h->order_buf, sizeof(int) * (size_t)h->P.E));
-        h->allocs.push_back(h->order_buf);
-    }
+    if (!h->order_buf) TSC_HIP(h->bufs.alloc(&h->order_buf, (size_t)h->P.E, false));
     TSC_HIP(hipMemcpy(h->order_buf, order_host, sizeof(int) * (size_t)h->P.E, hipMemcpyHostToDevice));
     h->P.order = h->order_buf;
     return 0;

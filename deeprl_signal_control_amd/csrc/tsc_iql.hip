@@ -275,7 +275,7 @@ struct tsc_iql {
     double gamma, rnorm, rclip, max_norm;
     long long adam_t;
     hipStream_t stream;
-    std::vector<void *> allocs;
+    tsc::DeviceBufs bufs;           // every device buffer of the handle
     int *n_act;
     int16_t *rowrange;            // [A][SMAX][2]
     float *params, *grads, *m1, *m2, *W2T, *WqT;
@@ -340,13 +340,6 @@ QFusedArgs fused_args(const tsc_iql *h, long long size) {
 
 extern "C" {
 
-#define QMALLOC(ptr, T, count)                                                         \
-    do {                                                                               \
-        TSC_HIP(hipMalloc((void **)&(ptr), sizeof(T) * (size_t)(count)));              \
-        TSC_HIP(hipMemset((ptr), 0, sizeof(T) * (size_t)(count)));                     \
-        h->allocs.push_back((void *)(ptr));                                            \
-    } while (0)
-
 int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iql **out) {
     if (!cfg || !out || n_env <= 0) return tsc::fail("tsc_iql_create: bad arguments");
     if (cfg->a_max > kQ) return tsc::fail("tsc_iql_create: a_max %d > %d", cfg->a_max, kQ);
@@ -386,22 +379,22 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
             rr[((size_t)a * L.SMAX + j) * 2] = (int16_t)lo; rr[((size_t)a * L.SMAX + j) * 2 + 1] = (int16_t)hi;
         }
     }
-    TSC_HIP(tsc::upload<int16_t>(&h->rowrange, rr.data(), rr.size())); h->allocs.push_back(h->rowrange);
-    TSC_HIP(tsc::upload<int>(&h->n_act, cfg->n_act, L.A)); h->allocs.push_back(h->n_act);
+    TSC_HIP(h->bufs.upload(&h->rowrange, rr.data(), rr.size()));
+    TSC_HIP(h->bufs.upload(&h->n_act, cfg->n_act, L.A));
     const long long E = n_env, A = L.A, R = E * h->B, per = A * L.SMAX;
-    QMALLOC(h->params, float, h->nparam); QMALLOC(h->grads, float, h->nparam);
-    QMALLOC(h->m1, float, h->nparam); QMALLOC(h->m2, float, h->nparam);
-    QMALLOC(h->r_obs, float, E * h->cap * per); QMALLOC(h->r_next, float, E * h->cap * per);
-    QMALLOC(h->r_rew, float, E * h->cap * A); QMALLOC(h->r_act, int, E * h->cap * A); QMALLOC(h->r_done, uint8_t, E * h->cap);
-    QMALLOC(h->idx, int, E * A * h->B);
-    QMALLOC(h->Qe, float, A * E * kQ);
-    QMALLOC(h->norm2, double, A * kNormSlices); QMALLOC(h->stats, double, A * 2);
+    TSC_HIP(h->bufs.alloc(&h->params, h->nparam, true)); TSC_HIP(h->bufs.alloc(&h->grads, h->nparam, true));
+    TSC_HIP(h->bufs.alloc(&h->m1, h->nparam, true)); TSC_HIP(h->bufs.alloc(&h->m2, h->nparam, true));
+    TSC_HIP(h->bufs.alloc(&h->r_obs, E * h->cap * per, true)); TSC_HIP(h->bufs.alloc(&h->r_next, E * h->cap * per, true));
+    TSC_HIP(h->bufs.alloc(&h->r_rew, E * h->cap * A, true)); TSC_HIP(h->bufs.alloc(&h->r_act, E * h->cap * A, true)); TSC_HIP(h->bufs.alloc(&h->r_done, E * h->cap, true));
+    TSC_HIP(h->bufs.alloc(&h->idx, E * A * h->B, true));
+    TSC_HIP(h->bufs.alloc(&h->Qe, A * E * kQ, true));
+    TSC_HIP(h->bufs.alloc(&h->norm2, A * kNormSlices, true)); TSC_HIP(h->bufs.alloc(&h->stats, A * 2, true));
     // The fused DeepQPolicy learner (tsc_iql_fused.h) is built for the reference's widths (config/config_iqld_*.ini: num_fc 128,
     // num_h 64 -> H1 = 160 with wait inputs, 128 without) and observations of at most 48 features; anything else, IQL-LR, and
     // TSC_IQL_FUSED=0 (the A/B switch of tests/test_iql_gpu.py) take the grouped-GEMM path.
     h->fused = 0; h->fS = h->fcps = 0; h->fws = h->fwsl = nullptr; h->dbg = nullptr;
-    TSC_HIP(tsc::upload<int>(&h->n_wave, cfg->n_wave, L.A)); h->allocs.push_back(h->n_wave);
-    TSC_HIP(tsc::upload<int>(&h->n_wait, cfg->n_wait, L.A)); h->allocs.push_back(h->n_wait);
+    TSC_HIP(h->bufs.upload(&h->n_wave, cfg->n_wave, L.A));
+    TSC_HIP(h->bufs.upload(&h->n_wait, cfg->n_wait, L.A));
     {
         const char *sw = getenv("TSC_IQL_FUSED");
         const bool want = !(sw && sw[0] == '0');
@@ -423,7 +416,7 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
         if (S > nchunks) S = nchunks;
         h->fcps = (int)((nchunks + S - 1) / S);
         h->fS = (int)((nchunks + h->fcps - 1) / h->fcps);
-        QMALLOC(h->fws, float, (long long)h->fS * A * L.stride); QMALLOC(h->fwsl, float, (long long)h->fS * A);
+        TSC_HIP(h->bufs.alloc(&h->fws, (long long)h->fS * A * L.stride, true)); TSC_HIP(h->bufs.alloc(&h->fwsl, (long long)h->fS * A, true));
         const int lds_g = (h->fused == 10 ? QFusedLds<10>::grad_floats : QFusedLds<8>::grad_floats) * 4;
         const int lds_f = (h->fused == 10 ? QFusedLds<10>::fwd_floats : QFusedLds<8>::fwd_floats) * 4;
         if (h->fused == 10) {
@@ -437,18 +430,18 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
         h->X1 = h->X2 = h->dX2 = h->X1e = h->X2e = h->W2T = h->WqT = nullptr;
         h->ws = h->wsc = nullptr; h->ws_floats = h->wsc_floats = 0;
     } else {
-        QMALLOC(h->S, float, A * R * L.SMAX); QMALLOC(h->S1, float, A * R * L.SMAX);
-        QMALLOC(h->rew, float, A * R); QMALLOC(h->q1, float, A * R); QMALLOC(h->act, int, A * R); QMALLOC(h->done, uint8_t, A * R);
-        QMALLOC(h->Q, float, A * R * kQ); QMALLOC(h->dQ, float, A * R * kQ);
+        TSC_HIP(h->bufs.alloc(&h->S, A * R * L.SMAX, true)); TSC_HIP(h->bufs.alloc(&h->S1, A * R * L.SMAX, true));
+        TSC_HIP(h->bufs.alloc(&h->rew, A * R, true)); TSC_HIP(h->bufs.alloc(&h->q1, A * R, true)); TSC_HIP(h->bufs.alloc(&h->act, A * R, true)); TSC_HIP(h->bufs.alloc(&h->done, A * R, true));
+        TSC_HIP(h->bufs.alloc(&h->Q, A * R * kQ, true)); TSC_HIP(h->bufs.alloc(&h->dQ, A * R * kQ, true));
         if (L.dqn) {
-            QMALLOC(h->X1, float, A * R * L.H1); QMALLOC(h->X2, float, A * R * L.H2); QMALLOC(h->dX2, float, A * R * L.H2);
-            QMALLOC(h->X1e, float, A * E * L.H1); QMALLOC(h->X2e, float, A * E * L.H2);
-            QMALLOC(h->W2T, float, A * L.H1 * L.H2); QMALLOC(h->WqT, float, A * L.H2 * kQ);
+            TSC_HIP(h->bufs.alloc(&h->X1, A * R * L.H1, true)); TSC_HIP(h->bufs.alloc(&h->X2, A * R * L.H2, true)); TSC_HIP(h->bufs.alloc(&h->dX2, A * R * L.H2, true));
+            TSC_HIP(h->bufs.alloc(&h->X1e, A * E * L.H1, true)); TSC_HIP(h->bufs.alloc(&h->X2e, A * E * L.H2, true));
+            TSC_HIP(h->bufs.alloc(&h->W2T, A * L.H1 * L.H2, true)); TSC_HIP(h->bufs.alloc(&h->WqT, A * L.H2 * kQ, true));
         } else {
             h->X1 = h->X2 = h->dX2 = h->X1e = h->X2e = h->W2T = h->WqT = nullptr;
         }
         h->ws_floats = (size_t)16 << 20; h->wsc_floats = (size_t)1 << 18;
-        QMALLOC(h->ws, float, h->ws_floats); QMALLOC(h->wsc, float, h->wsc_floats);
+        TSC_HIP(h->bufs.alloc(&h->ws, h->ws_floats, true)); TSC_HIP(h->bufs.alloc(&h->wsc, h->wsc_floats, true));
     }
     *out = guard.release();
     return 0;
@@ -457,8 +450,7 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
 int tsc_iql_destroy(tsc_iql *h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
-    for (void *p : h->allocs) (void)hipFree(p);
-    delete h;
+    delete h;                                    // (h->bufs frees the device buffers)
     return 0;
 }
 
@@ -672,9 +664,7 @@ int tsc_iql_debug_clock(tsc_iql *h, int32_t enable, int64_t *stamps_host, int32_
     TSC_HIP(hipStreamSynchronize(h->stream));
     const size_t n = 64 + 2 * (size_t)h->lay.A * h->fS;
     if (enable && !h->dbg) {
-        TSC_HIP(hipMalloc((void **)&h->dbg, n * sizeof(long long)));
-        TSC_HIP(hipMemset(h->dbg, 0, n * sizeof(long long)));
-        h->allocs.push_back(h->dbg);
+        TSC_HIP(h->bufs.alloc(&h->dbg, n, true));
     }
     if (stamps_host && h->dbg)
         TSC_HIP(hipMemcpy(stamps_host, h->dbg, sizeof(long long) * ((size_t)count < n ? (size_t)count : n), hipMemcpyDeviceToHost));

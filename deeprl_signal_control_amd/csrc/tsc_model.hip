@@ -2639,7 +2639,7 @@ struct tsc_model {
     int E, T, device;
     double gamma, rnorm, rclip, vcoef, max_norm, alpha, eps;
     hipStream_t stream;
-    std::vector<void *> allocs;
+    tsc::DeviceBufs bufs;           // every device buffer of the handle
     int *n_act;
     int16_t *rowrange;          // [A][SMAX][2]
     int *wgmap; unsigned fwd_wgs;   // Ws forward: blockIdx -> (tower << 8 | split), XCD-affine (null: TSC_FWD_XCD=0); workgroups
@@ -2704,13 +2704,6 @@ size_t fc_thread_lds(int H) { return sizeof(float) * ((size_t)64 * kFcLdo + (siz
 
 extern "C" {
 
-#define MALLOC(ptr, T, count)                                                          \
-    do {                                                                               \
-        TSC_HIP(hipMalloc((void **)&(ptr), sizeof(T) * (size_t)(count)));              \
-        TSC_HIP(hipMemset((ptr), 0, sizeof(T) * (size_t)(count)));                     \
-        m->allocs.push_back((void *)(ptr));                                            \
-    } while (0)
-
 int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, tsc_model **out) {
     if (!cfg || !out || n_env <= 0) return tsc::fail("tsc_model_create: bad arguments");
     if (cfg->n_lstm != kL) return tsc::fail("tsc_model_create: num_lstm must be %d", kL);
@@ -2746,7 +2739,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
             rr[((size_t)a * L.SMAX + j) * 2 + 1] = (int16_t)hi;
         }
     }
-    TSC_HIP(tsc::upload<int16_t>(&m->rowrange, rr.data(), rr.size())); m->allocs.push_back(m->rowrange);
+    TSC_HIP(m->bufs.upload(&m->rowrange, rr.data(), rr.size()));
     {   // per (agent, 32-column tile of the first layer): the obs rows with a structural non-zero in the tile, in MFMA steps
         std::vector<int> kr((size_t)L.A * 8 * 2, 0);
         for (int a = 0; a < L.A; ++a)
@@ -2759,7 +2752,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
                 if (j1 <= j0) { j0 = 0; j1 = 0; }
                 kr[((size_t)a * 8 + w) * 2] = j0 / 2; kr[((size_t)a * 8 + w) * 2 + 1] = (j1 + 1) / 2;
             }
-        TSC_HIP(tsc::upload<int>(&m->krange, kr.data(), kr.size())); m->allocs.push_back(m->krange);
+        TSC_HIP(m->bufs.upload(&m->krange, kr.data(), kr.size()));
     }
     {   // per (agent, 16-column unit): which 16-row tiles of W1 hold a structural non-zero
         const int ncu = (L.H + 15) / 16;
@@ -2770,28 +2763,28 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
                     const int lo = rr[((size_t)a * L.SMAX + j) * 2], hi = rr[((size_t)a * L.SMAX + j) * 2 + 1];
                     if (lo < 16 * u + 16 && hi > 16 * u) fm[(size_t)a * ncu + u] |= 1 << (j >> 4);
                 }
-        TSC_HIP(tsc::upload<int>(&m->ftmask, fm.data(), fm.size())); m->allocs.push_back(m->ftmask);
+        TSC_HIP(m->bufs.upload(&m->ftmask, fm.data(), fm.size()));
     }
-    TSC_HIP(tsc::upload<int>(&m->n_act, cfg->n_act, L.A)); m->allocs.push_back(m->n_act);
+    TSC_HIP(m->bufs.upload(&m->n_act, cfg->n_act, L.A));
     const long long E = n_env, T = m->T, N = E * T, G = L.G, A = L.A;
-    MALLOC(m->params, float, m->nparam); MALLOC(m->grads, float, m->nparam); MALLOC(m->ms, float, m->nparam);
-    MALLOC(m->WxT, float, G * L.H * kG4);
-    MALLOC(m->Wg, float, G * (L.H + kL) * kG4);
+    TSC_HIP(m->bufs.alloc(&m->params, m->nparam, true)); TSC_HIP(m->bufs.alloc(&m->grads, m->nparam, true)); TSC_HIP(m->bufs.alloc(&m->ms, m->nparam, true));
+    TSC_HIP(m->bufs.alloc(&m->WxT, G * L.H * kG4, true));
+    TSC_HIP(m->bufs.alloc(&m->Wg, G * (L.H + kL) * kG4, true));
     m->wg_dirty = 1;
-    MALLOC(m->state_fw, float, G * E * 2 * kL); MALLOC(m->state_bw, float, G * E * 2 * kL);
-    MALLOC(m->r_obs, float, (N + E) * A * L.SMAX);          // T + 1 slots: slot t + 1 receives the obs the env returns at step t
-    MALLOC(m->r_act, int, N * A); MALLOC(m->r_rew, double, N * A);
-    MALLOC(m->r_val, float, N * A); MALLOC(m->r_done, uint8_t, (T + 1) * E);
-    MALLOC(m->Rs, float, N * A); MALLOC(m->Advs, float, N * A);
-    MALLOC(m->X1, float, G * N * L.H + 32 * L.H);        // + one tile nobody reads: the ws forward's branch-free X1 store when the cache is off
-    MALLOC(m->Z, float, G * N * kG4);
-    MALLOC(m->Hh, float, G * N * kL); MALLOC(m->Cc, float, G * N * kL); MALLOC(m->Hp, float, G * N * kL);
-    MALLOC(m->dHh, float, G * N * kL);
-    MALLOC(m->norm2, double, A); MALLOC(m->stats, double, A * 6);        // [A][4] losses | [A][2] PPO: clipped share, approximate KL
-    MALLOC(m->norm_part, double, A * kNormParts);
+    TSC_HIP(m->bufs.alloc(&m->state_fw, G * E * 2 * kL, true)); TSC_HIP(m->bufs.alloc(&m->state_bw, G * E * 2 * kL, true));
+    TSC_HIP(m->bufs.alloc(&m->r_obs, (N + E) * A * L.SMAX, true));          // T + 1 slots: slot t + 1 receives the obs the env returns at step t
+    TSC_HIP(m->bufs.alloc(&m->r_act, N * A, true)); TSC_HIP(m->bufs.alloc(&m->r_rew, N * A, true));
+    TSC_HIP(m->bufs.alloc(&m->r_val, N * A, true)); TSC_HIP(m->bufs.alloc(&m->r_done, (T + 1) * E, true));
+    TSC_HIP(m->bufs.alloc(&m->Rs, N * A, true)); TSC_HIP(m->bufs.alloc(&m->Advs, N * A, true));
+    TSC_HIP(m->bufs.alloc(&m->X1, G * N * L.H + 32 * L.H, true));        // + one tile nobody reads: the ws forward's branch-free X1 store when the cache is off
+    TSC_HIP(m->bufs.alloc(&m->Z, G * N * kG4, true));
+    TSC_HIP(m->bufs.alloc(&m->Hh, G * N * kL, true)); TSC_HIP(m->bufs.alloc(&m->Cc, G * N * kL, true)); TSC_HIP(m->bufs.alloc(&m->Hp, G * N * kL, true));
+    TSC_HIP(m->bufs.alloc(&m->dHh, G * N * kL, true));
+    TSC_HIP(m->bufs.alloc(&m->norm2, A, true)); TSC_HIP(m->bufs.alloc(&m->stats, A * 6, true));        // [A][4] losses | [A][2] PPO: clipped share, approximate KL
+    TSC_HIP(m->bufs.alloc(&m->norm_part, A * kNormParts, true));
     m->logp_old = nullptr; m->ppo_ready = 0;
     m->ws_floats = (size_t)48 << 20; m->wsc_floats = (size_t)1 << 20;      // 192 MiB + 4 MiB
-    MALLOC(m->ws, float, m->ws_floats); MALLOC(m->wsc, float, m->wsc_floats);
+    TSC_HIP(m->bufs.alloc(&m->ws, m->ws_floats, true)); TSC_HIP(m->bufs.alloc(&m->wsc, m->wsc_floats, true));
     m->lds_fwd = sizeof(float) * (64 * kWhLd + 64 * kHsLd);
     m->lds_fused = sizeof(float) * ((size_t)(L.H + 64) * kXLd + kL * kOut + kOut + 8);   // activations + head weights
     m->lds_ws = sizeof(float) * ((size_t)32 * (L.H + 64 + 4) + 64 * kWsLdx + (size_t)kL * kWsLdg + (size_t)kG4 * kWsLdg + 528 + (kWsBuf + 2) * 32 * kOut + (size_t)L.SMAX * L.H);
@@ -2838,7 +2831,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
                 used[x] += take; spn += take; left -= take;
             }
         }
-        TSC_HIP(tsc::upload<int>(&m->wgmap, tab.data(), tab.size())); m->allocs.push_back(m->wgmap);
+        TSC_HIP(m->bufs.upload(&m->wgmap, tab.data(), tab.size()));
         m->fwd_wgs = (unsigned)tab.size();
     }
     // Every kernel this handle launches with dynamic LDS may use the 160 KiB the plan checked each launch against: the same
@@ -2869,8 +2862,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
 int tsc_model_destroy(tsc_model *m) {
     if (!m) return 0;
     (void)hipSetDevice(m->device);
-    for (void *p : m->allocs) (void)hipFree(p);
-    delete m;
+    delete m;                                    // (m->bufs frees the device buffers)
     return 0;
 }
 
@@ -3263,7 +3255,7 @@ int tsc_model_compute_grads_ppo(tsc_model *m, const float *R_boot, double beta, 
         return tsc::fail("tsc_model_compute_grads_ppo: epoch %d without epoch 0 on this rollout (advantages and logp_old are taken there)", epoch);
     if (!m->logp_old) {
         TSC_HIP(hipSetDevice(m->device));
-        MALLOC(m->logp_old, float, (size_t)m->T * m->E * m->lay.A);
+        TSC_HIP(m->bufs.alloc(&m->logp_old, (size_t)m->T * m->E * m->lay.A, true));
     }
     const PpoArgs ppo = {clip_eps, gae_lambda, epoch};
     if (epoch == 0) m->ppo_ready = 0;                 // until this epoch 0 is through
@@ -3336,9 +3328,7 @@ int tsc_model_debug_clock(tsc_model *m, int32_t enable, int64_t *stamps_host, in
     TSC_HIP(hipStreamSynchronize(m->stream));
     const size_t n = 64 + 2 * 8 * (size_t)((m->lay.G + 7) / 8) * ((m->E + 63) / 64);
     if (enable && !m->dbg) {
-        TSC_HIP(hipMalloc((void **)&m->dbg, n * sizeof(long long)));
-        TSC_HIP(hipMemset(m->dbg, 0, n * sizeof(long long)));
-        m->allocs.push_back(m->dbg);
+        TSC_HIP(m->bufs.alloc(&m->dbg, n, true));
     }
     if (stamps_host && m->dbg)
         TSC_HIP(hipMemcpy(stamps_host, m->dbg, sizeof(long long) * ((size_t)count < n ? (size_t)count : n), hipMemcpyDeviceToHost));

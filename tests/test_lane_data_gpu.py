@@ -306,6 +306,32 @@ def test_lane_data_arguments():
         env.close()
 
 
+def test_lane_data_refused_rearm_keeps_handle():
+    """A re-arming call the library refuses changes nothing: the handle goes on as one that never saw it."""
+    scn = build_large_grid('greedy')
+    E = 2
+    bad, good = _pair(scn, E)
+    for env in (bad, good):
+        env.set_lane_data(60)
+        env.reset()
+    rng = np.random.RandomState(2)
+    _step_both([bad, good], scn, rng, E, 2)                          # the lane data is live when the bad call comes
+    tabs = scn.lane_data_slots()
+    ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    with pytest.raises(RuntimeError, match='bad slot tables'):
+        _lib.check(bad._L.tsc_env_lane_data(bad._h, 120, scn.n_lane - 1, tabs['slot0'].ctypes.data_as(ip),
+                                            tabs['start'].ctypes.data_as(fp), tabs['sumo'].ctypes.data_as(ip)))
+    for env in (bad, good):
+        env.reset()
+    _step_both([bad, good], scn, rng, E, 4)
+    (ints_b, speed_b), (ints_g, speed_g) = bad.read_lane_data(), good.read_lane_data()
+    np.testing.assert_array_equal(ints_b, ints_g)
+    np.testing.assert_array_equal(speed_b, speed_g)
+    assert ints_g.sum() > 0 and speed_g.sum() > 0
+    for env in (bad, good):
+        env.close()
+
+
 def test_evaluate_lane_data(tmp_path):
     """evaluate --lane-data 300 with 4 seeds over the reference's 3600-s episode: 4 x 12 x n_sumo_lanes rows; per seed the sampled
     vehicle-seconds equal the traffic table's vehicles."""

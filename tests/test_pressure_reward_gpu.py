@@ -18,7 +18,7 @@ import torch
 from deeprl_signal_control_amd import _lib
 from deeprl_signal_control_amd.env import VecTrafficEnv
 from deeprl_signal_control_amd.scenario import build_scenario
-from deeprl_signal_control_amd.trainer import pressure_reward
+from deeprl_signal_control_amd.trainer import max_pressure_actions, pressure_reward
 
 pytestmark = pytest.mark.gpu
 _scn = {}
@@ -189,6 +189,36 @@ def test_independent_of_the_controller():
     assert changed and both.reward_sum() == rew.reward_sum() < 0
     for env in (both, ctrl, rew):
         env.close()
+
+
+def test_rearm_replaces_tables():
+    """Re-arming the controller and the reward on one handle, twice each: every step runs on the tables of the setting in force,
+    and the pressure sum runs on across the reward's re-arming."""
+    scn, tb = scenario('small_grid', 'ma2c')
+    E = 2
+    env = VecTrafficEnv(scn, E, seed=31)
+    obs = env.reset()
+    first, second = (('count', 1), 'queue'), (('queue', 2), 'count')
+    gs = []
+    for t in range(12):
+        (c_measure, min_green), r_measure = second if 4 <= t < 8 else first
+        if t % 4 == 0:
+            env.set_reward_pressure(r_measure)
+        _, prs = env.max_pressure_actions(measure=c_measure, min_green=min_green, return_pressure=True)    # (re-arms on a new setting)
+        prs = prs.cpu().numpy()
+        for e in range(E):
+            _, want_p = max_pressure_actions(scn, env.get_state(e), c_measure, return_pressure=True)
+            np.testing.assert_array_equal(prs[e], want_p, err_msg='t=%d e=%d' % (t, e))
+        obs, reward, _, g = env.step(env.greedy_actions(obs))
+        gs.append(g.cpu().numpy().copy())
+        r_h = reward.cpu().numpy()
+        for e in range(E):
+            want_r, want_g, _ = pressure_reward(scn, env.get_state(e), r_measure)
+            np.testing.assert_array_equal(r_h[e], want_r, err_msg='t=%d e=%d' % (t, e))
+            np.testing.assert_array_equal(gs[-1][e], want_g, err_msg='t=%d e=%d' % (t, e))
+    assert env.reward_sum() == instance_sum(gs)            # the accumulator survived both re-armings
+    assert min(float(g.min()) for g in gs) < 0             # (an all-zero run would pass the rest)
+    env.close()
 
 
 def test_errors():

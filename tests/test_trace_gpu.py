@@ -215,3 +215,28 @@ def test_trace_overflow_and_detach():
     _tables_equal(traced, plain)
     for env in (traced, plain):
         env.close()
+
+
+def test_trace_refused_rearm_keeps_handle():
+    """A re-arming call the library refuses changes nothing: the handle goes on as one that never saw it."""
+    scn = build_large_grid('greedy')
+    E = 4
+    bad, good = _pair(scn, E)
+    for env in (bad, good):
+        env.set_trace([0, 2])
+        env.reset()
+    rng = np.random.RandomState(2)
+    _step_both([bad, good], scn, rng, E, 2)                        # the trace is running when the bad call comes
+    with pytest.raises(RuntimeError, match='instance 1 listed twice'):
+        bad.set_trace([1, 1])
+    for env in (bad, good):
+        env.reset()
+    _step_both([bad, good], scn, rng, E, 4)
+    tr_b, tr_g = bad.collect_trajectories(), good.collect_trajectories()
+    assert sorted(tr_b) == sorted(tr_g) == [0, 2]
+    for e in tr_g:
+        assert len(tr_g[e]['time_sec']) > 0 and sorted(tr_b[e]) == sorted(tr_g[e])
+        for k in tr_g[e]:
+            np.testing.assert_array_equal(tr_b[e][k], tr_g[e][k], err_msg='%d %s' % (e, k))
+    for env in (bad, good):
+        env.close()
