@@ -177,6 +177,18 @@ __global__ void iql_qmax_kernel(const float *Q, const int *n_act, long long R, i
     q1[i] = m;
 }
 
+// Double DQN (tsc_iql_set_target, double_q): a* = first maximum of the ONLINE net's Q(s') (np.argmax), q1 = the TARGET net's Q(s')[a*]
+__global__ void iql_qsel_kernel(const float *Qon, const float *Qtg, const int *n_act, long long R, int A, float *q1, int *astar) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)A * R) return;
+    const int na = n_act[i / R];
+    const float *q = Qon + i * kQ;
+    int best = 0;
+    for (int k = 1; k < na; ++k) if (q[k] > q[best]) best = k;
+    q1[i] = Qtg[i * kQ + best];
+    astar[i] = best;
+}
+
 // tq = done ? r : r + gamma q1 ; loss = mean((q0 - tq)^2) ; dQ[k] = 2 (q0 - tq) / R at k = a   (agents/policies.py:317-318)
 __global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done,
                               long long R, int A, float gamma, float *dQ, double *stats) {
@@ -292,7 +304,12 @@ struct tsc_iql {
     int fused, fS, fcps;
     int *n_wave, *n_wait;
     float *fws, *fwsl;
-    long long *dbg;
+    long long *dbg, *dbg_buf;     // the stamp buffer the kernels see (null while tsc_iql_debug_clock is off) / its allocation
+    // target network (tsc_iql_set_target): refresh period in Adam steps (0 = none: the reference's loss), Double DQN on top of it
+    int tgt_period, tgt_double;
+    float *tparams, *y, *Q2;      // the frozen copy [A][stride]; per-row TD targets [A][R] (fused path); the online net's Q(s') (grouped path, double_q)
+    int *astar;                   // [A][R] Double DQN's picks
+    bool y_valid;                 // a compute_grads ran on the armed handle
 };
 
 namespace {
@@ -310,9 +327,8 @@ int qgemm(tsc_iql *h, bool tn, int epi, int M, int N, int K, const float *A, lon
 }
 
 // Q(S) for `rows` rows per agent: S [A][rows][SMAX] -> X1, X2 (DQN) -> Q [A][rows][8]
-int q_forward(tsc_iql *h, const float *S, long long sS, int ldS, long long rows, float *X1, float *X2, float *Q) {
+int q_forward(tsc_iql *h, const float *P, const float *S, long long sS, int ldS, long long rows, float *X1, float *X2, float *Q) {
     const QLayout &L = h->lay;
-    const float *P = h->params;
     if (!L.dqn)
         return qgemm(h, false, tsc::EPI_BIAS, (int)rows, kQ, L.SMAX, S, sS, ldS, P + L.oWq, L.stride, kQ, Q, rows * kQ, kQ,
                      P + L.obq, L.stride, nullptr, 0, 0, nullptr, 0, nullptr, 0);
@@ -392,7 +408,8 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
     // The fused DeepQPolicy learner (tsc_iql_fused.h) is built for the reference's widths (config/config_iqld_*.ini: num_fc 128,
     // num_h 64 -> H1 = 160 with wait inputs, 128 without) and observations of at most 48 features; anything else, IQL-LR, and
     // TSC_IQL_FUSED=0 (the A/B switch of tests/test_iql_gpu.py) take the grouped-GEMM path.
-    h->fused = 0; h->fS = h->fcps = 0; h->fws = h->fwsl = nullptr; h->dbg = nullptr;
+    h->fused = 0; h->fS = h->fcps = 0; h->fws = h->fwsl = nullptr; h->dbg = h->dbg_buf = nullptr;
+    h->tgt_period = h->tgt_double = 0; h->tparams = h->y = h->Q2 = nullptr; h->astar = nullptr; h->y_valid = false;
     TSC_HIP(h->bufs.upload(&h->n_wave, cfg->n_wave, L.A));
     TSC_HIP(h->bufs.upload(&h->n_wait, cfg->n_wait, L.A));
     {
@@ -422,9 +439,15 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
         if (h->fused == 10) {
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_act_kernel<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8, true, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<10, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<10, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds_f));
         } else {
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_act_kernel<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8, true, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<8, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<8, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds_f));
         }
         h->S = h->S1 = h->rew = h->q1 = h->Q = h->dQ = nullptr; h->act = nullptr; h->done = nullptr;
         h->X1 = h->X2 = h->dX2 = h->X1e = h->X2e = h->W2T = h->WqT = nullptr;
@@ -515,7 +538,7 @@ int tsc_iql_forward(tsc_iql *h, const float *obs, float *q_out, int32_t *action,
         return 0;
     }
     // obs [E][A][SMAX]: agent a's rows start at a * SMAX with row stride A * SMAX
-    if (q_forward(h, obs, L.SMAX, L.A * L.SMAX, h->E, h->X1e, h->X2e, h->Qe)) return tsc::fail("tsc_iql_forward: gemm launch failed");
+    if (q_forward(h, h->params, obs, L.SMAX, L.A * L.SMAX, h->E, h->X1e, h->X2e, h->Qe)) return tsc::fail("tsc_iql_forward: gemm launch failed");
     const int tot = h->E * L.A;
     hipLaunchKernelGGL(iql_act_kernel, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->Qe, h->n_act, h->E, L.A, L.AMAX,
                        (int)mode, eps, (unsigned long long)seed, (unsigned long long)step, q_out, action);
@@ -573,10 +596,31 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
             hipLaunchKernelGGL(iql_sample_kernel, dim3((unsigned)((E * A + 127) / 128)), dim3(128), 0, st, (int)E, (int)A, h->B, size,
                                (unsigned long long)seed, (unsigned long long)update_index, h->idx);
     }
+    const bool armed = h->tgt_period > 0;
+    if (armed) h->y_valid = true;
     if (h->fused) {
         QFusedArgs fa = fused_args(h, size);
         const unsigned grid = (unsigned)(A * h->fS);
-        {
+        if (armed) {        // two launches: the TD targets from the frozen copy (forward only), then the gradient with one row set
+            {
+                tsc::ProfScope ps(tsc::KID_IQL_TARGET, st);
+                const int lds_f = (h->fused == 10 ? QFusedLds<10>::fwd_floats : QFusedLds<8>::fwd_floats) * 4;
+                if (h->fused == 10 && h->tgt_double)
+                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, h->tparams, h->y, h->astar);
+                else if (h->fused == 10)
+                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, h->tparams, h->y, h->astar);
+                else if (h->tgt_double)
+                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, h->tparams, h->y, h->astar);
+                else
+                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, h->tparams, h->y, h->astar);
+            }
+            TSC_HIP(hipGetLastError());
+            tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
+            if (h->fused == 10)
+                hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8, true, const float *>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa, (const float *)h->y);
+            else
+                hipLaunchKernelGGL((iql_fused_grad_kernel<8, 8, true, const float *>), dim3(grid), dim3(256), QFusedLds<8>::grad_floats * 4, st, fa, (const float *)h->y);
+        } else {
             tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
             if (h->fused == 10)
                 hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa);
@@ -595,9 +639,15 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
                        (int)size, h->idx, h->r_obs, h->r_next, h->r_act, h->r_rew, h->r_done, h->S, h->S1, h->act, h->rew, h->done);
     TSC_HIP(hipGetLastError());
     // Q(s') first (its activations are not needed afterwards), then Q(s) with the activations the backward pass reads
-    if (q_forward(h, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
-    hipLaunchKernelGGL(iql_qmax_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->n_act, R, (int)A, h->q1);
-    if (q_forward(h, h->S, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
+    // (armed: Q(s') comes from the frozen copy; Double DQN adds the online net's Q(s'), whose first maximum picks the target's value)
+    if (q_forward(h, armed ? h->tparams : h->params, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
+    if (armed && h->tgt_double) {
+        if (q_forward(h, h->params, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q2)) return tsc::fail("gemm launch failed");
+        hipLaunchKernelGGL(iql_qsel_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q2, h->Q, h->n_act, R, (int)A, h->q1, h->astar);
+    } else {
+        hipLaunchKernelGGL(iql_qmax_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->n_act, R, (int)A, h->q1);
+    }
+    if (q_forward(h, h->params, h->S, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
     hipLaunchKernelGGL(iql_td_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, R,
                        (int)A, (float)h->gamma, h->dQ, h->stats);
     TSC_HIP(hipGetLastError());
@@ -646,6 +696,9 @@ int tsc_iql_apply_grads(tsc_iql *h, double lr, double grad_scale, double *stats_
                        L.stride, h->nparam, h->norm2, (float)grad_scale, (float)h->max_norm, (float)lr_t);
     TSC_HIP(hipGetLastError());
     ps.stop();
+    // target network: the frozen copy follows after every tgt_period-th Adam step of the handle (a resumed run keeps its phase)
+    if (h->tgt_period > 0 && h->adam_t % h->tgt_period == 0)
+        TSC_HIP(hipMemcpyAsync(h->tparams, h->params, sizeof(float) * h->nparam, hipMemcpyDeviceToDevice, st));
     if (stats_host) {
         std::vector<double> s(L.A * 2), n2p((size_t)L.A * kNormSlices), n2(L.A, 0.0);
         TSC_HIP(hipStreamSynchronize(st));
@@ -661,13 +714,86 @@ int tsc_iql_apply_grads(tsc_iql *h, double lr, double grad_scale, double *stats_
 int tsc_iql_debug_clock(tsc_iql *h, int32_t enable, int64_t *stamps_host, int32_t count) {
     if (!h) return tsc::fail("null handle");
     if (!h->fused) return tsc::fail("tsc_iql_debug_clock: only the fused learner carries clock stamps");
+    if (count < 0) return tsc::fail("tsc_iql_debug_clock: count %d < 0", count);
     TSC_HIP(hipStreamSynchronize(h->stream));
-    const size_t n = 64 + 2 * (size_t)h->lay.A * h->fS;
-    if (enable && !h->dbg) {
-        TSC_HIP(h->bufs.alloc(&h->dbg, n, true));
+    // [64] phase stamps | start / end of the gradient kernel's workgroups | start / end of the target kernel's (armed handles)
+    const size_t n = 64 + 4 * (size_t)h->lay.A * h->fS;
+    if (enable && !h->dbg_buf) {
+        TSC_HIP(h->bufs.alloc(&h->dbg_buf, n, true));
     }
-    if (stamps_host && h->dbg)
-        TSC_HIP(hipMemcpy(stamps_host, h->dbg, sizeof(long long) * ((size_t)count < n ? (size_t)count : n), hipMemcpyDeviceToHost));
+    h->dbg = enable ? h->dbg_buf : nullptr;       // off: the kernels stop stamping; the buffer (and what it holds) stays
+    if (stamps_host && h->dbg_buf)
+        TSC_HIP(hipMemcpy(stamps_host, h->dbg_buf, sizeof(long long) * ((size_t)count < n ? (size_t)count : n), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tsc_iql_set_target(tsc_iql *h, int32_t period, int32_t double_q) {
+    if (!h || period < 0 || (double_q != 0 && double_q != 1)) return tsc::fail("tsc_iql_set_target: bad arguments");
+    if (double_q && !period) return tsc::fail("tsc_iql_set_target: double_q needs a target network (period > 0)");
+    if (period > 0) {
+        const QLayout &L = h->lay;
+        const long long AR = (long long)L.A * h->E * h->B;
+        TSC_HIP(hipSetDevice(h->device));
+        // each buffer when its first user arms (a failed allocation leaves its pointer null, and the next call asks again)
+        if (!h->tparams) TSC_HIP(h->bufs.alloc(&h->tparams, h->nparam, true));
+        if (h->fused && !h->y) TSC_HIP(h->bufs.alloc(&h->y, AR, true));          // (the grouped path keeps q1, see tsc_iql_debug_targets)
+        if (double_q && !h->astar) TSC_HIP(h->bufs.alloc(&h->astar, AR, true));
+        if (double_q && !h->fused && !h->Q2) TSC_HIP(h->bufs.alloc(&h->Q2, AR * kQ, true));
+        if (!h->tgt_period)       // armed: the frozen copy starts as the parameters
+            TSC_HIP(hipMemcpyAsync(h->tparams, h->params, sizeof(float) * h->nparam, hipMemcpyDeviceToDevice, h->stream));
+    }
+    if (!period || period != h->tgt_period || double_q != h->tgt_double) h->y_valid = false;
+    h->tgt_period = period; h->tgt_double = double_q;
+    return 0;
+}
+
+int tsc_iql_sync_target(tsc_iql *h) {
+    if (!h) return tsc::fail("null handle");
+    if (!h->tgt_period) return tsc::fail("tsc_iql_sync_target: no target network (tsc_iql_set_target)");
+    TSC_HIP(hipMemcpyAsync(h->tparams, h->params, sizeof(float) * h->nparam, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+int tsc_iql_set_target_params(tsc_iql *h, const float *p) {
+    if (!h || !p) return tsc::fail("tsc_iql_set_target_params: bad arguments");
+    if (!h->tgt_period) return tsc::fail("tsc_iql_set_target_params: no target network (tsc_iql_set_target)");
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    TSC_HIP(hipMemcpy(h->tparams, p, sizeof(float) * h->nparam, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int tsc_iql_get_target_params(tsc_iql *h, float *p) {
+    if (!h || !p) return tsc::fail("tsc_iql_get_target_params: bad arguments");
+    if (!h->tgt_period) return tsc::fail("tsc_iql_get_target_params: no target network (tsc_iql_set_target)");
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    TSC_HIP(hipMemcpy(p, h->tparams, sizeof(float) * h->nparam, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tsc_iql_debug_targets(tsc_iql *h, float *y_host, int32_t *astar_host) {
+    if (!h || !y_host) return tsc::fail("tsc_iql_debug_targets: bad arguments");
+    if (!h->tgt_period || !h->y_valid) return tsc::fail("tsc_iql_debug_targets: no tsc_iql_compute_grads on an armed handle yet");
+    const size_t AR = (size_t)h->lay.A * h->E * h->B;
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    if (h->fused) {
+        TSC_HIP(hipMemcpy(y_host, h->y, sizeof(float) * AR, hipMemcpyDeviceToHost));
+    } else {
+        // the grouped path keeps q1 (what iql_td_kernel reads): the same float32 expression on the host
+        std::vector<float> q1(AR), rew(AR);
+        std::vector<uint8_t> done(AR);
+        TSC_HIP(hipMemcpy(q1.data(), h->q1, sizeof(float) * AR, hipMemcpyDeviceToHost));
+        TSC_HIP(hipMemcpy(rew.data(), h->rew, sizeof(float) * AR, hipMemcpyDeviceToHost));
+        TSC_HIP(hipMemcpy(done.data(), h->done, AR, hipMemcpyDeviceToHost));
+        const float gamma = (float)h->gamma;
+        for (size_t i = 0; i < AR; ++i) {
+            const float bootstrap = gamma * q1[i];
+            y_host[i] = done[i] ? rew[i] : rew[i] + bootstrap;
+        }
+    }
+    if (astar_host) {
+        if (h->tgt_double) TSC_HIP(hipMemcpy(astar_host, h->astar, sizeof(int32_t) * AR, hipMemcpyDeviceToHost));
+        else for (size_t i = 0; i < AR; ++i) astar_host[i] = -1;
+    }
     return 0;
 }
 

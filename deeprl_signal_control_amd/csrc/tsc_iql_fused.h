@@ -50,6 +50,7 @@ struct QFusedArgs {
     float *ws, *wsl;              // partial gradients [S][A][stride]; partial losses [S][A]
     long long stride, oW1, ob1, oW2, ob2, oWq, obq;
     long long *dbg;               // tsc_iql_debug_clock: [64] phase stamps of workgroup 0 (16 per wavefront, chunk 2) | [2 x workgroups] start / end (100 MHz)
+                                  //   | [2 x workgroups] start / end of the target kernel's workgroups (armed handles)
 };
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
@@ -115,7 +116,9 @@ struct QW1 {
     float t[NT][2][4];
 };
 
-template <int NB, int NM1, int NMW>
+// TAG: the armed handle's kernels (target network) take an instantiation of their own, 1: how the compiler inlines the lambdas below
+// depends on how many callers an instantiation has, and the default kernels must compile to what they compiled to without them
+template <int NB, int NM1, int NMW, int TAG = 0>
 __device__ __forceinline__ void q_nets(const QW1<NM1, NMW> &w1, const float4 (&s)[NB][3], const float *sm, const QRanges &rg, int m, int kq,
                                        f32x4 (&X1)[NB][NM1], f32x4 (&X2)[NB][4], f32x4 (&q)[NB], long long *fst = nullptr) {
     // NB independent row sets (the gradient kernel's s' and s) go through every layer side by side: one weight operand feeds NB
@@ -281,8 +284,15 @@ __device__ __forceinline__ float4 q_obs4(const float *row, int f0, int SMAX, boo
 }
 
 // ---- the minibatch gradient ---------------------------------------------------------------------------------------------------
-template <int NM1, int NMW>
-__global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p) {
+// TGT: the armed handle's variant, launched as iql_fused_grad_kernel<.., true, const float *>(p, y) -- the TD target of every row was
+// left by iql_fused_target_kernel in y [A][R], so only s goes through the nets (one row set) and neither s', the reward nor the done
+// flag is read; everything from the TD error on is the same code.  The default instantiations take no second argument (Y is empty).
+__device__ __forceinline__ const float *q_targets_of() { return nullptr; }
+__device__ __forceinline__ const float *q_targets_of(const float *y) { return y; }
+
+template <int NM1, int NMW, bool TGT = false, class... Y>
+__global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y... y_arg) {
+    static_assert(sizeof...(Y) == (TGT ? 1 : 0), "the armed variant takes the per-row targets, the default one nothing");
     using LD = QFusedLds<NM1>;
     constexpr int H1 = LD::H1;
     extern __shared__ __attribute__((aligned(16))) float q_smem[];
@@ -337,7 +347,15 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p) {
         const unsigned row = ((unsigned)c << 6) + 16 * wave + n;
         r.ok = row < uR && c < c1;
         const long long tr = ((long long)sl.e * p.cap + sl.slot) * p.A + a;
-        const float *o = p.r_obs + tr * p.SMAX, *o1 = p.r_next + tr * p.SMAX;
+        const float *o = p.r_obs + tr * p.SMAX;
+        if constexpr (TGT) {                             // the row's target is ready: rew carries it
+#pragma unroll
+            for (int qp = 0; qp < 3; ++qp) r.s0[qp] = q_obs4(o, 16 * qp + 4 * kq, p.SMAX, r.ok);
+            r.rew = q_targets_of(y_arg...)[(long long)a * p.R + (row < uR ? row : uR - 1)];
+            r.act = p.r_act[tr];
+            r.done = 0;
+        } else {
+        const float *o1 = p.r_next + tr * p.SMAX;
 #pragma unroll
         for (int qp = 0; qp < 3; ++qp) {
             r.s0[qp] = q_obs4(o, 16 * qp + 4 * kq, p.SMAX, r.ok);
@@ -346,6 +364,7 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p) {
         r.rew = p.r_rew[tr];
         r.act = p.r_act[tr];
         r.done = p.r_done[(long long)sl.e * p.cap + sl.slot];
+        }
     };
 
     const bool stamp_wg = p.dbg && blockIdx.x == 0 && lane == 0;
@@ -370,22 +389,28 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p) {
         // ================= phase A: 16 rows per wavefront =================
         QSTAMP(0);
         // Q(s') (set 0: only its maximum survives) and Q(s) (set 1: its activations feed the backward pass) side by side
-        f32x4 XX1[2][NM1], XX2[2][4], qq[2];
+        constexpr int NB = TGT ? 1 : 2;
+        f32x4 XX1[NB][NM1], XX2[NB][4], qq[NB];
         {
-            float4 ss[2][3];
+            float4 ss[NB][3];
 #pragma unroll
-            for (int qp = 0; qp < 3; ++qp) { ss[0][qp] = cur.s1[qp]; ss[1][qp] = cur.s0[qp]; }
-            q_nets<2, NM1, NMW>(w1, ss, sm, rg, n, kq, XX1, XX2, qq, (stamp_wg && c == c0 + 2) ? p.dbg + 16 * wave : nullptr);
+            for (int qp = 0; qp < 3; ++qp) {
+                if constexpr (!TGT) ss[0][qp] = cur.s1[qp];
+                ss[NB - 1][qp] = cur.s0[qp];
+            }
+            q_nets<NB, NM1, NMW, TGT ? 1 : 0>(w1, ss, sm, rg, n, kq, XX1, XX2, qq, (stamp_wg && c == c0 + 2) ? p.dbg + 16 * wave : nullptr);
         }
         QSTAMP(1);
-        f32x4 (&X1)[NM1] = XX1[1];
-        f32x4 (&X2)[4] = XX2[1];
-        const f32x4 q = qq[1];
+        f32x4 (&X1)[NM1] = XX1[NB - 1];
+        f32x4 (&X2)[4] = XX2[NB - 1];
+        const f32x4 q = qq[NB - 1];
         float q1 = -INFINITY;
+        if constexpr (!TGT) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) if (kq < 2 && 4 * kq + i < na) q1 = fmaxf(q1, qq[0][i]);
         q1 = fmaxf(q1, __shfl_xor(q1, 16, 64));
         q1 = fmaxf(q1, __shfl_xor(q1, 32, 64));
+        }
         const int act = cur.act;
         float q0 = 0.f;
 #pragma unroll
@@ -393,7 +418,9 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p) {
         q0 += __shfl_xor(q0, 16, 64);
         q0 += __shfl_xor(q0, 32, 64);
         // tq = done ? r : r + gamma q1;  loss = mean((q0 - tq)^2);  g = dLoss / dQ[a]   (agents/policies.py:315-318)
-        const float tq = cur.done ? cur.rew : cur.rew + p.gamma * q1;
+        float tq;
+        if constexpr (TGT) tq = cur.rew;                 // y of the row
+        else tq = cur.done ? cur.rew : cur.rew + p.gamma * q1;
         const float d = cur.ok ? q0 - tq : 0.f;
         const float g = 2.0f * d / fR;
         if (kq == 0) loss += d * d / fR;
@@ -734,6 +761,110 @@ __global__ void __launch_bounds__(256, 1) iql_fused_act_kernel(QFusedArgs p, con
             if (k < na && !found) { cdf += (double)qv[k] / sum; if (u < cdf / tot) { act = k; found = true; } }
     }
     action[idx] = act;
+}
+
+// ---- the TD targets of an armed handle (tsc_iql_set_target) ----------------------------------------------------------------
+// y[a][row] = done ? r : r + gamma max_j Q-(s')[j]                      (target network)
+//           = done ? r : r + gamma Q-(s')[argmax_j Q(s')[j]]            (DBL: Double DQN, van Hasselt 2016; first maximum like np.argmax)
+// Forward-only, the gradient kernel's shape: A x S workgroups, each walking its cps 64-row chunks with the weights staged once (the
+// frozen copy's W2 | Wq | biases in LDS and its W1 in registers; with DBL a second image and a second W1 for the online net, which
+// runs on the same observation registers), rows requested one chunk ahead.
+template <int NM1, int NMW, bool DBL>
+__global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, const float *__restrict__ tparams, float *__restrict__ y,
+                                                                  int *__restrict__ astar) {
+    using LD = QFusedLds<NM1>;
+    extern __shared__ __attribute__((aligned(16))) float q_smem[];
+    float *smT = q_smem, *smO = q_smem + LD::fwd_floats;
+    const int a = blockIdx.x % p.A, sp = blockIdx.x / p.A;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = lane & 15, kq = lane >> 4;
+    const float *PT = tparams + (long long)a * p.stride, *PO = p.params + (long long)a * p.stride;
+    const int na = p.n_act[a];
+    const QRanges rg = q_ranges(p.n_wave[a], p.n_wait[a]);
+    q_stage_weights<NM1>(PT, p, smT, tid, 256);
+    QW1<NM1, NMW> w1t;
+    q_load_w1<NM1, NMW>(PT, p, rg, n, kq, w1t);
+    [[maybe_unused]] QW1<NM1, NMW> w1o;
+    if constexpr (DBL) {
+        q_stage_weights<NM1>(PO, p, smO, tid, 256);
+        q_load_w1<NM1, NMW>(PO, p, rg, n, kq, w1o);
+    }
+    const long long nchunks = (p.R + 63) >> 6;
+    const long long c0 = (long long)sp * p.cps;
+    long long c1 = c0 + p.cps;
+    if (c1 > nchunks) c1 = nchunks;
+
+    struct Rows { float4 s1[3]; float rew; int done; bool ok; };
+    const unsigned uR = (unsigned)p.R, uB = (unsigned)p.B;                 // 32-bit rows, see iql_fused_grad_kernel
+    struct Slot { int slot; unsigned e; };
+    auto slot_of = [&](long long c) -> Slot {            // the gradient kernel's: the row is clamped into [0, R), the slot into the ring's filled part
+        unsigned row = ((unsigned)c << 6) + 16 * wave + n;
+        if (row >= uR) row = uR - 1;
+        Slot o;
+        o.e = row / uB;
+        const int s_ = p.idx[((long long)o.e * p.A + a) * p.B + (row - o.e * uB)];
+        o.slot = s_ < 0 ? 0 : s_ >= p.size ? p.size - 1 : s_;
+        return o;
+    };
+    auto load_rows = [&](long long c, const Slot &sl, Rows &r) {
+        const unsigned row = ((unsigned)c << 6) + 16 * wave + n;
+        r.ok = row < uR && c < c1;
+        const long long tr = ((long long)sl.e * p.cap + sl.slot) * p.A + a;
+        const float *o1 = p.r_next + tr * p.SMAX;
+#pragma unroll
+        for (int qp = 0; qp < 3; ++qp) r.s1[qp] = q_obs4(o1, 16 * qp + 4 * kq, p.SMAX, r.ok);
+        r.rew = p.r_rew[tr];
+        r.done = p.r_done[(long long)sl.e * p.cap + sl.slot];
+    };
+    long long *wg_dbg = p.dbg ? p.dbg + 64 + 2 * (long long)gridDim.x + 2 * blockIdx.x : nullptr;
+    if (wg_dbg && tid == 0) wg_dbg[0] = wall_clock64();
+    Rows cur, nxt;
+    Slot slot_n = {0, 0};
+    if (c0 < c1) {
+        load_rows(c0, slot_of(c0), cur);
+        slot_n = slot_of(c0 + 1 < c1 ? c0 + 1 : c0);
+    }
+    __syncthreads();                                      // weights are in LDS
+
+    for (long long c = c0; c < c1; ++c) {
+        load_rows(c + 1 < c1 ? c + 1 : c, slot_n, nxt);
+        slot_n = slot_of(c + 2 < c1 ? c + 2 : c);
+        float4 ss[1][3];
+#pragma unroll
+        for (int qp = 0; qp < 3; ++qp) ss[0][qp] = cur.s1[qp];
+        f32x4 X1[1][NM1], X2[1][4], qt[1];
+        q_nets<1, NM1, NMW, 1>(w1t, ss, smT, rg, n, kq, X1, X2, qt);
+        float q1 = -INFINITY;
+        int best = 8;
+        if constexpr (DBL) {
+            f32x4 qo[1];
+            q_nets<1, NM1, NMW, 1>(w1o, ss, smO, rg, n, kq, X1, X2, qo);
+            // first maximum of the online values over this row's four lanes (actions 4 kq + i, kq < 2), the target value riding along
+            float bv = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (kq < 2 && 4 * kq + i < na && qo[0][i] > bv) { bv = qo[0][i]; best = 4 * kq + i; q1 = qt[0][i]; }
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {
+                const float ov = __shfl_xor(bv, o, 64), oq = __shfl_xor(q1, o, 64);
+                const int ob = __shfl_xor(best, o, 64);
+                if (ov > bv || (ov == bv && ob < best)) { bv = ov; best = ob; q1 = oq; }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (kq < 2 && 4 * kq + i < na) q1 = fmaxf(q1, qt[0][i]);
+            q1 = fmaxf(q1, __shfl_xor(q1, 16, 64));
+            q1 = fmaxf(q1, __shfl_xor(q1, 32, 64));
+        }
+        const float tq = cur.done ? cur.rew : cur.rew + p.gamma * q1;
+        if (kq == 0 && cur.ok) {
+            const long long o = (long long)a * p.R + (((unsigned)c << 6) + 16 * wave + n);
+            y[o] = tq;
+            if constexpr (DBL) astar[o] = best;
+        }
+        cur = nxt;
+    }
+    if (wg_dbg && tid == 0) wg_dbg[1] = wall_clock64();
 }
 
 }  // namespace

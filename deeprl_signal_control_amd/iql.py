@@ -22,8 +22,20 @@ from .agents import CKPT_FORMAT, resume_sample_seed, Scheduler, allreduce_grads_
 
 IQL_DEFAULTS = dict(max_grad_norm=40.0, gamma=0.99, lr_init=1e-4, lr_decay='constant', lr_min=0.0, epsilon_init=1.0,
                     epsilon_min=0.01, epsilon_decay='linear', epsilon_ratio=0.5, num_fc=128, num_h=64, batch_size=20,
-                    buffer_size=1000.0, reward_norm=3000.0, reward_clip=2.0)     # config/config_iqld_large.ini
+                    buffer_size=1000.0, reward_norm=3000.0, reward_clip=2.0,     # config/config_iqld_large.ini
+                    target_update=0, double_q=0)    # opt-in, not the reference's: target network refreshed every N Adam steps / Double DQN
 N_UPDATE = 10                                                                    # agents/models.py:324
+
+
+def target_config(cfg):
+    """(target_update, double_q) of a coerced [MODEL_CONFIG]: 0 / 0 is the reference's loss (Q(s') from the network being updated,
+    agents/policies.py:315-318).  Double DQN needs the target network it evaluates a* with."""
+    period, dbl = int(cfg['target_update']), int(cfg['double_q'])
+    if period < 0 or dbl not in (0, 1):
+        raise ValueError('target_update must be >= 0 and double_q 0 or 1 (got %r, %r)' % (cfg['target_update'], cfg['double_q']))
+    if dbl and not period:
+        raise ValueError('double_q = 1 needs target_update > 0: without a target network it is the reference\'s loss under another name')
+    return period, dbl
 
 
 class TscIqlCfg(C.Structure):
@@ -56,6 +68,11 @@ def _setup_lib(L):
     L.tsc_iql_debug_batch.argtypes = [vp, vp]
     L.tsc_iql_path.argtypes = [vp, C.POINTER(C.c_int32)]
     L.tsc_iql_debug_clock.argtypes = [vp, C.c_int32, vp, C.c_int32]
+    L.tsc_iql_set_target.argtypes = [vp, C.c_int32, C.c_int32]
+    L.tsc_iql_sync_target.argtypes = [vp]
+    L.tsc_iql_set_target_params.argtypes = [vp, vp]
+    L.tsc_iql_get_target_params.argtypes = [vp, vp]
+    L.tsc_iql_debug_targets.argtypes = [vp, vp, vp]
     L._iql_ready = True
 
 
@@ -154,6 +171,7 @@ class VecIQL:
             raise ValueError("model_type must be 'dqn' or 'lr' (agents/models.py:298-307)")
         cfg = coerce_config(model_config, IQL_DEFAULTS)
         self.cfg, self.name, self.model_type = cfg, 'iql', model_type
+        self.target_update, self.double_q = target_config(cfg)
         self.n_agent, self.E = len(n_s_ls), int(n_env)
         self.n_s_ls, self.n_a_ls, self.n_w_ls = list(n_s_ls), list(n_a_ls), list(n_w_ls)
         self.n_wave_ls = [s - w for s, w in zip(self.n_s_ls, self.n_w_ls)]
@@ -199,11 +217,15 @@ class VecIQL:
         self.replay_seed = self.sample_seed ^ 0x5DEECE66D
         self.act_step = 0           # forward(mode='explore' / stochastic) calls so far: the action-RNG counter
         self.update_step = 0        # minibatch steps so far: the replay-sampling counter
+        if self.target_update:
+            _lib.check(L.tsc_iql_set_target(h, self.target_update, self.double_q))
         self.init_params(seed)
         if self.world > 1:
             t = torch.from_numpy(self.get_flat()).to(self.device)
             dist.broadcast(t, src=0, group=self.pg)
             self.set_flat(t.cpu().numpy())
+            if self.target_update:
+                self.sync_target()
 
     def _init_scheduler(self):
         """agents/models.py:297-317."""
@@ -224,6 +246,23 @@ class VecIQL:
         self.set_agent_params(init_agent_params(self.layout, rng))
         z = np.zeros(self.n_param, np.float32)
         _lib.check(self._L.tsc_iql_set_opt_state(self._h, z.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p), 0))
+        if self.target_update:
+            self.sync_target()
+
+    # ---- target network (target_update > 0; include/tsc.h tsc_iql_set_target) ------------------------------------
+    def sync_target(self):
+        """theta- <- theta.  set_flat / set_agent_params leave theta- alone; the refresh every target_update-th Adam step is the library's."""
+        _lib.check(self._L.tsc_iql_sync_target(self._h))
+
+    def get_target_flat(self):
+        out = np.zeros(self.n_param, np.float32)
+        _lib.check(self._L.tsc_iql_get_target_params(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_target_flat(self, flat):
+        flat = np.ascontiguousarray(flat, np.float32)
+        assert flat.size == self.n_param
+        _lib.check(self._L.tsc_iql_set_target_params(self._h, flat.ctypes.data_as(C.c_void_p)))
 
     def set_flat(self, flat):
         flat = np.ascontiguousarray(flat, np.float32)
@@ -335,10 +374,11 @@ class VecIQL:
     def save(self, model_dir, global_step):
         os.makedirs(model_dir, exist_ok=True)
         m, v, t = self.get_opt_state()
+        extra = {'target': self.get_target_flat()} if self.target_update else {}      # an unarmed model's file keeps its keys
         np.savez(os.path.join(model_dir, 'checkpoint-%d.npz' % int(global_step)), params=self.get_flat(), adam_m=m, adam_v=v,
                  layout=np.array(self.layout.as_tuple() + (self.s_max,), np.int64),
                  counters=np.array([t, self.act_step, self.update_step, self.base_seed, self.lr_scheduler.n, self.eps_scheduler.n], np.int64),
-                 format=np.int64(CKPT_FORMAT))
+                 format=np.int64(CKPT_FORMAT), **extra)
 
     def load(self, model_dir, checkpoint=None):
         save_file, save_step = None, 0
@@ -358,6 +398,11 @@ class VecIQL:
         if 'adam_m' not in z.files or tuple(int(x) for x in z['layout']) != want or z['params'].size != self.n_param:
             raise ValueError('checkpoint %s does not fit this model' % save_file)
         self.set_flat(z['params'])
+        if self.target_update:                  # a file written without a target network: theta- <- theta
+            if 'target' in z.files and z['target'].size == self.n_param:
+                self.set_target_flat(z['target'])
+            else:
+                self.sync_target()
         m, v = np.ascontiguousarray(z['adam_m'], np.float32), np.ascontiguousarray(z['adam_v'], np.float32)
         c = [int(x) for x in z['counters']]
         _lib.check(self._L.tsc_iql_set_opt_state(self._h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), c[0]))
@@ -418,6 +463,15 @@ class IQL:
 
     def reset(self):
         self.vec.reset()
+
+    def sync_target(self):
+        self.vec.sync_target()
+
+    def get_target_flat(self):
+        return self.vec.get_target_flat()
+
+    def set_target_flat(self, flat):
+        self.vec.set_target_flat(flat)
 
     def save(self, model_dir, global_step):
         self.vec.save(model_dir, global_step)

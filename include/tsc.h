@@ -100,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -508,12 +508,35 @@ int tsc_iql_debug_batch(tsc_iql *h, int32_t *idx_host);
  * (csrc/tsc_iql_fused.h: num_fc 128, num_h 64, s_max <= 48 -- the reference's configurations), 0 for the grouped-GEMM path
  * (IQL-LR, other widths, or TSC_IQL_FUSED=0 in the environment when the handle was created). */
 int tsc_iql_path(tsc_iql *h, int32_t *fused);
+/* Target network / Double DQN (opt-in; the reference has neither: agents/policies.py:315-318 bootstraps from the network it updates).
+ * period = N > 0 arms the handle: a frozen copy theta- of the parameters evaluates the bootstrap value,
+ *   double_q = 0:  y = done ? r : r + gamma max_{j < n_a} Q_theta-(s')[j]
+ *   double_q = 1:  a* = argmax_{j < n_a} Q_theta(s')[j] (first maximum, np.argmax);  y = done ? r : r + gamma Q_theta-(s')[a*]
+ * and the loss stays mean((Q_theta(s)[a] - stop_grad(y))^2).  theta- <- theta when the handle is armed, after every N-th Adam step
+ * counted by adam_t (tsc_iql_apply_grads; a device-to-device copy on the handle's stream behind the Adam kernel), and on
+ * tsc_iql_sync_target; tsc_iql_set_params does NOT touch it.  The first arming allocates theta- [A][stride] and what the path needs of the
+ * per-row targets and picks [A][E * batch_size].  period = 0 disarms: the handle launches what a handle that was never armed launches (double_q must
+ * be 0 then -- Double DQN without a target network is the reference's loss under another name).  tsc_iql_compute_grads / _at and
+ * tsc_iql_apply_grads keep their signatures; on the fused path an armed step is two launches, the targets (forward only) and the
+ * gradient with one row set. */
+int tsc_iql_set_target(tsc_iql *h, int32_t period, int32_t double_q);
+int tsc_iql_sync_target(tsc_iql *h);                                      /* theta- <- theta (armed handles) */
+int tsc_iql_set_target_params(tsc_iql *h, const float *params_host);      /* theta- of an armed handle: checkpoints, tests */
+int tsc_iql_get_target_params(tsc_iql *h, float *params_host);
+/* Debug / parity access: y [A][E * batch_size] of the last tsc_iql_compute_grads on an armed handle and (nullable) a* of the same
+ * rows, -1 unless double_q.  Fused path: the y the target kernel wrote and the gradient kernel read.  Grouped-GEMM path: the device
+ * keeps the bootstrap value q1 (max or picked target value) and iql_td_kernel forms y in registers, so y is restated here on the
+ * host from the device's q1, reward and done rows with the kernel's float32 expression -- what is checked there is q1 and a*.
+ * Synchronises. */
+int tsc_iql_debug_targets(tsc_iql *h, float *y_host, int32_t *astar_host);
 /* Measurement hook of the fused learner (tools/bench_iql.py --stamps): enable != 0 allocates the stamp buffer; the next
  * tsc_iql_compute_grads then records, for every workgroup, its start / end on the 100-MHz wall clock ([64 + 2 b],
  * [64 + 2 b + 1]) and -- in a measurement build with -DTSC_IQL_STAMPS (tools/build_variant.sh; the stamps' branches are kept
  * out of the product kernel) -- for workgroup 0 eleven shader-clock stamps per wavefront around the phases of its third 64-row
- * chunk ([16 w + k], csrc/tsc_iql_fused.h QSTAMP).  stamps_host (nullable) receives min(count, 64 + 2 x workgroups) values.
- * Synchronises. */
+ * chunk ([16 w + k], csrc/tsc_iql_fused.h QSTAMP).  On an armed handle (tsc_iql_set_target) the target kernel's workgroups leave
+ * their start / end behind the gradient kernel's ([64 + 2 W + 2 b], W = workgroups).  stamps_host (nullable) receives
+ * min(count, 64 + 4 x workgroups) values; count < 0 is refused.  enable = 0 detaches the buffer: the kernels stop stamping, what
+ * was recorded stays readable.  Synchronises. */
 int tsc_iql_debug_clock(tsc_iql *h, int32_t enable, int64_t *stamps_host, int32_t count);
 
 /* Test hook: the grouped fp32 MFMA GEMM used by every layer.  form: 0 = NN, 1 = TN; epi as

@@ -2,7 +2,12 @@
 """Times the IQL-DNN learner's launches in isolation (large_grid, E = 1024 by default): the minibatch gradient
 (tsc_iql_compute_grads: sample + fused gradient + reduce) and the acting forward, with HIP events on the launch stream.
 
-    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid]
+    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--target-update N [--double-q]]
+
+--target-update N arms the target network (two launches per gradient: the TD targets from the frozen copy, then the gradient with one
+row set).  --split adds the per-kernel split of the minibatch step ("kernel_us": iql_target / iql_grad / ..., each measured in a
+pass of its own with only its launches bracketed: 5 x reps more minibatch steps).  --stamps reads the gradient kernel's workgroups
+and, on an armed handle, the target kernel's as well ("target_wg_us").
 """
 import argparse
 import json
@@ -20,6 +25,9 @@ def main():
     ap.add_argument('--envs', type=int, default=1024)
     ap.add_argument('--reps', type=int, default=50)
     ap.add_argument('--scenario', default='large_grid')
+    ap.add_argument('--target-update', type=int, default=0, help='[MODEL_CONFIG] target_update: refresh the target network every N Adam steps (0: none)')
+    ap.add_argument('--double-q', action='store_true', help='[MODEL_CONFIG] double_q = 1 (needs --target-update)')
+    ap.add_argument('--split', action='store_true', help='per-kernel split of the minibatch step (one more pass of --reps steps per kernel)')
     ap.add_argument('--stamps', action='store_true', help='phase stamps of workgroup 0 and the start / end of every workgroup (tsc_iql_debug_clock)')
     args = ap.parse_args()
     from deeprl_signal_control_amd import _lib
@@ -28,7 +36,8 @@ def main():
     scn = build_scenario(args.scenario, 'iqld')
     E, A = args.envs, scn.n_agent
     m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, int(scn.green_tab.shape[1]),
-               dict(batch_size=20, buffer_size=1000, reward_norm=3000.0), total_step=10 ** 6, seed=0, model_type='dqn')
+               dict(batch_size=20, buffer_size=1000, reward_norm=3000.0, target_update=args.target_update, double_q=int(args.double_q)),
+               total_step=10 ** 6, seed=0, model_type='dqn')
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     mask = torch.zeros(A, scn.s_max, device='cuda')
     for a, n in enumerate(scn.n_s_ls):
@@ -59,9 +68,25 @@ def main():
     def grads():
         _lib.check(m._L.tsc_iql_compute_grads(m._h, 7, step[0]))
         step[0] += 1
-    out = {'fused': m.fused, 'E': E, 'compute_grads_us': timed(grads, args.reps),
+    out = {'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'compute_grads_us': timed(grads, args.reps),
            'forward_us': timed(lambda: m.forward(obs, mode='explore'), args.reps),
            'minibatch_step_us': timed(lambda: m.minibatch_step(1e-4), args.reps)}
+    # where a minibatch step's time goes: one kernel id at a time (an event pair inflates the launch behind it, include/tsc.h)
+    kern = {}
+    for name in (['iql_target'] * bool(m.target_update and m.fused) + ['iql_grad', 'iql_reduce', 'iql_sample', 'iql_adam']) * args.split:
+        _lib.profile_select([name])
+        _lib.profile(enable=True)
+        _lib.profile(reset=True)
+        for _ in range(args.reps):
+            m.minibatch_step(1e-4)
+        ms, cnt = _lib.profile().get(name, (0.0, 0))
+        _lib.profile(enable=False)
+        if cnt:
+            kern[name] = ms / cnt * 1e3
+    _lib.profile_select(None)
+    _lib.profile(reset=True)
+    if args.split:
+        out['kernel_us'] = kern
     if args.stamps and m.fused:
         import ctypes as C
         n = 64 + 2 * 4096
@@ -77,13 +102,20 @@ def main():
         fine = buf[:64].reshape(4, 16)
         if fine[0, 11]:
             out['nets_fine'] = {'L1': [int(fine[w, 11] - fine[w, 0]) for w in range(4)], 'relu1': [int(fine[w, 12] - fine[w, 11]) for w in range(4)], 'L2': [int(fine[w, 13] - fine[w, 12]) for w in range(4)], 'relu2': [int(fine[w, 14] - fine[w, 13]) for w in range(4)], 'Q': [int(fine[w, 1] - fine[w, 14]) for w in range(4)]}
+        def wg_stats(wg):
+            t0 = wg[:, 0].min()
+            return {'first_start': 0.0, 'last_start': float((wg[:, 0].max() - t0) / 100.0), 'min_dur': float((wg[:, 1] - wg[:, 0]).min() / 100.0),
+                    'median_dur': float(np.median(wg[:, 1] - wg[:, 0]) / 100.0), 'max_dur': float((wg[:, 1] - wg[:, 0]).max() / 100.0),
+                    'span': float((wg[:, 1].max() - t0) / 100.0)}
+        # [64 + 2 b]: the gradient kernel's workgroups; behind them, on an armed handle, the target kernel's (include/tsc.h): an unarmed
+        # handle leaves that half zero, so the number of workgroups is the number of stamped pairs, halved when armed
         wg = buf[64:].reshape(-1, 2)
         wg = wg[wg[:, 0] > 0]
-        t0 = wg[:, 0].min()
-        out['workgroups'] = int(len(wg))
-        out['wg_us'] = {'first_start': 0.0, 'last_start': float((wg[:, 0].max() - t0) / 100.0), 'min_dur': float((wg[:, 1] - wg[:, 0]).min() / 100.0),
-                        'median_dur': float(np.median(wg[:, 1] - wg[:, 0]) / 100.0), 'max_dur': float((wg[:, 1] - wg[:, 0]).max() / 100.0),
-                        'span': float((wg[:, 1].max() - t0) / 100.0)}
+        W = len(wg) // 2 if m.target_update else len(wg)
+        out['workgroups'] = int(W)
+        out['wg_us'] = wg_stats(wg[:W])
+        if m.target_update:
+            out['target_wg_us'] = wg_stats(wg[W:])
     gsum = float(m.grad_tensor().double().abs().sum().item())
     out['grad_abs_sum'] = gsum
     print(json.dumps(out))
