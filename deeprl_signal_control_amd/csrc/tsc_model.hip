@@ -2011,98 +2011,173 @@ __global__ void fill_kernel(float *p, long long n, float v) {
 // agents/utils.py:88-116 w.r.t. wx, wh, b):   [dWx ; dWh] = [X1 | h_prev]^T dZ,   dbl = colsum(dZ).
 // The output of a tower is only (H+64) x 256, so one workgroup (8 waves, one 32-column strip each, NT = (H+64)/32
 // accumulator tiles per wave) keeps ALL of it in registers and streams its share of the rows exactly once:
-//   * [X1 | h_prev] rows (the A operand, shared by all waves) are fetched once per workgroup with 16-byte loads,
-//     staged through registers into a double-buffered LDS chunk of 16 rows;
+//   * [X1 | h_prev] rows (the A operand, shared by all waves) are fetched once per workgroup with 16-byte loads, 16 rows
+//     (a sub-chunk) at a time, staged through registers into two LDS buffers of 64 rows: the MFMAs read one buffer while
+//     the rows four sub-chunks ahead are written into the other, so the workgroup meets at a barrier once per 64 rows;
 //   * dZ (the B operand, private to a wave's column strip) goes from HBM straight into MFMA operand registers
-//     (a 32x32x2 operand is two coalesced 128-byte row segments), one chunk ahead;
-//   * every global load is unconditional (rows clamped; rows past the split contribute through a zeroed dZ).
+//     (a 32x32x2 operand is two coalesced 128-byte row segments), one sub-chunk ahead;
+//   * intervals that touch nothing past the split load without any row compare, clamp or select; the last ones take the
+//     same schedule with clamped rows (rows past the split contribute through a zeroed dZ), so every load is unconditional.
+// -DTSC_UPD_STAMPS=1 (measurement builds): waves 0 and 4 of workgroup 0 stamp one step (tools/bench_update.py --stamps).
 // Deterministic: the row range of a tower is cut into S fixed splits (S x G workgroups ~ one per CU), partial
 // sums go to the workspace and are added in split order by dwxh_reduce_kernel.  Replaces two grouped GEMM
 // launches that each re-read dZ twice.
 // ------------------------------------------------------------------------------------------------
+// A workgroup-uniform pointer pinned to scalar registers: loads through it take the scalar base + 32-bit lane offset form, where
+// the loop optimiser would otherwise turn `base + lane offset` into a 64-bit induction pointer per lane and load.
+typedef const float __attribute__((address_space(1))) *gfloat_p;        // (the integer round trip would otherwise leave a flat pointer)
+typedef const f32x4 __attribute__((address_space(1))) *gfloat4_p;
+__device__ __forceinline__ gfloat_p uniform_ptr(const float *p) {
+    const unsigned long long v = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (gfloat_p)(((unsigned long long)hi << 32) | lo);
+}
+
+constexpr int kDwKc = 16, kDwKi = 64;     // rows per staging step (sub-chunk) / per LDS buffer (interval between two barriers)
+template <int NT> constexpr size_t dwxh_lds() { return sizeof(float) * 2 * kDwKi * (NT * 32 + 4); }
+
 template <int NT>
 __global__ void __launch_bounds__(512, 1)
 dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const float *__restrict__ dZ, long long N, int G,
-            int S, long long rows_per_split, float *__restrict__ ws) {
-    constexpr int HT = NT - 2, H = 32 * HT, KC = 16, LDA = NT * 32 + 4;     // +4: the two k rows of a step hit different banks
-    constexpr int XQ = H / 4, NX = KC * XQ, NQ = NX + KC * (kL / 4), NLD = (NQ + 511) / 512;
-    __shared__ __attribute__((aligned(16))) float As[2][KC][LDA];
+            int S, long long rows_per_split, float *__restrict__ ws, long long *dbg) {
+    constexpr int HT = NT - 2, H = 32 * HT, KC = kDwKc, LDA = NT * 32 + 4;     // +4: the two k rows of a step hit different banks
+    constexpr int XQ = H / 4, NX = KC * XQ;                     // float4s of a sub-chunk's X1 rows (its h_prev rows: KC * kL / 4 = 256)
+    static_assert(NX >= 512 && NX <= 1024 && NX % 64 == 0 && KC * (kL / 4) == 256, "staging slots");
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    float *As = (float *)smem_raw;                              // [2][kDwKi][LDA]: a ring of eight sub-chunks
     const int g = blockIdx.x % G, sp = blockIdx.x / G;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, kh = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, kh = lane >> 5;
     const int col0 = 32 * wave;
     const long long n0 = (long long)sp * rows_per_split;
     long long n1 = n0 + rows_per_split;
     if (n1 > N) n1 = N;
+    const long long R = n1 - n0;
     const float *x1 = X1 + (long long)g * N * H, *hp = Hp + (long long)g * N * kL;
-    const float *dz = dZ + (long long)g * N * kG4 + col0 + li;
+    const float *dz = dZ + (long long)g * N * kG4;
     f32x16 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     float bsum = 0.f;
-    // staging slots of this thread: (row in chunk, float4 column, source).  Kept in named scalars: as arrays
-    // the compiler parks the staged float4s in scratch and waits for every global load right after issuing it.
-    static_assert(NLD <= 3, "staging slots");
-    struct Slot { int row, col; bool x, ok; };
-    auto slot = [&](int q) {
-        Slot o;
-        int idx = tid + 512 * q;
-        o.ok = idx < NQ;
-        if (!o.ok) idx = NQ - 1;
-        o.x = idx < NX;
-        const int j = o.x ? idx : idx - NX, w = o.x ? XQ : kL / 4;
-        o.row = j / w; o.col = 4 * (j % w);
-        return o;
+    // Staging slots of a thread, per sub-chunk: float4 `tid` of the X1 rows, float4 `tid + 512` of them on the first
+    // (NX - 512) / 64 waves, and one float4 of the h_prev rows on waves 4..7.  Which slots a thread has is WAVE-uniform
+    // (scalar branches, no predicated LDS writes), and a slot's source is a workgroup-uniform row pointer plus a 32-bit
+    // lane offset that never changes.  Kept in named scalars: as arrays the compiler parks the staged float4s in scratch.
+    const bool has1 = wave < (NX - 512) / 64, has2 = wave >= 4;
+    struct Slots { int r0, c0, r1, c1, r2, c2; };
+    auto slots = [&](int t) {
+        const int i1 = has1 ? t + 512 : t, i2 = t & 255;
+        return Slots{t / XQ, 4 * (t % XQ), i1 / XQ, 4 * (i1 % XQ), i2 >> 4, 4 * (i2 & 15)};
     };
-    const Slot s0 = slot(0), s1 = slot(1), s2 = slot(2);
-    float4 g0, g1, g2;
-    auto fetch1 = [&](const Slot &o, long long row0) {
-        long long row = row0 + o.row;
-        if (row >= n1) row = n1 - 1;
-        const float *src = o.x ? x1 + row * H + o.col : hp + row * kL + o.col;
-        return *reinterpret_cast<const float4 *>(src);
-    };
-    auto commit1 = [&](const Slot &o, int buf, const float4 &v) {
-        if (o.ok) *reinterpret_cast<float4 *>(&As[buf][o.row][(o.x ? 0 : H) + o.col]) = v;
-    };
-#define DWXH_FETCH(row0) do { g0 = fetch1(s0, row0); if (NLD > 1) g1 = fetch1(s1, row0); if (NLD > 2) g2 = fetch1(s2, row0); } while (0)
-#define DWXH_COMMIT(buf) do { commit1(s0, buf, g0); if (NLD > 1) commit1(s1, buf, g1); if (NLD > 2) commit1(s2, buf, g2); } while (0)
+    const Slots sl = slots(tid);
+    const unsigned o0 = sl.r0 * H + sl.c0, o1 = sl.r1 * H + sl.c1, o2 = sl.r2 * kL + sl.c2;          // source, floats past the sub-chunk's first row
+    const unsigned l0 = sl.r0 * LDA + sl.c0, l1 = sl.r1 * LDA + sl.c1, l2 = sl.r2 * LDA + H + sl.c2; // LDS, floats past the sub-chunk's slot
+    const unsigned zb = kh * kG4 + col0 + li;
+    f32x4 g0, g1, g2;
     float bcur[KC / 2], bnxt[KC / 2];
-    auto fetch_b = [&](float *b, long long row0) {
-#pragma unroll
-        for (int ks = 0; ks < KC / 2; ++ks) {
-            const long long row = row0 + 2 * ks + kh;
-            const float z = dz[(row < n1 ? row : n1 - 1) * kG4];
-            b[ks] = row < n1 ? z : 0.f;
+    using Clamp = std::true_type;
+    using Plain = std::false_type;
+    // A rows [n0 + KC c, + KC) -> staging registers.  Plain: every row is inside the split; Clamp: rows past it read its last row.
+    auto fetch_a = [&](auto cl, long long c) {
+        if constexpr (decltype(cl)::value) {
+            // (the rows and columns once more from an opaque copy of tid: shared with the ones above they would stay live,
+            // in registers the full intervals cannot spare)
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            const Slots q = slots(t);
+            auto rowc = [&](long long r) { return r < n1 ? r : n1 - 1; };
+            const long long b = n0 + KC * c;
+            g0 = *reinterpret_cast<const f32x4 *>(x1 + rowc(b + q.r0) * H + q.c0);
+            if (has1) g1 = *reinterpret_cast<const f32x4 *>(x1 + rowc(b + q.r1) * H + q.c1);
+            if (has2) g2 = *reinterpret_cast<const f32x4 *>(hp + rowc(b + q.r2) * kL + q.c2);
+        } else {
+            const gfloat_p xs = uniform_ptr(x1 + (n0 + KC * c) * H), hs = uniform_ptr(hp + (n0 + KC * c) * kL);
+            g0 = *(gfloat4_p)(xs + o0);
+            if (has1) g1 = *(gfloat4_p)(xs + o1);
+            if (has2) g2 = *(gfloat4_p)(hs + o2);
         }
     };
-    if (n0 < n1) {
-        DWXH_FETCH(n0); fetch_b(bcur, n0);
-        DWXH_COMMIT(0);
-        DWXH_FETCH(n0 + KC);
-        __syncthreads();
-        int buf = 0;
-        for (long long row = n0; row < n1; row += KC, buf ^= 1) {
-            fetch_b(bnxt, row + KC);
-            __builtin_amdgcn_sched_barrier(0);
+    auto commit_a = [&](long long c) {
+        float *d = As + (unsigned)(c & 7) * (KC * LDA);
+        *reinterpret_cast<f32x4 *>(d + l0) = g0;
+        if (has1) *reinterpret_cast<f32x4 *>(d + l1) = g1;
+        if (has2) *reinterpret_cast<f32x4 *>(d + l2) = g2;
+    };
+    // dZ rows of sub-chunk c straight into MFMA operand registers; Clamp: rows past the split contribute zero
+    auto fetch_b = [&](auto cl, float *b, long long c) {
+        if constexpr (decltype(cl)::value) {
 #pragma unroll
             for (int ks = 0; ks < KC / 2; ++ks) {
-                float av[NT];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) av[t] = As[buf][2 * ks + kh][32 * t + li];
-                bsum += bcur[ks];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bcur[ks], acc[t], 0, 0, 0);
+                const long long row = n0 + KC * c + 2 * ks + kh;
+                const float z = dz[((row < n1 ? row : n1 - 1) - kh) * kG4 + zb];
+                b[ks] = row < n1 ? z : 0.f;
             }
-            __builtin_amdgcn_sched_barrier(0);
-            DWXH_COMMIT(buf ^ 1);                               // chunk row+KC (fetched one iteration ago)
-            DWXH_FETCH(row + 2 * KC);
+        } else {
+            const gfloat_p zs = uniform_ptr(dz + (n0 + KC * c) * kG4);
 #pragma unroll
-            for (int ks = 0; ks < KC / 2; ++ks) bcur[ks] = bnxt[ks];
+            for (int ks = 0; ks < KC / 2; ++ks) b[ks] = (zs + 2 * ks * kG4)[zb];
+        }
+    };
+#ifdef TSC_UPD_STAMPS
+    // dbg[0 .. 15] (dx1w1_kernel2: dbg[16 .. 31]) are also the rollout forward's stamp slots: the figures belong to this kernel only
+    // when the buffer is armed after the rollout, right before the update, as tools/bench_update.py --stamps does.  Sub-chunk 11
+    // must lie in a full interval (stamp 4 is taken after that loop's barrier): splits of at least 272 rows.
+    long long *stp = dbg && blockIdx.x == 0 && (tid == 0 || tid == 256) ? dbg + (tid >> 8) * 8 : nullptr;
+#define USTAMP(k, cc) do { if (stp && (cc) == 11) stp[k] = clock64(); } while (0)
+#else
+#define USTAMP(k, cc) do { } while (0)
+#endif
+    // Waves w and w + 4 share a SIMD.  Between two barriers they run out of phase: waves 0..3 stage first and then issue the
+    // sub-chunk's MFMAs, waves 4..7 issue the MFMAs first, so one wave's loads and LDS writes sit under its partner's MFMA
+    // stream and not beside its partner's staging.
+    const bool lead = wave < 4;
+    // sub-chunk c: dZ of c + 1 requested into bnxt (eight loads, no address arithmetic), then the MFMAs of its rows (LDS slot
+    // c & 7, dZ in bcur); staged before or after them: A rows of c + 4 into the other buffer (nobody reads it before the next
+    // barrier), A rows of c + 5 into the registers
+    auto sub = [&](auto cl, long long c) {
+        USTAMP(0, c);
+        auto stage = [&]() { commit_a(c + 4); fetch_a(cl, c + 5); };
+        fetch_b(cl, bnxt, c + 1);
+        if (lead) stage();
+        const float *a = As + (unsigned)(c & 7) * (KC * LDA) + kh * LDA + li;
+        __builtin_amdgcn_sched_barrier(0);
+        USTAMP(1, c);
+#pragma unroll
+        for (int ks = 0; ks < KC / 2; ++ks) {
+            float av[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) av[t] = a[2 * ks * LDA + 32 * t];
+            bsum += bcur[ks];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bcur[ks], acc[t], 0, 0, 0);
+        }
+        USTAMP(2, c);
+        __builtin_amdgcn_sched_barrier(0);
+        if (!lead) stage();
+#pragma unroll
+        for (int ks = 0; ks < KC / 2; ++ks) bcur[ks] = bnxt[ks];
+        USTAMP(3, c);
+    };
+    if (R > 0) {
+        for (int c = 0; c < 4; ++c) { fetch_a(Clamp{}, c); commit_a(c); }
+        fetch_a(Clamp{}, 4); fetch_b(Clamp{}, bcur, 0);
+        __syncthreads();
+        long long c = 0;
+        // full intervals: nothing they touch (MFMA rows of c .. c + 3, A rows up to sub-chunk c + 8) reaches past the split, and
+        // every 32-bit lane offset stays small; no row compare, clamp or select anywhere in the loop
+        for (; KC * (c + 9) <= R; c += 4) {
+            sub(Plain{}, c); sub(Plain{}, c + 1); sub(Plain{}, c + 2); sub(Plain{}, c + 3);
             __syncthreads();
+            USTAMP(4, c + 3);
+        }
+        // tail: the same schedule with clamped rows, until the split's rows are used up
+        for (; KC * c < R; ++c) {
+            sub(Clamp{}, c);
+            if ((c & 3) == 3) __syncthreads();
         }
     }
+#undef USTAMP
     float *w = ws + ((long long)sp * G + g) * ((long long)(NT * 32 + 1) * kG4);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
@@ -2113,8 +2188,6 @@ dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const fl
         }
     bsum += __shfl_xor(bsum, 32, 64);
     if (kh == 0) w[(long long)NT * 32 * kG4 + col0 + li] = bsum;
-#undef DWXH_FETCH
-#undef DWXH_COMMIT
 }
 
 // grads[g][oWx .. oWx + (H+64+1)*256) = sum over splits, in split order
@@ -2154,7 +2227,7 @@ template <int NCU>   // H / 16
 __global__ void __launch_bounds__(512, 1)
 dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const float *__restrict__ WxT,
               const float *__restrict__ obs, long long N, int G, int S, long long rows_per_split, int A, int SMAX,
-              float *__restrict__ ws, const int *__restrict__ ftm) {
+              float *__restrict__ ws, const int *__restrict__ ftm, long long *dbg) {
     constexpr int H = 16 * NCU, NHU = 2 * NCU;                  // half units (column unit x row tile) per chunk
     constexpr int CHI = (NHU + 7) / 8, CLO = NHU / 8;           // tiles of waves 0..3 / 4..7
     static_assert(NHU % 8 == 0 || NHU % 8 == 4, "H must be a multiple of 32");
@@ -2200,37 +2273,64 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     float bsum0 = 0.f, bsum1 = 0.f;
     // staging: thread -> four dZ float4s (rows tid >> 6 + 8 q, 16-byte column tid & 63) and one obs float4
     const int zr = tid >> 6, zc = tid & 63, orow = tid >> 4, oc = tid & 15;
-    float4 s0, s1, s2, s3, so;
-    auto fetch = [&](long long row0) {
-        auto rowc = [&](long long r) { return r < n1 ? r : n1 - 1; };
-        s0 = *reinterpret_cast<const float4 *>(dz + rowc(row0 + zr) * kG4 + 4 * zc);
-        s1 = *reinterpret_cast<const float4 *>(dz + rowc(row0 + zr + 8) * kG4 + 4 * zc);
-        s2 = *reinterpret_cast<const float4 *>(dz + rowc(row0 + zr + 16) * kG4 + 4 * zc);
-        s3 = *reinterpret_cast<const float4 *>(dz + rowc(row0 + zr + 24) * kG4 + 4 * zc);
-        const float4 o = *reinterpret_cast<const float4 *>(obs + rowc(row0 + orow) * AS + (long long)a * SMAX + 4 * (oc < sq ? oc : 0));
-        so = oc < sq ? o : make_float4(0.f, 0.f, 0.f, 0.f);
+    f32x4 s0, s1, s2, s3, so;
+    // Plain chunks lie whole inside the split: a workgroup-uniform row pointer plus 32-bit lane offsets that never change.
+    // Clamp (a split's last chunk): rows past the split read its last row and count as zero.
+    using Clamp = std::true_type;
+    using Plain = std::false_type;
+    const unsigned zo = zr * kG4 + 4 * zc, oo = (unsigned)orow * (unsigned)AS + 4 * (oc < sq ? oc : 0);
+    const bool ob_ok = oc < sq;
+    auto fetch = [&](auto cl, long long row0) {
+        if constexpr (decltype(cl)::value) {
+            auto rowc = [&](long long r) { return r < n1 ? r : n1 - 1; };
+            s0 = *reinterpret_cast<const f32x4 *>(dz + rowc(row0 + zr) * kG4 + 4 * zc);
+            s1 = *reinterpret_cast<const f32x4 *>(dz + rowc(row0 + zr + 8) * kG4 + 4 * zc);
+            s2 = *reinterpret_cast<const f32x4 *>(dz + rowc(row0 + zr + 16) * kG4 + 4 * zc);
+            s3 = *reinterpret_cast<const f32x4 *>(dz + rowc(row0 + zr + 24) * kG4 + 4 * zc);
+            const f32x4 o = *reinterpret_cast<const f32x4 *>(obs + rowc(row0 + orow) * AS + (long long)a * SMAX + 4 * (oc < sq ? oc : 0));
+            so = ob_ok ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            const gfloat_p zs = uniform_ptr(dz + row0 * kG4), os = uniform_ptr(obs + row0 * AS + (long long)a * SMAX);
+            s0 = *(gfloat4_p)(zs + zo);
+            s1 = *(gfloat4_p)(zs + 8 * kG4 + zo);
+            s2 = *(gfloat4_p)(zs + 16 * kG4 + zo);
+            s3 = *(gfloat4_p)(zs + 24 * kG4 + zo);
+            const f32x4 o = *(gfloat4_p)(os + oo);
+            so = ob_ok ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
     };
     auto put = [&](int buf) {
         float *zb = Az + (long long)buf * 32 * kD1Ld + 4 * zc;
-        *reinterpret_cast<float4 *>(zb + (zr) * kD1Ld) = s0;
-        *reinterpret_cast<float4 *>(zb + (zr + 8) * kD1Ld) = s1;
-        *reinterpret_cast<float4 *>(zb + (zr + 16) * kD1Ld) = s2;
-        *reinterpret_cast<float4 *>(zb + (zr + 24) * kD1Ld) = s3;
-        *reinterpret_cast<float4 *>(Ob + ((long long)buf * 32 + orow) * kObLd + 4 * oc) = so;
+        *reinterpret_cast<f32x4 *>(zb + (zr) * kD1Ld) = s0;
+        *reinterpret_cast<f32x4 *>(zb + (zr + 8) * kD1Ld) = s1;
+        *reinterpret_cast<f32x4 *>(zb + (zr + 16) * kD1Ld) = s2;
+        *reinterpret_cast<f32x4 *>(zb + (zr + 24) * kD1Ld) = s3;
+        *reinterpret_cast<f32x4 *>(Ob + ((long long)buf * 32 + orow) * kObLd + 4 * oc) = so;
     };
     // one column unit of the chunk in LDS buffer `buf`: both / one of its row tiles
-    auto unit = [&](int buf, long long row, const float (&bw)[64], int col, bool r0, bool r1, f32x4 (&aw)[4], float &bs, int fm) {
+    auto unit = [&](auto cl, int buf, long long row, const float (&bw)[64], int col, bool r0, bool r1, f32x4 (&aw)[4], float &bs, int fm) {
+        constexpr bool clamp = decltype(cl)::value;
         // relu mask rows 16 r + 4 kq + i of column col: requested first, consumed after the 64 / 128 MFMAs
         float xm0[4], xm1[4];
         int zq = 0;
         asm volatile("" : "+v"(zq));
+        if constexpr (clamp) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            long long ra = row + 4 * kq + i + zq, rb = ra + 16;
-            if (ra >= n1) ra = n1 - 1;
-            if (rb >= n1) rb = n1 - 1;
-            xm0[i] = x1[ra * H + col];
-            xm1[i] = x1[rb * H + col];
+            for (int i = 0; i < 4; ++i) {
+                long long ra = row + 4 * kq + i + zq, rb = ra + 16;
+                if (ra >= n1) ra = n1 - 1;
+                if (rb >= n1) rb = n1 - 1;
+                xm0[i] = x1[ra * H + col];
+                xm1[i] = x1[rb * H + col];
+            }
+        } else {
+            const gfloat_p xs = uniform_ptr(x1 + row * H);
+            const unsigned xo = (unsigned)(4 * kq * H + col + zq);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                xm0[i] = (xs + i * H)[xo];
+                xm1[i] = (xs + (16 + i) * H)[xo];
+            }
         }
         f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
         const float4 *A0 = reinterpret_cast<const float4 *>(Az + ((long long)buf * 32 + n) * kD1Ld + 4 * kq);
@@ -2280,7 +2380,7 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
             float d[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                d[i] = (xm[i] > 0.f && row + 16 * r + 4 * kq + i < n1) ? c[i] : 0.f;
+                d[i] = (xm[i] > 0.f && (!clamp || row + 16 * r + 4 * kq + i < n1)) ? c[i] : 0.f;
                 bs += d[i];
             }
 #pragma unroll
@@ -2293,19 +2393,41 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
         if (r0) tail(0, c0, xm0);
         if (r1) tail(1, c1, xm1);
     };
+#ifdef TSC_UPD_STAMPS
+    // (dbg[16 .. 31]: shared with the rollout forward's stamps like dwxh_kernel's dbg[0 .. 15], see there; chunk 5: splits of at
+    // least 192 rows)
+    long long *stp = dbg && blockIdx.x == 0 && (tid == 0 || tid == 256) ? dbg + 16 + (tid >> 8) * 8 : nullptr;
+#define USTAMP(k) do { if (stp && row == n0 + 5 * 32) stp[k] = clock64(); } while (0)
+#else
+#define USTAMP(k) do { } while (0)
+#endif
+    // Waves w and w + 4 share a SIMD: waves 0..3 request the next chunk before their tiles, waves 4..7 (one half unit fewer)
+    // between theirs, so that the two do not issue their staging side by side.  It lands while the chunk computes either way.
+    const bool lead = wave < 4 || !(a10 || a11);
+    auto chunk = [&](auto cl, int buf, long long row) {
+        USTAMP(0);
+        if (lead) fetch(cl, row + 32);
+        USTAMP(1);
+        if (a00 || a01) unit(cl, buf, row, bw0, col0, a00, a01, accW[0], bsum0, fm0);
+        if (!lead) fetch(cl, row + 32);
+        if (a10 || a11) unit(cl, buf, row, bw1, col1, a10, a11, accW[1], bsum1, fm1);
+        USTAMP(2);
+        put(buf ^ 1);
+        USTAMP(3);
+        __syncthreads();
+        USTAMP(4);
+    };
     if (n0 < n1) {
-        fetch(n0);
+        fetch(Clamp{}, n0);
         put(0);
         __syncthreads();
         int buf = 0;
-        for (long long row = n0; row < n1; row += 32, buf ^= 1) {
-            fetch(row + 32);                                    // lands while this chunk computes
-            if (a00 || a01) unit(buf, row, bw0, col0, a00, a01, accW[0], bsum0, fm0);
-            if (a10 || a11) unit(buf, row, bw1, col1, a10, a11, accW[1], bsum1, fm1);
-            put(buf ^ 1);
-            __syncthreads();
-        }
+        long long row = n0;
+        // full chunks whose successor is full too: no row compare, clamp or select anywhere in the loop
+        for (; row + 64 <= n1; row += 32, buf ^= 1) chunk(Plain{}, buf, row);
+        for (; row < n1; row += 32, buf ^= 1) chunk(Clamp{}, buf, row);
     }
+#undef USTAMP
     // partial results: slot 0 = row tile 0 (or both tiles of a unit owned by one wave), slot 1 = row tile 1 alone
     auto flush = [&](const f32x4 (&aw)[4], float bs, int col, bool r0, bool r1) {
         float *w0 = w + (long long)((r0 ? 0 : 1) * 65) * H;
@@ -2806,7 +2928,9 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
     if (!L.fc) {
         const bool tile = L.H % 32 == 0 && narrow_obs && m->lds_fused <= kLdsMax;
         P.fwd = !tile ? Fwd::Dense : wide && m->lds_ws <= kLdsMax && !(fwd_ws && fwd_ws[0] == '0') ? Fwd::Ws : Fwd::Tile;
-        P.dwxh = wide && !env_int("TSC_UNFUSED_DW", 0) && ws_fits((long long)(L.H + kL + 1) * kG4);
+        size_t lds_dwxh = 0;
+        with_fused_width(L.H, [&](auto w) { lds_dwxh = dwxh_lds<(decltype(w)::value + kL) / 32>(); });
+        P.dwxh = wide && lds_dwxh <= kLdsMax && !env_int("TSC_UNFUSED_DW", 0) && ws_fits((long long)(L.H + kL + 1) * kG4);
         P.dx1w1 = wide && narrow_obs && !unfused_dx && ws_fits((long long)2 * 65 * L.H);
     } else {
         // policy_fwd_fc_mfma_kernel fits every fused width (114 KiB of LDS at H = 224); the per-thread kernel does not fit at
@@ -2849,6 +2973,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
         constexpr int H = decltype(w)::value;
         if (P.fwd == Fwd::Ws) allow_lds((const void *)policy_fwd_ws_kernel<(H + kL) / 2>);
         if (P.fwd == Fwd::FcMfma) allow_lds((const void *)policy_fwd_fc_mfma_kernel<H / 32>);
+        if (P.dwxh) allow_lds((const void *)dwxh_kernel<(H + kL) / 32>);
         if (P.dx1w1) allow_lds((const void *)dx1w1_kernel2<H / 16>);
         if (P.fc_bwd) allow_lds((const void *)fc_bwd_kernel<H / 16>);
     });
@@ -3191,8 +3316,9 @@ static int compute_grads_impl(tsc_model *m, const float *R_boot, double beta, co
         {
             tsc::ProfScope ps(tsc::KID_DWX_GEMM, m->stream);
             with_fused_width(L.H, [&](auto w) {
-                hipLaunchKernelGGL(dwxh_kernel<(decltype(w)::value + kL) / 32>, dim3((unsigned)(S * G)), dim3(512), 0, st, m->X1, m->Hp,
-                                   m->Z, N, (int)G, S, rps, m->ws);
+                constexpr int NT = (decltype(w)::value + kL) / 32;
+                hipLaunchKernelGGL(dwxh_kernel<NT>, dim3((unsigned)(S * G)), dim3(512), dwxh_lds<NT>(), st, m->X1, m->Hp, m->Z, N, (int)G, S,
+                                   rps, m->ws, m->dbg);
             });
         }
         {
@@ -3216,7 +3342,7 @@ static int compute_grads_impl(tsc_model *m, const float *R_boot, double beta, co
             tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
             with_fused_width(L.H, [&](auto w) {
                 hipLaunchKernelGGL(dx1w1_kernel2<decltype(w)::value / 16>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->Z, m->X1, m->WxT,
-                                   m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask);
+                                   m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask, m->dbg);
             });
         }
         {

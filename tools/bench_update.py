@@ -4,7 +4,12 @@
     python tools/bench_update.py [--envs 1024] [--agent ma2c] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]]
 --algo ppo times `--ppo-epochs` epochs per rollout and also prints the wall time (stream-synchronised, profiling off) of an epoch-0
 update and of a later epoch (re-forward + update); --algo a2c prints the wall time of its one update the same way.
-Environment knobs of the library (TSC_UNFUSED_DW, TSC_UNFUSED_DX) select kernel variants for A/B runs."""
+Environment knobs of the library (TSC_UNFUSED_DW, TSC_UNFUSED_DX) select kernel variants for A/B runs.
+--stamps (a library built with TSC_BUILD_DEFS=-DTSC_UPD_STAMPS=1): shader-clock stamps of workgroup 0, waves 0 and 4 (the two
+wavefronts of one SIMD), in one step of dwxh_kernel (16 rows: sub-chunk 11, the last of its 64-row interval) and of dx1w1_kernel2
+(32 rows: chunk 5) -- step start, first MFMA, last MFMA, staging done, barrier passed -- printed as cycles per segment, each
+labelled with what that wave does in it (waves 0..3 stage before their MFMAs, waves 4..7 after).  Valid where the stamped step
+lies in an unclamped interval: splits of at least 272 rows (the benchmark shape: 24 576)."""
 import argparse
 import os
 import sys
@@ -23,6 +28,7 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--algo', default='a2c', choices=['a2c', 'ppo'])
     ap.add_argument('--ppo-epochs', type=int, default=2)
+    ap.add_argument('--stamps', action='store_true', help='per-step cycle split of dwxh / dx1w1 (needs a -DTSC_UPD_STAMPS=1 build)')
     ap.add_argument('--json', action='store_true', help='one JSON line with the wall times (ms) of the updates, per epoch index')
     args = ap.parse_args()
     from deeprl_signal_control_amd import _lib
@@ -49,8 +55,32 @@ def main():
         torch.cuda.synchronize()
         if rep == 1:
             _lib.profile(enable=1, reset=True)
+        if args.stamps and rep == args.reps:
+            _lib.check(m._L.tsc_model_debug_clock(m._h, 1, None, 0))
         m.backward(R)
     torch.cuda.synchronize()
+    if args.stamps:
+        import ctypes as C
+        st = np.zeros(32, np.int64)
+        _lib.check(m._L.tsc_model_debug_clock(m._h, 1, st.ctypes.data_as(C.c_void_p), 32))
+        # What lies between two stamps differs by wave: in dwxh waves 0..3 stage (LDS writes, row requests) BEFORE their MFMAs and
+        # waves 4..7 after; in dx1w1 waves 0..3 request the next chunk before their tiles, waves 4..7 between them (inside the MFMA
+        # segment), and both write LDS after the last MFMA.
+        seg_names = {('dwxh', 0): ('dZ requests + staging', 'MFMA block', 'operand moves', 'barrier'),
+                     ('dwxh', 1): ('dZ requests', 'MFMA block', 'staging + operand moves', 'barrier'),
+                     ('dx1w1', 0): ('next chunk requested', 'tiles', 'LDS writes', 'barrier'),
+                     ('dx1w1', 1): ('(nothing)', 'tiles with the request between them', 'LDS writes', 'barrier')}
+        need = {'dwxh': 272, 'dx1w1': 192}
+        for name, base in (('dwxh', 0), ('dx1w1', 16)):
+            for w in (0, 1):
+                t = st[base + 8 * w: base + 8 * w + 5]
+                seg = [int(t[i + 1] - t[i]) for i in range(4)]
+                if (t <= 0).any() or min(seg) < 0:
+                    print('stamps %-5s wave %d: not taken (library without -DTSC_UPD_STAMPS=1, or splits shorter than %d rows)'
+                          % (name, 4 * w, need[name]))
+                    continue
+                print('stamps %-5s wave %d: %s, step %d cycles'
+                      % (name, 4 * w, ', '.join('%s %d' % (n, c) for n, c in zip(seg_names[name, w], seg)), int(t[4] - t[0])))
     prof = _lib.profile()
     _lib.profile(enable=False)
     tot = 0.0
