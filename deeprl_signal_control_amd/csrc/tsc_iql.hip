@@ -222,6 +222,183 @@ __global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, c
     }
 }
 
+// ---- prioritized replay (tsc_iql_set_per; proportional, Schaul et al. 2016) -----------------------------------------------------
+// Stored priorities prio [E][A][cap] (already (|delta| + eps)^alpha, contiguous per ring: the sampler reads one whole ring at a time)
+// and the rings' running maxima qmax [E][A].
+
+// inclusive prefix sum of one double per lane over the wavefront, on the DPP data path (the simulator's scan, csrc/tsc_env.hip:
+// row_shr within the four 16-lane rows, then row_bcast:15 / :31); a lane without a source lane adds the identity's bits, 0.0
+template <int ctrl, int rows>
+__device__ __forceinline__ double per_dpp_f64(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)b, ctrl, rows, 0xF, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), ctrl, rows, 0xF, false);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ double per_wave_scan_add(double v) {
+    v += per_dpp_f64<0x111, 0xF>(v); v += per_dpp_f64<0x112, 0xF>(v); v += per_dpp_f64<0x114, 0xF>(v); v += per_dpp_f64<0x118, 0xF>(v);
+    v += per_dpp_f64<0x142, 0xA>(v); v += per_dpp_f64<0x143, 0xC>(v);
+    return v;
+}
+__device__ __forceinline__ double per_shfl_f64(double v, int lane) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __shfl((int)(unsigned)(unsigned long long)b, lane, 64), hi = __shfl((int)((unsigned long long)b >> 32), lane, 64);
+    return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+
+constexpr int kPerWaves = 4;       // rings per workgroup of the sampler: one wavefront each
+// LDS image of one ring: lane l owns the contiguous slots [l K, (l + 1) K), K = ceil(size / 64), at row stride K | 1 (odd: the 64 lanes'
+// walks over their own blocks fall on distinct banks)
+__host__ __device__ inline int per_block_len(int size) { return (size + 63) >> 6; }
+__host__ __device__ inline int per_wave_floats(int cap) { return 64 * (per_block_len(cap) | 1); }
+
+// The stratified proportional draw of one minibatch, one wavefront per ring p = e A + a:
+//   C[k] = sum_{s <= k} q[s] over the filled slots (float64), total = C[size - 1];
+//   pick i: t = (i + U(seed, upd, p B + i)) total / B; the smallest k with C[k] > t, clamped to the last slot with q > 0;
+//   w_i = (size q[k] / total)^-beta (float64: product, quotient, pow), divided by the largest of the ring's B weights.
+// The ring comes in with coalesced loads into LDS; every lane sums its block; the 64 block sums go through the wavefront scan; lane i < B
+// finds the lane whose block holds its target (the number of lanes whose inclusive sum is <= t), then walks that block.
+// given != 0: idx is the caller's draw (tsc_iql_compute_grads_at), clamped into the filled part like the gather's; only w is formed
+// (a slot with q = 0, which no draw of ours can produce, takes the ring's largest weight).
+__global__ void __launch_bounds__(64 * kPerWaves) iql_per_sample_kernel(int E, int A, int B, long long cap, int size, double beta,
+                                                                        unsigned long long seed, unsigned long long upd, int given,
+                                                                        const float *__restrict__ prio, int *__restrict__ idx,
+                                                                        float *__restrict__ w) {
+    extern __shared__ __attribute__((aligned(16))) float per_smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long p = (long long)blockIdx.x * kPerWaves + wave;
+    const bool live = p < (long long)E * A;
+    const int K = per_block_len(size), Ks = K | 1;
+    float *sm = per_smem + wave * per_wave_floats((int)cap);
+    const float *ring = prio + (live ? p : 0) * cap;
+    // slot g -> block g / K: g < 4096 and K <= 64 (TSC_IQL_PER_MAX_BUFFER), so with M = ceil(2^20 / K) the error M K - 2^20 < K gives
+    // g (M K - 2^20) < 2^18 < 2^20 and (g M) >> 20 is the exact quotient, in 32 bits -- no integer division per slot
+    const unsigned M = ((1u << 20) + (unsigned)K - 1) / (unsigned)K;
+    if (live)
+        for (int g0 = 0; g0 < size; g0 += 256) {      // four coalesced requests in flight per lane before the first LDS write
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const int g = g0 + 64 * u + lane; v[u] = ring[g < size ? g : size - 1]; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int g = g0 + 64 * u + lane, blk = (int)(((unsigned)g * M) >> 20);
+                if (g < size) sm[blk * Ks + (g - blk * K)] = v[u];
+            }
+        }
+    __syncthreads();
+    const int lo = lane * K, cnt = size - lo < 0 ? 0 : size - lo < K ? size - lo : K;
+    const float *mine = sm + lane * Ks;
+    double bsum = 0.0;
+    if (live)
+        for (int s = 0; s < cnt; ++s) bsum += (double)mine[s];
+    const double incl = per_wave_scan_add(bsum);
+    const double total = per_shfl_f64(incl, 63);
+    const unsigned long long pos = __ballot(bsum > 0.0);
+    const int last_lane = pos ? 63 - __clzll((long long)pos) : 0;       // the last block with mass
+    int k = 0;
+    if (given) {
+        if (live && lane < B) {
+            k = idx[p * B + lane];
+            k = k < 0 ? 0 : k >= size ? size - 1 : k;
+        }
+    } else {
+        const double t = ((double)lane + uniform01(seed, upd, (unsigned long long)p * B + lane)) * total / (double)B;
+        int j = 0;
+        for (int l = 0; l < 64; ++l) j += per_shfl_f64(incl, l) <= t ? 1 : 0;
+        if (j > last_lane) j = last_lane;           // t == total after rounding: the last slot with q > 0
+        const int jlo = j * K, jcnt = size - jlo < K ? size - jlo : K;
+        double c = per_shfl_f64(incl, j > 0 ? j - 1 : 0);           // C of the slot before the block: what the lane search compared with
+        if (j == 0) c = 0.0;
+        const float *blk = sm + j * Ks;
+        int hit = -1, lastpos = 0;
+        for (int s = 0; s < jcnt; ++s) {
+            const float q = blk[s];
+            c += (double)q;
+            if (q > 0.f) lastpos = s;
+            if (hit < 0 && q > 0.f && c > t) hit = s;
+        }
+        k = jlo + (hit < 0 ? lastpos : hit);
+    }
+    const bool on = live && lane < B;
+    const int kb = (int)(((unsigned)k * M) >> 20);
+    const float qk = sm[kb * Ks + (k - kb * K)];
+    double wi = 0.0;
+    if (on && qk > 0.f) wi = pow((double)size * (double)qk / total, -beta);
+    double wmax = wi;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) wmax = fmax(wmax, per_shfl_f64(wmax, lane ^ o));
+    if (on) {
+        const long long e = p / A, a = p % A;
+        if (!given) idx[p * B + lane] = k;
+        w[a * ((long long)E * B) + e * B + lane] = (wi > 0.0 && wmax > 0.0) ? (float)(wi / wmax) : 1.0f;
+    }
+}
+
+// priority write-back: q[k] = (float)pow(|delta| + eps, alpha) of every sampled row, qmax rises to the largest.  One thread per ring walks
+// its B picks in order, so a slot drawn twice has no write race: the later pick's value stays.
+__global__ void iql_per_update_kernel(int E, int A, int B, long long cap, int size, double alpha, double eps, const int *__restrict__ idx,
+                                      const float *__restrict__ td, float *__restrict__ prio, float *__restrict__ qmax) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (long long)E * A) return;
+    const long long e = p / A, a = p % A;
+    const float *d = td + a * ((long long)E * B) + e * B;
+    float m = qmax[p];
+    for (int i = 0; i < B; ++i) {
+        int k = idx[p * B + i];
+        k = k < 0 ? 0 : k >= size ? size - 1 : k;
+        const float v = (float)pow((double)d[i] + eps, alpha);
+        prio[p * cap + k] = v;
+        m = fmaxf(m, v);
+    }
+    qmax[p] = m;
+}
+
+// a new transition enters every ring at its running maximum (also where it overwrites an old one)
+__global__ void iql_per_add_kernel(long long rings, long long cap, long long slot, const float *__restrict__ qmax, float *__restrict__ prio) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < rings) prio[p * cap + slot] = qmax[p];
+}
+
+// arming: q = 1 on the filled slots, 0 behind them; qmax = 1
+__global__ void iql_per_init_kernel(long long rings, long long cap, long long size, float *__restrict__ prio, float *__restrict__ qmax) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rings * cap) prio[i] = i % cap < size ? 1.0f : 0.0f;
+    if (i < rings) qmax[i] = 1.0f;
+}
+
+// iql_td_kernel with the importance weight of the row in and |delta| out: loss = mean(w (q0 - tq)^2), dQ[k] = 2 w (q0 - tq) / R at k = a
+__global__ void iql_td_per_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done,
+                                  const float *__restrict__ w, long long R, int A, float gamma, float *dQ, float *__restrict__ td,
+                                  double *stats) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    float l = 0.f;
+    int a = 0;
+    if (i < (long long)A * R) {
+        a = (int)(i / R);
+        const float r = rew[i];
+        const float tq = done[i] ? r : r + gamma * q1[i];
+        const int k0 = act[i];
+        const float d = Q[i * kQ + k0] - tq, wi = w[i];
+        const float g = 2.0f * d * wi / (float)R;
+        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+        float *v = k0 < 4 ? &lo.x : &hi.x;
+        v[k0 & 3] = g;
+        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = lo;
+        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = hi;
+        td[i] = fabsf(d);
+        l = d * d * wi / (float)R;
+    }
+    const int a0 = __shfl(a, 0, 64);
+    const bool uni = __all(a == a0 || i >= (long long)A * R);
+    if (uni) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
+        if ((threadIdx.x & 63) == 0 && l != 0.f) atomicAdd(&stats[a0 * 2], (double)l);
+    } else if (l != 0.f) {
+        atomicAdd(&stats[a * 2], (double)l);
+    }
+}
+
 __global__ void iql_transpose_kernel(const float *params, QLayout L, float *W2T, float *WqT) {
     // W2T[a][n][k] = W2[a][k][n]  (H2 x H1) ; WqT[a][n][k] = Wq[a][k][n]  (8 x H2)
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -310,6 +487,11 @@ struct tsc_iql {
     float *tparams, *y, *Q2;      // the frozen copy [A][stride]; per-row TD targets [A][R] (fused path); the online net's Q(s') (grouped path, double_q)
     int *astar;                   // [A][R] Double DQN's picks
     bool y_valid;                 // a compute_grads ran on the armed handle
+    // prioritized replay (tsc_iql_set_per): stored priorities [E][A][cap], running maxima [E][A], importance weights and |delta| [A][R]
+    int per;
+    double per_alpha, per_eps, per_beta;
+    float *prio, *qmax, *w, *td;
+    bool per_valid;               // a compute_grads ran on the handle while prioritized replay was armed
 };
 
 namespace {
@@ -410,6 +592,7 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
     // TSC_IQL_FUSED=0 (the A/B switch of tests/test_iql_gpu.py) take the grouped-GEMM path.
     h->fused = 0; h->fS = h->fcps = 0; h->fws = h->fwsl = nullptr; h->dbg = h->dbg_buf = nullptr;
     h->tgt_period = h->tgt_double = 0; h->tparams = h->y = h->Q2 = nullptr; h->astar = nullptr; h->y_valid = false;
+    h->per = 0; h->per_alpha = h->per_eps = 0.0; h->per_beta = 1.0; h->prio = h->qmax = h->w = h->td = nullptr; h->per_valid = false;
     TSC_HIP(h->bufs.upload(&h->n_wave, cfg->n_wave, L.A));
     TSC_HIP(h->bufs.upload(&h->n_wait, cfg->n_wait, L.A));
     {
@@ -439,13 +622,15 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
         if (h->fused == 10) {
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_act_kernel<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8, true, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8, true, false, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8, true, true, const float *, const float *, float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<10, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<10, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds_f));
         } else {
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_act_kernel<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8, true, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8, true, false, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
+            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8, true, true, const float *, const float *, float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<8, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
             TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<8, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds_f));
         }
@@ -556,6 +741,14 @@ int tsc_iql_add_transition(tsc_iql *h, const float *obs, const int32_t *action, 
                        h->cum % h->cap, obs, action, reward, next_obs, done, h->rnorm, h->rclip, h->r_obs, h->r_next, h->r_act,
                        h->r_rew, h->r_done);
     TSC_HIP(hipGetLastError());
+    ps.stop();
+    if (h->per) {       // the new transition enters every ring at the ring's running maximum
+        tsc::ProfScope pp(tsc::KID_IQL_PER_ADD, h->stream);
+        const long long rings = (long long)h->E * L.A;
+        hipLaunchKernelGGL(iql_per_add_kernel, dim3((unsigned)((rings + 255) / 256)), dim3(256), 0, h->stream, rings, h->cap, h->cum % h->cap,
+                           h->qmax, h->prio);
+        TSC_HIP(hipGetLastError());
+    }
     h->cum += 1;
     return 0;
 }
@@ -568,13 +761,26 @@ int tsc_iql_replay_size(tsc_iql *h, int64_t *size, int64_t *cum) {
 
 static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, const int32_t *idx_dev);
 
+// prioritized replay: the priorities of the sampled slots follow the TD errors the gradient kernels left in td (nothing from the all-reduce)
+static int iql_grads_then_priorities(tsc_iql *h, uint64_t seed, uint64_t update_index, const int32_t *idx_dev) {
+    const int rc = iql_compute_grads(h, seed, update_index, idx_dev);
+    if (rc || !h->per) return rc;
+    const long long rings = (long long)h->E * h->lay.A, size = h->cum < h->cap ? h->cum : h->cap;
+    tsc::ProfScope ps(tsc::KID_IQL_PER_UPDATE, h->stream);
+    hipLaunchKernelGGL(iql_per_update_kernel, dim3((unsigned)((rings + 127) / 128)), dim3(128), 0, h->stream, h->E, h->lay.A, h->B, h->cap,
+                       (int)size, h->per_alpha, h->per_eps, h->idx, h->td, h->prio, h->qmax);
+    TSC_HIP(hipGetLastError());
+    h->per_valid = true;
+    return 0;
+}
+
 int tsc_iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index) {
-    return iql_compute_grads(h, seed, update_index, nullptr);
+    return iql_grads_then_priorities(h, seed, update_index, nullptr);
 }
 
 int tsc_iql_compute_grads_at(tsc_iql *h, const int32_t *idx_dev) {
     if (!idx_dev) return tsc::fail("tsc_iql_compute_grads_at: null index buffer");
-    return iql_compute_grads(h, 0, 0, idx_dev);
+    return iql_grads_then_priorities(h, 0, 0, idx_dev);
 }
 
 static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, const int32_t *idx_dev) {
@@ -587,7 +793,14 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
     TSC_HIP(hipMemsetAsync(h->stats, 0, sizeof(double) * A * 2, st));
     if (idx_dev) {      // the caller's draw (e.g. the reference's random.sample); the gather clamps every index into [0, size)
         TSC_HIP(hipMemcpyAsync(h->idx, idx_dev, sizeof(int) * E * A * h->B, hipMemcpyDeviceToDevice, st));
-    } else {
+    }
+    if (h->per) {       // the proportional draw and its importance weights; on the caller's draw only the weights
+        tsc::ProfScope ps(tsc::KID_IQL_PER_SAMPLE, st);
+        hipLaunchKernelGGL(iql_per_sample_kernel, dim3((unsigned)((E * A + kPerWaves - 1) / kPerWaves)), dim3(64 * kPerWaves),
+                           sizeof(float) * kPerWaves * per_wave_floats((int)h->cap), st, (int)E, (int)A, h->B, h->cap, (int)size, h->per_beta,
+                           (unsigned long long)seed, (unsigned long long)update_index, idx_dev ? 1 : 0, h->prio, h->idx, h->w);
+        TSC_HIP(hipGetLastError());
+    } else if (!idx_dev) {
         tsc::ProfScope ps(tsc::KID_IQL_SAMPLE, st);
         if (h->B == 20)
             hipLaunchKernelGGL(iql_sample_fixed_kernel<20>, dim3((unsigned)((E * A + 127) / 128)), dim3(128), 0, st, (int)E, (int)A, size,
@@ -601,25 +814,32 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
     if (h->fused) {
         QFusedArgs fa = fused_args(h, size);
         const unsigned grid = (unsigned)(A * h->fS);
-        if (armed) {        // two launches: the TD targets from the frozen copy (forward only), then the gradient with one row set
+        if (armed || h->per) {  // two launches: the TD targets from the frozen copy (forward only), then the gradient with one row set
+            // (prioritized replay always takes this route; without a target network the "frozen copy" is the parameters themselves)
+            const float *tp = armed ? h->tparams : h->params;
+            const bool dbl = armed && h->tgt_double;
             {
                 tsc::ProfScope ps(tsc::KID_IQL_TARGET, st);
                 const int lds_f = (h->fused == 10 ? QFusedLds<10>::fwd_floats : QFusedLds<8>::fwd_floats) * 4;
-                if (h->fused == 10 && h->tgt_double)
-                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, h->tparams, h->y, h->astar);
+                if (h->fused == 10 && dbl)
+                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, tp, h->y, h->astar);
                 else if (h->fused == 10)
-                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, h->tparams, h->y, h->astar);
-                else if (h->tgt_double)
-                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, h->tparams, h->y, h->astar);
+                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, tp, h->y, h->astar);
+                else if (dbl)
+                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, tp, h->y, h->astar);
                 else
-                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, h->tparams, h->y, h->astar);
+                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, tp, h->y, h->astar);
             }
             TSC_HIP(hipGetLastError());
             tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
-            if (h->fused == 10)
-                hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8, true, const float *>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa, (const float *)h->y);
+            if (h->fused == 10 && h->per)
+                hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8, true, true, const float *, const float *, float *>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa, (const float *)h->y, (const float *)h->w, h->td);
+            else if (h->per)
+                hipLaunchKernelGGL((iql_fused_grad_kernel<8, 8, true, true, const float *, const float *, float *>), dim3(grid), dim3(256), QFusedLds<8>::grad_floats * 4, st, fa, (const float *)h->y, (const float *)h->w, h->td);
+            else if (h->fused == 10)
+                hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8, true, false, const float *>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa, (const float *)h->y);
             else
-                hipLaunchKernelGGL((iql_fused_grad_kernel<8, 8, true, const float *>), dim3(grid), dim3(256), QFusedLds<8>::grad_floats * 4, st, fa, (const float *)h->y);
+                hipLaunchKernelGGL((iql_fused_grad_kernel<8, 8, true, false, const float *>), dim3(grid), dim3(256), QFusedLds<8>::grad_floats * 4, st, fa, (const float *)h->y);
         } else {
             tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
             if (h->fused == 10)
@@ -648,8 +868,12 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
         hipLaunchKernelGGL(iql_qmax_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->n_act, R, (int)A, h->q1);
     }
     if (q_forward(h, h->params, h->S, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
-    hipLaunchKernelGGL(iql_td_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, R,
-                       (int)A, (float)h->gamma, h->dQ, h->stats);
+    if (h->per)
+        hipLaunchKernelGGL(iql_td_per_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
+                           h->w, R, (int)A, (float)h->gamma, h->dQ, h->td, h->stats);
+    else
+        hipLaunchKernelGGL(iql_td_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, R,
+                           (int)A, (float)h->gamma, h->dQ, h->stats);
     TSC_HIP(hipGetLastError());
     float *g = h->grads;
     if (!L.dqn) {
@@ -794,6 +1018,83 @@ int tsc_iql_debug_targets(tsc_iql *h, float *y_host, int32_t *astar_host) {
         if (h->tgt_double) TSC_HIP(hipMemcpy(astar_host, h->astar, sizeof(int32_t) * AR, hipMemcpyDeviceToHost));
         else for (size_t i = 0; i < AR; ++i) astar_host[i] = -1;
     }
+    return 0;
+}
+
+int tsc_iql_set_per(tsc_iql *h, int32_t enable, double alpha, double eps) {
+    if (!h) return tsc::fail("null handle");
+    if (!enable) { h->per = 0; h->per_valid = false; return 0; }       // back to Floyd sampling and the kernels of an unarmed handle
+    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return tsc::fail("tsc_iql_set_per: alpha %g must be >= 0", alpha);
+    if (!(eps > 0.0) || !std::isfinite(eps)) return tsc::fail("tsc_iql_set_per: eps %g must be > 0", eps);
+    if (h->cap > TSC_IQL_PER_MAX_BUFFER)
+        return tsc::fail("tsc_iql_set_per: buffer_size %lld > TSC_IQL_PER_MAX_BUFFER (%d): the sampler stages a whole ring in LDS", h->cap,
+                         TSC_IQL_PER_MAX_BUFFER);
+    const QLayout &L = h->lay;
+    const long long rings = (long long)h->E * L.A, AR = rings * h->B, size = h->cum < h->cap ? h->cum : h->cap;
+    TSC_HIP(hipSetDevice(h->device));
+    const bool first = !h->prio || !h->qmax;
+    if (!h->prio) TSC_HIP(h->bufs.alloc(&h->prio, rings * h->cap, false));
+    if (!h->qmax) TSC_HIP(h->bufs.alloc(&h->qmax, rings, false));
+    if (!h->w) TSC_HIP(h->bufs.alloc(&h->w, AR, true));
+    if (!h->td) TSC_HIP(h->bufs.alloc(&h->td, AR, true));
+    if (h->fused && !h->y) TSC_HIP(h->bufs.alloc(&h->y, AR, true));
+    TSC_HIP(hipFuncSetAttribute((const void *)iql_per_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)sizeof(float) * kPerWaves * per_wave_floats((int)h->cap)));
+    // priorities are powers of alpha, so another alpha starts over; so does arming again after a disarm (slots filled meanwhile have none)
+    if (first || !h->per || alpha != h->per_alpha) {
+        const long long n = rings * h->cap;
+        hipLaunchKernelGGL(iql_per_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, rings, h->cap, size, h->prio, h->qmax);
+        TSC_HIP(hipGetLastError());
+        h->per_valid = false;
+    }
+    h->per = 1; h->per_alpha = alpha; h->per_eps = eps;
+    return 0;
+}
+
+int tsc_iql_set_per_beta(tsc_iql *h, double beta) {
+    if (!h) return tsc::fail("null handle");
+    if (!(beta >= 0.0 && beta <= 1.0)) return tsc::fail("tsc_iql_set_per_beta: beta %g outside [0, 1]", beta);
+    h->per_beta = beta;
+    return 0;
+}
+
+int tsc_iql_get_priorities(tsc_iql *h, float *prio_host, float *qmax_host) {
+    if (!h || !prio_host || !qmax_host) return tsc::fail("tsc_iql_get_priorities: bad arguments");
+    if (!h->per) return tsc::fail("tsc_iql_get_priorities: prioritized replay is not armed (tsc_iql_set_per)");
+    const size_t rings = (size_t)h->E * h->lay.A;
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    TSC_HIP(hipMemcpy(prio_host, h->prio, sizeof(float) * rings * h->cap, hipMemcpyDeviceToHost));
+    TSC_HIP(hipMemcpy(qmax_host, h->qmax, sizeof(float) * rings, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tsc_iql_set_priorities(tsc_iql *h, const float *prio_host, const float *qmax_host) {
+    if (!h || !prio_host || !qmax_host) return tsc::fail("tsc_iql_set_priorities: bad arguments");
+    if (!h->per) return tsc::fail("tsc_iql_set_priorities: prioritized replay is not armed (tsc_iql_set_per)");
+    const size_t rings = (size_t)h->E * h->lay.A, cap = (size_t)h->cap, size = (size_t)(h->cum < h->cap ? h->cum : h->cap);
+    for (size_t p = 0; p < rings; ++p) {
+        bool mass = size == 0;
+        for (size_t s = 0; s < cap; ++s) {
+            const float q = prio_host[p * cap + s];
+            if (!(q >= 0.f) || !std::isfinite(q)) return tsc::fail("tsc_iql_set_priorities: ring %zu slot %zu: priority %g is not a finite value >= 0", p, s, (double)q);
+            mass |= s < size && q > 0.f;
+        }
+        if (!(qmax_host[p] >= 0.f) || !std::isfinite(qmax_host[p])) return tsc::fail("tsc_iql_set_priorities: ring %zu: qmax %g is not a finite value >= 0", p, (double)qmax_host[p]);
+        if (!mass) return tsc::fail("tsc_iql_set_priorities: ring %zu has no positive priority among its %zu filled slots", p, size);
+    }
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    TSC_HIP(hipMemcpy(h->prio, prio_host, sizeof(float) * rings * cap, hipMemcpyHostToDevice));
+    TSC_HIP(hipMemcpy(h->qmax, qmax_host, sizeof(float) * rings, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int tsc_iql_debug_per(tsc_iql *h, float *w_host, float *td_host) {
+    if (!h || !w_host || !td_host) return tsc::fail("tsc_iql_debug_per: bad arguments");
+    if (!h->per || !h->per_valid) return tsc::fail("tsc_iql_debug_per: no tsc_iql_compute_grads with prioritized replay armed yet (tsc_iql_set_per)");
+    const size_t AR = (size_t)h->lay.A * h->E * h->B;
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    TSC_HIP(hipMemcpy(w_host, h->w, sizeof(float) * AR, hipMemcpyDeviceToHost));
+    TSC_HIP(hipMemcpy(td_host, h->td, sizeof(float) * AR, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -116,7 +116,7 @@ struct QW1 {
     float t[NT][2][4];
 };
 
-// TAG: the armed handle's kernels (target network) take an instantiation of their own, 1: how the compiler inlines the lambdas below
+// TAG: the armed handles' kernels take instantiations of their own (1: target network, 2: prioritized replay): how the compiler inlines the lambdas below
 // depends on how many callers an instantiation has, and the default kernels must compile to what they compiled to without them
 template <int NB, int NM1, int NMW, int TAG = 0>
 __device__ __forceinline__ void q_nets(const QW1<NM1, NMW> &w1, const float4 (&s)[NB][3], const float *sm, const QRanges &rg, int m, int kq,
@@ -287,12 +287,19 @@ __device__ __forceinline__ float4 q_obs4(const float *row, int f0, int SMAX, boo
 // TGT: the armed handle's variant, launched as iql_fused_grad_kernel<.., true, const float *>(p, y) -- the TD target of every row was
 // left by iql_fused_target_kernel in y [A][R], so only s goes through the nets (one row set) and neither s', the reward nor the done
 // flag is read; everything from the TD error on is the same code.  The default instantiations take no second argument (Y is empty).
+// PER (prioritized replay, tsc_iql_set_per; always with TGT): launched as <.., true, true, const float *, const float *, float *>(p, y, w, td)
+// -- the row's importance weight w [A][R] scales its gradient and its loss term, and the kq == 0 lanes store |delta| of the valid rows in
+// td [A][R] for the priority write-back.
 __device__ __forceinline__ const float *q_targets_of() { return nullptr; }
 __device__ __forceinline__ const float *q_targets_of(const float *y) { return y; }
+__device__ __forceinline__ const float *q_targets_of(const float *y, const float *, float *) { return y; }
+__device__ __forceinline__ const float *q_weights_of(const float *, const float *w, float *) { return w; }
+__device__ __forceinline__ float *q_tderr_of(const float *, const float *, float *td) { return td; }
 
-template <int NM1, int NMW, bool TGT = false, class... Y>
+template <int NM1, int NMW, bool TGT = false, bool PER = false, class... Y>
 __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y... y_arg) {
-    static_assert(sizeof...(Y) == (TGT ? 1 : 0), "the armed variant takes the per-row targets, the default one nothing");
+    static_assert(sizeof...(Y) == (PER ? 3 : TGT ? 1 : 0), "the armed variants take the per-row targets (and weights, |delta|), the default one nothing");
+    static_assert(TGT || !PER, "prioritized replay takes the two-launch route");
     using LD = QFusedLds<NM1>;
     constexpr int H1 = LD::H1;
     extern __shared__ __attribute__((aligned(16))) float q_smem[];
@@ -376,8 +383,16 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
 #endif
     Rows cur, nxt;
     Slot slot_n = {0, 0};
+    // PER: the importance weight of this lane's row in the current / next chunk (requested with the rows)
+    [[maybe_unused]] float wcur = 1.f, wnxt = 1.f;
+    [[maybe_unused]] auto weight_of = [&](long long c) {
+        const unsigned row = ((unsigned)c << 6) + 16 * wave + n;
+        if constexpr (PER) return q_weights_of(y_arg...)[(long long)a * p.R + (row < uR ? row : uR - 1)];
+        else return 1.f;
+    };
     if (c0 < c1) {
         load_rows(c0, slot_of(c0), cur);
+        if constexpr (PER) wcur = weight_of(c0);
         slot_n = slot_of(c0 + 1 < c1 ? c0 + 1 : c0);
     }
     __syncthreads();                                      // weights are in LDS
@@ -385,6 +400,7 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
     for (long long c = c0; c < c1; ++c) {
         // next chunk's rows (their slot arrived a chunk ago) and the slot of the chunk after it
         load_rows(c + 1 < c1 ? c + 1 : c, slot_n, nxt);
+        if constexpr (PER) wnxt = weight_of(c + 1 < c1 ? c + 1 : c);
         slot_n = slot_of(c + 2 < c1 ? c + 2 : c);
         // ================= phase A: 16 rows per wavefront =================
         QSTAMP(0);
@@ -398,7 +414,7 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
                 if constexpr (!TGT) ss[0][qp] = cur.s1[qp];
                 ss[NB - 1][qp] = cur.s0[qp];
             }
-            q_nets<NB, NM1, NMW, TGT ? 1 : 0>(w1, ss, sm, rg, n, kq, XX1, XX2, qq, (stamp_wg && c == c0 + 2) ? p.dbg + 16 * wave : nullptr);
+            q_nets<NB, NM1, NMW, PER ? 2 : TGT ? 1 : 0>(w1, ss, sm, rg, n, kq, XX1, XX2, qq, (stamp_wg && c == c0 + 2) ? p.dbg + 16 * wave : nullptr);
         }
         QSTAMP(1);
         f32x4 (&X1)[NM1] = XX1[NB - 1];
@@ -422,8 +438,16 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
         if constexpr (TGT) tq = cur.rew;                 // y of the row
         else tq = cur.done ? cur.rew : cur.rew + p.gamma * q1;
         const float d = cur.ok ? q0 - tq : 0.f;
-        const float g = 2.0f * d / fR;
-        if (kq == 0) loss += d * d / fR;
+        float g, lrow;
+        if constexpr (PER) {                             // (w = 1 leaves both products as they were)
+            g = 2.0f * d * wcur / fR;
+            lrow = d * d * wcur / fR;
+            if (kq == 0 && cur.ok) q_tderr_of(y_arg...)[(long long)a * p.R + (((unsigned)c << 6) + 16 * wave + n)] = fabsf(d);
+        } else {
+            g = 2.0f * d / fR;
+            lrow = d * d / fR;
+        }
+        if (kq == 0) loss += lrow;
         // transposed images for the weight gradients: [feature][row]
         const int rcol = 16 * wave + n;
         {
@@ -599,6 +623,7 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
         __syncthreads();
         QSTAMP(10);
         cur = nxt;
+        if constexpr (PER) wcur = wnxt;
     }
 
     // ---- this split's partial gradient, parameter layout; the reduce kernel never reads what is not written here

@@ -23,7 +23,8 @@ from .agents import CKPT_FORMAT, resume_sample_seed, Scheduler, allreduce_grads_
 IQL_DEFAULTS = dict(max_grad_norm=40.0, gamma=0.99, lr_init=1e-4, lr_decay='constant', lr_min=0.0, epsilon_init=1.0,
                     epsilon_min=0.01, epsilon_decay='linear', epsilon_ratio=0.5, num_fc=128, num_h=64, batch_size=20,
                     buffer_size=1000.0, reward_norm=3000.0, reward_clip=2.0,     # config/config_iqld_large.ini
-                    target_update=0, double_q=0)    # opt-in, not the reference's: target network refreshed every N Adam steps / Double DQN
+                    target_update=0, double_q=0,    # opt-in, not the reference's: target network refreshed every N Adam steps / Double DQN
+                    prioritized_replay=0, per_alpha=0.6, per_beta=0.4, per_eps=0.01)   # opt-in: proportional prioritized replay (Schaul et al. 2016)
 N_UPDATE = 10                                                                    # agents/models.py:324
 
 
@@ -36,6 +37,30 @@ def target_config(cfg):
     if dbl and not period:
         raise ValueError('double_q = 1 needs target_update > 0: without a target network it is the reference\'s loss under another name')
     return period, dbl
+
+
+def per_config(cfg):
+    """(prioritized_replay, per_alpha, per_beta, per_eps) of a coerced [MODEL_CONFIG]: 0 is the reference's uniform draw.  alpha >= 0 is the
+    exponent of the stored priority (|delta| + eps)^alpha, eps > 0 keeps every sampled slot drawable, per_beta in [0, 1] is where the
+    importance-weight exponent starts (it reaches 1 at total_step, per_beta_at)."""
+    on, alpha, beta, eps = int(cfg['prioritized_replay']), float(cfg['per_alpha']), float(cfg['per_beta']), float(cfg['per_eps'])
+    if on not in (0, 1):
+        raise ValueError('prioritized_replay must be 0 or 1 (got %r)' % (cfg['prioritized_replay'],))
+    if not (alpha >= 0 and np.isfinite(alpha)):
+        raise ValueError('per_alpha must be >= 0 (got %r)' % (cfg['per_alpha'],))
+    if not 0 <= beta <= 1:
+        raise ValueError('per_beta must lie in [0, 1] (got %r)' % (cfg['per_beta'],))
+    if not (eps > 0 and np.isfinite(eps)):
+        raise ValueError('per_eps must be > 0 (got %r)' % (cfg['per_eps'],))
+    return on, alpha, beta, eps
+
+
+def per_beta_at(beta0, n, total_step):
+    """The importance-weight exponent after n environment steps (counted like the learning-rate scheduler's n): linear from beta0 to 1
+    over total_step, 1 from there on; without a horizon (total_step <= 0) it stays beta0."""
+    if total_step <= 0:
+        return float(beta0)
+    return float(min(1.0, beta0 + (1.0 - beta0) * (n / float(total_step))))
 
 
 class TscIqlCfg(C.Structure):
@@ -73,6 +98,11 @@ def _setup_lib(L):
     L.tsc_iql_set_target_params.argtypes = [vp, vp]
     L.tsc_iql_get_target_params.argtypes = [vp, vp]
     L.tsc_iql_debug_targets.argtypes = [vp, vp, vp]
+    L.tsc_iql_set_per.argtypes = [vp, C.c_int32, C.c_double, C.c_double]
+    L.tsc_iql_set_per_beta.argtypes = [vp, C.c_double]
+    L.tsc_iql_get_priorities.argtypes = [vp, vp, vp]
+    L.tsc_iql_set_priorities.argtypes = [vp, vp, vp]
+    L.tsc_iql_debug_per.argtypes = [vp, vp, vp]
     L._iql_ready = True
 
 
@@ -172,6 +202,8 @@ class VecIQL:
         cfg = coerce_config(model_config, IQL_DEFAULTS)
         self.cfg, self.name, self.model_type = cfg, 'iql', model_type
         self.target_update, self.double_q = target_config(cfg)
+        self.prioritized_replay, self.per_alpha, self.per_beta, self.per_eps = per_config(cfg)
+        self.per_n = 0              # environment steps the beta schedule has counted (backward calls x batch_size, like lr_scheduler.n)
         self.n_agent, self.E = len(n_s_ls), int(n_env)
         self.n_s_ls, self.n_a_ls, self.n_w_ls = list(n_s_ls), list(n_a_ls), list(n_w_ls)
         self.n_wave_ls = [s - w for s, w in zip(self.n_s_ls, self.n_w_ls)]
@@ -219,6 +251,9 @@ class VecIQL:
         self.update_step = 0        # minibatch steps so far: the replay-sampling counter
         if self.target_update:
             _lib.check(L.tsc_iql_set_target(h, self.target_update, self.double_q))
+        if self.prioritized_replay:
+            _lib.check(L.tsc_iql_set_per(h, 1, self.per_alpha, self.per_eps))
+            _lib.check(L.tsc_iql_set_per_beta(h, self.per_beta))
         self.init_params(seed)
         if self.world > 1:
             t = torch.from_numpy(self.get_flat()).to(self.device)
@@ -263,6 +298,22 @@ class VecIQL:
         flat = np.ascontiguousarray(flat, np.float32)
         assert flat.size == self.n_param
         _lib.check(self._L.tsc_iql_set_target_params(self._h, flat.ctypes.data_as(C.c_void_p)))
+
+    # ---- prioritized replay (prioritized_replay = 1; include/tsc.h tsc_iql_set_per) ---------------------------------
+    def get_priorities(self):
+        """-> (prio f32 [E, A, buffer_size], qmax f32 [E, A]): the stored priorities (|delta| + eps)^alpha and every ring's running maximum."""
+        prio = np.zeros((self.E, self.n_agent, int(float(self.cfg['buffer_size']))), np.float32)
+        qmax = np.zeros((self.E, self.n_agent), np.float32)
+        _lib.check(self._L.tsc_iql_get_priorities(self._h, prio.ctypes.data_as(C.c_void_p), qmax.ctypes.data_as(C.c_void_p)))
+        return prio, qmax
+
+    def set_priorities(self, prio, qmax):
+        prio, qmax = np.ascontiguousarray(prio, np.float32), np.ascontiguousarray(qmax, np.float32)
+        assert prio.shape == (self.E, self.n_agent, int(float(self.cfg['buffer_size']))) and qmax.shape == (self.E, self.n_agent)
+        _lib.check(self._L.tsc_iql_set_priorities(self._h, prio.ctypes.data_as(C.c_void_p), qmax.ctypes.data_as(C.c_void_p)))
+
+    def current_per_beta(self):
+        return per_beta_at(self.per_beta, self.per_n, self.total_step)
 
     def set_flat(self, flat):
         flat = np.ascontiguousarray(flat, np.float32)
@@ -363,6 +414,9 @@ class VecIQL:
     def backward(self, summary_writer=None, global_step=None, want_stats=False):
         """agents/models.py:319-330: nothing until the rings hold one batch, then 10 minibatch steps."""
         cur_lr = self.lr_scheduler.get(self.n_step)
+        if self.prioritized_replay:                 # beta moves from per_beta to 1 over total_step, counted like the learning rate
+            self.per_n += self.n_step
+            _lib.check(self._L.tsc_iql_set_per_beta(self._h, self.current_per_beta()))
         if self.replay_size()[0] < self.n_step:
             return None
         stats = None
@@ -375,6 +429,8 @@ class VecIQL:
         os.makedirs(model_dir, exist_ok=True)
         m, v, t = self.get_opt_state()
         extra = {'target': self.get_target_flat()} if self.target_update else {}      # an unarmed model's file keeps its keys
+        if self.prioritized_replay:     # the beta counter only: the rings are not checkpointed, so neither are their priorities
+            extra['per_n'] = np.int64(self.per_n)
         np.savez(os.path.join(model_dir, 'checkpoint-%d.npz' % int(global_step)), params=self.get_flat(), adam_m=m, adam_v=v,
                  layout=np.array(self.layout.as_tuple() + (self.s_max,), np.int64),
                  counters=np.array([t, self.act_step, self.update_step, self.base_seed, self.lr_scheduler.n, self.eps_scheduler.n], np.int64),
@@ -411,6 +467,9 @@ class VecIQL:
         self.base_seed = self.base_seed if base is None else base
         self.replay_seed = self.sample_seed ^ 0x5DEECE66D
         self.lr_scheduler.n, self.eps_scheduler.n = c[4], c[5]
+        if self.prioritized_replay:             # a file written without prioritized replay: the learning rate's counter (they advance together)
+            self.per_n = int(z['per_n']) if 'per_n' in z.files else int(c[4])
+            _lib.check(self._L.tsc_iql_set_per_beta(self._h, self.current_per_beta()))
         return True
 
     def close(self):
@@ -472,6 +531,12 @@ class IQL:
 
     def set_target_flat(self, flat):
         self.vec.set_target_flat(flat)
+
+    def get_priorities(self):
+        return self.vec.get_priorities()
+
+    def set_priorities(self, prio, qmax):
+        self.vec.set_priorities(prio, qmax)
 
     def save(self, model_dir, global_step):
         self.vec.save(model_dir, global_step)

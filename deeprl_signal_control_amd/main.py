@@ -224,6 +224,8 @@ def train(args):
     log_step = int(config.getfloat('TRAIN_CONFIG', 'log_interval'))
     counter = Counter(total_step, test_step, log_step)
     model = init_model(env, config, total_step, args.envs, seed, args.device)
+    if getattr(model, 'prioritized_replay', 0):
+        logging.info('Training: prioritized replay, alpha %g, beta %g -> 1, eps %g' % (model.per_alpha, model.per_beta, model.per_eps))
     trainer = VecTrainer(env, model, counter, log_rewards=True)
     data = trainer.run_training(run_test=in_test, output_path=dirs['data'])
     if post_test:                                               # Tester.run_offline (utils.py:324-338)

@@ -529,6 +529,35 @@ int tsc_iql_get_target_params(tsc_iql *h, float *params_host);
  * host from the device's q1, reward and done rows with the kernel's float32 expression -- what is checked there is q1 and a*.
  * Synchronises. */
 int tsc_iql_debug_targets(tsc_iql *h, float *y_host, int32_t *astar_host);
+/* Prioritized experience replay (opt-in; proportional, Schaul et al. 2016; the reference samples uniformly).  Every ring (e, a) keeps a
+ * stored priority q[s] >= 0 per slot -- already (|delta| + eps)^alpha, float32, laid out prio[E][A][cap] -- and a running maximum
+ * qmax[e][a] that starts at 1.  On an armed handle
+ *   tsc_iql_add_transition   sets q[slot] = qmax[e][a] in every ring (iql_per_add_kernel behind iql_add_kernel);
+ *   tsc_iql_compute_grads    draws stratified, proportional, with replacement (iql_per_sample_kernel): C[k] = sum_{s <= k} q[s] over the
+ *       filled slots in float64, total = C[size - 1]; pick i of ring p = e A + a has the target t_i = (i + U(seed, update_index,
+ *       p batch_size + i)) total / batch_size (U: the counter-based uniform of the Floyd draw) and is the smallest k with C[k] > t_i,
+ *       clamped to the last slot with q > 0; a slot with q = 0 or >= size is never picked;
+ *   the importance weight of a row is w_i = (size q[k_i] / total)^-beta in float64 (product, quotient, pow), divided by the largest of the
+ *       ring's own batch_size weights and stored as float32 in w[A][E * batch_size]; loss = (1 / R) sum w delta^2, dLoss/dQ[a] = 2 w delta / R
+ *       with delta = Q(s)[a] - y exactly as without it, under any tsc_iql_set_target setting;
+ *   at the end of tsc_iql_compute_grads / _at (nothing from the all-reduce is needed) q[k] = (float)pow((double)|delta| + eps, alpha) for
+ *       every sampled row and qmax rises to the largest such value; a ring's picks are written in order, so the last pick of a slot drawn
+ *       twice stays;
+ *   tsc_iql_compute_grads_at takes the caller's indices as given (clamped as before), forms the weights from the priorities of those slots by the
+ *       same formula (a slot with q = 0 takes the ring's largest weight) and writes back as above.
+ * On the fused path an armed step always takes the two-launch route of tsc_iql_set_target (without a target network the targets come from
+ * the parameters themselves).  The sampler stages one whole ring in LDS: arming refuses buffer_size > TSC_IQL_PER_MAX_BUFFER.
+ * alpha >= 0, eps > 0.  The first arming allocates prio / qmax / w / td, with q = 1 on filled slots and qmax = 1; arming with another alpha,
+ * or again after a disarm, resets them.  enable = 0 disarms: back to the Floyd draw and the kernels of a handle that was never armed. */
+#define TSC_IQL_PER_MAX_BUFFER 4096
+int tsc_iql_set_per(tsc_iql *h, int32_t enable, double alpha, double eps);
+int tsc_iql_set_per_beta(tsc_iql *h, double beta);              /* beta in [0, 1]; default 1 */
+/* prio [E][A][cap], qmax [E][A] of an armed handle.  set: tests; every value finite and >= 0, every ring with at least one positive value among
+ * its filled slots.  Both synchronise. */
+int tsc_iql_get_priorities(tsc_iql *h, float *prio_host, float *qmax_host);
+int tsc_iql_set_priorities(tsc_iql *h, const float *prio_host, const float *qmax_host);
+/* Debug / parity access: w and |delta| [A][E * batch_size] of the last tsc_iql_compute_grads / _at on an armed handle.  Synchronises. */
+int tsc_iql_debug_per(tsc_iql *h, float *w_host, float *td_host);
 /* Measurement hook of the fused learner (tools/bench_iql.py --stamps): enable != 0 allocates the stamp buffer; the next
  * tsc_iql_compute_grads then records, for every workgroup, its start / end on the 100-MHz wall clock ([64 + 2 b],
  * [64 + 2 b + 1]) and -- in a measurement build with -DTSC_IQL_STAMPS (tools/build_variant.sh; the stamps' branches are kept

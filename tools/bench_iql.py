@@ -2,10 +2,12 @@
 """Times the IQL-DNN learner's launches in isolation (large_grid, E = 1024 by default): the minibatch gradient
 (tsc_iql_compute_grads: sample + fused gradient + reduce) and the acting forward, with HIP events on the launch stream.
 
-    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--target-update N [--double-q]]
+    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--target-update N [--double-q]] [--per]
 
 --target-update N arms the target network (two launches per gradient: the TD targets from the frozen copy, then the gradient with one
-row set).  --split adds the per-kernel split of the minibatch step ("kernel_us": iql_target / iql_grad / ..., each measured in a
+row set).  --per arms prioritized replay (the proportional sampler in place of the Floyd draw, the
+two-launch gradient with importance weights, the priority write-back and, on add_transition, the fill at the ring's maximum; the rings are
+filled to their capacity then, the sampler's full read).  --split adds the per-kernel split of the minibatch step ("kernel_us": iql_target / iql_grad / ..., each measured in a
 pass of its own with only its launches bracketed: 5 x reps more minibatch steps).  --stamps reads the gradient kernel's workgroups
 and, on an armed handle, the target kernel's as well ("target_wg_us").
 """
@@ -27,6 +29,7 @@ def main():
     ap.add_argument('--scenario', default='large_grid')
     ap.add_argument('--target-update', type=int, default=0, help='[MODEL_CONFIG] target_update: refresh the target network every N Adam steps (0: none)')
     ap.add_argument('--double-q', action='store_true', help='[MODEL_CONFIG] double_q = 1 (needs --target-update)')
+    ap.add_argument('--per', action='store_true', help='[MODEL_CONFIG] prioritized_replay = 1')
     ap.add_argument('--split', action='store_true', help='per-kernel split of the minibatch step (one more pass of --reps steps per kernel)')
     ap.add_argument('--stamps', action='store_true', help='phase stamps of workgroup 0 and the start / end of every workgroup (tsc_iql_debug_clock)')
     args = ap.parse_args()
@@ -36,14 +39,15 @@ def main():
     scn = build_scenario(args.scenario, 'iqld')
     E, A = args.envs, scn.n_agent
     m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, int(scn.green_tab.shape[1]),
-               dict(batch_size=20, buffer_size=1000, reward_norm=3000.0, target_update=args.target_update, double_q=int(args.double_q)),
+               dict(batch_size=20, buffer_size=1000, reward_norm=3000.0, target_update=args.target_update, double_q=int(args.double_q),
+                    prioritized_replay=int(args.per)),
                total_step=10 ** 6, seed=0, model_type='dqn')
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     mask = torch.zeros(A, scn.s_max, device='cuda')
     for a, n in enumerate(scn.n_s_ls):
         mask[a, :n] = 1
     obs = torch.rand(E, A, scn.s_max, generator=g, device='cuda') * 2 * mask
-    for t in range(40):
+    for t in range(1000 if args.per else 40):
         nobs = torch.rand(E, A, scn.s_max, generator=g, device='cuda') * 2 * mask
         act = (torch.rand(E, A, generator=g, device='cuda') * torch.as_tensor(scn.n_a_ls, device='cuda')).to(torch.int32)
         rew = -torch.rand(E, A, generator=g, device='cuda', dtype=torch.float64) * 6000.0
@@ -68,17 +72,23 @@ def main():
     def grads():
         _lib.check(m._L.tsc_iql_compute_grads(m._h, 7, step[0]))
         step[0] += 1
-    out = {'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'compute_grads_us': timed(grads, args.reps),
+    out = {'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'prioritized_replay': m.prioritized_replay,
+           'replay_size': m.replay_size()[0], 'compute_grads_us': timed(grads, args.reps),
            'forward_us': timed(lambda: m.forward(obs, mode='explore'), args.reps),
            'minibatch_step_us': timed(lambda: m.minibatch_step(1e-4), args.reps)}
     # where a minibatch step's time goes: one kernel id at a time (an event pair inflates the launch behind it, include/tsc.h)
     kern = {}
-    for name in (['iql_target'] * bool(m.target_update and m.fused) + ['iql_grad', 'iql_reduce', 'iql_sample', 'iql_adam']) * args.split:
+    two_launch = bool((m.target_update or m.prioritized_replay) and m.fused)
+    sample = ['iql_per_sample', 'iql_per_update', 'iql_per_add'] if m.prioritized_replay else ['iql_sample']
+    for name in (['iql_target'] * two_launch + ['iql_grad', 'iql_reduce'] + sample + ['iql_adam']) * args.split:
         _lib.profile_select([name])
         _lib.profile(enable=True)
         _lib.profile(reset=True)
         for _ in range(args.reps):
-            m.minibatch_step(1e-4)
+            if name == 'iql_per_add':
+                m.add_transition(obs, act, rew, nobs, done)
+            else:
+                m.minibatch_step(1e-4)
         ms, cnt = _lib.profile().get(name, (0.0, 0))
         _lib.profile(enable=False)
         if cnt:
@@ -87,6 +97,9 @@ def main():
     _lib.profile(reset=True)
     if args.split:
         out['kernel_us'] = kern
+        if 'iql_per_sample' in kern:       # the sampler's roofline: every ring's filled slots read once, over the measured time
+            out['per_sample_bytes'] = 4 * E * A * m.replay_size()[0]
+            out['per_sample_GBps'] = out['per_sample_bytes'] / kern['iql_per_sample'] * 1e-3
     if args.stamps and m.fused:
         import ctypes as C
         n = 64 + 2 * 4096
