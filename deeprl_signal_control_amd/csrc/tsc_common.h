@@ -146,3 +146,16 @@ template <class T> __device__ __forceinline__ void stg(T *base, unsigned byte_of
     *(T *)((char *)base + byte_off) = v;
 }
 
+// the counter-based uniform tsc_model_sample documents, U(seed, step, idx) in [0, 1): the one definition behind every device draw
+// (action sampling of both learners, Floyd and prioritized replay sampling)
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__device__ __forceinline__ double uniform01(unsigned long long seed, unsigned long long step, unsigned long long idx) {
+    const unsigned long long h = splitmix64(splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull)) + idx);
+    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
+}
+

@@ -22,6 +22,7 @@
 #include "tsc_gemm.h"
 #include "../../include/tsc.h"
 
+#include <cassert>
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -36,20 +37,12 @@ struct QLayout {
     long long stride, oW1, ob1, oW2, ob2, oWq, obq;
 };
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-// the uniform tsc_model_sample documents: U(seed, step, idx)
-__device__ __forceinline__ double uniform01(unsigned long long seed, unsigned long long step, unsigned long long idx) {
-    const unsigned long long h = splitmix64(splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull)) + idx);
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
-}
+// a replay index clamped into the filled part [0, size) of its ring: a caller-supplied draw never reads out of bounds
+__device__ __forceinline__ int iql_ring_slot(int s, int size) { return s < 0 ? 0 : s >= size ? size - 1 : s; }
 
 // IQL.forward (agents/models.py:332-348): mode 0 = argmax, 1 = explore (np.random.random() < eps -> randint), 2 = stochastic
-// (qs / sum(qs) -> np.random.choice).  One thread per (instance, agent); q rows come from the Q GEMM.
+// (qs / sum(qs) -> np.random.choice).  One thread per (instance, agent); q rows come from the Q GEMM.  (iql_fused_act_kernel states the same
+// rule over registers: one shared function changed that kernel's register allocation, so the rule stays written in both.)
 __global__ void iql_act_kernel(const float *Q, const int *n_act, int E, int A, int AMAX, int mode, double eps,
                                unsigned long long seed, unsigned long long step, float *q_out, int *action) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -150,16 +143,14 @@ __global__ void iql_gather_kernel(int E, int A, int SMAX, int B, long long cap, 
         const int c = (int)(i % q4);
         const long long row = (i / q4) % R, a = i / ((long long)q4 * R);
         const long long e = row / B;
-        int s = idx[(e * A + a) * B + row % B];
-        s = s < 0 ? 0 : s >= size ? size - 1 : s;
+        const int s = iql_ring_slot(idx[(e * A + a) * B + row % B], size);
         const long long src = ((e * cap + s) * A + a) * SMAX + 4 * c;
         reinterpret_cast<float4 *>(S)[i] = *reinterpret_cast<const float4 *>(r_obs + src);
         reinterpret_cast<float4 *>(S1)[i] = *reinterpret_cast<const float4 *>(r_next + src);
     }
     if (i < (long long)A * R) {
         const long long row = i % R, a = i / R, e = row / B;
-        int s = idx[(e * A + a) * B + row % B];
-        s = s < 0 ? 0 : s >= size ? size - 1 : s;
+        const int s = iql_ring_slot(idx[(e * A + a) * B + row % B], size);
         act[i] = r_act[(e * cap + s) * A + a];
         rew[i] = r_rew[(e * cap + s) * A + a];
         done[i] = r_done[e * cap + s];
@@ -190,8 +181,17 @@ __global__ void iql_qsel_kernel(const float *Qon, const float *Qtg, const int *n
 }
 
 // tq = done ? r : r + gamma q1 ; loss = mean((q0 - tq)^2) ; dQ[k] = 2 (q0 - tq) / R at k = a   (agents/policies.py:317-318)
+// iql_td_kernel<true> (prioritized replay): the importance weight of the row in and |delta| out -- loss = mean(w (q0 - tq)^2),
+// dQ[k] = 2 w (q0 - tq) / R.  PER_ is empty or {true}, not a plain bool, so that w and td are parameters of that variant only, each in its
+// place: iql_td_kernel<> has the argument block, and with it the machine code, of a kernel without them (the device of
+// iql_fused_grad_kernel's `class... Y`, csrc/tsc_iql_fused.h, for the same reason).
+template <bool, class T> using TdPerArg = T;
+template <bool... PER_>
 __global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done,
-                              long long R, int A, float gamma, float *dQ, double *stats) {
+                              TdPerArg<PER_, const float *__restrict__>... w, long long R, int A, float gamma, float *dQ,
+                              TdPerArg<PER_, float *__restrict__>... td, double *stats) {
+    static_assert(sizeof...(PER_) <= 1, "iql_td_kernel<> or iql_td_kernel<true>");
+    constexpr bool PER = (PER_ || ...);
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     float l = 0.f;
     int a = 0;
@@ -201,13 +201,16 @@ __global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, c
         const float tq = done[i] ? r : r + gamma * q1[i];
         const int k0 = act[i];
         const float d = Q[i * kQ + k0] - tq;
-        const float g = 2.0f * d / (float)R;
+        [[maybe_unused]] float wi = 1.f;
+        if constexpr (PER) wi = (w, ...)[i];
+        const float g = PER ? 2.0f * d * wi / (float)R : 2.0f * d / (float)R;
         float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
         float *v = k0 < 4 ? &lo.x : &hi.x;
         v[k0 & 3] = g;
         reinterpret_cast<float4 *>(dQ + i * kQ)[0] = lo;
         reinterpret_cast<float4 *>(dQ + i * kQ)[1] = hi;
-        l = d * d / (float)R;
+        if constexpr (PER) (td, ...)[i] = fabsf(d);
+        l = PER ? d * d * wi / (float)R : d * d / (float)R;
     }
     // logging only (policies.py:330-337): rows of one agent are contiguous, a wave may straddle two agents -> per-lane atomics
     // are avoided by reducing only when the whole wave belongs to one agent
@@ -298,8 +301,7 @@ __global__ void __launch_bounds__(64 * kPerWaves) iql_per_sample_kernel(int E, i
     int k = 0;
     if (given) {
         if (live && lane < B) {
-            k = idx[p * B + lane];
-            k = k < 0 ? 0 : k >= size ? size - 1 : k;
+            k = iql_ring_slot(idx[p * B + lane], size);
         }
     } else {
         const double t = ((double)lane + uniform01(seed, upd, (unsigned long long)p * B + lane)) * total / (double)B;
@@ -344,8 +346,7 @@ __global__ void iql_per_update_kernel(int E, int A, int B, long long cap, int si
     const float *d = td + a * ((long long)E * B) + e * B;
     float m = qmax[p];
     for (int i = 0; i < B; ++i) {
-        int k = idx[p * B + i];
-        k = k < 0 ? 0 : k >= size ? size - 1 : k;
+        const int k = iql_ring_slot(idx[p * B + i], size);
         const float v = (float)pow((double)d[i] + eps, alpha);
         prio[p * cap + k] = v;
         m = fmaxf(m, v);
@@ -364,39 +365,6 @@ __global__ void iql_per_init_kernel(long long rings, long long cap, long long si
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < rings * cap) prio[i] = i % cap < size ? 1.0f : 0.0f;
     if (i < rings) qmax[i] = 1.0f;
-}
-
-// iql_td_kernel with the importance weight of the row in and |delta| out: loss = mean(w (q0 - tq)^2), dQ[k] = 2 w (q0 - tq) / R at k = a
-__global__ void iql_td_per_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done,
-                                  const float *__restrict__ w, long long R, int A, float gamma, float *dQ, float *__restrict__ td,
-                                  double *stats) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    float l = 0.f;
-    int a = 0;
-    if (i < (long long)A * R) {
-        a = (int)(i / R);
-        const float r = rew[i];
-        const float tq = done[i] ? r : r + gamma * q1[i];
-        const int k0 = act[i];
-        const float d = Q[i * kQ + k0] - tq, wi = w[i];
-        const float g = 2.0f * d * wi / (float)R;
-        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-        float *v = k0 < 4 ? &lo.x : &hi.x;
-        v[k0 & 3] = g;
-        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = lo;
-        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = hi;
-        td[i] = fabsf(d);
-        l = d * d * wi / (float)R;
-    }
-    const int a0 = __shfl(a, 0, 64);
-    const bool uni = __all(a == a0 || i >= (long long)A * R);
-    if (uni) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
-        if ((threadIdx.x & 63) == 0 && l != 0.f) atomicAdd(&stats[a0 * 2], (double)l);
-    } else if (l != 0.f) {
-        atomicAdd(&stats[a * 2], (double)l);
-    }
 }
 
 __global__ void iql_transpose_kernel(const float *params, QLayout L, float *W2T, float *WqT) {
@@ -457,41 +425,86 @@ __global__ void iql_adam_kernel(float *w, float *m1, float *m2, const float *gra
 
 #include "tsc_iql_fused.h"
 
+namespace {
+
+// The fused path's launch plan (the role of Plan in tsc_model.hip): which instantiation serves each role and the dynamic LDS it is
+// launched with, filled once at create and only read afterwards.  make<NM1>() is the only place that spells an instantiation: a new
+// variant is a member here, a set() line there, and a branch of the route in iql_compute_grads.  set() is the only way a member gets
+// its kernel, and it lists the kernel in entries[] as it does so: create's LDS opt-in walks that list, so it cannot miss one.
+template <class... Args>
+struct QKernel {
+    void (*fn)(QFusedArgs, Args...) = nullptr;
+    int lds = 0;                  // dynamic LDS bytes
+    void launch(unsigned grid, hipStream_t st, const QFusedArgs &fa, Args... args) const {
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, st, fa, args...);
+    }
+};
+struct QPlan {
+    QKernel<const float *, int, double, unsigned long long, unsigned long long, int, float *, float *, int *> act;
+    QKernel<> grad;                                           // one launch: Q(s') from the parameters, inside the kernel
+    QKernel<const float *> grad_y;                            // the rows' TD targets come from target[]
+    QKernel<const float *, const float *, float *> grad_yw;   // ... and their importance weights; |delta| out
+    QKernel<const float *, float *, int *> target[2];         // [0] max, [1] Double DQN (two weight images)
+    int S = 0, cps = 0;           // row splits per agent (workgroups = A S); 64-row chunks per split
+    struct Entry { const void *fn; int lds; } entries[8] = {};     // (six in use)
+    int n_entries = 0;
+
+    template <class... Args> void set(QKernel<Args...> &k, void (*fn)(QFusedArgs, Args...), int lds) {
+        k.fn = fn; k.lds = lds;
+        assert(n_entries < 8);
+        entries[n_entries++] = {(const void *)fn, lds};
+    }
+    template <int NM1> static QPlan make() {
+        constexpr int fwd = QFusedLds<NM1>::fwd_floats * 4, grd = QFusedLds<NM1>::grad_floats * 4;
+        QPlan P;
+        P.set(P.act, iql_fused_act_kernel<NM1, 8>, fwd);
+        P.set(P.grad, iql_fused_grad_kernel<NM1, 8>, grd);
+        P.set(P.grad_y, iql_fused_grad_kernel<NM1, 8, true, false, const float *>, grd);
+        P.set(P.grad_yw, iql_fused_grad_kernel<NM1, 8, true, true, const float *, const float *, float *>, grd);
+        P.set(P.target[0], iql_fused_target_kernel<NM1, 8, false>, fwd);
+        P.set(P.target[1], iql_fused_target_kernel<NM1, 8, true>, 2 * fwd);
+        return P;
+    }
+};
+
+}  // namespace
+
 struct tsc_iql {
-    QLayout lay;
-    int E, B, device;
-    long long cap, cum;           // ring capacity / transitions added so far (per instance)
-    double gamma, rnorm, rclip, max_norm;
-    long long adam_t;
-    hipStream_t stream;
-    tsc::DeviceBufs bufs;           // every device buffer of the handle
-    int *n_act;
-    int16_t *rowrange;            // [A][SMAX][2]
-    float *params, *grads, *m1, *m2, *W2T, *WqT;
-    float *r_obs, *r_next, *r_rew; int *r_act; uint8_t *r_done;
-    int *idx;
-    float *S, *S1, *rew, *q1; int *act; uint8_t *done;
-    float *X1, *X2, *Q, *dQ, *dX2;
-    float *Qe;                    // [A][E][8] q rows of the acting forward
-    float *X1e, *X2e;
-    double *norm2, *stats;
-    float *ws, *wsc; size_t ws_floats, wsc_floats;
-    long long nparam;
-    // fused DeepQPolicy learner (tsc_iql_fused.h): 0 = grouped-GEMM path, 8 / 10 = first-layer column tiles of the instantiation
-    int fused, fS, fcps;
-    int *n_wave, *n_wait;
-    float *fws, *fwsl;
-    long long *dbg, *dbg_buf;     // the stamp buffer the kernels see (null while tsc_iql_debug_clock is off) / its allocation
+    QLayout lay{};
+    int E = 0, B = 0, device = 0;
+    long long cap = 0, cum = 0;   // ring capacity / transitions added so far (per instance)
+    double gamma = 0, rnorm = 0, rclip = 0, max_norm = 0;
+    long long adam_t = 0;
+    hipStream_t stream = nullptr;
+    tsc::DeviceBufs bufs;           // every device buffer of the handle (a pointer below stays null until its path allocates it)
+    int *n_act = nullptr;
+    int16_t *rowrange = nullptr;  // [A][SMAX][2]
+    float *params = nullptr, *grads = nullptr, *m1 = nullptr, *m2 = nullptr, *W2T = nullptr, *WqT = nullptr;
+    float *r_obs = nullptr, *r_next = nullptr, *r_rew = nullptr; int *r_act = nullptr; uint8_t *r_done = nullptr;
+    int *idx = nullptr;
+    float *S = nullptr, *S1 = nullptr, *rew = nullptr, *q1 = nullptr; int *act = nullptr; uint8_t *done = nullptr;
+    float *X1 = nullptr, *X2 = nullptr, *Q = nullptr, *dQ = nullptr, *dX2 = nullptr;
+    float *Qe = nullptr;          // [A][E][8] q rows of the acting forward
+    float *X1e = nullptr, *X2e = nullptr;
+    double *norm2 = nullptr, *stats = nullptr;
+    float *ws = nullptr, *wsc = nullptr; size_t ws_floats = 0, wsc_floats = 0;
+    long long nparam = 0;
+    // fused DeepQPolicy learner (tsc_iql_fused.h): 0 = grouped-GEMM path, 8 / 10 = first-layer column tiles of the plan's instantiations
+    int fused = 0;
+    QPlan plan;
+    int *n_wave = nullptr, *n_wait = nullptr;
+    float *fws = nullptr, *fwsl = nullptr;
+    long long *dbg = nullptr, *dbg_buf = nullptr;     // the stamp buffer the kernels see (null while tsc_iql_debug_clock is off) / its allocation
     // target network (tsc_iql_set_target): refresh period in Adam steps (0 = none: the reference's loss), Double DQN on top of it
-    int tgt_period, tgt_double;
-    float *tparams, *y, *Q2;      // the frozen copy [A][stride]; per-row TD targets [A][R] (fused path); the online net's Q(s') (grouped path, double_q)
-    int *astar;                   // [A][R] Double DQN's picks
-    bool y_valid;                 // a compute_grads ran on the armed handle
+    int tgt_period = 0, tgt_double = 0;
+    float *tparams = nullptr, *y = nullptr, *Q2 = nullptr;      // the frozen copy [A][stride]; per-row TD targets [A][R] (fused path); the online net's Q(s') (grouped path, double_q)
+    int *astar = nullptr;         // [A][R] Double DQN's picks
+    bool y_valid = false;         // a compute_grads ran on the armed handle
     // prioritized replay (tsc_iql_set_per): stored priorities [E][A][cap], running maxima [E][A], importance weights and |delta| [A][R]
-    int per;
-    double per_alpha, per_eps, per_beta;
-    float *prio, *qmax, *w, *td;
-    bool per_valid;               // a compute_grads ran on the handle while prioritized replay was armed
+    int per = 0;
+    double per_alpha = 0, per_eps = 0, per_beta = 1.0;
+    float *prio = nullptr, *qmax = nullptr, *w = nullptr, *td = nullptr;
+    bool per_valid = false;       // a compute_grads ran on the handle while prioritized replay was armed
 };
 
 namespace {
@@ -528,11 +541,26 @@ QFusedArgs fused_args(const tsc_iql *h, long long size) {
     fa.params = h->params; fa.n_act = h->n_act; fa.n_wave = h->n_wave; fa.n_wait = h->n_wait; fa.idx = h->idx;
     fa.r_obs = h->r_obs; fa.r_next = h->r_next; fa.r_rew = h->r_rew; fa.r_act = h->r_act; fa.r_done = h->r_done;
     fa.E = h->E; fa.A = L.A; fa.B = h->B; fa.SMAX = L.SMAX; fa.size = (int)size; fa.cap = h->cap; fa.R = (long long)h->E * h->B;
-    fa.gamma = (float)h->gamma; fa.S = h->fS; fa.cps = h->fcps; fa.ws = h->fws; fa.wsl = h->fwsl;
+    fa.gamma = (float)h->gamma; fa.S = h->plan.S; fa.cps = h->plan.cps; fa.ws = h->fws; fa.wsl = h->fwsl;
     fa.dbg = h->dbg;
     fa.stride = L.stride; fa.oW1 = L.oW1; fa.ob1 = L.ob1; fa.oW2 = L.oW2; fa.ob2 = L.ob2; fa.oWq = L.oWq; fa.obq = L.obq;
     return fa;
 }
+
+// transitions in the filled part of every ring
+long long replay_size(const tsc_iql *h) { return h->cum < h->cap ? h->cum : h->cap; }
+
+// theta- <- theta on the handle's stream
+hipError_t freeze_params(tsc_iql *h) {
+    return hipMemcpyAsync(h->tparams, h->params, sizeof(float) * h->nparam, hipMemcpyDeviceToDevice, h->stream);
+}
+
+// a buffer its first user allocates (a failed allocation leaves the pointer null, and the next call asks again)
+template <class T> hipError_t alloc_once(tsc_iql *h, T **field, long long count, bool zero = true) {
+    return *field ? hipSuccess : h->bufs.alloc(field, count, zero);
+}
+
+size_t per_sample_lds(const tsc_iql *h) { return sizeof(float) * kPerWaves * per_wave_floats((int)h->cap); }
 
 }  // namespace
 
@@ -548,9 +576,8 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
     TSC_HIP(hipSetDevice(device));
     tsc_iql *h = new tsc_iql();
     tsc::CreateGuard<tsc_iql, tsc_iql_destroy> guard(h);        // an error return below frees the handle and its buffers
-    h->device = device; h->stream = nullptr; h->E = n_env; h->B = cfg->batch_size; h->cap = cfg->buffer_size; h->cum = 0;
+    h->device = device; h->E = n_env; h->B = cfg->batch_size; h->cap = cfg->buffer_size;
     h->gamma = cfg->gamma; h->rnorm = cfg->reward_norm; h->rclip = cfg->reward_clip; h->max_norm = cfg->max_grad_norm;
-    h->adam_t = 0;
     QLayout &L = h->lay;
     L.A = cfg->n_agent; L.SMAX = cfg->s_max; L.AMAX = cfg->a_max; L.dqn = cfg->kind;
     bool any_wait = false;
@@ -590,9 +617,6 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
     // The fused DeepQPolicy learner (tsc_iql_fused.h) is built for the reference's widths (config/config_iqld_*.ini: num_fc 128,
     // num_h 64 -> H1 = 160 with wait inputs, 128 without) and observations of at most 48 features; anything else, IQL-LR, and
     // TSC_IQL_FUSED=0 (the A/B switch of tests/test_iql_gpu.py) take the grouped-GEMM path.
-    h->fused = 0; h->fS = h->fcps = 0; h->fws = h->fwsl = nullptr; h->dbg = h->dbg_buf = nullptr;
-    h->tgt_period = h->tgt_double = 0; h->tparams = h->y = h->Q2 = nullptr; h->astar = nullptr; h->y_valid = false;
-    h->per = 0; h->per_alpha = h->per_eps = 0.0; h->per_beta = 1.0; h->prio = h->qmax = h->w = h->td = nullptr; h->per_valid = false;
     TSC_HIP(h->bufs.upload(&h->n_wave, cfg->n_wave, L.A));
     TSC_HIP(h->bufs.upload(&h->n_wait, cfg->n_wait, L.A));
     {
@@ -609,34 +633,21 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
     }
     if (h->fused && R >= ((long long)1 << 31) / 64) h->fused = 0;       // the fused kernel indexes rows and chunks in 32 bits
     if (h->fused) {
+        switch (h->fused) {
+            case 8: h->plan = QPlan::make<8>(); break;
+            case 10: h->plan = QPlan::make<10>(); break;
+            default: return tsc::fail("tsc_iql_create: no fused instantiation for %d first-layer column tiles", h->fused);
+        }
         // row splits per agent: one workgroup per CU (the kernel holds its gradient tiles in registers over its whole slice)
         const long long nchunks = (R + 63) / 64;
         long long S = 256 / A;
         if (S < 1) S = 1;
         if (S > nchunks) S = nchunks;
-        h->fcps = (int)((nchunks + S - 1) / S);
-        h->fS = (int)((nchunks + h->fcps - 1) / h->fcps);
-        TSC_HIP(h->bufs.alloc(&h->fws, (long long)h->fS * A * L.stride, true)); TSC_HIP(h->bufs.alloc(&h->fwsl, (long long)h->fS * A, true));
-        const int lds_g = (h->fused == 10 ? QFusedLds<10>::grad_floats : QFusedLds<8>::grad_floats) * 4;
-        const int lds_f = (h->fused == 10 ? QFusedLds<10>::fwd_floats : QFusedLds<8>::fwd_floats) * 4;
-        if (h->fused == 10) {
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_act_kernel<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8, true, false, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<10, 8, true, true, const float *, const float *, float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<10, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<10, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds_f));
-        } else {
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_act_kernel<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8, true, false, const float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_grad_kernel<8, 8, true, true, const float *, const float *, float *>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_g));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<8, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_f));
-            TSC_HIP(hipFuncSetAttribute((const void *)iql_fused_target_kernel<8, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * lds_f));
-        }
-        h->S = h->S1 = h->rew = h->q1 = h->Q = h->dQ = nullptr; h->act = nullptr; h->done = nullptr;
-        h->X1 = h->X2 = h->dX2 = h->X1e = h->X2e = h->W2T = h->WqT = nullptr;
-        h->ws = h->wsc = nullptr; h->ws_floats = h->wsc_floats = 0;
+        h->plan.cps = (int)((nchunks + S - 1) / S);
+        h->plan.S = (int)((nchunks + h->plan.cps - 1) / h->plan.cps);
+        TSC_HIP(h->bufs.alloc(&h->fws, (long long)h->plan.S * A * L.stride, true)); TSC_HIP(h->bufs.alloc(&h->fwsl, (long long)h->plan.S * A, true));
+        for (int k = 0; k < h->plan.n_entries; ++k)
+            TSC_HIP(hipFuncSetAttribute(h->plan.entries[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->plan.entries[k].lds));
     } else {
         TSC_HIP(h->bufs.alloc(&h->S, A * R * L.SMAX, true)); TSC_HIP(h->bufs.alloc(&h->S1, A * R * L.SMAX, true));
         TSC_HIP(h->bufs.alloc(&h->rew, A * R, true)); TSC_HIP(h->bufs.alloc(&h->q1, A * R, true)); TSC_HIP(h->bufs.alloc(&h->act, A * R, true)); TSC_HIP(h->bufs.alloc(&h->done, A * R, true));
@@ -645,8 +656,6 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
             TSC_HIP(h->bufs.alloc(&h->X1, A * R * L.H1, true)); TSC_HIP(h->bufs.alloc(&h->X2, A * R * L.H2, true)); TSC_HIP(h->bufs.alloc(&h->dX2, A * R * L.H2, true));
             TSC_HIP(h->bufs.alloc(&h->X1e, A * E * L.H1, true)); TSC_HIP(h->bufs.alloc(&h->X2e, A * E * L.H2, true));
             TSC_HIP(h->bufs.alloc(&h->W2T, A * L.H1 * L.H2, true)); TSC_HIP(h->bufs.alloc(&h->WqT, A * L.H2 * kQ, true));
-        } else {
-            h->X1 = h->X2 = h->dX2 = h->X1e = h->X2e = h->W2T = h->WqT = nullptr;
         }
         h->ws_floats = (size_t)16 << 20; h->wsc_floats = (size_t)1 << 18;
         TSC_HIP(h->bufs.alloc(&h->ws, h->ws_floats, true)); TSC_HIP(h->bufs.alloc(&h->wsc, h->wsc_floats, true));
@@ -711,14 +720,9 @@ int tsc_iql_forward(tsc_iql *h, const float *obs, float *q_out, int32_t *action,
     const QLayout &L = h->lay;
     if (h->fused) {
         QFusedArgs fa = fused_args(h, 0);
-        const unsigned grid = (unsigned)(L.A * ((h->E + 63) / 64));
         tsc::ProfScope ps(tsc::KID_IQL_ACT, h->stream);
-        if (h->fused == 10)
-            hipLaunchKernelGGL((iql_fused_act_kernel<10, 8>), dim3(grid), dim3(256), QFusedLds<10>::fwd_floats * 4, h->stream, fa, obs, (int)mode,
-                               eps, (unsigned long long)seed, (unsigned long long)step, L.AMAX, h->Qe, q_out, action);
-        else
-            hipLaunchKernelGGL((iql_fused_act_kernel<8, 8>), dim3(grid), dim3(256), QFusedLds<8>::fwd_floats * 4, h->stream, fa, obs, (int)mode,
-                               eps, (unsigned long long)seed, (unsigned long long)step, L.AMAX, h->Qe, q_out, action);
+        h->plan.act.launch((unsigned)(L.A * ((h->E + 63) / 64)), h->stream, fa, obs, (int)mode, eps, (unsigned long long)seed,
+                           (unsigned long long)step, L.AMAX, h->Qe, q_out, action);
         TSC_HIP(hipGetLastError());
         return 0;
     }
@@ -755,7 +759,7 @@ int tsc_iql_add_transition(tsc_iql *h, const float *obs, const int32_t *action, 
 
 int tsc_iql_replay_size(tsc_iql *h, int64_t *size, int64_t *cum) {
     if (!h || !size || !cum) return tsc::fail("tsc_iql_replay_size: bad arguments");
-    *size = h->cum < h->cap ? h->cum : h->cap; *cum = h->cum;
+    *size = replay_size(h); *cum = h->cum;
     return 0;
 }
 
@@ -765,7 +769,7 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
 static int iql_grads_then_priorities(tsc_iql *h, uint64_t seed, uint64_t update_index, const int32_t *idx_dev) {
     const int rc = iql_compute_grads(h, seed, update_index, idx_dev);
     if (rc || !h->per) return rc;
-    const long long rings = (long long)h->E * h->lay.A, size = h->cum < h->cap ? h->cum : h->cap;
+    const long long rings = (long long)h->E * h->lay.A, size = replay_size(h);
     tsc::ProfScope ps(tsc::KID_IQL_PER_UPDATE, h->stream);
     hipLaunchKernelGGL(iql_per_update_kernel, dim3((unsigned)((rings + 127) / 128)), dim3(128), 0, h->stream, h->E, h->lay.A, h->B, h->cap,
                        (int)size, h->per_alpha, h->per_eps, h->idx, h->td, h->prio, h->qmax);
@@ -786,21 +790,28 @@ int tsc_iql_compute_grads_at(tsc_iql *h, const int32_t *idx_dev) {
 static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, const int32_t *idx_dev) {
     if (!h) return tsc::fail("null handle");
     const QLayout &L = h->lay;
-    const long long size = h->cum < h->cap ? h->cum : h->cap;
+    const long long size = replay_size(h);
     if (size < h->B) return tsc::fail("tsc_iql_compute_grads: replay holds %lld < batch_size %d transitions", size, h->B);
     hipStream_t st = h->stream;
     const long long E = h->E, A = L.A, R = E * h->B;
+    // the route of this call (arming can change between calls); both paths below read these names and nothing else
+    const bool given = idx_dev != nullptr;                   // the draw: the caller's, else prioritized (per), else Floyd's
+    const bool per = h->per != 0;                            // importance weights in, |delta| out
+    const bool armed = h->tgt_period > 0;                    // Q(s') from the frozen copy
+    const bool dbl = armed && h->tgt_double;                 // ... at the online net's first maximum
+    const float *tp = armed ? h->tparams : h->params;        // the net behind the TD targets
+    const bool two_launch = armed || per;                    // fused path: the TD targets in a launch of their own, else inside the gradient's
     TSC_HIP(hipMemsetAsync(h->stats, 0, sizeof(double) * A * 2, st));
-    if (idx_dev) {      // the caller's draw (e.g. the reference's random.sample); the gather clamps every index into [0, size)
+    if (given) {        // (e.g. the reference's random.sample); the gather clamps every index into [0, size)
         TSC_HIP(hipMemcpyAsync(h->idx, idx_dev, sizeof(int) * E * A * h->B, hipMemcpyDeviceToDevice, st));
     }
-    if (h->per) {       // the proportional draw and its importance weights; on the caller's draw only the weights
+    if (per) {          // the proportional draw and its importance weights; on the caller's draw only the weights
         tsc::ProfScope ps(tsc::KID_IQL_PER_SAMPLE, st);
         hipLaunchKernelGGL(iql_per_sample_kernel, dim3((unsigned)((E * A + kPerWaves - 1) / kPerWaves)), dim3(64 * kPerWaves),
-                           sizeof(float) * kPerWaves * per_wave_floats((int)h->cap), st, (int)E, (int)A, h->B, h->cap, (int)size, h->per_beta,
-                           (unsigned long long)seed, (unsigned long long)update_index, idx_dev ? 1 : 0, h->prio, h->idx, h->w);
+                           per_sample_lds(h), st, (int)E, (int)A, h->B, h->cap, (int)size, h->per_beta,
+                           (unsigned long long)seed, (unsigned long long)update_index, given ? 1 : 0, h->prio, h->idx, h->w);
         TSC_HIP(hipGetLastError());
-    } else if (!idx_dev) {
+    } else if (!given) {
         tsc::ProfScope ps(tsc::KID_IQL_SAMPLE, st);
         if (h->B == 20)
             hipLaunchKernelGGL(iql_sample_fixed_kernel<20>, dim3((unsigned)((E * A + 127) / 128)), dim3(128), 0, st, (int)E, (int)A, size,
@@ -809,48 +820,29 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
             hipLaunchKernelGGL(iql_sample_kernel, dim3((unsigned)((E * A + 127) / 128)), dim3(128), 0, st, (int)E, (int)A, h->B, size,
                                (unsigned long long)seed, (unsigned long long)update_index, h->idx);
     }
-    const bool armed = h->tgt_period > 0;
     if (armed) h->y_valid = true;
     if (h->fused) {
-        QFusedArgs fa = fused_args(h, size);
-        const unsigned grid = (unsigned)(A * h->fS);
-        if (armed || h->per) {  // two launches: the TD targets from the frozen copy (forward only), then the gradient with one row set
-            // (prioritized replay always takes this route; without a target network the "frozen copy" is the parameters themselves)
-            const float *tp = armed ? h->tparams : h->params;
-            const bool dbl = armed && h->tgt_double;
+        const QPlan &P = h->plan;
+        const QFusedArgs fa = fused_args(h, size);
+        const unsigned grid = (unsigned)(A * P.S);
+        if (two_launch) {       // the TD targets from tp (forward only), then the gradient with one row set
+            // (prioritized replay always takes this route; without a target network tp is the parameters themselves)
             {
                 tsc::ProfScope ps(tsc::KID_IQL_TARGET, st);
-                const int lds_f = (h->fused == 10 ? QFusedLds<10>::fwd_floats : QFusedLds<8>::fwd_floats) * 4;
-                if (h->fused == 10 && dbl)
-                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, tp, h->y, h->astar);
-                else if (h->fused == 10)
-                    hipLaunchKernelGGL((iql_fused_target_kernel<10, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, tp, h->y, h->astar);
-                else if (dbl)
-                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, true>), dim3(grid), dim3(256), 2 * lds_f, st, fa, tp, h->y, h->astar);
-                else
-                    hipLaunchKernelGGL((iql_fused_target_kernel<8, 8, false>), dim3(grid), dim3(256), lds_f, st, fa, tp, h->y, h->astar);
+                P.target[dbl].launch(grid, st, fa, tp, h->y, h->astar);
             }
             TSC_HIP(hipGetLastError());
             tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
-            if (h->fused == 10 && h->per)
-                hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8, true, true, const float *, const float *, float *>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa, (const float *)h->y, (const float *)h->w, h->td);
-            else if (h->per)
-                hipLaunchKernelGGL((iql_fused_grad_kernel<8, 8, true, true, const float *, const float *, float *>), dim3(grid), dim3(256), QFusedLds<8>::grad_floats * 4, st, fa, (const float *)h->y, (const float *)h->w, h->td);
-            else if (h->fused == 10)
-                hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8, true, false, const float *>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa, (const float *)h->y);
-            else
-                hipLaunchKernelGGL((iql_fused_grad_kernel<8, 8, true, false, const float *>), dim3(grid), dim3(256), QFusedLds<8>::grad_floats * 4, st, fa, (const float *)h->y);
+            if (per) P.grad_yw.launch(grid, st, fa, h->y, h->w, h->td);
+            else P.grad_y.launch(grid, st, fa, h->y);
         } else {
             tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
-            if (h->fused == 10)
-                hipLaunchKernelGGL((iql_fused_grad_kernel<10, 8>), dim3(grid), dim3(256), QFusedLds<10>::grad_floats * 4, st, fa);
-            else
-                hipLaunchKernelGGL((iql_fused_grad_kernel<8, 8>), dim3(grid), dim3(256), QFusedLds<8>::grad_floats * 4, st, fa);
+            P.grad.launch(grid, st, fa);
         }
         TSC_HIP(hipGetLastError());
         tsc::ProfScope ps(tsc::KID_IQL_REDUCE, st);
         hipLaunchKernelGGL(iql_fused_reduce_kernel, dim3((unsigned)((L.stride + 255) / 256), (unsigned)A), dim3(256), 0, st, h->fws, h->fwsl,
-                           (int)A, h->fS, L.stride, L.ob1, L.H1, h->rowrange, L.SMAX, h->grads, h->stats);
+                           (int)A, P.S, L.stride, L.ob1, L.H1, h->rowrange, L.SMAX, h->grads, h->stats);
         TSC_HIP(hipGetLastError());
         return 0;
     }
@@ -860,19 +852,19 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
     TSC_HIP(hipGetLastError());
     // Q(s') first (its activations are not needed afterwards), then Q(s) with the activations the backward pass reads
     // (armed: Q(s') comes from the frozen copy; Double DQN adds the online net's Q(s'), whose first maximum picks the target's value)
-    if (q_forward(h, armed ? h->tparams : h->params, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
-    if (armed && h->tgt_double) {
+    if (q_forward(h, tp, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
+    if (dbl) {
         if (q_forward(h, h->params, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q2)) return tsc::fail("gemm launch failed");
         hipLaunchKernelGGL(iql_qsel_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q2, h->Q, h->n_act, R, (int)A, h->q1, h->astar);
     } else {
         hipLaunchKernelGGL(iql_qmax_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->n_act, R, (int)A, h->q1);
     }
     if (q_forward(h, h->params, h->S, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
-    if (h->per)
-        hipLaunchKernelGGL(iql_td_per_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
+    if (per)
+        hipLaunchKernelGGL(iql_td_kernel<true>, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
                            h->w, R, (int)A, (float)h->gamma, h->dQ, h->td, h->stats);
     else
-        hipLaunchKernelGGL(iql_td_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, R,
+        hipLaunchKernelGGL(iql_td_kernel<>, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, R,
                            (int)A, (float)h->gamma, h->dQ, h->stats);
     TSC_HIP(hipGetLastError());
     float *g = h->grads;
@@ -921,8 +913,7 @@ int tsc_iql_apply_grads(tsc_iql *h, double lr, double grad_scale, double *stats_
     TSC_HIP(hipGetLastError());
     ps.stop();
     // target network: the frozen copy follows after every tgt_period-th Adam step of the handle (a resumed run keeps its phase)
-    if (h->tgt_period > 0 && h->adam_t % h->tgt_period == 0)
-        TSC_HIP(hipMemcpyAsync(h->tparams, h->params, sizeof(float) * h->nparam, hipMemcpyDeviceToDevice, st));
+    if (h->tgt_period > 0 && h->adam_t % h->tgt_period == 0) TSC_HIP(freeze_params(h));
     if (stats_host) {
         std::vector<double> s(L.A * 2), n2p((size_t)L.A * kNormSlices), n2(L.A, 0.0);
         TSC_HIP(hipStreamSynchronize(st));
@@ -941,7 +932,7 @@ int tsc_iql_debug_clock(tsc_iql *h, int32_t enable, int64_t *stamps_host, int32_
     if (count < 0) return tsc::fail("tsc_iql_debug_clock: count %d < 0", count);
     TSC_HIP(hipStreamSynchronize(h->stream));
     // [64] phase stamps | start / end of the gradient kernel's workgroups | start / end of the target kernel's (armed handles)
-    const size_t n = 64 + 4 * (size_t)h->lay.A * h->fS;
+    const size_t n = 64 + 4 * (size_t)h->lay.A * h->plan.S;
     if (enable && !h->dbg_buf) {
         TSC_HIP(h->bufs.alloc(&h->dbg_buf, n, true));
     }
@@ -958,13 +949,12 @@ int tsc_iql_set_target(tsc_iql *h, int32_t period, int32_t double_q) {
         const QLayout &L = h->lay;
         const long long AR = (long long)L.A * h->E * h->B;
         TSC_HIP(hipSetDevice(h->device));
-        // each buffer when its first user arms (a failed allocation leaves its pointer null, and the next call asks again)
-        if (!h->tparams) TSC_HIP(h->bufs.alloc(&h->tparams, h->nparam, true));
-        if (h->fused && !h->y) TSC_HIP(h->bufs.alloc(&h->y, AR, true));          // (the grouped path keeps q1, see tsc_iql_debug_targets)
-        if (double_q && !h->astar) TSC_HIP(h->bufs.alloc(&h->astar, AR, true));
-        if (double_q && !h->fused && !h->Q2) TSC_HIP(h->bufs.alloc(&h->Q2, AR * kQ, true));
-        if (!h->tgt_period)       // armed: the frozen copy starts as the parameters
-            TSC_HIP(hipMemcpyAsync(h->tparams, h->params, sizeof(float) * h->nparam, hipMemcpyDeviceToDevice, h->stream));
+        // each buffer when its first user arms
+        TSC_HIP(alloc_once(h, &h->tparams, h->nparam));
+        if (h->fused) TSC_HIP(alloc_once(h, &h->y, AR));                         // (the grouped path keeps q1, see tsc_iql_debug_targets)
+        if (double_q) TSC_HIP(alloc_once(h, &h->astar, AR));
+        if (double_q && !h->fused) TSC_HIP(alloc_once(h, &h->Q2, AR * kQ));
+        if (!h->tgt_period) TSC_HIP(freeze_params(h));       // armed: the frozen copy starts as the parameters
     }
     if (!period || period != h->tgt_period || double_q != h->tgt_double) h->y_valid = false;
     h->tgt_period = period; h->tgt_double = double_q;
@@ -974,7 +964,7 @@ int tsc_iql_set_target(tsc_iql *h, int32_t period, int32_t double_q) {
 int tsc_iql_sync_target(tsc_iql *h) {
     if (!h) return tsc::fail("null handle");
     if (!h->tgt_period) return tsc::fail("tsc_iql_sync_target: no target network (tsc_iql_set_target)");
-    TSC_HIP(hipMemcpyAsync(h->tparams, h->params, sizeof(float) * h->nparam, hipMemcpyDeviceToDevice, h->stream));
+    TSC_HIP(freeze_params(h));
     return 0;
 }
 
@@ -1030,16 +1020,15 @@ int tsc_iql_set_per(tsc_iql *h, int32_t enable, double alpha, double eps) {
         return tsc::fail("tsc_iql_set_per: buffer_size %lld > TSC_IQL_PER_MAX_BUFFER (%d): the sampler stages a whole ring in LDS", h->cap,
                          TSC_IQL_PER_MAX_BUFFER);
     const QLayout &L = h->lay;
-    const long long rings = (long long)h->E * L.A, AR = rings * h->B, size = h->cum < h->cap ? h->cum : h->cap;
+    const long long rings = (long long)h->E * L.A, AR = rings * h->B, size = replay_size(h);
     TSC_HIP(hipSetDevice(h->device));
     const bool first = !h->prio || !h->qmax;
-    if (!h->prio) TSC_HIP(h->bufs.alloc(&h->prio, rings * h->cap, false));
-    if (!h->qmax) TSC_HIP(h->bufs.alloc(&h->qmax, rings, false));
-    if (!h->w) TSC_HIP(h->bufs.alloc(&h->w, AR, true));
-    if (!h->td) TSC_HIP(h->bufs.alloc(&h->td, AR, true));
-    if (h->fused && !h->y) TSC_HIP(h->bufs.alloc(&h->y, AR, true));
-    TSC_HIP(hipFuncSetAttribute((const void *)iql_per_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sizeof(float) * kPerWaves * per_wave_floats((int)h->cap)));
+    TSC_HIP(alloc_once(h, &h->prio, rings * h->cap, false));
+    TSC_HIP(alloc_once(h, &h->qmax, rings, false));
+    TSC_HIP(alloc_once(h, &h->w, AR));
+    TSC_HIP(alloc_once(h, &h->td, AR));
+    if (h->fused) TSC_HIP(alloc_once(h, &h->y, AR));
+    TSC_HIP(hipFuncSetAttribute((const void *)iql_per_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)per_sample_lds(h)));
     // priorities are powers of alpha, so another alpha starts over; so does arming again after a disarm (slots filled meanwhile have none)
     if (first || !h->per || alpha != h->per_alpha) {
         const long long n = rings * h->cap;
@@ -1071,7 +1060,7 @@ int tsc_iql_get_priorities(tsc_iql *h, float *prio_host, float *qmax_host) {
 int tsc_iql_set_priorities(tsc_iql *h, const float *prio_host, const float *qmax_host) {
     if (!h || !prio_host || !qmax_host) return tsc::fail("tsc_iql_set_priorities: bad arguments");
     if (!h->per) return tsc::fail("tsc_iql_set_priorities: prioritized replay is not armed (tsc_iql_set_per)");
-    const size_t rings = (size_t)h->E * h->lay.A, cap = (size_t)h->cap, size = (size_t)(h->cum < h->cap ? h->cum : h->cap);
+    const size_t rings = (size_t)h->E * h->lay.A, cap = (size_t)h->cap, size = (size_t)replay_size(h);
     for (size_t p = 0; p < rings; ++p) {
         bool mass = size == 0;
         for (size_t s = 0; s < cap; ++s) {

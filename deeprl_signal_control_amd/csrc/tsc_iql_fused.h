@@ -21,6 +21,12 @@
 //     slice and are written once, as the split's partial gradient; iql_fused_reduce_kernel folds the splits in fixed order
 //     (deterministic), applies W1's block-diagonal mask and sums the loss.
 // Arithmetic: fp32 MFMA (exact f32 products, f32 accumulate) -- the same numbers as the grouped-GEMM path up to summation order.
+//
+// Variants and how they are launched: the kernels below are templates over the first layer's column tiles (NM1 = 8 without a wait part,
+// 10 with one) and, for the gradient and target kernels, over the route (TGT / PER, DBL).  No launch site names an instantiation: QPlan
+// in csrc/tsc_iql.hip takes the address and the dynamic LDS bytes of every one of them once, in QPlan::make<NM1>(), tsc_iql_create opts
+// each into its LDS from that list, and tsc_iql_forward / iql_compute_grads launch through the plan.  A new variant is a member of QPlan,
+// a line in make<>, and a branch of the route in iql_compute_grads.
 #pragma once
 #include <type_traits>
 
@@ -283,11 +289,25 @@ __device__ __forceinline__ float4 q_obs4(const float *row, int f0, int SMAX, boo
     return in ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// ring slot of the row of lane (wave, n) in 64-row chunk c of agent a: the row is clamped into [0, R), the slot into the ring's filled
+// part (like the gather kernel's).  Rows are 32-bit here (the host refuses E * B >= 2^31): a 64-bit division per lane and chunk costs
+// more than the chunk's VALU work
+struct QSlot { int slot; unsigned e; };
+__device__ __forceinline__ QSlot q_slot_of(const QFusedArgs &p, int a, int wave, int n, long long c) {
+    const unsigned uR = (unsigned)p.R, uB = (unsigned)p.B;
+    unsigned row = ((unsigned)c << 6) + 16 * wave + n;
+    if (row >= uR) row = uR - 1;
+    QSlot o;
+    o.e = row / uB;
+    o.slot = iql_ring_slot(p.idx[((long long)o.e * p.A + a) * p.B + (row - o.e * uB)], p.size);
+    return o;
+}
+
 // ---- the minibatch gradient ---------------------------------------------------------------------------------------------------
-// TGT: the armed handle's variant, launched as iql_fused_grad_kernel<.., true, const float *>(p, y) -- the TD target of every row was
+// TGT: the armed handle's variant (QPlan::grad_y), iql_fused_grad_kernel<.., true, false, const float *>(p, y) -- the TD target of every row was
 // left by iql_fused_target_kernel in y [A][R], so only s goes through the nets (one row set) and neither s', the reward nor the done
 // flag is read; everything from the TD error on is the same code.  The default instantiations take no second argument (Y is empty).
-// PER (prioritized replay, tsc_iql_set_per; always with TGT): launched as <.., true, true, const float *, const float *, float *>(p, y, w, td)
+// PER (prioritized replay, tsc_iql_set_per; always with TGT; QPlan::grad_yw): <.., true, true, const float *, const float *, float *>(p, y, w, td)
 // -- the row's importance weight w [A][R] scales its gradient and its loss term, and the kq == 0 lanes store |delta| of the valid rows in
 // td [A][R] for the priority write-back.
 __device__ __forceinline__ const float *q_targets_of() { return nullptr; }
@@ -338,19 +358,12 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
     const float fR = (float)p.R;
 
     struct Rows { float4 s0[3], s1[3]; float rew; int act, done; bool ok; };
-    // rows are 32-bit here (the host refuses E * B >= 2^31): a 64-bit division per lane and chunk costs more than the chunk's VALU work
-    const unsigned uR = (unsigned)p.R, uB = (unsigned)p.B;
-    struct Slot { int slot; unsigned e; };
-    auto slot_of = [&](long long c) -> Slot {            // ring slot of this lane's row in chunk c (clamped like the gather kernel's)
-        unsigned row = ((unsigned)c << 6) + 16 * wave + n;
-        if (row >= uR) row = uR - 1;
-        Slot o;
-        o.e = row / uB;
-        const int s_ = p.idx[((long long)o.e * p.A + a) * p.B + (row - o.e * uB)];
-        o.slot = s_ < 0 ? 0 : s_ >= p.size ? p.size - 1 : s_;
-        return o;
-    };
-    auto load_rows = [&](long long c, const Slot &sl, Rows &r) {
+    const unsigned uR = (unsigned)p.R;                   // 32-bit rows, see q_slot_of
+    // q_slot_of stays behind this lambda on purpose: called directly at its three sites the forced-inline helper is expanded before the
+    // optimiser runs instead of by its inliner, and this kernel's instruction order and register allocation change (measured by comparing
+    // the assembly); the hot kernel must not move for a tidier call
+    auto slot_of = [&](long long c) { return q_slot_of(p, a, wave, n, c); };
+    auto load_rows = [&](long long c, const QSlot &sl, Rows &r) {
         const unsigned row = ((unsigned)c << 6) + 16 * wave + n;
         r.ok = row < uR && c < c1;
         const long long tr = ((long long)sl.e * p.cap + sl.slot) * p.A + a;
@@ -382,7 +395,7 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
 #define QSTAMP(k) do { } while (0)
 #endif
     Rows cur, nxt;
-    Slot slot_n = {0, 0};
+    QSlot slot_n = {0, 0};
     // PER: the importance weight of this lane's row in the current / next chunk (requested with the rows)
     [[maybe_unused]] float wcur = 1.f, wnxt = 1.f;
     [[maybe_unused]] auto weight_of = [&](long long c) {
@@ -708,17 +721,6 @@ __global__ void iql_fused_reduce_kernel(const float *__restrict__ ws, const floa
 }
 
 // ---- IQL.forward (agents/models.py:332-348) in one launch: the same nets on the E acting rows + the action choice -------
-__device__ __forceinline__ unsigned long long qf_splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ double qf_uniform01(unsigned long long seed, unsigned long long step, unsigned long long idx) {
-    const unsigned long long h = qf_splitmix64(qf_splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull)) + idx);
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
-}
-
 template <int NM1, int NMW>
 __global__ void __launch_bounds__(256, 1) iql_fused_act_kernel(QFusedArgs p, const float *__restrict__ obs, int mode, double eps,
                                                                unsigned long long seed, unsigned long long step, int AMAX,
@@ -763,19 +765,20 @@ __global__ void __launch_bounds__(256, 1) iql_fused_act_kernel(QFusedArgs p, con
         for (int j = 0; j < 8; ++j) if (j == k && k < na) v = qv[j];
         q_out[idx * AMAX + k] = v;
     }
+    // the action choice of iql_act_kernel (csrc/tsc_iql.hip) over registers: k < na as a predicate, so qv is never indexed by a run-time value
     int best = 0;
     float qbest = qv[0];
 #pragma unroll
     for (int k = 1; k < 8; ++k) if (k < na && qv[k] > qbest) { qbest = qv[k]; best = k; }       // np.argmax: first maximum
     int act = best;
     if (mode == 1) {
-        const double u0 = qf_uniform01(seed, step, 2ull * idx), u1 = qf_uniform01(seed, step, 2ull * idx + 1);
+        const double u0 = uniform01(seed, step, 2ull * idx), u1 = uniform01(seed, step, 2ull * idx + 1);
         if (u0 < eps) { act = (int)(u1 * (double)na); if (act >= na) act = na - 1; }
     } else if (mode == 2) {
         double sum = 0.0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) if (k < na) sum += (double)qv[k];
-        const double u = qf_uniform01(seed, step, 2ull * idx);
+        const double u = uniform01(seed, step, 2ull * idx);
         double cdf = 0.0, tot = 0.0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) if (k < na) tot += (double)qv[k] / sum;
@@ -820,18 +823,11 @@ __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, 
     if (c1 > nchunks) c1 = nchunks;
 
     struct Rows { float4 s1[3]; float rew; int done; bool ok; };
-    const unsigned uR = (unsigned)p.R, uB = (unsigned)p.B;                 // 32-bit rows, see iql_fused_grad_kernel
-    struct Slot { int slot; unsigned e; };
-    auto slot_of = [&](long long c) -> Slot {            // the gradient kernel's: the row is clamped into [0, R), the slot into the ring's filled part
-        unsigned row = ((unsigned)c << 6) + 16 * wave + n;
-        if (row >= uR) row = uR - 1;
-        Slot o;
-        o.e = row / uB;
-        const int s_ = p.idx[((long long)o.e * p.A + a) * p.B + (row - o.e * uB)];
-        o.slot = s_ < 0 ? 0 : s_ >= p.size ? p.size - 1 : s_;
-        return o;
-    };
-    auto load_rows = [&](long long c, const Slot &sl, Rows &r) {
+    const unsigned uR = (unsigned)p.R;                   // 32-bit rows, see q_slot_of
+    // behind a lambda on purpose, as in iql_fused_grad_kernel: three direct calls of the forced-inline q_slot_of change this kernel's
+    // instruction order and register allocation
+    auto slot_of = [&](long long c) { return q_slot_of(p, a, wave, n, c); };
+    auto load_rows = [&](long long c, const QSlot &sl, Rows &r) {
         const unsigned row = ((unsigned)c << 6) + 16 * wave + n;
         r.ok = row < uR && c < c1;
         const long long tr = ((long long)sl.e * p.cap + sl.slot) * p.A + a;
@@ -844,7 +840,7 @@ __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, 
     long long *wg_dbg = p.dbg ? p.dbg + 64 + 2 * (long long)gridDim.x + 2 * blockIdx.x : nullptr;
     if (wg_dbg && tid == 0) wg_dbg[0] = wall_clock64();
     Rows cur, nxt;
-    Slot slot_n = {0, 0};
+    QSlot slot_n = {0, 0};
     if (c0 < c1) {
         load_rows(c0, slot_of(c0), cur);
         slot_n = slot_of(c0 + 1 < c1 ? c0 + 1 : c0);

@@ -838,15 +838,8 @@ __global__ void head_bwd2_reduce_kernel(const float *__restrict__ part, int A, i
 }
 
 // np.random.choice(n, p=pi): cdf = cumsum(p); cdf /= cdf[-1]; searchsorted(cdf, u, 'right')
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 __device__ __forceinline__ int sample_action(const float *pi, int na, unsigned long long seed, unsigned long long step, long long idx) {
-    const unsigned long long h = splitmix64(splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull)) + (unsigned long long)idx);
-    const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);
+    const double u = uniform01(seed, step, (unsigned long long)idx);
     double cdf[kOut], sacc = 0.0;
     for (int k = 0; k < na; ++k) { sacc += (double)pi[k]; cdf[k] = sacc; }
     int ans = na - 1;
@@ -1141,8 +1134,7 @@ policy_fwd_fc_mfma_kernel(const float *__restrict__ params, Layout lay, const in
             if (k == km) mine = sacc;
         }
         const long long idx = (long long)(e0 + hr) * lay.A + a;
-        const unsigned long long hh = splitmix64(splitmix64(seed ^ (step * 0xD1B54A32D192ED03ull)) + (unsigned long long)idx);
-        const double uu = (double)(hh >> 11) * (1.0 / 9007199254740992.0);
+        const double uu = uniform01(seed, step, (unsigned long long)idx);
         const bool below = hc < 8 && km < na && uu < mine / sacc;          // searchsorted(cdf / cdf[-1], u, 'right'): first k with u < cdf_k
         const unsigned long long bal = __ballot(below);
         const unsigned rowbits = (unsigned)((bal >> row0) & 0xFFull);

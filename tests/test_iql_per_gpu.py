@@ -1,5 +1,5 @@
 """GPU tests of the opt-in prioritized replay of the Q-learners ([MODEL_CONFIG] prioritized_replay / per_alpha / per_beta / per_eps;
-include/tsc.h tsc_iql_set_per; csrc/tsc_iql.hip iql_per_sample_kernel, iql_per_update_kernel, iql_per_add_kernel, iql_td_per_kernel and
+include/tsc.h tsc_iql_set_per; csrc/tsc_iql.hip iql_per_sample_kernel, iql_per_update_kernel, iql_per_add_kernel, iql_td_kernel<true> and
 csrc/tsc_iql_fused.h iql_fused_grad_kernel<.., true, true>) against the float64 restatement of tests/iql_per_oracle.py.
 
 Shapes: tests/test_iql_target_gpu.py::CASES, the smallest at which each gradient path can go wrong, plus two IQL-LR rings for the sampler
