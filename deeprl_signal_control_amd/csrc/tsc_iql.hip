@@ -225,6 +225,66 @@ __global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, c
     }
 }
 
+// ---- dueling head (tsc_iql_set_dueling; Wang et al. 2016), grouped-GEMM path ----------------------------------------------------
+// The head's eight outputs of a row, out = X2 Wq + bq as q_forward leaves them, in place:  Q[j] = V + A_j - (1 / n_a) sum_{k < n_a} A_k for
+// j < n_a with A = out[0 .. n_a) and V = out[7]; columns >= n_a stay (every reader masks them with k < n_a).  Q [A][rows][8].
+__global__ void iql_duel_combine_kernel(float *Q, const int *n_act, long long rows, int A) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)A * rows) return;
+    const int na = n_act[i / rows];
+    float *q = Q + i * kQ;
+    float s = 0.f;
+    for (int k = 0; k < na; ++k) s += q[k];
+    const float base = q[kQ - 1] - s * (1.f / (float)na);
+    for (int k = 0; k < na; ++k) q[k] = base + q[k];
+}
+
+// iql_td_kernel over the combined Q of a dueling handle: the same TD error, loss and |delta|, and the DENSE dQ row the head's backward
+// needs -- g (delta_ja - 1 / n_a) for j < n_a, g at the value column 7, 0 between.  Always weighted (w = 1 on every row when prioritized
+// replay is off), so there is one dueling form.
+__global__ void iql_td_duel_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done, const int *n_act,
+                                   const float *__restrict__ w, long long R, int A, float gamma, float *dQ, float *__restrict__ td,
+                                   double *stats) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    float l = 0.f;
+    int a = 0;
+    if (i < (long long)A * R) {
+        a = (int)(i / R);
+        const int na = n_act[a];
+        const float inv_na = 1.f / (float)na;
+        const float r = rew[i];
+        const float tq = done[i] ? r : r + gamma * q1[i];
+        const int k0 = act[i];
+        const float d = Q[i * kQ + k0] - tq, wi = w[i];
+        const float g = 2.0f * d * wi / (float)R;
+        float row[kQ];
+#pragma unroll
+        for (int k = 0; k < kQ; ++k) {
+            const float off = k < na ? -inv_na : k == kQ - 1 ? 1.f : 0.f;
+            row[k] = g * (k == k0 ? 1.f + off : off);
+        }
+        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = make_float4(row[0], row[1], row[2], row[3]);
+        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = make_float4(row[4], row[5], row[6], row[7]);
+        td[i] = fabsf(d);
+        l = d * d * wi / (float)R;
+    }
+    // (the per-agent loss sum of iql_td_kernel)
+    const int a0 = __shfl(a, 0, 64);
+    const bool uni = __all(a == a0 || i >= (long long)A * R);
+    if (uni) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
+        if ((threadIdx.x & 63) == 0 && l != 0.f) atomicAdd(&stats[a0 * 2], (double)l);
+    } else if (l != 0.f) {
+        atomicAdd(&stats[a * 2], (double)l);
+    }
+}
+
+__global__ void iql_fill_kernel(float *x, long long n, float v) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = v;
+}
+
 // ---- prioritized replay (tsc_iql_set_per; proportional, Schaul et al. 2016) -----------------------------------------------------
 // Stored priorities prio [E][A][cap] (already (|delta| + eps)^alpha, contiguous per ring: the sampler reads one whole ring at a time)
 // and the rings' running maxima qmax [E][A].
@@ -445,13 +505,17 @@ struct QPlan {
     QKernel<const float *> grad_y;                            // the rows' TD targets come from target[]
     QKernel<const float *, const float *, float *> grad_yw;   // ... and their importance weights; |delta| out
     QKernel<const float *, float *, int *> target[2];         // [0] max, [1] Double DQN (two weight images)
+    // the dueling head's (tsc_iql_set_dueling): always the two-launch route, the gradient always with weights (1 without prioritized replay)
+    QKernel<const float *, int, double, unsigned long long, unsigned long long, int, float *, float *, int *, QDuel> act_duel;
+    QKernel<const float *, const float *, float *, QDuel> grad_duel;
+    QKernel<const float *, float *, int *, QDuel> target_duel[2];
     int S = 0, cps = 0;           // row splits per agent (workgroups = A S); 64-row chunks per split
-    struct Entry { const void *fn; int lds; } entries[8] = {};     // (six in use)
+    struct Entry { const void *fn; int lds; } entries[12] = {};    // (ten in use)
     int n_entries = 0;
 
     template <class... Args> void set(QKernel<Args...> &k, void (*fn)(QFusedArgs, Args...), int lds) {
         k.fn = fn; k.lds = lds;
-        assert(n_entries < 8);
+        assert(n_entries < 12);
         entries[n_entries++] = {(const void *)fn, lds};
     }
     template <int NM1> static QPlan make() {
@@ -463,6 +527,10 @@ struct QPlan {
         P.set(P.grad_yw, iql_fused_grad_kernel<NM1, 8, true, true, const float *, const float *, float *>, grd);
         P.set(P.target[0], iql_fused_target_kernel<NM1, 8, false>, fwd);
         P.set(P.target[1], iql_fused_target_kernel<NM1, 8, true>, 2 * fwd);
+        P.set(P.act_duel, iql_fused_act_kernel<NM1, 8, QDuel>, fwd);
+        P.set(P.grad_duel, iql_fused_grad_kernel<NM1, 8, true, true, const float *, const float *, float *, QDuel>, QFusedLds<NM1>::duel_floats * 4);
+        P.set(P.target_duel[0], iql_fused_target_kernel<NM1, 8, false, QDuel>, fwd);
+        P.set(P.target_duel[1], iql_fused_target_kernel<NM1, 8, true, QDuel>, 2 * fwd);
         return P;
     }
 };
@@ -505,6 +573,10 @@ struct tsc_iql {
     double per_alpha = 0, per_eps = 0, per_beta = 1.0;
     float *prio = nullptr, *qmax = nullptr, *w = nullptr, *td = nullptr;
     bool per_valid = false;       // a compute_grads ran on the handle while prioritized replay was armed
+    // dueling head (tsc_iql_set_dueling): column 7 of Wq | bq is the value stream; the weights of a step without prioritized replay [A][R], all 1
+    int duel = 0;
+    float *w_one = nullptr;
+    std::vector<int> n_act_host;
 };
 
 namespace {
@@ -560,6 +632,12 @@ template <class T> hipError_t alloc_once(tsc_iql *h, T **field, long long count,
     return *field ? hipSuccess : h->bufs.alloc(field, count, zero);
 }
 
+// dueling handles: the head's outputs Q [A][rows][8] -> combined values, in place, behind the q_forward that wrote them
+void duel_combine(tsc_iql *h, float *Q, long long rows) {
+    const long long n = (long long)h->lay.A * rows;
+    hipLaunchKernelGGL(iql_duel_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, Q, h->n_act, rows, h->lay.A);
+}
+
 size_t per_sample_lds(const tsc_iql *h) { return sizeof(float) * kPerWaves * per_wave_floats((int)h->cap); }
 
 }  // namespace
@@ -606,6 +684,7 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
     }
     TSC_HIP(h->bufs.upload(&h->rowrange, rr.data(), rr.size()));
     TSC_HIP(h->bufs.upload(&h->n_act, cfg->n_act, L.A));
+    h->n_act_host.assign(cfg->n_act, cfg->n_act + L.A);
     const long long E = n_env, A = L.A, R = E * h->B, per = A * L.SMAX;
     TSC_HIP(h->bufs.alloc(&h->params, h->nparam, true)); TSC_HIP(h->bufs.alloc(&h->grads, h->nparam, true));
     TSC_HIP(h->bufs.alloc(&h->m1, h->nparam, true)); TSC_HIP(h->bufs.alloc(&h->m2, h->nparam, true));
@@ -721,13 +800,19 @@ int tsc_iql_forward(tsc_iql *h, const float *obs, float *q_out, int32_t *action,
     if (h->fused) {
         QFusedArgs fa = fused_args(h, 0);
         tsc::ProfScope ps(tsc::KID_IQL_ACT, h->stream);
-        h->plan.act.launch((unsigned)(L.A * ((h->E + 63) / 64)), h->stream, fa, obs, (int)mode, eps, (unsigned long long)seed,
-                           (unsigned long long)step, L.AMAX, h->Qe, q_out, action);
+        const unsigned grid = (unsigned)(L.A * ((h->E + 63) / 64));
+        if (h->duel)
+            h->plan.act_duel.launch(grid, h->stream, fa, obs, (int)mode, eps, (unsigned long long)seed, (unsigned long long)step, L.AMAX, h->Qe,
+                                    q_out, action, QDuel{});
+        else
+            h->plan.act.launch(grid, h->stream, fa, obs, (int)mode, eps, (unsigned long long)seed, (unsigned long long)step, L.AMAX, h->Qe,
+                               q_out, action);
         TSC_HIP(hipGetLastError());
         return 0;
     }
     // obs [E][A][SMAX]: agent a's rows start at a * SMAX with row stride A * SMAX
     if (q_forward(h, h->params, obs, L.SMAX, L.A * L.SMAX, h->E, h->X1e, h->X2e, h->Qe)) return tsc::fail("tsc_iql_forward: gemm launch failed");
+    if (h->duel) duel_combine(h, h->Qe, h->E);
     const int tot = h->E * L.A;
     hipLaunchKernelGGL(iql_act_kernel, dim3((tot + 255) / 256), dim3(256), 0, h->stream, h->Qe, h->n_act, h->E, L.A, L.AMAX,
                        (int)mode, eps, (unsigned long long)seed, (unsigned long long)step, q_out, action);
@@ -800,7 +885,8 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
     const bool armed = h->tgt_period > 0;                    // Q(s') from the frozen copy
     const bool dbl = armed && h->tgt_double;                 // ... at the online net's first maximum
     const float *tp = armed ? h->tparams : h->params;        // the net behind the TD targets
-    const bool two_launch = armed || per;                    // fused path: the TD targets in a launch of their own, else inside the gradient's
+    const bool duel = h->duel != 0;                          // dueling head: combined Q everywhere, dense dQ
+    const bool two_launch = armed || per || duel;            // fused path: the TD targets in a launch of their own, else inside the gradient's
     TSC_HIP(hipMemsetAsync(h->stats, 0, sizeof(double) * A * 2, st));
     if (given) {        // (e.g. the reference's random.sample); the gather clamps every index into [0, size)
         TSC_HIP(hipMemcpyAsync(h->idx, idx_dev, sizeof(int) * E * A * h->B, hipMemcpyDeviceToDevice, st));
@@ -820,7 +906,7 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
             hipLaunchKernelGGL(iql_sample_kernel, dim3((unsigned)((E * A + 127) / 128)), dim3(128), 0, st, (int)E, (int)A, h->B, size,
                                (unsigned long long)seed, (unsigned long long)update_index, h->idx);
     }
-    if (armed) h->y_valid = true;
+    if (armed || duel) h->y_valid = true;
     if (h->fused) {
         const QPlan &P = h->plan;
         const QFusedArgs fa = fused_args(h, size);
@@ -829,11 +915,13 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
             // (prioritized replay always takes this route; without a target network tp is the parameters themselves)
             {
                 tsc::ProfScope ps(tsc::KID_IQL_TARGET, st);
-                P.target[dbl].launch(grid, st, fa, tp, h->y, h->astar);
+                if (duel) P.target_duel[dbl].launch(grid, st, fa, tp, h->y, h->astar, QDuel{});
+                else P.target[dbl].launch(grid, st, fa, tp, h->y, h->astar);
             }
             TSC_HIP(hipGetLastError());
             tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
-            if (per) P.grad_yw.launch(grid, st, fa, h->y, h->w, h->td);
+            if (duel) P.grad_duel.launch(grid, st, fa, h->y, per ? h->w : h->w_one, h->td, QDuel{});
+            else if (per) P.grad_yw.launch(grid, st, fa, h->y, h->w, h->td);
             else P.grad_y.launch(grid, st, fa, h->y);
         } else {
             tsc::ProfScope ps(tsc::KID_IQL_GRAD, st);
@@ -853,14 +941,20 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
     // Q(s') first (its activations are not needed afterwards), then Q(s) with the activations the backward pass reads
     // (armed: Q(s') comes from the frozen copy; Double DQN adds the online net's Q(s'), whose first maximum picks the target's value)
     if (q_forward(h, tp, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
+    if (duel) duel_combine(h, h->Q, R);
     if (dbl) {
         if (q_forward(h, h->params, h->S1, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q2)) return tsc::fail("gemm launch failed");
+        if (duel) duel_combine(h, h->Q2, R);
         hipLaunchKernelGGL(iql_qsel_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q2, h->Q, h->n_act, R, (int)A, h->q1, h->astar);
     } else {
         hipLaunchKernelGGL(iql_qmax_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->n_act, R, (int)A, h->q1);
     }
     if (q_forward(h, h->params, h->S, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
-    if (per)
+    if (duel) {
+        duel_combine(h, h->Q, R);
+        hipLaunchKernelGGL(iql_td_duel_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
+                           h->n_act, per ? h->w : h->w_one, R, (int)A, (float)h->gamma, h->dQ, h->td, h->stats);
+    } else if (per)
         hipLaunchKernelGGL(iql_td_kernel<true>, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
                            h->w, R, (int)A, (float)h->gamma, h->dQ, h->td, h->stats);
     else
@@ -986,7 +1080,7 @@ int tsc_iql_get_target_params(tsc_iql *h, float *p) {
 
 int tsc_iql_debug_targets(tsc_iql *h, float *y_host, int32_t *astar_host) {
     if (!h || !y_host) return tsc::fail("tsc_iql_debug_targets: bad arguments");
-    if (!h->tgt_period || !h->y_valid) return tsc::fail("tsc_iql_debug_targets: no tsc_iql_compute_grads on an armed handle yet");
+    if ((!h->tgt_period && !h->duel) || !h->y_valid) return tsc::fail("tsc_iql_debug_targets: no tsc_iql_compute_grads on an armed handle yet");
     const size_t AR = (size_t)h->lay.A * h->E * h->B;
     TSC_HIP(hipStreamSynchronize(h->stream));
     if (h->fused) {
@@ -1084,6 +1178,35 @@ int tsc_iql_debug_per(tsc_iql *h, float *w_host, float *td_host) {
     TSC_HIP(hipStreamSynchronize(h->stream));
     TSC_HIP(hipMemcpy(w_host, h->w, sizeof(float) * AR, hipMemcpyDeviceToHost));
     TSC_HIP(hipMemcpy(td_host, h->td, sizeof(float) * AR, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tsc_iql_set_dueling(tsc_iql *h, int32_t enable) {
+    if (!h || (enable != 0 && enable != 1)) return tsc::fail("tsc_iql_set_dueling: bad arguments");
+    if (enable != h->duel) h->y_valid = false;
+    if (!enable) { h->duel = 0; return 0; }       // back to the kernels of a handle that was never armed
+    const QLayout &L = h->lay;
+    if (!L.dqn) return tsc::fail("tsc_iql_set_dueling: kind must be 1 (dqn); a linear Q with a value column spans the same functions");
+    for (int a = 0; a < L.A; ++a)
+        if (h->n_act_host[a] > kQ - 1)
+            return tsc::fail("tsc_iql_set_dueling: agent %d has %d actions > %d: column %d of the head is the value stream", a, h->n_act_host[a],
+                             kQ - 1, kQ - 1);
+    const long long AR = (long long)L.A * h->E * h->B;
+    TSC_HIP(hipSetDevice(h->device));
+    if (!h->w_one) {
+        TSC_HIP(h->bufs.alloc(&h->w_one, AR, false));
+        hipLaunchKernelGGL(iql_fill_kernel, dim3((unsigned)((AR + 255) / 256)), dim3(256), 0, h->stream, h->w_one, AR, 1.0f);
+        TSC_HIP(hipGetLastError());
+    }
+    TSC_HIP(alloc_once(h, &h->td, AR));
+    if (h->fused) TSC_HIP(alloc_once(h, &h->y, AR));
+    h->duel = 1;
+    return 0;
+}
+
+int tsc_iql_get_dueling(tsc_iql *h, int32_t *enabled) {
+    if (!h || !enabled) return tsc::fail("tsc_iql_get_dueling: bad arguments");
+    *enabled = h->duel;
     return 0;
 }
 

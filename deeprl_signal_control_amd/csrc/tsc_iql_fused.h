@@ -75,6 +75,8 @@ struct QFusedLds {
     static constexpr int oS = oD2 + kFH2 * kFLd;          // [kFSF][kFLd]
     static constexpr int oG = oS + kFSF * kFLd;           // g[64] | action[64]
     static constexpr int grad_floats = oG + 128;
+    static constexpr int oU = grad_floats;                // u[64]: the dueling gradient kernel only (q_duel_u)
+    static constexpr int duel_floats = oU + kFH2;
 };
 
 template <int NM1>
@@ -124,6 +126,7 @@ struct QW1 {
 
 // TAG: the armed handles' kernels take instantiations of their own (1: target network, 2: prioritized replay): how the compiler inlines the lambdas below
 // depends on how many callers an instantiation has, and the default kernels must compile to what they compiled to without them
+// (3: the dueling head's kernels)
 template <int NB, int NM1, int NMW, int TAG = 0>
 __device__ __forceinline__ void q_nets(const QW1<NM1, NMW> &w1, const float4 (&s)[NB][3], const float *sm, const QRanges &rg, int m, int kq,
                                        f32x4 (&X1)[NB][NM1], f32x4 (&X2)[NB][4], f32x4 (&q)[NB], long long *fst = nullptr) {
@@ -310,16 +313,53 @@ __device__ __forceinline__ QSlot q_slot_of(const QFusedArgs &p, int a, int wave,
 // PER (prioritized replay, tsc_iql_set_per; always with TGT; QPlan::grad_yw): <.., true, true, const float *, const float *, float *>(p, y, w, td)
 // -- the row's importance weight w [A][R] scales its gradient and its loss term, and the kq == 0 lanes store |delta| of the valid rows in
 // td [A][R] for the priority write-back.
+// DUEL (dueling head, tsc_iql_set_dueling; always with TGT and PER's arguments, w = 1 on every row when prioritized replay is off;
+// QPlan::grad_duel): <.., true, true, const float *, const float *, float *, QDuel>(p, y, w, td, {}) -- the head's eight outputs are
+// combined (q_duel) before Q(s)[a] is taken, dQ is dense: g (delta_ja - 1 / n_a) on the advantage columns j < n_a, g on the value column 7,
+// so dX2 = g (Wq[:, a] + u) relu'(X2) with the agent's u = Wq[:, 7] - mean_{k < n_a} Wq[:, k] staged in LDS, and phase B's dQ operand and dbq
+// follow the same rule.  The empty trailing argument picks the instantiation the way the other armed variants' arguments pick theirs.
+struct QDuel {};
 __device__ __forceinline__ const float *q_targets_of() { return nullptr; }
 __device__ __forceinline__ const float *q_targets_of(const float *y) { return y; }
 __device__ __forceinline__ const float *q_targets_of(const float *y, const float *, float *) { return y; }
 __device__ __forceinline__ const float *q_weights_of(const float *, const float *w, float *) { return w; }
 __device__ __forceinline__ float *q_tderr_of(const float *, const float *, float *td) { return td; }
+__device__ __forceinline__ const float *q_targets_of(const float *y, const float *, float *, QDuel) { return y; }
+__device__ __forceinline__ const float *q_weights_of(const float *, const float *w, float *, QDuel) { return w; }
+__device__ __forceinline__ float *q_tderr_of(const float *, const float *, float *td, QDuel) { return td; }
+
+// The dueling head on the eight outputs of one row as q_nets leaves them -- lane (n, kq < 2) holds out[4 kq + i], V = out[7] is register 3
+// of lane (n, 1), a lane group that holds no action when n_a <= 4:  Q[j] = V + A_j - (1 / n_a) sum_{k < n_a} A_k for j < n_a, the other
+// registers stay as they are.  4 kq + i < na is a predicate: the registers are never indexed by a run-time value.
+__device__ __forceinline__ f32x4 q_duel(f32x4 q, int na, float inv_na, int n, int kq) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) if (kq < 2 && 4 * kq + i < na) s += q[i];
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    const float v = __shfl(q[3], 16 + n, 64);
+    const float base = v - s * inv_na;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) if (kq < 2 && 4 * kq + i < na) q[i] = base + q[i];
+    return q;
+}
+// u[r] = Wq[r][7] - (1 / n_a) sum_{k < n_a} Wq[r][k] of one agent into LDS (threads [0, 64); read behind the weights' barrier)
+__device__ __forceinline__ void q_duel_u(const float *__restrict__ P, const QFusedArgs &p, int na, float inv_na, float *u, int tid) {
+    if (tid < kFH2) {
+        const float *wr = P + p.oWq + tid * 8;
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) if (k < na) s += wr[k];
+        u[tid] = wr[7] - s * inv_na;
+    }
+}
 
 template <int NM1, int NMW, bool TGT = false, bool PER = false, class... Y>
 __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y... y_arg) {
-    static_assert(sizeof...(Y) == (PER ? 3 : TGT ? 1 : 0), "the armed variants take the per-row targets (and weights, |delta|), the default one nothing");
+    constexpr bool DUEL = (std::is_same_v<Y, QDuel> || ...);
+    static_assert(sizeof...(Y) == (PER ? 3 : TGT ? 1 : 0) + DUEL, "the armed variants take the per-row targets (and weights, |delta|), the default one nothing");
     static_assert(TGT || !PER, "prioritized replay takes the two-launch route");
+    static_assert(PER || !DUEL, "the dueling variant takes the weights and |delta| (w = 1 without prioritized replay)");
     using LD = QFusedLds<NM1>;
     constexpr int H1 = LD::H1;
     extern __shared__ __attribute__((aligned(16))) float q_smem[];
@@ -331,6 +371,8 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
     const int na = p.n_act[a];
     const QRanges rg = q_ranges(p.n_wave[a], p.n_wait[a]);
     q_stage_weights<NM1>(P, p, sm, tid, 256);
+    [[maybe_unused]] const float inv_na = DUEL ? 1.f / (float)na : 0.f;
+    if constexpr (DUEL) q_duel_u(P, p, na, inv_na, sm + LD::oU, tid);
     QW1<NM1, NMW> w1;
     q_load_w1<NM1, NMW>(P, p, rg, n, kq, w1);
 
@@ -427,12 +469,13 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
                 if constexpr (!TGT) ss[0][qp] = cur.s1[qp];
                 ss[NB - 1][qp] = cur.s0[qp];
             }
-            q_nets<NB, NM1, NMW, PER ? 2 : TGT ? 1 : 0>(w1, ss, sm, rg, n, kq, XX1, XX2, qq, (stamp_wg && c == c0 + 2) ? p.dbg + 16 * wave : nullptr);
+            q_nets<NB, NM1, NMW, DUEL ? 3 : PER ? 2 : TGT ? 1 : 0>(w1, ss, sm, rg, n, kq, XX1, XX2, qq, (stamp_wg && c == c0 + 2) ? p.dbg + 16 * wave : nullptr);
         }
         QSTAMP(1);
         f32x4 (&X1)[NM1] = XX1[NB - 1];
         f32x4 (&X2)[4] = XX2[NB - 1];
-        const f32x4 q = qq[NB - 1];
+        f32x4 q = qq[NB - 1];
+        if constexpr (DUEL) q = q_duel(q, na, inv_na, n, kq);
         float q1 = -INFINITY;
         if constexpr (!TGT) {
 #pragma unroll
@@ -493,6 +536,8 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
+                    if constexpr (DUEL) D2[t][i] = X2[t][i] > 0.f ? g * (wq[(16 * t + i) * kFLq] + sm[LD::oU + 16 * t + 4 * kq + i]) : 0.f;
+                    else
                     D2[t][i] = X2[t][i] > 0.f ? g * wq[(16 * t + i) * kFLq] : 0.f;
                     d2s[(16 * t + i) * kFLd] = D2[t][i];
                 }
@@ -537,8 +582,14 @@ __global__ void __launch_bounds__(256, 1) iql_fused_grad_kernel(QFusedArgs p, Y.
                 o.bv[0] = bv4.x; o.bv[1] = bv4.y; o.bv[2] = bv4.z; o.bv[3] = bv4.w;
                 const float4 gv = *reinterpret_cast<const float4 *>(sm + LD::oG + 16 * tp + 4 * kq);
                 const int4 tv = *reinterpret_cast<const int4 *>(sm + LD::oG + 64 + 16 * tp + 4 * kq);
+                if constexpr (DUEL) {                   // column n of the dense dQ row: advantage j < n_a | dead | value 7
+                    const float off = n < na ? -inv_na : n == 7 ? 1.f : 0.f;
+                    o.qv[0] = gv.x * (tv.x == n ? 1.f + off : off); o.qv[1] = gv.y * (tv.y == n ? 1.f + off : off);
+                    o.qv[2] = gv.z * (tv.z == n ? 1.f + off : off); o.qv[3] = gv.w * (tv.w == n ? 1.f + off : off);
+                } else {
                 o.qv[0] = tv.x == n ? gv.x : 0.f; o.qv[1] = tv.y == n ? gv.y : 0.f;
                 o.qv[2] = tv.z == n ? gv.z : 0.f; o.qv[3] = tv.w == n ? gv.w : 0.f;
+                }
                 const float4 xv4 = *reinterpret_cast<const float4 *>(x2a + 16 * tp);
                 o.xv[0] = xv4.x; o.xv[1] = xv4.y; o.xv[2] = xv4.z; o.xv[3] = xv4.w;
 #pragma unroll
@@ -721,10 +772,15 @@ __global__ void iql_fused_reduce_kernel(const float *__restrict__ ws, const floa
 }
 
 // ---- IQL.forward (agents/models.py:332-348) in one launch: the same nets on the E acting rows + the action choice -------
-template <int NM1, int NMW>
+// D = QDuel (tsc_iql_set_dueling; QPlan::act_duel): an empty trailing argument, as the gradient kernel's, picks the instantiation that combines
+// the head's outputs with q_duel before anything reads them; the default instantiation has no such argument.
+template <int NM1, int NMW, class... D>
 __global__ void __launch_bounds__(256, 1) iql_fused_act_kernel(QFusedArgs p, const float *__restrict__ obs, int mode, double eps,
                                                                unsigned long long seed, unsigned long long step, int AMAX,
-                                                               float *__restrict__ Qe, float *__restrict__ q_out, int *__restrict__ action) {
+                                                               float *__restrict__ Qe, float *__restrict__ q_out, int *__restrict__ action,
+                                                               D...) {
+    static_assert(sizeof...(D) <= 1 && (std::is_same_v<D, QDuel> && ...), "iql_fused_act_kernel<NM1, NMW> or <NM1, NMW, QDuel>");
+    constexpr bool DUEL = sizeof...(D) == 1;
     extern __shared__ __attribute__((aligned(16))) float q_smem[];
     float *sm = q_smem;
     const int a = blockIdx.x % p.A, blk = blockIdx.x / p.A;
@@ -747,9 +803,10 @@ __global__ void __launch_bounds__(256, 1) iql_fused_act_kernel(QFusedArgs p, con
     f32x4 X1[1][NM1], X2[1][4], qo[1];
     {
         float4 ss[1][3] = {{s[0], s[1], s[2]}};
-        q_nets<1, NM1, NMW>(w1, ss, sm, rg, n, kq, X1, X2, qo);
+        q_nets<1, NM1, NMW, DUEL ? 3 : 0>(w1, ss, sm, rg, n, kq, X1, X2, qo);
     }
-    const f32x4 q = qo[0];
+    f32x4 q = qo[0];
+    if constexpr (DUEL) q = q_duel(q, na, 1.f / (float)na, n, kq);
     // the row's eight Q values into its kq == 0 lane
     float qv[8];
 #pragma unroll
@@ -797,9 +854,13 @@ __global__ void __launch_bounds__(256, 1) iql_fused_act_kernel(QFusedArgs p, con
 // Forward-only, the gradient kernel's shape: A x S workgroups, each walking its cps 64-row chunks with the weights staged once (the
 // frozen copy's W2 | Wq | biases in LDS and its W1 in registers; with DBL a second image and a second W1 for the online net, which
 // runs on the same observation registers), rows requested one chunk ahead.
-template <int NM1, int NMW, bool DBL>
+// D = QDuel (tsc_iql_set_dueling; QPlan::target_duel, the act kernel's device): both nets' outputs are combined with q_duel first, so the
+// maximum, a* and the picked value are those of the combined values.
+template <int NM1, int NMW, bool DBL, class... D>
 __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, const float *__restrict__ tparams, float *__restrict__ y,
-                                                                  int *__restrict__ astar) {
+                                                                  int *__restrict__ astar, D...) {
+    static_assert(sizeof...(D) <= 1 && (std::is_same_v<D, QDuel> && ...), "iql_fused_target_kernel<.., DBL> or <.., DBL, QDuel>");
+    constexpr bool DUEL = sizeof...(D) == 1;
     using LD = QFusedLds<NM1>;
     extern __shared__ __attribute__((aligned(16))) float q_smem[];
     float *smT = q_smem, *smO = q_smem + LD::fwd_floats;
@@ -808,6 +869,7 @@ __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, 
     const int n = lane & 15, kq = lane >> 4;
     const float *PT = tparams + (long long)a * p.stride, *PO = p.params + (long long)a * p.stride;
     const int na = p.n_act[a];
+    [[maybe_unused]] const float inv_na = DUEL ? 1.f / (float)na : 0.f;
     const QRanges rg = q_ranges(p.n_wave[a], p.n_wait[a]);
     q_stage_weights<NM1>(PT, p, smT, tid, 256);
     QW1<NM1, NMW> w1t;
@@ -854,12 +916,14 @@ __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, 
 #pragma unroll
         for (int qp = 0; qp < 3; ++qp) ss[0][qp] = cur.s1[qp];
         f32x4 X1[1][NM1], X2[1][4], qt[1];
-        q_nets<1, NM1, NMW, 1>(w1t, ss, smT, rg, n, kq, X1, X2, qt);
+        q_nets<1, NM1, NMW, DUEL ? 3 : 1>(w1t, ss, smT, rg, n, kq, X1, X2, qt);
+        if constexpr (DUEL) qt[0] = q_duel(qt[0], na, inv_na, n, kq);
         float q1 = -INFINITY;
         int best = 8;
         if constexpr (DBL) {
             f32x4 qo[1];
-            q_nets<1, NM1, NMW, 1>(w1o, ss, smO, rg, n, kq, X1, X2, qo);
+            q_nets<1, NM1, NMW, DUEL ? 3 : 1>(w1o, ss, smO, rg, n, kq, X1, X2, qo);
+            if constexpr (DUEL) qo[0] = q_duel(qo[0], na, inv_na, n, kq);
             // first maximum of the online values over this row's four lanes (actions 4 kq + i, kq < 2), the target value riding along
             float bv = -INFINITY;
 #pragma unroll

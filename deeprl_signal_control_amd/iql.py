@@ -24,7 +24,8 @@ IQL_DEFAULTS = dict(max_grad_norm=40.0, gamma=0.99, lr_init=1e-4, lr_decay='cons
                     epsilon_min=0.01, epsilon_decay='linear', epsilon_ratio=0.5, num_fc=128, num_h=64, batch_size=20,
                     buffer_size=1000.0, reward_norm=3000.0, reward_clip=2.0,     # config/config_iqld_large.ini
                     target_update=0, double_q=0,    # opt-in, not the reference's: target network refreshed every N Adam steps / Double DQN
-                    prioritized_replay=0, per_alpha=0.6, per_beta=0.4, per_eps=0.01)   # opt-in: proportional prioritized replay (Schaul et al. 2016)
+                    prioritized_replay=0, per_alpha=0.6, per_beta=0.4, per_eps=0.01,   # opt-in: proportional prioritized replay (Schaul et al. 2016)
+                    dueling=0)      # opt-in, IQL-DNN only: dueling head (Wang et al. 2016); with double_q and prioritized_replay the literature's 3DQN
 N_UPDATE = 10                                                                    # agents/models.py:324
 
 
@@ -37,6 +38,18 @@ def target_config(cfg):
     if dbl and not period:
         raise ValueError('double_q = 1 needs target_update > 0: without a target network it is the reference\'s loss under another name')
     return period, dbl
+
+
+def dueling_config(cfg):
+    """dueling of a coerced [MODEL_CONFIG]: 0 is the reference's plain head, 1 the dueling head Q = V + A - mean(A) (include/tsc.h
+    tsc_iql_set_dueling)."""
+    try:
+        on = int(cfg['dueling'])
+    except (TypeError, ValueError):
+        on = None
+    if on not in (0, 1) or on != float(cfg['dueling']):
+        raise ValueError('dueling must be 0 or 1 (got %r)' % (cfg['dueling'],))
+    return on
 
 
 def per_config(cfg):
@@ -103,16 +116,22 @@ def _setup_lib(L):
     L.tsc_iql_get_priorities.argtypes = [vp, vp, vp]
     L.tsc_iql_set_priorities.argtypes = [vp, vp, vp]
     L.tsc_iql_debug_per.argtypes = [vp, vp, vp]
+    L.tsc_iql_set_dueling.argtypes = [vp, C.c_int32]
+    L.tsc_iql_get_dueling.argtypes = [vp, C.POINTER(C.c_int32)]
     L._iql_ready = True
 
 
 class QParamLayout:
     """Flat per-agent layout of csrc/tsc_iql.hip (include/tsc.h tsc_iql_layout) <-> TF-variable-style dicts
-    (q_fcw / q_fct / q_fc_0 / q of agents/policies.py:299-303,355-362)."""
+    (q_fcw / q_fct / q_fc_0 / q of agents/policies.py:299-303,355-362).  dueling: the value stream v_w [H2, 1] / v_b [1] rides in
+    column out_pad - 1 of Wq | bq (include/tsc.h tsc_iql_set_dueling), so the flat layout -- as_tuple() -- is the same with and without it."""
 
-    def __init__(self, n_wave_ls, n_w_ls, n_a_ls, s_max, kind, n_fc0, n_h, out_pad=8):
+    def __init__(self, n_wave_ls, n_w_ls, n_a_ls, s_max, kind, n_fc0, n_h, out_pad=8, dueling=False):
         self.n_wave_ls, self.n_w_ls, self.n_a_ls = list(n_wave_ls), list(n_w_ls), list(n_a_ls)
         self.s_max, self.kind, self.n_fc0, self.out_pad = int(s_max), kind, int(n_fc0), out_pad
+        self.dueling = bool(dueling)
+        if self.dueling and (kind != 'dqn' or max(self.n_a_ls) > out_pad - 1):
+            raise ValueError('the dueling head needs kind dqn and at most %d actions per agent' % (out_pad - 1))
         self.A = len(self.n_a_ls)
         self.ft = self.n_fc0 // 4 if (kind == 'dqn' and max(self.n_w_ls) > 0) else 0
         self.H1 = self.n_fc0 + self.ft if kind == 'dqn' else 0
@@ -141,6 +160,8 @@ class QParamLayout:
         if self.ft:
             sh.update({'fct_w': (nt, self.ft), 'fct_b': (self.ft,)})
         sh.update({'fc0_w': (self.H1, self.H2), 'fc0_b': (self.H2,), 'q_w': (self.H2, na), 'q_b': (na,)})
+        if self.dueling:        # after q: the reference would create fc(h, 'v', 1) behind it, so every other tensor keeps its draw
+            sh.update({'v_w': (self.H2, 1), 'v_b': (1,)})
         return sh
 
     def pack(self, agents):
@@ -151,6 +172,9 @@ class QParamLayout:
             rows = self.H2 if self.kind == 'dqn' else self.s_max
             Wq = np.zeros((rows, self.out_pad), np.float32)
             Wq[:p['q_w'].shape[0], :na] = p['q_w']
+            if self.dueling:
+                Wq[:, self.out_pad - 1] = np.asarray(p['v_w'], np.float32).reshape(rows)
+                f[self.obq + self.out_pad - 1] = np.asarray(p['v_b'], np.float32).reshape(())
             f[self.oWq:self.obq] = Wq.ravel()
             f[self.obq:self.obq + na] = p['q_b']
             if self.kind == 'dqn':
@@ -172,6 +196,8 @@ class QParamLayout:
             rows = self.H2 if self.kind == 'dqn' else self.s_max
             Wq = f[self.oWq:self.obq].reshape(rows, self.out_pad)
             p = {'q_w': Wq[:(rows if self.kind == 'dqn' else nw + nt), :na].copy(), 'q_b': f[self.obq:self.obq + na].copy()}
+            if self.dueling:
+                p.update({'v_w': Wq[:, self.out_pad - 1:].copy(), 'v_b': f[self.obq + self.out_pad - 1:self.obq + self.out_pad].copy()})
             if self.kind == 'dqn':
                 W1 = f[self.oW1:self.ob1].reshape(self.s_max, self.H1); b1 = f[self.ob1:self.oW2]
                 p.update({'fcw_w': W1[:nw, :self.n_fc0].copy(), 'fcw_b': b1[:self.n_fc0].copy()})
@@ -186,8 +212,12 @@ def init_agent_params(layout, rng):
     """Initial Q-net weights of all agents in the reference's variable-creation order (q_fcw, q_fct, q_fc_0, q per agent,
     agents/policies.py:299-303,355-362; ortho_init is called when the variable is created): with
     rng = np.random.RandomState(s) the reference's weights under np.random.seed(s) (tests/test_refnet_oracle.py)."""
-    return [{k: ortho_init(sh, rng) if len(sh) == 2 else np.zeros(sh, np.float32) for k, sh in layout.shapes(a).items()}
-            for a in range(layout.A)]
+    def draw(sh):
+        return ortho_init(sh, rng) if len(sh) == 2 else np.zeros(sh, np.float32)
+    agents = [{k: draw(sh) for k, sh in layout.shapes(a).items() if k not in ('v_w', 'v_b')} for a in range(layout.A)]
+    for a, p in enumerate(agents):      # dueling: the value streams are drawn behind every agent's own tensors, which so keep a plain model's draws
+        p.update({k: draw(sh) for k, sh in layout.shapes(a).items() if k in ('v_w', 'v_b')})
+    return agents
 
 
 class VecIQL:
@@ -203,6 +233,9 @@ class VecIQL:
         self.cfg, self.name, self.model_type = cfg, 'iql', model_type
         self.target_update, self.double_q = target_config(cfg)
         self.prioritized_replay, self.per_alpha, self.per_beta, self.per_eps = per_config(cfg)
+        self.dueling = dueling_config(cfg)
+        if self.dueling and model_type != 'dqn':
+            raise ValueError("dueling = 1 needs model_type 'dqn': a linear Q with a value column spans the same functions")
         self.per_n = 0              # environment steps the beta schedule has counted (backward calls x batch_size, like lr_scheduler.n)
         self.n_agent, self.E = len(n_s_ls), int(n_env)
         self.n_s_ls, self.n_a_ls, self.n_w_ls = list(n_s_ls), list(n_a_ls), list(n_w_ls)
@@ -226,7 +259,10 @@ class VecIQL:
         self._h = h
         lay = (C.c_int64 * 12)()
         _lib.check(L.tsc_iql_layout(h, lay))
-        self.layout = QParamLayout(self.n_wave_ls, self.n_w_ls, self.n_a_ls, self.s_max, model_type, cfg['num_fc'], cfg['num_h'])
+        if self.dueling:            # (refuses more than 7 actions per agent; before the layout, which carries v_w / v_b in column 7)
+            _lib.check(L.tsc_iql_set_dueling(h, 1))
+        self.layout = QParamLayout(self.n_wave_ls, self.n_w_ls, self.n_a_ls, self.s_max, model_type, cfg['num_fc'], cfg['num_h'],
+                                   dueling=bool(self.dueling))
         assert self.layout.as_tuple() == tuple(int(x) for x in lay), 'host / device parameter layouts disagree'
         self.n_param = self.layout.n_param
         f = C.c_int32()
@@ -431,6 +467,8 @@ class VecIQL:
         extra = {'target': self.get_target_flat()} if self.target_update else {}      # an unarmed model's file keeps its keys
         if self.prioritized_replay:     # the beta counter only: the rings are not checkpointed, so neither are their priorities
             extra['per_n'] = np.int64(self.per_n)
+        if self.dueling:                # same layout, another function of it
+            extra['dueling'] = np.int64(1)
         np.savez(os.path.join(model_dir, 'checkpoint-%d.npz' % int(global_step)), params=self.get_flat(), adam_m=m, adam_v=v,
                  layout=np.array(self.layout.as_tuple() + (self.s_max,), np.int64),
                  counters=np.array([t, self.act_step, self.update_step, self.base_seed, self.lr_scheduler.n, self.eps_scheduler.n], np.int64),
@@ -453,6 +491,9 @@ class VecIQL:
         want = self.layout.as_tuple() + (self.s_max,)
         if 'adam_m' not in z.files or tuple(int(x) for x in z['layout']) != want or z['params'].size != self.n_param:
             raise ValueError('checkpoint %s does not fit this model' % save_file)
+        file_dueling = int(z['dueling']) if 'dueling' in z.files else 0
+        if file_dueling != self.dueling:        # column 7 of the head is the value stream in one and unused in the other
+            raise ValueError('checkpoint %s was written with dueling = %d, this model has dueling = %d' % (save_file, file_dueling, self.dueling))
         self.set_flat(z['params'])
         if self.target_update:                  # a file written without a target network: theta- <- theta
             if 'target' in z.files and z['target'].size == self.n_param:

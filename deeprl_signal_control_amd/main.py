@@ -226,6 +226,8 @@ def train(args):
     model = init_model(env, config, total_step, args.envs, seed, args.device)
     if getattr(model, 'prioritized_replay', 0):
         logging.info('Training: prioritized replay, alpha %g, beta %g -> 1, eps %g' % (model.per_alpha, model.per_beta, model.per_eps))
+    if getattr(model, 'dueling', 0):
+        logging.info('Training: dueling head, Q = V + A - mean(A)')
     trainer = VecTrainer(env, model, counter, log_rewards=True)
     data = trainer.run_training(run_test=in_test, output_path=dirs['data'])
     if post_test:                                               # Tester.run_offline (utils.py:324-338)

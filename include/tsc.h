@@ -100,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -558,6 +558,23 @@ int tsc_iql_get_priorities(tsc_iql *h, float *prio_host, float *qmax_host);
 int tsc_iql_set_priorities(tsc_iql *h, const float *prio_host, const float *qmax_host);
 /* Debug / parity access: w and |delta| [A][E * batch_size] of the last tsc_iql_compute_grads / _at on an armed handle.  Synchronises. */
 int tsc_iql_debug_per(tsc_iql *h, float *w_host, float *td_host);
+/* Dueling Q-network head for IQL-DNN (opt-in; Wang et al. 2016; the reference's head is plain).  The parameter layout does not change: with
+ * out[0..7] = X2 Wq + bq the head's eight outputs as every kernel computes them, column 7 of Wq | bq becomes the value stream and
+ *   A_j = out[j] (j < n_a),  V = out[7],  Q[j] = V + A_j - (1 / n_a) sum_{k < n_a} A_k   (j < n_a).
+ * Q replaces out[0 .. n_a) wherever a Q value is used: the greedy / epsilon-greedy / stochastic action choice, q_out (padding stays 0, V
+ * is never exposed), max_j Q(s'), Double DQN's a* (first maximum of the combined online values, evaluated on the combined target values),
+ * Q(s)[a] in the TD error and the |delta| prioritized replay stores.  The loss stays mean(w (Q(s)[a] - stop_grad(y))^2) under every
+ * tsc_iql_set_target / tsc_iql_set_per setting.  Backward, with g = dLoss/dQ[a] of the row: dOut[j] = g (delta_ja - 1 / n_a) for j < n_a,
+ * dOut[7] = g, dOut[j] = 0 for n_a <= j < 7 (those columns of the gradient stay exactly zero), so dX2 = relu'(X2) g (Wq[:, a] + u) with
+ * u = Wq[:, 7] - (1 / n_a) sum_{k < n_a} Wq[:, k], and dWq | dbq contract X2 | 1 against the dense dOut.
+ * enable = 1 arms; it refuses kind = 0 (a linear Q with a value column spans the same functions) and any n_act[a] > 7 (never clamped), and
+ * touches neither parameters nor optimizer state.  The first arming allocates |delta| and a weight vector of ones [A][E * batch_size] (the
+ * dueling kernels always take weights) and, on the fused path, the per-row targets.  On the fused path a dueling step always takes the
+ * two-launch route of tsc_iql_set_target, as prioritized replay does.  enable = 0 disarms: the handle launches what a handle that was never
+ * armed launches.  tsc_iql_forward, tsc_iql_compute_grads / _at and tsc_iql_apply_grads keep their signatures; tsc_iql_debug_targets also
+ * answers on a dueling handle without a target network (a* = -1 unless double_q). */
+int tsc_iql_set_dueling(tsc_iql *h, int32_t enable);
+int tsc_iql_get_dueling(tsc_iql *h, int32_t *enabled);          /* 1 while the dueling head is armed */
 /* Measurement hook of the fused learner (tools/bench_iql.py --stamps): enable != 0 allocates the stamp buffer; the next
  * tsc_iql_compute_grads then records, for every workgroup, its start / end on the 100-MHz wall clock ([64 + 2 b],
  * [64 + 2 b + 1]) and -- in a measurement build with -DTSC_IQL_STAMPS (tools/build_variant.sh; the stamps' branches are kept
