@@ -258,6 +258,7 @@ def _setup_lib(L):
     L.tsc_model_set_stream.argtypes = [vp, vp]
     L.tsc_model_layout.argtypes = [vp, C.POINTER(C.c_int64)]
     L.tsc_model_path.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_model_plan.argtypes = [vp, C.POINTER(C.c_int32)]
     for f in ('tsc_model_set_params', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state'):
         getattr(L, f).argtypes = [vp, vp]
     L.tsc_model_reset_opt_state.argtypes = [vp]
@@ -334,6 +335,10 @@ class VecA2C:
         # FC policy: (rollout forward 2 = policy_fwd_fc_mfma_kernel / 1 = policy_fwd_fc_kernel / 0 = dense GEMMs,
         # update 1 = fused fc_bwd_kernel / 0 = grouped GEMMs); (-1, -1) for the LSTM policy (include/tsc.h tsc_model_path)
         self.fc_path = (int(path[0]), int(path[1]))
+        plan = (C.c_int32 * 6)()
+        _lib.check(L.tsc_model_plan(h, plan))
+        # (rollout forward 0 Dense / 1 Tile / 2 Ws / 3 FcThread / 4 FcMfma, dwxh, dx1w1, fc_bwd, s_fwd, s_upd) (include/tsc.h tsc_model_plan)
+        self.plan = tuple(int(x) for x in plan)
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream(self.device)
             _lib.check(L.tsc_model_set_stream(h, C.c_void_p(self.stream.cuda_stream)))

@@ -168,7 +168,10 @@ __device__ __forceinline__ void q_nets(const QW1<NM1, NMW> &w1, const float4 (&s
     if (NM1 > NMW) {
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) {
-            const int qp = rg.qt0 + qq;                            // wavefront-uniform; qt0 + 1 <= 2 (n_wave <= 32)
+            // wavefront-uniform.  qt0 <= 2 (n_wave <= 32), so qp reaches 3 at n_wave = 32: a group past the staged observation
+            // (s_max <= 48 = three groups).  It reads group 2 below, against weights q_load_w1 zeroed (features >= s_max), and the
+            // gradient side never visits it (qt0 + 1 < qt1 fails); tests/test_layouts_gpu.py, q160_edge, runs this case.
+            const int qp = rg.qt0 + qq;
             float sv[NB][4];
 #pragma unroll
             for (int b_ = 0; b_ < NB; ++b_)

@@ -28,7 +28,7 @@
 //                     the grouped split-K GEMMs of tsc_gemm.h behind TSC_UNFUSED_DX and for other shapes)
 // Which of these a handle runs is decided once, in tsc_model_create: its Plan (forward kernel, the three one-pass update
 // kernels, split counts) follows from the shapes, the LDS and workspace fits and the knobs of INTEGRATION.md section 5, which
-// are read there and nowhere else.  The forward and the update only switch on the plan; tsc_model_path reports it.  The fused
+// are read there and nowhere else.  The forward and the update only switch on the plan; tsc_model_plan / tsc_model_path report it.  The fused
 // kernels exist for the hidden widths of with_fused_width, and each launch derives its template argument from H.
 #include "tsc_common.h"
 #include "tsc_gemm.h"
@@ -2726,7 +2726,7 @@ template <int... W, class F> bool with_width(int H, F &&f) { return ((H == W && 
 template <class F> bool with_fused_width(int H, F &&f) { return with_width<128, 160, 192, 224>(H, f); }
 
 // Which kernels a handle runs: decided once in tsc_model_create from its shapes and the knobs.
-enum class Fwd : int8_t {
+enum class Fwd : int8_t {      // (tsc_model_plan reports the enumerator's value: keep the order)
     Dense,      // grouped GEMMs + lstm_fwd (LSTM) + head_fwd: the shapes no fused forward covers
     Tile,       // LSTM: policy_fwd_fused_kernel, one 64-instance tile per workgroup
     Ws,         // LSTM: policy_fwd_ws_kernel<(H + kL) / 2>, [Wx ; Wh] stationary in registers
@@ -3047,6 +3047,14 @@ int tsc_model_path(tsc_model *m, int32_t out[2]) {
     const Fwd f = m->plan.fwd;
     out[0] = !fc ? -1 : f == Fwd::FcMfma ? 2 : f == Fwd::FcThread ? 1 : 0;
     out[1] = !fc ? -1 : m->plan.fc_bwd ? 1 : 0;
+    return 0;
+}
+
+int tsc_model_plan(tsc_model *m, int32_t out[6]) {
+    if (!m || !out) return tsc::fail("tsc_model_plan: bad arguments");
+    const Plan &P = m->plan;
+    const int32_t v[6] = {(int32_t)P.fwd, P.dwxh, P.dx1w1, P.fc_bwd, P.s_fwd, P.s_upd};
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
     return 0;
 }
 

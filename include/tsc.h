@@ -100,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -347,6 +347,9 @@ int tsc_model_layout(tsc_model *m, int64_t out[12]);
  * per-thread policy_fwd_fc_kernel, 0 for the dense GEMMs + head kernel; out[1] = update, 1 for the fused fc_bwd_kernel (same
  * widths; not with TSC_UNFUSED_DX=1), 0 for the grouped split-K GEMMs.  Both -1 for the LSTM policy. */
 int tsc_model_path(tsc_model *m, int32_t out[2]);
+/* The handle's plan, fixed at create: out[] = {rollout forward (0 Dense, 1 Tile, 2 Ws, 3 FcThread, 4 FcMfma),
+ * dwxh, dx1w1, fc_bwd (0 / 1), s_fwd, s_upd}. */
+int tsc_model_plan(tsc_model *m, int32_t out[6]);
 int tsc_model_set_params(tsc_model *m, const float *params_host);     /* optimizer state untouched */
 int tsc_model_reset_opt_state(tsc_model *m);                         /* RMSProp ms <- 1 (TF1 slot init) */
 int tsc_model_get_params(tsc_model *m, float *params_host);

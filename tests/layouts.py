@@ -1,0 +1,209 @@
+"""Synthetic agent layouts for the learner parity tests -- TEST INFRASTRUCTURE ONLY, host only (no GPU, no library).
+
+Both learners choose their kernels from the shape of the agents (csrc/tsc_model.hip "The plan", csrc/tsc_iql.hip tsc_iql_create); the
+three built-in scenarios visit only a corner of what those choices accept.  A Layout carries exactly what the test helpers read from a
+scenario -- n_agent, n_s_ls, n_a_ls, n_w_ls, n_f_ls, s_max, a_max -- and nothing else: no environment, no scenario tables.  Every
+layout of the two registries exists because of one declared limit ("Supported layouts"); the limit is named
+next to it.
+
+Every layout is uniform the way the reference is: either every agent has wait inputs or none has, and in MA2C every agent has at least
+one fingerprint input.  A mixed layout (some agents with a wait / fingerprint part, some without) has no definition in the oracle or
+the reference -- tower() drops the whole block of an agent whose count is zero while the device keeps the block's bias columns -- and
+is out of scope here.
+
+Routes.  `route[policy]` is what tsc_model_plan must report: LSTM (rollout forward, dwxh, dx1w1), FC (rollout forward, fc_bwd), with
+the forward numbered as in include/tsc.h (0 Dense, 1 Tile, 2 Ws, 3 FcThread, 4 FcMfma).  They follow from the width table and the
+s_max <= 64 gate of the plan; the three that also depend on an LDS budget (obs64 LSTM: Ws or Tile; h96 / h112 FC: FcThread or Dense)
+are the values an MI355X handle reported, recorded here and asserted from then on (RECORDED).
+
+The rollouts of tests/test_layouts_gpu.py are redrawn on the host by forward_inputs / fill_host / iql_transitions below: the same
+RandomState seeds in the same order of draws as tests/test_model_gpu.py::_fill and tests/test_iql_gpu.py, so that
+tests/test_layouts_host.py states conditions about the very samples the GPU tests compare."""
+import contextlib
+
+import numpy as np
+
+
+class Layout:
+    """agents: one (n_wave, n_wait, n_fp, n_a) per agent, observation = [wave | wait | fingerprint] like the environment's."""
+
+    def __init__(self, agents, s_max):
+        self.agents = [tuple(int(x) for x in a) for a in agents]
+        self.n_agent = len(self.agents)
+        self.n_wave_ls = [a[0] for a in self.agents]
+        self.n_w_ls = [a[1] for a in self.agents]
+        self.n_f_ls = [a[2] for a in self.agents]
+        self.n_a_ls = [a[3] for a in self.agents]
+        self.n_s_ls = [a[0] + a[1] + a[2] for a in self.agents]
+        self.s_max, self.a_max = int(s_max), max(self.n_a_ls)
+        assert self.s_max % 4 == 0 and max(self.n_s_ls) <= self.s_max
+        waits, fps = [w > 0 for w in self.n_w_ls], [f > 0 for f in self.n_f_ls]
+        assert all(waits) or not any(waits), 'mixed wait inputs: out of scope (module docstring)'
+        assert all(fps) or not any(fps), 'mixed fingerprint inputs: out of scope (module docstring)'
+
+    def only(self, keep):
+        """The layout of the agents for which keep(n_a) holds (same s_max)."""
+        return Layout([a for a in self.agents if keep(a[3])], self.s_max)
+
+
+# large_grid's ranges (build_scenario prints them): MA2C wave 18-30, wait 6, fingerprint 8-16, five actions; IA2C the same without fingerprints
+_LG_MA2C = [(30, 6, 16, 5), (24, 6, 12, 5), (18, 6, 8, 5), (24, 6, 12, 5), (18, 6, 8, 5)]
+_LG_IA2C = [(30, 6, 0, 5), (24, 6, 0, 5), (18, 6, 0, 5), (24, 6, 0, 5)]
+# real_net's ranges, MA2C: wave 5-34, no wait, fingerprint 1-16, two to six actions
+_RN_MA2C = [(34, 0, 16, 6), (5, 0, 1, 2), (20, 0, 8, 4), (12, 0, 16, 3), (34, 0, 2, 5)]
+
+DENSE, TILE, WS, FC_THREAD, FC_MFMA = 0, 1, 2, 3, 4
+
+
+def _a2c(agent, widths, s_max, agents, lstm, fc, why, wide=False):
+    fw, fp, ft = widths
+    return dict(agent=agent, layout=Layout(agents, s_max), cfg=dict(num_fw=fw, num_fp=fp, num_ft=ft), H=fw + fp + ft,
+                route=dict(lstm=lstm, fc=fc), why=why, wide=wide)
+
+
+# name -> agent kind, widths fw / fp / ft, s_max, agents, LSTM route (forward, dwxh, dx1w1), FC route (forward, fc_bwd), the limit it drives
+A2C_LAYOUTS = {
+    'head8': _a2c('ma2c', (128, 64, 32), 52, [(30, 6, 16, 8), (24, 6, 12, 7), (18, 6, 8, 2), (24, 6, 12, 5), (30, 6, 16, 8)],
+                  (WS, 1, 1), (FC_MFMA, 1), 'full 8-wide head, n_a = 7'),
+    'obs64': _a2c('ma2c', (128, 64, 32), 64, [(40, 8, 16, 5), (37, 8, 16, 3), (2, 1, 1, 2), (30, 6, 12, 8)],
+                  (WS, 1, 1), (FC_MFMA, 1), 'full fourth 16-row obs tile; an agent with 4 inputs beside one with 64', wide=True),
+    # s_max > 64: every kernel that stages the observation falls back.  dwxh reads X1 / h_prev / dZ only, never the observation, and stays.
+    'obs68': _a2c('ia2c', (128, 0, 32), 68, [(60, 8, 0, 5), (57, 8, 0, 4), (9, 1, 0, 2)],
+                  (DENSE, 1, 0), (DENSE, 0), 'narrow_obs false: dense forward, grouped first-layer update', wide=True),
+    'tiny': _a2c('ia2c', (128, 0, 32), 4, [(3, 1, 0, 2), (1, 1, 0, 2), (2, 1, 0, 3)],
+                 (WS, 1, 1), (FC_MFMA, 1), 'one partial obs tile, K = 4 GEMMs'),
+    'edges160': _a2c('ma2c', (100, 28, 32), 52, _LG_MA2C, (WS, 1, 1), (FC_MFMA, 1), 'H = 160, block edges at columns 100 and 128'),
+    'edges224': _a2c('ma2c', (150, 42, 32), 52, _LG_MA2C, (WS, 1, 1), (FC_MFMA, 1), 'H = 224, block edges at columns 150 and 192'),
+    'edges128': _a2c('ia2c', (104, 0, 24), 36, _LG_IA2C, (WS, 1, 1), (FC_MFMA, 1), 'H = 128, block edge at column 104'),
+    'edges192': _a2c('ma2c', (130, 62, 0), 52, _RN_MA2C, (WS, 1, 1), (FC_MFMA, 1), 'H = 192 without a wait block, edge at column 130'),
+    'h96': _a2c('ia2c', (64, 0, 32), 36, _LG_IA2C, (TILE, 0, 0), (FC_THREAD, 0), 'off the width table, H % 32 == 0'),
+    'h112': _a2c('ia2c', (96, 0, 16), 36, _LG_IA2C, (DENSE, 0, 0), (FC_THREAD, 0), 'H % 16 == 0 only'),
+    'h124': _a2c('ia2c', (100, 0, 24), 36, _LG_IA2C, (DENSE, 0, 0), (DENSE, 0), 'H % 4 == 0 only'),
+}
+RECORDED = [('obs64', 'lstm'), ('h96', 'fc'), ('h112', 'fc')]       # routes behind an LDS budget: as reported by an MI355X handle
+# tsc_model_create must refuse this one: "hidden width must be a multiple of 4"
+A2C_REFUSED = _a2c('ia2c', (101, 0, 32), 36, _LG_IA2C, None, None, 'H = 133')
+
+
+def _iql(model_type, num_fc, num_h, s_max, agents, fused, why, wide=False):
+    return dict(model_type=model_type, layout=Layout([(w, t, 0, a) for w, t, a in agents], s_max), cfg=dict(num_fc=num_fc, num_h=num_h),
+                fused=fused, why=why, wide=wide)
+
+
+_Q160 = [(32, 16, 8), (31, 16, 7), (17, 16, 2), (16, 16, 3), (15, 1, 5), (1, 1, 8)]
+_LG_IQL = [(30, 6, 5), (24, 6, 5), (18, 6, 5), (24, 6, 5)]
+# name -> model type, num_fc / num_h, s_max, agents (wave, wait, n_a), fused?, the limit it drives.  batch_size 20 throughout.
+IQL_LAYOUTS = {
+    'q160_edge': _iql('dqn', 128, 64, 48, _Q160, True, 'fused limit with a wait part: n_wave = 32, n_wait = 16, s_max = 48'),
+    'q160_past_wave': _iql('dqn', 128, 64, 48, [(33, 15, 8)] + _Q160[1:], False, 'n_wave = 33 with a wait part'),
+    'q160_past_wait': _iql('dqn', 128, 64, 48, [(31, 17, 8)] + _Q160[1:], False, 'n_wait = 17'),
+    'q128_edge': _iql('dqn', 128, 64, 48, [(48, 0, 8), (47, 0, 7), (33, 0, 2), (16, 0, 4), (1, 0, 6)], True, 'fused limit without a wait part: 48 wave inputs'),
+    'q_obs52': _iql('dqn', 128, 64, 52, [(52, 0, 5), (49, 0, 4), (5, 0, 2)], False, 's_max > 48', wide=True),
+    'q_small': _iql('dqn', 64, 32, 36, _LG_IQL, False, 'num_fc != 128: H1 = 80, H2 = 32'),
+    'q_h2': _iql('dqn', 128, 32, 36, _LG_IQL, False, 'num_h != 64'),
+    'lr_tiny': _iql('lr', 128, 64, 4, [(3, 1, 8), (1, 1, 2), (2, 1, 3)], False, 'IQL-LR, K = 4, n_a = 8'),
+    'lr_wide': _iql('lr', 128, 64, 68, [(60, 8, 8), (57, 8, 4), (9, 1, 2)], False, 'IQL-LR, 68 inputs, n_a = 8', wide=True),
+}
+# tsc_iql_create must refuse this one: num_fc = 100 with wait inputs, H1 = 125, "hidden widths must be multiples of 4"
+IQL_REFUSED = _iql('dqn', 100, 64, 36, _LG_IQL, None, 'H1 = 125')
+
+# The batches of the GPU module: A2C (E, T) -- N = 30 and N = 259 rows, ragged in every row loop; IQL E instances, ring capacity
+A2C_BATCHES = [(5, 6), (37, 7)]
+A2C_FORWARD_E, A2C_FORWARD_STEPS = 37, 3
+IQL_E, IQL_CAP, IQL_STEPS = 5, 30, 2
+IQL_REWARD_NORM = 100.0
+
+# name -> seed of the weight init and of the rollouts (data_seed).  Chosen on the host (tests/test_layouts_host.py states what they must satisfy: few hidden units on a ReLU
+# kink, no saturated head, float32 drift of the second round inside its allowance); the GPU module takes the same table.
+SEEDS = {name: 5 for name in list(A2C_LAYOUTS) + list(IQL_LAYOUTS)}
+SEEDS.update(tiny=11, q_small=6)        # 5 fails there: tiny 5 - 10 put more than 4 columns of a one-input block on a kink, q_small 5 a second-layer unit
+# PPO on head8 (MA2C, LSTM, K = 3): (E, T, init seed, rollout seed, lr) under tests/ppo_oracle.py's k3_conditions
+PPO_HEAD8 = (16, 8, 5, 7, 5e-2)
+
+
+def data_seed(name, E, T=0):
+    """RandomState seed of a case's rollout: one stream per (layout, batch), moved by the layout's entry in SEEDS -- a layout whose
+    agents have one or two inputs needs a rollout without an input within ~1e-3 of zero (after the first update the biases are
+    ~1e-4, and such a sample puts many hidden units of the block on their kink at once)."""
+    return 100000 * (sorted(list(A2C_LAYOUTS) + list(IQL_LAYOUTS)).index(name) + 1) + 1000 * SEEDS[name] + 10 * E + T
+
+
+def rand_obs(lay, E, rng):
+    """tests/test_model_gpu.py::_rand_obs: uniform [0, 2) on an agent's own inputs, zero padding behind them."""
+    obs = np.zeros((E, lay.n_agent, lay.s_max), np.float32)
+    for a, n in enumerate(lay.n_s_ls):
+        obs[:, a, :n] = rng.rand(E, n).astype(np.float32) * 2
+    return obs
+
+
+def forward_inputs(lay, E, steps, rng):
+    """The (obs, done) pairs of tests/test_model_gpu.py::_forward_vs_oracle, then the bootstrap observation."""
+    out = []
+    for t in range(steps):
+        obs = rand_obs(lay, E, rng)
+        out.append((obs, (rng.rand(E) < (1.0 if t == 0 else 0.3)).astype(np.uint8)))
+    return out, rand_obs(lay, E, rng)
+
+
+def fill_host(lay, oracles, E, T, rng, reward_norm, p_done=0.1):
+    """tests/test_model_gpu.py::_fill without a device: the same draws in the same order.  The stored value is the first oracle's,
+    rounded to float32 (on the GPU: the kernel's).  -> (next obs, carried done, list of per-step pi of the first oracle)."""
+    obs, done, pis = rand_obs(lay, E, rng), np.ones(E, np.uint8), []
+    for t in range(T):
+        v = None
+        for o in oracles:
+            pi, ov = o.forward(obs, done, 'pv')
+            if v is None:
+                v = np.asarray(ov, np.float64).astype(np.float32)
+                pis.append(pi)
+        act = np.stack([rng.randint(0, n, E) for n in lay.n_a_ls], 1).astype(np.int32)
+        rew = -rng.rand(E, lay.n_agent) * 3.0 * reward_norm
+        dpost = (rng.rand(E) < p_done).astype(np.uint8)
+        for o in oracles:
+            o.add_transition(obs, done, act, rew, v, dpost)
+        obs, done = rand_obs(lay, E, rng), dpost
+    return obs, done, pis
+
+
+def iql_transitions(lay, E, cap, rng, reward_norm):
+    """The transitions of tests/test_iql_gpu.py::_replay_vs_oracle (E < 100): -> list of (obs, act, rew, next obs, done)."""
+    out, obs = [], rand_obs(lay, E, rng)
+    for t in range(cap + 7):
+        nobs = rand_obs(lay, E, rng)
+        act = np.stack([rng.randint(0, n, E) for n in lay.n_a_ls], 1).astype(np.int32)
+        rew = -rng.rand(E, lay.n_agent) * 3.0 * reward_norm
+        done = (rng.rand(E) < 0.1).astype(np.uint8)
+        out.append((obs, act, rew, nobs, done))
+        obs = nobs
+    return out
+
+
+@contextlib.contextmanager
+def oracle_dtype(dt):
+    """Run oracle.nets_oracle / oracle.iql_oracle in another floating-point type: the float32 restatement of the float64 oracles (same
+    code, torch float32 on the CPU), whose distance to float64 is what a correct float32 kernel may show."""
+    from oracle import iql_oracle, nets_oracle
+    saved = nets_oracle.DT, iql_oracle.DT
+    nets_oracle.DT = iql_oracle.DT = dt
+    try:
+        yield
+    finally:
+        nets_oracle.DT, iql_oracle.DT = saved
+
+
+def f32_oracle_class(base):
+    """A subclass of an oracle class whose every public method runs under oracle_dtype(torch.float32)."""
+    import torch
+
+    def wrap(fn):
+        def inner(*a, **k):
+            with oracle_dtype(torch.float32):
+                return fn(*a, **k)
+        return inner
+
+    body = {}
+    for klass in reversed(base.__mro__[:-1]):
+        for k, v in vars(klass).items():
+            if callable(v) and not isinstance(v, (staticmethod, classmethod)) and (not k.startswith('__') or k == '__init__'):
+                body[k] = wrap(getattr(base, k))
+    return type(base.__name__ + 'F32', (base,), body)

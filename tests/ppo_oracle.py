@@ -152,9 +152,11 @@ class PPOOracle(OracleA2C):
 
 
 # ---- shared fixtures of tests/test_ppo_oracle.py (CPU) and tests/test_ppo_gpu.py ------------------------------------------------
-def make_oracle(scn, agent, policy, E, seed, clip_eps=0.2, gae_lambda=0.95, cfg=None, towers=None, sel=None):
+def make_oracle(scn, agent, policy, E, seed, clip_eps=0.2, gae_lambda=0.95, cfg=None, towers=None, sel=None, layout=None):
     """PPOOracle over the towers VecA2C(seed=seed) starts from (agents.init_tower_params with RandomState(seed)), or over
-    `towers`; sel = the agents to keep (the benchmarked shape affords three)."""
+    `towers`; sel = the agents to keep (the benchmarked shape affords three).  layout: a layout object (tests/layouts.py) in place of
+    the scenario -- it carries the same per-agent lists; its hidden widths come in through cfg."""
+    scn = scn if layout is None else layout
     from deeprl_signal_control_amd.agents import A2C_DEFAULTS, init_tower_params
     c = dict(A2C_DEFAULTS)
     c.update(cfg or {})

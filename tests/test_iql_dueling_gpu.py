@@ -121,16 +121,10 @@ def _dead_columns_are_zero(m, flat_g):
 
 
 # ---- 1. forward ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('scenario,agent,model_type,E,cap,fused', CASES)
-def test_forward_against_the_oracle(scenario, agent, model_type, E, cap, fused, monkeypatch):
+def _forward_vs_oracle(scn, m, o, E, rng):
     from oracle.iql_oracle import act_epsilon_greedy
     from oracle.nets_oracle import sample_uniform
-    monkeypatch.setenv('TSC_IQL_FUSED', fused)
-    scn, m = _duel_model(scenario, E, cap, seed=3)
-    assert m.fused == (fused == '1')
-    o = _oracle(m)
     A = scn.n_agent
-    rng = np.random.RandomState(E)
     for t in range(2):
         obs = _rand_obs_decided(scn, E, rng, o)
         act, q = m.forward(torch.from_numpy(obs).cuda())
@@ -155,6 +149,14 @@ def test_forward_against_the_oracle(scenario, agent, model_type, E, cap, fused, 
                 u0 = sample_uniform(m.sample_seed, m.act_step - 1, 2 * (e * A + a))
                 u1 = sample_uniform(m.sample_seed, m.act_step - 1, 2 * (e * A + a) + 1)
                 assert act[e, a] == act_epsilon_greedy(q[e, a, :scn.n_a_ls[a]], eps, u0, u1)
+
+
+@pytest.mark.parametrize('scenario,agent,model_type,E,cap,fused', CASES)
+def test_forward_against_the_oracle(scenario, agent, model_type, E, cap, fused, monkeypatch):
+    monkeypatch.setenv('TSC_IQL_FUSED', fused)
+    scn, m = _duel_model(scenario, E, cap, seed=3)
+    assert m.fused == (fused == '1')
+    _forward_vs_oracle(scn, m, _oracle(m), E, np.random.RandomState(E))
     m.close()
 
 
@@ -170,15 +172,9 @@ def _arm_disagreeing_target(m, o):
     assert np.abs(m.get_target_flat() - m.get_flat()).max() > 0.01
 
 
-@pytest.mark.parametrize('target_update,double_q', TARGETS)
-@pytest.mark.parametrize('scenario,agent,model_type,E,cap,fused', CASES)
-def test_targets_and_gradient_against_the_oracle(scenario, agent, model_type, E, cap, fused, target_update, double_q, monkeypatch):
-    monkeypatch.setenv('TSC_IQL_FUSED', fused)
-    scn, m = _duel_model(scenario, E, cap, target_update=target_update, double_q=double_q)
-    assert m.fused == (fused == '1')
-    o = _oracle(m)
+def _targets_and_gradient_vs_oracle(scn, m, o, E, cap, rng, target_update, double_q):
+    """-> the flat gradient buffer of the step (the caller may look at single columns)."""
     A, B = scn.n_agent, m.n_step
-    rng = np.random.RandomState(cap + E + double_q + target_update)
     _fill([m], o, scn, E, cap, rng, draw_next=lambda: _rand_obs_decided(scn, E, rng, o))
     if target_update:
         _arm_disagreeing_target(m, o)
@@ -208,6 +204,16 @@ def test_targets_and_gradient_against_the_oracle(scenario, agent, model_type, E,
     _dead_columns_are_zero(m, flat_g)
     np.testing.assert_allclose(stats[:, 0], losses, rtol=1e-4, atol=1e-9)
     np.testing.assert_allclose(stats[:, 1], norms, rtol=1e-4)
+    return flat_g
+
+
+@pytest.mark.parametrize('target_update,double_q', TARGETS)
+@pytest.mark.parametrize('scenario,agent,model_type,E,cap,fused', CASES)
+def test_targets_and_gradient_against_the_oracle(scenario, agent, model_type, E, cap, fused, target_update, double_q, monkeypatch):
+    monkeypatch.setenv('TSC_IQL_FUSED', fused)
+    scn, m = _duel_model(scenario, E, cap, target_update=target_update, double_q=double_q)
+    assert m.fused == (fused == '1')
+    _targets_and_gradient_vs_oracle(scn, m, _oracle(m), E, cap, np.random.RandomState(cap + E + double_q + target_update), target_update, double_q)
     m.close()
 
 

@@ -180,19 +180,12 @@ def test_draw(scenario, agent, model_type, E, cap, fused, monkeypatch):
 
 
 # ---- 3. weights, loss, gradient --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('beta', [0.4, 1.0])
-@pytest.mark.parametrize('target_update,double_q', TARGETS)
-@pytest.mark.parametrize('scenario,agent,model_type,E,cap,fused', CASES)
-def test_weights_loss_and_gradient_against_the_oracle(scenario, agent, model_type, E, cap, fused, target_update, double_q, beta, monkeypatch):
+def _per_step_vs_oracle(scn, m, E, cap, rng, target_update, double_q, beta):
     from tests.iql_per_oracle import PerOracleIQL, per_weights
-    monkeypatch.setenv('TSC_IQL_FUSED', fused)
-    scn, m = _model(scenario, agent, model_type, E, buffer_size=cap, prioritized_replay=1, target_update=target_update, double_q=double_q)
-    assert m.fused == (fused == '1')
     o = PerOracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, m.E, alpha=0.6, eps=0.01, target_update=target_update,
                      double_q=bool(double_q), batch_size=m.n_step, buffer_size=cap, gamma=m.cfg['gamma'], reward_norm=m.cfg['reward_norm'],
                      reward_clip=m.cfg['reward_clip'], max_grad_norm=m.cfg['max_grad_norm'], replay_seed=m.replay_seed)
     A, B = scn.n_agent, m.n_step
-    rng = np.random.RandomState(cap + E + double_q + target_update)
     size = _fill([m], o, scn, E, cap, rng, draw_next=lambda: _rand_obs_decided(scn, E, rng, o))
     if target_update:
         m.set_target_flat(m.layout.pack(_disagreeing_target(m, o)))
@@ -236,6 +229,16 @@ def test_weights_loss_and_gradient_against_the_oracle(scenario, agent, model_typ
             assert err.size == 0 or err.max() <= tol * scale, 'agent %d %s: %.2e' % (a, k, err.max() / scale)
     np.testing.assert_allclose(stats[:, 0], losses, rtol=1e-4, atol=1e-9)
     np.testing.assert_allclose(stats[:, 1], norms, rtol=1e-4)
+
+
+@pytest.mark.parametrize('beta', [0.4, 1.0])
+@pytest.mark.parametrize('target_update,double_q', TARGETS)
+@pytest.mark.parametrize('scenario,agent,model_type,E,cap,fused', CASES)
+def test_weights_loss_and_gradient_against_the_oracle(scenario, agent, model_type, E, cap, fused, target_update, double_q, beta, monkeypatch):
+    monkeypatch.setenv('TSC_IQL_FUSED', fused)
+    scn, m = _model(scenario, agent, model_type, E, buffer_size=cap, prioritized_replay=1, target_update=target_update, double_q=double_q)
+    assert m.fused == (fused == '1')
+    _per_step_vs_oracle(scn, m, E, cap, np.random.RandomState(cap + E + double_q + target_update), target_update, double_q, beta)
     m.close()
 
 

@@ -27,12 +27,14 @@ GAP = 1e-4
 
 
 def _model(scenario, agent, model_type, E, seed=5, **cfg):
+    """scenario: the name of a built-in scenario, or a layout object (tests/layouts.py: the attributes read below and nothing else)."""
     from deeprl_signal_control_amd.iql import VecIQL
     from deeprl_signal_control_amd.scenario import build_scenario
-    scn = build_scenario(scenario, agent)
+    scn = build_scenario(scenario, agent) if isinstance(scenario, str) else scenario
     mc = dict(batch_size=20, buffer_size=1000, reward_norm=3000.0 if scenario == 'large_grid' else 1.0 if scenario == 'real_net' else 100.0)
     mc.update(cfg)
-    m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, int(scn.green_tab.shape[1]), mc, total_step=10000, seed=seed,
+    a_max = int(scn.green_tab.shape[1]) if hasattr(scn, 'green_tab') else scn.a_max
+    m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, a_max, mc, total_step=10000, seed=seed,
                model_type=model_type)
     return scn, m
 

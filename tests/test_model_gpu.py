@@ -84,15 +84,17 @@ def test_gemm_tn_colsum_rowrange(Kred, M, N, G, split):
 
 
 def _make(agent, E, n_step, seed=0, policy='lstm', scenario='large_grid', **cfg):
+    """scenario: the name of a built-in scenario, or a layout object (tests/layouts.py: the attributes read below and nothing else)."""
     from deeprl_signal_control_amd.agents import VecA2C
     from deeprl_signal_control_amd.scenario import build_scenario
     from oracle.nets_oracle import OracleA2C
-    scn = build_scenario(scenario, agent)
+    scn = build_scenario(scenario, agent) if isinstance(scenario, str) else scenario
     mc = dict(batch_size=n_step)
     if scenario == 'real_net':
         mc['reward_norm'] = 1.0                                # config/config_{ma2c,ia2c}_real.ini
     mc.update(cfg)
-    m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, E, scn.s_max, int(scn.green_tab.shape[1]), mc, device=0,
+    a_max = int(scn.green_tab.shape[1]) if hasattr(scn, 'green_tab') else scn.a_max
+    m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, E, scn.s_max, a_max, mc, device=0,
                seed=seed, name=agent, policy=policy)
     o = OracleA2C(m.get_tower_params(), m.n_wave_ls, m.n_w_ls, m.n_f_ls, m.n_a_ls, E,
                   gamma=m.cfg['gamma'], reward_norm=m.cfg['reward_norm'], reward_clip=m.cfg['reward_clip'],
@@ -126,28 +128,48 @@ def _rand_obs(scn, E, rng):
     return obs
 
 
-@pytest.mark.parametrize('agent,E,policy', [('ma2c', 5, 'lstm'), ('ia2c', 70, 'lstm'), ('ia2c', 33, 'fc')])
-def test_forward_matches_oracle(agent, E, policy):
-    scn, m, o = _make(agent, E, 4, policy=policy)
-    rng = np.random.RandomState(1)
+def _forward_vs_oracle(scn, m, o, E, rng, steps=5, sample=False, vtol=2e-5):
+    """`steps` advancing forwards with random dones, then the non-advancing bootstrap value, against the oracle.  sample: through
+    forward_sample, whose action must be np.random.choice on the kernel's own pi and the documented uniform.  vtol: bound on |dv|,
+    or a function of the oracle's values (layouts whose values leave the reference's range, tests/test_layouts_gpu.py)."""
+    from oracle.nets_oracle import choice_from_uniform, sample_uniform
+    tol = vtol if callable(vtol) else (lambda ov: vtol)
     m.reset(); o.reset()
-    for t in range(5):
+    for t in range(steps):
         obs = _rand_obs(scn, E, rng)
         done = (rng.rand(E) < (1.0 if t == 0 else 0.3)).astype(np.uint8)
-        pi, v = m.forward(torch.from_numpy(obs).cuda(), torch.from_numpy(done).cuda(), 'pv')
+        if sample:
+            step = m.sample_step
+            pi, v, act = m.forward_sample(torch.from_numpy(obs).cuda(), torch.from_numpy(done).cuda(), cache=False)
+            act = act.cpu().numpy()
+        else:
+            pi, v = m.forward(torch.from_numpy(obs).cuda(), torch.from_numpy(done).cuda(), 'pv')
         pi, v = pi.cpu().numpy(), v.cpu().numpy()
         opi, ov = o.forward(obs, done, 'pv')
         for a in range(scn.n_agent):
             np.testing.assert_allclose(pi[:, a, :scn.n_a_ls[a]], opi[a], atol=2e-5, err_msg='pi t=%d a=%d' % (t, a))
-        np.testing.assert_allclose(v, ov, atol=2e-5)
+            if sample:
+                assert np.all(pi[:, a, scn.n_a_ls[a]:] == 0)
+        np.testing.assert_allclose(v, ov, atol=tol(ov))
         assert np.allclose(pi.sum(-1), 1.0, atol=1e-5)
+        if sample:
+            for e in range(E):
+                for a in range(scn.n_agent):
+                    u = sample_uniform(m.sample_seed, step, e * scn.n_agent + a)
+                    assert act[e, a] == choice_from_uniform(pi[e, a, :scn.n_a_ls[a]], u), (t, e, a)
     # bootstrap value: state must NOT advance (policies.py:127-135)
     obs = _rand_obs(scn, E, rng)
     vb = m.forward(torch.from_numpy(obs).cuda(), False, 'v').cpu().numpy()
     _, ovb = o.forward(obs, np.zeros(E), 'v')
-    np.testing.assert_allclose(vb, ovb, atol=2e-5)
+    np.testing.assert_allclose(vb, ovb, atol=tol(ovb))
     vb2 = m.forward(torch.from_numpy(obs).cuda(), False, 'v').cpu().numpy()
     np.testing.assert_array_equal(vb, vb2)
+
+
+@pytest.mark.parametrize('agent,E,policy', [('ma2c', 5, 'lstm'), ('ia2c', 70, 'lstm'), ('ia2c', 33, 'fc')])
+def test_forward_matches_oracle(agent, E, policy):
+    scn, m, o = _make(agent, E, 4, policy=policy)
+    _forward_vs_oracle(scn, m, o, E, np.random.RandomState(1))
     m.close()
 
 
@@ -260,12 +282,8 @@ def _fill(scn, m, o, E, T, rng, p_done=0.1, terminal=False, use_cache=False):
     return obs, done
 
 
-@pytest.mark.parametrize('agent,E,T,terminal,policy,use_cache', [
-    ('ma2c', 3, 6, False, 'lstm', False), ('ma2c', 66, 8, True, 'lstm', False), ('ia2c', 4, 40, False, 'lstm', False),
-    ('ia2c', 37, 12, True, 'fc', False), ('ma2c', 70, 7, True, 'lstm', True), ('ia2c', 5, 30, False, 'lstm', True)])
-def test_backward_matches_oracle(agent, E, T, terminal, policy, use_cache):
-    scn, m, o = _make(agent, E, T, seed=5, policy=policy)
-    rng = np.random.RandomState(E * T)
+def _backward_vs_oracle(scn, m, o, E, T, rng, terminal, use_cache):
+    """Two update rounds against the oracle: returns bit-exact, every gradient tensor, structural zeros, losses, norm, parameters."""
     m.reset(); o.reset()
     from deeprl_signal_control_amd import _lib
     for it in range(2):                                       # second round exercises states_bw / carried done
@@ -300,6 +318,14 @@ def test_backward_matches_oracle(agent, E, T, terminal, policy, use_cache):
         for t in range(m.G):
             for k in op[t]:
                 np.testing.assert_allclose(p[t][k], op[t][k], atol=3e-5, err_msg='param tower=%d %s' % (t, k))
+
+
+@pytest.mark.parametrize('agent,E,T,terminal,policy,use_cache', [
+    ('ma2c', 3, 6, False, 'lstm', False), ('ma2c', 66, 8, True, 'lstm', False), ('ia2c', 4, 40, False, 'lstm', False),
+    ('ia2c', 37, 12, True, 'fc', False), ('ma2c', 70, 7, True, 'lstm', True), ('ia2c', 5, 30, False, 'lstm', True)])
+def test_backward_matches_oracle(agent, E, T, terminal, policy, use_cache):
+    scn, m, o = _make(agent, E, T, seed=5, policy=policy)
+    _backward_vs_oracle(scn, m, o, E, T, np.random.RandomState(E * T), terminal, use_cache)
     m.close()
 
 
@@ -346,20 +372,15 @@ def test_forward_sample_equals_forward_then_sample():
     m.close()
 
 
-@pytest.mark.parametrize('agent,knob,policy', [('ma2c', 'TSC_UNFUSED_DW', 'lstm'), ('ia2c', 'TSC_UNFUSED_DW', 'lstm'),
-                                               ('ma2c', 'TSC_UNFUSED_DX', 'lstm'), ('ia2c', 'TSC_UNFUSED_DX', 'lstm'),
-                                               ('ia2c', 'TSC_UNFUSED_DX', 'fc')])
-def test_fused_update_kernels_equal_grouped_gemms(agent, knob, policy, monkeypatch):
-    """(policy 'fc': fc_bwd_kernel -- dWfc | dbfc | dW1 | db1 of the FcACPolicy in one pass -- against its three grouped GEMMs.)
-    dwxh_kernel (dWx | dWh | dbl in one pass, whole tower output in accumulators) and dx1w1_kernel2 (dX1 kept in
-    registers, dW1 | db1 from the same pass, only the structurally non-zero feature tiles of W1) against the grouped GEMMs
-    they replace: same gradient up to fp32 summation order, structural zeros of W1 exactly zero."""
-    E, T = 40, 9
-    rng = np.random.RandomState(11)
-    grads = []
+def _fused_vs_grouped(agent, knobs, policy, monkeypatch, E=40, T=9, scenario='large_grid', **cfg):
+    """The update with and without the one-pass kernels the knobs switch off: same gradient up to fp32 summation order, the same
+    zero pattern.  -> the two handles' plans."""
+    grads, plans = [], []
     for unfused in ('0', '1'):
-        monkeypatch.setenv(knob, unfused)
-        scn, m, o = _make(agent, E, T, seed=5, policy=policy)
+        for knob in knobs:
+            monkeypatch.setenv(knob, unfused)
+        scn, m, o = _make(agent, E, T, seed=5, policy=policy, scenario=scenario, **cfg)
+        plans.append(m.plan)
         m.reset(); o.reset()
         r2 = np.random.RandomState(123)
         obs, done = _fill(scn, m, o, E, T, r2, terminal=False, use_cache=True)
@@ -372,6 +393,18 @@ def test_fused_update_kernels_equal_grouped_gemms(agent, knob, policy, monkeypat
     assert scale > 0
     np.testing.assert_allclose(grads[0], grads[1], atol=2e-5 * scale, rtol=0)
     np.testing.assert_array_equal(grads[0] == 0, grads[1] == 0)
+    return plans
+
+
+@pytest.mark.parametrize('agent,knob,policy', [('ma2c', 'TSC_UNFUSED_DW', 'lstm'), ('ia2c', 'TSC_UNFUSED_DW', 'lstm'),
+                                               ('ma2c', 'TSC_UNFUSED_DX', 'lstm'), ('ia2c', 'TSC_UNFUSED_DX', 'lstm'),
+                                               ('ia2c', 'TSC_UNFUSED_DX', 'fc')])
+def test_fused_update_kernels_equal_grouped_gemms(agent, knob, policy, monkeypatch):
+    """(policy 'fc': fc_bwd_kernel -- dWfc | dbfc | dW1 | db1 of the FcACPolicy in one pass -- against its three grouped GEMMs.)
+    dwxh_kernel (dWx | dWh | dbl in one pass, whole tower output in accumulators) and dx1w1_kernel2 (dX1 kept in
+    registers, dW1 | db1 from the same pass, only the structurally non-zero feature tiles of W1) against the grouped GEMMs
+    they replace: same gradient up to fp32 summation order, structural zeros of W1 exactly zero."""
+    _fused_vs_grouped(agent, (knob,), policy, monkeypatch)
 
 
 def test_multibatch_trainer_keeps_replicas_identical():

@@ -23,13 +23,15 @@ def _vec(scn, agent, policy, E, T, seed, **cfg):
     from deeprl_signal_control_amd.agents import VecA2C
     mc = dict(batch_size=T)
     mc.update(cfg)
-    return VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, E, scn.s_max, int(scn.green_tab.shape[1]), mc, device=0, seed=seed,
+    a_max = int(scn.green_tab.shape[1]) if hasattr(scn, 'green_tab') else scn.a_max
+    return VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, E, scn.s_max, a_max, mc, device=0, seed=seed,
                   name=agent, policy=policy)
 
 
-def _make(agent, policy, E, T, seed, sel=None, **cfg):
+def _make(agent, policy, E, T, seed, sel=None, layout=None, **cfg):
+    """layout: a layout object (tests/layouts.py) in place of large_grid."""
     from deeprl_signal_control_amd.scenario import build_scenario
-    scn = build_scenario('large_grid', agent)
+    scn = build_scenario('large_grid', agent) if layout is None else layout
     m = _vec(scn, agent, policy, E, T, seed, **cfg)
     o = make_oracle(scn, agent, policy, E, seed, clip_eps=m.ppo_clip, gae_lambda=m.gae_lambda, cfg=m.cfg, towers=m.get_tower_params(),
                     sel=sel)
@@ -181,8 +183,8 @@ def test_gae_matches_oracle(lam):
 
 
 # ---- 6: K = 3 with the clip active -------------------------------------------------------------------------------------------------
-def _k3(agent, policy, E, T, seed, rseed, lr, sel=None, tol0=2e-5, p_done=0.1):
-    scn, m, o = _make(agent, policy, E, T, seed, sel=sel, algo='ppo', ppo_epochs=3, reward_norm=K3_REWARD_NORM, lr_init=lr)
+def _k3(agent, policy, E, T, seed, rseed, lr, sel=None, tol0=2e-5, p_done=0.1, layout=None, **cfg):
+    scn, m, o = _make(agent, policy, E, T, seed, sel=sel, layout=layout, algo='ppo', ppo_epochs=3, reward_norm=K3_REWARD_NORM, lr_init=lr, **cfg)
     obs, _ = fill(scn, o, E, T, np.random.RandomState(rseed), K3_REWARD_NORM, put=_put_copy(m), sel=sel, p_done=p_done)
     Rb = m.forward(_dev(obs), False, 'v').clone()
     Rb_o = Rb.cpu().numpy() if sel is None else Rb.cpu().numpy()[:, sel]
