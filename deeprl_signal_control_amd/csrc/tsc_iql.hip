@@ -180,6 +180,20 @@ __global__ void iql_qsel_kernel(const float *Qon, const float *Qtg, const int *n
     astar[i] = best;
 }
 
+// The TD kernels' per-agent loss sum, stats[a][0] += l of row i -- logging only (policies.py:330-337): rows of one agent are contiguous, a
+// wave may straddle two agents -> per-lane atomics are avoided by reducing only when the whole wave belongs to one agent
+__device__ __forceinline__ void td_loss_sum(float l, int a, long long i, long long R, int A, double *stats) {
+    const int a0 = __shfl(a, 0, 64);
+    const bool uni = __all(a == a0 || i >= (long long)A * R);
+    if (uni) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
+        if ((threadIdx.x & 63) == 0 && l != 0.f) atomicAdd(&stats[a0 * 2], (double)l);
+    } else if (l != 0.f) {
+        atomicAdd(&stats[a * 2], (double)l);
+    }
+}
+
 // tq = done ? r : r + gamma q1 ; loss = mean((q0 - tq)^2) ; dQ[k] = 2 (q0 - tq) / R at k = a   (agents/policies.py:317-318)
 // iql_td_kernel<true> (prioritized replay): the importance weight of the row in and |delta| out -- loss = mean(w (q0 - tq)^2),
 // dQ[k] = 2 w (q0 - tq) / R.  PER_ is empty or {true}, not a plain bool, so that w and td are parameters of that variant only, each in its
@@ -212,17 +226,7 @@ __global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, c
         if constexpr (PER) (td, ...)[i] = fabsf(d);
         l = PER ? d * d * wi / (float)R : d * d / (float)R;
     }
-    // logging only (policies.py:330-337): rows of one agent are contiguous, a wave may straddle two agents -> per-lane atomics
-    // are avoided by reducing only when the whole wave belongs to one agent
-    const int a0 = __shfl(a, 0, 64);
-    const bool uni = __all(a == a0 || i >= (long long)A * R);
-    if (uni) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
-        if ((threadIdx.x & 63) == 0 && l != 0.f) atomicAdd(&stats[a0 * 2], (double)l);
-    } else if (l != 0.f) {
-        atomicAdd(&stats[a * 2], (double)l);
-    }
+    td_loss_sum(l, a, i, R, A, stats);
 }
 
 // ---- dueling head (tsc_iql_set_dueling; Wang et al. 2016), grouped-GEMM path ----------------------------------------------------
@@ -268,16 +272,7 @@ __global__ void iql_td_duel_kernel(const float *Q, const float *q1, const int *a
         td[i] = fabsf(d);
         l = d * d * wi / (float)R;
     }
-    // (the per-agent loss sum of iql_td_kernel)
-    const int a0 = __shfl(a, 0, 64);
-    const bool uni = __all(a == a0 || i >= (long long)A * R);
-    if (uni) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) l += __shfl_down(l, o, 64);
-        if ((threadIdx.x & 63) == 0 && l != 0.f) atomicAdd(&stats[a0 * 2], (double)l);
-    } else if (l != 0.f) {
-        atomicAdd(&stats[a * 2], (double)l);
-    }
+    td_loss_sum(l, a, i, R, A, stats);
 }
 
 __global__ void iql_fill_kernel(float *x, long long n, float v) {

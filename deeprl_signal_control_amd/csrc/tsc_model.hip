@@ -20,10 +20,10 @@
 //                     software-pipelined over two barrier intervals, also fills the activation cache the update reads
 //                     (policy_fwd_fused_kernel: tile-per-workgroup variant; policy_fwd_fc_mfma_kernel: FcACPolicy;
 //                     grouped GEMMs + lstm_fwd + head_fwd: training-shape re-forward)
-//   update .......... head_bwd2 (persistent, loss gradient + dH + dWo | dbo) -> lstm_bwd2 (Wh^T stationary in registers,
+//   update .......... head_bwd (persistent, loss gradient + dH + dWo | dbo) -> lstm_bwd2 (Wh^T stationary in registers,
 //                     dc in registers / dh through LDS over the n_step time steps, next step's inputs in flight under the
 //                     MFMAs) -> dwxh (dWx | dWh | dbl, whole tower output in accumulators) -> dx1w1_kernel2 (dX1 in
-//                     registers, chained into dW1 | db1) -> grad_norm -> rmsprop; the FcACPolicy update: head_bwd2 ->
+//                     registers, chained into dW1 | db1) -> grad_norm -> rmsprop; the FcACPolicy update: head_bwd ->
 //                     fc_bwd_kernel (dWfc | dbfc | dW1 | db1 in one pass over the X1 / Hh rows its rollout forward cached;
 //                     the grouped split-K GEMMs of tsc_gemm.h behind TSC_UNFUSED_DX and for other shapes)
 // Which of these a handle runs is decided once, in tsc_model_create: its Plan (forward kernel, the three one-pass update
@@ -443,15 +443,30 @@ __global__ void __launch_bounds__(64) head_fwd_kernel(const float *__restrict__ 
 // added in slice order by head_bwd2_reduce_kernel (deterministic), which replaces the separate split-K dWo GEMM and
 // its second pass over h and dL.  grid = (slices, agents), 256 threads.
 // ------------------------------------------------------------------------------------------------
-// head_bwd_ppo_kernel below is this pass with PPO's policy term; the two bodies are kept apart because sharing one (a templated
-// device function) changed this kernel's register allocation.  A fix to the shared part goes into BOTH.
+// head_bwd_kernel<true> is this pass for the PPO update (tsc_model_compute_grads_ppo): same decomposition, same partial records for
+// head_bwd2_reduce_kernel, same value and entropy terms, with the clipped-surrogate policy term
+//   -mean(min(ratio A, clip(ratio, 1 - eps, 1 + eps) A)),   ratio = exp(logp - logp_old).
+// A sample's policy gradient is -A ratio / N through logp, and zero where the clipped branch is the smaller one (A > 0 and
+// ratio > 1 + eps, or A < 0 and ratio < 1 - eps) or pi sits below the 1e-10 clamp.  logp_old [N][A] holds log(clip(pi_old(a_n),
+// 1e-10, 1)), one more 4-byte stream per (sample, agent): record != 0 (epoch 0) writes it from this very evaluation, record == 0
+// reads it.  stats[a][0] is the surrogate loss; ppo_stats [A][2] += {clipped share, mean(logp_old - logp)}.
+// PPO_ is empty or {true}, not a plain bool, so that logp_old, record, clip_eps and ppo_stats are parameters of that variant only:
+// head_bwd_kernel<> has the argument block, and with it the machine code, of a kernel without them (the device of iql_td_kernel's
+// `bool... PER_`, csrc/tsc_iql.hip).  One kernel template, not a shared device function: that changed the A2C kernel's register
+// allocation, this leaves both instantiations' instructions as they were (measured by comparing the assembly, tools/isa_diff.py).
+// Each variant keeps its own statement order where they differ (A2C sums lpa in the dot / ent shuffle loop, PPO before the gradient).
 constexpr int kHbPer = kL * kOut + kOut + kL + 1;      // partial record of a slice: dWo [64][8] | dbo [8] | dWv [64] | dbv
 
+template <bool, class T> using PpoArg = T;
+template <bool... PPO_>
 __global__ void __launch_bounds__(256, 3)
-head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__restrict__ n_act, const float *__restrict__ Hh,
-                 const int *__restrict__ act, const float *__restrict__ Rs, const float *__restrict__ Advs, long long N,
-                 long long rows_per_slice, float v_coef, float beta, float *__restrict__ dH, float *__restrict__ part,
-                 double *stats) {
+head_bwd_kernel(const float *__restrict__ params, Layout lay, const int *__restrict__ n_act, const float *__restrict__ Hh,
+                const int *__restrict__ act, const float *__restrict__ Rs, const float *__restrict__ Advs, long long N,
+                long long rows_per_slice, float v_coef, float beta, float *__restrict__ dH, float *__restrict__ part,
+                double *stats, PpoArg<PPO_, float *__restrict__>... logp_old, PpoArg<PPO_, int>... record,
+                PpoArg<PPO_, float>... clip_eps, PpoArg<PPO_, double *>... ppo_stats) {
+    static_assert(sizeof...(PPO_) <= 1, "head_bwd_kernel<> or head_bwd_kernel<true>");
+    constexpr bool PPO = (PPO_ || ...);
     __shared__ float red[4][16][36];
     const int a = blockIdx.y, sp = blockIdx.x, na = n_act[a];
     const int tid = threadIdx.x, c = tid & 15, grp = tid >> 4;          // 16 sample groups per workgroup
@@ -476,6 +491,7 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
 #pragma unroll
     for (int k = 0; k < kOut; ++k) ab[k] = 0.f;
     float lp = 0.f, lv = 0.f, le = 0.f;
+    [[maybe_unused]] float lc = 0.f, lk = 0.f;                    // PPO: clipped share and approximate KL
     const long long n0 = (long long)sp * rows_per_slice;
     long long n1 = n0 + rows_per_slice;
     if (n1 > N) n1 = N;
@@ -483,6 +499,8 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
     float *dp = dH + (long long)(2 * a) * N * kL + 4 * c, *dq = dH + (long long)(2 * a + 1) * N * kL + 4 * c;
     const float invN = 1.0f / (float)N;
     for (long long nb = n0; nb < n1; nb += 16) {
+        [[maybe_unused]] float lpo = 0.f, ratio = 1.f;           // PPO: log pi_old(a_n), pi / pi_old
+        [[maybe_unused]] bool clipped = false;
         const long long n = nb + grp;
         const bool in = n < n1;
         const long long nc = in ? n : n1 - 1;                           // clamped: unconditional loads
@@ -525,15 +543,35 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
         const float pim = pk / sum;
         const bool inr = pim >= 1e-10f;                                  // tf.clip_by_value(pi, 1e-10, 1)
         const float logpm = valid ? logf(fminf(fmaxf(pim, 1e-10f), 1.0f)) : 0.f;
-        float gpi = 0.f;
-        if (valid) {
-            if (km == ac && inr) gpi += -adv * invN / fmaxf(pim, 1e-10f);
-            gpi += beta * invN * (logpm + (inr ? 1.0f : 0.f));
-        }
-        float dot = pim * gpi, ent = valid ? -pim * logpm : 0.f, lpa = (km == (ac < na ? ac : 0)) ? logpm : 0.f;
+        float gpi = 0.f, dot, ent, lpa;
+        if constexpr (PPO) {
+            lpa = (km == (ac < na ? ac : 0)) ? logpm : 0.f;
+            // the surrogate needs log pi(a_n) before the gradient: one nonzero term per 8-lane row, so the sum is exact
 #pragma unroll
-        for (int o = 1; o < 8; o <<= 1) {
-            dot += __shfl_xor(dot, o, 64); ent += __shfl_xor(ent, o, 64); lpa += __shfl_xor(lpa, o, 64);
+            for (int o = 1; o < 8; o <<= 1) lpa += __shfl_xor(lpa, o, 64);
+            lpo = (record, ...) ? lpa : (logp_old, ...)[idx];
+            ratio = expf(lpa - lpo);                                    // record: exp(0) = 1, the A2C gradient bit for bit
+            clipped = (adv > 0.f && ratio > 1.0f + (clip_eps, ...)) || (adv < 0.f && ratio < 1.0f - (clip_eps, ...));
+            if ((record, ...) && in && c == 0) (logp_old, ...)[idx] = lpa;
+            if (valid) {
+                if (km == ac && inr && !clipped) gpi += -adv * ratio * invN / fmaxf(pim, 1e-10f);
+                gpi += beta * invN * (logpm + (inr ? 1.0f : 0.f));
+            }
+            dot = pim * gpi, ent = valid ? -pim * logpm : 0.f;
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) {
+                dot += __shfl_xor(dot, o, 64); ent += __shfl_xor(ent, o, 64);
+            }
+        } else {
+            if (valid) {
+                if (km == ac && inr) gpi += -adv * invN / fmaxf(pim, 1e-10f);
+                gpi += beta * invN * (logpm + (inr ? 1.0f : 0.f));
+            }
+            dot = pim * gpi, ent = valid ? -pim * logpm : 0.f, lpa = (km == (ac < na ? ac : 0)) ? logpm : 0.f;
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) {
+                dot += __shfl_xor(dot, o, 64); ent += __shfl_xor(ent, o, 64); lpa += __shfl_xor(lpa, o, 64);
+            }
         }
         const float dlm = (in && valid) ? pim * (gpi - dot) : 0.f;
         float dl[kOut];
@@ -561,7 +599,14 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
             for (int k = 0; k < kOut; ++k) ab[k] += dl[k];
             abv += dv;
             if (in) {
-                lp += -lpa * adv * invN;
+                if constexpr (PPO) {
+                    const float rc = fminf(fmaxf(ratio, 1.0f - (clip_eps, ...)), 1.0f + (clip_eps, ...));
+                    lp += -fminf(ratio * adv, rc * adv) * invN;
+                    lc += clipped ? invN : 0.f;
+                    lk += (lpo - lpa) * invN;
+                } else {
+                    lp += -lpa * adv * invN;
+                }
                 lv += 0.5f * v_coef * (R - v) * (R - v) * invN;
                 le += -beta * ent * invN;
             }
@@ -581,6 +626,7 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
         for (int k = 0; k < kOut; ++k) ab[k] += __shfl_xor(ab[k], o, 64);
         abv += __shfl_xor(abv, o, 64);
         lp += __shfl_xor(lp, o, 64); lv += __shfl_xor(lv, o, 64); le += __shfl_xor(le, o, 64);
+        if constexpr (PPO) { lc += __shfl_xor(lc, o, 64); lk += __shfl_xor(lk, o, 64); }
     }
     if ((tid & 63) < 16) {
 #pragma unroll
@@ -591,12 +637,13 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
         }
     }
     __shared__ float redb[4][kOut + 1];
-    __shared__ float redl[4][3];
+    __shared__ float redl[4][PPO ? 5 : 3];
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < kOut; ++k) redb[wave][k] = ab[k];
         redb[wave][kOut] = abv;
         redl[wave][0] = lp; redl[wave][1] = lv; redl[wave][2] = le;
+        if constexpr (PPO) { redl[wave][3] = lc; redl[wave][4] = lk; }
     }
     __syncthreads();
     float *out = part + ((long long)sp * lay.A + a) * kHbPer;
@@ -619,205 +666,11 @@ head_bwd2_kernel(const float *__restrict__ params, Layout lay, const int *__rest
         double a0 = 0, a1 = 0, a2 = 0;
         for (int w = 0; w < 4; ++w) { a0 += redl[w][0]; a1 += redl[w][1]; a2 += redl[w][2]; }
         atomicAdd(&stats[a * 4 + 0], a0); atomicAdd(&stats[a * 4 + 1], a1); atomicAdd(&stats[a * 4 + 2], a2);
-    }
-}
-
-// head_bwd for the PPO update (tsc_model_compute_grads_ppo): a copy of head_bwd2_kernel above (keep the two in step: what differs
-// is the block between `logpm` and `dot`, the lp / lc / lk sums and redl's width) -- same decomposition, same partial records
-// for head_bwd2_reduce_kernel, same value and entropy terms -- with the clipped-surrogate policy term
-//   -mean(min(ratio A, clip(ratio, 1 - eps, 1 + eps) A)),   ratio = exp(logp - logp_old).
-// A sample's policy gradient is -A ratio / N through logp, and zero where the clipped branch is the smaller one (A > 0 and
-// ratio > 1 + eps, or A < 0 and ratio < 1 - eps) or pi sits below the 1e-10 clamp.  logp_old [N][A] holds log(clip(pi_old(a_n),
-// 1e-10, 1)), one more 4-byte stream per (sample, agent): record != 0 (epoch 0) writes it from this very evaluation, record == 0
-// reads it.  stats[a][0] is the surrogate loss; ppo_stats [A][2] += {clipped share, mean(logp_old - logp)}.
-__global__ void __launch_bounds__(256, 3)
-head_bwd_ppo_kernel(const float *__restrict__ params, Layout lay, const int *__restrict__ n_act, const float *__restrict__ Hh,
-                    const int *__restrict__ act, const float *__restrict__ Rs, const float *__restrict__ Advs, long long N,
-                    long long rows_per_slice, float v_coef, float beta, float *__restrict__ dH, float *__restrict__ part,
-                    double *stats, float *__restrict__ logp_old, int record, float clip_eps, double *ppo_stats) {
-    __shared__ float red[4][16][36];
-    const int a = blockIdx.y, sp = blockIdx.x, na = n_act[a];
-    const int tid = threadIdx.x, c = tid & 15, grp = tid >> 4;          // 16 sample groups per workgroup
-    const float *Pp = params + (long long)(2 * a) * lay.stride, *Pv = params + (long long)(2 * a + 1) * lay.stride;
-    float wo[4][kOut], wv[4], bo[kOut];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) wo[u][k] = Pp[lay.oWo + (4 * c + u) * kOut + k];
-        wv[u] = Pv[lay.oWo + (4 * c + u) * kOut];
-    }
-#pragma unroll
-    for (int k = 0; k < kOut; ++k) bo[k] = Pp[lay.obo + k];
-    const float bv = Pv[lay.obo];
-    float aw[4][kOut], awv[4], ab[kOut], abv = 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        awv[u] = 0.f;
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) aw[u][k] = 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < kOut; ++k) ab[k] = 0.f;
-    float lp = 0.f, lv = 0.f, le = 0.f, lc = 0.f, lk = 0.f;       // lc, lk: clipped share and approximate KL
-    const long long n0 = (long long)sp * rows_per_slice;
-    long long n1 = n0 + rows_per_slice;
-    if (n1 > N) n1 = N;
-    const float *hp = Hh + (long long)(2 * a) * N * kL + 4 * c, *hq = Hh + (long long)(2 * a + 1) * N * kL + 4 * c;
-    float *dp = dH + (long long)(2 * a) * N * kL + 4 * c, *dq = dH + (long long)(2 * a + 1) * N * kL + 4 * c;
-    const float invN = 1.0f / (float)N;
-    for (long long nb = n0; nb < n1; nb += 16) {
-        const long long n = nb + grp;
-        const bool in = n < n1;
-        const long long nc = in ? n : n1 - 1;                           // clamped: unconditional loads
-        const float4 h4 = *reinterpret_cast<const float4 *>(hp + nc * kL);
-        const float4 g4 = *reinterpret_cast<const float4 *>(hq + nc * kL);
-        const long long idx = nc * lay.A + a;
-        const int ac = act[idx];
-        const float adv = Advs[idx], R = Rs[idx];
-        const float hh[4] = {h4.x, h4.y, h4.z, h4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
-        float lg[kOut], vv = 0.f;
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) lg[k] = 0.f;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int k = 0; k < kOut; ++k) lg[k] += hh[u] * wo[u][k];
-            vv += gg[u] * wv[u];
+        if constexpr (PPO) {
+            double a3 = 0, a4 = 0;
+            for (int w = 0; w < 4; ++w) { a3 += redl[w][3]; a4 += redl[w][4]; }
+            atomicAdd(&(ppo_stats, ...)[a * 2 + 0], a3); atomicAdd(&(ppo_stats, ...)[a * 2 + 1], a4);
         }
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {                              // the 16 lanes of a sample are one shuffle row
-#pragma unroll
-            for (int k = 0; k < kOut; ++k) lg[k] += __shfl_xor(lg[k], o, 64);
-            vv += __shfl_xor(vv, o, 64);
-        }
-        const float v = vv + bv;
-        // softmax / loss gradient: lane c of the sample's 16 handles action k = c & 7 (one exp, one log, one division per
-        // lane instead of eight of each), sums go over the 8-lane row by xor-shuffles, then every lane collects all dl[k]
-        float mx = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) { lg[k] += bo[k]; if (k < na && lg[k] > mx) mx = lg[k]; }
-        const int km = c & 7;
-        float lgm = lg[0];
-#pragma unroll
-        for (int k = 1; k < kOut; ++k) lgm = km == k ? lg[k] : lgm;
-        const bool valid = km < na;
-        const float pk = valid ? expf(lgm - mx) : 0.f;
-        float sum = pk;
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) sum += __shfl_xor(sum, o, 64);
-        const float pim = pk / sum;
-        const bool inr = pim >= 1e-10f;                                  // tf.clip_by_value(pi, 1e-10, 1)
-        const float logpm = valid ? logf(fminf(fmaxf(pim, 1e-10f), 1.0f)) : 0.f;
-        float gpi = 0.f;
-        float lpa = (km == (ac < na ? ac : 0)) ? logpm : 0.f;
-        // the surrogate needs log pi(a_n) before the gradient: one nonzero term per 8-lane row, so the sum is exact
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) lpa += __shfl_xor(lpa, o, 64);
-        const float lpo = record ? lpa : logp_old[idx];
-        const float ratio = expf(lpa - lpo);                            // record: exp(0) = 1, the A2C gradient bit for bit
-        const bool clipped = (adv > 0.f && ratio > 1.0f + clip_eps) || (adv < 0.f && ratio < 1.0f - clip_eps);
-        if (record && in && c == 0) logp_old[idx] = lpa;
-        if (valid) {
-            if (km == ac && inr && !clipped) gpi += -adv * ratio * invN / fmaxf(pim, 1e-10f);
-            gpi += beta * invN * (logpm + (inr ? 1.0f : 0.f));
-        }
-        float dot = pim * gpi, ent = valid ? -pim * logpm : 0.f;
-#pragma unroll
-        for (int o = 1; o < 8; o <<= 1) {
-            dot += __shfl_xor(dot, o, 64); ent += __shfl_xor(ent, o, 64);
-        }
-        const float dlm = (in && valid) ? pim * (gpi - dot) : 0.f;
-        float dl[kOut];
-        const int row0 = (tid & 63) & ~15;
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) dl[k] = __shfl(dlm, row0 + k, 64);
-        const float dv = in ? v_coef * (v - R) * invN : 0.f;
-        // dH of my quad (FC policy: the head input is relu(.), fold its derivative in), dWo / dWv accumulation
-        float o4[4], q4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int k = 0; k < kOut; ++k) { sacc += dl[k] * wo[u][k]; aw[u][k] += hh[u] * dl[k]; }
-            o4[u] = (lay.fc && !(hh[u] > 0.f)) ? 0.f : sacc;
-            q4[u] = (lay.fc && !(gg[u] > 0.f)) ? 0.f : dv * wv[u];
-            awv[u] += gg[u] * dv;
-        }
-        if (in) {
-            *reinterpret_cast<float4 *>(dp + n * kL) = make_float4(o4[0], o4[1], o4[2], o4[3]);
-            *reinterpret_cast<float4 *>(dq + n * kL) = make_float4(q4[0], q4[1], q4[2], q4[3]);
-        }
-        if (c == 0) {
-#pragma unroll
-            for (int k = 0; k < kOut; ++k) ab[k] += dl[k];
-            abv += dv;
-            if (in) {
-                const float rc = fminf(fmaxf(ratio, 1.0f - clip_eps), 1.0f + clip_eps);
-                lp += -fminf(ratio * adv, rc * adv) * invN;
-                lc += clipped ? invN : 0.f;
-                lk += (lpo - lpa) * invN;
-                lv += 0.5f * v_coef * (R - v) * (R - v) * invN;
-                le += -beta * ent * invN;
-            }
-        }
-    }
-    // fold the 16 sample groups: across the wave's four groups by shuffles, across the four waves through LDS
-    const int wave = tid >> 6;
-#pragma unroll
-    for (int o = 16; o < 64; o <<= 1) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int k = 0; k < kOut; ++k) aw[u][k] += __shfl_xor(aw[u][k], o, 64);
-            awv[u] += __shfl_xor(awv[u], o, 64);
-        }
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) ab[k] += __shfl_xor(ab[k], o, 64);
-        abv += __shfl_xor(abv, o, 64);
-        lp += __shfl_xor(lp, o, 64); lv += __shfl_xor(lv, o, 64); le += __shfl_xor(le, o, 64);
-        lc += __shfl_xor(lc, o, 64); lk += __shfl_xor(lk, o, 64);
-    }
-    if ((tid & 63) < 16) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int k = 0; k < kOut; ++k) red[wave][c][u * kOut + k] = aw[u][k];
-            red[wave][c][32 + u] = awv[u];
-        }
-    }
-    __shared__ float redb[4][kOut + 1];
-    __shared__ float redl[4][5];
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < kOut; ++k) redb[wave][k] = ab[k];
-        redb[wave][kOut] = abv;
-        redl[wave][0] = lp; redl[wave][1] = lv; redl[wave][2] = le;
-        redl[wave][3] = lc; redl[wave][4] = lk;
-    }
-    __syncthreads();
-    float *out = part + ((long long)sp * lay.A + a) * kHbPer;
-    for (int j = tid; j < kHbPer; j += 256) {
-        float acc = 0.f;
-        if (j < kL * kOut) {                       // dWo[jj][k]: jj = 4 c + u
-            const int jj = j / kOut, k = j % kOut;
-            for (int w = 0; w < 4; ++w) acc += red[w][jj >> 2][(jj & 3) * kOut + k];
-        } else if (j < kL * kOut + kOut) {
-            for (int w = 0; w < 4; ++w) acc += redb[w][j - kL * kOut];
-        } else if (j < kL * kOut + kOut + kL) {
-            const int jj = j - (kL * kOut + kOut);
-            for (int w = 0; w < 4; ++w) acc += red[w][jj >> 2][32 + (jj & 3)];
-        } else {
-            for (int w = 0; w < 4; ++w) acc += redb[w][kOut];
-        }
-        out[j] = acc;
-    }
-    if (stats && tid == 0) {     // logging only (policies.py:63-72)
-        double a0 = 0, a1 = 0, a2 = 0;
-        for (int w = 0; w < 4; ++w) { a0 += redl[w][0]; a1 += redl[w][1]; a2 += redl[w][2]; }
-        atomicAdd(&stats[a * 4 + 0], a0); atomicAdd(&stats[a * 4 + 1], a1); atomicAdd(&stats[a * 4 + 2], a2);
-        double a3 = 0, a4 = 0;
-        for (int w = 0; w < 4; ++w) { a3 += redl[w][3]; a4 += redl[w][4]; }
-        atomicAdd(&ppo_stats[a * 2 + 0], a3); atomicAdd(&ppo_stats[a * 2 + 1], a4);
     }
 }
 
@@ -2468,7 +2321,7 @@ __global__ void dx1w1_reduce2_kernel(const float *__restrict__ ws, int G, int S,
 
 // ------------------------------------------------------------------------------------------------
 // FcACPolicy (agents/policies.py:214-256; BASELINE configs[1]): both layers' weight gradients of one tower in ONE pass over
-// the n-step batch.  The second layer is fc(H -> 64) + relu, so its pre-activation gradient dZ [N][64] is what head_bwd2
+// the n-step batch.  The second layer is fc(H -> 64) + relu, so its pre-activation gradient dZ [N][64] is what head_bwd
 // leaves in dH (relu' of the 64 units folded in); then
 //   dWfc = X1^T dZ,  dbfc = colsum(dZ),
 //   dX1  = (dZ Wfc^T) * relu'(X1)     (16 x 16 tiles, never leaves the registers)
@@ -3203,12 +3056,12 @@ static int launch_head_bwd(tsc_model *m, long long N, double beta, const PpoArgs
     if ((size_t)((long long)S * L.A * kHbPer) > m->ws_floats) return tsc::fail("head_bwd: workspace too small");
     if (ppo) {
         tsc::ProfScope ps7(tsc::KID_HEAD_BWD_PPO, m->stream);
-        hipLaunchKernelGGL(head_bwd_ppo_kernel, dim3((unsigned)S, (unsigned)L.A), dim3(256), 0, st, m->params, L, m->n_act, m->Hh, m->r_act,
+        hipLaunchKernelGGL(head_bwd_kernel<true>, dim3((unsigned)S, (unsigned)L.A), dim3(256), 0, st, m->params, L, m->n_act, m->Hh, m->r_act,
                            m->Rs, m->Advs, N, rps, (float)m->vcoef, (float)beta, m->dHh, m->ws, m->stats, m->logp_old,
                            ppo->epoch == 0 ? 1 : 0, (float)ppo->clip_eps, m->stats + 4 * L.A);
     } else {
         tsc::ProfScope ps7(tsc::KID_HEAD_BWD, m->stream);
-        hipLaunchKernelGGL(head_bwd2_kernel, dim3((unsigned)S, (unsigned)L.A), dim3(256), 0, st, m->params, L, m->n_act, m->Hh, m->r_act,
+        hipLaunchKernelGGL(head_bwd_kernel<>, dim3((unsigned)S, (unsigned)L.A), dim3(256), 0, st, m->params, L, m->n_act, m->Hh, m->r_act,
                            m->Rs, m->Advs, N, rps, (float)m->vcoef, (float)beta, m->dHh, m->ws, m->stats);
     }
     {

@@ -1,6 +1,6 @@
 """GPU tests of the opt-in dueling head of the IQL-DNN learner ([MODEL_CONFIG] dueling; include/tsc.h tsc_iql_set_dueling; csrc/tsc_iql_fused.h
 q_duel and the QDuel instantiations of the act, target and gradient kernels; csrc/tsc_iql.hip iql_duel_combine_kernel and iql_td_duel_kernel
-on the grouped-GEMM path) against the float64 restatement of tests/iql_duel_oracle.py.
+on the grouped-GEMM path) against the float64 restatement of tests/iql_ext_oracle.py.
 
 Shapes: the dqn rows of tests/test_iql_target_gpu.py::CASES, the smallest at which each path can go wrong -- large_grid E = 70 (width-10
 instantiation, several row splits, ragged last chunk 1400 = 21 x 64 + 56), E = 3 (one partial chunk), E = 6 on the grouped-GEMM path,
@@ -62,8 +62,8 @@ def _duel_model(scenario, E, cap, seed=5, **cfg):
 
 
 def _oracle(m, per=False):
-    from tests.iql_duel_oracle import DuelOracleIQL
-    return DuelOracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, m.E, per=per, alpha=m.per_alpha, eps=m.per_eps,
+    from tests.iql_ext_oracle import ExtOracleIQL
+    return ExtOracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, m.E, per=per, alpha=m.per_alpha, eps=m.per_eps,
                          target_update=m.target_update, double_q=bool(m.double_q), batch_size=m.n_step,
                          buffer_size=int(m.cfg['buffer_size']), gamma=m.cfg['gamma'], reward_norm=m.cfg['reward_norm'],
                          reward_clip=m.cfg['reward_clip'], max_grad_norm=m.cfg['max_grad_norm'], replay_seed=m.replay_seed)
@@ -73,7 +73,7 @@ def _rand_obs_decided(scn, E, rng, o):
     """tests/test_iql_target_gpu.py's _rand_obs_decided with the dueling net: every row re-drawn until its agent's two best COMBINED online
     values are at least GAP apart in float64, so the greedy action and Double DQN's pick are the same in float32."""
     from oracle.iql_oracle import DT
-    from tests.iql_duel_oracle import q_net_duel
+    from tests.iql_ext_oracle import q_net_duel
     obs = _rand_obs(scn, E, rng)
     for a, n in enumerate(scn.n_s_ls):
         rows = np.arange(E)
@@ -220,7 +220,7 @@ def test_targets_and_gradient_against_the_oracle(scenario, agent, model_type, E,
 @pytest.mark.parametrize('scenario,agent,model_type,E,cap,fused', [CASES[4], CASES[2]])
 def test_prioritized_dueling_step_against_the_oracle(scenario, agent, model_type, E, cap, fused, monkeypatch):
     """The full 3DQN step (dueling + Double DQN + prioritized replay): weights, |delta| written back, new priorities, loss, gradient."""
-    from tests.iql_per_oracle import per_weights
+    from tests.iql_ext_oracle import per_weights
     monkeypatch.setenv('TSC_IQL_FUSED', fused)
     beta = 0.4
     scn, m = _duel_model(scenario, E, cap, target_update=100, double_q=1, prioritized_replay=1)

@@ -1,5 +1,5 @@
 """Host-side checks of the opt-in dueling head of IQL-DNN ([MODEL_CONFIG] dueling; deeprl_signal_control_amd/iql.py dueling_config,
-QParamLayout(dueling=True)) and self-checks of its float64 oracle (tests/iql_duel_oracle.py) -- no GPU."""
+QParamLayout(dueling=True)) and self-checks of its float64 oracle (tests/iql_ext_oracle.py) -- no GPU."""
 import configparser
 
 import numpy as np
@@ -87,10 +87,10 @@ def test_one_seed_draws_the_same_existing_tensors_with_and_without_dueling():
 
 
 def _oracle_and_rows(rng):
-    from tests.iql_duel_oracle import DuelOracleIQL
+    from tests.iql_ext_oracle import ExtOracleIQL
     lay = _layout(True)
     agents = [{k: rng.randn(*sh) * 0.5 for k, sh in lay.shapes(a).items()} for a in range(lay.A)]
-    o = DuelOracleIQL(agents, N_WAVE, N_WAIT, N_A, 1, batch_size=6, buffer_size=8, reward_norm=1.0, reward_clip=0.0)
+    o = ExtOracleIQL(agents, N_WAVE, N_WAIT, N_A, 1, batch_size=6, buffer_size=8, reward_norm=1.0, reward_clip=0.0)
     return lay, agents, o
 
 
@@ -113,7 +113,7 @@ def test_oracle_gradient_structure():
 
 def test_oracle_q_is_invariant_to_a_constant_on_the_advantage_biases():
     from oracle.iql_oracle import DT
-    from tests.iql_duel_oracle import q_net_duel
+    from tests.iql_ext_oracle import q_net_duel
     rng = np.random.RandomState(4)
     lay, agents, o = _oracle_and_rows(rng)
     for a, q in enumerate(o.qs):
@@ -124,3 +124,76 @@ def test_oracle_q_is_invariant_to_a_constant_on_the_advantage_biases():
         moved = dict(q.p, v_b=q.p['v_b'] + 0.37)                    # ... while the value bias moves every action alike
         assert ((q_net_duel(moved, S, q.n_s, q.n_w) - base) - 0.37).abs().max() <= 1e-12
         assert base.shape == (11, N_A[a])
+
+
+def _fill_rings(oracles, E, rng, n=11):
+    for t in range(n):
+        tr = (rng.rand(E, 3, S_MAX) * 2, np.stack([rng.randint(0, k, E) for k in N_A], 1), -rng.rand(E, 3) * 3, rng.rand(E, 3, S_MAX) * 2,
+              rng.rand(E) < 0.2)
+        for o in oracles:
+            o.add_transition(*tr)
+
+
+def test_every_option_off_is_the_reference_oracle_bit_for_bit():
+    """ExtOracleIQL without target network, Double DQN, prioritized replay and value stream against oracle.iql_oracle.OracleIQL over three
+    minibatch steps: a weight of exactly 1 and theta- = theta change no bit of the losses, norms, gradients and parameters."""
+    from oracle.iql_oracle import OracleIQL
+    from tests.iql_ext_oracle import ExtOracleIQL
+    rng = np.random.RandomState(5)
+    lay = _layout(False)
+    agents = [{k: rng.randn(*sh) * 0.5 for k, sh in lay.shapes(a).items()} for a in range(lay.A)]
+    kw = dict(batch_size=6, buffer_size=8, reward_norm=1.0, reward_clip=0.0, replay_seed=3)
+    ref, ext = OracleIQL(agents, N_WAVE, N_WAIT, N_A, 2, **kw), ExtOracleIQL(agents, N_WAVE, N_WAIT, N_A, 2, **kw)
+    _fill_rings([ref, ext], 2, rng)
+    for step in range(3):
+        l0, n0, g0 = ref.minibatch_step(1e-2)
+        l1, n1, g1 = ext.minibatch_step(1e-2)
+        np.testing.assert_array_equal(l0, l1)
+        np.testing.assert_array_equal(n0, n1)
+        np.testing.assert_array_equal(ref.last_idx, ext.last_idx)
+        for a in range(lay.A):
+            assert list(g0[a]) == list(g1[a])
+            for k in g0[a]:
+                np.testing.assert_array_equal(g0[a][k], g1[a][k])
+                assert torch.equal(ref.qs[a].p[k], ext.qs[a].p[k]), (step, a, k)
+        assert (ext.last_w == 1).all() and (ext.prio == 0).all()
+
+
+def test_float32_restatement_runs_with_every_option_on():
+    """layouts.f32_oracle_class(ExtOracleIQL) with target network + Double DQN + prioritized replay + dueling head: one step in float32
+    throughout, and its parameters at float32 distance of the float64 run.  The first Adam step of a component with gradient g is
+    lr f(g), f(x) = x / (|x| + c), c = 1e-8 / sqrt(1 - beta2) (m = (1 - beta1) g, v = (1 - beta2) g^2 and Adam's bias correction), f
+    increasing; with the float32 gradient within e = 2e-5 max|g| of g (the first-round allowance of tests/test_layouts_host.py, asserted
+    here too), the step moves by at most lr max(f(g + e) - f(g), f(g) - f(g - e)), plus a few float32 roundings of the parameter."""
+    from tests import layouts as LY
+    from tests.iql_ext_oracle import ExtOracleIQL
+    rng = np.random.RandomState(6)
+    lay, lr, E = _layout(True), 1e-3, 2
+    agents = [{k: rng.randn(*sh) * 0.5 for k, sh in lay.shapes(a).items()} for a in range(lay.A)]
+    other = [{k: v + rng.randn(*v.shape) * 0.1 for k, v in p.items()} for p in agents]
+    kw = dict(per=True, alpha=0.6, eps=0.01, target_update=2, double_q=True, batch_size=6, buffer_size=8, reward_norm=1.0, reward_clip=0.0,
+              replay_seed=3)
+    o64 = ExtOracleIQL(agents, N_WAVE, N_WAIT, N_A, E, **kw)
+    o32 = LY.f32_oracle_class(ExtOracleIQL)(agents, N_WAVE, N_WAIT, N_A, E, **kw)
+    assert o64.qs[0].p['q_w'].dtype == torch.float64 and o32.qs[0].p['q_w'].dtype == torch.float32
+    _fill_rings([o64, o32], E, rng)
+    prio = (rng.rand(E, lay.A, 8) + 0.05).astype(np.float32)
+    for o in (o64, o32):
+        o.set_target_params(other)
+        o.prio[:] = prio
+    before = [{k: v.clone() for k, v in q.p.items()} for q in o64.qs]
+    _, n64, g64 = o64.minibatch_step(lr, beta=0.4)
+    _, n32, g32 = o32.minibatch_step(lr, beta=0.4)
+    np.testing.assert_array_equal(o64.last_idx, o32.last_idx)
+    assert o64.last_w.min() < 1 and n64.max() < 40.0 and n32.max() < 40.0                     # weighted rows, no clipping on either side
+    c = 1e-8 / np.sqrt(1e-3)
+    f = lambda x: x / (np.abs(x) + c)
+    for a, (q64, q32) in enumerate(zip(o64.qs, o32.qs)):
+        assert q32.target['v_w'].dtype == torch.float32 and q32.last_y.dtype == np.float32 and q32.last_astar is not None
+        for k, g in g64[a].items():
+            assert g32[a][k].dtype == np.float32 and q32.p[k].dtype == torch.float32
+            e = 2e-5 * np.abs(g).max()
+            assert e > 0 and np.abs(g32[a][k] - g).max() <= e, (a, k)
+            bound = 2.0 ** -22 * max(1.0, float(before[a][k].abs().max())) + lr * np.maximum(f(g + e) - f(g), f(g) - f(g - e))
+            assert (np.abs(q32.p[k].double().numpy() - q64.p[k].numpy()) <= bound).all(), (a, k)
+            assert float((q64.p[k] - before[a][k]).abs().max()) > 0.5 * lr                    # ... and the step was taken

@@ -1,6 +1,6 @@
 """GPU tests of the opt-in prioritized replay of the Q-learners ([MODEL_CONFIG] prioritized_replay / per_alpha / per_beta / per_eps;
 include/tsc.h tsc_iql_set_per; csrc/tsc_iql.hip iql_per_sample_kernel, iql_per_update_kernel, iql_per_add_kernel, iql_td_kernel<true> and
-csrc/tsc_iql_fused.h iql_fused_grad_kernel<.., true, true>) against the float64 restatement of tests/iql_per_oracle.py.
+csrc/tsc_iql_fused.h iql_fused_grad_kernel<.., true, true>) against the float64 restatement of tests/iql_ext_oracle.py.
 
 Shapes: tests/test_iql_target_gpu.py::CASES, the smallest at which each gradient path can go wrong, plus two IQL-LR rings for the sampler
 alone: buffer_size 150 filled past its capacity (size = 150 = 2 x 64 + 22: the 64 lanes' blocks are ragged, the last lanes own nothing)
@@ -181,8 +181,8 @@ def test_draw(scenario, agent, model_type, E, cap, fused, monkeypatch):
 
 # ---- 3. weights, loss, gradient --------------------------------------------------------------------------------------------------
 def _per_step_vs_oracle(scn, m, E, cap, rng, target_update, double_q, beta):
-    from tests.iql_per_oracle import PerOracleIQL, per_weights
-    o = PerOracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, m.E, alpha=0.6, eps=0.01, target_update=target_update,
+    from tests.iql_ext_oracle import ExtOracleIQL, per_weights
+    o = ExtOracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, m.E, per=True, alpha=0.6, eps=0.01, target_update=target_update,
                      double_q=bool(double_q), batch_size=m.n_step, buffer_size=cap, gamma=m.cfg['gamma'], reward_norm=m.cfg['reward_norm'],
                      reward_clip=m.cfg['reward_clip'], max_grad_norm=m.cfg['max_grad_norm'], replay_seed=m.replay_seed)
     A, B = scn.n_agent, m.n_step

@@ -1,11 +1,10 @@
 """Host-side checks of the opt-in prioritized replay of the Q-learners: the float64 restatement the GPU tests compare against
-(tests/iql_per_oracle.py), the configuration keys (`prioritized_replay`, `per_alpha`, `per_beta`, `per_eps`) and the beta schedule."""
+(tests/iql_ext_oracle.py), the configuration keys (`prioritized_replay`, `per_alpha`, `per_beta`, `per_eps`) and the beta schedule."""
 import numpy as np
 import pytest
 import torch
 
-from tests.iql_per_oracle import PerOracleIQL, PerOracleQ, per_draw, per_priority, per_weights
-from tests.iql_target_oracle import TargetOracleQ
+from tests.iql_ext_oracle import ExtOracleIQL, ExtOracleQ, per_draw, per_priority, per_weights
 
 
 def test_hand_computed_three_slot_ring():
@@ -52,7 +51,7 @@ def _lr_params():
 
 def test_weighted_loss_and_gradient_by_hand():
     """IQL-LR with one-hot observations (Q(s) is a row of q_w): loss = mean(w delta^2), dLoss/dq_w[s, a] = 2 w delta / n."""
-    o = PerOracleQ(_lr_params(), 2, 0, gamma=0.5, target_update=0)
+    o = ExtOracleQ(_lr_params(), 2, 0, gamma=0.5, target_update=0)
     obs, nobs, acts, rs = np.eye(2), np.eye(2), [2, 0], [0.25, -1.0]
     o.weights = np.array([1.0, 0.25])
     loss, g = o.loss_and_grads(obs, acts, nobs, [False, True], rs)
@@ -63,7 +62,7 @@ def test_weighted_loss_and_gradient_by_hand():
     gw = np.zeros((2, 3)); gw[0, 2] = 1.0 * d[0]; gw[1, 0] = 0.25 * d[1]
     np.testing.assert_allclose(g['q_w'].numpy(), gw, rtol=1e-15)
     # weights of 1 are the target oracle's loss, exactly
-    ref = TargetOracleQ(_lr_params(), 2, 0, gamma=0.5, target_update=3)
+    ref = ExtOracleQ(_lr_params(), 2, 0, gamma=0.5, target_update=3)
     o.weights = None
     l0, g0 = ref.loss_and_grads(obs, acts, nobs, [False, True], rs)
     l1, g1 = o.loss_and_grads(obs, acts, nobs, [False, True], rs)
@@ -73,7 +72,7 @@ def test_weighted_loss_and_gradient_by_hand():
 def test_vector_oracle_rings_priorities_and_write_back():
     rng = np.random.RandomState(2)
     ps = [_lr_params(), _lr_params()]
-    o = PerOracleIQL(ps, [2, 2], [0, 0], [3, 3], 2, alpha=0.5, eps=0.01, batch_size=3, buffer_size=4, reward_norm=1.0, reward_clip=0.0, replay_seed=9)
+    o = ExtOracleIQL(ps, [2, 2], [0, 0], [3, 3], 2, per=True, alpha=0.5, eps=0.01, batch_size=3, buffer_size=4, reward_norm=1.0, reward_clip=0.0, replay_seed=9)
     assert (o.qmax == 1).all() and (o.prio == 0).all()
     for t in range(6):                                                          # wraps: slots 0 and 1 are overwritten
         o.add_transition(rng.rand(2, 2, 2), rng.randint(0, 3, (2, 2)), -rng.rand(2, 2), rng.rand(2, 2, 2), rng.rand(2) < .2)

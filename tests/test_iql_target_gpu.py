@@ -1,6 +1,6 @@
 """GPU tests of the opt-in target network / Double DQN of the Q-learners ([MODEL_CONFIG] target_update / double_q; include/tsc.h
 tsc_iql_set_target; csrc/tsc_iql_fused.h iql_fused_target_kernel and iql_fused_grad_kernel<.., true>, csrc/tsc_iql.hip for the
-grouped-GEMM path) against the float64 restatement of tests/iql_target_oracle.py.
+grouped-GEMM path) against the float64 restatement of tests/iql_ext_oracle.py.
 
 Shapes: the smallest at which each path can go wrong, by the reasoning of tests/test_iql_gpu.py -- E = 70 x batch 20 = 1400 rows =
 21 x 64 + 56 (several row splits, a ragged last chunk), E = 3 one partial chunk, the grouped-GEMM path for IQL-DNN (TSC_IQL_FUSED=0)
@@ -40,8 +40,8 @@ def _model(scenario, agent, model_type, E, seed=5, **cfg):
 
 
 def _oracle(m, target_update, double_q):
-    from tests.iql_target_oracle import TargetOracleIQL
-    return TargetOracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, m.E, target_update=target_update, double_q=double_q,
+    from tests.iql_ext_oracle import ExtOracleIQL
+    return ExtOracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, m.E, target_update=target_update, double_q=double_q,
                            batch_size=m.n_step, buffer_size=int(m.cfg['buffer_size']), gamma=m.cfg['gamma'],
                            reward_norm=m.cfg['reward_norm'], reward_clip=m.cfg['reward_clip'], max_grad_norm=m.cfg['max_grad_norm'],
                            replay_seed=m.replay_seed)

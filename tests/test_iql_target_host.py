@@ -1,11 +1,11 @@
 """Host-side checks of the opt-in target network / Double DQN of the Q-learners: the float64 restatement the GPU tests compare
-against (tests/iql_target_oracle.py) and the configuration keys (`target_update`, `double_q`)."""
+against (tests/iql_ext_oracle.py) and the configuration keys (`target_update`, `double_q`)."""
 import numpy as np
 import pytest
 import torch
 
 from oracle.iql_oracle import OracleQ
-from tests.iql_target_oracle import TargetOracleIQL, TargetOracleQ
+from tests.iql_ext_oracle import ExtOracleIQL, ExtOracleQ
 
 
 def _dqn_params(rng, nw=5, nt=3, fc=8, h=6, na=4):
@@ -24,7 +24,7 @@ def test_target_equal_to_parameters_is_the_reference_loss(double_q):
     p = _dqn_params(rng)
     obs, acts, nobs, dones, rs = _batch(rng)
     ref = OracleQ(p, 5, 3)
-    new = TargetOracleQ(p, 5, 3, target_update=3, double_q=double_q)
+    new = ExtOracleQ(p, 5, 3, target_update=3, double_q=double_q)
     l0, g0 = ref.loss_and_grads(obs, acts, nobs, dones, rs)
     l1, g1 = new.loss_and_grads(obs, acts, nobs, dones, rs)
     assert l0 == l1 and set(g0) == set(g1)
@@ -42,7 +42,7 @@ def test_hand_computed_targets():
     nobs, acts = np.eye(2), [2, 0]
     rs, gamma = [0.25, -1.0], 0.5
     for double_q, q1 in ((False, [7.0, 8.0]), (True, [1.0, 0.5])):
-        o = TargetOracleQ({'q_w': Wo, 'q_b': b}, 2, 0, gamma=gamma, target_update=1, double_q=double_q)
+        o = ExtOracleQ({'q_w': Wo, 'q_b': b}, 2, 0, gamma=gamma, target_update=1, double_q=double_q)
         o.set_target({'q_w': Wt, 'q_b': b})
         loss, g = o.loss_and_grads(obs, acts, nobs, [False, False], rs)
         y = np.array([0.25 + 0.5 * q1[0], -1.0 + 0.5 * q1[1]])
@@ -58,7 +58,7 @@ def test_hand_computed_targets():
         o.loss_and_grads(obs, acts, nobs, [True, False], rs)
         np.testing.assert_array_equal(o.last_y, [0.25, y[1]])
     # a tie in the online values: the first maximum, like np.argmax
-    o = TargetOracleQ({'q_w': np.array([[3.0, 3.0, 1.0], [0.0, 2.0, 2.0]]), 'q_b': b}, 2, 0, gamma=1.0, target_update=1, double_q=True)
+    o = ExtOracleQ({'q_w': np.array([[3.0, 3.0, 1.0], [0.0, 2.0, 2.0]]), 'q_b': b}, 2, 0, gamma=1.0, target_update=1, double_q=True)
     o.set_target({'q_w': Wt, 'q_b': b})
     o.loss_and_grads(obs, acts, nobs, [False, False], [0.0, 0.0])
     np.testing.assert_array_equal(o.last_astar, [0, 1])
@@ -68,7 +68,7 @@ def test_hand_computed_targets():
 @pytest.mark.parametrize('N', [1, 2, 3])
 def test_refresh_after_every_nth_adam_step_only(N):
     rng = np.random.RandomState(1)
-    o = TargetOracleQ(_dqn_params(rng), 5, 3, target_update=N)
+    o = ExtOracleQ(_dqn_params(rng), 5, 3, target_update=N)
     eq = lambda a, b: all(torch.equal(a[k], b[k]) for k in a)
     assert eq(o.target, o.p)
     frozen = {k: v.clone() for k, v in o.target.items()}
@@ -85,8 +85,8 @@ def test_refresh_after_every_nth_adam_step_only(N):
 def test_vector_oracle_uses_the_target_learners():
     rng = np.random.RandomState(2)
     ps = [_dqn_params(rng), _dqn_params(rng)]
-    o = TargetOracleIQL(ps, [5, 5], [3, 3], [4, 4], 2, target_update=2, double_q=True, batch_size=3, buffer_size=8)
-    assert all(isinstance(q, TargetOracleQ) and q.double_q and q.target_update == 2 for q in o.qs)
+    o = ExtOracleIQL(ps, [5, 5], [3, 3], [4, 4], 2, target_update=2, double_q=True, batch_size=3, buffer_size=8)
+    assert all(isinstance(q, ExtOracleQ) and q.double_q and q.target_update == 2 for q in o.qs)
     for t in range(5):
         o.add_transition(rng.rand(2, 2, 8), rng.randint(0, 4, (2, 2)), -rng.rand(2, 2) * 3000, rng.rand(2, 2, 8), rng.rand(2) < .2)
     o.set_target_params([_dqn_params(rng), _dqn_params(rng)])

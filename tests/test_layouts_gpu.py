@@ -90,8 +90,8 @@ def test_a2c_fused_update_equals_grouped_gemms_on_block_edges_inside_a_tile(name
 
 
 def test_a2c_ppo_k3_on_the_full_head():
-    """Three PPO epochs on head8 (MA2C, LSTM; n_a = 8, 7, 2, 5, 8) against tests/ppo_oracle.py: head_bwd_ppo_kernel has its own copy of the
-    8-lane head mapping.  The case and what it must satisfy on the oracle alone: tests/layouts.py PPO_HEAD8,
+    """Three PPO epochs on head8 (MA2C, LSTM; n_a = 8, 7, 2, 5, 8) against tests/ppo_oracle.py: head_bwd_kernel<true> is an instantiation of
+    its own of the 8-lane head mapping.  The case and what it must satisfy on the oracle alone: tests/layouts.py PPO_HEAD8,
     tests/test_layouts_host.py::test_ppo_head8_conditions."""
     from tests.test_ppo_gpu import _k3
     spec = LY.A2C_LAYOUTS['head8']
@@ -190,7 +190,7 @@ def test_iql_dueling_targets_and_gradient(name, fused_knob, target_update, doubl
 
 
 def test_iql_prioritized_replay_step_at_the_fused_limit(monkeypatch):
-    """One prioritized-replay step (target network + Double DQN, beta 0.4) on q160_edge against tests/iql_per_oracle.py."""
+    """One prioritized-replay step (target network + Double DQN, beta 0.4) on q160_edge against tests/iql_ext_oracle.py."""
     from tests.test_iql_per_gpu import _per_step_vs_oracle
     from tests.test_iql_target_gpu import _model
     name = 'q160_edge'

@@ -1,5 +1,5 @@
 """GPU parity of the opt-in PPO update (include/tsc.h tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats;
-csrc/tsc_model.hip head_bwd_ppo_kernel, gae_kernel) against the float64 PPOOracle of tests/ppo_oracle.py, and of `algo = ppo` with
+csrc/tsc_model.hip head_bwd_kernel<true>, gae_kernel) against the float64 PPOOracle of tests/ppo_oracle.py, and of `algo = ppo` with
 one epoch and lambda = 1 against the A2C update it must then be.
 
 Tolerances are the ones tests/test_model_gpu.py uses for the A2C update: gradients |d| <= 2e-5 max|g| per tensor against the
