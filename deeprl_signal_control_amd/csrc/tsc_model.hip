@@ -30,6 +30,10 @@
 // kernels, split counts) follows from the shapes, the LDS and workspace fits and the knobs of INTEGRATION.md section 5, which
 // are read there and nowhere else.  The forward and the update only switch on the plan; tsc_model_plan / tsc_model_path report it.  The fused
 // kernels exist for the hidden widths of with_fused_width, and each launch derives its template argument from H.
+// Where a kernel's sizes live: next to the kernel, as constexpr functions of its shape -- <kernel>_lds (dynamic LDS, bytes),
+// <kernel>_ws_floats (a split's partial in the split-K workspace) -- written in the constants the kernel carves its pointers by,
+// and a row quantum (kDwK, kW1Chunk, kHbRows) that its row loop steps by and split_rows rounds a split to.  tsc_model_create, the
+// launch sites and the reduce kernels call these; no size expression is restated anywhere else.
 #include "tsc_common.h"
 #include "tsc_gemm.h"
 #include "../../include/tsc.h"
@@ -90,6 +94,7 @@ __device__ __forceinline__ void st_stream4(float *p, const float4 &v) {
 // ------------------------------------------------------------------------------------------------
 constexpr int kWhLd = kG4 + 4;
 constexpr int kHsLd = 64 + 4;
+constexpr size_t lstm_fwd_lds() { return sizeof(float) * (64 * kWhLd + 64 * kHsLd); }      // Whs | hs
 
 template <bool PF>   // PF: prefetch the next step's Z under the MFMAs (training, T > 1); the 1-step rollout
                       // variant keeps the register budget for 2 workgroups per CU
@@ -227,6 +232,7 @@ __global__ void __launch_bounds__(256, PF ? 1 : 2) lstm_fwd_kernel(const float *
 // ------------------------------------------------------------------------------------------------
 constexpr int kDz2Ld = kG4 + 4;   // dz tile [32 env][256 k + 4]
 constexpr int kDh3Ld = kL + 4;    // recurrent dh tile [32 env][64 units + 4]
+constexpr size_t lstm_bwd2_lds() { return sizeof(float) * (32 * kDz2Ld + 32 * kDh3Ld); }    // dzs | dhs
 
 __global__ void __launch_bounds__(256, 2) lstm_bwd2_kernel(const float *__restrict__ params, Layout lay, float *Z,
                                                             const float *Cc, const float *state_bw, const float *dH,
@@ -456,6 +462,7 @@ __global__ void __launch_bounds__(64) head_fwd_kernel(const float *__restrict__ 
 // allocation, this leaves both instantiations' instructions as they were (measured by comparing the assembly, tools/isa_diff.py).
 // Each variant keeps its own statement order where they differ (A2C sums lpa in the dot / ent shuffle loop, PPO before the gradient).
 constexpr int kHbPer = kL * kOut + kOut + kL + 1;      // partial record of a slice: dWo [64][8] | dbo [8] | dWv [64] | dbv
+constexpr int kHbRows = 16;      // samples per pass of the workgroup (its 16 sample groups): a slice is a whole number of passes
 
 template <bool, class T> using PpoArg = T;
 template <bool... PPO_>
@@ -498,7 +505,7 @@ head_bwd_kernel(const float *__restrict__ params, Layout lay, const int *__restr
     const float *hp = Hh + (long long)(2 * a) * N * kL + 4 * c, *hq = Hh + (long long)(2 * a + 1) * N * kL + 4 * c;
     float *dp = dH + (long long)(2 * a) * N * kL + 4 * c, *dq = dH + (long long)(2 * a + 1) * N * kL + 4 * c;
     const float invN = 1.0f / (float)N;
-    for (long long nb = n0; nb < n1; nb += 16) {
+    for (long long nb = n0; nb < n1; nb += kHbRows) {
         [[maybe_unused]] float lpo = 0.f, ratio = 1.f;           // PPO: log pi_old(a_n), pi / pi_old
         [[maybe_unused]] bool clipped = false;
         const long long n = nb + grp;
@@ -716,6 +723,7 @@ __device__ __forceinline__ int sample_action(const float *pi, int na, unsigned l
 // the cumulative distribution (tests/test_model_gpu.py::test_fc_policy_forward_kernels_agree_with_each_other).
 // ------------------------------------------------------------------------------------------------
 constexpr int kFcLdo = 64 + 1;
+constexpr size_t fc_thread_lds(int H) { return sizeof(float) * ((size_t)64 * kFcLdo + (size_t)2 * 64 * (H + 1) + (size_t)2 * 64 * kFcLdo); }
 __global__ void __launch_bounds__(512) policy_fwd_fc_kernel(const float *__restrict__ params, Layout lay, const int *__restrict__ n_act,
                                                            const float *__restrict__ obs, int E, float *__restrict__ pi_out,
                                                            float *__restrict__ v_out, int *action_out, unsigned long long seed,
@@ -809,6 +817,9 @@ __global__ void __launch_bounds__(512) policy_fwd_fc_kernel(const float *__restr
 // wave needs is requested before the first barrier, so the launch costs two L2 round trips plus ~4k cycles of MFMA chains.
 // ------------------------------------------------------------------------------------------------
 constexpr int kFmLd = 33;        // [k or row][32 instances / columns + 1]
+constexpr size_t policy_fwd_fc_mfma_lds(int H) {          // Os | X1s | P2 | X2s
+    return sizeof(float) * ((size_t)64 * kFmLd + (size_t)2 * 32 * (H + 1) + (size_t)8 * 32 * kFmLd + (size_t)2 * 32 * kFcLdo);
+}
 
 template <int NCT>               // H / 32
 __global__ void __launch_bounds__(512, 1)
@@ -1014,6 +1025,8 @@ policy_fwd_fc_mfma_kernel(const float *__restrict__ params, Layout lay, const in
 // and reuse its L2-resident weights.
 // ------------------------------------------------------------------------------------------------
 constexpr int kXLd = 68;
+// XH [H + 64][kXLd] | WoS: head weights [64][8] + bias [8] (+ 8 pad)
+constexpr size_t policy_fwd_fused_lds(int H) { return sizeof(float) * ((size_t)(H + 64) * kXLd + kL * kOut + kOut + 8); }
 
 __global__ void __launch_bounds__(256, 2)
 policy_fwd_fused_kernel(const float *__restrict__ params, Layout lay, const int *__restrict__ n_act,
@@ -1289,6 +1302,10 @@ policy_fwd_fused_kernel(const float *__restrict__ params, Layout lay, const int 
 constexpr int kWsLdx = 36;       // activations [k][32 instances + 4]
 constexpr int kWsLdg = 33;       // gate pre-activations [256 columns][32 instances + 1]
 constexpr int kWsBuf = 8;        // tiles whose logits are buffered before the softmax / sampling pass
+constexpr size_t policy_fwd_ws_lds(int H, int SMAX) {     // XH | Hs | Hn | Gz | WoS | LG | LGp | W1s
+    return sizeof(float) * ((size_t)32 * (H + 64 + 4) + 64 * kWsLdx + (size_t)kL * kWsLdg + (size_t)kG4 * kWsLdg + 528 +
+                            (kWsBuf + 2) * 32 * kOut + (size_t)SMAX * H);
+}
 
 template <int KS2>
 __global__ void __launch_bounds__(512, 1)
@@ -1850,8 +1867,6 @@ __global__ void fill_kernel(float *p, long long n, float v) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-
-// ------------------------------------------------------------------------------------------------
 // LSTM weight gradients of one tower in ONE pass over the n-step batch (tf.gradients of
 // agents/utils.py:88-116 w.r.t. wx, wh, b):   [dWx ; dWh] = [X1 | h_prev]^T dZ,   dbl = colsum(dZ).
 // The output of a tower is only (H+64) x 256, so one workgroup (8 waves, one 32-column strip each, NT = (H+64)/32
@@ -1878,8 +1893,14 @@ __device__ __forceinline__ gfloat_p uniform_ptr(const float *p) {
     return (gfloat_p)(((unsigned long long)hi << 32) | lo);
 }
 
+// Rows per split of a split-K pass: N rows cut into at most S row ranges, each a whole number of the kernel's row quantum
+// (the constant its row loop steps by: kDwK, kW1Chunk, kHbRows).
+constexpr long long split_rows(long long N, int S, int quantum) { return ((N + S - 1) / S + quantum - 1) / quantum * quantum; }
+
 constexpr int kDwKc = 16, kDwKi = 64;     // rows per staging step (sub-chunk) / per LDS buffer (interval between two barriers)
+constexpr int kDwK = 2;                   // rows of one MFMA k-step: the row quantum of a split
 template <int NT> constexpr size_t dwxh_lds() { return sizeof(float) * 2 * kDwKi * (NT * 32 + 4); }
+constexpr long long dwxh_ws_floats(int H) { return (long long)(H + kL + 1) * kG4; }    // a split's partial: [dWx ; dWh ; dbl]
 
 template <int NT>
 __global__ void __launch_bounds__(512, 1)
@@ -1920,7 +1941,7 @@ dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const fl
     const unsigned l0 = sl.r0 * LDA + sl.c0, l1 = sl.r1 * LDA + sl.c1, l2 = sl.r2 * LDA + H + sl.c2; // LDS, floats past the sub-chunk's slot
     const unsigned zb = kh * kG4 + col0 + li;
     f32x4 g0, g1, g2;
-    float bcur[KC / 2], bnxt[KC / 2];
+    float bcur[KC / kDwK], bnxt[KC / kDwK];
     using Clamp = std::true_type;
     using Plain = std::false_type;
     // A rows [n0 + KC c, + KC) -> staging registers.  Plain: every row is inside the split; Clamp: rows past it read its last row.
@@ -1953,15 +1974,15 @@ dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const fl
     auto fetch_b = [&](auto cl, float *b, long long c) {
         if constexpr (decltype(cl)::value) {
 #pragma unroll
-            for (int ks = 0; ks < KC / 2; ++ks) {
-                const long long row = n0 + KC * c + 2 * ks + kh;
+            for (int ks = 0; ks < KC / kDwK; ++ks) {
+                const long long row = n0 + KC * c + kDwK * ks + kh;
                 const float z = dz[((row < n1 ? row : n1 - 1) - kh) * kG4 + zb];
                 b[ks] = row < n1 ? z : 0.f;
             }
         } else {
             const gfloat_p zs = uniform_ptr(dz + (n0 + KC * c) * kG4);
 #pragma unroll
-            for (int ks = 0; ks < KC / 2; ++ks) b[ks] = (zs + 2 * ks * kG4)[zb];
+            for (int ks = 0; ks < KC / kDwK; ++ks) b[ks] = (zs + kDwK * ks * kG4)[zb];
         }
     };
 #ifdef TSC_UPD_STAMPS
@@ -1989,10 +2010,10 @@ dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const fl
         __builtin_amdgcn_sched_barrier(0);
         USTAMP(1, c);
 #pragma unroll
-        for (int ks = 0; ks < KC / 2; ++ks) {
+        for (int ks = 0; ks < KC / kDwK; ++ks) {
             float av[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) av[t] = a[2 * ks * LDA + 32 * t];
+            for (int t = 0; t < NT; ++t) av[t] = a[kDwK * ks * LDA + 32 * t];
             bsum += bcur[ks];
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t], bcur[ks], acc[t], 0, 0, 0);
@@ -2001,7 +2022,7 @@ dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const fl
         __builtin_amdgcn_sched_barrier(0);
         if (!lead) stage();
 #pragma unroll
-        for (int ks = 0; ks < KC / 2; ++ks) bcur[ks] = bnxt[ks];
+        for (int ks = 0; ks < KC / kDwK; ++ks) bcur[ks] = bnxt[ks];
         USTAMP(3, c);
     };
     if (R > 0) {
@@ -2023,7 +2044,7 @@ dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const fl
         }
     }
 #undef USTAMP
-    float *w = ws + ((long long)sp * G + g) * ((long long)(NT * 32 + 1) * kG4);
+    float *w = ws + ((long long)sp * G + g) * dwxh_ws_floats(H);
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -2046,7 +2067,6 @@ __global__ void dwxh_reduce_kernel(const float *__restrict__ ws, int G, int S, l
     grads[g * stride + off + j] = acc;
 }
 
-
 // ------------------------------------------------------------------------------------------------
 // First-layer gradients of one tower in ONE pass over the n-step batch, without ever writing dX1:
 //   dX1 = (dZ Wx^T) * relu'(X1)   (32-row chunks, never leaves the registers)
@@ -2062,11 +2082,68 @@ __global__ void dwxh_reduce_kernel(const float *__restrict__ ws, int G, int S, l
 // against the obs tile (accumulator row = contraction index of the step), only for the 16-feature tiles of W1 that hold a
 // structural non-zero in the column unit.
 // Replaces the dX1 GEMM (second column tile 25 % empty, dZ read twice), the 11 GB dX1 round trip through HBM and the dW1
-// GEMM.  Deterministic: partial dW1 | db1 per (workgroup, row-tile slot), added in that order by dx1w1_reduce2_kernel, which
+// GEMM.  Deterministic: partial dW1 | db1 per (workgroup, row-tile slot), added in that order by w1_reduce_kernel, which
 // also applies the structural zeros of the block-diagonal first layer.
 // ------------------------------------------------------------------------------------------------
 constexpr int kD1Ld = 260;       // dZ chunk [32 rows][256 k + 4]: row-major like HBM, read as 16-byte A-operand quads
 constexpr int kObLd = 68;        // obs chunk [32 rows][64 features + 4]
+constexpr int kW1Chunk = 32;     // rows per chunk: the row quantum of a split (dx1w1_kernel2 and fc_bwd_kernel)
+// Rows of one row-tile slot of a first-layer partial: 64 feature rows of dW1 (four 16-feature tiles) + the db1 row.  Tied to
+// narrow_obs (SMAX <= 64), which tsc_model_create requires of every handle that runs these kernels.
+constexpr int kW1Rows = 64 + 1;
+constexpr size_t dx1w1_lds() { return sizeof(float) * 2 * kW1Chunk * (kD1Ld + kObLd); }       // Az | Ob
+// a split's first-layer partial: two row-tile slots of dW1 | db1 (w1_flush writes them, w1_reduce_kernel adds them)
+constexpr long long w1_ws_floats(int H) { return (long long)2 * kW1Rows * H; }
+
+// ---- the first-layer gradient body shared by dx1w1_kernel2 (LSTM) and fc_bwd_kernel (FcACPolicy)
+// dW1 += obs^T dX1 for row tile r of a column unit: c is the tile's dZ W^T accumulator, xm its relu mask; contraction step i
+// takes rows 16 r + 4 kq + i = the accumulator's own rows.  CLAMP: rows from n1 on count as zero.
+template <bool CLAMP>
+__device__ __forceinline__ void w1_tail(const float *Ob, int buf, int r, int kq, int n, const f32x4 &c, const float (&xm)[4],
+                                        long long row, long long n1, int fm, f32x4 (&aw)[4], float &bs) {
+    const float *Os = Ob + ((long long)buf * 32 + 16 * r + 4 * kq) * kObLd + n;
+    // all 16 obs operands first, unconditionally (the registers of the A-operand quads are free by now): with the
+    // feature-tile test around every single MFMA each of them sat in a basic block of its own -- LDS read, wait, MFMA --
+    // and paid its operand's LDS latency alone (round 5: 16 % of the kernel)
+    float os[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) os[4 * ft + i] = Os[i * kObLd + 16 * ft];
+    float d[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        d[i] = (xm[i] > 0.f && (!CLAMP || row + 16 * r + 4 * kq + i < n1)) ? c[i] : 0.f;
+        bs += d[i];
+    }
+#pragma unroll
+    for (int ft = 0; ft < 4; ++ft)
+        if ((fm >> ft) & 1) {                                   // wave-uniform: one test per feature tile
+#pragma unroll
+            for (int i = 0; i < 4; ++i) aw[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(os[4 * ft + i], d[i], aw[ft], 0, 0, 0);
+        }
+}
+// A column unit's partial dW1 | db1 into the split's record w: slot 0 = row tile 0 (or both tiles of a unit owned by one wave, which
+// then zeroes slot 1), slot 1 = row tile 1 alone.
+template <int H>
+__device__ __forceinline__ void w1_flush(float *w, int kq, const f32x4 (&aw)[4], float bs, int col, bool r0, bool r1) {
+    float *w0 = w + (long long)((r0 ? 0 : 1) * kW1Rows) * H;
+    float *wz = w + (long long)kW1Rows * H;                 // slot 1, zeroed by the owner of both tiles
+#pragma unroll
+    for (int ft = 0; ft < 4; ++ft)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int f = 16 * ft + 4 * kq + i;
+            w0[(long long)f * H + col] = aw[ft][i];
+            if (r0 && r1) wz[(long long)f * H + col] = 0.f;
+        }
+    bs += __shfl_xor(bs, 16, 64);
+    bs += __shfl_xor(bs, 32, 64);
+    if (kq == 0) {
+        w0[(long long)(kW1Rows - 1) * H + col] = bs;
+        if (r0 && r1) wz[(long long)(kW1Rows - 1) * H + col] = 0.f;
+    }
+}
 
 template <int NCU>   // H / 16
 __global__ void __launch_bounds__(512, 1)
@@ -2078,7 +2155,7 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     static_assert(NHU % 8 == 0 || NHU % 8 == 4, "H must be a multiple of 32");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float *Az = (float *)smem_raw;                              // [2][32][kD1Ld]
-    float *Ob = Az + 2 * 32 * kD1Ld;                            // [2][32][kObLd]
+    float *Ob = Az + 2 * kW1Chunk * kD1Ld;                      // [2][32][kObLd]
     const int g = blockIdx.x % G, sp = blockIdx.x / G, a = g >> 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n = lane & 15, kq = lane >> 4;
     const long long n0 = (long long)sp * rows_per_split;
@@ -2087,8 +2164,9 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     const float *dz = dZ + (long long)g * N * kG4, *x1 = X1 + (long long)g * N * H;
     const long long AS = (long long)A * SMAX;
     const int sq = SMAX >> 2;
-    float *w = ws + ((long long)sp * G + g) * ((long long)2 * 65 * H);
-    // this wave's half units [st, st + cnt): unit = h >> 1, row tile = h & 1
+    float *w = ws + ((long long)sp * G + g) * w1_ws_floats(H);
+    // this wave's half units [st, st + cnt): unit = h >> 1, row tile = h & 1.  (These five lines are also in fc_bwd_kernel: as a
+    // shared struct or pair of functions they changed the register allocation or the instruction count of both kernels.)
     const int st = wave < 4 ? wave * CHI : 4 * CHI + (wave - 4) * CLO, cnt = wave < 4 ? CHI : CLO;
     const int U0 = st >> 1;
     const bool a00 = 2 * U0 >= st, a01 = 2 * U0 + 1 < st + cnt, a10 = 2 * U0 + 2 < st + cnt, a11 = 2 * U0 + 3 < st + cnt;
@@ -2096,7 +2174,7 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     const int col0 = 16 * U0 + n, col1 = 16 * U1 + n;
     // W1 is block-structured (obs rows of one kind feed one block of hidden columns, agents/policies.py:41-61): of the four
     // 16-feature tiles of dW1 a column unit only accumulates the ones with a structural non-zero (two of four on the
-    // reference's nets: 72 instead of 80 MFMAs per 16 x 16 tile); the others stay zero, as dx1w1_reduce2_kernel writes them
+    // reference's nets: 72 instead of 80 MFMAs per 16 x 16 tile); the others stay zero, as w1_reduce_kernel writes them
     const int fm0 = ftm[a * NCU + U0], fm1 = ftm[a * NCU + U1];
     // stationary B operands: bwX[4 j + c] = Wx^T[k = 16 j + 4 kq + c][col]
     float bw0[64], bw1[64];
@@ -2211,30 +2289,7 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
             }
             if (!r0) { c1 = c0; }
         }
-        // dW1 += obs^T dX1 : contraction step i takes rows 16 r + 4 kq + i = the accumulator's own rows
-        auto tail = [&](int r, const f32x4 &c, const float (&xm)[4]) {
-            const float *Os = Ob + ((long long)buf * 32 + 16 * r + 4 * kq) * kObLd + n;
-            // all 16 obs operands first, unconditionally (the registers of the A-operand quads are free by now): with the
-            // feature-tile test around every single MFMA each of them sat in a basic block of its own -- LDS read, wait, MFMA --
-            // and paid its operand's LDS latency alone (round 5: 16 % of the kernel)
-            float os[16];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int ft = 0; ft < 4; ++ft) os[4 * ft + i] = Os[i * kObLd + 16 * ft];
-            float d[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                d[i] = (xm[i] > 0.f && (!clamp || row + 16 * r + 4 * kq + i < n1)) ? c[i] : 0.f;
-                bs += d[i];
-            }
-#pragma unroll
-            for (int ft = 0; ft < 4; ++ft)
-                if ((fm >> ft) & 1) {                                   // wave-uniform: one test per feature tile
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) aw[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(os[4 * ft + i], d[i], aw[ft], 0, 0, 0);
-                }
-        };
+        auto tail = [&](int r, const f32x4 &c, const float (&xm)[4]) { w1_tail<clamp>(Ob, buf, r, kq, n, c, xm, row, n1, fm, aw, bs); };
         if (r0) tail(0, c0, xm0);
         if (r1) tail(1, c1, xm1);
     };
@@ -2269,54 +2324,13 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
         int buf = 0;
         long long row = n0;
         // full chunks whose successor is full too: no row compare, clamp or select anywhere in the loop
-        for (; row + 64 <= n1; row += 32, buf ^= 1) chunk(Plain{}, buf, row);
-        for (; row < n1; row += 32, buf ^= 1) chunk(Clamp{}, buf, row);
+        for (; row + 2 * kW1Chunk <= n1; row += kW1Chunk, buf ^= 1) chunk(Plain{}, buf, row);
+        for (; row < n1; row += kW1Chunk, buf ^= 1) chunk(Clamp{}, buf, row);
     }
 #undef USTAMP
-    // partial results: slot 0 = row tile 0 (or both tiles of a unit owned by one wave), slot 1 = row tile 1 alone
-    auto flush = [&](const f32x4 (&aw)[4], float bs, int col, bool r0, bool r1) {
-        float *w0 = w + (long long)((r0 ? 0 : 1) * 65) * H;
-        float *wz = w + (long long)65 * H;                      // slot 1, zeroed by the owner of both tiles
-#pragma unroll
-        for (int ft = 0; ft < 4; ++ft)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int f = 16 * ft + 4 * kq + i;
-                w0[(long long)f * H + col] = aw[ft][i];
-                if (r0 && r1) wz[(long long)f * H + col] = 0.f;
-            }
-        bs += __shfl_xor(bs, 16, 64);
-        bs += __shfl_xor(bs, 32, 64);
-        if (kq == 0) {
-            w0[(long long)64 * H + col] = bs;
-            if (r0 && r1) wz[(long long)64 * H + col] = 0.f;
-        }
-    };
+    auto flush = [&](const f32x4 (&aw)[4], float bs, int col, bool r0, bool r1) { w1_flush<H>(w, kq, aw, bs, col, r0, r1); };
     if (a00 || a01) flush(accW[0], bsum0, col0, a00, a01);
     if (a10 || a11) flush(accW[1], bsum1, col1, a10, a11);
-}
-
-// grads[g][oW1 .. +SMAX*H) and [ob1 .. +H) = sum over (split, row-tile slot) in that order; structural zeros of W1 applied
-__global__ void dx1w1_reduce2_kernel(const float *__restrict__ ws, int G, int S, int H, int SMAX, const int16_t *__restrict__ rr,
-                                     float *__restrict__ grads, long long stride, long long oW1, long long ob1) {
-    const long long per = (long long)65 * H, out = (long long)(SMAX + 1) * H;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= out * G) return;
-    const long long g = i / out, j = i % out;
-    const int f = (int)(j / H), n = (int)(j % H);
-    const long long src = f < SMAX ? j : (long long)64 * H + n;
-    float acc = 0.f;
-    for (int s = 0; s < S; ++s) {
-        acc += ws[(((long long)s * G + g) * 2 + 0) * per + src];
-        acc += ws[(((long long)s * G + g) * 2 + 1) * per + src];
-    }
-    if (f < SMAX) {
-        const int16_t *q = rr + ((g >> 1) * SMAX + f) * 2;
-        if (n < q[0] || n >= q[1]) acc = 0.f;
-        grads[g * stride + oW1 + j] = acc;
-    } else {
-        grads[g * stride + ob1 + n] = acc;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2330,9 +2344,13 @@ __global__ void dx1w1_reduce2_kernel(const float *__restrict__ ws, int G, int S,
 // LDS, which serves the relu mask (from HBM per lane before) and is the A operand of the dWfc tiles: H/16 x 4 tiles of
 // 16 x 16, wave w owns unit column w & 3 and every second hidden unit from w >> 2 (5 tiles at H = 160, K = the chunk's 32
 // rows).  Replaces three grouped GEMMs (dWfc, dX1 with its 1-GB round trip through HBM, dW1 at a quarter-empty tile).
-// Deterministic like its model: fixed row splits, partial sums folded in split order by fc_bwd_reduce_kernel.
+// Deterministic like its model: fixed row splits, partial sums folded in split order by w1_reduce_kernel.
 // ------------------------------------------------------------------------------------------------
 constexpr int kFbLdz = kL + 4;   // dZ chunk [32 rows][64 k + 4]: row-major like HBM, read as 16-byte A-operand quads
+constexpr int fc_bwd_ldx(int H) { return H + 16; }      // X1 chunk rows: (LDX % 32) == 16 -> the four k rows of an MFMA step sit on two bank halves
+constexpr size_t fc_bwd_lds(int H) { return sizeof(float) * 2 * kW1Chunk * (kFbLdz + kObLd + fc_bwd_ldx(H)); }      // Az | Ob | Xs
+constexpr long long fc2_ws_floats(int H) { return (long long)(H + 1) * kL; }                        // a split's second-layer partial: dWfc | dbfc
+constexpr long long fc_bwd_ws_floats(int H) { return w1_ws_floats(H) + fc2_ws_floats(H); }      // a split's record: first layer, then second
 
 template <int NCU>   // H / 16
 __global__ void __launch_bounds__(512, 1)
@@ -2342,14 +2360,14 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     constexpr int H = 16 * NCU, NHU = 2 * NCU;                  // half units (column unit x row tile) per chunk
     constexpr int CHI = (NHU + 7) / 8, CLO = NHU / 8;           // tiles of waves 0..3 / 4..7
     static_assert(NHU % 8 == 0 || NHU % 8 == 4, "H must be a multiple of 32");
-    constexpr int LDX = H + 16;                                 // X1 chunk rows: (LDX % 32) == 16 -> the four k rows of an MFMA step sit on two bank halves
+    constexpr int LDX = fc_bwd_ldx(H);
     constexpr int NF = NCU / 2;                                 // dWfc tiles per wave
     constexpr int XQ = H / 4, NXQ = 32 * XQ, NXL = (NXQ + 511) / 512;
     static_assert(NXL <= 4, "X1 staging slots");             // 4 at H = 224 (MA2C-FC, large_grid): 32 x 56 quads
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     float *Az = (float *)smem_raw;                              // [2][32][kFbLdz]
-    float *Ob = Az + 2 * 32 * kFbLdz;                           // [2][32][kObLd]
-    float *Xs = Ob + 2 * 32 * kObLd;                            // [2][32][LDX]
+    float *Ob = Az + 2 * kW1Chunk * kFbLdz;                     // [2][32][kObLd]
+    float *Xs = Ob + 2 * kW1Chunk * kObLd;                      // [2][32][LDX]
     const int g = blockIdx.x % G, sp = blockIdx.x / G, a = g >> 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n = lane & 15, kq = lane >> 4;
     const long long n0 = (long long)sp * rows_per_split;
@@ -2358,10 +2376,10 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     const float *dz = dZ + (long long)g * N * kL, *x1 = X1 + (long long)g * N * H;
     const long long AS = (long long)A * SMAX;
     const int sq = SMAX >> 2;
-    constexpr long long kPer1 = (long long)65 * H, kPerF = (long long)(H + 1) * kL;
-    float *w = ws + ((long long)sp * G + g) * (2 * kPer1 + kPerF);
-    float *wF = w + 2 * kPer1;
-    // ---- first layer: this wave's half units [st, st + cnt): unit = h >> 1, row tile = h & 1 (as in dx1w1_kernel2)
+    float *w = ws + ((long long)sp * G + g) * fc_bwd_ws_floats(H);
+    float *wF = w + w1_ws_floats(H);
+    // ---- first layer: this wave's half units [st, st + cnt): unit = h >> 1, row tile = h & 1 (the five lines of dx1w1_kernel2,
+    // repeated here for the reason given there)
     const int st = wave < 4 ? wave * CHI : 4 * CHI + (wave - 4) * CLO, cnt = wave < 4 ? CHI : CLO;
     const int U0 = st >> 1;
     const bool a00 = 2 * U0 >= st, a01 = 2 * U0 + 1 < st + cnt, a10 = 2 * U0 + 2 < st + cnt, a11 = 2 * U0 + 3 < st + cnt;
@@ -2456,27 +2474,8 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
                 c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(q.w, bw[4 * j + 3], c1, 0, 0, 0);
             }
         }
-        // dW1 += obs^T dX1 : contraction step i takes rows 16 r + 4 kq + i = the accumulator's own rows
-        auto tail = [&](int r, const f32x4 &c, const float (&xm)[4]) {
-            const float *Os = Ob + ((long long)buf * 32 + 16 * r + 4 * kq) * kObLd + n;
-            float os[16];                                      // all obs operands first (see dx1w1_kernel2: one test per feature tile)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int ft = 0; ft < 4; ++ft) os[4 * ft + i] = Os[i * kObLd + 16 * ft];
-            float d[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                d[i] = xm[i] > 0.f ? c[i] : 0.f;               // rows past the split: c is exactly zero (zero dZ rows)
-                bs += d[i];
-            }
-#pragma unroll
-            for (int ft = 0; ft < 4; ++ft)
-                if ((fm >> ft) & 1) {                                   // wave-uniform
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) aw[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(os[4 * ft + i], d[i], aw[ft], 0, 0, 0);
-                }
-        };
+        // no row clamp: for rows past the split c is exactly zero (zero dZ rows)
+        auto tail = [&](int r, const f32x4 &c, const float (&xm)[4]) { w1_tail<false>(Ob, buf, r, kq, n, c, xm, row, n1, fm, aw, bs); };
         if (r0) tail(0, c0, xm0);
         if (r1) tail(1, c1, xm1);
     };
@@ -2485,7 +2484,7 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
         put(0);
         __syncthreads();
         int buf = 0;
-        for (long long row = n0; row < n1; row += 32, buf ^= 1) {
+        for (long long row = n0; row < n1; row += kW1Chunk, buf ^= 1) {
             fetch(row + 32);                                    // lands while this chunk computes
             {   // dWfc += X1^T dZ: A[m = hidden][k = row] from the X1 chunk, B[k = row][n = unit] from the dZ chunk
                 const float *Bz = Az + ((long long)buf * 32 + kq) * kFbLdz + 16 * c2 + n;
@@ -2505,25 +2504,7 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
             __syncthreads();
         }
     }
-    // partial results of the first layer: slot 0 = row tile 0 (or both tiles of a unit owned by one wave), slot 1 = row tile 1 alone
-    auto flush = [&](const f32x4 (&aw)[4], float bs, int col, bool r0, bool r1) {
-        float *w0 = w + (long long)((r0 ? 0 : 1) * 65) * H;
-        float *wz = w + (long long)65 * H;                      // slot 1, zeroed by the owner of both tiles
-#pragma unroll
-        for (int ft = 0; ft < 4; ++ft)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int f = 16 * ft + 4 * kq + i;
-                w0[(long long)f * H + col] = aw[ft][i];
-                if (r0 && r1) wz[(long long)f * H + col] = 0.f;
-            }
-        bs += __shfl_xor(bs, 16, 64);
-        bs += __shfl_xor(bs, 32, 64);
-        if (kq == 0) {
-            w0[(long long)64 * H + col] = bs;
-            if (r0 && r1) wz[(long long)64 * H + col] = 0.f;
-        }
-    };
+    auto flush = [&](const f32x4 (&aw)[4], float bs, int col, bool r0, bool r1) { w1_flush<H>(w, kq, aw, bs, col, r0, r1); };
     if (a00 || a01) flush(accW[0], bsum0, col0, a00, a01);
     if (a10 || a11) flush(accW[1], bsum1, col1, a10, a11);
     // second layer: accF[j][i] = dWfc[hidden 16 (hu0 + 2 j) + 4 kq + i][unit 16 c2 + n]
@@ -2537,10 +2518,13 @@ fc_bwd_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const 
     if (kq == 0 && hu0 == 0) wF[(long long)H * kL + 16 * c2 + n] = bsumF;
 }
 
-// grads[g]: W1 | b1 (sum over (split, row-tile slot), structural zeros of W1 applied) and Wfc | bfc (sum over splits), in order
-__global__ void fc_bwd_reduce_kernel(const float *__restrict__ ws, int G, int S, int H, int SMAX, const int16_t *__restrict__ rr,
-                                     float *__restrict__ grads, long long stride, long long oW1, long long ob1, long long oWx) {
-    const long long per1 = (long long)65 * H, perF = (long long)(H + 1) * kL, per = 2 * per1 + perF;
+// The reduce pass of dx1w1_kernel2 and fc_bwd_kernel.  A split's record is the first-layer partial (w1_ws_floats) followed by perF
+// floats of a second-layer partial (fc2_ws_floats; 0 after dx1w1_kernel2).  grads[g]: W1 | b1 = sum over (split, row-tile slot) in
+// that order, structural zeros of W1 applied; [oWx, oWx + perF) = Wfc | bfc = sum over splits in order.
+__global__ void w1_reduce_kernel(const float *__restrict__ ws, int G, int S, int H, int SMAX, long long perF,
+                                 const int16_t *__restrict__ rr, float *__restrict__ grads, long long stride, long long oW1,
+                                 long long ob1, long long oWx) {
+    const long long per1 = (long long)kW1Rows * H, per = w1_ws_floats(H) + perF;
     const long long out1 = (long long)(SMAX + 1) * H, out = out1 + perF;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= out * G) return;
@@ -2548,7 +2532,7 @@ __global__ void fc_bwd_reduce_kernel(const float *__restrict__ ws, int G, int S,
     float acc = 0.f;
     if (j < out1) {
         const int f = (int)(j / H), n = (int)(j % H);
-        const long long src = f < SMAX ? j : (long long)64 * H + n;
+        const long long src = f < SMAX ? j : (long long)(kW1Rows - 1) * H + n;
         for (int s = 0; s < S; ++s) {
             const float *b = ws + ((long long)s * G + g) * per;
             acc += b[src];
@@ -2563,7 +2547,7 @@ __global__ void fc_bwd_reduce_kernel(const float *__restrict__ ws, int G, int S,
         }
     } else {
         const long long jj = j - out1;                         // Wfc [H][64] | bfc [64] are contiguous in the layout
-        for (int s = 0; s < S; ++s) acc += ws[((long long)s * G + g) * per + 2 * per1 + jj];
+        for (int s = 0; s < S; ++s) acc += ws[((long long)s * G + g) * per + w1_ws_floats(H) + jj];
         grads[g * stride + oWx + jj] = acc;
     }
 }
@@ -2575,8 +2559,19 @@ constexpr size_t kLdsMax = 160 * 1024;      // LDS of one workgroup on gfx950
 // The hidden widths H = n_fc_wave + n_fc_fp + n_fc_wait the fused kernels are instantiated for.  with_fused_width calls
 // f(std::integral_constant<int, H>{}) for one of them and returns false for any other H; every launch site derives its
 // template argument from H.  bench.py:fused_update_kernels mirrors this list: change both together.
-template <int... W, class F> bool with_width(int H, F &&f) { return ((H == W && (f(std::integral_constant<int, W>{}), true)) || ...); }
-template <class F> bool with_fused_width(int H, F &&f) { return with_width<128, 160, 192, 224>(H, f); }
+template <int... W> struct Widths {};
+using FusedWidths = Widths<128, 160, 192, 224>;
+template <int... W, class F> bool with_width(Widths<W...>, int H, F &&f) { return ((H == W && (f(std::integral_constant<int, W>{}), true)) || ...); }
+template <class F> bool with_fused_width(int H, F &&f) { return with_width(FusedWidths{}, H, f); }
+
+// Every kernel's dynamic LDS is the constexpr function next to it, in bytes.  The ones that depend on nothing but a fused width fit
+// by construction, so tsc_model_create has no runtime test (and no failure path) for them; it compares the others (Tile, Ws, FcThread:
+// any H, SMAX) with kLdsMax where it picks the forward.
+template <int... W> constexpr bool fused_kernels_fit(Widths<W...>) {
+    return ((policy_fwd_fc_mfma_lds(W) <= kLdsMax && dwxh_lds<(W + kL) / 32>() <= kLdsMax && fc_bwd_lds(W) <= kLdsMax) && ...);
+}
+static_assert(fused_kernels_fit(FusedWidths{}) && dx1w1_lds() <= kLdsMax && lstm_fwd_lds() <= kLdsMax && lstm_bwd2_lds() <= kLdsMax,
+              "a kernel's dynamic LDS exceeds the workgroup's");
 
 // Which kernels a handle runs: decided once in tsc_model_create from its shapes and the knobs.
 enum class Fwd : int8_t {      // (tsc_model_plan reports the enumerator's value: keep the order)
@@ -2627,7 +2622,6 @@ struct tsc_model {
     double *norm2, *stats, *norm_part;
     float *ws, *wsc;            // split-K workspace
     size_t ws_floats, wsc_floats;
-    size_t lds_fwd, lds_fused, lds_ws;
     int inplace;                // the running rollout is written straight into the buffer's slots (tsc_model_rollout_slot): slot T -> 0 carry
     int cached_next;            // next rollout slot whose activations the fused forward will cache; T = all cached
     long long *dbg;
@@ -2663,9 +2657,6 @@ int dense_forward(tsc_model *m, const float *obs, long long rows, float *X1, flo
         return 1;
     return 0;
 }
-
-// dynamic LDS of the per-thread FcACPolicy forward (policy_fwd_fc_kernel), bytes
-size_t fc_thread_lds(int H) { return sizeof(float) * ((size_t)64 * kFcLdo + (size_t)2 * 64 * (H + 1) + (size_t)2 * 64 * kFcLdo); }
 
 }  // namespace
 
@@ -2752,9 +2743,6 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
     m->logp_old = nullptr; m->ppo_ready = 0;
     m->ws_floats = (size_t)48 << 20; m->wsc_floats = (size_t)1 << 20;      // 192 MiB + 4 MiB
     TSC_HIP(m->bufs.alloc(&m->ws, m->ws_floats, true)); TSC_HIP(m->bufs.alloc(&m->wsc, m->wsc_floats, true));
-    m->lds_fwd = sizeof(float) * (64 * kWhLd + 64 * kHsLd);
-    m->lds_fused = sizeof(float) * ((size_t)(L.H + 64) * kXLd + kL * kOut + kOut + 8);   // activations + head weights
-    m->lds_ws = sizeof(float) * ((size_t)32 * (L.H + 64 + 4) + 64 * kWsLdx + (size_t)kL * kWsLdg + (size_t)kG4 * kWsLdg + 528 + (kWsBuf + 2) * 32 * kOut + (size_t)L.SMAX * L.H);
     m->dbg = nullptr;
     m->cached_next = 0;
     m->inplace = 0;
@@ -2771,18 +2759,17 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
     const bool wide = with_fused_width(L.H, [](auto) {}), narrow_obs = L.SMAX <= 64;
     const auto ws_fits = [&](long long per_split) { return (size_t)(P.s_upd * G * per_split) <= m->ws_floats; };
     if (!L.fc) {
-        const bool tile = L.H % 32 == 0 && narrow_obs && m->lds_fused <= kLdsMax;
-        P.fwd = !tile ? Fwd::Dense : wide && m->lds_ws <= kLdsMax && !(fwd_ws && fwd_ws[0] == '0') ? Fwd::Ws : Fwd::Tile;
-        size_t lds_dwxh = 0;
-        with_fused_width(L.H, [&](auto w) { lds_dwxh = dwxh_lds<(decltype(w)::value + kL) / 32>(); });
-        P.dwxh = wide && lds_dwxh <= kLdsMax && !env_int("TSC_UNFUSED_DW", 0) && ws_fits((long long)(L.H + kL + 1) * kG4);
-        P.dx1w1 = wide && narrow_obs && !unfused_dx && ws_fits((long long)2 * 65 * L.H);
+        const bool tile = L.H % 32 == 0 && narrow_obs && policy_fwd_fused_lds(L.H) <= kLdsMax;
+        P.fwd = !tile ? Fwd::Dense
+              : wide && policy_fwd_ws_lds(L.H, L.SMAX) <= kLdsMax && !(fwd_ws && fwd_ws[0] == '0') ? Fwd::Ws : Fwd::Tile;
+        P.dwxh = wide && !env_int("TSC_UNFUSED_DW", 0) && ws_fits(dwxh_ws_floats(L.H));
+        P.dx1w1 = wide && narrow_obs && !unfused_dx && ws_fits(w1_ws_floats(L.H));
     } else {
         // policy_fwd_fc_mfma_kernel fits every fused width (114 KiB of LDS at H = 224); the per-thread kernel does not fit at
         // H = 224 (161 KiB), so MA2C-FC on large_grid with TSC_FC_MFMA=0 takes the dense GEMMs + head_fwd_kernel
         P.fwd = wide && narrow_obs && env_int("TSC_FC_MFMA", 1) ? Fwd::FcMfma
               : L.H % 16 == 0 && narrow_obs && fc_thread_lds(L.H) <= kLdsMax ? Fwd::FcThread : Fwd::Dense;
-        P.fc_bwd = wide && narrow_obs && !unfused_dx && ws_fits((long long)2 * 65 * L.H + (long long)(L.H + 1) * kL);
+        P.fc_bwd = wide && narrow_obs && !unfused_dx && ws_fits(fc_bwd_ws_floats(L.H));
     }
     m->fwd_wgs = (unsigned)(G * P.s_fwd);
     if (P.fwd == Fwd::Ws && env_int("TSC_FWD_XCD", 1) && P.s_fwd > 1 && P.s_fwd < 256) {
@@ -2938,7 +2925,7 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
         tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
         with_fused_width(L.H, [&](auto w) {
             constexpr int H = decltype(w)::value;
-            hipLaunchKernelGGL(policy_fwd_ws_kernel<(H + kL) / 2>, dim3(m->fwd_wgs), dim3(512), m->lds_ws, m->stream, m->params, L,
+            hipLaunchKernelGGL(policy_fwd_ws_kernel<(H + kL) / 2>, dim3(m->fwd_wgs), dim3(512), policy_fwd_ws_lds(H, L.SMAX), m->stream, m->params, L,
                                m->n_act, obs, done, m->state_fw, (int)advance, E, P.s_fwd, pi, v, action, (unsigned long long)seed,
                                (unsigned long long)step, (int)tslot, (long long)m->T * E, m->X1, m->Z, m->Hh, m->Cc, m->Hp, m->dbg, m->Wg,
                                m->krange, m->dbg_tid, m->wgmap);
@@ -2950,7 +2937,7 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
     case Fwd::Tile: {
         const int n_tiles = (E + 63) / 64, per_xcd = (L.G + 7) / 8;
         tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
-        hipLaunchKernelGGL(policy_fwd_fused_kernel, dim3(8 * per_xcd * n_tiles), dim3(256), m->lds_fused, m->stream, m->params,
+        hipLaunchKernelGGL(policy_fwd_fused_kernel, dim3(8 * per_xcd * n_tiles), dim3(256), policy_fwd_fused_lds(L.H), m->stream, m->params,
                            L, m->n_act, obs, done, m->state_fw, (int)advance, E, n_tiles, pi, v, action,
                            (unsigned long long)seed, (unsigned long long)step, m->dbg, (int)tslot, (long long)m->T * E,
                            m->X1, m->Z, m->Hh, m->Cc, m->Hp, m->Wg);
@@ -2959,13 +2946,12 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
         return 0;
     }
     case Fwd::FcMfma: {     // FcACPolicy on the matrix cores (IA2C H = 160 / 128, MA2C H = 224 / 192: large_grid / Monaco)
-        const size_t lds = sizeof(float) * ((size_t)64 * kFmLd + (size_t)2 * 32 * (L.H + 1) + (size_t)8 * 32 * kFmLd + (size_t)2 * 32 * kFcLdo);
         tsc::ProfScope ps(tsc::KID_FUSED_FWD, m->stream);
         with_fused_width(L.H, [&](auto w) {
             constexpr int H = decltype(w)::value;
-            hipLaunchKernelGGL(policy_fwd_fc_mfma_kernel<H / 32>, dim3((unsigned)((E + 31) / 32), (unsigned)L.A), dim3(512), lds, m->stream,
-                               m->params, L, m->n_act, obs, E, pi, v, action, (unsigned long long)seed, (unsigned long long)step,
-                               (int)tslot, (long long)m->T * E, m->X1, m->Hh);
+            hipLaunchKernelGGL(policy_fwd_fc_mfma_kernel<H / 32>, dim3((unsigned)((E + 31) / 32), (unsigned)L.A), dim3(512),
+                               policy_fwd_fc_mfma_lds(H), m->stream, m->params, L, m->n_act, obs, E, pi, v, action,
+                               (unsigned long long)seed, (unsigned long long)step, (int)tslot, (long long)m->T * E, m->X1, m->Hh);
         });
         ps.stop();
         TSC_HIP(hipGetLastError());
@@ -2993,7 +2979,7 @@ static int model_forward(tsc_model *m, const float *obs, const uint8_t *done, fl
         return action ? tsc_model_sample(m, pi, action, seed, step) : 0;
     }
     tsc::ProfScope ps1(tsc::KID_LSTM_FWD, m->stream);
-    hipLaunchKernelGGL(lstm_fwd_kernel<false>, dim3(L.G, (E + 63) / 64), dim3(256), m->lds_fwd, m->stream, m->params, L, m->Z,
+    hipLaunchKernelGGL(lstm_fwd_kernel<false>, dim3(L.G, (E + 63) / 64), dim3(256), lstm_fwd_lds(), m->stream, m->params, L, m->Z,
                        m->state_fw, advance ? m->state_fw : (float *)nullptr, m->Hh, m->Cc, m->Hp, done, 1, E, 0);
     ps1.stop();
     tsc::ProfScope ps3(tsc::KID_HEAD_FWD, m->stream);
@@ -3050,8 +3036,7 @@ static int launch_head_bwd(tsc_model *m, long long N, double beta, const PpoArgs
     const Layout &L = m->lay;
     hipStream_t st = m->stream;
     int S = (int)((8 * 256 + L.A - 1) / L.A);        // ~8 workgroups per CU
-    long long rps = (N + S - 1) / S;
-    rps = (rps + 15) / 16 * 16;
+    const long long rps = split_rows(N, S, kHbRows);
     S = (int)((N + rps - 1) / rps);
     if ((size_t)((long long)S * L.A * kHbPer) > m->ws_floats) return tsc::fail("head_bwd: workspace too small");
     if (ppo) {
@@ -3086,14 +3071,137 @@ int tsc_model_rollout_slot(tsc_model *m, int32_t t, void *ptrs[6]) {
     return 0;
 }
 
+// The one-pass weight-gradient launches of the update (dwxh, dx1w1 / fc_bwd): the kernel over S x G workgroups of
+// split_rows(N, S, its quantum) rows each, then its reduce pass, under their two profile ids.
+static void launch_dwxh(tsc_model *m, long long N) {        // LSTM: dWx | dWh | dbl
+    const Layout &L = m->lay;
+    const int G = L.G, S = m->plan.s_upd;
+    const long long per = dwxh_ws_floats(L.H);
+    {
+        tsc::ProfScope ps(tsc::KID_DWX_GEMM, m->stream);
+        with_fused_width(L.H, [&](auto w) {
+            constexpr int NT = (decltype(w)::value + kL) / 32;
+            hipLaunchKernelGGL(dwxh_kernel<NT>, dim3((unsigned)(S * G)), dim3(512), dwxh_lds<NT>(), m->stream, m->X1, m->Hp, m->Z, N, G, S,
+                               split_rows(N, S, kDwK), m->ws, m->dbg);
+        });
+    }
+    tsc::ProfScope ps(tsc::KID_DWH_GEMM, m->stream);
+    hipLaunchKernelGGL(dwxh_reduce_kernel, dim3((unsigned)((per * G + 255) / 256)), dim3(256), 0, m->stream, m->ws, G, S, per, m->grads,
+                       L.stride, L.oWx);
+}
+
+// dX1 stays in registers, dW1 | db1 come out of the same pass.  LSTM: dx1w1_kernel2 over the gate gradients in Z; FcACPolicy:
+// fc_bwd_kernel over dZ in dHh, which adds dWfc | dbfc (perF floats of every split's record).
+static void launch_w1(tsc_model *m, long long N) {
+    const Layout &L = m->lay;
+    const int G = L.G, S = m->plan.s_upd;
+    const long long rps = split_rows(N, S, kW1Chunk), perF = L.fc ? fc2_ws_floats(L.H) : 0;
+    {
+        tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
+        with_fused_width(L.H, [&](auto w) {
+            constexpr int H = decltype(w)::value;
+            if (L.fc)
+                hipLaunchKernelGGL(fc_bwd_kernel<H / 16>, dim3((unsigned)(S * G)), dim3(512), fc_bwd_lds(H), m->stream, m->dHh, m->X1, m->WxT,
+                                   m->r_obs, N, G, S, rps, L.A, L.SMAX, m->ws, m->ftmask);
+            else
+                hipLaunchKernelGGL(dx1w1_kernel2<H / 16>, dim3((unsigned)(S * G)), dim3(512), dx1w1_lds(), m->stream, m->Z, m->X1, m->WxT,
+                                   m->r_obs, N, G, S, rps, L.A, L.SMAX, m->ws, m->ftmask, m->dbg);
+        });
+    }
+    tsc::ProfScope ps(tsc::KID_DW1_GEMM, m->stream);
+    const long long tot = ((long long)(L.SMAX + 1) * L.H + perF) * G;
+    hipLaunchKernelGGL(w1_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, m->stream, m->ws, G, S, L.H, L.SMAX, perF,
+                       m->rowrange, m->grads, L.stride, L.oW1, L.ob1, L.oWx);
+}
+
+static int launch_transpose_wx(tsc_model *m) {
+    const Layout &L = m->lay;
+    tsc::ProfScope ps(tsc::KID_TRANSPOSE, m->stream);
+    hipLaunchKernelGGL(transpose_wx_kernel, dim3((unsigned)(((long long)L.G * L.H * L.NZ + 255) / 256)), dim3(256), 0, m->stream, m->params, L,
+                       m->WxT);
+    ps.stop();
+    TSC_HIP(hipGetLastError());
+    return 0;
+}
+
+// dW1 = obs^T dX1 masked to the block-diagonal structure (+ db1), dX1 in place over X1: the end of both unfused updates
+static int dw1_gemm(tsc_model *m, long long N) {
+    const Layout &L = m->lay;
+    return gemm(m, tsc::KID_DW1_GEMM, true, tsc::EPI_ROWRANGE, L.G, L.SMAX, L.H, (int)N, m->r_obs, L.SMAX, L.A * L.SMAX, 2, m->X1, N * L.H, L.H,
+                m->grads + L.oW1, L.stride, L.H, nullptr, 0, nullptr, 0, 0, m->rowrange, L.SMAX, m->grads + L.ob1, L.stride);
+}
+
+// FcACPolicy (agents/policies.py:214-256): Hh = relu(X1 Wfc + bfc); dZ = dH * (Hh > 0) comes out of head_bwd
+static int update_fc(tsc_model *m, long long N, double beta, const PpoArgs *ppo) {
+    const Layout &L = m->lay;
+    const int G = L.G;
+    float *g = m->grads;
+    // (the forward is skipped when the rollout forward cached X1 / Hh of all n_step slots under these very parameters)
+    if (m->cached_next != m->T && dense_forward(m, m->r_obs, N, m->X1, m->Hh)) return tsc::fail("gemm launch failed");
+    if (launch_head_bwd(m, N, beta, ppo)) return tsc::fail("head_bwd failed");       // + dWo, dbo
+    if (launch_transpose_wx(m)) return 1;
+    if (m->plan.fc_bwd) {
+        launch_w1(m, N);
+    } else {
+        if (gemm(m, tsc::KID_DWX_GEMM, true, tsc::EPI_NONE, G, L.H, kL, (int)N, m->X1, N * L.H, L.H, 1, m->dHh, N * kL, kL, g + L.oWx,
+                 L.stride, kL, nullptr, 0, nullptr, 0, 0, nullptr, 0, g + L.obl, L.stride)) return tsc::fail("gemm failed");
+        if (gemm(m, tsc::KID_DX1_GEMM, false, tsc::EPI_MASK_POS, G, (int)N, L.H, kL, m->dHh, N * kL, kL, 1, m->WxT, (long long)L.H * kL, L.H,
+                 m->X1, N * L.H, L.H, nullptr, 0, m->X1, N * L.H, L.H, nullptr, 0, nullptr, 0)) return tsc::fail("gemm failed");
+        if (dw1_gemm(m, N)) return tsc::fail("gemm failed");
+    }
+    TSC_HIP(hipGetLastError());
+    m->cached_next = 0;                               // the update consumes the cache
+    return 0;
+}
+
+// LstmACPolicy: forward with stored activations, from the backward state (agents/policies.py:144-152).  The rollout ran with
+// these very parameters from this very state, so when the fused forward cached all n_step slots (X1, gates, c, h, masked
+// h_prev) the graph does not have to be evaluated a second time.
+static int update_lstm(tsc_model *m, long long N, double beta, const PpoArgs *ppo) {
+    const Layout &L = m->lay;
+    const int G = L.G, E = m->E, T = m->T;
+    hipStream_t st = m->stream;
+    float *g = m->grads;
+    if (m->cached_next != T) {
+        if (dense_forward(m, m->r_obs, N, m->X1, m->Z)) return tsc::fail("gemm launch failed");
+        tsc::ProfScope ps2(tsc::KID_LSTM_FWD, m->stream);
+        hipLaunchKernelGGL(lstm_fwd_kernel<true>, dim3((unsigned)G, (unsigned)((E + 63) / 64)), dim3(256), lstm_fwd_lds(), st, m->params, L,
+                           m->Z, m->state_bw, (float *)nullptr, m->Hh, m->Cc, m->Hp, m->r_done, T, E, 1);
+        ps2.stop();
+    }
+    if (launch_head_bwd(m, N, beta, ppo)) return tsc::fail("head_bwd failed");           // + dWo, dbo
+    tsc::ProfScope ps8(tsc::KID_LSTM_BWD, m->stream);
+    hipLaunchKernelGGL(lstm_bwd2_kernel, dim3((unsigned)G, (unsigned)((E + 31) / 32)), dim3(256), lstm_bwd2_lds(), st, m->params, L, m->Z,
+                       m->Cc, m->state_bw, m->dHh, m->r_done, T, E);
+    ps8.stop();
+    if (launch_transpose_wx(m)) return 1;
+    // dWh = Hp^T dZ (+ dbl) ; dWx = X1^T dZ        (dWo = Hh^T dL and dbo came out of head_bwd)
+    if (m->plan.dwxh) {
+        launch_dwxh(m, N);
+    } else {
+        if (gemm(m, tsc::KID_DWH_GEMM, true, tsc::EPI_NONE, G, kL, kG4, (int)N, m->Hp, N * kL, kL, 1, m->Z, N * kG4, kG4, g + L.oWh, L.stride,
+                 kG4, nullptr, 0, nullptr, 0, 0, nullptr, 0, g + L.obl, L.stride)) return tsc::fail("gemm failed");
+        if (gemm(m, tsc::KID_DWX_GEMM, true, tsc::EPI_NONE, G, L.H, kG4, (int)N, m->X1, N * L.H, L.H, 1, m->Z, N * kG4, kG4, g + L.oWx, L.stride,
+                 kG4, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0)) return tsc::fail("gemm failed");
+    }
+    if (m->plan.dx1w1) {
+        launch_w1(m, N);
+    } else {
+        // dX1 = (dZ Wx^T) * relu'(X1), in place over X1
+        if (gemm(m, tsc::KID_DX1_GEMM, false, tsc::EPI_MASK_POS, G, (int)N, L.H, kG4, m->Z, N * kG4, kG4, 1, m->WxT, (long long)L.H * kG4, L.H,
+                 m->X1, N * L.H, L.H, nullptr, 0, m->X1, N * L.H, L.H, nullptr, 0, nullptr, 0)) return tsc::fail("gemm failed");
+        if (dw1_gemm(m, N)) return tsc::fail("gemm failed");
+    }
+    TSC_HIP(hipGetLastError());
+    m->cached_next = 0;                               // the update consumes the cache
+    return 0;
+}
+
 // The update's first half.  ppo == null: the A2C update.  Otherwise epoch ppo->epoch of a PPO update: the returns / advantages are
 // taken at epoch 0 only (from the rollout's stored values), epoch 0 reads the rollout's activation cache when it is valid, and every
 // later epoch finds the cache consumed (cached_next == 0) and takes the re-forward branch from state_bw with the current parameters.
 static int compute_grads_impl(tsc_model *m, const float *R_boot, double beta, const PpoArgs *ppo) {
-    const Layout &L = m->lay;
-    const Plan &P = m->plan;
-    const long long E = m->E, T = m->T, N = E * T, A = L.A, G = L.G;
-    const int AS = L.A * L.SMAX, S = P.s_upd;
+    const long long E = m->E, T = m->T, A = m->lay.A;
     hipStream_t st = m->stream;
     TSC_HIP(hipMemsetAsync(m->stats, 0, sizeof(double) * A * (ppo ? 6 : 4), st));
     if (!ppo || (ppo->epoch == 0 && ppo->lambda == 1.0)) {
@@ -3105,119 +3213,7 @@ static int compute_grads_impl(tsc_model *m, const float *R_boot, double beta, co
         hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((E * A + 255) / 256)), dim3(256), 0, st, m->r_rew, m->r_val, m->r_done, R_boot,
                            (int)T, (int)E, (int)A, m->gamma, ppo->lambda, m->rnorm, m->rclip, m->Rs, m->Advs);
     }
-    float *g = m->grads;
-    if (L.fc) {
-        // FcACPolicy (agents/policies.py:214-256): Hh = relu(X1 Wfc + bfc); dZ = dH * (Hh > 0) comes out of head_bwd
-        // (skipped when the rollout forward cached X1 / Hh of all n_step slots under these very parameters)
-        if (m->cached_next != (int)T && dense_forward(m, m->r_obs, N, m->X1, m->Hh)) return tsc::fail("gemm launch failed");
-        if (launch_head_bwd(m, N, beta, ppo)) return tsc::fail("head_bwd failed");       // + dWo, dbo
-        tsc::ProfScope ps9(tsc::KID_TRANSPOSE, m->stream);
-        hipLaunchKernelGGL(transpose_wx_kernel, dim3((unsigned)((G * L.H * L.NZ + 255) / 256)), dim3(256), 0, st, m->params, L, m->WxT);
-        ps9.stop();
-        TSC_HIP(hipGetLastError());
-        if (P.fc_bwd) {
-            // both layers' weight gradients in one pass, dX1 never leaves the registers (fc_bwd_kernel)
-            long long rps = (N + S - 1) / S;
-            rps = (rps + 31) / 32 * 32;                  // whole 32-row chunks
-            const size_t lds = sizeof(float) * (2 * 32 * kFbLdz + 2 * 32 * kObLd + 2 * 32 * (L.H + 16));
-            {
-                tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
-                with_fused_width(L.H, [&](auto w) {
-                    hipLaunchKernelGGL(fc_bwd_kernel<decltype(w)::value / 16>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->dHh, m->X1,
-                                       m->WxT, m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask);
-                });
-            }
-            {
-                tsc::ProfScope ps(tsc::KID_DW1_GEMM, m->stream);
-                const long long tot = ((long long)(L.SMAX + 1) * L.H + (long long)(L.H + 1) * kL) * G;
-                hipLaunchKernelGGL(fc_bwd_reduce_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m->ws, (int)G, S, L.H, L.SMAX,
-                                   m->rowrange, g, L.stride, L.oW1, L.ob1, L.oWx);
-            }
-            TSC_HIP(hipGetLastError());
-            m->cached_next = 0;
-            return 0;
-        }
-        if (gemm(m, tsc::KID_DWX_GEMM, true, tsc::EPI_NONE, (int)G, L.H, kL, (int)N, m->X1, N * L.H, L.H, 1, m->dHh, N * kL, kL, g + L.oWx,
-                 L.stride, kL, nullptr, 0, nullptr, 0, 0, nullptr, 0, g + L.obl, L.stride)) return tsc::fail("gemm failed");
-        if (gemm(m, tsc::KID_DX1_GEMM, false, tsc::EPI_MASK_POS, (int)G, (int)N, L.H, kL, m->dHh, N * kL, kL, 1, m->WxT, (long long)L.H * kL, L.H,
-                 m->X1, N * L.H, L.H, nullptr, 0, m->X1, N * L.H, L.H, nullptr, 0, nullptr, 0)) return tsc::fail("gemm failed");
-    } else {
-    // forward with stored activations, from the backward state (agents/policies.py:144-152).  The rollout
-    // ran with these very parameters from this very state, so when the fused forward cached all n_step
-    // slots (X1, gates, c, h, masked h_prev) the graph does not have to be evaluated a second time.
-    if (m->cached_next != (int)T) {
-        if (dense_forward(m, m->r_obs, N, m->X1, m->Z)) return tsc::fail("gemm launch failed");
-        tsc::ProfScope ps2(tsc::KID_LSTM_FWD, m->stream);
-        hipLaunchKernelGGL(lstm_fwd_kernel<true>, dim3((unsigned)G, (unsigned)((E + 63) / 64)), dim3(256), m->lds_fwd, st, m->params, L,
-                           m->Z, m->state_bw, (float *)nullptr, m->Hh, m->Cc, m->Hp, m->r_done, (int)T, (int)E, 1);
-        ps2.stop();
-    }
-    if (launch_head_bwd(m, N, beta, ppo)) return tsc::fail("head_bwd failed");           // + dWo, dbo
-    tsc::ProfScope ps8(tsc::KID_LSTM_BWD, m->stream);
-    hipLaunchKernelGGL(lstm_bwd2_kernel, dim3((unsigned)G, (unsigned)((E + 31) / 32)), dim3(256), sizeof(float) * 32 * (kDz2Ld + kDh3Ld), st,
-                       m->params, L, m->Z, m->Cc, m->state_bw, m->dHh, m->r_done, (int)T, (int)E);
-    ps8.stop();
-    tsc::ProfScope ps9(tsc::KID_TRANSPOSE, m->stream);
-    hipLaunchKernelGGL(transpose_wx_kernel, dim3((unsigned)((G * L.H * kG4 + 255) / 256)), dim3(256), 0, st, m->params, L, m->WxT);
-    ps9.stop();
-    TSC_HIP(hipGetLastError());
-    // dWh = Hp^T dZ (+ dbl) ; dWx = X1^T dZ        (dWo = Hh^T dL and dbo came out of head_bwd)
-    if (P.dwxh) {
-        const long long per = (long long)(L.H + kL + 1) * kG4;      // a split's [dWx ; dWh ; dbl] partial
-        long long rps = (N + S - 1) / S;
-        rps += rps & 1;                           // a k-step is two rows
-        {
-            tsc::ProfScope ps(tsc::KID_DWX_GEMM, m->stream);
-            with_fused_width(L.H, [&](auto w) {
-                constexpr int NT = (decltype(w)::value + kL) / 32;
-                hipLaunchKernelGGL(dwxh_kernel<NT>, dim3((unsigned)(S * G)), dim3(512), dwxh_lds<NT>(), st, m->X1, m->Hp, m->Z, N, (int)G, S,
-                                   rps, m->ws, m->dbg);
-            });
-        }
-        {
-            tsc::ProfScope ps(tsc::KID_DWH_GEMM, m->stream);
-            hipLaunchKernelGGL(dwxh_reduce_kernel, dim3((unsigned)((per * G + 255) / 256)), dim3(256), 0, st, m->ws, (int)G, S, per, g,
-                               L.stride, L.oWx);
-        }
-        TSC_HIP(hipGetLastError());
-    } else {
-    if (gemm(m, tsc::KID_DWH_GEMM, true, tsc::EPI_NONE, (int)G, kL, kG4, (int)N, m->Hp, N * kL, kL, 1, m->Z, N * kG4, kG4, g + L.oWh, L.stride,
-             kG4, nullptr, 0, nullptr, 0, 0, nullptr, 0, g + L.obl, L.stride)) return tsc::fail("gemm failed");
-    if (gemm(m, tsc::KID_DWX_GEMM, true, tsc::EPI_NONE, (int)G, L.H, kG4, (int)N, m->X1, N * L.H, L.H, 1, m->Z, N * kG4, kG4, g + L.oWx, L.stride,
-             kG4, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, 0)) return tsc::fail("gemm failed");
-    }
-    if (P.dx1w1) {
-        // dX1 stays in registers: dW1 | db1 come out of the same pass (dx1w1_kernel2)
-        long long rps = (N + S - 1) / S;
-        rps = (rps + 31) / 32 * 32;                  // whole 32-row chunks
-        const size_t lds = sizeof(float) * (2 * 32 * kD1Ld + 2 * 32 * kObLd);
-        {
-            tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
-            with_fused_width(L.H, [&](auto w) {
-                hipLaunchKernelGGL(dx1w1_kernel2<decltype(w)::value / 16>, dim3((unsigned)(S * G)), dim3(512), lds, st, m->Z, m->X1, m->WxT,
-                                   m->r_obs, N, (int)G, S, rps, (int)A, L.SMAX, m->ws, m->ftmask, m->dbg);
-            });
-        }
-        {
-            tsc::ProfScope ps(tsc::KID_DW1_GEMM, m->stream);
-            const long long tot = (long long)(L.SMAX + 1) * L.H * G;
-            hipLaunchKernelGGL(dx1w1_reduce2_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, m->ws, (int)G, S, L.H, L.SMAX,
-                               m->rowrange, g, L.stride, L.oW1, L.ob1);
-        }
-        TSC_HIP(hipGetLastError());
-        m->cached_next = 0;
-        return 0;
-    }
-    // dX1 = (dZ Wx^T) * relu'(X1), in place over X1
-    if (gemm(m, tsc::KID_DX1_GEMM, false, tsc::EPI_MASK_POS, (int)G, (int)N, L.H, kG4, m->Z, N * kG4, kG4, 1, m->WxT, (long long)L.H * kG4, L.H,
-             m->X1, N * L.H, L.H, nullptr, 0, m->X1, N * L.H, L.H, nullptr, 0, nullptr, 0)) return tsc::fail("gemm failed");
-    }
-    // dW1 = obs^T dX1 masked to the block-diagonal structure (+ db1)
-    if (gemm(m, tsc::KID_DW1_GEMM, true, tsc::EPI_ROWRANGE, (int)G, L.SMAX, L.H, (int)N, m->r_obs, L.SMAX, AS, 2, m->X1, N * L.H, L.H, g + L.oW1,
-             L.stride, L.H, nullptr, 0, nullptr, 0, 0, m->rowrange, L.SMAX, g + L.ob1, L.stride)) return tsc::fail("gemm failed");
-    m->cached_next = 0;                               // the update consumes the cache
-    TSC_HIP(hipGetLastError());
-    return 0;
+    return m->lay.fc ? update_fc(m, E * T, beta, ppo) : update_lstm(m, E * T, beta, ppo);
 }
 
 int tsc_model_compute_grads(tsc_model *m, const float *R_boot, double beta) {

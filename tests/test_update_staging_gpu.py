@@ -19,6 +19,11 @@ clamped otherwise.  What each shape drives (tests/test_update_staging_host.py re
                     dx1w1 seven unclamped chunks + one clamped per split, every row valid
 and Monaco (real_net: H = 192, s_max = 52, heterogeneous towers, N = 360 in splits below 144 rows: clamped path only) at
 E, T = 40, 9 for the other instantiation.  The unclamped loops at many intervals run in test_model_gpu's T = 120 cases.
+fc_bwd_kernel (FcACPolicy: dWfc | dbfc | dW1 | db1, against TSC_UNFUSED_DX=1) has ONE row loop: 32-row chunks, every row index
+clamped and rows past the split stored as zero dZ rows, rps = ceil(N / 5) rounded up to a multiple of 32 like dx1w1:
+    large_grid IA2C fc (H = 160):  E, T = 1, 1 and 3, 7 (N = 1 and 21: empty splits, one short chunk), 33, 13 (N = 429: ragged last
+                    chunk, last split 45 rows), 64, 20 (N = 1280: every row valid)
+    large_grid MA2C fc (H = 224, the fourth X1 staging slot) at 33, 13;  real_net MA2C fc (H = 192) at 40, 9
 Tolerance as in test_model_gpu.test_fused_update_kernels_equal_grouped_gemms: |d| <= 2e-5 * max|g| (fp32 summation order), and
 the same entries exactly zero."""
 import ctypes as C
@@ -37,7 +42,7 @@ def _rand_obs(scn, E, rng):
     return obs
 
 
-def _grads(scenario, E, T, unfused, monkeypatch):
+def _grads(scenario, E, T, unfused, monkeypatch, agent='ma2c', policy='lstm'):
     """One rollout through the trainer's path (fused forward + sampling, activations cached for the update; random dones),
     then compute_grads: the flat gradient."""
     from deeprl_signal_control_amd import _lib
@@ -45,12 +50,12 @@ def _grads(scenario, E, T, unfused, monkeypatch):
     from deeprl_signal_control_amd.scenario import build_scenario
     monkeypatch.setenv('TSC_UNFUSED_DW', unfused)
     monkeypatch.setenv('TSC_UNFUSED_DX', unfused)
-    scn = build_scenario(scenario, 'ma2c')
+    scn = build_scenario(scenario, agent)
     cfg = dict(batch_size=T)
     if scenario == 'real_net':
         cfg['reward_norm'] = 1.0
     m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, E, scn.s_max, int(scn.green_tab.shape[1]), cfg, device=0, seed=5,
-               name='ma2c', policy='lstm')
+               name=agent, policy=policy)
     m.reset()
     rng = np.random.RandomState(123)
     obs, done = _rand_obs(scn, E, rng), np.ones(E, np.uint8)
@@ -78,5 +83,17 @@ def test_update_staging_equals_grouped_gemms(scenario, E, T, monkeypatch):
     scale = np.abs(ref).max()
     assert scale > 0
     print('%s E=%d T=%d: max |fused - grouped| = %.3e of max|g| = %.3e' % (scenario, E, T, np.abs(fused - ref).max() / scale, scale))
+    np.testing.assert_allclose(fused, ref, atol=2e-5 * scale, rtol=0)
+    np.testing.assert_array_equal(fused == 0, ref == 0)
+
+
+@pytest.mark.parametrize('scenario,agent,E,T', [('large_grid', 'ia2c', 1, 1), ('large_grid', 'ia2c', 3, 7), ('large_grid', 'ia2c', 33, 13),
+                                                ('large_grid', 'ia2c', 64, 20), ('large_grid', 'ma2c', 33, 13), ('real_net', 'ma2c', 40, 9)])
+def test_fc_bwd_equals_grouped_gemms(scenario, agent, E, T, monkeypatch):
+    fused = _grads(scenario, E, T, '0', monkeypatch, agent, 'fc')
+    ref = _grads(scenario, E, T, '1', monkeypatch, agent, 'fc')
+    scale = np.abs(ref).max()
+    assert scale > 0
+    print('%s %s fc E=%d T=%d: max |fused - grouped| = %.3e of max|g| = %.3e' % (scenario, agent, E, T, np.abs(fused - ref).max() / scale, scale))
     np.testing.assert_allclose(fused, ref, atol=2e-5 * scale, rtol=0)
     np.testing.assert_array_equal(fused == 0, ref == 0)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Time the A2C update's kernels alone (no simulator): fill one rollout of the benchmark shape through the fused forward
 (random observations, E env instances, T = n_step), then run compute_grads `--reps` times with HIP-event timing on.
-    python tools/bench_update.py [--envs 1024] [--agent ma2c] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]]
+    python tools/bench_update.py [--envs 1024] [--agent ma2c] [--policy lstm] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]]
 --algo ppo times `--ppo-epochs` epochs per rollout and also prints the wall time (stream-synchronised, profiling off) of an epoch-0
 update and of a later epoch (re-forward + update); --algo a2c prints the wall time of its one update the same way.
 Environment knobs of the library (TSC_UNFUSED_DW, TSC_UNFUSED_DX) select kernel variants for A/B runs.
@@ -25,11 +25,12 @@ def main():
     ap.add_argument('--envs', type=int, default=1024)
     ap.add_argument('--agent', default='ma2c')
     ap.add_argument('--scenario', default='large_grid')
+    ap.add_argument('--policy', default='lstm', choices=['lstm', 'fc'], help='fc = FcACPolicy (the benchmark runs it with --agent ia2c)')
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--algo', default='a2c', choices=['a2c', 'ppo'])
     ap.add_argument('--ppo-epochs', type=int, default=2)
     ap.add_argument('--stamps', action='store_true', help='per-step cycle split of dwxh / dx1w1 (needs a -DTSC_UPD_STAMPS=1 build)')
-    ap.add_argument('--json', action='store_true', help='one JSON line with the wall times (ms) of the updates, per epoch index')
+    ap.add_argument('--json', action='store_true', help='one JSON line with the wall times (ms) of the updates, per epoch index, and the kernel times at full precision')
     args = ap.parse_args()
     from deeprl_signal_control_amd import _lib
     from deeprl_signal_control_amd.agents import VecA2C
@@ -38,7 +39,7 @@ def main():
     T = 120 if args.scenario == 'large_grid' else 40
     m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, args.envs, scn.s_max, int(scn.green_tab.shape[1]),
                dict(batch_size=T, **(dict(algo='ppo', ppo_epochs=args.ppo_epochs) if args.algo == 'ppo' else {})), device=0, seed=0,
-               name=args.agent)
+               name=args.agent, policy=args.policy)
     sl = m.rollout_slots()
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     out = {}
@@ -83,11 +84,11 @@ def main():
                       % (name, 4 * w, ', '.join('%s %d' % (n, c) for n, c in zip(seg_names[name, w], seg)), int(t[4] - t[0])))
     prof = _lib.profile()
     _lib.profile(enable=False)
-    tot = 0.0
+    tot, kern = 0.0, {}
     for k, (ms, cnt) in sorted(prof.items(), key=lambda kv: -kv[1][0]):
         if k in ('policy_fwd_fused',):
             continue
-        per = ms / args.reps
+        per = kern[k] = ms / args.reps
         tot += per
         print('%-18s %8.3f ms per update  (%d launches)' % (k, per, cnt))
     print('%-18s %8.3f ms' % ('update total', tot))
@@ -119,7 +120,8 @@ def main():
     for k, w in enumerate(wall):
         print('wall: %s update, epoch %d: %s ms (median %.3f)' % (args.algo, k, ' '.join('%.3f' % x for x in w), float(np.median(w))))
     if args.json:
-        print(json.dumps(dict(algo=args.algo, envs=args.envs, agent=args.agent, scenario=args.scenario, n_step=T, wall_ms_per_epoch=wall)))
+        print(json.dumps(dict(algo=args.algo, envs=args.envs, agent=args.agent, scenario=args.scenario, n_step=T, wall_ms_per_epoch=wall,
+                              kernel_ms_per_update=kern)))
 
 
 if __name__ == '__main__':
