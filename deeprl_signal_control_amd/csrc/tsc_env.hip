@@ -352,8 +352,8 @@ size_t smem_bytes(const EnvDev &P) {
     return tot;
 }
 
-// numpy's float64 pairwise sum for n <= 128 (np.sum at envs/env.py:580)
-__device__ double np_sum(const double *a, int n) {
+// numpy's float64 pairwise sum (np.sum at envs/env.py:580), one block: n <= 128
+__device__ __forceinline__ double np_sum_block(const double *a, int n) {
     if (n < 8) {
         double r = 0.0;
         for (int i = 0; i < n; ++i) r += a[i];
@@ -367,6 +367,39 @@ __device__ double np_sum(const double *a, int n) {
     double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
     for (; i < n; ++i) res += a[i];
     return res;
+}
+// ... and the whole sum: above 128 elements numpy halves recursively -- pw(a, n) = pw(a, n2) + pw(a + n2, n - n2) with n2 = n / 2
+// rounded down to a multiple of 8 -- down to blocks.  The same walk without recursion: seg[2 d], seg[2 d + 1] are (offset, length)
+// of the node at depth d of the path to the current block, left[d] the sum of that node's left half once the walk is in its right
+// half.  A half is at most n / 2 + 8 long, so kNpSumDepth levels reach blocks for every n <= 2048, and tsc_env_create admits no
+// more agents than that (2 n_agent <= kMaxCross * NLA <= 4096).  left / seg: kNpSumDepth entries / pairs of the caller's (LDS).
+// Networks of more than 128 agents: tests/test_networks_gpu.py isolated_130 (one split), isolated_254 (a split inside the right half)
+// and isolated_300 (the left half splits again: two levels down the left).
+constexpr int kNpSumDepth = 8;
+__device__ __forceinline__ double np_sum(const double *a, int n, double *left, int *seg) {
+    if (n <= 128) return np_sum_block(a, n);
+    int d = 0;
+    unsigned right = 0u;                            // bit d: the node at depth d is a right half
+    seg[0] = 0; seg[1] = n;
+    for (;;) {
+        while (seg[2 * d + 1] > 128 && d + 1 < kNpSumDepth) {       // down the left halves to a block
+            int n2 = seg[2 * d + 1] / 2;
+            n2 -= n2 % 8;
+            seg[2 * d + 2] = seg[2 * d]; seg[2 * d + 3] = n2;
+            ++d;
+            right &= ~(1u << d);
+        }
+        double ret = np_sum_block(a + seg[2 * d], seg[2 * d + 1]);
+        while (d > 0 && ((right >> d) & 1u)) { --d; ret = left[d] + ret; }      // a right half closes its parent
+        if (d == 0) return ret;
+        --d;                                        // a left half: keep its sum and go to the right half
+        left[d] = ret;
+        int n2 = seg[2 * d + 1] / 2;
+        n2 -= n2 % 8;
+        seg[2 * d + 2] = seg[2 * d] + n2; seg[2 * d + 3] = seg[2 * d + 1] - n2;
+        ++d;
+        right |= 1u << d;
+    }
 }
 
 __device__ __forceinline__ double norm_clip(double x, double norm, double clip) {
@@ -791,7 +824,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     // Round 6: the first 8 / 4 words per thread of the two tables are REQUESTED here, next to the level-1 loads, and stored behind the
     // level-2 requests (one memory round trip for both tables instead of one per 4-word round: three on large_grid -- the workgroup is a
     // latency chain, 64 us alone on a CU against 80 us with three neighbours, so a round trip is ~ 1 % of the step); what does not fit
-    // (no reference scenario) takes the loop.
+    // (no reference scenario; tests/test_networks_gpu.py grid_x2, grid_x4) takes the loop.
     constexpr int kTW = 8, kTZ = 4;
     const int n_mv = P.NU * NR, n_zip = (P.NU * NR + 3) / 4;                            // zip padded to 4 B
     uint32_t tw[kTW], tz[kTZ];
@@ -826,11 +859,11 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         s.pend[l] = pend0; s.ser[l] = ser0;
         for (int q = 0; q < 8; ++q) s.emit[l * 8 + q] = q < P.ctrl ? emit_tab[(size_t)l * P.emit_len + t + q] : 0;
     }
-    for (int r = blockDim.x + l; r < NS; r += blockDim.x) {              // more streams than threads (not on the reference scenarios)
+    for (int r = blockDim.x + l; r < NS; r += blockDim.x) {              // more streams than threads (tests/test_networks_gpu.py few_threads)
         s.pend[r] = P.pending[(size_t)e * NS + r]; s.ser[r] = P.serial[(size_t)e * NS + r];
         for (int q = 0; q < 8; ++q) s.emit[r * 8 + q] = q < P.ctrl ? emit_tab[(size_t)r * P.emit_len + t + q] : 0;
     }
-    for (int a2 = blockDim.x + l; a2 < P.A; a2 += blockDim.x) {          // more agents than threads (ditto)
+    for (int a2 = blockDim.x + l; a2 < P.A; a2 += blockDim.x) {          // more agents than threads (few_threads as well: its live junctions are agents 70 .. 99)
         const int act2 = action[(size_t)e * P.A + a2], prev2 = P.prev_action[(size_t)e * P.A + a2];
         P.prev_action[(size_t)e * P.A + a2] = act2;
         const uint8_t *g = P.green_tab + ((size_t)a2 * P.PMAX + act2) * P.KMAX;
@@ -1637,7 +1670,10 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         s.r[a] = r;
     }
     __syncthreads();
-    if (l == 0) { double g = np_sum(s.r, P.A); s.r[P.A] = g; greward[e] = g; P.reward_acc[e] += g; }
+    if (l == 0) {                                   // (np_sum's scratch: the outbox targets, dead since the last second's gather)
+        double g = np_sum(s.r, P.A, (double *)s.oto, s.oto + 2 * kNpSumDepth);
+        s.r[P.A] = g; greward[e] = g; P.reward_acc[e] += g;
+    }
     __syncthreads();
     // (the loop of shape_rewards, kept in place: calling it here changes the scalar register allocation of the whole kernel)
     for (int a = l; a < P.A; a += blockDim.x) {
@@ -1872,8 +1908,11 @@ int tsc_version(void) { return 118; }      // 1.18: tsc_model_plan; 1.17: tsc_iq
 
 int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_env **out) {
     if (!sc || !out || n_env <= 0) return tsc::fail("tsc_env_create: bad arguments");
-    if (sc->n_lane > 1024) return tsc::fail("tsc_env_create: n_lane %d > 1024 unsupported", sc->n_lane);
-    if (sc->n_route > 254) return tsc::fail("tsc_env_create: n_route %d > 254 unsupported", sc->n_route);
+    // (every refusal below has its twin in Scenario.check_limits, scenario.py; tests/test_networks_gpu.py asks for each by its text)
+    if (sc->n_lane < 1 || sc->n_route < 1 || sc->n_agent < 1)         // (the table prefetch of step_kernel reads entry n_mv - 1)
+        return tsc::fail("tsc_env_create: %d lanes, %d routes, %d agents: a scenario needs at least one of each", sc->n_lane, sc->n_route, sc->n_agent);
+    if (sc->n_lane > 1024) return tsc::fail("tsc_env_create: n_lane %d > 1024 unsupported (one thread per live lane): split the network", sc->n_lane);
+    if (sc->n_route > 254) return tsc::fail("tsc_env_create: n_route %d > 254 unsupported (route ids are bytes on the device): let disjoint parts of the network share route indices", sc->n_route);
     TSC_HIP(hipSetDevice(device));
     tsc_env *h = new tsc_env();
     tsc::CreateGuard<tsc_env, tsc_env_destroy> guard(h);        // an error return below frees the handle and its buffers
@@ -1895,7 +1934,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     const bool streams = sc->n_stream > 0;
     const int NS = streams ? sc->n_stream : NR, KC = streams ? sc->k_choice : 1;
     P.NS = NS; P.KC = KC;
-    if (NS > 254) return tsc::fail("tsc_env_create: n_stream %d > 254 unsupported", NS);
+    if (NS > 254) return tsc::fail("tsc_env_create: n_stream %d > 254 unsupported (stream lists are bytes on the device): merge the flow elements of streams that share an entry lane and a route", NS);
     if (streams && (!sc->stream_entry || !sc->stream_mode || !sc->stream_choice || KC < 1 || sc->n_interval < 1 || sc->choice_interval_sec < 1))
         return tsc::fail("tsc_env_create: incomplete stream tables");
     const int NI = streams ? sc->n_interval : 1;
@@ -1943,7 +1982,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     for (int i = 0; i < NL * NR; ++i) {
         const int nx = sc->mv_next[i], lk = sc->mv_link[i], pr = sc->mv_prio[i];
         const int yl = (sc->mv_yield[i] >= 0 && reach[sc->mv_yield[i]]) ? sc->mv_yield[i] : -1;   // an empty lane has no right of way to give
-        if (lk > 62) return tsc::fail("tsc_env_create: signal link index %d > 62 unsupported", lk);
+        if (lk > 62) return tsc::fail("tsc_env_create: signal link index %d > 62 unsupported (six bits of the movement word, 63 = none): split the junction into two agents", lk);
         const unsigned a = nx == -1 ? 0xFFFu : nx < -1 ? 0xFFEu : (unsigned)nx;
         const unsigned b = lk < 0 ? 63u : (unsigned)lk;
         const unsigned c = yl < 0 ? 0xFFFu : (unsigned)yl;
@@ -1956,7 +1995,8 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
         std::vector<uint8_t> zp(((size_t)NL * NR + 3) / 4 * 4, 0);
         for (int i = 0; i < NL * NR; ++i) {
             const int z = sc->mv_zip[i], rank = z & 0xFF, cnt = z >> 8;
-            if (rank > 15 || cnt > 15) return tsc::fail("tsc_env_create: zipper slot overflow");
+            if (z < 0 || rank > 15 || cnt > 15)
+                return tsc::fail("tsc_env_create: zipper slot overflow: rank %d of %d at lane %d, route %d (four bits each on the device)", rank, cnt, i / NR, i % NR);
             zp[i] = (uint8_t)(rank | (cnt << 4));
         }
         TSC_HIP(h->bufs.upload(&P.zip, zp.data(), zp.size()));
@@ -2005,7 +2045,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
             if (l < 0 || l >= NL) return tsc::fail("tsc_env_create: stream %d has no entry lane", r);
             int q = 0;
             while (q < kMaxEntry && lr[l * kMaxEntry + q] >= 0) ++q;
-            if (q == kMaxEntry) return tsc::fail("tsc_env_create: more than %d routes enter lane %d", kMaxEntry, l);
+            if (q == kMaxEntry) return tsc::fail("tsc_env_create: more than %d streams enter lane %d: merge the flow elements of streams that share a route", kMaxEntry, l);
             lr[l * kMaxEntry + q] = r;
         }
         std::vector<uint32_t> lrp((size_t)NL * 2, 0xFFFFFFFFu);         // one byte per route (n_route <= 255 checked above)
@@ -2020,11 +2060,13 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
             const long long b = sc->flows[f * 4], en = sc->flows[f * 4 + 1], vph = sc->flows[f * 4 + 2];
             const int r = sc->flows[f * 4 + 3];
             if (r < 0 || r >= NS) return tsc::fail("tsc_env_create: flow %d names stream %d of %d", f, r, NS);
+            if (b < 0 || vph < 0)                         // (the table starts at second 0: t = b would index in front of it)
+                return tsc::fail("tsc_env_create: flow %d begins at second %lld with %lld veh/h: neither may be negative: cut the element at 0", f, b, vph);
             for (long long t = b; t < en && t < P.emit_len; ++t) {
                 const long long tau = t - b;
                 const long long c = (((tau + 1) * vph + 3599) / 3600) - ((tau * vph + 3599) / 3600);
                 const long long v = em[(size_t)r * P.emit_len + t] + c;
-                if (v > 255) return tsc::fail("tsc_env_create: flow %d emits more than 255 vehicles per second", f);
+                if (v > 255) return tsc::fail("tsc_env_create: flow %d makes stream %d emit more than 255 vehicles per second (a byte per second and stream): spread the vehicles over more seconds", f, r);
                 em[(size_t)r * P.emit_len + t] = (uint8_t)v;
             }
         }
@@ -2034,7 +2076,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
         h->n_flow = sc->n_flow;
         h->h_flows.assign(sc->flows, sc->flows + (size_t)sc->n_flow * 4);
     }
-    if (sc->control_interval_sec > 8) return tsc::fail("tsc_env_create: control interval > 8 s unsupported");
+    if (sc->control_interval_sec > 8) return tsc::fail("tsc_env_create: control interval %d > 8 s unsupported (eight emission and record rows per launch)", sc->control_interval_sec);
     TSC_HIP(h->bufs.upload(&P.agent_lanes, sc->agent_lanes, A * P.LMAX));
     TSC_HIP(h->bufs.upload(&P.agent_nlane, sc->agent_nlane, A)); TSC_HIP(h->bufs.upload(&P.agent_nlink, sc->agent_nlink, A));
     TSC_HIP(h->bufs.upload(&P.agent_nphase, sc->agent_nphase, A));
@@ -2081,7 +2123,7 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
         P.help = (ev && ev[0] == '0') ? 0 : 1;
     }
     if (kMaxCross * P.NLA < P.NLP || kMaxCross * P.NLA < 2 * P.A)
-        return tsc::fail("tsc_env_create: too few live lanes (%d of %d) for the observation scratch", P.NU, P.NL);
+        return tsc::fail("tsc_env_create: too few live lanes (%d of %d, %d agents) for the observation scratch: leave out lanes and junctions that no route reaches", P.NU, P.NL, P.A);
     h->smem = smem_bytes(P);
     h->threads = (P.help && P.NLA < 256) ? 256 : P.NLA;
     // the reference's large_grid / Monaco get the instantiation with compile-time table dimensions (TSC_ENV_SPEC=0: off)

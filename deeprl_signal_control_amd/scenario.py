@@ -40,6 +40,8 @@ LANE_CAP = 28        # vehicle slots per lane: 200 m / 7.5 m = 26.7 -> 27 (+1); 
 LANE_CHANGE_DEFAULT = True    # large_grid: lane choice by the junction's connections + lane changes on the two-lane streets (rule 10)
 MAX_CROSS = 4        # vehicles that may leave one lane in one sim-step
 MAX_UP = 4           # upstream feeder lanes per lane
+MAX_ENTRY = 8        # insertion streams that may share one entry lane (csrc/tsc_env.hip kMaxEntry)
+MAX_LINK = 62        # largest signal link index of a movement (six bits on the device, 63 = none)
 DET_LEN = 50.0       # lane-area detector covers the last 50 m
 NO_LANE = -1
 
@@ -305,17 +307,84 @@ class Scenario:
         if long_:
             raise ValueError('lanes %s hold more than %d standing vehicles (%.1f m each): split them into pieces of at most %.0f m '
                              '(as build_small_grid does with its 400 m edges)' % (long_[:4], LANE_CAP, veh, LANE_CAP * veh))
+        # (every refusal below has its twin in tsc_env_create, csrc/tsc_env.hip; tests/test_networks_gpu.py asks both for each)
+        if self.n_lane < 1 or self.n_route < 1 or self.n_agent < 1:
+            raise ValueError('%d lanes, %d routes, %d agents: a scenario needs at least one of each' % (self.n_lane, self.n_route, self.n_agent))
+        if self.n_lane > 1024:
+            raise ValueError('%d lanes: at most 1024 (one thread per live lane): split the network' % self.n_lane)
         if self.n_route > 254 or self.n_stream > 254:
-            raise ValueError('%d routes / %d insertion streams: at most 254 each (route ids and stream lists are bytes on the device)'
-                             % (self.n_route, self.n_stream))
-        if self.n_lane > 255 and (np.asarray(self.mv_zip) >> 8 > 1).any():
+            raise ValueError('%d routes / %d insertion streams: at most 254 each (route ids and stream lists are bytes on the device): '
+                             'let disjoint parts of the network share route indices, merge the flow elements of streams that share '
+                             'an entry lane and a route' % (self.n_route, self.n_stream))
+        entry = self.route_entry_lane if self.stream_entry_lane is None else self.stream_entry_lane
+        per_lane = np.bincount(np.asarray(entry, np.int64)[np.asarray(entry) >= 0], minlength=1)
+        if per_lane.max() > MAX_ENTRY:
+            raise ValueError('%d streams enter lane %d: at most %d (a lane keeps its streams as %d bytes on the device): merge the flow '
+                             'elements of streams that share a route' % (per_lane.max(), int(per_lane.argmax()), MAX_ENTRY, MAX_ENTRY))
+        if np.asarray(self.mv_link).size and int(np.asarray(self.mv_link).max()) > MAX_LINK:
+            raise ValueError('signal link index %d: at most %d (six bits of the movement word on the device): split the junction '
+                             'into two agents' % (int(np.asarray(self.mv_link).max()), MAX_LINK))
+        zp = np.asarray(self.mv_zip)
+        if zp.size and (zp.min() < 0 or (zp & 0xFF).max() > 15 or (zp >> 8).max() > 15):
+            raise ValueError('zipper slot overflow: rank %d of %d (four bits each on the device; a lane has at most %d feeders)'
+                             % (int((zp & 0xFF).max()), int((zp >> 8).max()), MAX_UP))
+        if self.n_lane > 255 and (zp >> 8 > 1).any():
             raise ValueError('%d lanes with zipper merges: the merge arbitration keeps a lane\'s feeders as bytes on the device, '
                              'lane indices must stay below 255' % self.n_lane)
         if np.asarray(self.lane_up).shape[1] != MAX_UP:
             raise ValueError('lane_up must list %d feeder slots per lane' % MAX_UP)
         if self.control_interval_sec > 8:
-            raise ValueError('control_interval_sec %d > 8 unsupported' % self.control_interval_sec)
+            raise ValueError('control_interval_sec %d > 8 unsupported (eight emission and record rows per launch)' % self.control_interval_sec)
+        fl = np.asarray(self.flows, np.int64).reshape(-1, 4)
+        bad = np.flatnonzero((fl[:, 0] < 0) | (fl[:, 2] < 0))
+        if len(bad):
+            raise ValueError('flow %d begins at second %d with %d veh/h: neither may be negative (the emission table starts at second 0): '
+                             'cut the element at 0' % (bad[0], fl[bad[0], 0], fl[bad[0], 2]))
+        nu = self.live_lane_prefix()
+        nla, nlp = (max(nu, 1) + 63) // 64 * 64, (self.n_lane + 63) // 64 * 64
+        if MAX_CROSS * nla < nlp or MAX_CROSS * nla < 2 * self.n_agent:
+            raise ValueError('too few live lanes (%d of %d, %d agents) for the observation scratch: the lanes rounded up to 64 and twice '
+                             'the agents may be at most %d, four times the live lanes rounded up to 64: leave out lanes and junctions '
+                             'that no route reaches' % (nu, self.n_lane, self.n_agent, MAX_CROSS * nla))
+        rate = self.peak_emission()
+        if rate[0] > 255:
+            raise ValueError('flow %d makes stream %d emit %d vehicles in one second: at most 255 (a byte per second and stream on the '
+                             'device): spread the vehicles over more seconds' % (rate[1], rate[2], rate[0]))
         return self
+
+    def peak_emission(self):
+        """(most vehicles one stream emits in one second, the first flow element that reaches it, its stream) by tsc_env_create's
+        integer rule: second t of an element that begins at b emits ceil((t - b + 1) vph / 3600) - ceil((t - b) vph / 3600), and the
+        elements of a stream add up, in flow order."""
+        horizon = (int(self.episode_length_sec) + 64 + 3) // 4 * 4          # the emission table's length (tsc_env_create)
+        tab = np.zeros((max(1, self.n_stream), horizon), np.int64)
+        best = (0, -1, -1)
+        for f, (b, en, vph, s_) in enumerate(np.asarray(self.flows, np.int64).reshape(-1, 4).tolist()):
+            lo, hi = max(b, 0), min(en, horizon)              # (check_limits refuses a negative begin, as tsc_env_create does)
+            if hi <= lo or not 0 <= s_ < len(tab):
+                continue
+            tau = np.arange(lo, hi, dtype=np.int64) - b
+            tab[s_, lo:hi] += ((tau + 1) * vph + 3599) // 3600 - (tau * vph + 3599) // 3600
+            c = int(tab[s_, lo:hi].max())
+            if c > best[0]:
+                best = (c, f, int(s_))
+        return best
+
+    def live_lane_prefix(self):
+        """1 + the highest lane a vehicle can ever stand on: tsc_env_create's chain walk (entry lane -> mv_next -> ..., a vehicle on the
+        wrong lane of a two-lane street moves over to the sibling), the NU of the device.  After load sorting these lanes are a prefix."""
+        nu, NL = 0, self.n_lane
+        nxt = np.asarray(self.mv_next).reshape(NL, -1)
+        for l, r in set(self.entry_lanes()):
+            hops = 0
+            while 0 <= l < NL and 0 <= r < nxt.shape[1] and hops <= 2 * NL:
+                nu = max(nu, l + 1)
+                nx = int(nxt[l, r])
+                if nx < -1 and self.lane_sib is not None and self.lane_sib[l] >= 0 and nxt[self.lane_sib[l], r] >= -1:
+                    nx = int(self.lane_sib[l])
+                l = nx
+                hops += 1
+        return nu
 
     def entry_lanes(self):
         """(entry lane, route) of every way a vehicle can enter: what decides which lanes can ever be occupied."""

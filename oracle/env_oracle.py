@@ -17,11 +17,16 @@ REALNET_REWARD_NORM = 20            # envs/env.py:18
 
 
 def numpy_pairwise_sum(a):
-    """The order np.sum uses for n <= 128 float64 (numpy loops_utils pairwise sum,
-    8 accumulators); `global_reward = np.sum(reward)` at envs/env.py:580 depends on it.
-    Restated here in plain Python so tests can pin the HIP kernel's order."""
+    """The order np.sum uses for float64 (numpy loops_utils pairwise sum: 8 accumulators up to
+    128 elements, above that the two halves' sums, the left half n // 2 rounded down to a multiple
+    of 8); `global_reward = np.sum(reward)` at envs/env.py:580 depends on it.
+    Restated here in plain Python so tests can pin the HIP kernel's order (np_sum, csrc/tsc_env.hip)."""
     a = [float(x) for x in a]
     n = len(a)
+    if n > 128:
+        n2 = n // 2
+        n2 -= n2 % 8
+        return numpy_pairwise_sum(a[:n2]) + numpy_pairwise_sum(a[n2:])
     if n < 8:
         r = 0.0
         for x in a:

@@ -1,0 +1,530 @@
+"""Synthetic road networks for the simulator parity tests -- TEST INFRASTRUCTURE ONLY, host only (no GPU, no library).
+
+step_kernel (csrc/tsc_env.hip) is the one kernel every configuration shares, and the three built-in scenarios visit a small corner of
+what tsc_env_create accepts: at most 113 live lanes, 16 routes, 28 agents, three feeders per lane, link index 21, a 5 s / 2 s control
+interval, one vehicle per second and stream.  Every network of NETWORKS exists because of one declared limit (INTEGRATION.md section 5,
+"Supported scenarios"); the limit is named next to it.  Three tools build them:
+
+* tile(scn, k): k disjoint copies of a compiled Scenario as one scenario;
+* compile_network(...): a small compiler for hand-made networks (lanes, routes as lane sequences, phase strings, streams, flows);
+* NETWORKS: name -> Net (factory, the limit it drives, the step plan tsc_env_step_plan must report, and the run: E, control steps,
+  share of random actions, seed).
+
+The runs of tests/test_networks_gpu.py are redrawn on the host by run_oracle / draw_actions below, so that tests/test_networks_host.py
+states conditions (the limit is reached, the roads are not empty) about the very runs the GPU tests compare."""
+import copy
+
+import numpy as np
+
+from deeprl_signal_control_amd.scenario import (DET_LEN, MAX_UP, Scenario, _obs_table, _signal_tables, _state_dims, build_large_grid,
+                                                sort_lanes_by_load)
+
+
+# ---------------------------------------------------------------------------
+# tile
+# ---------------------------------------------------------------------------
+def _block_diag(m, k, fill, lane_off=0):
+    """k copies of the [NL, NR] table m on the diagonal of a [k NL, k NR] table, `fill` off the blocks; entries >= 0 of copy j are
+    moved by j * lane_off (tables that name lanes)."""
+    m = np.asarray(m)
+    NL, NR = m.shape
+    out = np.full((k * NL, k * NR), fill, m.dtype)
+    for j in range(k):
+        out[j * NL:(j + 1) * NL, j * NR:(j + 1) * NR] = np.where(m >= 0, m + j * lane_off, m) if lane_off else m
+    return out
+
+
+def _offset(a, k, step):
+    """k copies of the index array a along axis 0, entries >= 0 of copy j moved by j * step."""
+    a = np.asarray(a)
+    return np.concatenate([np.where(a >= 0, a + j * step, a) for j in range(k)]).astype(a.dtype)
+
+
+def tile(scn, k, **env_kw):
+    """k disjoint copies of `scn` as one scenario: lane, route, agent (and stream = route) indices of copy j moved by j times the
+    base's counts, the movement tables block-diagonal (off the blocks: next -2, link -1, yield -1, prio 0, zip 0), the observation
+    tables rebuilt from the moved neighbour lists, the lanes sorted by load again so that the live lanes are a prefix.  env_kw:
+    Scenario fields to replace (episode_length_sec, ...).  Scenarios with declared insertion streams are not needed here."""
+    assert scn.stream_entry_lane is None, 'tile: every route must be its own stream'
+    NL, NR, A = scn.n_lane, scn.n_route, scn.n_agent
+    t = copy.copy(scn)
+    tag = lambda j, nm: 'c%d.%s' % (j, nm)
+    t.name = '%s_x%d' % (scn.name, k)
+    t.n_agent, t.n_route = k * A, k * NR
+    t.node_names = [tag(j, n) for j in range(k) for n in scn.node_names]
+    t.lane_names = [tag(j, n) for j in range(k) for n in scn.lane_names]
+    t.lane_pieces = [[(tag(j, nm), st, ln) for nm, st, ln in ps] for j in range(k) for ps in scn.lane_pieces]
+    for f in ('lane_len', 'lane_vmax', 'lane_det_start', 'lane_origin', 'agent_nlane', 'agent_nlink', 'agent_nphase', 'green_tab',
+              'yellow_tab', 'link_foes'):
+        setattr(t, f, np.concatenate([np.asarray(getattr(scn, f))] * k))
+    t.lane_node = _offset(scn.lane_node, k, A)
+    t.lane_up = _offset(scn.lane_up, k, NL)
+    t.lane_sib = None if scn.lane_sib is None else _offset(scn.lane_sib, k, NL)
+    t.mv_next = _block_diag(scn.mv_next, k, -2, NL)
+    t.mv_link = _block_diag(scn.mv_link, k, -1)
+    t.mv_yield = _block_diag(scn.mv_yield, k, -1, NL)
+    t.mv_prio = _block_diag(scn.mv_prio, k, 0)
+    t.mv_zip = _block_diag(scn.mv_zip, k, 0)
+    t.route_entry_lane = _offset(scn.route_entry_lane, k, NL)
+    t.route_names = [(tag(j, a), tag(j, b)) for j in range(k) for a, b in scn.route_names]
+    t.agent_lanes = _offset(scn.agent_lanes, k, NL)
+    t.link_lane = _offset(scn.link_lane, k, NL)
+    t.phases = [list(p) for _ in range(k) for p in scn.phases]
+    t.neighbors = [[n + j * A for n in ns] for j in range(k) for ns in scn.neighbors]
+    t.n_a_ls = list(scn.n_a_ls) * k
+    nlane = [int(x) for x in t.agent_nlane]
+    t.n_s_ls, t.n_w_ls, t.n_f_ls = _state_dims(scn.agent, nlane, t.n_a_ls, t.neighbors, scn.has_wait_state)
+    t.obs_kind, t.obs_src, t.obs_len = _obs_table(scn.agent, t.agent_lanes, nlane, t.n_a_ls, t.neighbors, scn.has_wait_state,
+                                                  int(scn.green_tab.shape[1]))
+    fl = np.asarray(scn.flows, np.int32)
+    t.flows = np.concatenate([fl + np.array([0, 0, 0, j * NR], np.int32) for j in range(k)])
+    t.extra = dict(scn.extra, tiles=k)
+    for key, v in env_kw.items():
+        assert key in Scenario.__dataclass_fields__, key
+        setattr(t, key, v)
+    t = sort_lanes_by_load(t)
+    return t.streams_ready().check_limits()
+
+
+def tile_block(t, base, j):
+    """Copy j of tile(base, k) brought back to the base's numbering: dict of the tables a copy must share with the base (lanes
+    matched by name, indices moved back), for the faithfulness test."""
+    NL, NR, A = base.n_lane, base.n_route, base.n_agent
+    at = {nm: i for i, nm in enumerate(t.lane_names)}
+    rows = np.array([at['c%d.%s' % (j, nm)] for nm in base.lane_names])
+    back = np.full(t.n_lane, -9, np.int64)
+    back[rows] = np.arange(NL)
+
+    def lanes(v):
+        v = np.asarray(v)
+        return np.where(v >= 0, back[np.clip(v, 0, None)], v)
+    cols = slice(j * NR, (j + 1) * NR)
+    ag = slice(j * A, (j + 1) * A)
+    out = dict(lane_len=t.lane_len[rows], lane_vmax=t.lane_vmax[rows], lane_det_start=t.lane_det_start[rows],
+               lane_origin=t.lane_origin[rows], lane_node=np.where(t.lane_node[rows] >= 0, t.lane_node[rows] - j * A, -1),
+               lane_up=np.sort(lanes(t.lane_up[rows]), axis=1), mv_next=lanes(t.mv_next[rows, cols]), mv_link=t.mv_link[rows, cols],
+               mv_yield=lanes(t.mv_yield[rows, cols]), mv_prio=t.mv_prio[rows, cols], mv_zip=t.mv_zip[rows, cols],
+               route_entry_lane=lanes(t.route_entry_lane[cols]), agent_lanes=lanes(t.agent_lanes[ag]), link_lane=lanes(t.link_lane[ag]),
+               green_tab=t.green_tab[ag], yellow_tab=t.yellow_tab[ag], agent_nlane=t.agent_nlane[ag],
+               neighbors=[[n - j * A for n in ns] for ns in t.neighbors[ag]], n_s_ls=t.n_s_ls[ag], n_w_ls=t.n_w_ls[ag], n_f_ls=t.n_f_ls[ag],
+               obs_kind=t.obs_kind[ag, :base.s_max])
+    if base.lane_sib is not None:
+        out['lane_sib'] = lanes(t.lane_sib[rows])
+    src = t.obs_src[ag, :base.s_max].astype(np.int64)
+    kind = out['obs_kind']
+    src = np.where((kind >= 1) & (kind <= 3), back[np.clip(src, 0, t.n_lane - 1)], np.where(kind == 4, src - j * A * int(t.green_tab.shape[1]), src))
+    out['obs_src'] = src
+    fl = np.asarray(t.flows)
+    mine = fl[(fl[:, 3] >= j * NR) & (fl[:, 3] < (j + 1) * NR)]
+    out['flows'] = mine - np.array([0, 0, 0, j * NR])
+    # everything outside the block is "no movement"
+    other = np.ones(t.n_route, bool)
+    other[cols] = False
+    out['off_block'] = (bool((t.mv_next[rows][:, other] == -2).all()), bool((t.mv_link[rows][:, other] == -1).all()),
+                        bool((t.mv_yield[rows][:, other] == -1).all()), bool((t.mv_prio[rows][:, other] == 0).all()),
+                        bool((t.mv_zip[rows][:, other] == 0).all()))
+    return out
+
+
+def base_block(base):
+    """The same dict for the base scenario itself."""
+    out = {f: np.asarray(getattr(base, f)) for f in ('lane_len', 'lane_vmax', 'lane_det_start', 'lane_origin', 'lane_node', 'mv_next',
+                                                     'mv_link', 'mv_yield', 'mv_prio', 'mv_zip', 'route_entry_lane', 'agent_lanes', 'link_lane',
+                                                     'green_tab', 'yellow_tab', 'agent_nlane', 'obs_kind', 'obs_src', 'flows')}
+    out['lane_up'] = np.sort(np.asarray(base.lane_up), axis=1)
+    out.update(neighbors=[list(n) for n in base.neighbors], n_s_ls=list(base.n_s_ls), n_w_ls=list(base.n_w_ls), n_f_ls=list(base.n_f_ls))
+    if base.lane_sib is not None:
+        out['lane_sib'] = np.asarray(base.lane_sib)
+    out['off_block'] = (True,) * 5
+    return out
+
+
+def reachable_prefix(scn):
+    """The NU of the device: Scenario.live_lane_prefix (tsc_env_create's chain walk)."""
+    return scn.live_lane_prefix()
+
+
+# ---------------------------------------------------------------------------
+# a compiler for hand-made networks
+# ---------------------------------------------------------------------------
+def compile_network(name, agent, lanes, routes, phases, neighbors, flows, streams=None, merge='zipper', check=True, **env_kw):
+    """A Scenario from a hand-made network.
+    lanes: (length m, speed limit m/s, downstream agent or -1) per lane.
+    routes: per route index a list of paths; a path is a list of (lane, signal link of the hop that leaves it, -1 = none); the last
+        lane of a path is where the route ends.  Disjoint parts of the network may share a route index -- the movement table is
+        keyed by (lane, route) and a stream names its entry lane -- which keeps n_live_lanes x n_route small with many agents.
+    phases: per agent its phase strings (one char per signal link); neighbors: per agent a list of agents.
+    flows: (begin, end, veh/h, stream).  streams: (entry lane, route) per insertion stream; None = route r is stream r and enters at
+        the first lane of its only path.
+    merge: what arbitrates a lane with several feeders -- 'zipper' (mv_zip = rank | count << 8, rank = position among the ascending
+        feeders) or 'yield' (the lowest feeder has priority, the others yield to its head).
+    Derived: lane_up, the mv_* tables, the agents' lanes (dedup of their links' lanes in link order) and the signal / observation
+    tables with the scenario compiler's own helpers.  Detectors cover the last 50 m of a signalised lane.  Ends with
+    streams_ready().check_limits() (check=False: the caller wants a scenario past a limit)."""
+    NL, NR, A = len(lanes), len(routes), len(phases)
+    lane_len = np.array([l[0] for l in lanes], np.float32)
+    lane_vmax = np.array([l[1] for l in lanes], np.float32)
+    lane_node = np.array([l[2] for l in lanes], np.int32)
+    mv_next = np.full((NL, NR), -2, np.int32)
+    mv_link = np.full((NL, NR), -1, np.int32)
+    for r, paths in enumerate(routes):
+        for path in paths:
+            for i, (l, k) in enumerate(path):
+                assert mv_next[l, r] == -2, 'lane %d appears twice on route %d' % (l, r)
+                mv_next[l, r] = path[i + 1][0] if i + 1 < len(path) else -1
+                if i + 1 < len(path) and lane_node[l] >= 0:
+                    mv_link[l, r] = k
+    lane_up = np.full((NL, MAX_UP), -1, np.int32)
+    mv_zip = np.zeros((NL, NR), np.int32)
+    mv_yield = np.full((NL, NR), -1, np.int32)
+    mv_prio = np.zeros((NL, NR), np.int32)
+    for l2 in range(NL):
+        ups = sorted({int(l) for l in np.nonzero((mv_next == l2).any(axis=1))[0]})
+        assert len(ups) <= MAX_UP, 'lane %d has %d feeders' % (l2, len(ups))
+        lane_up[l2, :len(ups)] = ups
+        if len(ups) > 1:
+            for rank, l in enumerate(ups):
+                into = mv_next[l] == l2
+                if merge == 'zipper':
+                    mv_zip[l, into] = rank | (len(ups) << 8)
+                elif rank == 0:
+                    mv_prio[l, into] = 1
+                else:
+                    mv_yield[l, into] = ups[0]
+    kmax = max(len(p[0]) for p in phases)
+    link_lane = np.full((A, kmax), -1, np.int32)
+    for l, r in zip(*np.nonzero(mv_link >= 0)):
+        a, k = int(lane_node[l]), int(mv_link[l, r])
+        assert k < len(phases[a][0]), 'lane %d uses link %d, agent %d has %d' % (l, k, a, len(phases[a][0]))
+        assert link_lane[a, k] in (-1, l), 'link %d of agent %d serves lanes %d and %d' % (k, a, link_lane[a, k], l)
+        link_lane[a, k] = l
+    per_agent = []
+    for a in range(A):
+        ded = []
+        for l in link_lane[a]:
+            if l >= 0 and int(l) not in ded:
+                ded.append(int(l))
+        assert ded, 'agent %d controls no lane' % a
+        per_agent.append(ded)
+    lmax = max(len(d) for d in per_agent)
+    agent_lanes = np.full((A, lmax), -1, np.int32)
+    for a, d in enumerate(per_agent):
+        agent_lanes[a, :len(d)] = d
+    nlane = [len(d) for d in per_agent]
+    n_a_ls = [len(p) for p in phases]
+    has_wait = bool(env_kw.get('has_wait_state', True))
+    n_s, n_w, n_f = _state_dims(agent, nlane, n_a_ls, neighbors, has_wait)
+    obs_kind, obs_src, lens = _obs_table(agent, agent_lanes, nlane, n_a_ls, neighbors, has_wait, max(n_a_ls))
+    green, yellow = _signal_tables(phases, kmax)
+    stream_kw = {}
+    if streams is not None:
+        choice = np.zeros((len(streams), 1, 1, 2), np.int32)
+        choice[:, 0, 0, 0] = [s[1] for s in streams]
+        choice[:, 0, 0, 1] = 65536
+        stream_kw = dict(stream_entry_lane=np.array([s[0] for s in streams], np.int32), stream_choice=choice)
+    scn = Scenario(
+        name=name, agent=agent, node_names=['n%d' % a for a in range(A)], n_agent=A,
+        lane_names=['l%d' % l for l in range(NL)], lane_len=lane_len, lane_vmax=lane_vmax, lane_node=lane_node,
+        lane_det_start=np.where(lane_node >= 0, np.maximum(lane_len - DET_LEN, 0.0), 0.0).astype(np.float32), lane_up=lane_up,
+        n_route=NR, mv_next=mv_next, mv_link=mv_link, mv_yield=mv_yield, mv_prio=mv_prio, mv_zip=mv_zip,
+        route_entry_lane=np.array([paths[0][0][0] if paths else 0 for paths in routes], np.int32),
+        route_names=[('r%d' % r, 'r%d' % r) for r in range(NR)],
+        agent_lanes=agent_lanes, agent_nlane=np.array(nlane, np.int32), agent_nlink=np.array([len(p[0]) for p in phases], np.int32),
+        agent_nphase=np.array(n_a_ls, np.int32), link_lane=link_lane, phases=[list(p) for p in phases], green_tab=green,
+        yellow_tab=yellow, neighbors=[list(n) for n in neighbors], n_s_ls=n_s, n_w_ls=n_w, n_f_ls=n_f, n_a_ls=n_a_ls,
+        obs_kind=obs_kind, obs_src=obs_src, flows=np.array(flows, np.int32).reshape(-1, 4), obs_len=lens, **stream_kw, **env_kw)
+    scn = sort_lanes_by_load(scn).streams_ready()
+    return scn.check_limits() if check else scn
+
+
+# ---------------------------------------------------------------------------
+# the networks
+# ---------------------------------------------------------------------------
+def isolated(n, agent='ia2c', live=None, streams_per_lane=None, **env_kw):
+    """n one-lane junctions: an in lane of 150 m, an out lane of 100 m, phases G / r, ring neighbours, all on route 0.  Junction j
+    has one stream (streams_per_lane: {junction: count} for those with more) whose rate differs from junction to junction, so that
+    the local rewards differ between the agents; only the junctions of `live` (default: all) carry demand -- the lanes of the others
+    are dead."""
+    live = set(range(n) if live is None else live)
+    episode = env_kw.setdefault('episode_length_sec', 600)
+    lanes, paths, streams, flows = [], [], [], []
+    for j in range(n):
+        lanes += [(150.0, 13.89, j), (100.0, 13.89, -1)]
+        paths.append([(2 * j, 0), (2 * j + 1, -1)])
+        if j in live:
+            nq = (streams_per_lane or {}).get(j, 1)
+            for q in range(nq):                     # (a lane with several streams: each at 2 / nq of the rate, so that the lane still drains)
+                flows.append((0, episode, (240 + 40 * ((7 * j + 3 * q) % 13)) // ((nq + 1) // 2), len(streams)))
+                streams.append((2 * j, 0))
+    return compile_network('isolated_%d' % n, agent, lanes, [paths], [['G', 'r']] * n, [[(j - 1) % n, (j + 1) % n] for j in range(n)],
+                           flows, streams, **env_kw)
+
+
+def few_threads():
+    """100 junctions of which the LAST 30 carry demand (60 live lanes: one wavefront under TSC_ENV_HELP=0), nine of them with eight
+    streams on the entry lane (kMaxEntry): 93 streams and 100 agents on 64 threads.  The agents that signal live lanes are 70 .. 99
+    and the streams 64 .. 92 enter live lanes: what the two stride loops of step_kernel's prologue write -- the link states and
+    prev_action of the agents, the pending vehicles and emissions of the streams past the first 64 -- decides the traffic."""
+    return isolated(100, live=range(70, 100), streams_per_lane={j: 8 for j in range(70, 97, 3)}, episode_length_sec=450, teleport_sec=120)
+
+
+def merge4(merge, **env_kw):
+    """Four feeder lanes (links 0-3 of agent 0) into one lane, which agent 1 holds back at its own signal: every feeder carries
+    900 veh/h, so the four heads compete for the lane in the same second -- as a zipper of four (rank | 4 << 8) or by right of
+    way (the lowest feeder has priority, the other three yield to its head)."""
+    env_kw.setdefault('episode_length_sec', 400)
+    lanes = [(150.0, 13.89, 0)] * 4 + [(120.0, 13.89, 1), (100.0, 13.89, -1)]
+    routes = [[[(f, f), (4, 0), (5, -1)]] for f in range(4)]
+    flows = [(0, 400, 900, f) for f in range(4)]
+    return compile_network('merge4_%s' % merge, 'ia2c', lanes, routes, [['GGGG', 'GGrr', 'rrGG', 'GrGr'], ['G', 'r', 'G']], [[1], [0]], flows,
+                           merge=merge, teleport_sec=90, **env_kw)
+
+
+def link62(last=62, check=True):
+    """One agent with 63 signal links (k_max = 63) and eight phases (p_max = 8): six lanes on links 0, 13, 31, 47, 61 and `last`
+    (62 is the largest index the movement word holds), each with its own exit."""
+    used = [0, 13, 31, 47, 61, last]
+    nlink = max(63, last + 1)
+    rng = np.random.RandomState(62)
+    phases = []
+    for p in range(8):
+        s = rng.choice(list('Ggr'), size=nlink, p=[0.3, 0.1, 0.6])
+        for i, k in enumerate(used):
+            s[k] = 'G' if (i + p) % 3 == 0 else ('g' if (i + p) % 3 == 1 and p % 2 else 'r')
+        phases.append(''.join(s))
+    lanes = [(150.0, 13.89, 0)] * 6 + [(100.0, 13.89, -1)] * 6
+    routes = [[[(i, used[i]), (6 + i, -1)]] for i in range(6)]
+    flows = [(0, 400, 500 + 60 * i, i) for i in range(6)]
+    return compile_network('link62', 'ia2c', lanes, routes, [phases], [[]], flows, check=check, episode_length_sec=400, teleport_sec=120)
+
+
+def corridor(n=3, **env_kw):
+    """n junctions in a row: the main road (route 0) passes all of them, every junction has a side street whose traffic crosses
+    (route 1) or turns into the main road (route 2) and yields to it there.  Links per junction: 0 main, 1 side crossing, 2 side
+    turning (the side street has one lane for both)."""
+    episode = env_kw.setdefault('episode_length_sec', 500)
+    lanes = [(120.0, 13.89, j if j < n else -1) for j in range(n + 1)]              # main lanes 0 .. n
+    main = [(j, 0) for j in range(n)] + [(n, -1)]
+    cross, turn, flows, streams = [], [], [], [(0, 0)]
+    flows.append((0, episode, 700, 0))
+    for j in range(n):
+        s, x = len(lanes), len(lanes) + 1
+        lanes += [(100.0, 11.0, j), (80.0, 11.0, -1)]
+        cross.append([(s, 1), (x, -1)])
+        streams += [(s, 1), (s, 2)]
+        flows += [(0, episode, 300 + 50 * j, len(streams) - 2), (0, episode, 250, len(streams) - 1)]
+    # route 2: side street j -> main lane j + 1 -> ... -> the end of the main road; one path per side street would put main lanes on
+    # route 2 twice, so the turners of junction j take route 2 + j
+    routes = [[main], cross] + [[[(n + 1 + 2 * j, 2)] + main[j + 1:]] for j in range(n)]
+    streams = [(e, r if r < 2 else 2 + (e - n - 1) // 2) for e, r in streams]
+    return compile_network('corridor_%d' % n, 'ma2c', lanes, routes, [['Grr', 'rGg', 'GrG']] * n,
+                           [[k for k in (j - 1, j + 1) if 0 <= k < n] for j in range(n)], flows, streams, merge='yield', **env_kw)
+
+
+def burst(peak=9000, begin=0, check=True):
+    """One stream at 9000 veh/h (two or three vehicles a second) for 100 s into a 40 m lane that takes one insertion a second at
+    best: `pending` backs up for most of the run.  The lane and a second feeder zip into a 30 m lane whose signal is red in two of
+    three phases: it stays full up to its start, the two heads behind it compete for the little room it gives, and teleport_sec =
+    20 makes the teleport surrogate fire -- heads pass the red signal after 20 s of standing, heads that still find no room are
+    taken out of the network."""
+    lanes = [(40.0, 13.89, 0), (150.0, 13.89, 0), (30.0, 13.89, 1), (100.0, 13.89, -1)]
+    routes = [[[(0, 0), (2, 0), (3, -1)]], [[(1, 1), (2, 0), (3, -1)]]]
+    flows = [(begin, 100, peak, 0), (150, 200, 7200, 0), (0, 300, 1200, 1)]
+    return compile_network('burst', 'ia2c', lanes, routes, [['GG', 'rG', 'Gr'], ['r', 'r', 'G']], [[1], [0]], flows, check=check,
+                           episode_length_sec=300, teleport_sec=20)
+
+
+def zip254(n_lane=254, check=True):
+    """Groups of three feeders zipping into one signalised lane with its exit, plus two isolated junctions: n_lane lanes (254: 50
+    groups).  The feeders carry the least load, so after load sorting they have the highest indices -- up to 253, the largest a
+    feeder byte of Smem::up4 holds (0xFF = none)."""
+    groups = (n_lane - 4) // 5
+    lanes, flows, streams = [], [], []
+    paths = [[], [], []]
+    for g in range(groups):
+        m = len(lanes)
+        lanes += [(150.0, 13.89, g), (100.0, 13.89, -1)]
+        for f in range(3):
+            lanes.append((100.0 + 10.0 * f, 13.89, -1))
+            paths[f].append([(m + 2 + f, -1), (m, 0), (m + 1, -1)])
+            flows.append((0, 400, 260 + 30 * ((g + 2 * f) % 5), len(streams)))
+            streams.append((m + 2 + f, f))
+    for j in range(2):
+        m = len(lanes)
+        lanes += [(150.0, 13.89, groups + j), (100.0, 13.89, -1)]
+        paths[j].append([(m, 0), (m + 1, -1)])
+        flows.append((0, 400, 500, len(streams)))
+        streams.append((m, j))
+    while len(lanes) < n_lane:                      # (n_lane not of the form 5 g + 4: dead lanes make up the count)
+        lanes.append((50.0, 13.89, -1))
+    A = groups + 2
+    return compile_network('zip%d' % n_lane, 'ia2c', lanes, paths, [['G', 'r']] * A, [[(a + 1) % A] for a in range(A)], flows, streams,
+                           check=check, episode_length_sec=400, teleport_sec=60)
+
+
+class Net:
+    """One entry of NETWORKS.  plan: (MAXT, HELP, REC, KF, SPEC, threads) of tsc_env_step_plan for a fresh handle under `env` (the
+    TSC_ENV_* variables the case sets).  E instances run `steps` control steps; an action is random with probability p_random, else
+    the greedy rule (greedy_action); peak: the control step after which the vehicle state is compared too (and at the end);
+    live_floor: the least mean number of vehicles per instance the oracle must show over the run."""
+
+    def __init__(self, factory, why, plan, E, steps, p_random, seed, peak, live_floor, env=None):
+        self.factory, self.why, self.plan = factory, why, plan
+        self.E, self.steps, self.p_random, self.seed, self.peak, self.live_floor = E, steps, p_random, seed, peak, live_floor
+        self.env = dict(env or {})
+        self._scn = None
+
+    def scenario(self):
+        """The compiled scenario (built once; callers do not modify it)."""
+        if self._scn is None:
+            self._scn = self.factory()
+        return self._scn
+
+
+_NARROW, _WIDE = (256, 1, 0, 1, 0), (1024, 1, 0, 4, 0)
+NETWORKS = {
+    # n_mv = NU x NR = 166 x 24 > 8 x 256 words: the copy_words fallback of the prologue, runtime dimensions (no kSpec row matches)
+    'grid_x2': Net(lambda: tile(build_large_grid('ma2c'), 2, episode_length_sec=600), 'movement table past the register prefetch',
+                   _NARROW + (256,), 3, 120, 0.3, 410, 90, 60.0),
+    # the largest k tsc_env_create accepts (157,584 B of the 160 KiB of LDS; Krauss 163,728 B; k = 5: REFUSED): NU = 332 > 256 live lanes,
+    # workgroups of NLA = 384 threads (6 wavefronts), 4-wide flat phase
+    'grid_x4': Net(lambda: tile(build_large_grid('ma2c'), 4, episode_length_sec=500),
+                   'more than 256 live lanes: the wide runtime-dimension kernel', _WIDE + (384,), 2, 100, 0.3, 420, 80, 120.0),
+    # A > 128: numpy's np.sum splits the agents' rewards recursively; NU = 260 -> NLA = 320
+    'isolated_130': Net(lambda: isolated(130, objective='hybrid'), 'more than 128 agents: np_sum past one block', _WIDE + (320,),
+                        2, 120, 0.5, 430, 60, 200.0),
+    'isolated_254': Net(lambda: isolated(254, objective='hybrid'), '254 insertion streams (the limit), 254 agents', _WIDE + (512,),
+                        2, 120, 0.5, 440, 60, 400.0),
+    # A > 256: np.sum's left half splits again (300 -> 144 + 156 -> 72 + 72, 72 + 84); 250 of the junctions carry demand (254 streams at most)
+    'isolated_300': Net(lambda: isolated(300, live=[j for j in range(300) if j % 6 != 5], objective='hybrid'),
+                        'more than 256 agents: np_sum two levels down the left', _WIDE + (512,), 2, 120, 0.5, 445, 60, 400.0),
+    'few_threads': Net(few_threads, 'more streams and more agents than threads; eight streams on one entry lane', (256, 0, 0, 4, 0, 64),
+                       3, 90, 0.5, 450, 50, 60.0, env={'TSC_ENV_HELP': '0'}),
+    'merge4_zipper': Net(lambda: merge4('zipper'), 'four feeders of one lane as a zipper (TSC_MAX_UP)', _NARROW + (256,), 4, 80, 0.4, 460, 40, 25.0),
+    'merge4_yield': Net(lambda: merge4('yield'), 'four feeders of one lane by right of way', _NARROW + (256,), 4, 80, 0.4, 461, 40, 25.0),
+    'link62': Net(link62, 'signal link 62, k_max = 63, p_max = 8', _NARROW + (256,), 4, 80, 0.7, 470, 40, 15.0),
+    'ctrl8': Net(lambda: corridor(3, control_interval_sec=8, yellow_interval_sec=3, episode_length_sec=500), 'control interval 8 s / yellow 3 s, '
+                 'episode no multiple of 8', _NARROW + (256,), 3, 63, 0.5, 480, 30, 15.0),
+    'ctrl1': Net(lambda: corridor(3, control_interval_sec=1, yellow_interval_sec=0, episode_length_sec=140), 'control interval 1 s, no yellow',
+                 _NARROW + (256,), 3, 140, 0.1, 481, 100, 8.0),
+    'burst': Net(burst, 'several vehicles per second from one stream, pending backs up, frequent teleports', _NARROW + (256,),
+                 4, 60, 0.6, 490, 20, 8.0),
+    # NLA = 256 live lanes: 256 threads, no helper wavefront
+    'zip254': Net(zip254, 'feeder lane indices up to 253 in the merge arbitration bytes', _NARROW + (256,), 2, 80, 0.5, 500, 40, 100.0),
+}
+RECORDED = ['grid_x4']          # the one plan behind the LDS budget (whether k = 4 fits): as reported by an MI355X handle
+
+
+def _routes255():
+    """255 junctions, each on a route (and so a stream) of its own."""
+    n = 255
+    lanes = [(150.0, 13.89, j) for j in range(n)] + [(100.0, 13.89, -1) for j in range(n)]
+    return compile_network('routes255', 'ia2c', lanes, [[[(j, 0), (n + j, -1)]] for j in range(n)], [['G', 'r']] * n, [[] for _ in range(n)],
+                           [(0, 100, 300, j) for j in range(n)], check=False, episode_length_sec=100)
+
+
+def _no_route():
+    scn = copy.copy(isolated(2))
+    NL = scn.n_lane
+    scn.n_route = 0
+    for f in ('mv_next', 'mv_link', 'mv_yield', 'mv_prio', 'mv_zip'):
+        setattr(scn, f, np.zeros((NL, 0), np.int32))
+    scn.route_entry_lane, scn.flows, scn.route_names = np.zeros(0, np.int32), np.zeros((0, 4), np.int32), []
+    scn.stream_entry_lane = scn.stream_origin = scn.stream_limit = scn.stream_mode = scn.stream_choice = None
+    return scn
+
+
+def _zip_rank16():
+    scn = copy.copy(merge4('zipper'))
+    scn.mv_zip = np.where(scn.mv_zip == (3 | 4 << 8), 16 | 4 << 8, scn.mv_zip).astype(np.int32)
+    return scn
+
+
+# Scenarios one step past a limit: name -> (factory, what Scenario.check_limits says (None: only the library can tell), what tsc_env_create
+# says).  Host checks on both sides: nothing is ever launched with them.
+REFUSED = {
+    'routes255': (_routes255, 'at most 254 each', 'n_route 255 > 254'),
+    'streams255': (lambda: isolated(255, check=False), 'at most 254 each', 'n_stream 255 > 254'),
+    'entry9': (lambda: isolated(2, streams_per_lane={0: 9}, check=False), '9 streams enter lane', 'more than 8 streams enter lane'),
+    'link63': (lambda: link62(last=63, check=False), 'signal link index 63', 'signal link index 63 > 62'),
+    'ctrl9': (lambda: corridor(3, control_interval_sec=9, yellow_interval_sec=3, check=False), 'control_interval_sec 9 > 8', 'control interval 9 > 8 s'),
+    'rate256': (lambda: burst(peak=256 * 3600, check=False), 'emit 256 vehicles in one second', 'emit more than 255 vehicles per second'),
+    'zip256': (lambda: zip254(256, check=False), '256 lanes with zipper merges', 'zipper merges need lane indices < 255'),
+    'zip_rank16': (_zip_rank16, 'zipper slot overflow: rank 16', 'zipper slot overflow: rank 16'),
+    'grid_x5': (lambda: tile(build_large_grid('ma2c'), 5), None, 'LDS need [0-9]+ B > 160 KiB'),
+    'no_route': (_no_route, 'at least one of each', 'at least one of each'),
+    'scratch': (lambda: isolated(130, live=range(30), check=False), 'too few live lanes \\(60 of 260, 130 agents\\)',
+                'too few live lanes \\(60 of 260, 130 agents\\)'),
+    'begin_neg': (lambda: burst(begin=-5, check=False), 'flow 0 begins at second -5', 'flow 0 begins at second -5'),
+}
+
+
+# ---------------------------------------------------------------------------
+# the runs
+# ---------------------------------------------------------------------------
+def green_lanes(scn):
+    """Per agent and phase the positions (in the agent's lane list = its first observation entries) of the lanes with a 'G' link."""
+    out = []
+    for a in range(scn.n_agent):
+        lanes = [int(x) for x in scn.agent_lanes[a, :scn.agent_nlane[a]]]
+        out.append([sorted({lanes.index(int(scn.link_lane[a, k])) for k in range(int(scn.agent_nlink[a]))
+                            if scn.green_tab[a, p, k] == ord('G') and scn.link_lane[a, k] >= 0}) for p in range(int(scn.agent_nphase[a]))])
+    return out
+
+
+def draw_actions(scn, greens, rng, p_random, obs):
+    """One instance's actions of a control step: per agent a random phase with probability p_random, else the phase whose green lanes
+    hold the largest wave (first maximum); obs: the oracle's observation list.  The draws do not depend on the observations."""
+    act = np.zeros(scn.n_agent, np.int32)
+    rnd = rng.rand(scn.n_agent) < p_random
+    pick = rng.randint(0, 1 << 30, scn.n_agent)
+    for a in range(scn.n_agent):
+        if rnd[a]:
+            act[a] = pick[a] % scn.n_a_ls[a]
+        else:
+            act[a] = int(np.argmax([sum(float(obs[a][j]) for j in g) for g in greens[a]]))
+    return act
+
+
+def draw_policy(scn, rng):
+    """A random policy per agent (the fingerprints of MA2C), float32 [A, a_max], zero behind an agent's own phases."""
+    a_max = int(scn.green_tab.shape[1])
+    pol = np.zeros((scn.n_agent, a_max), np.float32)
+    for a, n in enumerate(scn.n_a_ls):
+        pol[a, :n] = rng.dirichlet(np.ones(n)).astype(np.float32)
+    return pol
+
+
+def eval_seeds(net, E=None):
+    """The test-mode seeds of a case, one per instance (VecTrafficEnv.reset(test_ind=arange(E)))."""
+    return tuple(net.seed + 1000 + e for e in range(net.E if E is None else E))
+
+
+def run_oracle(scn, net, on_second=None, train_mode=True, is_record=False, E=None):
+    """The oracle's side of a case: E OracleEnvs with seeds net.seed + e (test mode: eval_seeds(net)[e]), the actions of draw_actions
+    from one RandomState(net.seed).  Generator: first (-1, None, None, the reset observations [E], the OracleEnvs), then per control
+    step (t, acts [E, A], pols [E, A, a_max] or None, the results [E] of OracleEnv.step, the OracleEnvs), so that the GPU test steps
+    its environment in between.  on_second(e, ms): called after every simulated second of instance e."""
+    from oracle.env_oracle import OracleEnv
+    E = net.E if E is None else E
+    orc = [OracleEnv(scn, seed=net.seed + e, test_seeds=eval_seeds(net, E), train_mode=train_mode, is_record=is_record) for e in range(E)]
+    if on_second is not None:
+        for e, o in enumerate(orc):
+            def stepper(n=1, _ms=o.ms, _e=e, _step=o.ms.step):
+                for _ in range(n):
+                    _step(1)
+                    on_second(_e, _ms)
+            o.ms.step = stepper
+    obs = [o.reset(test_ind=e) for e, o in enumerate(orc)]
+    yield -1, None, None, obs, orc
+    greens, rng = green_lanes(scn), np.random.RandomState(net.seed)
+    for t in range(net.steps):
+        acts = np.stack([draw_actions(scn, greens, rng, net.p_random, obs[e]) for e in range(E)])
+        pols = np.stack([draw_policy(scn, rng) for e in range(E)]) if scn.agent == 'ma2c' else None
+        res = []
+        for e, o in enumerate(orc):
+            if pols is not None:
+                o.update_fingerprint([pols[e, a, :n] for a, n in enumerate(scn.n_a_ls)])
+            res.append(o.step(list(acts[e])))
+            obs[e] = res[-1][0]
+        yield t, acts, pols, res, orc
