@@ -56,7 +56,8 @@ SYMBOLS = ['tsc_last_error', 'tsc_version', 'tsc_profile_enable', 'tsc_profile_s
            'tsc_iql_compute_grads', 'tsc_iql_compute_grads_at', 'tsc_iql_grad_buffer', 'tsc_iql_apply_grads', 'tsc_iql_debug_batch', 'tsc_iql_path', 'tsc_iql_debug_clock',
            'tsc_iql_set_target', 'tsc_iql_sync_target', 'tsc_iql_set_target_params', 'tsc_iql_get_target_params', 'tsc_iql_debug_targets',
            'tsc_iql_set_per', 'tsc_iql_set_per_beta', 'tsc_iql_get_priorities', 'tsc_iql_set_priorities', 'tsc_iql_debug_per',
-           'tsc_iql_set_dueling', 'tsc_iql_get_dueling']
+           'tsc_iql_set_dueling', 'tsc_iql_get_dueling',
+           'tsc_iql_set_return_steps', 'tsc_iql_get_return_steps', 'tsc_iql_debug_nstep']
 
 
 def lib():

@@ -280,6 +280,111 @@ __global__ void iql_fill_kernel(float *x, long long n, float v) {
     if (i < n) x[i] = v;
 }
 
+// ---- multi-step returns (tsc_iql_set_return_steps; Sutton 1988, the n-step component of Rainbow) ---------------------------------
+// The window of every sampled row, walked over the ring at sample time (INTEGRATION.md "Multi-step returns"): from the sampled slot s,
+//   j = s; G = 0; c = 1; k = 0;  repeat { G += c r[e][j][a]; c *= gamma; ++k; stop at done[e][j], j == w or k == n; j = (j + 1) mod cap }
+// with w the newest slot of the rings.  G and c are float64 (the build forbids contraction: one rounding per product and per sum, the
+// oracle's), rounded to float32 once per row.  ns_slot [E][A][B] (idx layout) = j, ns_ret | ns_disc | ns_k [A][R] = G | gamma^k | k.
+// One thread per row in idx order: the draw and ns_slot move as whole cache lines, the three [A][R] rows in runs of B.  The k <= n reward
+// reads of a row are 4-byte gathers at stride A inside the cap x A floats of its instance's ring, and the done bytes lie inside the ring's
+// cap bytes -- the B rows of a ring and the A rings of an instance, neighbours in this order, meet in the same lines of L2.  s is
+// clamped like the gather's, so j stays inside [0, size): j only moves forward to w, and w = size - 1 while the ring is unfilled.
+__global__ void iql_nstep_kernel(int E, int A, int B, long long cap, int size, int w, int n, double gamma, const int *__restrict__ idx,
+                                 const float *__restrict__ r_rew, const uint8_t *__restrict__ r_done, int *__restrict__ ns_slot,
+                                 float *__restrict__ ns_ret, float *__restrict__ ns_disc, int *__restrict__ ns_k) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)E * A * B) return;
+    const int b = (int)(t % B);
+    const long long p = t / B, e = p / A, a = p % A;
+    const float *rew = r_rew + e * cap * A + a;
+    const uint8_t *dn = r_done + e * cap;
+    int j = iql_ring_slot(idx[t], size), k = 0;
+    double G = 0.0, c = 1.0;
+    for (;;) {
+        G += c * (double)rew[(long long)j * A];
+        c *= gamma;
+        ++k;
+        if (dn[j] || j == w || k >= n) break;
+        j = j + 1 == (int)cap ? 0 : j + 1;
+    }
+    const long long row = a * ((long long)E * B) + e * B + b;
+    ns_slot[t] = j;
+    ns_ret[row] = (float)G;
+    ns_disc[row] = (float)c;
+    ns_k[row] = k;
+}
+
+// iql_gather_kernel of a return-steps handle: S and the action are those of the sampled slot (idx), S1 and done those of the bootstrap
+// slot (ns_slot, already inside [0, size)), and the row's reward is its return G.
+__global__ void iql_gather_nstep_kernel(int E, int A, int SMAX, int B, long long cap, int size, const int *idx, const int *ns_slot,
+                                        const float *ns_ret, const float *r_obs, const float *r_next, const int *r_act, const uint8_t *r_done,
+                                        float *S, float *S1, int *act, float *rew, uint8_t *done) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int q4 = SMAX >> 2;
+    const long long R = (long long)E * B, tot = (long long)A * R * q4;
+    if (i < tot) {
+        const int c = (int)(i % q4);
+        const long long row = (i / q4) % R, a = i / ((long long)q4 * R);
+        const long long e = row / B, at = (e * A + a) * B + row % B;
+        const int s = iql_ring_slot(idx[at], size), j = iql_ring_slot(ns_slot[at], size);
+        reinterpret_cast<float4 *>(S)[i] = *reinterpret_cast<const float4 *>(r_obs + ((e * cap + s) * A + a) * SMAX + 4 * c);
+        reinterpret_cast<float4 *>(S1)[i] = *reinterpret_cast<const float4 *>(r_next + ((e * cap + j) * A + a) * SMAX + 4 * c);
+    }
+    if (i < (long long)A * R) {
+        const long long row = i % R, a = i / R, e = row / B, at = (e * A + a) * B + row % B;
+        const int s = iql_ring_slot(idx[at], size), j = iql_ring_slot(ns_slot[at], size);
+        act[i] = r_act[(e * cap + s) * A + a];
+        rew[i] = ns_ret[i];
+        done[i] = r_done[e * cap + j];
+    }
+}
+
+// The TD kernels of a return-steps handle, one body: tq = done ? G : G + disc[i] q1 with the row's own discount gamma^k in place of the
+// scalar gamma.  FORM 0: iql_td_kernel<> (sparse dQ, no weight), 1: iql_td_kernel<true> (weights in, |delta| out), 2: iql_td_duel_kernel
+// (dense dQ over the combined values, always weighted).  w, td and n_act are read only by the forms that have them.
+template <int FORM>
+__global__ void iql_td_nstep_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done, const int *n_act,
+                                    const float *__restrict__ w, const float *__restrict__ disc, long long R, int A, float *dQ,
+                                    float *__restrict__ td, double *stats) {
+    static_assert(FORM >= 0 && FORM <= 2, "0 plain, 1 prioritized replay, 2 dueling");
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    float l = 0.f;
+    int a = 0;
+    if (i < (long long)A * R) {
+        a = (int)(i / R);
+        const float r = rew[i];
+        const float tq = done[i] ? r : r + disc[i] * q1[i];
+        const int k0 = act[i];
+        const float d = Q[i * kQ + k0] - tq;
+        float g;
+        if constexpr (FORM == 0) {
+            g = 2.0f * d / (float)R;
+            l = d * d / (float)R;
+        } else {
+            const float wi = w[i];
+            g = 2.0f * d * wi / (float)R;
+            l = d * d * wi / (float)R;
+            td[i] = fabsf(d);
+        }
+        float row[kQ];
+        if constexpr (FORM == 2) {
+            const int na = n_act[a];
+            const float inv_na = 1.f / (float)na;
+#pragma unroll
+            for (int k = 0; k < kQ; ++k) {
+                const float off = k < na ? -inv_na : k == kQ - 1 ? 1.f : 0.f;
+                row[k] = g * (k == k0 ? 1.f + off : off);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kQ; ++k) row[k] = k == k0 ? g : 0.f;
+        }
+        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = make_float4(row[0], row[1], row[2], row[3]);
+        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = make_float4(row[4], row[5], row[6], row[7]);
+    }
+    td_loss_sum(l, a, i, R, A, stats);
+}
+
 // ---- prioritized replay (tsc_iql_set_per; proportional, Schaul et al. 2016) -----------------------------------------------------
 // Stored priorities prio [E][A][cap] (already (|delta| + eps)^alpha, contiguous per ring: the sampler reads one whole ring at a time)
 // and the rings' running maxima qmax [E][A].
@@ -504,13 +609,16 @@ struct QPlan {
     QKernel<const float *, int, double, unsigned long long, unsigned long long, int, float *, float *, int *, QDuel> act_duel;
     QKernel<const float *, const float *, float *, QDuel> grad_duel;
     QKernel<const float *, float *, int *, QDuel> target_duel[2];
+    // multi-step returns (tsc_iql_set_return_steps): the target kernels with the rows' return and discount; launched with idx = the bootstrap slots
+    QKernel<const float *, float *, int *, QNStep> target_n[2];
+    QKernel<const float *, float *, int *, QDuel, QNStep> target_duel_n[2];
     int S = 0, cps = 0;           // row splits per agent (workgroups = A S); 64-row chunks per split
-    struct Entry { const void *fn; int lds; } entries[12] = {};    // (ten in use)
+    struct Entry { const void *fn; int lds; } entries[16] = {};    // (fourteen in use)
     int n_entries = 0;
 
     template <class... Args> void set(QKernel<Args...> &k, void (*fn)(QFusedArgs, Args...), int lds) {
         k.fn = fn; k.lds = lds;
-        assert(n_entries < 12);
+        assert(n_entries < 16);
         entries[n_entries++] = {(const void *)fn, lds};
     }
     template <int NM1> static QPlan make() {
@@ -526,6 +634,10 @@ struct QPlan {
         P.set(P.grad_duel, iql_fused_grad_kernel<NM1, 8, true, true, const float *, const float *, float *, QDuel>, QFusedLds<NM1>::duel_floats * 4);
         P.set(P.target_duel[0], iql_fused_target_kernel<NM1, 8, false, QDuel>, fwd);
         P.set(P.target_duel[1], iql_fused_target_kernel<NM1, 8, true, QDuel>, 2 * fwd);
+        P.set(P.target_n[0], iql_fused_target_kernel<NM1, 8, false, QNStep>, fwd);
+        P.set(P.target_n[1], iql_fused_target_kernel<NM1, 8, true, QNStep>, 2 * fwd);
+        P.set(P.target_duel_n[0], iql_fused_target_kernel<NM1, 8, false, QDuel, QNStep>, fwd);
+        P.set(P.target_duel_n[1], iql_fused_target_kernel<NM1, 8, true, QDuel, QNStep>, 2 * fwd);
         return P;
     }
 };
@@ -571,6 +683,12 @@ struct tsc_iql {
     // dueling head (tsc_iql_set_dueling): column 7 of Wq | bq is the value stream; the weights of a step without prioritized replay [A][R], all 1
     int duel = 0;
     float *w_one = nullptr;
+    // multi-step returns (tsc_iql_set_return_steps): the horizon n (1 = the reference's one-step target) and iql_nstep_kernel's outputs --
+    // bootstrap slots [E][A][B] (idx layout), returns G, discounts gamma^k and horizons k [A][R]
+    int nstep = 1;
+    int *ns_slot = nullptr, *ns_k = nullptr;
+    float *ns_ret = nullptr, *ns_disc = nullptr;
+    bool ns_valid = false;        // a compute_grads ran on the handle while return_steps > 1
     std::vector<int> n_act_host;
 };
 
@@ -881,7 +999,8 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
     const bool dbl = armed && h->tgt_double;                 // ... at the online net's first maximum
     const float *tp = armed ? h->tparams : h->params;        // the net behind the TD targets
     const bool duel = h->duel != 0;                          // dueling head: combined Q everywhere, dense dQ
-    const bool two_launch = armed || per || duel;            // fused path: the TD targets in a launch of their own, else inside the gradient's
+    const bool nstep = h->nstep > 1;                         // multi-step returns: s', done, G and gamma^k of the row's window
+    const bool two_launch = armed || per || duel || nstep;   // fused path: the TD targets in a launch of their own, else inside the gradient's
     TSC_HIP(hipMemsetAsync(h->stats, 0, sizeof(double) * A * 2, st));
     if (given) {        // (e.g. the reference's random.sample); the gather clamps every index into [0, size)
         TSC_HIP(hipMemcpyAsync(h->idx, idx_dev, sizeof(int) * E * A * h->B, hipMemcpyDeviceToDevice, st));
@@ -901,7 +1020,16 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
             hipLaunchKernelGGL(iql_sample_kernel, dim3((unsigned)((E * A + 127) / 128)), dim3(128), 0, st, (int)E, (int)A, h->B, size,
                                (unsigned long long)seed, (unsigned long long)update_index, h->idx);
     }
-    if (armed || duel) h->y_valid = true;
+    if (nstep) {        // the window of every sampled row, behind the draw: bootstrap slot, return, discount
+        tsc::ProfScope ps(tsc::KID_IQL_NSTEP, st);
+        const long long rows = E * A * h->B;
+        hipLaunchKernelGGL(iql_nstep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, (int)E, (int)A, h->B, h->cap, (int)size,
+                           (int)((h->cum - 1) % h->cap), h->nstep, h->gamma, h->idx, h->r_rew, h->r_done, h->ns_slot, h->ns_ret, h->ns_disc,
+                           h->ns_k);
+        TSC_HIP(hipGetLastError());
+        h->ns_valid = true;
+    }
+    if (armed || duel || nstep) h->y_valid = true;
     if (h->fused) {
         const QPlan &P = h->plan;
         const QFusedArgs fa = fused_args(h, size);
@@ -910,7 +1038,13 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
             // (prioritized replay always takes this route; without a target network tp is the parameters themselves)
             {
                 tsc::ProfScope ps(tsc::KID_IQL_TARGET, st);
-                if (duel) P.target_duel[dbl].launch(grid, st, fa, tp, h->y, h->astar, QDuel{});
+                if (nstep) {    // s' and done at the bootstrap slot: the target kernel finds its slot through idx
+                    QFusedArgs fn = fa;
+                    fn.idx = h->ns_slot;
+                    const QNStep ns{h->ns_ret, h->ns_disc};
+                    if (duel) P.target_duel_n[dbl].launch(grid, st, fn, tp, h->y, h->astar, QDuel{}, ns);
+                    else P.target_n[dbl].launch(grid, st, fn, tp, h->y, h->astar, ns);
+                } else if (duel) P.target_duel[dbl].launch(grid, st, fa, tp, h->y, h->astar, QDuel{});
                 else P.target[dbl].launch(grid, st, fa, tp, h->y, h->astar);
             }
             TSC_HIP(hipGetLastError());
@@ -930,6 +1064,11 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
         return 0;
     }
     const long long tot = A * R * (L.SMAX / 4);
+    if (nstep)
+        hipLaunchKernelGGL(iql_gather_nstep_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)E, (int)A, L.SMAX, h->B, h->cap,
+                           (int)size, h->idx, h->ns_slot, h->ns_ret, h->r_obs, h->r_next, h->r_act, h->r_done, h->S, h->S1, h->act, h->rew,
+                           h->done);
+    else
     hipLaunchKernelGGL(iql_gather_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)E, (int)A, L.SMAX, h->B, h->cap,
                        (int)size, h->idx, h->r_obs, h->r_next, h->r_act, h->r_rew, h->r_done, h->S, h->S1, h->act, h->rew, h->done);
     TSC_HIP(hipGetLastError());
@@ -945,8 +1084,19 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
         hipLaunchKernelGGL(iql_qmax_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->n_act, R, (int)A, h->q1);
     }
     if (q_forward(h, h->params, h->S, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
-    if (duel) {
-        duel_combine(h, h->Q, R);
+    if (duel) duel_combine(h, h->Q, R);
+    if (nstep) {        // the row's own discount gamma^k in place of gamma
+        const dim3 tg((unsigned)((A * R + 255) / 256));
+        if (duel)
+            hipLaunchKernelGGL(iql_td_nstep_kernel<2>, tg, dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, h->n_act, per ? h->w : h->w_one,
+                               h->ns_disc, R, (int)A, h->dQ, h->td, h->stats);
+        else if (per)
+            hipLaunchKernelGGL(iql_td_nstep_kernel<1>, tg, dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, h->n_act, h->w, h->ns_disc, R,
+                               (int)A, h->dQ, h->td, h->stats);
+        else
+            hipLaunchKernelGGL(iql_td_nstep_kernel<0>, tg, dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, h->n_act, nullptr, h->ns_disc, R,
+                               (int)A, h->dQ, nullptr, h->stats);
+    } else if (duel) {
         hipLaunchKernelGGL(iql_td_duel_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
                            h->n_act, per ? h->w : h->w_one, R, (int)A, (float)h->gamma, h->dQ, h->td, h->stats);
     } else if (per)
@@ -1075,21 +1225,25 @@ int tsc_iql_get_target_params(tsc_iql *h, float *p) {
 
 int tsc_iql_debug_targets(tsc_iql *h, float *y_host, int32_t *astar_host) {
     if (!h || !y_host) return tsc::fail("tsc_iql_debug_targets: bad arguments");
-    if ((!h->tgt_period && !h->duel) || !h->y_valid) return tsc::fail("tsc_iql_debug_targets: no tsc_iql_compute_grads on an armed handle yet");
+    if ((!h->tgt_period && !h->duel && h->nstep <= 1) || !h->y_valid) return tsc::fail("tsc_iql_debug_targets: no tsc_iql_compute_grads on an armed handle yet");
     const size_t AR = (size_t)h->lay.A * h->E * h->B;
     TSC_HIP(hipStreamSynchronize(h->stream));
     if (h->fused) {
         TSC_HIP(hipMemcpy(y_host, h->y, sizeof(float) * AR, hipMemcpyDeviceToHost));
     } else {
         // the grouped path keeps q1 (what iql_td_kernel reads): the same float32 expression on the host
-        std::vector<float> q1(AR), rew(AR);
+        std::vector<float> q1(AR), rew(AR), disc;
         std::vector<uint8_t> done(AR);
+        if (h->nstep > 1) {     // a return-steps handle: rew holds G, done the bootstrap slot's flag, and the discount is the row's gamma^k
+            disc.resize(AR);
+            TSC_HIP(hipMemcpy(disc.data(), h->ns_disc, sizeof(float) * AR, hipMemcpyDeviceToHost));
+        }
         TSC_HIP(hipMemcpy(q1.data(), h->q1, sizeof(float) * AR, hipMemcpyDeviceToHost));
         TSC_HIP(hipMemcpy(rew.data(), h->rew, sizeof(float) * AR, hipMemcpyDeviceToHost));
         TSC_HIP(hipMemcpy(done.data(), h->done, AR, hipMemcpyDeviceToHost));
         const float gamma = (float)h->gamma;
         for (size_t i = 0; i < AR; ++i) {
-            const float bootstrap = gamma * q1[i];
+            const float bootstrap = (disc.empty() ? gamma : disc[i]) * q1[i];
             y_host[i] = done[i] ? rew[i] : rew[i] + bootstrap;
         }
     }
@@ -1202,6 +1356,42 @@ int tsc_iql_set_dueling(tsc_iql *h, int32_t enable) {
 int tsc_iql_get_dueling(tsc_iql *h, int32_t *enabled) {
     if (!h || !enabled) return tsc::fail("tsc_iql_get_dueling: bad arguments");
     *enabled = h->duel;
+    return 0;
+}
+
+int tsc_iql_set_return_steps(tsc_iql *h, int32_t n) {
+    if (!h) return tsc::fail("null handle");
+    if (n < 1 || n > TSC_IQL_MAX_RETURN_STEPS)
+        return tsc::fail("tsc_iql_set_return_steps: n %d outside [1, %d]", n, TSC_IQL_MAX_RETURN_STEPS);
+    if (n != h->nstep) { h->y_valid = false; h->ns_valid = false; }
+    if (n == 1) { h->nstep = 1; return 0; }        // back to the kernels of a handle that was never armed
+    const long long AR = (long long)h->lay.A * h->E * h->B;
+    TSC_HIP(hipSetDevice(h->device));
+    TSC_HIP(alloc_once(h, &h->ns_slot, AR));
+    TSC_HIP(alloc_once(h, &h->ns_ret, AR));
+    TSC_HIP(alloc_once(h, &h->ns_disc, AR));
+    TSC_HIP(alloc_once(h, &h->ns_k, AR));
+    if (h->fused) TSC_HIP(alloc_once(h, &h->y, AR));
+    h->nstep = n;
+    return 0;
+}
+
+int tsc_iql_get_return_steps(tsc_iql *h, int32_t *n) {
+    if (!h || !n) return tsc::fail("tsc_iql_get_return_steps: bad arguments");
+    *n = h->nstep;
+    return 0;
+}
+
+int tsc_iql_debug_nstep(tsc_iql *h, int32_t *slot_host, float *ret_host, float *disc_host, int32_t *k_host) {
+    if (!h || !slot_host || !ret_host || !disc_host || !k_host) return tsc::fail("tsc_iql_debug_nstep: bad arguments");
+    if (h->nstep <= 1 || !h->ns_valid)
+        return tsc::fail("tsc_iql_debug_nstep: no tsc_iql_compute_grads with return_steps > 1 yet (tsc_iql_set_return_steps)");
+    const size_t AR = (size_t)h->lay.A * h->E * h->B;
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    TSC_HIP(hipMemcpy(slot_host, h->ns_slot, sizeof(int32_t) * AR, hipMemcpyDeviceToHost));
+    TSC_HIP(hipMemcpy(ret_host, h->ns_ret, sizeof(float) * AR, hipMemcpyDeviceToHost));
+    TSC_HIP(hipMemcpy(disc_host, h->ns_disc, sizeof(float) * AR, hipMemcpyDeviceToHost));
+    TSC_HIP(hipMemcpy(k_host, h->ns_k, sizeof(int32_t) * AR, hipMemcpyDeviceToHost));
     return 0;
 }
 

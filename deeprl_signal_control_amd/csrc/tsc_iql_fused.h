@@ -126,7 +126,7 @@ struct QW1 {
 
 // TAG: the armed handles' kernels take instantiations of their own (1: target network, 2: prioritized replay): how the compiler inlines the lambdas below
 // depends on how many callers an instantiation has, and the default kernels must compile to what they compiled to without them
-// (3: the dueling head's kernels)
+// (3: the dueling head's kernels; 4 / 5: the multi-step target kernels, plain / dueling)
 template <int NB, int NM1, int NMW, int TAG = 0>
 __device__ __forceinline__ void q_nets(const QW1<NM1, NMW> &w1, const float4 (&s)[NB][3], const float *sm, const QRanges &rg, int m, int kq,
                                        f32x4 (&X1)[NB][NM1], f32x4 (&X2)[NB][4], f32x4 (&q)[NB], long long *fst = nullptr) {
@@ -859,11 +859,23 @@ __global__ void __launch_bounds__(256, 1) iql_fused_act_kernel(QFusedArgs p, con
 // runs on the same observation registers), rows requested one chunk ahead.
 // D = QDuel (tsc_iql_set_dueling; QPlan::target_duel, the act kernel's device): both nets' outputs are combined with q_duel first, so the
 // maximum, a* and the picked value are those of the combined values.
+// D ends in QNStep (multi-step returns, tsc_iql_set_return_steps; QPlan::target_n / target_duel_n): the handle launches the kernel with
+// p.idx = ns_slot, the bootstrap slot j of every row as iql_nstep_kernel left it, so s' and done are slot j's as they stand; the row's
+// return G and discount gamma^k come from the two arrays [A][R] of the trailing argument in place of r_rew[slot] and p.gamma:
+//   y[a][row] = done[j] ? G : G + gamma^k Qsel(next_obs[j]).  The instantiations without QNStep carry neither argument nor load.
+struct QNStep { const float *ret, *disc; };
+__device__ __forceinline__ QNStep q_nstep_of() { return QNStep{nullptr, nullptr}; }
+__device__ __forceinline__ QNStep q_nstep_of(QDuel) { return QNStep{nullptr, nullptr}; }
+__device__ __forceinline__ QNStep q_nstep_of(QNStep ns) { return ns; }
+__device__ __forceinline__ QNStep q_nstep_of(QDuel, QNStep ns) { return ns; }
 template <int NM1, int NMW, bool DBL, class... D>
 __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, const float *__restrict__ tparams, float *__restrict__ y,
-                                                                  int *__restrict__ astar, D...) {
-    static_assert(sizeof...(D) <= 1 && (std::is_same_v<D, QDuel> && ...), "iql_fused_target_kernel<.., DBL> or <.., DBL, QDuel>");
-    constexpr bool DUEL = sizeof...(D) == 1;
+                                                                  int *__restrict__ astar, D... d_arg) {
+    static_assert(sizeof...(D) <= 2 && ((std::is_same_v<D, QDuel> || std::is_same_v<D, QNStep>) && ...),
+                  "iql_fused_target_kernel<.., DBL>, <.., DBL, QDuel>, <.., DBL, QNStep> or <.., DBL, QDuel, QNStep>");
+    constexpr bool DUEL = (std::is_same_v<D, QDuel> || ...), NSTEP = (std::is_same_v<D, QNStep> || ...);
+    static_assert(sizeof...(D) == (DUEL ? 1 : 0) + (NSTEP ? 1 : 0), "each trailing argument at most once");
+    constexpr int TAG = NSTEP ? (DUEL ? 5 : 4) : DUEL ? 3 : 1;       // q_nets: the multi-step variants take instantiations of their own, too
     using LD = QFusedLds<NM1>;
     extern __shared__ __attribute__((aligned(16))) float q_smem[];
     float *smT = q_smem, *smO = q_smem + LD::fwd_floats;
@@ -899,8 +911,17 @@ __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, 
         const float *o1 = p.r_next + tr * p.SMAX;
 #pragma unroll
         for (int qp = 0; qp < 3; ++qp) r.s1[qp] = q_obs4(o1, 16 * qp + 4 * kq, p.SMAX, r.ok);
+        if constexpr (NSTEP) r.rew = q_nstep_of(d_arg...).ret[(long long)a * p.R + (row < uR ? row : uR - 1)];     // G of the row
+        else
         r.rew = p.r_rew[tr];
         r.done = p.r_done[(long long)sl.e * p.cap + sl.slot];
+    };
+    // NSTEP: gamma^k of this lane's row in the current / next chunk (requested with the rows)
+    [[maybe_unused]] float gcur = 0.f, gnxt = 0.f;
+    [[maybe_unused]] auto disc_of = [&](long long c) {
+        const unsigned row = ((unsigned)c << 6) + 16 * wave + n;
+        if constexpr (NSTEP) return q_nstep_of(d_arg...).disc[(long long)a * p.R + (row < uR ? row : uR - 1)];
+        else return 0.f;
     };
     long long *wg_dbg = p.dbg ? p.dbg + 64 + 2 * (long long)gridDim.x + 2 * blockIdx.x : nullptr;
     if (wg_dbg && tid == 0) wg_dbg[0] = wall_clock64();
@@ -908,24 +929,26 @@ __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, 
     QSlot slot_n = {0, 0};
     if (c0 < c1) {
         load_rows(c0, slot_of(c0), cur);
+        if constexpr (NSTEP) gcur = disc_of(c0);
         slot_n = slot_of(c0 + 1 < c1 ? c0 + 1 : c0);
     }
     __syncthreads();                                      // weights are in LDS
 
     for (long long c = c0; c < c1; ++c) {
         load_rows(c + 1 < c1 ? c + 1 : c, slot_n, nxt);
+        if constexpr (NSTEP) gnxt = disc_of(c + 1 < c1 ? c + 1 : c);
         slot_n = slot_of(c + 2 < c1 ? c + 2 : c);
         float4 ss[1][3];
 #pragma unroll
         for (int qp = 0; qp < 3; ++qp) ss[0][qp] = cur.s1[qp];
         f32x4 X1[1][NM1], X2[1][4], qt[1];
-        q_nets<1, NM1, NMW, DUEL ? 3 : 1>(w1t, ss, smT, rg, n, kq, X1, X2, qt);
+        q_nets<1, NM1, NMW, TAG>(w1t, ss, smT, rg, n, kq, X1, X2, qt);
         if constexpr (DUEL) qt[0] = q_duel(qt[0], na, inv_na, n, kq);
         float q1 = -INFINITY;
         int best = 8;
         if constexpr (DBL) {
             f32x4 qo[1];
-            q_nets<1, NM1, NMW, DUEL ? 3 : 1>(w1o, ss, smO, rg, n, kq, X1, X2, qo);
+            q_nets<1, NM1, NMW, TAG>(w1o, ss, smO, rg, n, kq, X1, X2, qo);
             if constexpr (DUEL) qo[0] = q_duel(qo[0], na, inv_na, n, kq);
             // first maximum of the online values over this row's four lanes (actions 4 kq + i, kq < 2), the target value riding along
             float bv = -INFINITY;
@@ -944,13 +967,17 @@ __global__ void __launch_bounds__(256, 1) iql_fused_target_kernel(QFusedArgs p, 
             q1 = fmaxf(q1, __shfl_xor(q1, 16, 64));
             q1 = fmaxf(q1, __shfl_xor(q1, 32, 64));
         }
-        const float tq = cur.done ? cur.rew : cur.rew + p.gamma * q1;
+        float tq;
+        if constexpr (NSTEP) tq = cur.done ? cur.rew : cur.rew + gcur * q1;
+        else
+        tq = cur.done ? cur.rew : cur.rew + p.gamma * q1;
         if (kq == 0 && cur.ok) {
             const long long o = (long long)a * p.R + (((unsigned)c << 6) + 16 * wave + n);
             y[o] = tq;
             if constexpr (DBL) astar[o] = best;
         }
         cur = nxt;
+        if constexpr (NSTEP) gcur = gnxt;
     }
     if (wg_dbg && tid == 0) wg_dbg[1] = wall_clock64();
 }

@@ -25,7 +25,9 @@ IQL_DEFAULTS = dict(max_grad_norm=40.0, gamma=0.99, lr_init=1e-4, lr_decay='cons
                     buffer_size=1000.0, reward_norm=3000.0, reward_clip=2.0,     # config/config_iqld_large.ini
                     target_update=0, double_q=0,    # opt-in, not the reference's: target network refreshed every N Adam steps / Double DQN
                     prioritized_replay=0, per_alpha=0.6, per_beta=0.4, per_eps=0.01,   # opt-in: proportional prioritized replay (Schaul et al. 2016)
-                    dueling=0)      # opt-in, IQL-DNN only: dueling head (Wang et al. 2016); with double_q and prioritized_replay the literature's 3DQN
+                    dueling=0,      # opt-in, IQL-DNN only: dueling head (Wang et al. 2016); with double_q and prioritized_replay the literature's 3DQN
+                    return_steps=1)  # opt-in: multi-step (n-step) returns, 1 <= n <= 32 (n_step is taken: the batch size, as in the reference)
+MAX_RETURN_STEPS = 32                                                            # include/tsc.h TSC_IQL_MAX_RETURN_STEPS
 N_UPDATE = 10                                                                    # agents/models.py:324
 
 
@@ -50,6 +52,21 @@ def dueling_config(cfg):
     if on not in (0, 1) or on != float(cfg['dueling']):
         raise ValueError('dueling must be 0 or 1 (got %r)' % (cfg['dueling'],))
     return on
+
+
+def return_steps_config(cfg):
+    """return_steps of a coerced [MODEL_CONFIG]: 1 is the reference's one-step TD target, n in [2, 32] bootstraps after up to n control steps
+    (include/tsc.h tsc_iql_set_return_steps).  Also takes the section as it was given: a string is read as a number first, so '2.5' is
+    refused here where coerce_config would have cut it to 2."""
+    raw = cfg['return_steps']
+    try:
+        n = int(float(raw))
+        whole = not isinstance(raw, bool) and n == float(raw)
+    except (TypeError, ValueError, OverflowError):
+        n, whole = None, False
+    if not whole or not 1 <= n <= MAX_RETURN_STEPS:
+        raise ValueError('return_steps must be an integer in [1, %d] (got %r)' % (MAX_RETURN_STEPS, raw))
+    return n
 
 
 def per_config(cfg):
@@ -118,6 +135,9 @@ def _setup_lib(L):
     L.tsc_iql_debug_per.argtypes = [vp, vp, vp]
     L.tsc_iql_set_dueling.argtypes = [vp, C.c_int32]
     L.tsc_iql_get_dueling.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_iql_set_return_steps.argtypes = [vp, C.c_int32]
+    L.tsc_iql_get_return_steps.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_iql_debug_nstep.argtypes = [vp, vp, vp, vp, vp]
     L._iql_ready = True
 
 
@@ -234,6 +254,8 @@ class VecIQL:
         self.target_update, self.double_q = target_config(cfg)
         self.prioritized_replay, self.per_alpha, self.per_beta, self.per_eps = per_config(cfg)
         self.dueling = dueling_config(cfg)
+        given = {str(k).lower(): v for k, v in dict(model_config or {}).items()}      # (before coerce_config cut a string like '2.5' to 2)
+        self.return_steps = return_steps_config({'return_steps': given.get('return_steps', cfg['return_steps'])})
         if self.dueling and model_type != 'dqn':
             raise ValueError("dueling = 1 needs model_type 'dqn': a linear Q with a value column spans the same functions")
         self.per_n = 0              # environment steps the beta schedule has counted (backward calls x batch_size, like lr_scheduler.n)
@@ -290,6 +312,8 @@ class VecIQL:
         if self.prioritized_replay:
             _lib.check(L.tsc_iql_set_per(h, 1, self.per_alpha, self.per_eps))
             _lib.check(L.tsc_iql_set_per_beta(h, self.per_beta))
+        if self.return_steps > 1:   # (no checkpoint key: the parameters mean the same under every horizon)
+            _lib.check(L.tsc_iql_set_return_steps(h, self.return_steps))
         self.init_params(seed)
         if self.world > 1:
             t = torch.from_numpy(self.get_flat()).to(self.device)

@@ -228,6 +228,8 @@ def train(args):
         logging.info('Training: prioritized replay, alpha %g, beta %g -> 1, eps %g' % (model.per_alpha, model.per_beta, model.per_eps))
     if getattr(model, 'dueling', 0):
         logging.info('Training: dueling head, Q = V + A - mean(A)')
+    if getattr(model, 'return_steps', 1) > 1:
+        logging.info('Training: %d-step returns' % model.return_steps)
     trainer = VecTrainer(env, model, counter, log_rewards=True)
     data = trainer.run_training(run_test=in_test, output_path=dirs['data'])
     if post_test:                                               # Tester.run_offline (utils.py:324-338)

@@ -100,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -578,6 +578,30 @@ int tsc_iql_debug_per(tsc_iql *h, float *w_host, float *td_host);
  * answers on a dueling handle without a target network (a* = -1 unless double_q). */
 int tsc_iql_set_dueling(tsc_iql *h, int32_t enable);
 int tsc_iql_get_dueling(tsc_iql *h, int32_t *enabled);          /* 1 while the dueling head is armed */
+/* Multi-step (n-step) returns (opt-in; Sutton 1988, the n-step component of Rainbow; the reference bootstraps after one control step).
+ * Nothing changes at tsc_iql_add_transition: the window of a sampled row is walked at sample time over the rewards and done flags of its
+ * ring.  For a sampled slot s of instance e, agent a, with the newest slot w = (cum - 1) mod cap:
+ *   j = s; G = 0; c = 1; k = 0
+ *   repeat:  G += c r[e][j][a];  c *= gamma;  k += 1;  stop if done[e][j] or j == w or k == n;  j = (j + 1) mod cap
+ *   y = done[e][j] ? G : G + c Qsel(next_obs[e][j][a])                              (c = gamma^k, 1 <= k <= n)
+ * Qsel is whatever the handle is armed with (max of the net being updated, max of the frozen copy, Double DQN's pick, each on the combined
+ * values of a dueling handle).  The window never runs past an episode end nor past the newest transition -- a row cut by the newest slot
+ * bootstraps early with its own gamma^k -- and n >= cap is harmless (the walk meets w before it returns to s).  G and c are accumulated in
+ * float64 over the ring's float32 rewards and rounded to float32 once per row.  Q(s)[a], the action, the importance weight and the
+ * priority write-back stay those of slot s; with prioritized replay |delta| is taken against the n-step target.  k = 1 on every row is the
+ * one-step target.  PRECONDITION (not checked): between two done flags, consecutive slots of a ring hold consecutive steps of one
+ * trajectory -- a caller who feeds tsc_iql_add_transition by hand must keep that.
+ * 1 <= n <= TSC_IQL_MAX_RETURN_STEPS, refused outside; n = 1 disarms: the handle launches what a handle that was never armed launches.  May
+ * be called at any time; the rings are untouched.  The first arming allocates the pre-pass outputs [A][E * batch_size] and, on the fused
+ * path, the per-row targets; an armed step runs iql_nstep_kernel (profile id iql_nstep) behind the draw and, on the fused path, always
+ * takes the two-launch route of tsc_iql_set_target.  tsc_iql_debug_targets also answers on a return-steps handle. */
+#define TSC_IQL_MAX_RETURN_STEPS 32
+int tsc_iql_set_return_steps(tsc_iql *h, int32_t n);
+int tsc_iql_get_return_steps(tsc_iql *h, int32_t *n);
+/* Debug / parity access: the pre-pass outputs of the last tsc_iql_compute_grads / _at with return_steps > 1 -- the bootstrap slot j
+ * [E][A][batch_size] (the layout of tsc_iql_debug_batch) and G, gamma^k, k [A][E * batch_size].  Refused before the first such step.
+ * Synchronises. */
+int tsc_iql_debug_nstep(tsc_iql *h, int32_t *slot_host, float *ret_host, float *disc_host, int32_t *k_host);
 /* Measurement hook of the fused learner (tools/bench_iql.py --stamps): enable != 0 allocates the stamp buffer; the next
  * tsc_iql_compute_grads then records, for every workgroup, its start / end on the 100-MHz wall clock ([64 + 2 b],
  * [64 + 2 b + 1]) and -- in a measurement build with -DTSC_IQL_STAMPS (tools/build_variant.sh; the stamps' branches are kept

@@ -2,13 +2,14 @@
 """Times the IQL-DNN learner's launches in isolation (large_grid, E = 1024 by default): the minibatch gradient
 (tsc_iql_compute_grads: sample + fused gradient + reduce) and the acting forward, with HIP events on the launch stream.
 
-    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--target-update N [--double-q]] [--per] [--dueling]
+    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--target-update N [--double-q]] [--per] [--dueling] [--return-steps N]
 
 --target-update N arms the target network (two launches per gradient: the TD targets from the frozen copy, then the gradient with one
 row set).  --per arms prioritized replay (the proportional sampler in place of the Floyd draw, the
 two-launch gradient with importance weights, the priority write-back and, on add_transition, the fill at the ring's maximum; the rings are
 filled to their capacity then, the sampler's full read).  --dueling arms the dueling head (always the two-launch gradient, its own
-instantiations of the act, target and gradient kernels).  --split adds the per-kernel split of the minibatch step ("kernel_us": iql_target / iql_grad / ..., each measured in a
+instantiations of the act, target and gradient kernels).  --return-steps N arms multi-step returns (the window pre-pass iql_nstep behind the
+draw, always the two-launch gradient, the target kernel's instantiations with the rows' return and discount).  --split adds the per-kernel split of the minibatch step ("kernel_us": iql_target / iql_grad / ..., each measured in a
 pass of its own with only its launches bracketed: 5 x reps more minibatch steps).  --stamps reads the gradient kernel's workgroups
 and, on an armed handle, the target kernel's as well ("target_wg_us").
 """
@@ -32,6 +33,7 @@ def main():
     ap.add_argument('--double-q', action='store_true', help='[MODEL_CONFIG] double_q = 1 (needs --target-update)')
     ap.add_argument('--per', action='store_true', help='[MODEL_CONFIG] prioritized_replay = 1')
     ap.add_argument('--dueling', action='store_true', help='[MODEL_CONFIG] dueling = 1')
+    ap.add_argument('--return-steps', type=int, default=1, help='[MODEL_CONFIG] return_steps (multi-step returns; 1: the one-step target)')
     ap.add_argument('--split', action='store_true', help='per-kernel split of the minibatch step (one more pass of --reps steps per kernel)')
     ap.add_argument('--stamps', action='store_true', help='phase stamps of workgroup 0 and the start / end of every workgroup (tsc_iql_debug_clock)')
     args = ap.parse_args()
@@ -42,7 +44,7 @@ def main():
     E, A = args.envs, scn.n_agent
     m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, int(scn.green_tab.shape[1]),
                dict(batch_size=20, buffer_size=1000, reward_norm=3000.0, target_update=args.target_update, double_q=int(args.double_q),
-                    prioritized_replay=int(args.per), dueling=int(args.dueling)),
+                    prioritized_replay=int(args.per), dueling=int(args.dueling), return_steps=args.return_steps),
                total_step=10 ** 6, seed=0, model_type='dqn')
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     mask = torch.zeros(A, scn.s_max, device='cuda')
@@ -74,15 +76,15 @@ def main():
     def grads():
         _lib.check(m._L.tsc_iql_compute_grads(m._h, 7, step[0]))
         step[0] += 1
-    out = {'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'prioritized_replay': m.prioritized_replay, 'dueling': m.dueling,
+    out = {'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'prioritized_replay': m.prioritized_replay, 'dueling': m.dueling, 'return_steps': m.return_steps,
            'replay_size': m.replay_size()[0], 'compute_grads_us': timed(grads, args.reps),
            'forward_us': timed(lambda: m.forward(obs, mode='explore'), args.reps),
            'minibatch_step_us': timed(lambda: m.minibatch_step(1e-4), args.reps)}
     # where a minibatch step's time goes: one kernel id at a time (an event pair inflates the launch behind it, include/tsc.h)
     kern = {}
-    two_launch = bool((m.target_update or m.prioritized_replay or m.dueling) and m.fused)
+    two_launch = bool((m.target_update or m.prioritized_replay or m.dueling or m.return_steps > 1) and m.fused)
     sample = ['iql_per_sample', 'iql_per_update', 'iql_per_add'] if m.prioritized_replay else ['iql_sample']
-    for name in (['iql_target'] * two_launch + ['iql_grad', 'iql_reduce'] + sample + ['iql_adam']) * args.split:
+    for name in (['iql_nstep'] * (m.return_steps > 1) + ['iql_target'] * two_launch + ['iql_grad', 'iql_reduce'] + sample + ['iql_adam']) * args.split:
         _lib.profile_select([name])
         _lib.profile(enable=True)
         _lib.profile(reset=True)

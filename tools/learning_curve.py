@@ -46,7 +46,7 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
         qcfg = dict(batch_size=20, buffer_size=1000, reward_norm=3000.0 if scenario == 'large_grid' else 1.0)
         if lr is not None:
             qcfg['lr_init'] = lr
-        qcfg.update(q_kw or {})         # opt-in keys of the Q-learners ([MODEL_CONFIG] prioritized_replay, per_alpha, per_beta, dueling, target_update, double_q)
+        qcfg.update(q_kw or {})         # opt-in keys of the Q-learners ([MODEL_CONFIG] prioritized_replay, per_alpha, per_beta, dueling, target_update, double_q, return_steps)
         model = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, n_env, scn.s_max, int(scn.green_tab.shape[1]), qcfg,
                        total_step=episodes * int(env.T), device=0, seed=seed, model_type='dqn' if agent == 'iqld' else 'lr')
     else:
@@ -96,6 +96,7 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
     # the update rule in force, defaults resolved (the A2C agents; IQL has none of these)
     run.algo_in_force = dict({k: model.cfg[k] for k in ('prioritized_replay', 'per_alpha', 'per_beta', 'per_eps')} if model.prioritized_replay else {},
                              **({'dueling': model.dueling} if model.dueling else {}),
+                             **({'return_steps': model.return_steps} if model.return_steps > 1 else {}),
                              **({'target_update': model.target_update, 'double_q': model.double_q} if model.target_update else {})) if is_q else dict(algo=model.algo, ppo_epochs=model.n_epoch, ppo_clip=model.ppo_clip, gae_lambda=model.gae_lambda)
     env.close(); model.close()
     return rows, ev
@@ -125,13 +126,14 @@ def main():
     ap.add_argument('--dueling', action='store_true', help='IQL-DNN: [MODEL_CONFIG] dueling = 1 (dueling head, Wang et al. 2016)')
     ap.add_argument('--target-update', type=int, default=None, help='the IQL agents: [MODEL_CONFIG] target_update (target network refreshed every N Adam steps)')
     ap.add_argument('--double-q', action='store_true', help='the IQL agents: [MODEL_CONFIG] double_q = 1 (needs --target-update)')
+    ap.add_argument('--return-steps', type=int, default=None, help='the IQL agents: [MODEL_CONFIG] return_steps (multi-step returns, 1 <= n <= 32)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     kw = {} if args.lane_change is None else {'lane_change': bool(args.lane_change)}
     kw.update({k: v for k, v in dict(objective=args.objective, pressure_measure=args.pressure_measure).items() if v is not None})
     q_kw = {k: v for k, v in dict(prioritized_replay=1 if args.prioritized_replay else None, per_alpha=args.per_alpha, per_beta=args.per_beta,
                                    dueling=1 if args.dueling else None, target_update=args.target_update,
-                                   double_q=1 if args.double_q else None).items() if v is not None}
+                                   double_q=1 if args.double_q else None, return_steps=args.return_steps).items() if v is not None}
     rows, ev = run(args.episodes, args.envs, args.scenario, args.agent, lr=args.lr, log=print, policy=args.policy, scn_kw=kw,
                    test_seeds=[int(x) for x in args.test_seeds.split(',')] if args.test_seeds else None,
                    algo=args.algo, ppo_epochs=args.ppo_epochs, ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, q_kw=q_kw)
