@@ -133,27 +133,28 @@ __global__ void iql_sample_fixed_kernel(int E, int A, long long size, unsigned l
 
 // minibatch rows of agent a: row = e * B + i  <-  transition idx[e][a][i] of instance e
 // (a caller-supplied index outside the filled part [0, size) of the ring is clamped into it: no out-of-bounds read)
-__global__ void iql_gather_kernel(int E, int A, int SMAX, int B, long long cap, int size, const int *idx, const float *r_obs,
-                                  const float *r_next, const int *r_act, const float *r_rew, const uint8_t *r_done, float *S,
-                                  float *S1, int *act, float *rew, uint8_t *done) {
+// S and the action are those of the sampled slot (idx), S1 and done those of the bootstrap slot (boot): idx itself on a one-step handle,
+// ns_slot of a return-steps one.  The row's reward is ret[row], its return G, or with ret == nullptr the sampled slot's stored reward.
+__global__ void iql_gather_kernel(int E, int A, int SMAX, int B, long long cap, int size, const int *idx, const int *boot, const float *ret,
+                                  const float *r_obs, const float *r_next, const int *r_act, const float *r_rew, const uint8_t *r_done,
+                                  float *S, float *S1, int *act, float *rew, uint8_t *done) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int q4 = SMAX >> 2;
     const long long R = (long long)E * B, tot = (long long)A * R * q4;
     if (i < tot) {
         const int c = (int)(i % q4);
         const long long row = (i / q4) % R, a = i / ((long long)q4 * R);
-        const long long e = row / B;
-        const int s = iql_ring_slot(idx[(e * A + a) * B + row % B], size);
-        const long long src = ((e * cap + s) * A + a) * SMAX + 4 * c;
-        reinterpret_cast<float4 *>(S)[i] = *reinterpret_cast<const float4 *>(r_obs + src);
-        reinterpret_cast<float4 *>(S1)[i] = *reinterpret_cast<const float4 *>(r_next + src);
+        const long long e = row / B, at = (e * A + a) * B + row % B;
+        const int s = iql_ring_slot(idx[at], size), j = iql_ring_slot(boot[at], size);
+        reinterpret_cast<float4 *>(S)[i] = *reinterpret_cast<const float4 *>(r_obs + ((e * cap + s) * A + a) * SMAX + 4 * c);
+        reinterpret_cast<float4 *>(S1)[i] = *reinterpret_cast<const float4 *>(r_next + ((e * cap + j) * A + a) * SMAX + 4 * c);
     }
     if (i < (long long)A * R) {
-        const long long row = i % R, a = i / R, e = row / B;
-        const int s = iql_ring_slot(idx[(e * A + a) * B + row % B], size);
+        const long long row = i % R, a = i / R, e = row / B, at = (e * A + a) * B + row % B;
+        const int s = iql_ring_slot(idx[at], size), j = iql_ring_slot(boot[at], size);
         act[i] = r_act[(e * cap + s) * A + a];
-        rew[i] = r_rew[(e * cap + s) * A + a];
-        done[i] = r_done[e * cap + s];
+        rew[i] = ret ? ret[i] : r_rew[(e * cap + s) * A + a];
+        done[i] = r_done[e * cap + j];
     }
 }
 
@@ -195,36 +196,51 @@ __device__ __forceinline__ void td_loss_sum(float l, int a, long long i, long lo
 }
 
 // tq = done ? r : r + gamma q1 ; loss = mean((q0 - tq)^2) ; dQ[k] = 2 (q0 - tq) / R at k = a   (agents/policies.py:317-318)
-// iql_td_kernel<true> (prioritized replay): the importance weight of the row in and |delta| out -- loss = mean(w (q0 - tq)^2),
-// dQ[k] = 2 w (q0 - tq) / R.  PER_ is empty or {true}, not a plain bool, so that w and td are parameters of that variant only, each in its
-// place: iql_td_kernel<> has the argument block, and with it the machine code, of a kernel without them (the device of
-// iql_fused_grad_kernel's `class... Y`, csrc/tsc_iql_fused.h, for the same reason).
-template <bool, class T> using TdPerArg = T;
-template <bool... PER_>
-__global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done,
-                              TdPerArg<PER_, const float *__restrict__>... w, long long R, int A, float gamma, float *dQ,
-                              TdPerArg<PER_, float *__restrict__>... td, double *stats) {
-    static_assert(sizeof...(PER_) <= 1, "iql_td_kernel<> or iql_td_kernel<true>");
-    constexpr bool PER = (PER_ || ...);
+// The options of a route, each a pointer that is nullptr when the option is off (uniform over the grid, so no wave diverges on them):
+struct TdOpts {
+    const float *w;         // prioritized replay: the row's importance weight -- loss = mean(w (q0 - tq)^2), dQ[k] = 2 w (q0 - tq) / R; else 1
+    const float *disc;      // multi-step returns: the row's own discount gamma^k (rew is then its return G); else the scalar gamma
+    float *td;              // |delta| out; else no store
+    const int *n_act;       // dueling head, Q the combined values: the DENSE dQ row the head's backward needs -- g (delta_ja - 1 / n_a) for
+                            // j < n_a, g at the value column 7, 0 between; else the sparse row.  (Dueling is always weighted: w = 1 on every
+                            // row when prioritized replay is off.)
+};
+__global__ void iql_td_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done, TdOpts o, long long R,
+                              int A, float gamma, float *dQ, double *stats) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     float l = 0.f;
     int a = 0;
     if (i < (long long)A * R) {
         a = (int)(i / R);
         const float r = rew[i];
-        const float tq = done[i] ? r : r + gamma * q1[i];
+        const float tq = done[i] ? r : r + (o.disc ? o.disc[i] : gamma) * q1[i];
         const int k0 = act[i];
         const float d = Q[i * kQ + k0] - tq;
-        [[maybe_unused]] float wi = 1.f;
-        if constexpr (PER) wi = (w, ...)[i];
-        const float g = PER ? 2.0f * d * wi / (float)R : 2.0f * d / (float)R;
-        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
-        float *v = k0 < 4 ? &lo.x : &hi.x;
-        v[k0 & 3] = g;
-        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = lo;
-        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = hi;
-        if constexpr (PER) (td, ...)[i] = fabsf(d);
-        l = PER ? d * d * wi / (float)R : d * d / (float)R;
+        float g;
+        if (o.w) {
+            const float wi = o.w[i];
+            g = 2.0f * d * wi / (float)R;
+            l = d * d * wi / (float)R;
+        } else {
+            g = 2.0f * d / (float)R;
+            l = d * d / (float)R;
+        }
+        float row[kQ];
+        if (o.n_act) {
+            const int na = o.n_act[a];
+            const float inv_na = 1.f / (float)na;
+#pragma unroll
+            for (int k = 0; k < kQ; ++k) {
+                const float off = k < na ? -inv_na : k == kQ - 1 ? 1.f : 0.f;
+                row[k] = g * (k == k0 ? 1.f + off : off);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kQ; ++k) row[k] = k == k0 ? g : 0.f;
+        }
+        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = make_float4(row[0], row[1], row[2], row[3]);
+        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = make_float4(row[4], row[5], row[6], row[7]);
+        if (o.td) o.td[i] = fabsf(d);
     }
     td_loss_sum(l, a, i, R, A, stats);
 }
@@ -241,38 +257,6 @@ __global__ void iql_duel_combine_kernel(float *Q, const int *n_act, long long ro
     for (int k = 0; k < na; ++k) s += q[k];
     const float base = q[kQ - 1] - s * (1.f / (float)na);
     for (int k = 0; k < na; ++k) q[k] = base + q[k];
-}
-
-// iql_td_kernel over the combined Q of a dueling handle: the same TD error, loss and |delta|, and the DENSE dQ row the head's backward
-// needs -- g (delta_ja - 1 / n_a) for j < n_a, g at the value column 7, 0 between.  Always weighted (w = 1 on every row when prioritized
-// replay is off), so there is one dueling form.
-__global__ void iql_td_duel_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done, const int *n_act,
-                                   const float *__restrict__ w, long long R, int A, float gamma, float *dQ, float *__restrict__ td,
-                                   double *stats) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    float l = 0.f;
-    int a = 0;
-    if (i < (long long)A * R) {
-        a = (int)(i / R);
-        const int na = n_act[a];
-        const float inv_na = 1.f / (float)na;
-        const float r = rew[i];
-        const float tq = done[i] ? r : r + gamma * q1[i];
-        const int k0 = act[i];
-        const float d = Q[i * kQ + k0] - tq, wi = w[i];
-        const float g = 2.0f * d * wi / (float)R;
-        float row[kQ];
-#pragma unroll
-        for (int k = 0; k < kQ; ++k) {
-            const float off = k < na ? -inv_na : k == kQ - 1 ? 1.f : 0.f;
-            row[k] = g * (k == k0 ? 1.f + off : off);
-        }
-        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = make_float4(row[0], row[1], row[2], row[3]);
-        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = make_float4(row[4], row[5], row[6], row[7]);
-        td[i] = fabsf(d);
-        l = d * d * wi / (float)R;
-    }
-    td_loss_sum(l, a, i, R, A, stats);
 }
 
 __global__ void iql_fill_kernel(float *x, long long n, float v) {
@@ -312,77 +296,6 @@ __global__ void iql_nstep_kernel(int E, int A, int B, long long cap, int size, i
     ns_ret[row] = (float)G;
     ns_disc[row] = (float)c;
     ns_k[row] = k;
-}
-
-// iql_gather_kernel of a return-steps handle: S and the action are those of the sampled slot (idx), S1 and done those of the bootstrap
-// slot (ns_slot, already inside [0, size)), and the row's reward is its return G.
-__global__ void iql_gather_nstep_kernel(int E, int A, int SMAX, int B, long long cap, int size, const int *idx, const int *ns_slot,
-                                        const float *ns_ret, const float *r_obs, const float *r_next, const int *r_act, const uint8_t *r_done,
-                                        float *S, float *S1, int *act, float *rew, uint8_t *done) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int q4 = SMAX >> 2;
-    const long long R = (long long)E * B, tot = (long long)A * R * q4;
-    if (i < tot) {
-        const int c = (int)(i % q4);
-        const long long row = (i / q4) % R, a = i / ((long long)q4 * R);
-        const long long e = row / B, at = (e * A + a) * B + row % B;
-        const int s = iql_ring_slot(idx[at], size), j = iql_ring_slot(ns_slot[at], size);
-        reinterpret_cast<float4 *>(S)[i] = *reinterpret_cast<const float4 *>(r_obs + ((e * cap + s) * A + a) * SMAX + 4 * c);
-        reinterpret_cast<float4 *>(S1)[i] = *reinterpret_cast<const float4 *>(r_next + ((e * cap + j) * A + a) * SMAX + 4 * c);
-    }
-    if (i < (long long)A * R) {
-        const long long row = i % R, a = i / R, e = row / B, at = (e * A + a) * B + row % B;
-        const int s = iql_ring_slot(idx[at], size), j = iql_ring_slot(ns_slot[at], size);
-        act[i] = r_act[(e * cap + s) * A + a];
-        rew[i] = ns_ret[i];
-        done[i] = r_done[e * cap + j];
-    }
-}
-
-// The TD kernels of a return-steps handle, one body: tq = done ? G : G + disc[i] q1 with the row's own discount gamma^k in place of the
-// scalar gamma.  FORM 0: iql_td_kernel<> (sparse dQ, no weight), 1: iql_td_kernel<true> (weights in, |delta| out), 2: iql_td_duel_kernel
-// (dense dQ over the combined values, always weighted).  w, td and n_act are read only by the forms that have them.
-template <int FORM>
-__global__ void iql_td_nstep_kernel(const float *Q, const float *q1, const int *act, const float *rew, const uint8_t *done, const int *n_act,
-                                    const float *__restrict__ w, const float *__restrict__ disc, long long R, int A, float *dQ,
-                                    float *__restrict__ td, double *stats) {
-    static_assert(FORM >= 0 && FORM <= 2, "0 plain, 1 prioritized replay, 2 dueling");
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    float l = 0.f;
-    int a = 0;
-    if (i < (long long)A * R) {
-        a = (int)(i / R);
-        const float r = rew[i];
-        const float tq = done[i] ? r : r + disc[i] * q1[i];
-        const int k0 = act[i];
-        const float d = Q[i * kQ + k0] - tq;
-        float g;
-        if constexpr (FORM == 0) {
-            g = 2.0f * d / (float)R;
-            l = d * d / (float)R;
-        } else {
-            const float wi = w[i];
-            g = 2.0f * d * wi / (float)R;
-            l = d * d * wi / (float)R;
-            td[i] = fabsf(d);
-        }
-        float row[kQ];
-        if constexpr (FORM == 2) {
-            const int na = n_act[a];
-            const float inv_na = 1.f / (float)na;
-#pragma unroll
-            for (int k = 0; k < kQ; ++k) {
-                const float off = k < na ? -inv_na : k == kQ - 1 ? 1.f : 0.f;
-                row[k] = g * (k == k0 ? 1.f + off : off);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kQ; ++k) row[k] = k == k0 ? g : 0.f;
-        }
-        reinterpret_cast<float4 *>(dQ + i * kQ)[0] = make_float4(row[0], row[1], row[2], row[3]);
-        reinterpret_cast<float4 *>(dQ + i * kQ)[1] = make_float4(row[4], row[5], row[6], row[7]);
-    }
-    td_loss_sum(l, a, i, R, A, stats);
 }
 
 // ---- prioritized replay (tsc_iql_set_per; proportional, Schaul et al. 2016) -----------------------------------------------------
@@ -1064,13 +977,10 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
         return 0;
     }
     const long long tot = A * R * (L.SMAX / 4);
-    if (nstep)
-        hipLaunchKernelGGL(iql_gather_nstep_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)E, (int)A, L.SMAX, h->B, h->cap,
-                           (int)size, h->idx, h->ns_slot, h->ns_ret, h->r_obs, h->r_next, h->r_act, h->r_done, h->S, h->S1, h->act, h->rew,
-                           h->done);
-    else
+    // multi-step returns: s' and done at the bootstrap slot, the row's return in place of its reward
     hipLaunchKernelGGL(iql_gather_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)E, (int)A, L.SMAX, h->B, h->cap,
-                       (int)size, h->idx, h->r_obs, h->r_next, h->r_act, h->r_rew, h->r_done, h->S, h->S1, h->act, h->rew, h->done);
+                       (int)size, h->idx, nstep ? h->ns_slot : h->idx, nstep ? h->ns_ret : nullptr, h->r_obs, h->r_next, h->r_act, h->r_rew,
+                       h->r_done, h->S, h->S1, h->act, h->rew, h->done);
     TSC_HIP(hipGetLastError());
     // Q(s') first (its activations are not needed afterwards), then Q(s) with the activations the backward pass reads
     // (armed: Q(s') comes from the frozen copy; Double DQN adds the online net's Q(s'), whose first maximum picks the target's value)
@@ -1085,26 +995,11 @@ static int iql_compute_grads(tsc_iql *h, uint64_t seed, uint64_t update_index, c
     }
     if (q_forward(h, h->params, h->S, R * L.SMAX, L.SMAX, R, h->X1, h->X2, h->Q)) return tsc::fail("gemm launch failed");
     if (duel) duel_combine(h, h->Q, R);
-    if (nstep) {        // the row's own discount gamma^k in place of gamma
-        const dim3 tg((unsigned)((A * R + 255) / 256));
-        if (duel)
-            hipLaunchKernelGGL(iql_td_nstep_kernel<2>, tg, dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, h->n_act, per ? h->w : h->w_one,
-                               h->ns_disc, R, (int)A, h->dQ, h->td, h->stats);
-        else if (per)
-            hipLaunchKernelGGL(iql_td_nstep_kernel<1>, tg, dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, h->n_act, h->w, h->ns_disc, R,
-                               (int)A, h->dQ, h->td, h->stats);
-        else
-            hipLaunchKernelGGL(iql_td_nstep_kernel<0>, tg, dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, h->n_act, nullptr, h->ns_disc, R,
-                               (int)A, h->dQ, nullptr, h->stats);
-    } else if (duel) {
-        hipLaunchKernelGGL(iql_td_duel_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
-                           h->n_act, per ? h->w : h->w_one, R, (int)A, (float)h->gamma, h->dQ, h->td, h->stats);
-    } else if (per)
-        hipLaunchKernelGGL(iql_td_kernel<true>, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done,
-                           h->w, R, (int)A, (float)h->gamma, h->dQ, h->td, h->stats);
-    else
-        hipLaunchKernelGGL(iql_td_kernel<>, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, R,
-                           (int)A, (float)h->gamma, h->dQ, h->stats);
+    // the route's options (TdOpts): weights, the rows' own discounts gamma^k, |delta| out, the dueling head's dense dQ row
+    const TdOpts td{per ? h->w : duel ? h->w_one : nullptr, nstep ? h->ns_disc : nullptr, per || duel ? h->td : nullptr,
+                    duel ? h->n_act : nullptr};
+    hipLaunchKernelGGL(iql_td_kernel, dim3((unsigned)((A * R + 255) / 256)), dim3(256), 0, st, h->Q, h->q1, h->act, h->rew, h->done, td, R,
+                       (int)A, (float)h->gamma, h->dQ, h->stats);
     TSC_HIP(hipGetLastError());
     float *g = h->grads;
     if (!L.dqn) {

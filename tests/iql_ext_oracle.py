@@ -1,6 +1,6 @@
 """Float64 restatement of the opt-in extensions of the Q-learners -- TEST INFRASTRUCTURE ONLY, never the code under test.  ExtOracleQ /
 ExtOracleIQL extend oracle.iql_oracle.OracleQ / OracleIQL (their nets, rings, clip + Adam), which stay the restatement of the reference,
-with three options that combine freely:
+with four options that combine freely:
 
 target network / Double DQN (include/tsc.h tsc_iql_set_target)
   * `target`: a second parameter dict theta-, a copy of the parameters when the oracle is made;
@@ -23,6 +23,15 @@ dueling head (tsc_iql_set_dueling; Wang et al. 2016), chosen by the parameters: 
     h = the hidden layers of oracle.iql_oracle.q_net;  A = h q_w + q_b  [n_a];  V = h v_w + v_b  [1]
     Q[j] = V + A_j - (1 / n_a) sum_{k < n_a} A_k
   wherever a Q value is used: forward, max_j Q(s'), Double DQN's a* and picked value, Q(s)[a], |delta|.
+
+multi-step returns (tsc_iql_set_return_steps; INTEGRATION.md "Multi-step returns"), `return_steps` = None | n >= 1
+  * nstep_window: the rule in plain Python, for one sampled slot of one ring;
+  * every minibatch row is assembled from its ring -- observation and action of the sampled slot s; the return G, the discount gamma^k,
+    the next observation and the done flag of the bootstrap slot j -- and y = done ? G : G + gamma^k Qsel(s').  return_steps = 1 runs the
+    window code too (k = 1 on every row); None is the stored tuple of slot s and the scalar gamma.  The draw, the importance weights and
+    the priority write-back (slot s) do not change;
+  * `last_slot` [E][A][B] and `last_G`, `last_disc`, `last_k`, `last_s` [A][E * B] keep the windows of the last minibatch_step (float64,
+    not rounded).  A window is `wrapped` when its bootstrap slot lies before its sampled slot: the walk crossed cap - 1 -> 0.
 
 The loss is mean(w (Q_theta(s)[a] - stop_grad(y))^2), its gradient torch autograd's.  `last_y`, `last_astar`, `last_q1_online`,
 `last_q1_target`, `last_delta` keep the targets, the picks, both nets' Q(s') and delta of the last loss_and_grads; `last_w`, `last_td`
@@ -70,12 +79,29 @@ def per_priority(abs_delta, eps, alpha):
     return np.float32((np.float64(abs_delta) + eps) ** alpha)
 
 
+def nstep_window(rews, dones, s, size, cap, cum, n, gamma):
+    """rews / dones: the ring's stored rewards (float32 values) and done flags by slot; s the sampled slot in [0, size); `size` filled
+    slots of `cap`, `cum` transitions added so far; horizon n >= 1.  -> (bootstrap slot j, G, gamma^k, k), G and gamma^k as Python
+    floats: float64, one rounding per product and per sum."""
+    assert 0 <= s < size <= cap and size == min(cum, cap) and n >= 1
+    w = (cum - 1) % cap
+    j, G, c, k = int(s), 0.0, 1.0, 0
+    while True:
+        G += c * float(rews[j])
+        c *= float(gamma)
+        k += 1
+        if dones[j] or j == w or k == n:
+            return j, G, c, k
+        j = (j + 1) % cap
+
+
 class ExtOracleQ(OracleQ):
     def __init__(self, params, n_s, n_w, gamma=0.99, max_grad_norm=40.0, target_update=0, double_q=False):
         super().__init__(params, n_s, n_w, gamma, max_grad_norm)
         assert target_update >= 0 and not (double_q and not target_update), 'Double DQN needs a target network'
         self.target_update, self.double_q = int(target_update), bool(double_q)
         self.weights = None                                   # per-row loss weights of the next loss; None: every row weighs 1
+        self.row_disc = None                                  # per-row discounts of the next loss; None: self.gamma on every row
         self.sync_target()
         self.last_y = self.last_astar = self.last_q1_online = self.last_q1_target = self.last_delta = None
 
@@ -92,8 +118,9 @@ class ExtOracleQ(OracleQ):
     def set_target(self, params):
         self.target = {k: torch.as_tensor(np.asarray(v), dtype=iql_oracle.DT).clone() for k, v in params.items()}
 
-    def targets(self, next_obs, dones, rs):
-        """-> (y, a* or None, online Q(s'), target Q(s')) as float64 tensors."""
+    def targets(self, next_obs, dones, rs, disc=None):
+        """disc: the rows' discounts, a tensor in row order, or None for self.gamma.
+        -> (y, a* or None, online Q(s'), target Q(s')) as float64 tensors."""
         S1 = torch.as_tensor(np.asarray(next_obs), dtype=iql_oracle.DT)
         with torch.no_grad():
             qt = self.net(self.target, S1)
@@ -105,7 +132,7 @@ class ExtOracleQ(OracleQ):
                 astar, q1 = None, qt.max(1).values
             r = torch.as_tensor(np.asarray(rs), dtype=iql_oracle.DT)
             d = torch.as_tensor(np.asarray(dones).astype(bool))
-            return torch.where(d, r, r + self.gamma * q1), astar, qo, qt
+            return torch.where(d, r, r + (self.gamma if disc is None else disc) * q1), astar, qo, qt
 
     def loss_and_grads(self, obs, acts, next_obs, dones, rs):
         if not self.target_update:
@@ -113,7 +140,11 @@ class ExtOracleQ(OracleQ):
         P = {k: v.clone().requires_grad_(True) for k, v in self.p.items()}
         S = torch.as_tensor(np.asarray(obs), dtype=iql_oracle.DT)
         q0 = self.net(P, S).gather(1, torch.as_tensor(np.asarray(acts), dtype=torch.long)[:, None])[:, 0]
-        y, astar, qo, qt = self.targets(next_obs, dones, rs)
+        disc = None
+        if self.row_disc is not None:
+            assert len(self.row_disc) == len(rs)
+            disc = torch.as_tensor(np.asarray(self.row_disc, np.float64), dtype=iql_oracle.DT)
+        y, astar, qo, qt = self.targets(next_obs, dones, rs, disc)
         self.last_y, self.last_q1_online, self.last_q1_target = y.numpy().copy(), qo.numpy().copy(), qt.numpy().copy()
         self.last_astar = None if astar is None else astar.numpy().astype(np.int32)
         w = torch.ones_like(y) if self.weights is None else torch.as_tensor(np.asarray(self.weights), dtype=iql_oracle.DT)
@@ -132,8 +163,11 @@ class ExtOracleQ(OracleQ):
 
 class ExtOracleIQL(OracleIQL):
     def __init__(self, agent_params, n_wave_ls, n_w_ls, n_a_ls, n_env, per=False, alpha=0.6, eps=0.01, target_update=0, double_q=False,
-                 gamma=0.99, max_grad_norm=40.0, **kw):
+                 return_steps=None, gamma=0.99, max_grad_norm=40.0, **kw):
         super().__init__(agent_params, n_wave_ls, n_w_ls, n_a_ls, n_env, gamma=gamma, max_grad_norm=max_grad_norm, **kw)
+        assert return_steps is None or int(return_steps) >= 1
+        self.return_steps, self.gamma = None if return_steps is None else int(return_steps), float(gamma)
+        self.last_slot = self.last_G = self.last_disc = self.last_k = self.last_s = None
         self.qs = [ExtOracleQ(p, nw, nt, gamma, max_grad_norm, target_update, double_q) for p, nw, nt in zip(agent_params, n_wave_ls, n_w_ls)]
         self.per, self.alpha, self.eps = bool(per), float(alpha), float(eps)
         self.prio = np.zeros((self.E, self.A, self.cap), np.float32)
@@ -162,6 +196,18 @@ class ExtOracleIQL(OracleIQL):
         if self.per:
             self.prio[:, :, slot] = self.qmax
 
+    def row(self, e, a, s, log):
+        """The minibatch row of slot s of ring (e, a) -> (obs, action, reward or return, next obs, done).  return_steps = None: the stored
+        tuple.  Else the row of the window from s, which is appended to log as (s, j, G, gamma^k, k)."""
+        buf = self.rings[e][a].buffer
+        if self.return_steps is None:
+            return buf[s]
+        ring = self.rings[e][a]
+        j, G, disc, k = nstep_window([t[2] for t in buf], [t[4] for t in buf], s, ring.size, self.cap, ring.cum_size, self.return_steps,
+                                     self.gamma)
+        log.append((s, j, G, disc, k))
+        return buf[s][0], buf[s][1], G, buf[j][3], buf[j][4]
+
     def minibatch_step(self, lr, beta=1.0, idx_given=None):
         """-> (per-agent loss, per-agent grad norm, grads list[A] of dict); applies Adam and, with per, the priority write-back.
         idx_given [E, A, B]: the caller's draw, clamped into [0, size) as include/tsc.h documents for the device (with per the weights
@@ -170,9 +216,9 @@ class ExtOracleIQL(OracleIQL):
         size, B = self.rings[0][0].size, self.B
         idx = np.zeros((self.E, self.A, B), np.int32)
         self.last_w, self.last_td = np.ones((self.A, self.E * B)), np.zeros((self.A, self.E * B))
-        losses, norms, grads = [], [], []
+        losses, norms, grads, logs = [], [], [], []
         for a, q in enumerate(self.qs):
-            obs, acts, nobs, rs, dones = [], [], [], [], []
+            obs, acts, nobs, rs, dones, log = [], [], [], [], [], []
             for e in range(self.E):
                 uniform = lambda i, p=e * self.A + a: sample_uniform(self.replay_seed, self.update_step, p * B + i)
                 if idx_given is not None:
@@ -185,13 +231,16 @@ class ExtOracleIQL(OracleIQL):
                 if self.per:
                     self.last_w[a, e * B:(e + 1) * B] = per_weights(self.prio[e, a], size, ids, beta)
                 for s in ids:
-                    ob, ac, r, nob, d = self.rings[e][a].buffer[s]
+                    ob, ac, r, nob, d = self.row(e, a, s, log)
                     obs.append(ob); acts.append(ac); rs.append(r); nobs.append(nob); dones.append(d)
+            logs.append(log)
             q.weights = self.last_w[a] if self.per else None
+            q.row_disc = None if self.return_steps is None else [w[3] for w in log]
             loss, g = q.loss_and_grads(obs, acts, nobs, dones, rs)
             self.last_td[a] = np.abs(q.last_delta)
             grads.append({k: v.numpy().copy() for k, v in g.items()})
             _, norm = q.backward(obs, acts, nobs, dones, rs, lr)
+            q.row_disc = None
             losses.append(loss); norms.append(norm)
             if self.per:
                 for e in range(self.E):
@@ -201,4 +250,17 @@ class ExtOracleIQL(OracleIQL):
                         self.qmax[e, a] = max(self.qmax[e, a], v)
         self.update_step += 1
         self.last_idx = idx
+        if self.return_steps is not None:
+            win = np.array(logs, np.float64)                          # [A][R][5]
+            self.last_s, self.last_k = win[:, :, 0].astype(np.int64), win[:, :, 4].astype(np.int32)
+            self.last_G, self.last_disc = win[:, :, 2].copy(), win[:, :, 3].copy()
+            self.last_slot = win[:, :, 1].astype(np.int32).reshape(self.A, self.E, self.B).transpose(1, 0, 2).copy()
         return np.array(losses), np.array(norms), grads
+
+    def categories(self):
+        """-> dict of bool [A][R] over the rows of the last minibatch_step: full horizon (k = n), cut by done, cut by the newest slot,
+        wrapped window.  (A row can be in several: the done slot can be the newest one, a full window can end on either.)"""
+        w = (self.rings[0][0].cum_size - 1) % self.cap
+        j = self.last_slot.transpose(1, 0, 2).reshape(self.A, -1)
+        done_j = np.array([[self.rings[r // self.B][a].buffer[j[a, r]][4] for r in range(j.shape[1])] for a in range(self.A)], bool)
+        return dict(full=self.last_k == self.return_steps, done=done_j, newest=(j == w) & ~done_j, wrapped=j < self.last_s)

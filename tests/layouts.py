@@ -17,7 +17,7 @@ s_max <= 64 gate of the plan; the three that also depend on an LDS budget (obs64
 are the values an MI355X handle reported, recorded here and asserted from then on (RECORDED).
 
 The rollouts of tests/test_layouts_gpu.py are redrawn on the host by forward_inputs / fill_host / iql_transitions below: the same
-RandomState seeds in the same order of draws as tests/test_model_gpu.py::_fill and tests/test_iql_gpu.py, so that
+RandomState seeds in the same order of draws as tests/test_model_gpu.py::_fill and tests/iql_harness.py::replay_vs_oracle, so that
 tests/test_layouts_host.py states conditions about the very samples the GPU tests compare."""
 import contextlib
 
@@ -166,7 +166,7 @@ def fill_host(lay, oracles, E, T, rng, reward_norm, p_done=0.1):
 
 
 def iql_transitions(lay, E, cap, rng, reward_norm):
-    """The transitions of tests/test_iql_gpu.py::_replay_vs_oracle (E < 100): -> list of (obs, act, rew, next obs, done)."""
+    """The transitions of tests/iql_harness.py::replay_vs_oracle (E < 100): -> list of (obs, act, rew, next obs, done)."""
     out, obs = [], rand_obs(lay, E, rng)
     for t in range(cap + 7):
         nobs = rand_obs(lay, E, rng)

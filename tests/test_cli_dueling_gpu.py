@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_iql_target_gpu import INI
+from tests.iql_harness import INI
 
 pytestmark = pytest.mark.gpu
 

@@ -6,14 +6,14 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_iql_target_gpu import INI
+from tests.iql_harness import INI
 
 pytestmark = pytest.mark.gpu
 
 
 def test_train_with_return_steps_then_load_without(tmp_path):
     from deeprl_signal_control_amd import main as cli
-    from tests.test_iql_target_gpu import _model
+    from tests.iql_harness import model
     ini = INI.replace('target_update = 5\n', 'target_update = 5\nreturn_steps = 3\n')
     assert all(line in ini for line in ('return_steps = 3', 'double_q = 1', 'agent = iqld', 'scenario = small_grid'))
     cfg = tmp_path / 'config_iqld.ini'
@@ -28,7 +28,7 @@ def test_train_with_return_steps_then_load_without(tmp_path):
     assert int(z['counters'][0]) >= 2 and int(z['counters'][2]) >= 2                                      # Adam steps, minibatch draws
     # a model without the key (and one with another horizon) loads the file; `evaluate` runs on it
     for kw in ({}, dict(return_steps=5)):
-        _, m = _model('small_grid', 'iqld', 'dqn', 2, seed=9, target_update=5, double_q=1, **kw)
+        _, m = model('small_grid', 'iqld', 'dqn', 2, seed=9, target_update=5, double_q=1, **kw)
         assert m.return_steps == kw.get('return_steps', 1)
         assert m.load(base + '/iqld/model')
         np.testing.assert_array_equal(m.get_flat(), z['params'])

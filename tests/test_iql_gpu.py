@@ -12,195 +12,18 @@ import numpy as np
 import pytest
 import torch
 
+from tests import iql_harness as H
+
 pytestmark = pytest.mark.gpu
-
-
-def _make(scenario, agent, model_type, E, seed=0, **cfg):
-    """scenario: the name of a built-in scenario, or a layout object (tests/layouts.py: the attributes read below and nothing else)."""
-    from deeprl_signal_control_amd.iql import VecIQL
-    from deeprl_signal_control_amd.scenario import build_scenario
-    from oracle.iql_oracle import OracleIQL
-    scn = build_scenario(scenario, agent) if isinstance(scenario, str) else scenario
-    mc = dict(batch_size=20, buffer_size=1000, reward_norm=3000.0 if scenario == 'large_grid' else 1.0 if scenario == 'real_net' else 100.0)
-    mc.update(cfg)
-    a_max = int(scn.green_tab.shape[1]) if hasattr(scn, 'green_tab') else scn.a_max
-    m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, a_max, mc, total_step=10000,
-               seed=seed, model_type=model_type)
-    o = OracleIQL(m.get_agent_params(), m.n_wave_ls, m.n_w_ls, m.n_a_ls, E, batch_size=m.n_step,
-                  buffer_size=int(m.cfg['buffer_size']), gamma=m.cfg['gamma'], reward_norm=m.cfg['reward_norm'],
-                  reward_clip=m.cfg['reward_clip'], max_grad_norm=m.cfg['max_grad_norm'], replay_seed=m.replay_seed)
-    return scn, m, o
-
-
-def _rand_obs(scn, E, rng):
-    obs = np.zeros((E, scn.n_agent, scn.s_max), np.float32)
-    for a, n in enumerate(scn.n_s_ls):
-        obs[:, a, :n] = rng.rand(E, n).astype(np.float32) * 2
-    return obs
-
-
-def _forward_and_act(scn, m, o, E, rng, steps=3, qtol=2e-5):
-    """Q values, the greedy action and the epsilon-greedy action on the documented uniforms against the oracle.  qtol: bound on |dQ|,
-    or a function of an agent's oracle values (layouts whose values leave the reference's range, tests/test_layouts_gpu.py)."""
-    from oracle.iql_oracle import act_epsilon_greedy
-    from oracle.nets_oracle import sample_uniform
-    tol = qtol if callable(qtol) else (lambda oq: qtol)
-    A = scn.n_agent
-    for t in range(steps):
-        obs = _rand_obs(scn, E, rng)
-        act, q = m.forward(torch.from_numpy(obs).cuda())                       # mode 'act': argmax
-        act, q = act.cpu().numpy(), q.cpu().numpy()
-        oq = o.forward(obs)
-        for a in range(A):
-            np.testing.assert_allclose(q[:, a, :scn.n_a_ls[a]], oq[a], atol=tol(oq[a]))
-            assert np.all(q[:, a, scn.n_a_ls[a]:] == 0)
-            np.testing.assert_array_equal(act[:, a], np.argmax(q[:, a, :scn.n_a_ls[a]], 1))
-        eps_before = m.eps_scheduler.n
-        act, q = m.forward(torch.from_numpy(obs).cuda(), mode='explore')
-        eps = max(m.cfg['epsilon_min'], m.cfg['epsilon_init'] * (1 - (eps_before + 1) / (10000 * m.cfg['epsilon_ratio'])))
-        act, q = act.cpu().numpy(), q.cpu().numpy()
-        for e in range(E):
-            for a in range(A):
-                u0 = sample_uniform(m.sample_seed, m.act_step - 1, 2 * (e * A + a))
-                u1 = sample_uniform(m.sample_seed, m.act_step - 1, 2 * (e * A + a) + 1)
-                assert act[e, a] == act_epsilon_greedy(q[e, a, :scn.n_a_ls[a]], eps, u0, u1)
 
 
 @pytest.mark.parametrize('scenario,agent,model_type,E', [('large_grid', 'iqld', 'dqn', 70), ('large_grid', 'iqll', 'lr', 33),
                                                          ('real_net', 'iqld', 'dqn', 40), ('real_net', 'iqll', 'lr', 5)])
 def test_forward_and_epsilon_greedy(scenario, agent, model_type, E):
-    scn, m, o = _make(scenario, agent, model_type, E, seed=3)
+    scn, m, o = H.make(scenario, agent, model_type, E, seed=3)
     assert scn.n_f_ls == [0] * scn.n_agent and (scenario == 'real_net') == (max(scn.n_w_ls) == 0)
-    _forward_and_act(scn, m, o, E, np.random.RandomState(E))
+    H.forward_and_act(scn, m, o, E, np.random.RandomState(E))
     m.close()
-
-
-def _kinks(o, obs_rows, a, thr=1e-6):
-    """(layer-1 columns, any layer-2 unit) of agent a whose pre-activation is within thr of zero on the minibatch."""
-    from oracle.iql_oracle import DT
-    p = o.qs[a].p
-    if 'fcw_w' not in p:
-        return None, False
-    S = torch.as_tensor(np.asarray(obs_rows), dtype=DT)
-    nw = o.nw[a]
-    z = [S[:, :nw] @ p['fcw_w'] + p['fcw_b']]
-    if o.nt[a]:
-        z.append(S[:, nw:] @ p['fct_w'] + p['fct_b'])
-    z1 = torch.cat(z, 1)
-    z2 = torch.relu(z1) @ p['fc0_w'] + p['fc0_b']
-    return (z1.abs() < thr).any(0).numpy(), bool((z2.abs() < thr).any())
-
-
-def _rand_obs_off_the_kinks(scn, E, rng, o, thr=5e-6):
-    """_rand_obs, with every row re-drawn until no hidden unit of its agent's net (the oracle's CURRENT parameters) has a
-    pre-activation within thr of zero: on such rows the float64 gradient is the gradient, not one of two subgradients, and a
-    20 480-row minibatch (which meets ~ 4 such units per agent otherwise) can be compared tensor by tensor without exceptions."""
-    from oracle.iql_oracle import DT
-    obs = _rand_obs(scn, E, rng)
-    for a, n in enumerate(scn.n_s_ls):
-        p, nw = o.qs[a].p, o.nw[a]
-        if 'fcw_w' not in p:
-            continue
-        rows = np.arange(E)
-        while rows.size:
-            S = torch.as_tensor(obs[rows, a, :n].astype(np.float64), dtype=DT)
-            z = [S[:, :nw] @ p['fcw_w'] + p['fcw_b']]
-            if o.nt[a]:
-                z.append(S[:, nw:] @ p['fct_w'] + p['fct_b'])
-            z1 = torch.cat(z, 1)
-            z2 = torch.relu(z1) @ p['fc0_w'] + p['fc0_b']
-            bad = ((z1.abs() < thr).any(1) | (z2.abs() < thr).any(1)).numpy()
-            rows = rows[bad]
-            if rows.size:
-                obs[rows, a, :n] = rng.rand(rows.size, n).astype(np.float32) * 2
-    return obs
-
-
-def _replay_vs_oracle(scn, m, o, E, cap, rng, steps=None):
-    """Fill the rings past their capacity, then minibatch steps (three, two at E >= 100, or `steps`): replay indices exact, TD loss /
-    gradient / clip norm / Adam-updated parameters against the oracle."""
-    from deeprl_signal_control_amd import _lib
-    A, B = scn.n_agent, m.n_step
-    n_add = cap + (7 if E < 100 else 3) if cap < 100 else 45
-    # big batches: observations off the ReLU kinks of the initial nets, so that the first step is compared without exceptions
-    draw = (lambda: _rand_obs_off_the_kinks(scn, E, rng, o)) if E >= 100 else (lambda: _rand_obs(scn, E, rng))
-    obs = draw()
-    assert m.backward() is None                                              # fewer than a batch: no update (models.py:321-322)
-    for t in range(n_add):
-        nobs = draw()
-        act = np.stack([rng.randint(0, n, E) for n in scn.n_a_ls], 1).astype(np.int32)
-        rew = -rng.rand(E, A) * 3.0 * m.cfg['reward_norm']
-        done = (rng.rand(E) < 0.1).astype(np.uint8)
-        m.add_transition(torch.from_numpy(obs).cuda(), torch.from_numpy(act).cuda(), torch.from_numpy(rew).cuda(),
-                         torch.from_numpy(nobs).cuda(), torch.from_numpy(done).cuda())
-        o.add_transition(obs, act, rew, nobs, done)
-        obs = nobs
-    assert m.replay_size() == (min(cap, n_add), n_add)
-    lr = 1e-3
-    kinked = set()          # agents with a hidden unit on a ReLU kink in some minibatch so far (enters Adam's moments)
-    for step in range((3 if E < 100 else 2) if steps is None else steps):
-        before = m.get_flat().reshape(A, -1).copy()
-        _lib.check(m._L.tsc_iql_compute_grads(m._h, m.replay_seed, m.update_step))
-        m.update_step += 1
-        idx = np.zeros((E, A, B), np.int32)
-        _lib.check(m._L.tsc_iql_debug_batch(m._h, idx.ctypes.data_as(C.c_void_p)))
-        g = m.layout.unpack(m.grad_tensor().cpu().numpy())
-        flat_g = m.grad_tensor().cpu().numpy().reshape(A, -1).copy()
-        stats = np.zeros((A, 2))
-        _lib.check(m._L.tsc_iql_apply_grads(m._h, lr, 1.0, stats.ctypes.data_as(C.c_void_p)))
-        obefore = m.layout.pack(o.agent_params()).reshape(A, -1)
-        rows_before = [[o.rings[e][a].buffer for e in range(E)] for a in range(A)]
-        params_before = [{k: v.clone() for k, v in q.p.items()} for q in o.qs]
-        losses, norms, og = o.minibatch_step(lr)
-        np.testing.assert_array_equal(idx, o.last_idx)
-        assert all(len(set(idx[e, a])) == B and idx[e, a].max() < min(cap, n_add) for e in range(E) for a in range(A))
-        tol = 2e-5
-        for a in range(A):
-            # ReLU kinks of this minibatch under the parameters the gradient was taken at
-            saved = o.qs[a].p
-            o.qs[a].p = params_before[a]
-            rows = [rows_before[a][e][s][0] for e in range(E) for s in idx[e, a]]
-            cols, deep = _kinks(o, rows, a)
-            o.qs[a].p = saved
-            if E >= 100 and step == 0:
-                assert not deep and (cols is None or not cols.any()), 'agent %d: a row of the first minibatch sits on a ReLU kink' % a
-            if deep or (cols is not None and cols.any()):
-                kinked.add(a)
-            for k, ref in og[a].items():
-                if deep and k not in ('q_w', 'q_b'):
-                    continue
-                got, scale = g[a][k], max(np.abs(ref).max(), 1e-9)
-                err = np.abs(got - ref)
-                if cols is not None and k.startswith(('fcw', 'fct')) and cols.any():
-                    sel = cols[:m.layout.n_fc0] if k.startswith('fcw') else cols[m.layout.n_fc0:]
-                    err = err[..., ~sel] if err.ndim == 2 else err[~sel]
-                assert err.size == 0 or err.max() <= tol * scale, 'step %d agent %d %s: %.2e' % (step, a, k, err.max() / scale)
-        np.testing.assert_allclose(stats[:, 0], losses, rtol=1e-4, atol=1e-9)
-        np.testing.assert_allclose(stats[:, 1], norms, rtol=1e-4)
-        # Adam: this step's parameter change.  Adam's first steps move a weight by ~lr * sign-like(m / sqrt(v)): entries
-        # whose gradient is well above the gradient tolerance must move alike; entries whose gradient is itself
-        # rounding noise may move either way, by at most ~lr
-        after = m.get_flat().reshape(A, -1)
-        oflat = m.layout.pack(o.agent_params()).reshape(A, -1)
-        d_hip, d_orc = after - before, oflat - obefore
-        real = np.abs(flat_g) > 1e-2 * np.abs(flat_g).max(1, keepdims=True)
-        real[sorted(kinked)] = False
-        assert step > 0 or real.any()
-        if real.any():
-            assert np.abs(d_hip - d_orc)[real].max() <= 2e-6, np.abs(d_hip - d_orc)[real].max()
-        assert np.abs(d_hip).max() <= 1.01 * lr and np.abs(d_hip - d_orc).max() <= 2.02 * lr
-        if step == 0:
-            assert np.array_equal(after == before, flat_g == 0)                  # structural zeros never move
-        # every step is checked from the SAME state: hand the oracle the device's parameters and Adam moments (entries
-        # whose gradient is rounding noise legitimately step the other way, and would otherwise compound)
-        hm, hv, ht = m.get_opt_state()
-        assert ht == step + 1 == o.qs[0].t
-        for a, (pp, mm, vv) in enumerate(zip(m.get_agent_params(), m.layout.unpack(hm), m.layout.unpack(hv))):
-            for k in o.qs[a].p:
-                o.qs[a].p[k] = torch.as_tensor(pp[k].astype(np.float64))
-                o.qs[a].m[k] = torch.as_tensor(mm[k].astype(np.float64))
-                o.qs[a].v[k] = torch.as_tensor(vv[k].astype(np.float64))
-        kinked.clear()
 
 
 # fused: '1' = the one-kernel DeepQPolicy learner (csrc/tsc_iql_fused.h, what bench.py --config q1 times), '0' = the grouped-GEMM
@@ -217,9 +40,9 @@ def test_replay_minibatch_gradient_and_adam(scenario, agent, model_type, E, cap,
     """Fill the rings past their capacity, then three minibatch steps: replay indices (Floyd on the documented
     uniform) exact, TD loss / gradient / clip norm / Adam-updated parameters against the oracle."""
     monkeypatch.setenv('TSC_IQL_FUSED', fused)
-    scn, m, o = _make(scenario, agent, model_type, E, seed=5, buffer_size=cap)
+    scn, m, o = H.make(scenario, agent, model_type, E, seed=5, buffer_size=cap)
     assert m.fused == (fused == '1')
-    _replay_vs_oracle(scn, m, o, E, cap, np.random.RandomState(cap + E))
+    H.replay_vs_oracle(scn, m, o, E, cap, np.random.RandomState(cap + E))
     m.close()
 
 
@@ -275,12 +98,12 @@ def test_every_instance_draws_its_own_minibatch():
     draw different minibatches (independent samples, as E independent reference learners would)."""
     from deeprl_signal_control_amd import _lib
     E = 4
-    scn, full, _ = _make('large_grid', 'iqld', 'dqn', E, seed=2, buffer_size=40)
+    scn, full, _ = H.make('large_grid', 'iqld', 'dqn', E, seed=2, buffer_size=40)
     rng = np.random.RandomState(0)
     A = scn.n_agent
-    obs = _rand_obs(scn, 1, rng)
+    obs = H.rand_obs(scn, 1, rng)
     for t in range(30):
-        nobs = _rand_obs(scn, 1, rng)
+        nobs = H.rand_obs(scn, 1, rng)
         act = rng.randint(0, 5, (1, A)).astype(np.int32)
         rew = -rng.rand(1, A) * 6000.0
         full.add_transition(torch.from_numpy(np.repeat(obs, E, 0)).cuda(), torch.from_numpy(np.repeat(act, E, 0)).cuda(),
@@ -300,13 +123,13 @@ def test_other_batch_sizes_take_the_generic_draw_and_the_same_kernels():
     """batch_size != 20 (the reference's value, which has its own register-resident Floyd draw): the generic sampler and the fused
     learner at 8 rows per instance -- indices exact, gradients against the oracle."""
     from deeprl_signal_control_amd import _lib
-    scn, m, o = _make('large_grid', 'iqld', 'dqn', 9, seed=4, buffer_size=16, batch_size=8)
+    scn, m, o = H.make('large_grid', 'iqld', 'dqn', 9, seed=4, buffer_size=16, batch_size=8)
     assert m.fused and m.n_step == 8
     A, B, E = scn.n_agent, 8, 9
     rng = np.random.RandomState(1)
-    obs = _rand_obs(scn, E, rng)
+    obs = H.rand_obs(scn, E, rng)
     for t in range(19):
-        nobs = _rand_obs(scn, E, rng)
+        nobs = H.rand_obs(scn, E, rng)
         act = np.stack([rng.randint(0, n, E) for n in scn.n_a_ls], 1).astype(np.int32)
         rew = -rng.rand(E, A) * 3.0 * m.cfg['reward_norm']
         done = (rng.rand(E) < 0.1).astype(np.uint8)

@@ -1,5 +1,5 @@
 """Host-side checks of the opt-in multi-step returns of the Q-learners ([MODEL_CONFIG] return_steps; deeprl_signal_control_amd/iql.py
-return_steps_config) and self-checks of their float64 oracle (tests/iql_nstep_oracle.py) -- no GPU."""
+return_steps_config) and self-checks of their float64 oracle (tests/iql_ext_oracle.py, return_steps) -- no GPU."""
 import configparser
 
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 
 from deeprl_signal_control_amd.agents import coerce_config
 from deeprl_signal_control_amd.iql import IQL_DEFAULTS, QParamLayout, init_agent_params
-from tests.iql_nstep_oracle import nstep_window
+from tests.iql_ext_oracle import ExtOracleIQL, nstep_window
 
 GAMMA = 0.9
 
@@ -108,9 +108,7 @@ def test_every_slot_and_horizon_against_the_unroll():
 
 
 def _pair(n, **kw):
-    """ExtOracleIQL and NStepOracleIQL(return_steps = n) over the same parameters and transitions: the smallest layout of tests/layouts.py."""
-    from tests.iql_ext_oracle import ExtOracleIQL
-    from tests.iql_nstep_oracle import NStepOracleIQL
+    """ExtOracleIQL() and ExtOracleIQL(return_steps = n) over the same parameters and transitions: the smallest layout of tests/layouts.py."""
     from tests.layouts import IQL_LAYOUTS, iql_transitions
     spec = IQL_LAYOUTS['lr_tiny']
     lay = spec['layout']
@@ -119,7 +117,7 @@ def _pair(n, **kw):
     E, cap = 2, 24
     common = dict(batch_size=20, buffer_size=cap, gamma=0.99, reward_norm=100.0, reward_clip=2.0, replay_seed=11, **kw)
     ext = ExtOracleIQL(params, lay.n_wave_ls, lay.n_w_ls, lay.n_a_ls, E, **common)
-    nst = NStepOracleIQL(params, lay.n_wave_ls, lay.n_w_ls, lay.n_a_ls, E, return_steps=n, **common)
+    nst = ExtOracleIQL(params, lay.n_wave_ls, lay.n_w_ls, lay.n_a_ls, E, return_steps=n, **common)
     for tr in iql_transitions(lay, E, cap, np.random.RandomState(9), 100.0):
         ext.add_transition(*tr)
         nst.add_transition(*tr)

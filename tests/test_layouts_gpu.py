@@ -10,7 +10,7 @@ Batches: A2C (E, T) = (5, 6) and (37, 7), N = 30 and 259 rows, ragged in every r
 tests/test_update_staging_gpu.py's); IQL E = 5 with ring capacity 30, 100 rows = one 64-row chunk and a partial one.
 
 Tolerances are the ones the reused modules state: pi |d| <= 2e-5; gradients 2e-5 max|g| per tensor, 2e-4 in the second round;
-ReLU-kink columns excepted as _grad_err / _kinks do; parameters 3e-5.  v and Q: |d| <= 2e-5 on the layouts inside the reference's
+ReLU-kink columns excepted as _grad_err / iql_harness.kinks do; parameters 3e-5.  v and Q: |d| <= 2e-5 on the layouts inside the reference's
 input ranges; 2e-5 max(1, max|oracle value|) on the `wide` ones (up to 68 inputs in [0, 2): obs64, obs68, q_obs52, lr_wide), whose
 values leave the reference's range.  tests/test_layouts_host.py measures the float32 restatement of the oracle against float64 on
 these very inputs: |dv| <= 8.2e-7 (max|v| 2.35) and |dQ| <= 8.5e-7 (max|Q| 4.28) over all layouts, far inside either bound, and on
@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import iql_harness as H
 from tests import layouts as LY
 from tests.test_layouts_host import value_bound
 
@@ -122,13 +123,12 @@ def test_a2c_refuses_a_hidden_width_that_is_no_multiple_of_4():
 
 # ---- IQL --------------------------------------------------------------------------------------------------------------------------
 def _iql(name, monkeypatch, fused_knob=None):
-    from tests.test_iql_gpu import _make
     spec = LY.IQL_LAYOUTS[name]
     if fused_knob is not None:
         monkeypatch.setenv('TSC_IQL_FUSED', fused_knob)
     else:
         monkeypatch.delenv('TSC_IQL_FUSED', raising=False)
-    lay, m, o = _make(spec['layout'], 'iql', spec['model_type'], LY.IQL_E, seed=LY.SEEDS[name], buffer_size=LY.IQL_CAP,
+    lay, m, o = H.make(spec['layout'], 'iql', spec['model_type'], LY.IQL_E, seed=LY.SEEDS[name], buffer_size=LY.IQL_CAP,
                       reward_norm=LY.IQL_REWARD_NORM, **spec['cfg'])
     want = spec['fused'] and fused_knob != '0'
     assert m.fused == want, '%s: fused = %r, the layout table says %r' % (name, m.fused, want)
@@ -137,39 +137,35 @@ def _iql(name, monkeypatch, fused_knob=None):
 
 @pytest.mark.parametrize('name', list(LY.IQL_LAYOUTS))
 def test_iql_forward_and_epsilon_greedy(name, monkeypatch):
-    from tests.test_iql_gpu import _forward_and_act
     spec, lay, m, o = _iql(name, monkeypatch)
-    _forward_and_act(lay, m, o, LY.IQL_E, np.random.RandomState(LY.data_seed(name, LY.IQL_E)), qtol=value_bound if spec['wide'] else 2e-5)
+    H.forward_and_act(lay, m, o, LY.IQL_E, np.random.RandomState(LY.data_seed(name, LY.IQL_E)), qtol=value_bound if spec['wide'] else 2e-5)
     m.close()
 
 
 @pytest.mark.parametrize('name', list(LY.IQL_LAYOUTS))
 def test_iql_replay_gradient_and_adam(name, monkeypatch):
     """The body of test_replay_minibatch_gradient_and_adam with two minibatch steps."""
-    from tests.test_iql_gpu import _replay_vs_oracle
     spec, lay, m, o = _iql(name, monkeypatch)
-    _replay_vs_oracle(lay, m, o, LY.IQL_E, LY.IQL_CAP, np.random.RandomState(LY.data_seed(name, LY.IQL_E, LY.IQL_CAP)), steps=LY.IQL_STEPS)
+    H.replay_vs_oracle(lay, m, o, LY.IQL_E, LY.IQL_CAP, np.random.RandomState(LY.data_seed(name, LY.IQL_E, LY.IQL_CAP)), steps=LY.IQL_STEPS)
     m.close()
 
 
 def _duel(name, fused_knob, monkeypatch, **cfg):
     """The dueling head on the layout's agents with n_a <= 7 (column 7 of the head is V; tsc_iql_set_dueling refuses n_a = 8)."""
-    from tests.test_iql_dueling_gpu import _duel_model, _oracle
     spec = LY.IQL_LAYOUTS[name]
     lay = spec['layout'].only(lambda na: na <= 7)
     assert max(lay.n_a_ls) == 7 and lay.n_agent >= 4
     monkeypatch.setenv('TSC_IQL_FUSED', fused_knob)
-    _, m = _duel_model(lay, LY.IQL_E, LY.IQL_CAP, seed=LY.SEEDS[name], **spec['cfg'], **cfg)
+    _, m = H.duel_model(lay, LY.IQL_E, LY.IQL_CAP, seed=LY.SEEDS[name], **spec['cfg'], **cfg)
     assert m.fused == (fused_knob == '1')
-    return lay, m, _oracle(m)
+    return lay, m, H.oracle_for(m)
 
 
 @pytest.mark.parametrize('fused_knob', ['1', '0'])
 @pytest.mark.parametrize('name', ['q160_edge', 'q128_edge'])
 def test_iql_dueling_forward(name, fused_knob, monkeypatch):
-    from tests.test_iql_dueling_gpu import _forward_vs_oracle
     lay, m, o = _duel(name, fused_knob, monkeypatch)
-    _forward_vs_oracle(lay, m, o, LY.IQL_E, np.random.RandomState(LY.data_seed(name, LY.IQL_E)))
+    H.duel_forward_vs_oracle(lay, m, o, LY.IQL_E, np.random.RandomState(LY.data_seed(name, LY.IQL_E)))
     m.close()
 
 
@@ -178,11 +174,10 @@ def test_iql_dueling_forward(name, fused_knob, monkeypatch):
 @pytest.mark.parametrize('name', ['q160_edge', 'q128_edge'])
 def test_iql_dueling_targets_and_gradient(name, fused_knob, target_update, double_q, monkeypatch):
     """Targets and gradient of the dueling head at its last legal action count: the columns n_a <= j < 7 of dWq | dbq are exactly zero
-    (_dead_columns_are_zero), and at n_a = 7 that range is empty and column 7 carries dV right behind the seventh action's column."""
-    from tests.test_iql_dueling_gpu import _targets_and_gradient_vs_oracle
+    (dead_columns_are_zero), and at n_a = 7 that range is empty and column 7 carries dV right behind the seventh action's column."""
     lay, m, o = _duel(name, fused_knob, monkeypatch, target_update=target_update, double_q=double_q)
     rng = np.random.RandomState(LY.data_seed(name, LY.IQL_E, LY.IQL_CAP) + double_q + target_update)
-    flat_g = _targets_and_gradient_vs_oracle(lay, m, o, LY.IQL_E, LY.IQL_CAP, rng, target_update, double_q)
+    flat_g = H.targets_and_gradient_vs_oracle(lay, m, o, LY.IQL_E, LY.IQL_CAP, rng)
     ql, a7 = m.layout, lay.n_a_ls.index(7)
     head = flat_g.reshape(ql.A, ql.stride)[a7, ql.oWq:ql.obq].reshape(ql.H2, 8)
     assert (np.abs(head).max(0) > 0).all() and (flat_g.reshape(ql.A, ql.stride)[a7, ql.obq:ql.obq + 8] != 0).all()
@@ -191,15 +186,13 @@ def test_iql_dueling_targets_and_gradient(name, fused_knob, target_update, doubl
 
 def test_iql_prioritized_replay_step_at_the_fused_limit(monkeypatch):
     """One prioritized-replay step (target network + Double DQN, beta 0.4) on q160_edge against tests/iql_ext_oracle.py."""
-    from tests.test_iql_per_gpu import _per_step_vs_oracle
-    from tests.test_iql_target_gpu import _model
     name = 'q160_edge'
     spec = LY.IQL_LAYOUTS[name]
     monkeypatch.delenv('TSC_IQL_FUSED', raising=False)
-    lay, m = _model(spec['layout'], 'iql', 'dqn', LY.IQL_E, seed=LY.SEEDS[name], buffer_size=LY.IQL_CAP, prioritized_replay=1,
+    lay, m = H.model(spec['layout'], 'iql', 'dqn', LY.IQL_E, seed=LY.SEEDS[name], buffer_size=LY.IQL_CAP, prioritized_replay=1,
                     target_update=100, double_q=1, **spec['cfg'])
     assert m.fused
-    _per_step_vs_oracle(lay, m, LY.IQL_E, LY.IQL_CAP, np.random.RandomState(LY.data_seed(name, LY.IQL_E, LY.IQL_CAP) + 1), 100, 1, 0.4)
+    H.per_step_vs_oracle(lay, m, LY.IQL_E, LY.IQL_CAP, np.random.RandomState(LY.data_seed(name, LY.IQL_E, LY.IQL_CAP) + 1), 0.4)
     m.close()
 
 

@@ -2,7 +2,7 @@
 and the seeds of its table, the very inputs of the GPU module go through OracleA2C / OracleIQL and through their float32 restatement
 (the same code in torch float32 on the CPU, layouts.f32_oracle_class), and
 
-  * at most 4 hidden columns of a tower fall under the ReLU-kink exception of _grad_err / _kinks in any round (and no second-layer
+  * at most 4 hidden columns of a tower fall under the ReLU-kink exception of _grad_err / iql_harness.kinks in any round (and no second-layer
     unit of a Q-net sits on a kink: that would take every tensor below the head out of the comparison);
   * every action of every agent has an oracle probability in (1e-4, 1 - 1e-4) on some sample: no head is saturated, no gradient
     vacuous (a saturated softmax passes any kernel);
@@ -120,12 +120,12 @@ def _iql_pair(name):
 
 @pytest.mark.parametrize('name', list(LY.IQL_LAYOUTS))
 def test_iql_conditions(name):
-    from tests.test_iql_gpu import _kinks
+    from tests.iql_harness import kinks
     lay, o64, o32 = _iql_pair(name)
     E, A = LY.IQL_E, lay.n_agent
     rng = np.random.RandomState(LY.data_seed(name, E))
     qmax, worst = 0.0, 0.0
-    for t in range(3):                                                  # _forward_and_act's observations
+    for t in range(3):                                                  # forward_and_act's observations
         obs = LY.rand_obs(lay, E, rng)
         for q, q32 in zip(o64.forward(obs), o32.forward(obs)):
             assert np.abs(q32 - q).max() <= value_bound(q)
@@ -143,7 +143,7 @@ def test_iql_conditions(name):
         np.testing.assert_array_equal(o64.last_idx, o32.last_idx)
         for a in range(A):
             saved, o64.qs[a].p = o64.qs[a].p, before[a]
-            cols, deep = _kinks(o64, [rows[a][e][s][0] for e in range(E) for s in o64.last_idx[e, a]], a)
+            cols, deep = kinks(o64, [rows[a][e][s][0] for e in range(E) for s in o64.last_idx[e, a]], a)
             o64.qs[a].p = saved
             assert not deep, 'step %d agent %d: a second-layer unit on a ReLU kink' % (step, a)
             assert cols is None or cols.sum() <= 4, 'step %d agent %d: %d first-layer columns on a ReLU kink' % (step, a, cols.sum())

@@ -1,8 +1,13 @@
 #!/usr/bin/env python
-"""Times the IQL-DNN learner's launches in isolation (large_grid, E = 1024 by default): the minibatch gradient
+"""Times an IQL learner's launches in isolation (large_grid, E = 1024 by default): the minibatch gradient
 (tsc_iql_compute_grads: sample + fused gradient + reduce) and the acting forward, with HIP events on the launch stream.
 
-    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--target-update N [--double-q]] [--per] [--dueling] [--return-steps N]
+    python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--model-type dqn|lr] [--target-update N [--double-q]] [--per]
+                              [--dueling] [--return-steps N]
+
+--model-type lr times IQL-LR, which always runs the grouped-GEMM path (gather, GEMMs, iql_td_kernel).  IQL-DNN runs the fused kernels at
+the widths they are built for; TSC_IQL_FUSED=0 in the environment selects the grouped path for it too ("fused" in the output line says
+which path ran).
 
 --target-update N arms the target network (two launches per gradient: the TD targets from the frozen copy, then the gradient with one
 row set).  --per arms prioritized replay (the proportional sampler in place of the Floyd draw, the
@@ -29,6 +34,7 @@ def main():
     ap.add_argument('--envs', type=int, default=1024)
     ap.add_argument('--reps', type=int, default=50)
     ap.add_argument('--scenario', default='large_grid')
+    ap.add_argument('--model-type', choices=('dqn', 'lr'), default='dqn', help='IQL-DNN or IQL-LR (lr: always the grouped-GEMM path)')
     ap.add_argument('--target-update', type=int, default=0, help='[MODEL_CONFIG] target_update: refresh the target network every N Adam steps (0: none)')
     ap.add_argument('--double-q', action='store_true', help='[MODEL_CONFIG] double_q = 1 (needs --target-update)')
     ap.add_argument('--per', action='store_true', help='[MODEL_CONFIG] prioritized_replay = 1')
@@ -40,12 +46,12 @@ def main():
     from deeprl_signal_control_amd import _lib
     from deeprl_signal_control_amd.iql import VecIQL
     from deeprl_signal_control_amd.scenario import build_scenario
-    scn = build_scenario(args.scenario, 'iqld')
+    scn = build_scenario(args.scenario, 'iqld' if args.model_type == 'dqn' else 'iqll')
     E, A = args.envs, scn.n_agent
     m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, int(scn.green_tab.shape[1]),
                dict(batch_size=20, buffer_size=1000, reward_norm=3000.0, target_update=args.target_update, double_q=int(args.double_q),
                     prioritized_replay=int(args.per), dueling=int(args.dueling), return_steps=args.return_steps),
-               total_step=10 ** 6, seed=0, model_type='dqn')
+               total_step=10 ** 6, seed=0, model_type=args.model_type)
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     mask = torch.zeros(A, scn.s_max, device='cuda')
     for a, n in enumerate(scn.n_s_ls):
@@ -76,7 +82,7 @@ def main():
     def grads():
         _lib.check(m._L.tsc_iql_compute_grads(m._h, 7, step[0]))
         step[0] += 1
-    out = {'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'prioritized_replay': m.prioritized_replay, 'dueling': m.dueling, 'return_steps': m.return_steps,
+    out = {'model_type': args.model_type, 'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'prioritized_replay': m.prioritized_replay, 'dueling': m.dueling, 'return_steps': m.return_steps,
            'replay_size': m.replay_size()[0], 'compute_grads_us': timed(grads, args.reps),
            'forward_us': timed(lambda: m.forward(obs, mode='explore'), args.reps),
            'minibatch_step_us': timed(lambda: m.minibatch_step(1e-4), args.reps)}
