@@ -2161,6 +2161,10 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
 int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
     if (!h || trip_cap < 0) return tsc::fail("tsc_env_record: bad arguments");
     EnvDev &P = h->P;
+    EnvDev want = P;                             // checked before anything changes: a refusal leaves the handle, its plan included, as it was
+    want.rec = enable ? 1 : 0;
+    const size_t need = smem_bytes(want);
+    if (need > kLdsMax) return tsc::fail("tsc_env_record: LDS need %zu B > 160 KiB", need);
     TSC_HIP(hipStreamSynchronize(h->stream));
     if (enable && !P.R1) {
         const size_t slots = (size_t)P.E * kCap * P.NLP;
@@ -2172,8 +2176,7 @@ int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap) {
         TSC_HIP(h->bufs.alloc(&P.trips, (size_t)P.E * P.trip_cap * 6, true));
     }
     P.rec = enable ? 1 : 0;
-    h->smem = smem_bytes(P);
-    if (h->smem > kLdsMax) { h->plan = StepPlan(); return tsc::fail("tsc_env_record: LDS need %zu B > 160 KiB", h->smem); }
+    h->smem = need;
     TSC_HIP(hipFuncSetAttribute((const void *)reset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem));
     // (the Krauss and lane-data layouts need no check of their own here: with recording on a Krauss kernel takes what the IDM one
     // takes, without it what tsc_env_set_car_following checked; lane data was checked, recording on, when it was armed)

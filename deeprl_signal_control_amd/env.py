@@ -137,11 +137,11 @@ class VecTrafficEnv:
         """init_data(is_record=True) (envs/env.py:517-528): the following steps keep, per simulated second, the network
         statistics of _measure_traffic_step (:409-437), per control step the control log (:581-588) and a log of finished
         trips (:498-515), per env instance.  Uses the recording instantiation of the step kernel (plain lane walk)."""
+        if on or getattr(self, '_rec_alloc', False):     # (a refusal -- the recording kernels' LDS need -- leaves the handle as it was)
+            _lib.check(self._L.tsc_env_record(self._h, int(bool(on)), int(trip_cap)))
+            self._rec_alloc = True
         self.is_record = bool(on)
         self.trip_cap = int(trip_cap)
-        if self.is_record or getattr(self, '_rec_alloc', False):
-            _lib.check(self._L.tsc_env_record(self._h, int(self.is_record), int(trip_cap)))
-            self._rec_alloc = True
         if self.is_record:
             K = self.scn.agent_lanes.shape[1]
             self._rec_ints = np.zeros((self.E, 8, 4), np.int64)

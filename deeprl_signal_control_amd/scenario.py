@@ -207,7 +207,8 @@ class Scenario:
         small_grid: SmallGridController.greedy compares the first len(STATE_PHASE_MAP[node]) entries and returns the mapped
         phase (envs/small_grid_env.py:29-30,51-55).
         otherwise (real_net): RealNetController.greedy (envs/real_net_env.py:90-111) -- per phase the lanes of its 'G' links
-        ('g' does not count) in link order, every lane once."""
+        ('g' does not count) in link order, every lane once; a 'G' link that no lane uses (link_lane -1) adds no term, so a
+        phase whose 'G' links are all laneless is an empty candidate with flow 0.0."""
         A = self.n_agent
         cands, acts = [], []
         if self.name == 'large_grid':
@@ -225,7 +226,7 @@ class Scenario:
                 for p in range(int(self.agent_nphase[a])):
                     seen = []
                     for k in range(int(self.agent_nlink[a])):
-                        if self.green_tab[a, p, k] == ord('G'):
+                        if self.green_tab[a, p, k] == ord('G') and self.link_lane[a, k] >= 0:    # (a link no lane uses adds no term)
                             j = lanes.index(int(self.link_lane[a, k]))
                             if j not in seen:
                                 seen.append(j)

@@ -272,7 +272,9 @@ int tsc_env_live_sum(tsc_env *h, double *sum_host, int32_t reset);
 
 /* Evaluation recording = init_data(is_record=True) (envs/env.py:517-528): the following steps also keep, per simulated
  * second, _measure_traffic_step's inputs (envs/env.py:409-437) and a log of finished trips (the --tripinfo-output file
- * collect_tripinfo parses, :498-515).  Off on the training path (separate kernel instantiation).  Call before reset(). */
+ * collect_tripinfo parses, :498-515).  Off on the training path (separate kernel instantiation).  Call before reset().
+ * Refused, with the LDS need in the error, where the recording kernels' arrays do not fit beside the scenario's tables; a refused
+ * call changes nothing: the handle goes on as it was. */
 int tsc_env_record(tsc_env *h, int32_t enable, int32_t trip_cap);
 /* Rows of the LAST step: ints [E, 8, 4] = vehicles in the network, departed, arrived, sum of waiting times of second q <
  * control_interval_sec; speed [E, 8] = sum of speeds; queue [E, 8, A * l_max] = lane.getLastStepHaltingNumber of every

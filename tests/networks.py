@@ -11,7 +11,11 @@ interval, one vehicle per second and stream.  Every network of NETWORKS exists b
   share of random actions, seed).
 
 The runs of tests/test_networks_gpu.py are redrawn on the host by run_oracle / draw_actions below, so that tests/test_networks_host.py
-states conditions (the limit is reached, the roads are not empty) about the very runs the GPU tests compare."""
+states conditions (the limit is reached, the roads are not empty) about the very runs the GPU tests compare.
+
+The kernels around the step (controllers, pressure reward, recording walks, per-instance demand) run on the same networks: AUX, at the
+end of this file, lists those runs for tests/test_networks_aux_host.py and tests/test_networks_aux_gpu.py; windows() and split_pieces()
+exist for them."""
 import copy
 
 import numpy as np
@@ -268,15 +272,15 @@ def few_threads():
     return isolated(100, live=range(70, 100), streams_per_lane={j: 8 for j in range(70, 97, 3)}, episode_length_sec=450, teleport_sec=120)
 
 
-def merge4(merge, **env_kw):
+def merge4(merge, phases0=('GGGG', 'GGrr', 'rrGG', 'GrGr'), **env_kw):
     """Four feeder lanes (links 0-3 of agent 0) into one lane, which agent 1 holds back at its own signal: every feeder carries
     900 veh/h, so the four heads compete for the lane in the same second -- as a zipper of four (rank | 4 << 8) or by right of
-    way (the lowest feeder has priority, the other three yield to its head)."""
+    way (the lowest feeder has priority, the other three yield to its head).  phases0: agent 0's four phase strings."""
     env_kw.setdefault('episode_length_sec', 400)
     lanes = [(150.0, 13.89, 0)] * 4 + [(120.0, 13.89, 1), (100.0, 13.89, -1)]
     routes = [[[(f, f), (4, 0), (5, -1)]] for f in range(4)]
     flows = [(0, 400, 900, f) for f in range(4)]
-    return compile_network('merge4_%s' % merge, 'ia2c', lanes, routes, [['GGGG', 'GGrr', 'rrGG', 'GrGr'], ['G', 'r', 'G']], [[1], [0]], flows,
+    return compile_network('merge4_%s' % merge, 'ia2c', lanes, routes, [list(phases0), ['G', 'r', 'G']], [[1], [0]], flows,
                            merge=merge, teleport_sec=90, **env_kw)
 
 
@@ -362,6 +366,103 @@ def zip254(n_lane=254, check=True):
                            check=check, episode_length_sec=400, teleport_sec=60)
 
 
+WINDOWS_EPISODE = 120
+# flow elements of windows(): (begin, end, veh/h, stream).  The emission tables hold the seconds [0, episode + 64) = [0, 184).
+WINDOWS_FLOWS = [
+    (1, 18, 1800, 0),           # begins at 1, ends at 2 mod 4
+    (22, 43, 2400, 0),          # begins at 2, ends at 3 mod 4
+    (47, 61, 1500, 0),          # begins at 3, ends at 1 mod 4
+    (66, 67, 3600, 0),          # a one-second window
+    (70, 70, 3600, 0),          # an empty window
+    (5, 30, 1200, 1), (10, 23, 900, 1),         # two overlapping elements on one stream
+    (40, 90, 0, 1),             # a zero-rate element
+    (3, 119, 700, 2),
+    (100, 300, 1000, 2),        # ends past the table
+    (190, 250, 2000, 2),        # begins past the table
+    (81, 84, 900, 3), (82, 86, 1800, 3),        # WINDOWS_PAIR: the second begins a second after the first, they share seconds 82 and 83
+    (6, 78, 600, 3),            # (the stream's other element stays clear of the pair)
+]
+WINDOWS_PAIR = (11, 12)
+
+
+def windows():
+    """Three isolated one-lane junctions (as isolated(): in lane 150 m, out lane 100 m, phases G / r) under a 1 s control interval
+    without yellow, four insertion streams (two on the first junction's lane) and the flow elements of WINDOWS_FLOWS: windows that
+    begin and end at 1, 2 and 3 mod 4 (demand_kernel packs four seconds per thread and clamps tau at both ends of a window), one
+    second long, empty, overlapping on one stream, of rate zero, and past the emission table at their end or altogether."""
+    lanes, paths = [], []
+    for j in range(3):
+        lanes += [(150.0, 13.89, j), (100.0, 13.89, -1)]
+        paths.append([(2 * j, 0), (2 * j + 1, -1)])
+    streams = [(0, 0), (0, 0), (2, 0), (4, 0)]
+    return compile_network('windows', 'ia2c', lanes, [paths], [['G', 'r']] * 3, [[(j - 1) % 3, (j + 1) % 3] for j in range(3)],
+                           WINDOWS_FLOWS, streams, control_interval_sec=1, yellow_interval_sec=0, episode_length_sec=WINDOWS_EPISODE,
+                           teleport_sec=60)
+
+
+def windows_columns(scn):
+    """The veh/h columns of the per-instance demand runs on windows(), int32 [4, n_flow]; with (a, b) = WINDOWS_PAIR:
+    0: the scenario's own column;
+    1: a = 3600 x 55, b = 3600 x 200: 55 + 200 = 255 vehicles in each of the two shared seconds (the limit: accepted);
+    2: every rate redrawn (zero stays zero), one element of several vehicles a second;
+    3: a = 3600 x 55 + 1, b = 3600 x 200: the bounds ceil(vph / 3600) add up to 56 + 200 = 256, but a emits its 56 only in its own
+       first second, before b begins -- no second exceeds 255, and only the per-second path of the host check can tell."""
+    nominal = np.asarray(scn.flows)[:, 2].astype(np.int32)
+    a, b = WINDOWS_PAIR
+    cols = np.tile(nominal, (4, 1))
+    cols[1, a], cols[1, b] = 3600 * 55, 3600 * 200
+    rng = np.random.RandomState(77)
+    cols[2] = np.where(nominal > 0, rng.randint(300, 3000, len(nominal)), 0)
+    cols[2, 1] = 9000
+    cols[3, a], cols[3, b] = 3600 * 55 + 1, 3600 * 200
+    return cols
+
+
+def windows_refused_column(scn):
+    """Column 1 of windows_columns with a = 3600 x 56: 256 vehicles in second 82 -> (column, flow named, second named): the sum
+    passes 255 when the second element of the pair is added."""
+    col = windows_columns(scn)[1].copy()
+    col[WINDOWS_PAIR[0]] = 3600 * 56
+    return col, WINDOWS_PAIR[1], 82
+
+
+def demand254_columns(scn, E):
+    """The veh/h columns of the isolated_254 demand run, int32 [E, 254]: every instance its own rates (the junctions still drain),
+    the last stream of instance e at several vehicles a second."""
+    rng = np.random.RandomState(254)
+    cols = rng.randint(150, 700, (E, len(scn.flows))).astype(np.int32)
+    cols[np.arange(E), -1] = 5000 + 1000 * np.arange(E)
+    return cols
+
+
+def with_rates(scn, vph):
+    """scn with the veh/h column vph in place of its own (what instance e of a handle under set_demand runs)."""
+    import dataclasses
+    fl = np.array(scn.flows, np.int32)
+    fl[:, 2] = vph
+    return dataclasses.replace(scn, flows=fl)
+
+
+def split_pieces(scn, cuts):
+    """A copy of scn whose lanes named in cuts = {lane name: ascending cut positions in m} are made of len(cuts) + 1 SUMO lanes
+    '<name>#0', '<name>#1', ... that each begin at 0: lane_pieces only, which the lane data and the trajectories' SUMO positions
+    read (Scenario.lane_data_slots, sumo_lane_pos) -- the simulator's lanes stay whole."""
+    out = copy.copy(scn)
+    out.name = scn.name + '_pieces'
+    pieces = [list(ps) for ps in scn.lane_pieces]
+    for nm, cs in cuts.items():
+        l = scn.lane_names.index(nm)
+        assert len(pieces[l]) == 1 and 1 <= len(cs) <= 4 and list(cs) == sorted(cs) and 0.0 < cs[0] and cs[-1] < float(scn.lane_len[l]), nm
+        edges = [0.0] + [float(c) for c in cs] + [float(scn.lane_len[l])]
+        pieces[l] = [('%s#%d' % (nm, i), 0.0, edges[i + 1] - edges[i]) for i in range(len(edges) - 1)]
+    out.lane_pieces = pieces
+    return out
+
+
+# merge4_zipper in pieces: the merged lane in five, a feeder in three, the exit in two; 33.3, 61.7, 20.1 and 90.9 are no float32 values
+MERGE4_CUTS = {'l4': [20.1, 33.3, 61.7, 90.9], 'l0': [33.3, 100.1], 'l5': [61.7]}
+
+
 class Net:
     """One entry of NETWORKS.  plan: (MAXT, HELP, REC, KF, SPEC, threads) of tsc_env_step_plan for a fresh handle under `env` (the
     TSC_ENV_* variables the case sets).  E instances run `steps` control steps; an action is random with probability p_random, else
@@ -412,7 +513,9 @@ NETWORKS = {
     # NLA = 256 live lanes: 256 threads, no helper wavefront
     'zip254': Net(zip254, 'feeder lane indices up to 253 in the merge arbitration bytes', _NARROW + (256,), 2, 80, 0.5, 500, 40, 100.0),
 }
-RECORDED = ['grid_x4']          # the one plan behind the LDS budget (whether k = 4 fits): as reported by an MI355X handle
+NETWORKS['windows'] = Net(windows, 'flow windows that begin and end inside a 4-second word of the emission table; 1 s control interval',
+                          _NARROW + (256,), 3, 120, 0.3, 510, 60, 8.0)
+RECORDED = ['grid_x4']         # the one plan behind the LDS budget (whether k = 4 fits): as reported by an MI355X handle
 
 
 def _routes255():
@@ -528,3 +631,205 @@ def run_oracle(scn, net, on_second=None, train_mode=True, is_record=False, E=Non
             res.append(o.step(list(acts[e])))
             obs[e] = res[-1][0]
         yield t, acts, pols, res, orc
+
+
+# ---------------------------------------------------------------------------
+# the kernels around the step: controllers, pressure reward, recording walks, per-instance demand
+# ---------------------------------------------------------------------------
+_aux_scn = {}
+
+
+def aux_scenario(key):
+    """The scenario of an AUX case (built once; callers do not modify it): a registry entry's own, or one of its variants."""
+    if key not in _aux_scn:
+        if key == 'isolated_130_ma2c':
+            scn = isolated(130, agent='ma2c', objective='hybrid')
+        elif key == 'isolated_130_200s':            # (an episode of 200 s: the walks run to its end)
+            scn = isolated(130, objective='hybrid', episode_length_sec=200)
+        elif key == 'merge4_n3':
+            scn = merge4('zipper', norm_wave=3.0, clip_wave=1.5)
+        elif key == 'merge4_pieces':
+            scn = split_pieces(NETWORKS['merge4_zipper'].scenario(), MERGE4_CUTS)
+        elif key == 'merge4_krauss':
+            scn = copy.copy(NETWORKS['merge4_zipper'].scenario())
+            scn.car_following, scn.krauss_sigma = 'krauss', 0.5
+        else:
+            scn = NETWORKS[key].scenario()
+        _aux_scn[key] = scn
+    return _aux_scn[key]
+
+
+class Aux:
+    """One run of the AUX table: the scenario `key` (aux_scenario) under the run of the registry entry `net` (its seed, its share of
+    random actions) with E instances for `steps` control steps; what else a family needs is in `kw` (read as attributes)."""
+
+    def __init__(self, key, net, E, steps, **kw):
+        self.key, self.net_name, self.E, self.steps = key, net, E, steps
+        self.__dict__.update(kw)
+
+    def scenario(self):
+        return aux_scenario(self.key)
+
+    def net(self):
+        n = copy.copy(NETWORKS[self.net_name])
+        n.E, n.steps = self.E, self.steps
+        return n
+
+    def compared(self, t):
+        """Is the state after control step t one the case compares?  Every `every` steps and at the entry's peak."""
+        return (t > 0 and t % self.every == 0) or t == NETWORKS[self.net_name].peak or t == self.steps - 1
+
+    def __repr__(self):
+        return self.key
+
+
+# E, steps, seeds and actions of the runs below are run_oracle's (train mode: instance e runs seed net.seed + e); the walks draw their
+# own actions (walk_actions) from RandomState(rng_seed) and run the train-mode seeds seed + e.
+AUX = {
+    # pressure_kernel against loop_pressure, both measures.  isolated_130: 260 walked lanes (chunk 2); isolated_300: 600 walked lanes
+    # (chunk 3), 300 agents and 600 (agent, phase) pairs; grid_x4: 664 walked lanes (chunk 3), 1104 movements (five rounds of zeroing)
+    'pressure': [Aux('isolated_130', 'isolated_130', 2, 61, every=10), Aux('isolated_300', 'isolated_300', 2, 61, every=10),
+                 Aux('grid_x4', 'grid_x4', 2, 91, every=15), Aux('link62', 'link62', 3, 41, every=5),
+                 Aux('merge4_yield', 'merge4_yield', 3, 41, every=5), Aux('burst', 'burst', 3, 31, every=5)],
+    # the hold state [E][A][2] with A > 256: `steps` control steps of run_oracle's actions first, then the controller drives
+    'hold': Aux('isolated_300', 'isolated_300', 2, 8, min_green=3, least=30, most=60),
+    # pressure_reward_kernel against trainer.pressure_reward
+    'reward': [Aux('isolated_130_ma2c', 'isolated_130', 2, 41, every=8, measure='count', train_mode=True, record=False),
+               Aux('isolated_300', 'isolated_300', 2, 41, every=8, measure='queue', train_mode=True, record=False),
+               Aux('grid_x2', 'grid_x2', 3, 61, every=12, measure='count', train_mode=False, record=False),
+               Aux('ctrl8', 'ctrl8', 3, 40, every=8, measure='count', train_mode=True, record=True)],
+    # greedy_kernel against the float64 rule on the oracle's observations
+    'greedy': [Aux('link62', 'link62', 4, 80), Aux('merge4_zipper', 'merge4_zipper', 4, 80), Aux('grid_x2', 'grid_x2', 2, 60),
+               Aux('merge4_n3', 'merge4_zipper', 4, 80)],
+    # fixed_time_kernel: steps_per_phase s over `steps` control steps, twice
+    'fixed': [Aux('isolated_300', 'isolated_300', 3, 9, s=2), Aux('ctrl8', 'ctrl8', 2, 9, s=1), Aux('ctrl8', 'ctrl8', 2, 9, s=3)],
+    # the trace and the lane data of one handle against the oracle's vehicles after every second; steps None: to the end of the episode;
+    # watch: the instances an oracle follows
+    'walk': [Aux('isolated_130_200s', 'isolated_130', 2, None, period=55, watch=[1], seed=21, rng_seed=3),
+             Aux('burst', 'burst', 3, None, period=40, watch=[0, 2], seed=22, rng_seed=4),
+             Aux('ctrl8', 'ctrl8', 2, None, period=56, watch=[0, 1], seed=23, rng_seed=5),
+             Aux('ctrl1', 'ctrl1', 2, None, period=7, watch=[0, 1], seed=24, rng_seed=6),
+             Aux('merge4_pieces', 'merge4_zipper', 3, None, period=60, watch=[0, 2], seed=25, rng_seed=7),
+             Aux('grid_x2', 'grid_x2', 2, 60, period=60, watch=[1], seed=26, rng_seed=8),
+             Aux('merge4_krauss', 'merge4_zipper', 3, None, period=60, watch=[1, 2], seed=27, rng_seed=9)],
+    'trace254': Aux('isolated_254', 'isolated_254', 2, 12, watch=[1], seed=28, rng_seed=10),
+    # tsc_env_set_demand on windows(): instance e runs column e of windows_columns; isolated_254: demand_kernel on a 254 x 3 grid
+    'demand': Aux('windows', 'windows', 4, WINDOWS_EPISODE, seed=600),
+    'demand254': Aux('isolated_254', 'isolated_254', 3, 40, seed=610),
+}
+
+
+def aux_run(case, **kw):
+    """run_oracle over an AUX case."""
+    return run_oracle(case.scenario(), case.net(), E=case.E, **kw)
+
+
+def walk_steps(case):
+    scn = case.scenario()
+    return -(-int(scn.episode_length_sec) // int(scn.control_interval_sec)) if case.steps is None else case.steps
+
+
+def walk_actions(scn, rng, E):
+    """One control step's actions of a walk case, int32 [E, A]: agent after agent, E uniform draws among its phases."""
+    act = np.zeros((E, scn.n_agent), np.int32)
+    for a, n in enumerate(scn.n_a_ls):
+        act[:, a] = rng.randint(0, n, E)
+    return act
+
+
+def greedy_rule(tables, ob):
+    """The greedy controller's rule as Scenario.greedy_controller_tables states it, for one agent: tables = (its term rows [GC, GT],
+    its action row [GC], its candidate count), ob its float64 observation.  Per candidate the terms are added in table order, in
+    float64, from 0.0; the first maximum wins.  -> (action, flows)."""
+    term, action, n_cand = tables
+    flows = []
+    for c in range(int(n_cand)):
+        flow = 0.0
+        for j in term[c]:
+            if j < 0:
+                break
+            flow = flow + float(ob[j])
+        flows.append(flow)
+    best = 0
+    for c in range(1, len(flows)):
+        if flows[c] > flows[best]:
+            best = c
+    return int(action[best]), flows
+
+
+# the exhaustive check of greedy_kernel's float32 -> float64 recovery: agent 0 of merge4, every tuple of 0 .. 8 vehicles on its four
+# lanes.  Under the registry's phases the first candidate ('GGGG') holds every lane and always wins, and candidates of two lanes each
+# can only tie on the same two addends; here one lane alone comes first and pairs follow, so that 3 / 5 against 1 / 5 + 2 / 5 -- a tie
+# on the float32 entries, which the first candidate would win, and 0.6 < 0.6000000000000001 in float64 -- decides the action
+GREEDY_PHASES = ('rrrG', 'GGrr', 'GrGr', 'rGGr')
+GREEDY_NORMS = [(3.0, 1.5), (5.0, 1.1), (7.0, 0.9)]         # (norm_wave, clip_wave): the clip lies below 8 / norm_wave
+
+
+def greedy_exhaustive(norm, clip):
+    """-> (scn, counts int [6561, 4], the float32 observation entries [6561, 4] = float32(min(c / norm, clip)), the float64 rule's
+    action [6561], the action of the rule on the float32 entries added in float64 [6561], ... added in float32 [6561])."""
+    import itertools
+    scn = merge4('zipper', phases0=GREEDY_PHASES, norm_wave=norm, clip_wave=clip)
+    n_cand, term, action = scn.greedy_controller_tables()
+    assert int(scn.agent_nlane[0]) == 4 and int(n_cand[0]) == 4
+    tab = (term[0], action[0], n_cand[0])
+    counts = np.array(list(itertools.product(range(9), repeat=4)), np.int64)
+    ob64 = np.clip(counts.astype(np.float64) / norm, 0, clip)           # (OracleEnv._norm_clip)
+    ob32 = ob64.astype(np.float32)
+    want = np.array([greedy_rule(tab, row)[0] for row in ob64], np.int32)
+    naive64 = np.array([greedy_rule(tab, row.astype(np.float64))[0] for row in ob32], np.int32)
+    naive32 = np.zeros(len(counts), np.int32)
+    for i, row in enumerate(ob32):
+        flows = []
+        for c in range(4):
+            f = np.float32(0.0)
+            for j in term[0][c]:
+                if j >= 0:
+                    f = np.float32(f + row[j])
+            flows.append(f)
+        naive32[i] = action[0][int(np.argmax(flows))]
+    return scn, counts, ob32, want, naive64, naive32
+
+
+class WalkOracles:
+    """The oracle's side of a walk case: one snapshot oracle (tests.test_trace_gpu._snapshot_oracle: every lane's vehicles after
+    every simulated second) per watched instance, seed case.seed + e.  A control interval that does not divide the episode runs
+    the last launch past its end, which the device neither traces nor counts: views() cuts the snapshots at the episode's end and
+    answers totals() as of that second."""
+
+    def __init__(self, case):
+        from tests.test_trace_gpu import _snapshot_oracle
+        self.case, self.scn = case, case.scenario()
+        self.T = int(self.scn.episode_length_sec)
+        self.orc = {e: _snapshot_oracle(self.scn, case.seed + e) for e in case.watch}
+        self.at_end = {}
+        for e, o in self.orc.items():
+            def stepper(n=1, _o=o, _e=e, _step=o.ms.step):
+                for _ in range(n):
+                    _step(1)
+                    if len(_o.snaps) + 1 == self.T:         # (the snapshot of this second is appended after the step)
+                        self.at_end[_e] = _o.ms.totals()
+            o.ms.step = stepper
+            o.reset()
+
+    def step(self, acts):
+        for e, o in self.orc.items():
+            o.step(list(acts[e]))
+
+    def views(self):
+        """{e: what tests.test_lane_data_gpu._check reads of an oracle: snaps (seconds 0 .. T - 1) and ms.totals()}."""
+        import types
+        out = {}
+        for e, o in self.orc.items():
+            tot = self.at_end.get(e) if len(o.snaps) >= self.T else o.ms.totals()
+            out[e] = types.SimpleNamespace(snaps=o.snaps[:self.T], ms=types.SimpleNamespace(totals=lambda _t=tot: _t))
+        return out
+
+
+def walk_context(case):
+    """The Krauss walk cases run the oracle's Krauss model (a switch of the oracle library) for the length of the case."""
+    import contextlib
+    if case.scenario().car_following == 'krauss':
+        from tests.test_krauss_gpu import oracle_krauss
+        return oracle_krauss(case.scenario().krauss_sigma)
+    return contextlib.nullcontext()

@@ -271,3 +271,20 @@ def test_limits_agree_between_check_limits_and_the_registry():
             continue
         with pytest.raises(ValueError, match=text):
             make().streams_ready().check_limits()
+
+
+def test_windows_emits_what_the_integer_rule_says():
+    """The create-time emission table over windows that begin and end inside a 4-second word, overlap, are empty or lie past the
+    table: per instance, departed + pending is the integer rule's count over the run's seconds, stream by stream."""
+    out = _run('windows')
+    _common(out)
+    scn, net = out['scn'], out['net']
+    T = net.steps * scn.control_interval_sec
+    assert (scn.control_interval_sec, scn.yellow_interval_sec) == (1, 0) and T == scn.episode_length_sec
+    emitted = np.zeros(scn.n_stream, np.int64)
+    for b, en, vph, s_ in np.asarray(scn.flows, np.int64).tolist():
+        emitted[s_] += (max(0, min(T, en) - b) * vph + 3599) // 3600
+    assert (emitted > 0).all() and {int(b) % 4 for b in scn.flows[:, 0]} >= {1, 2, 3} and {int(x) % 4 for x in scn.flows[:, 1]} >= {1, 2, 3}
+    for o in out['orc']:
+        tot = o.ms.totals()
+        assert tot['departed'] + tot['pending'] == emitted.sum() and tot['departed'] > 0.8 * emitted.sum(), (tot, emitted)

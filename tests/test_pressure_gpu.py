@@ -96,6 +96,29 @@ def test_block_indexing():
     env.close()
 
 
+def hold_state(E, A, g):
+    """The hold's bookkeeping of a freshly armed (or reset) handle: (cur, age, last_change); the first decision is free."""
+    return np.full((E, A), -1), np.full((E, A), g), np.full((E, A), -10)
+
+
+def hold_update(state, e, p_star, t, g):
+    """One control step of instance e's hold bookkeeping, from this step's argmax p_star [A]: -> phase changes counted (the first
+    choice after arming is none)."""
+    cur, age, last_change = state
+    n_changes = 0
+    for a in range(len(p_star)):
+        if age[e, a] < g:
+            age[e, a] += 1
+        elif p_star[a] != cur[e, a]:
+            if cur[e, a] >= 0:
+                assert t - last_change[e, a] >= g, (t, e, a)
+                n_changes += 1
+            cur[e, a], age[e, a], last_change[e, a] = p_star[a], 1, t
+        else:
+            age[e, a] += 1
+    return n_changes
+
+
 def test_hold():
     scn, tb = scenario('large_grid')
     E, A, g = 4, 25, 3
@@ -104,8 +127,8 @@ def test_hold():
     rng = np.random.RandomState(2)
     for t in range(8):                                     # some traffic first (the hold is not armed yet)
         env.step(random_actions(rng, scn, E))
-    cur, age = np.full((E, A), -1), np.full((E, A), g)     # arming frees the first decision, as reset() does
-    last_change = np.full((E, A), -10)
+    state = hold_state(E, A, g)                            # arming frees the first decision, as reset() does
+    cur, age, _ = state
     t, n_changes = 0, 0
     while t < 30 or not ((age < g) & (cur != 0)).any():
         assert t < 60, 'no agent inside a hold on a phase other than 0'
@@ -113,16 +136,7 @@ def test_hold():
         act_h = act.cpu().numpy()
         for e in range(E):
             p_star, _ = loop_pressure(scn, tb, env.get_state(e), 'count')
-            for a in range(A):
-                if age[e, a] < g:
-                    age[e, a] += 1
-                elif p_star[a] != cur[e, a]:
-                    if cur[e, a] >= 0:
-                        assert t - last_change[e, a] >= g, (t, e, a)
-                        n_changes += 1
-                    cur[e, a], age[e, a], last_change[e, a] = p_star[a], 1, t
-                else:
-                    age[e, a] += 1
+            n_changes += hold_update(state, e, p_star, t, g)
         np.testing.assert_array_equal(act_h, cur, err_msg='t=%d' % t)
         env.step(act)
         t += 1

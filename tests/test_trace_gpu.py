@@ -39,21 +39,24 @@ def _actions(env, scn, rng, policy, E):
     return torch.from_numpy(act).cuda()
 
 
-def _check_against_oracle(scn, tr, snaps):
+def _check_against_oracle(scn, tr, snaps, by_entry_lane=False):
     """Rows of every second (time_sec = second + 1) == the oracle's vehicles in (lane, slot) order; oracle id <-> (route, serial)
-    one bijection over the whole run."""
+    one bijection over the whole run.  by_entry_lane: serials count per insertion stream, so where several streams share a route
+    (the synthetic networks of tests/networks.py) the key is (route, serial, the lane the vehicle was first seen on -- its
+    stream's entry lane)."""
     assert len(snaps) > 0
     ends = np.cumsum([0] + [int((tr['time_sec'] == j + 1).sum()) for j in range(len(snaps))])
     assert ends[-1] == len(tr['time_sec']), 'rows after the last simulated second'
-    id_of, key_of = {}, {}
+    id_of, key_of, entry = {}, {}, {}
     for j, sn in enumerate(snaps):
         sl = slice(ends[j], ends[j + 1])
         np.testing.assert_array_equal(tr['sim_lane'][sl], np.repeat(np.arange(scn.n_lane), sn['n']), err_msg='second %d' % j)
         np.testing.assert_array_equal(tr['route'][sl], sn['r'], err_msg='second %d' % j)
         np.testing.assert_array_equal(tr['x'][sl].view(np.uint32), sn['x'].view(np.uint32), err_msg='second %d' % j)
         np.testing.assert_array_equal(tr['speed'][sl].astype(np.float32).view(np.uint32), sn['v'].view(np.uint32), err_msg='second %d' % j)
-        for oid, r, s in zip(sn['id'].tolist(), tr['route'][sl].tolist(), tr['serial'][sl].tolist()):
-            assert id_of.setdefault((r, s), oid) == oid and key_of.setdefault(oid, (r, s)) == (r, s), (j, oid, r, s)
+        for oid, l, r, s in zip(sn['id'].tolist(), tr['sim_lane'][sl].tolist(), tr['route'][sl].tolist(), tr['serial'][sl].tolist()):
+            key = (r, s, entry.setdefault(oid, l)) if by_entry_lane else (r, s)
+            assert id_of.setdefault(key, oid) == oid and key_of.setdefault(oid, key) == key, (j, oid, r, s)
     return len(id_of)
 
 
