@@ -18,7 +18,21 @@ are the values an MI355X handle reported, recorded here and asserted from then o
 
 The rollouts of tests/test_layouts_gpu.py are redrawn on the host by forward_inputs / fill_host / iql_transitions below: the same
 RandomState seeds in the same order of draws as tests/test_model_gpu.py::_fill and tests/iql_harness.py::replay_vs_oracle, so that
-tests/test_layouts_host.py states conditions about the very samples the GPU tests compare."""
+tests/test_layouts_host.py states conditions about the very samples the GPU tests compare.
+
+The agent-count axis.  A2C_COUNT_LAYOUTS holds layouts of 1, 64, 65, 130, 340 and 341 agents: the number of agents sets the row splits
+per tower (upd_splits), the forward workgroups per tower (fwd_splits), the head slices (head_slices) and, through the workspace, the
+choice of dwxh_kernel at all (dwxh_fits).  Those functions restate the lines of csrc/tsc_model.hip they name.  From 64 agents on the
+float64 oracle evaluates pick(A) agents only.
+
+ROWS.  From 65 agents on s_upd = 1, so one workgroup of dwxh_kernel / dx1w1_kernel2 / fc_bwd_kernel walks the whole batch and a case
+(E, T) chooses its rows R = E T directly.  dwxh_schedule(R) and w1_schedule(R) restate the kernels' row loops -- full 64-row intervals
+and the clamped tail of 16-row sub-chunks; plain and clamped 32-row chunks -- and ROWS is the list of (E, T) with R <= 300 that walks
+every class of them: no, one and several full intervals, every tail length a full interval can leave behind (5 - 9) and every one
+without (1 - 8), last sub-chunks of 1, 2, 15 and 16 rows.  At R <= 300 a lost or doubled row is at least 3e-3 of a weight gradient;
+at the benchmarked batches, the only other place these schedules run, it is 1e-5 and below tolerance.  What ROWS must cover is
+asserted by tests/test_layouts_host.py::test_rows_cover_the_schedules, not by the list.  count_cases() lists every update case of
+the three axes (agent count, rows, time) for the GPU module and the host module alike."""
 import contextlib
 
 import numpy as np
@@ -106,6 +120,138 @@ IQL_LAYOUTS = {
 }
 # tsc_iql_create must refuse this one: num_fc = 100 with wait inputs, H1 = 125, "hidden widths must be multiples of 4"
 IQL_REFUSED = _iql('dqn', 100, 64, 36, _LG_IQL, None, 'H1 = 125')
+# (the layouts above, in the order data_seed numbers them: names added later come behind, so that no rollout of an older case moves)
+_SEED_ORDER = sorted(list(A2C_LAYOUTS) + list(IQL_LAYOUTS))
+
+
+# ---- the agent-count axis ---------------------------------------------------------------------------------------------------------
+# The number of agents A decides how the learner launches its kernels (csrc/tsc_model.hip tsc_model_create "The plan", launch_head_bwd,
+# launch_dwxh, launch_w1); the functions below restate those lines on the host, and the layouts of A2C_COUNT_LAYOUTS sit where they change.
+WS_FLOATS = 48 << 20                                    # tsc_model_create: m->ws_floats
+
+
+def upd_splits(A):
+    """Row splits per tower of dwxh_kernel / dx1w1_kernel2 / fc_bwd_kernel (tsc_model_create: P.s_upd = 256 / G, at least 1; G = 2 A)."""
+    return max(1, 256 // (2 * A))
+
+
+def fwd_splits(A, E):
+    """Workgroups per tower of the Ws forward (tsc_model_create: P.s_fwd = min(s_upd, ceil(E / 32)))."""
+    return min(upd_splits(A), (E + 31) // 32)
+
+
+def split_rows(N, S, q):
+    """Rows per split (split_rows in csrc/tsc_model.hip): ceil(N / S) rounded up to the kernel's row quantum q."""
+    return ((N + S - 1) // S + q - 1) // q * q
+
+
+def split_R(N, S, q):
+    """The rows R = n1 - n0 each of the S workgroups of a tower sees (dwxh_kernel / dx1w1_kernel2: n0 = sp rows_per_split, n1 =
+    min(n0 + rows_per_split, N)); 0 for a split that starts at or behind row N and skips its loops."""
+    rps = split_rows(N, S, q)
+    return [max(0, min(N, (sp + 1) * rps) - sp * rps) for sp in range(S)]
+
+
+DWXH_Q, W1_Q, HEAD_Q = 2, 32, 16                        # kDwK, kW1Chunk, kHbRows: the row quanta of the three split passes
+
+
+def head_slices(A, N):
+    """Slices of head_bwd_kernel (launch_head_bwd: S = ceil(2048 / A), rows per slice = split_rows(N, S, kHbRows), S = ceil(N / rows))."""
+    rps = split_rows(N, (8 * 256 + A - 1) // A, HEAD_Q)
+    return (N + rps - 1) // rps
+
+
+def dwxh_ws_floats(H):
+    """A split's partial record of dwxh_kernel: [dWx ; dWh ; dbl] (dwxh_ws_floats in csrc/tsc_model.hip)."""
+    return (H + 64 + 1) * 256
+
+
+def dwxh_fits(A, H):
+    """tsc_model_create's ws_fits(dwxh_ws_floats(H)): the fused dWx | dWh | dbl kernel is chosen only when every split's record fits."""
+    return upd_splits(A) * 2 * A * dwxh_ws_floats(H) <= WS_FLOATS
+
+
+def dwxh_schedule(R):
+    """dwxh_kernel's row loop over a split of R rows (the two loops behind its prologue: `for (; KC * (c + 9) <= R; c += 4)`, four Plain
+    16-row sub-chunks and a barrier; then `for (; KC * c < R; ++c)`, Clamp sub-chunks) -> (full intervals, tail sub-chunks, rows
+    of the last sub-chunk)."""
+    if R <= 0:
+        return 0, 0, 0
+    c = full = 0
+    while 16 * (c + 9) <= R:
+        c, full = c + 4, full + 1
+    n = (R + 15) // 16
+    return full, n - c, R - 16 * (n - 1)
+
+
+def w1_schedule(R):
+    """dx1w1_kernel2's row loop over a split of R rows (`for (; row + 2 * kW1Chunk <= n1; ...) chunk(Plain)`, then `for (; row < n1; ...)
+    chunk(Clamp)`, 32-row chunks; fc_bwd_kernel walks the same chunks in one loop) -> (plain chunks, clamp chunks, rows of the last chunk)."""
+    if R <= 0:
+        return 0, 0, 0
+    plain = 0
+    while 32 * plain + 64 <= R:
+        plain += 1
+    n = (R + 31) // 32
+    return plain, n - plain, R - 32 * (n - 1)
+
+
+def _cycle(agents, n):
+    return [agents[i % len(agents)] for i in range(n)]
+
+
+def pick(A):
+    """The agents the float64 oracle evaluates on a layout of A agents (the full oracle costs seconds per round from 65 agents on):
+    the first, the last, two in between, and index 128 where there is one."""
+    return sorted(set([0, A // 3, 2 * A // 3, A - 1] + ([128] if A > 128 else [])))
+
+
+# three inputs or four per agent: the smallest observation a handle accepts (s_max % 4 == 0), so that 341 agents stay small
+_EDGE_MA2C = [(2, 1, 1, 5), (1, 1, 2, 3), (1, 2, 1, 2), (1, 1, 1, 4)]
+_W224, _W160, _W128, _W192 = (150, 42, 32), (100, 28, 32), (104, 0, 24), (130, 62, 0)
+# name -> as A2C_LAYOUTS; what the agent count drives is the `why`.  Kept apart from A2C_LAYOUTS: the tests of that table run the full oracle.
+A2C_COUNT_LAYOUTS = {
+    'solo': _a2c('ma2c', _W224, 52, _LG_MA2C[:1], (WS, 1, 1), (FC_MFMA, 1), 's_upd = 128: nearly every split empty at small N; XCD map with G = 2'),
+    'many64': _a2c('ma2c', _W224, 52, _cycle(_LG_MA2C, 64), (WS, 1, 1), (FC_MFMA, 1),
+                   's_upd = 2, the last count before 1; s_fwd = 2 from E = 33 on; XCD map with G = 128'),
+    'many65': _a2c('ma2c', _W224, 52, _cycle(_LG_MA2C, 65), (WS, 1, 1), (FC_MFMA, 1), 's_upd = 1: R = N = E T, a case chooses its R'),
+    'many65_h128': _a2c('ia2c', _W128, 36, _cycle(_LG_IA2C, 65), (WS, 1, 1), (FC_MFMA, 1), 's_upd = 1 at H = 128: dwxh<6>, dx1w1<8>, fc_bwd<8>'),
+    'many65_h160': _a2c('ma2c', _W160, 52, _cycle(_LG_MA2C, 65), (WS, 1, 1), (FC_MFMA, 1), 's_upd = 1 at H = 160: dwxh<7>, dx1w1<10>, fc_bwd<10>'),
+    'many65_h192': _a2c('ma2c', _W192, 52, _cycle(_RN_MA2C, 65), (WS, 1, 1), (FC_MFMA, 1), 's_upd = 1 at H = 192: dwxh<8>, dx1w1<12>, fc_bwd<12>'),
+    'many130': _a2c('ia2c', _W128, 36, _cycle(_LG_IA2C, 130), (WS, 1, 1), (FC_MFMA, 1),
+                    '256 / G = 0 clamped to 1; head_bwd S = 16; the agent count of isolated_130'),
+    'ws_edge_340': _a2c('ma2c', _W224, 4, _cycle(_EDGE_MA2C, 340), (WS, 1, 1), (FC_MFMA, 1), 'the last count whose dwxh records fit the workspace at H = 224'),
+    'ws_edge_341': _a2c('ma2c', _W224, 4, _cycle(_EDGE_MA2C, 341), (WS, 0, 1), (FC_MFMA, 1), 'the first count past it: the plan must report dwxh = 0'),
+}
+ROW_WIDTHS = ['many65_h128', 'many65_h160', 'many65_h192']
+
+# ROWS: the (E, T) of the row-split sweep on the 65-agent layouts, where s_upd = 1 and a split's R is the whole batch N = E T.  At
+# N <= 300 one lost or doubled row is at least 3e-3 of a weight gradient, against a tolerance of 2e-5.  What the table must cover is
+# stated by tests/test_layouts_host.py::test_rows_cover_the_schedules through dwxh_schedule / w1_schedule.  R = E T, in order:
+#   2, 18, 33, 64, 65, 95, 111, 128, 130, 142: no full interval, tails of 1 - 9 sub-chunks, last sub-chunk of 1, 2, 14, 15, 16 rows
+#   144, 146, 160, 176, 192, 195, 207: one full interval, then 5 - 9 tail sub-chunks in the ring it filled
+#   208, 224, 255, 296: two and three full intervals
+# The pairs of R = 95, 111, 130, 142, 146, 195, 207, 255 and 296 have E % 16 != 0: the BPTT tiles are ragged too.
+ROWS = [(1, 2), (3, 6), (3, 11), (32, 2), (5, 13), (19, 5), (37, 3), (16, 8), (65, 2), (71, 2), (16, 9), (73, 2), (16, 10), (16, 11),
+        (32, 6), (65, 3), (23, 9), (16, 13), (32, 7), (51, 5), (37, 8)]
+# the reduced set of the other three widths: every tail length behind a full interval once, odd and 15-row last sub-chunks, no full interval
+ROWS_REDUCED = [(5, 13), (73, 2), (65, 3), (23, 9), (51, 5)]
+# many64 (s_upd = 2): split boundaries off the 16-row grid and a short last split -- N = 297: R = 150 | 147 in dwxh and 160 | 137 in
+# dx1w1 / fc_bwd; N = 295: 148 | 147 and 160 | 135
+ROWS_64 = [(27, 11), (59, 5)]
+# fused against grouped GEMMs, and PPO: a full interval and a ragged tail
+ROWS_FUSED = [(73, 2), (23, 9), (51, 5)]
+PPO_ROWS = (23, 9, 5, 7, 5e-2)          # (E, T, init seed, rollout seed, lr) on many65, K = 2: epoch 1 takes the re-forward path
+WS_EDGE_BATCH = (3, 2)
+TIME_LAYOUTS, TIME_BATCHES = ['head8', 'edges160'], [(37, 1), (5, 2), (37, 2)]      # the edges of the lstm_fwd / lstm_bwd2 prefetch pipelines
+DONE_PATTERNS = [('always', 1.0), ('never', 0.0)]       # on head8, T = 7: h_prev masked at every step / never after the reset
+DONE_BATCH = (37, 7)
+
+IQL_LAYOUTS.update({
+    'q130_fused': _iql('dqn', 128, 64, 48, _cycle(_Q160, 130), True, '130 agents inside the fused limits'),
+    'q130_grouped': _iql('dqn', 64, 32, 36, _cycle(_LG_IQL, 130), False, '130 agents on the grouped path'),
+})
+_SEED_ORDER += list(A2C_COUNT_LAYOUTS) + ['q130_fused', 'q130_grouped']
 
 # The batches of the GPU module: A2C (E, T) -- N = 30 and N = 259 rows, ragged in every row loop; IQL E instances, ring capacity
 A2C_BATCHES = [(5, 6), (37, 7)]
@@ -117,6 +263,14 @@ IQL_REWARD_NORM = 100.0
 # kink, no saturated head, float32 drift of the second round inside its allowance); the GPU module takes the same table.
 SEEDS = {name: 5 for name in list(A2C_LAYOUTS) + list(IQL_LAYOUTS)}
 SEEDS.update(tiny=11, q_small=6)        # 5 fails there: tiny 5 - 10 put more than 4 columns of a one-input block on a kink, q_small 5 a second-layer unit
+# the same for the layouts of the agent-count axis: 5 meets every condition of tests/test_layouts_host.py::test_count_update_conditions
+COUNT_SEEDS = {name: 5 for name in A2C_COUNT_LAYOUTS}
+
+
+def seed_of(name):
+    return SEEDS[name] if name in SEEDS else COUNT_SEEDS[name]
+
+
 # PPO on head8 (MA2C, LSTM, K = 3): (E, T, init seed, rollout seed, lr) under tests/ppo_oracle.py's k3_conditions
 PPO_HEAD8 = (16, 8, 5, 7, 5e-2)
 
@@ -125,7 +279,7 @@ def data_seed(name, E, T=0):
     """RandomState seed of a case's rollout: one stream per (layout, batch), moved by the layout's entry in SEEDS -- a layout whose
     agents have one or two inputs needs a rollout without an input within ~1e-3 of zero (after the first update the biases are
     ~1e-4, and such a sample puts many hidden units of the block on their kink at once)."""
-    return 100000 * (sorted(list(A2C_LAYOUTS) + list(IQL_LAYOUTS)).index(name) + 1) + 1000 * SEEDS[name] + 10 * E + T
+    return 100000 * (_SEED_ORDER.index(name) + 1) + 1000 * seed_of(name) + 10 * E + T
 
 
 def rand_obs(lay, E, rng):
@@ -145,22 +299,26 @@ def forward_inputs(lay, E, steps, rng):
     return out, rand_obs(lay, E, rng)
 
 
-def fill_host(lay, oracles, E, T, rng, reward_norm, p_done=0.1):
+def fill_host(lay, oracles, E, T, rng, reward_norm, p_done=0.1, terminal=False, sel=None):
     """tests/test_model_gpu.py::_fill without a device: the same draws in the same order.  The stored value is the first oracle's,
-    rounded to float32 (on the GPU: the kernel's).  -> (next obs, carried done, list of per-step pi of the first oracle)."""
+    rounded to float32 (on the GPU: the kernel's).  sel: the oracles hold these agents only (the draws are those of the whole layout).
+    -> (next obs, carried done, list of per-step pi of the first oracle)."""
+    pk = (lambda x: x) if sel is None else (lambda x: x[:, sel])
     obs, done, pis = rand_obs(lay, E, rng), np.ones(E, np.uint8), []
     for t in range(T):
         v = None
         for o in oracles:
-            pi, ov = o.forward(obs, done, 'pv')
+            pi, ov = o.forward(pk(obs), done, 'pv')
             if v is None:
                 v = np.asarray(ov, np.float64).astype(np.float32)
                 pis.append(pi)
         act = np.stack([rng.randint(0, n, E) for n in lay.n_a_ls], 1).astype(np.int32)
         rew = -rng.rand(E, lay.n_agent) * 3.0 * reward_norm
         dpost = (rng.rand(E) < p_done).astype(np.uint8)
+        if terminal and t == T - 1:
+            dpost[:] = 1
         for o in oracles:
-            o.add_transition(obs, done, act, rew, v, dpost)
+            o.add_transition(pk(obs), done, pk(act), pk(rew), v, dpost)
         obs, done = rand_obs(lay, E, rng), dpost
     return obs, done, pis
 
@@ -207,3 +365,30 @@ def f32_oracle_class(base):
             if callable(v) and not isinstance(v, (staticmethod, classmethod)) and (not k.startswith('__') or k == '__init__'):
                 body[k] = wrap(getattr(base, k))
     return type(base.__name__ + 'F32', (base,), body)
+
+
+def count_cases():
+    """Every update case the agent-count, row-split and time axes add to tests/test_layouts_gpu.py, one tuple per rollout stream:
+    (group, layout name, policy, E, T, rounds, first round ends on a terminal step, p_done).  The GPU module runs each (some with the
+    activation cache on and off: the draws do not depend on it); tests/test_layouts_host.py states the oracle-only conditions of each."""
+    out = []
+    for name in ('solo', 'many64', 'many65', 'many130'):
+        out += [('count', name, p, E, T, 2, False, 0.1) for p in ('lstm', 'fc') for E, T in A2C_BATCHES]
+    out += [('rows', 'many65', p, E, T, 1, False, 0.1) for p in ('lstm', 'fc') for E, T in ROWS]
+    out += [('rows', n, p, E, T, 1, False, 0.1) for n in ROW_WIDTHS for p in ('lstm', 'fc') for E, T in ROWS_REDUCED]
+    out += [('rows', 'many64', p, E, T, 1, False, 0.1) for p in ('lstm', 'fc') for E, T in ROWS_64]
+    out += [('time', n, p, E, T, 2, True, 0.1) for n in TIME_LAYOUTS for p in ('lstm', 'fc') for E, T in TIME_BATCHES]
+    out += [('done', 'head8', 'lstm', DONE_BATCH[0], DONE_BATCH[1], 2, False, pd) for _, pd in DONE_PATTERNS]
+    # (the update runs past the workspace edge only; at 340 agents the GPU module asserts the plan)
+    out += [('edge', 'ws_edge_341', 'lstm', WS_EDGE_BATCH[0], WS_EDGE_BATCH[1], 1, False, 0.1)]
+    return out
+
+
+def spec_of(name):
+    return A2C_LAYOUTS[name] if name in A2C_LAYOUTS else A2C_COUNT_LAYOUTS[name]
+
+
+def pick_of(name):
+    """The agents the oracle evaluates on a layout: all of them on the small ones (None), pick() from 64 agents on."""
+    A = spec_of(name)['layout'].n_agent
+    return pick(A) if A >= 64 else None

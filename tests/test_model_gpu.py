@@ -83,8 +83,9 @@ def test_gemm_tn_colsum_rowrange(Kred, M, N, G, split):
     np.testing.assert_allclose(out2.cpu().numpy(), ref * mask, atol=tol, rtol=1e-4)
 
 
-def _make(agent, E, n_step, seed=0, policy='lstm', scenario='large_grid', **cfg):
-    """scenario: the name of a built-in scenario, or a layout object (tests/layouts.py: the attributes read below and nothing else)."""
+def _make(agent, E, n_step, seed=0, policy='lstm', scenario='large_grid', sel=None, **cfg):
+    """scenario: the name of a built-in scenario, or a layout object (tests/layouts.py: the attributes read below and nothing else).
+    sel: the oracle holds these agents only (towers 2 a, 2 a + 1 of each, in this order)."""
     from deeprl_signal_control_amd.agents import VecA2C
     from deeprl_signal_control_amd.scenario import build_scenario
     from oracle.nets_oracle import OracleA2C
@@ -96,10 +97,16 @@ def _make(agent, E, n_step, seed=0, policy='lstm', scenario='large_grid', **cfg)
     a_max = int(scn.green_tab.shape[1]) if hasattr(scn, 'green_tab') else scn.a_max
     m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, E, scn.s_max, a_max, mc, device=0,
                seed=seed, name=agent, policy=policy)
-    o = OracleA2C(m.get_tower_params(), m.n_wave_ls, m.n_w_ls, m.n_f_ls, m.n_a_ls, E,
+    ids, tw = _ids(scn, sel), m.get_tower_params()
+    o = OracleA2C([tw[2 * a + k] for a in ids for k in (0, 1)], *[[ls[a] for a in ids] for ls in (m.n_wave_ls, m.n_w_ls, m.n_f_ls, m.n_a_ls)], E,
                   gamma=m.cfg['gamma'], reward_norm=m.cfg['reward_norm'], reward_clip=m.cfg['reward_clip'],
                   value_coef=m.cfg['value_coef'], max_grad_norm=m.cfg['max_grad_norm'])
     return scn, m, o
+
+
+def _ids(scn, sel):
+    """The agents an oracle holds: all of them, or the pick `sel` (oracle agent i = device agent _ids[i])."""
+    return list(range(scn.n_agent)) if sel is None else list(sel)
 
 
 def _grad_err(o, t, k, got, og):
@@ -128,12 +135,13 @@ def _rand_obs(scn, E, rng):
     return obs
 
 
-def _forward_vs_oracle(scn, m, o, E, rng, steps=5, sample=False, vtol=2e-5):
+def _forward_vs_oracle(scn, m, o, E, rng, steps=5, sample=False, vtol=2e-5, sel=None):
     """`steps` advancing forwards with random dones, then the non-advancing bootstrap value, against the oracle.  sample: through
     forward_sample, whose action must be np.random.choice on the kernel's own pi and the documented uniform.  vtol: bound on |dv|,
     or a function of the oracle's values (layouts whose values leave the reference's range, tests/test_layouts_gpu.py)."""
     from oracle.nets_oracle import choice_from_uniform, sample_uniform
     tol = vtol if callable(vtol) else (lambda ov: vtol)
+    ids = _ids(scn, sel)                                      # pi and v against the oracle on these agents; everything else on all
     m.reset(); o.reset()
     for t in range(steps):
         obs = _rand_obs(scn, E, rng)
@@ -145,12 +153,13 @@ def _forward_vs_oracle(scn, m, o, E, rng, steps=5, sample=False, vtol=2e-5):
         else:
             pi, v = m.forward(torch.from_numpy(obs).cuda(), torch.from_numpy(done).cuda(), 'pv')
         pi, v = pi.cpu().numpy(), v.cpu().numpy()
-        opi, ov = o.forward(obs, done, 'pv')
+        opi, ov = o.forward(obs[:, ids], done, 'pv')
+        for i, a in enumerate(ids):
+            np.testing.assert_allclose(pi[:, a, :scn.n_a_ls[a]], opi[i], atol=2e-5, err_msg='pi t=%d a=%d' % (t, a))
         for a in range(scn.n_agent):
-            np.testing.assert_allclose(pi[:, a, :scn.n_a_ls[a]], opi[a], atol=2e-5, err_msg='pi t=%d a=%d' % (t, a))
             if sample:
                 assert np.all(pi[:, a, scn.n_a_ls[a]:] == 0)
-        np.testing.assert_allclose(v, ov, atol=tol(ov))
+        np.testing.assert_allclose(v[:, ids], ov, atol=tol(ov))
         assert np.allclose(pi.sum(-1), 1.0, atol=1e-5)
         if sample:
             for e in range(E):
@@ -160,8 +169,8 @@ def _forward_vs_oracle(scn, m, o, E, rng, steps=5, sample=False, vtol=2e-5):
     # bootstrap value: state must NOT advance (policies.py:127-135)
     obs = _rand_obs(scn, E, rng)
     vb = m.forward(torch.from_numpy(obs).cuda(), False, 'v').cpu().numpy()
-    _, ovb = o.forward(obs, np.zeros(E), 'v')
-    np.testing.assert_allclose(vb, ovb, atol=tol(ovb))
+    _, ovb = o.forward(obs[:, ids], np.zeros(E), 'v')
+    np.testing.assert_allclose(vb[:, ids], ovb, atol=tol(ovb))
     vb2 = m.forward(torch.from_numpy(obs).cuda(), False, 'v').cpu().numpy()
     np.testing.assert_array_equal(vb, vb2)
 
@@ -260,7 +269,10 @@ def test_fc_policy_forward_kernels_agree_with_each_other(monkeypatch):
     print('FC kernels: %d of %d sampled actions differ (all on a cdf boundary)' % (differ, 3 * E * 25))
 
 
-def _fill(scn, m, o, E, T, rng, p_done=0.1, terminal=False, use_cache=False):
+def _fill(scn, m, o, E, T, rng, p_done=0.1, terminal=False, use_cache=False, sel=None, log=None):
+    """sel: the oracle holds these agents only (the draws are those of all agents).  log: a list that receives every step's
+    (reward, stored value, done after the step) of ALL agents, for the returns of the agents the oracle does not hold."""
+    ids = _ids(scn, sel)
     obs = _rand_obs(scn, E, rng)
     done = np.ones(E, np.uint8)
     for t in range(T):
@@ -269,7 +281,7 @@ def _fill(scn, m, o, E, T, rng, p_done=0.1, terminal=False, use_cache=False):
         else:
             pi, v = m.forward(torch.from_numpy(obs).cuda(), torch.from_numpy(done).cuda(), 'pv')
         v = v.cpu().numpy()
-        o.forward(obs, done, 'pv')
+        o.forward(obs[:, ids], done, 'pv')
         act = np.stack([rng.randint(0, n, E) for n in scn.n_a_ls], 1).astype(np.int32)
         rew = -rng.rand(E, scn.n_agent) * 3.0 * m.cfg['reward_norm']
         dpost = (rng.rand(E) < p_done).astype(np.uint8)
@@ -277,47 +289,75 @@ def _fill(scn, m, o, E, T, rng, p_done=0.1, terminal=False, use_cache=False):
             dpost[:] = 1
         m.add_transition(torch.from_numpy(obs).cuda(), torch.from_numpy(done).cuda(), torch.from_numpy(act).cuda(),
                          torch.from_numpy(rew).cuda(), torch.from_numpy(v).cuda(), torch.from_numpy(dpost).cuda())
-        o.add_transition(obs, done, act, rew, v, dpost)
+        o.add_transition(obs[:, ids], done, act[:, ids], rew[:, ids], v[:, ids], dpost)
+        if log is not None:
+            log.append((rew, v, dpost))
         obs, done = _rand_obs(scn, E, rng), dpost
     return obs, done
 
 
-def _backward_vs_oracle(scn, m, o, E, T, rng, terminal, use_cache):
-    """Two update rounds against the oracle: returns bit-exact, every gradient tensor, structural zeros, losses, norm, parameters."""
+def _returns_of_all(o, log, Rb):
+    """Returns and advantages of every agent from the logged transitions: OracleA2C.add_transition's reward shaping and
+    OracleA2C.returns_advs (float64 recursion), for the agents an oracle with a pick does not hold."""
+    r = np.stack([x[0] for x in log]).astype(np.float64)
+    if o.rnorm:
+        r = r / o.rnorm
+    if o.rclip:
+        r = np.clip(r, -o.rclip, o.rclip)
+    vs = np.stack([x[1] for x in log]).astype(np.float32).astype(np.float64)
+    dpost = np.stack([np.zeros_like(log[0][2])] + [x[2] for x in log]).astype(np.float64)[:, :, None] * np.ones((1, 1, r.shape[2]))
+    return o.returns_advs(r, vs, dpost, Rb, o.gamma)
+
+
+def _backward_vs_oracle(scn, m, o, E, T, rng, terminal, use_cache, sel=None, p_done=0.1, rounds=2, worst=None):
+    """Two update rounds against the oracle: returns bit-exact, every gradient tensor, structural zeros, losses, norm, parameters.
+    sel: the oracle holds these agents (their towers, losses, norms and parameters are compared; returns and advantages of all
+    agents).  worst: a dict that receives the largest |dg| / max|g| per round and, under ('where', round), its (tower, tensor,
+    max|g| of that tensor).  -> the gradient buffer of every round."""
     m.reset(); o.reset()
     from deeprl_signal_control_amd import _lib
-    for it in range(2):                                       # second round exercises states_bw / carried done
-        obs, done = _fill(scn, m, o, E, T, rng, terminal=terminal and it == 0, use_cache=use_cache)
+    ids, flats = _ids(scn, sel), []
+    for it in range(rounds):                                  # second round exercises states_bw / carried done
+        log = []
+        obs, done = _fill(scn, m, o, E, T, rng, p_done=p_done, terminal=terminal and it == 0, use_cache=use_cache, sel=sel, log=log)
         Rb = m.forward(torch.from_numpy(obs).cuda(), False, 'v').clone()
-        _, oRb = o.forward(obs, np.zeros(E), 'v')
         Rb_np = Rb.cpu().numpy()
         beta = 0.01
         _lib.check(m._L.tsc_model_compute_grads(m._h, C.c_void_p(Rb.data_ptr()), beta))
-        ograds, ostats = o.compute_grads(Rb_np, beta)
+        ograds, ostats = o.compute_grads(Rb_np[:, ids], beta)
         Rs = np.zeros((T, E, scn.n_agent), np.float32); Advs = np.zeros_like(Rs)
         _lib.check(m._L.tsc_model_get_returns(m._h, Rs.ctypes.data_as(C.c_void_p), Advs.ctypes.data_as(C.c_void_p)))
-        np.testing.assert_array_equal(Rs, o.Rs)               # float64 recursion on both sides
-        np.testing.assert_array_equal(Advs, o.Advs)
+        np.testing.assert_array_equal(Rs[:, :, ids], o.Rs)    # float64 recursion on both sides
+        np.testing.assert_array_equal(Advs[:, :, ids], o.Advs)
+        if sel is not None:
+            Rs_all, Advs_all = _returns_of_all(o, log, Rb_np)
+            np.testing.assert_array_equal(Rs_all[:, :, ids], o.Rs)
+            np.testing.assert_array_equal(Rs, Rs_all)
+            np.testing.assert_array_equal(Advs, Advs_all)
         g = m.unpack(m.grad_tensor().cpu().numpy())
-        for t in range(m.G):
+        for t in range(2 * len(ids)):
             for k, og in ograds[t].items():
-                err = _grad_err(o, t, k, g[t][k], og.numpy())
+                err = _grad_err(o, t, k, g[2 * ids[t // 2] + t % 2][k], og.numpy())
+                if worst is not None and err >= worst.get(it, 0.0):
+                    worst[it], worst['where', it] = err, (2 * ids[t // 2] + t % 2, k, float(np.abs(og.numpy()).max()))
                 # second round: the parameters already differ by the first update's fp32 rounding (<= 3e-5)
                 assert err <= (2e-5 if it == 0 else 2e-4), 'it=%d tower=%d %s: |dg| / max|g| = %.2e' % (it, t, k, err)
         # structural zeros of the block-diagonal FC must have exactly zero gradient
         flat = m.grad_tensor().cpu().numpy().reshape(m.G, m.stride)
         packed = m.pack(g).reshape(m.G, m.stride)
         np.testing.assert_array_equal(flat, packed)
+        flats.append(flat.copy())
         stats = np.zeros((scn.n_agent, 4))
         _lib.check(m._L.tsc_model_apply_grads(m._h, 5e-4, 1.0, stats.ctypes.data_as(C.c_void_p)))
         m.cur_t = 0
         onorm = o.apply_grads(ograds, 5e-4)
-        np.testing.assert_allclose(stats[:, :3], ostats, rtol=2e-3, atol=1e-6)
-        np.testing.assert_allclose(stats[:, 3], onorm, rtol=2e-3)
+        np.testing.assert_allclose(stats[ids, :3], ostats, rtol=2e-3, atol=1e-6)
+        np.testing.assert_allclose(stats[ids, 3], onorm, rtol=2e-3)
         p, op = m.get_tower_params(), o.tower_params()
-        for t in range(m.G):
+        for t in range(2 * len(ids)):
             for k in op[t]:
-                np.testing.assert_allclose(p[t][k], op[t][k], atol=3e-5, err_msg='param tower=%d %s' % (t, k))
+                np.testing.assert_allclose(p[2 * ids[t // 2] + t % 2][k], op[t][k], atol=3e-5, err_msg='param tower=%d %s' % (t, k))
+    return flats
 
 
 @pytest.mark.parametrize('agent,E,T,terminal,policy,use_cache', [
@@ -372,18 +412,18 @@ def test_forward_sample_equals_forward_then_sample():
     m.close()
 
 
-def _fused_vs_grouped(agent, knobs, policy, monkeypatch, E=40, T=9, scenario='large_grid', **cfg):
+def _fused_vs_grouped(agent, knobs, policy, monkeypatch, E=40, T=9, scenario='large_grid', sel=None, **cfg):
     """The update with and without the one-pass kernels the knobs switch off: same gradient up to fp32 summation order, the same
-    zero pattern.  -> the two handles' plans."""
+    zero pattern.  sel: the agents the (unused) oracle holds, for layouts where a full one is slow.  -> the two handles' plans."""
     grads, plans = [], []
     for unfused in ('0', '1'):
         for knob in knobs:
             monkeypatch.setenv(knob, unfused)
-        scn, m, o = _make(agent, E, T, seed=5, policy=policy, scenario=scenario, **cfg)
+        scn, m, o = _make(agent, E, T, seed=5, policy=policy, scenario=scenario, sel=sel, **cfg)
         plans.append(m.plan)
         m.reset(); o.reset()
         r2 = np.random.RandomState(123)
-        obs, done = _fill(scn, m, o, E, T, r2, terminal=False, use_cache=True)
+        obs, done = _fill(scn, m, o, E, T, r2, terminal=False, use_cache=True, sel=sel)
         Rb = m.forward(torch.from_numpy(obs).cuda(), False, 'v').clone()
         from deeprl_signal_control_amd import _lib
         _lib.check(m._L.tsc_model_compute_grads(m._h, C.c_void_p(Rb.data_ptr()), 0.01))
