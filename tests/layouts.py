@@ -388,6 +388,128 @@ def spec_of(name):
     return A2C_LAYOUTS[name] if name in A2C_LAYOUTS else A2C_COUNT_LAYOUTS[name]
 
 
+# ---- value regimes ------------------------------------------------------------------------------------------------------------------
+# Every layout above keeps the VALUES in the regime of the initialisation: probabilities between 0.06 and 0.6, gradient norms below
+# max_grad_norm.  A regime is a transform of the per-tower dicts (even towers are the policy towers) that leaves that corner:
+# name -> policy -> (scale of the policy head out_w / out_b, scale of the recurrent or second layer of BOTH towers, one-hot bias).
+#   peaked     the policy head scaled up: a share of the taken actions below the 1e-10 clamp of log pi, every agent's norm above the clip
+#   half_clip  a smaller scale: agents on both sides of max_grad_norm in one launch
+#   gates      a peaked head, and lstm_wx / lstm_wh / lstm_b (policy 'fc': fc_w / fc_b) scaled on both towers: saturated gates
+#   onehot     policy out_b[a % n_a] += 200 for agent a: pi exactly one-hot in float32
+# The scales were chosen on the host (tests/test_regimes_host.py states what each must produce on the cases of regime_cases(), ten
+# rollout streams tried per case, REGIME_STREAM).  Starting points were 30 / 8 / (30, 6) for both policies; they moved because
+#   * LSTM, peaked 30: on edges192 at N = 30 at most 2.7 % of the taken actions fall below the clamp in any stream (45: 8 %);
+#   * FC, peaked 30: the head input is a ReLU layer, not h in (-1, 1), so the logits are larger: the two-action agent of head8 saturates
+#     (every gradient of its policy tower below 1e-7) or stays below the clip; 12 leaves edges192 under 5 % below the clamp; 16 meets both;
+#   * FC, gates (30, 6): the restatement's |dpi| leaves half the bound; (16, 2) saturates the two-action agent again, (12, 2) does not;
+#   * half_clip 8: every FC agent clips (norms 74 - 175; 3: 28 - 62), and at the learning rate the clip check needs (HALF_CLIP_LR) every
+#     LSTM agent of head8 at N = 259 clips in the second round (7: 37 - 75).
+REGIMES = {'peaked': {'lstm': (45.0, 1.0, 0.0), 'fc': (16.0, 1.0, 0.0)}, 'half_clip': {'lstm': (7.0, 1.0, 0.0), 'fc': (3.0, 1.0, 0.0)},
+           'gates': {'lstm': (45.0, 6.0, 0.0), 'fc': (12.0, 2.0, 0.0)}, 'onehot': {'lstm': (1.0, 1.0, 200.0), 'fc': (1.0, 1.0, 200.0)}}
+CLAMP = 1e-10                           # tf.clip_by_value(pi, 1e-10, 1) of the loss (agents/policies.py:41-52)
+REGIME_FORWARD_LAYOUTS = ['head8', 'h96', 'h124', 'edges192']
+REGIME_PPO = (16, 8, 5, 7, 5e-5)        # (E, T, init seed, rollout seed, lr) on head8, 'peaked', K = 2
+HALF_CLIP_LR = 2e-3                     # tests/test_regimes_gpu.py: the learning rate at which a wrong clip factor shows in the parameters
+
+
+# (regime, layout, policy, E, T) -> which of ten rollout streams the case takes, where stream 0 misses a condition of the host module
+REGIME_STREAM = {('half_clip', 'edges192', 'fc', 5, 6): 1, ('gates', 'head8', 'fc', 37, 7): 1, ('half_clip', 'head8', 'fc', 5, 6): 4,
+                 ('gates', 'head8', 'fc', 5, 6): 1, ('half_clip', 'edges192', 'lstm', 5, 6): 2, ('gates', 'head8', 'lstm', 37, 7): 4}
+
+
+def regime_data_seed(regime, name, policy, E, T):
+    """RandomState seed of a regime case's rollout: data_seed's stream of the batch, or one of nine more (REGIME_STREAM)."""
+    return data_seed(name, E, T) + 7919 * REGIME_STREAM.get((regime, name, policy, E, T), 0)
+
+
+def apply_regime(towers, name, lay):
+    """The towers (list of per-tower dicts as VecA2C.get_tower_params / init_tower_params return them, ALL agents of lay) under a
+    regime of REGIMES -> a new list; float32 arithmetic, so that the host module and a device handle hold the same bits."""
+    head, rec, hot = (np.float32(x) for x in REGIMES[name]['fc' if 'fc_w' in towers[0] else 'lstm'])
+    out = [{k: np.array(v, np.float32) for k, v in p.items()} for p in towers]
+    assert len(out) == 2 * lay.n_agent
+    for t, p in enumerate(out):
+        if t % 2 == 0:
+            p['out_w'], p['out_b'] = p['out_w'] * head, p['out_b'] * head
+            if hot:
+                p['out_b'][(t // 2) % lay.n_a_ls[t // 2]] += hot
+        for k in ('lstm_wx', 'lstm_wh', 'lstm_b', 'fc_w', 'fc_b'):
+            if k in p:
+                p[k] = p[k] * rec
+    return out
+
+
+def clip_step_gap(grads, ms, norms, clip, lr, alpha=0.99, eps=1e-5):
+    """What a wrong clip factor moves: per agent whose norm exceeds clip, the largest |parameter step with factor 1 - step with clip /
+    norm| over its entries under RMSProp (ms before the step) -> the largest of those figures over the clipped agents.
+    grads, ms: per-tower dicts of float64 arrays."""
+    def step(g, m, sc):
+        g = g * sc
+        return lr * g / np.sqrt(alpha * m + (1 - alpha) * g * g + eps)
+    gaps = []
+    for a, nrm in enumerate(norms):
+        if nrm > clip:
+            gaps.append(max(float(np.abs(step(np.asarray(g), np.asarray(ms[t][k]), 1.0) - step(np.asarray(g), np.asarray(ms[t][k]), clip / nrm)).max())
+                            for t in (2 * a, 2 * a + 1) for k, g in grads[t].items()))
+    return max(gaps)
+
+
+def onehot_action(lay):
+    """The action the `onehot` regime gives all of an agent's probability."""
+    return [a % n for a, n in enumerate(lay.n_a_ls)]
+
+
+# ---- the Q-learners' regimes: one fused and one grouped layout of IQL_LAYOUTS, and IQL-LR
+IQL_REGIME_LAYOUTS = ['q160_edge', 'q_small', 'lr_tiny']
+IQL_CLIP_SCALE = {'q160_edge': 5.0, 'q_small': 3.0, 'lr_tiny': 10.0}    # head scale of the `clip` regime per layout, chosen on the host
+IQL_CLIP_STEPS, IQL_CLIP_LR = 3, 1e-3
+
+
+def adam_step_bound(d_ref, w):
+    """Bound on |d step| of one tensor in the `clip` regime's Adam steps (second moments preloaded with 1, so that a step is nearly linear
+    in the clipped gradient): the gradient tolerance 2e-5 max|g| per tensor and the clip norm's rtol 1e-4 carry over to the step as
+    1.2e-4 max|step|; on top the float32 rounding of the parameter itself, 2^-23 max|w|."""
+    return 1.2e-4 * float(np.abs(d_ref).max()) + 2.0 ** -23 * float(np.abs(w).max())
+
+
+def tie_pair(a, na):
+    """The two head columns j < k of agent a the `tied` regime makes identical."""
+    return a % (na - 1), na - 1
+
+
+def apply_iql_regime(agents, regime, name):
+    """Per-agent parameter dicts (VecIQL.get_agent_params / init_agent_params) of layout `name` under a Q-learner regime -> new list.
+      tied  head column k = column j (weights and bias), every other column's bias lowered by 50: the pair is the maximum on every row
+      flat  head weights and bias zero: Q is exactly 0, every action ties
+      clip  head weights and bias x IQL_CLIP_SCALE[name]: gradient norms on both sides of max_grad_norm"""
+    out = [{k: np.array(v, np.float32) for k, v in p.items()} for p in agents]
+    for a, p in enumerate(out):
+        na = p['q_b'].shape[0]
+        if regime == 'tied':
+            j, k = tie_pair(a, na)
+            p['q_w'][:, k], p['q_b'][k] = p['q_w'][:, j], p['q_b'][j]
+            p['q_b'][[c for c in range(na) if c not in (j, k)]] -= np.float32(50.0)
+        elif regime == 'flat':
+            p['q_w'][:], p['q_b'][:] = 0, 0
+        else:
+            assert regime == 'clip'
+            p['q_w'], p['q_b'] = p['q_w'] * np.float32(IQL_CLIP_SCALE[name]), p['q_b'] * np.float32(IQL_CLIP_SCALE[name])
+    return out
+
+
+def regime_cases():
+    """Every update case of tests/test_regimes_gpu.py, one tuple per rollout stream: (regime, layout, policy, E, T)."""
+    out = [(r, 'head8', p, E, T) for r in ('peaked', 'half_clip', 'gates') for p in ('lstm', 'fc') for E, T in A2C_BATCHES]
+    out += [(r, 'edges192', p) + A2C_BATCHES[0] for r in ('peaked', 'half_clip', 'gates') for p in ('lstm', 'fc')]
+    out += [('peaked', n, p) + A2C_BATCHES[0] for n in ('h96', 'h124') for p in ('lstm', 'fc')]
+    out += [('onehot', 'head8', p, E, T) for p in ('lstm', 'fc') for E, T in A2C_BATCHES]
+    return out
+
+
+def regime_forward_cases():
+    return [(r, n, p) for r in ('peaked', 'gates', 'onehot') for n in REGIME_FORWARD_LAYOUTS for p in ('lstm', 'fc')]
+
+
 def pick_of(name):
     """The agents the oracle evaluates on a layout: all of them on the small ones (None), pick() from 64 agents on."""
     A = spec_of(name)['layout'].n_agent

@@ -39,13 +39,16 @@ def _towers(name, policy):
     return init_tower_params(lay.n_wave_ls, lay.n_w_ls, n_f, lay.n_a_ls, n_fc, 64, policy, np.random.RandomState(LY.seed_of(name))), n_f
 
 
-def _a2c_pair(name, policy, E, sel=None):
-    """The float64 oracle and its float32 restatement on a layout's agents, or on the agents `sel` of it."""
+def _a2c_pair(name, policy, E, sel=None, regime=None):
+    """The float64 oracle and its float32 restatement on a layout's agents, or on the agents `sel` of it; regime: a value regime of
+    tests/layouts.py REGIMES on the initial weights."""
     from deeprl_signal_control_amd.agents import A2C_DEFAULTS
     from oracle.nets_oracle import OracleA2C
     spec = LY.spec_of(name)
     lay, c = spec['layout'], dict(A2C_DEFAULTS, **spec['cfg'])
     towers, n_f = _towers(name, policy)
+    if regime is not None:
+        towers = LY.apply_regime(towers, regime, lay)
     kw = dict(gamma=c['gamma'], reward_norm=c['reward_norm'], reward_clip=c['reward_clip'], value_coef=c['value_coef'],
               max_grad_norm=c['max_grad_norm'])
     ids = list(range(lay.n_agent)) if sel is None else list(sel)
@@ -132,13 +135,15 @@ def test_a2c_update_conditions(name, policy, E, T):
     _update_conditions(name, policy, E, T)
 
 
-def _iql_pair(name):
+def _iql_pair(name, regime=None):
     from deeprl_signal_control_amd.iql import IQL_DEFAULTS, QParamLayout, init_agent_params
     from oracle.iql_oracle import OracleIQL
     spec = LY.IQL_LAYOUTS[name]
     lay, c = spec['layout'], dict(IQL_DEFAULTS, **spec['cfg'])
     ql = QParamLayout(lay.n_wave_ls, lay.n_w_ls, lay.n_a_ls, lay.s_max, spec['model_type'], c['num_fc'], c['num_h'])
     params = init_agent_params(ql, np.random.RandomState(LY.SEEDS[name]))
+    if regime is not None:                                                # a Q-learner regime of tests/layouts.py apply_iql_regime
+        params = LY.apply_iql_regime(params, regime, name)
     kw = dict(batch_size=20, buffer_size=LY.IQL_CAP, gamma=c['gamma'], reward_norm=LY.IQL_REWARD_NORM, reward_clip=c['reward_clip'],
               max_grad_norm=c['max_grad_norm'], replay_seed=LY.SEEDS[name] ^ 0x5DEECE66D)
     o64 = OracleIQL(params, lay.n_wave_ls, lay.n_w_ls, lay.n_a_ls, LY.IQL_E, **kw)

@@ -83,9 +83,10 @@ def test_gemm_tn_colsum_rowrange(Kred, M, N, G, split):
     np.testing.assert_allclose(out2.cpu().numpy(), ref * mask, atol=tol, rtol=1e-4)
 
 
-def _make(agent, E, n_step, seed=0, policy='lstm', scenario='large_grid', sel=None, **cfg):
+def _make(agent, E, n_step, seed=0, policy='lstm', scenario='large_grid', sel=None, regime=None, **cfg):
     """scenario: the name of a built-in scenario, or a layout object (tests/layouts.py: the attributes read below and nothing else).
-    sel: the oracle holds these agents only (towers 2 a, 2 a + 1 of each, in this order)."""
+    sel: the oracle holds these agents only (towers 2 a, 2 a + 1 of each, in this order).
+    regime: a value regime of tests/layouts.py REGIMES, applied to the handle's parameters; the oracle is built from what the handle then returns."""
     from deeprl_signal_control_amd.agents import VecA2C
     from deeprl_signal_control_amd.scenario import build_scenario
     from oracle.nets_oracle import OracleA2C
@@ -97,6 +98,9 @@ def _make(agent, E, n_step, seed=0, policy='lstm', scenario='large_grid', sel=No
     a_max = int(scn.green_tab.shape[1]) if hasattr(scn, 'green_tab') else scn.a_max
     m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, E, scn.s_max, a_max, mc, device=0,
                seed=seed, name=agent, policy=policy)
+    if regime is not None:
+        from tests.layouts import apply_regime
+        m.set_tower_params(apply_regime(m.get_tower_params(), regime, scn))
     ids, tw = _ids(scn, sel), m.get_tower_params()
     o = OracleA2C([tw[2 * a + k] for a in ids for k in (0, 1)], *[[ls[a] for a in ids] for ls in (m.n_wave_ls, m.n_w_ls, m.n_f_ls, m.n_a_ls)], E,
                   gamma=m.cfg['gamma'], reward_norm=m.cfg['reward_norm'], reward_clip=m.cfg['reward_clip'],
@@ -309,11 +313,11 @@ def _returns_of_all(o, log, Rb):
     return o.returns_advs(r, vs, dpost, Rb, o.gamma)
 
 
-def _backward_vs_oracle(scn, m, o, E, T, rng, terminal, use_cache, sel=None, p_done=0.1, rounds=2, worst=None):
+def _backward_vs_oracle(scn, m, o, E, T, rng, terminal, use_cache, sel=None, p_done=0.1, rounds=2, worst=None, lr=5e-4):
     """Two update rounds against the oracle: returns bit-exact, every gradient tensor, structural zeros, losses, norm, parameters.
     sel: the oracle holds these agents (their towers, losses, norms and parameters are compared; returns and advantages of all
     agents).  worst: a dict that receives the largest |dg| / max|g| per round and, under ('where', round), its (tower, tensor,
-    max|g| of that tensor).  -> the gradient buffer of every round."""
+    max|g| of that tensor).  lr: the learning rate of both sides' RMSProp step.  -> the gradient buffer of every round."""
     m.reset(); o.reset()
     from deeprl_signal_control_amd import _lib
     ids, flats = _ids(scn, sel), []
@@ -348,9 +352,9 @@ def _backward_vs_oracle(scn, m, o, E, T, rng, terminal, use_cache, sel=None, p_d
         np.testing.assert_array_equal(flat, packed)
         flats.append(flat.copy())
         stats = np.zeros((scn.n_agent, 4))
-        _lib.check(m._L.tsc_model_apply_grads(m._h, 5e-4, 1.0, stats.ctypes.data_as(C.c_void_p)))
+        _lib.check(m._L.tsc_model_apply_grads(m._h, lr, 1.0, stats.ctypes.data_as(C.c_void_p)))
         m.cur_t = 0
-        onorm = o.apply_grads(ograds, 5e-4)
+        onorm = o.apply_grads(ograds, lr)
         np.testing.assert_allclose(stats[ids, :3], ostats, rtol=2e-3, atol=1e-6)
         np.testing.assert_allclose(stats[ids, 3], onorm, rtol=2e-3)
         p, op = m.get_tower_params(), o.tower_params()

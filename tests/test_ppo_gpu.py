@@ -28,11 +28,15 @@ def _vec(scn, agent, policy, E, T, seed, **cfg):
                   name=agent, policy=policy)
 
 
-def _make(agent, policy, E, T, seed, sel=None, layout=None, **cfg):
-    """layout: a layout object (tests/layouts.py) in place of large_grid."""
+def _make(agent, policy, E, T, seed, sel=None, layout=None, regime=None, **cfg):
+    """layout: a layout object (tests/layouts.py) in place of large_grid.  regime: a value regime of tests/layouts.py REGIMES, applied to
+    the handle's parameters; the oracle is built from what the handle then returns."""
     from deeprl_signal_control_amd.scenario import build_scenario
     scn = build_scenario('large_grid', agent) if layout is None else layout
     m = _vec(scn, agent, policy, E, T, seed, **cfg)
+    if regime is not None:
+        from tests.layouts import apply_regime
+        m.set_tower_params(apply_regime(m.get_tower_params(), regime, scn))
     o = make_oracle(scn, agent, policy, E, seed, clip_eps=m.ppo_clip, gae_lambda=m.gae_lambda, cfg=m.cfg, towers=m.get_tower_params(),
                     sel=sel)
     m.reset(); o.reset()
