@@ -1,0 +1,403 @@
+"""Shared scaffolding of the simulator tests (tests/test_env_gpu.py, test_krauss_gpu.py, test_trace_gpu.py, test_lane_data_gpu.py,
+test_demand_gpu.py, test_pressure*_gpu.py, test_networks*_gpu.py and their host twins) -- TEST INFRASTRUCTURE ONLY: the oracle's
+Krauss switch, the snapshot oracle, the action and fingerprint draws, the comparisons of a step, of the vehicle state and of the
+counters, the walk of a device handle beside its oracles and the walk of several handles under the same actions.  One copy of each; a
+test module keeps its tests and the helpers only it uses.  The host reference rules of the kernels around the step are in
+tests/env_rules.py.
+
+Nothing here has a tolerance: the simulator's contract is bit equality with the oracle (observations == float32 of the oracle's float64
+ones, rewards identical float64).  The module imports without a GPU and without the library, and puts arrays on the handle's own device
+(env.device): tests/test_env_harness_host.py runs every comparison on the CPU against a stand-in handle with planted errors."""
+import contextlib
+
+import numpy as np
+import torch
+
+STATE_KEYS = ('n', 'x', 'v', 'sf', 'w', 'r')        # VecTrafficEnv.get_state / ms.snapshot: per lane the count, then per slot position,
+                                                    # speed, standing flag, waiting time, route
+RECORD_TABLES = ('traffic_data', 'control_data', 'trip_data', 'truncated_trip_data')
+
+
+def _items(x):
+    """(instance, value) of a per-instance list (all instances) or dict (the watched ones)."""
+    return x.items() if isinstance(x, dict) else enumerate(x)
+
+
+def upload(env, x):
+    return (x if torch.is_tensor(x) else torch.from_numpy(x)).to(env.device)
+
+
+# ---- the oracle -------------------------------------------------------------------------------------------------------------------
+@contextlib.contextmanager
+def oracle_krauss(sigma):
+    """The oracle's Krauss model for the length of the block: a process-wide switch of the oracle library, off again in `finally`."""
+    from oracle.microsim import lib
+    L = lib()
+    L.ms_set_krauss(1, float(sigma))
+    try:
+        yield
+    finally:
+        L.ms_set_krauss(0, 0.5)
+
+
+def snapshot_oracle(scn, seed):
+    """OracleEnv whose _simulate also keeps, after every simulated second, every lane's vehicles (route, x, v, global id)."""
+    from oracle.env_oracle import OracleEnv
+
+    class SnapOracle(OracleEnv):
+        def _simulate(self, num_step):
+            for _ in range(num_step):
+                self.ms.step(1)
+                self.cur_sec += 1
+                if self.is_record:
+                    self._measure_traffic_step()
+                lv = [self.ms.lane_vehicles(l) for l in range(self.scn.n_lane)]
+                self.snaps.append({k: np.concatenate([d[k] for d in lv]) for k in ('r', 'x', 'v', 'id')}
+                                  | {'n': np.array([d['n'] for d in lv])})
+
+    o = SnapOracle(scn, seed=seed)
+    o.snaps = []
+    return o
+
+
+# ---- the draws --------------------------------------------------------------------------------------------------------------------
+# Each consumes its generator in an order of its own; the runs the non-vacuity assertions were tuned on depend on that order.
+def uniform_actions(scn, rng, E):
+    """One control step's actions, int32 [E, A]: agent after agent, E uniform draws among its phases."""
+    act = np.zeros((E, scn.n_agent), np.int32)
+    for a, n in enumerate(scn.n_a_ls):
+        act[:, a] = rng.randint(0, n, E)
+    return act
+
+
+def policy_actions(env, rng, policy):
+    """'greedy': the handle's own greedy controller on its last observations (a tensor); anything else: uniform_actions."""
+    return env.greedy_actions() if policy == 'greedy' else uniform_actions(env.scn, rng, env.E)
+
+
+def agent_policies(scn, rng, E):
+    """Random fingerprints, float32 [E, A, a_max], zero behind an agent's own phases: agent after agent, E Dirichlet draws."""
+    pol = np.zeros((E, scn.n_agent, scn.green_tab.shape[1]), np.float32)
+    for a, n in enumerate(scn.n_a_ls):
+        pol[:, a, :n] = rng.dirichlet(np.ones(n), size=E)
+    return pol
+
+
+def change_actions(scn, rng, act, p_change):
+    """In act [E, A]: agent after agent, every instance takes a new uniform phase with probability p_change (E draws for the choice,
+    then one per change)."""
+    for a, n in enumerate(scn.n_a_ls):
+        change = rng.rand(len(act)) < p_change
+        act[change, a] = rng.randint(0, n, int(change.sum()))
+
+
+def policies_and_changes(scn, rng, act, p_change=1.0):
+    """agent_policies and change_actions interleaved -- agent after agent its fingerprints, then its changes -> the fingerprints."""
+    pol = np.zeros((len(act), scn.n_agent, int(scn.green_tab.shape[1])), np.float32)
+    for a, n in enumerate(scn.n_a_ls):
+        pol[:, a, :n] = rng.dirichlet(np.ones(n), size=len(act))
+        change = rng.rand(len(act)) < p_change
+        act[change, a] = rng.randint(0, n, int(change.sum()))
+    return pol
+
+
+def mixed_large_grid(rng, obs, p_random):
+    """large_grid: fingerprints float32 [E, 25, 5] in one Dirichlet draw, then instance after instance and agent after agent a uniform
+    phase with probability p_random[e], else oracle.env_oracle.greedy_large_grid on the oracle's observation -> (actions, fingerprints)."""
+    from oracle.env_oracle import greedy_large_grid
+    E = len(obs)
+    pol = rng.dirichlet(np.ones(5), size=(E, 25)).astype(np.float32)
+    act = np.zeros((E, 25), np.int32)
+    for e in range(E):
+        for a in range(25):
+            act[e, a] = rng.randint(5) if rng.rand() < p_random[e] else greedy_large_grid(obs[e][a][:6])
+    return act, pol
+
+
+def green_lanes(scn):
+    """Per agent and phase the positions (in the agent's lane list = its first observation entries) of the lanes with a 'G' link."""
+    out = []
+    for a in range(scn.n_agent):
+        lanes = [int(x) for x in scn.agent_lanes[a, :scn.agent_nlane[a]]]
+        out.append([sorted({lanes.index(int(scn.link_lane[a, k])) for k in range(int(scn.agent_nlink[a]))
+                            if scn.green_tab[a, p, k] == ord('G') and scn.link_lane[a, k] >= 0}) for p in range(int(scn.agent_nphase[a]))])
+    return out
+
+
+def draw_actions(scn, greens, rng, p_random, obs):
+    """One instance's actions of a control step: per agent a random phase with probability p_random, else the phase whose green lanes
+    hold the largest wave (first maximum); obs: the oracle's observation list.  The draws do not depend on the observations."""
+    act = np.zeros(scn.n_agent, np.int32)
+    rnd = rng.rand(scn.n_agent) < p_random
+    pick = rng.randint(0, 1 << 30, scn.n_agent)
+    for a in range(scn.n_agent):
+        if rnd[a]:
+            act[a] = pick[a] % scn.n_a_ls[a]
+        else:
+            act[a] = int(np.argmax([sum(float(obs[a][j]) for j in g) for g in greens[a]]))
+    return act
+
+
+def draw_policy(scn, rng):
+    """A random policy per agent (the fingerprints of MA2C) of one instance, float32 [A, a_max], zero behind an agent's own phases."""
+    a_max = int(scn.green_tab.shape[1])
+    pol = np.zeros((scn.n_agent, a_max), np.float32)
+    for a, n in enumerate(scn.n_a_ls):
+        pol[a, :n] = rng.dirichlet(np.ones(n)).astype(np.float32)
+    return pol
+
+
+# ---- the comparisons --------------------------------------------------------------------------------------------------------------
+def assert_step_equal(scn, t, out, res):
+    """out: what the handle's step returned, as numpy arrays (observations [E, A, s_max], rewards [E, A], done [E], global_reward [E]);
+    res: per instance what OracleEnv.step returned."""
+    o, r, d, g = out
+    for e, (oo, orr, od, og) in _items(res):
+        for a in range(scn.n_agent):
+            n = len(oo[a])                  # n_s_ls[a]; the greedy controller's observation is its waves alone, on both sides
+            assert n == scn.n_s_ls[a] or scn.agent == 'greedy', 'obs t=%d e=%d a=%d: %d entries' % (t, e, a, n)
+            np.testing.assert_array_equal(o[e, a, :n], oo[a].astype(np.float32), err_msg='obs t=%d e=%d a=%d' % (t, e, a))
+        np.testing.assert_array_equal(r[e], np.asarray(orr, np.float64), err_msg='reward t=%d e=%d' % (t, e))
+        assert g[e] == og, 'global_reward t=%d e=%d: %r != %r' % (t, e, g[e], og)
+        assert bool(d[e]) == bool(od), 'done t=%d e=%d: %r != %r' % (t, e, d[e], od)
+
+
+def assert_state_equal(env, ref, instances, t=-1):
+    """The vehicle state of the listed instances of a handle against ref: the oracles (per instance, ms.snapshot()) or another handle."""
+    for e in instances:
+        st, sn = env.get_state(e), ref.get_state(e) if hasattr(ref, 'get_state') else ref[e].ms.snapshot()
+        for k in STATE_KEYS:
+            np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s t=%d e=%d' % (k, t, e))
+
+
+def assert_counters_equal(env, orc, t=-1):
+    """counters() of the handle against ms.totals() of the oracles -> the totals, per oracle."""
+    arrived, teleported = env.counters()
+    tot = [o.ms.totals() for _, o in _items(orc)]
+    for (e, _), x in zip(_items(orc), tot):
+        assert (int(arrived[e]), int(teleported[e])) == (x['arrived'], x['teleported']), 'counters t=%d e=%d: %r' % (t, e, x)
+    return tot
+
+
+def assert_tables_equal(a, b):
+    """The four record tables of two recording handles."""
+    a.collect_tripinfo(); b.collect_tripinfo()
+    for k in RECORD_TABLES:
+        assert getattr(a, k) == getattr(b, k), k
+
+
+def assert_same(a, b):
+    """Two lists of arrays (episode_outputs)."""
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        np.testing.assert_array_equal(x, y)
+
+
+# ---- a handle beside its oracles --------------------------------------------------------------------------------------------------
+def oracle_steps(scn, orc, obs, steps, draw):
+    """The oracle's side of a walk.  orc: the OracleEnvs, a list (every instance) or a dict (the watched ones), already reset; obs:
+    their reset observations, kept up to date in place.  draw(t, obs) -> (actions [E, A], fingerprints [E, A, a_max] or None); the
+    actions are an int32 array, or a tensor where the handle chooses them (env.greedy_actions()).  Generator: per control step
+    (t, actions and fingerprints as drawn, the results of OracleEnv.step per instance, orc), so that the handle steps in between."""
+    for t in range(steps):
+        acts, pols = draw(t, obs)
+        act_h = acts.cpu().numpy() if torch.is_tensor(acts) else acts
+        res = obs.copy()
+        for e, o in _items(orc):
+            if pols is not None:
+                o.update_fingerprint([pols[e, a, :n] for a, n in enumerate(scn.n_a_ls)])
+            res[e] = o.step(list(act_h[e]))
+            obs[e] = res[e][0]
+        yield t, acts, pols, res, orc
+
+
+def follow(env, side, state_at=(), state_of=None, counters=False, after=None):
+    """The handle's side: steps `env` (already reset) through the actions and fingerprints of `side` (oracle_steps, or run_oracle past
+    its reset) and compares every step with the oracles'; after the control steps of state_at also the vehicle state of the instances
+    state_of (default: every oracle's), after the last step the counters if asked.  after(t, out, res, orc) is called behind every
+    step's comparison.  -> the oracles."""
+    t = orc = None
+    for t, acts, pols, res, orc in side:
+        if pols is not None:
+            env.update_fingerprint(upload(env, pols))
+        out = [x.cpu().numpy() for x in env.step(upload(env, acts))]
+        assert_step_equal(env.scn, t, out, res)
+        if t in state_at:
+            assert_state_equal(env, orc, [e for e, _ in _items(orc)] if state_of is None else state_of, t)
+        if after is not None:
+            after(t, out, res, orc)
+    assert t is not None, 'no step'
+    if counters:
+        assert_counters_equal(env, orc, t)
+    return orc
+
+
+def with_rates(scn, vph):
+    """scn with the veh/h column vph in place of its own (what instance e of a handle under set_demand runs)."""
+    import dataclasses
+    fl = np.array(scn.flows, np.int32)
+    fl[:, 2] = vph
+    return dataclasses.replace(scn, flows=fl)
+
+
+def demand_parity(scn, E, steps, seed0, vph, watch=None, rng_seed=0, p_random=0.7, p_change=1.0):
+    """A handle of E instances under the veh/h columns vph [E, n_flow] (set_demand) against the oracles of the watched instances
+    (default: all), OracleEnv(with_rates(scn, vph[e])): every step, then the vehicle state and the insertion counters of at most
+    six of them.  Fingerprints and actions: policies_and_changes; on large_grid with p_random < 1 an agent of a watched instance
+    then takes greedy_large_grid with probability 1 - p_random.  -> (the handle, the oracles)."""
+    from deeprl_signal_control_amd.env import VecTrafficEnv
+    from oracle.env_oracle import OracleEnv, greedy_large_grid
+    from tests.env_rules import expected_vehicles
+    watch = list(range(E)) if watch is None else list(watch)
+    env = VecTrafficEnv(scn, E, seed=seed0)
+    env.set_demand(vph)
+    orc = {e: OracleEnv(with_rates(scn, vph[e]), seed=seed0 + e) for e in watch}
+    env.reset()
+    np.testing.assert_array_equal(env.demand(), vph)
+    obs = {e: o.reset() for e, o in orc.items()}
+    rng = np.random.RandomState(rng_seed)
+    act = np.zeros((E, scn.n_agent), np.int32)
+
+    def draw(t, obs):
+        pol = policies_and_changes(scn, rng, act, p_change)
+        if scn.name == 'large_grid' and p_random < 1.0:
+            for e in watch:
+                for a in range(scn.n_agent):
+                    if rng.rand() >= p_random:
+                        act[e, a] = greedy_large_grid(obs[e][a][:6])
+        return act, pol if scn.agent == 'ma2c' else None
+    compared = watch[::max(1, len(watch) // 6)][:6] if len(watch) > 6 else watch
+    follow(env, oracle_steps(scn, orc, obs, steps, draw), state_at=[steps - 1], state_of=compared)
+    for e in compared:
+        st, tot = env.get_state(e), orc[e].ms.totals()
+        assert int(st['serial'].sum()) == tot['departed'] and int(st['pending'].sum()) == tot['pending'], e
+        assert int(st['serial'].sum() + st['pending'].sum()) == expected_vehicles(scn, vph[e], int(st['t'][0])), e
+    return env, orc
+
+
+def eval_seeds(net, E=None):
+    """The test-mode seeds of a case, one per instance (VecTrafficEnv.reset(test_ind=arange(E)))."""
+    return tuple(net.seed + 1000 + e for e in range(net.E if E is None else E))
+
+
+def run_oracle(scn, net, on_second=None, train_mode=True, is_record=False, E=None):
+    """The oracle's side of a case of tests/networks.py: E OracleEnvs with seeds net.seed + e (test mode: eval_seeds(net)[e]), the
+    actions of draw_actions from one RandomState(net.seed).  Generator: first (-1, None, None, the reset observations [E], the
+    OracleEnvs), then oracle_steps.  on_second(e, ms): called after every simulated second of instance e."""
+    from oracle.env_oracle import OracleEnv
+    E = net.E if E is None else E
+    orc = [OracleEnv(scn, seed=net.seed + e, test_seeds=eval_seeds(net, E), train_mode=train_mode, is_record=is_record) for e in range(E)]
+    if on_second is not None:
+        for e, o in enumerate(orc):
+            def stepper(n=1, _ms=o.ms, _e=e, _step=o.ms.step):
+                for _ in range(n):
+                    _step(1)
+                    on_second(_e, _ms)
+            o.ms.step = stepper
+    obs = [o.reset(test_ind=e) for e, o in enumerate(orc)]
+    yield -1, None, None, obs, orc
+    greens, rng = green_lanes(scn), np.random.RandomState(net.seed)
+
+    def draw(t, obs):
+        acts = np.stack([draw_actions(scn, greens, rng, net.p_random, obs[e]) for e in range(E)])
+        return acts, np.stack([draw_policy(scn, rng) for e in range(E)]) if scn.agent == 'ma2c' else None
+    yield from oracle_steps(scn, orc, list(obs), net.steps, draw)
+
+
+# ---- several handles under the same actions ---------------------------------------------------------------------------------------
+def recording_pair(scn, E, seed=5):
+    """Two recording handles of the same seeds."""
+    from deeprl_signal_control_amd.env import VecTrafficEnv
+    envs = []
+    for _ in range(2):
+        env = VecTrafficEnv(scn, E, seed=seed)
+        env.set_record(True)
+        envs.append(env)
+    return envs
+
+
+def lockstep(envs, steps, draw, state_of=(), tables=False, before=None):
+    """The same actions, and fingerprints where draw gives them, into every handle of envs (already reset): draw(t) -> (actions,
+    fingerprints or None), arrays or tensors; before(t) is called ahead of the draw.  Everything step returns is equal among the
+    handles at every step; afterwards the vehicle state of the instances state_of and, if asked, the record tables.
+    -> per step what the first handle returned, as numpy arrays."""
+    first = []
+    for t in range(steps):
+        if before is not None:
+            before(t)
+        acts, pols = draw(t)
+        outs = []
+        for env in envs:
+            if pols is not None:
+                env.update_fingerprint(upload(env, pols))
+            outs.append([x.cpu().numpy().copy() for x in env.step(upload(env, acts))])
+        for k, other in enumerate(outs[1:]):
+            for name, x, y in zip(('obs', 'reward', 'done', 'global_reward'), outs[0], other):
+                assert x.dtype == y.dtype, (name, t)
+                np.testing.assert_array_equal(x, y, err_msg='%s t=%d, handle %d against handle 0' % (name, t, k + 1))
+        first.append(outs[0])
+    for other in envs[1:]:
+        assert_state_equal(envs[0], other, state_of, steps - 1)
+        if tables:
+            assert_tables_equal(envs[0], other)
+    return first
+
+
+def lockstep_uniform(envs, scn, rng, E, steps, tables=False):
+    """lockstep under uniform_actions, without fingerprints."""
+    lockstep(envs, steps, lambda t: (uniform_actions(scn, rng, E), None), tables=tables)
+
+
+def episode_outputs(env, steps, rng_seed, before=None):
+    """One episode of one handle under policies_and_changes from RandomState(rng_seed): the reset observations, then per step
+    observations, rewards and global_reward, then every instance's state, as one list of arrays (assert_same)."""
+    scn, E = env.scn, env.E
+    rng = np.random.RandomState(rng_seed)
+    act = np.zeros((E, scn.n_agent), np.int32)
+    out = [env.reset().cpu().numpy().copy()]
+    for o, r, _, g in lockstep([env], steps, lambda t: (act, policies_and_changes(scn, rng, act)), before=before):
+        out += [o, r, g]
+    for e in range(E):
+        st = env.get_state(e)
+        out += [st[k] for k in STATE_KEYS + ('pending', 'serial')]
+    return out
+
+
+# ---- the recording walks of tests/networks.py (AUX['walk']) -----------------------------------------------------------------------
+class WalkOracles:
+    """The oracle's side of a walk case: one snapshot oracle (every lane's vehicles after every simulated second) per watched
+    instance, seed case.seed + e.  A control interval that does not divide the episode runs the last launch past its end, which the
+    device neither traces nor counts: views() cuts the snapshots at the episode's end and answers totals() as of that second."""
+
+    def __init__(self, case):
+        self.case, self.scn = case, case.scenario()
+        self.T = int(self.scn.episode_length_sec)
+        self.orc = {e: snapshot_oracle(self.scn, case.seed + e) for e in case.watch}
+        self.at_end = {}
+        for e, o in self.orc.items():
+            def stepper(n=1, _o=o, _e=e, _step=o.ms.step):
+                for _ in range(n):
+                    _step(1)
+                    if len(_o.snaps) + 1 == self.T:         # (the snapshot of this second is appended after the step)
+                        self.at_end[_e] = _o.ms.totals()
+            o.ms.step = stepper
+            o.reset()
+
+    def step(self, acts):
+        for e, o in self.orc.items():
+            o.step(list(acts[e]))
+
+    def views(self):
+        """{e: what env_rules.check_lane_data reads of an oracle: snaps (seconds 0 .. T - 1) and ms.totals()}."""
+        import types
+        out = {}
+        for e, o in self.orc.items():
+            tot = self.at_end.get(e) if len(o.snaps) >= self.T else o.ms.totals()
+            out[e] = types.SimpleNamespace(snaps=o.snaps[:self.T], ms=types.SimpleNamespace(totals=lambda _t=tot: _t))
+        return out
+
+
+def walk_context(case):
+    """The Krauss walk cases run the oracle's Krauss model for the length of the case."""
+    scn = case.scenario()
+    return oracle_krauss(scn.krauss_sigma) if scn.car_following == 'krauss' else contextlib.nullcontext()

@@ -10,7 +10,7 @@ interval, one vehicle per second and stream.  Every network of NETWORKS exists b
 * NETWORKS: name -> Net (factory, the limit it drives, the step plan tsc_env_step_plan must report, and the run: E, control steps,
   share of random actions, seed).
 
-The runs of tests/test_networks_gpu.py are redrawn on the host by run_oracle / draw_actions below, so that tests/test_networks_host.py
+The runs of tests/test_networks_gpu.py are redrawn on the host by run_oracle / draw_actions of tests/env_harness.py, so that tests/test_networks_host.py
 states conditions (the limit is reached, the roads are not empty) about the very runs the GPU tests compare.
 
 The kernels around the step (controllers, pressure reward, recording walks, per-instance demand) run on the same networks: AUX, at the
@@ -22,6 +22,8 @@ import numpy as np
 
 from deeprl_signal_control_amd.scenario import (DET_LEN, MAX_UP, Scenario, _obs_table, _signal_tables, _state_dims, build_large_grid,
                                                 sort_lanes_by_load)
+from tests.env_harness import run_oracle, with_rates         # noqa: F401 (with_rates: under this module's name for the cases' columns)
+from tests.env_rules import greedy_rule
 
 
 # ---------------------------------------------------------------------------
@@ -435,14 +437,6 @@ def demand254_columns(scn, E):
     return cols
 
 
-def with_rates(scn, vph):
-    """scn with the veh/h column vph in place of its own (what instance e of a handle under set_demand runs)."""
-    import dataclasses
-    fl = np.array(scn.flows, np.int32)
-    fl[:, 2] = vph
-    return dataclasses.replace(scn, flows=fl)
-
-
 def split_pieces(scn, cuts):
     """A copy of scn whose lanes named in cuts = {lane name: ascending cut positions in m} are made of len(cuts) + 1 SUMO lanes
     '<name>#0', '<name>#1', ... that each begin at 0: lane_pieces only, which the lane data and the trajectories' SUMO positions
@@ -563,77 +557,6 @@ REFUSED = {
 
 
 # ---------------------------------------------------------------------------
-# the runs
-# ---------------------------------------------------------------------------
-def green_lanes(scn):
-    """Per agent and phase the positions (in the agent's lane list = its first observation entries) of the lanes with a 'G' link."""
-    out = []
-    for a in range(scn.n_agent):
-        lanes = [int(x) for x in scn.agent_lanes[a, :scn.agent_nlane[a]]]
-        out.append([sorted({lanes.index(int(scn.link_lane[a, k])) for k in range(int(scn.agent_nlink[a]))
-                            if scn.green_tab[a, p, k] == ord('G') and scn.link_lane[a, k] >= 0}) for p in range(int(scn.agent_nphase[a]))])
-    return out
-
-
-def draw_actions(scn, greens, rng, p_random, obs):
-    """One instance's actions of a control step: per agent a random phase with probability p_random, else the phase whose green lanes
-    hold the largest wave (first maximum); obs: the oracle's observation list.  The draws do not depend on the observations."""
-    act = np.zeros(scn.n_agent, np.int32)
-    rnd = rng.rand(scn.n_agent) < p_random
-    pick = rng.randint(0, 1 << 30, scn.n_agent)
-    for a in range(scn.n_agent):
-        if rnd[a]:
-            act[a] = pick[a] % scn.n_a_ls[a]
-        else:
-            act[a] = int(np.argmax([sum(float(obs[a][j]) for j in g) for g in greens[a]]))
-    return act
-
-
-def draw_policy(scn, rng):
-    """A random policy per agent (the fingerprints of MA2C), float32 [A, a_max], zero behind an agent's own phases."""
-    a_max = int(scn.green_tab.shape[1])
-    pol = np.zeros((scn.n_agent, a_max), np.float32)
-    for a, n in enumerate(scn.n_a_ls):
-        pol[a, :n] = rng.dirichlet(np.ones(n)).astype(np.float32)
-    return pol
-
-
-def eval_seeds(net, E=None):
-    """The test-mode seeds of a case, one per instance (VecTrafficEnv.reset(test_ind=arange(E)))."""
-    return tuple(net.seed + 1000 + e for e in range(net.E if E is None else E))
-
-
-def run_oracle(scn, net, on_second=None, train_mode=True, is_record=False, E=None):
-    """The oracle's side of a case: E OracleEnvs with seeds net.seed + e (test mode: eval_seeds(net)[e]), the actions of draw_actions
-    from one RandomState(net.seed).  Generator: first (-1, None, None, the reset observations [E], the OracleEnvs), then per control
-    step (t, acts [E, A], pols [E, A, a_max] or None, the results [E] of OracleEnv.step, the OracleEnvs), so that the GPU test steps
-    its environment in between.  on_second(e, ms): called after every simulated second of instance e."""
-    from oracle.env_oracle import OracleEnv
-    E = net.E if E is None else E
-    orc = [OracleEnv(scn, seed=net.seed + e, test_seeds=eval_seeds(net, E), train_mode=train_mode, is_record=is_record) for e in range(E)]
-    if on_second is not None:
-        for e, o in enumerate(orc):
-            def stepper(n=1, _ms=o.ms, _e=e, _step=o.ms.step):
-                for _ in range(n):
-                    _step(1)
-                    on_second(_e, _ms)
-            o.ms.step = stepper
-    obs = [o.reset(test_ind=e) for e, o in enumerate(orc)]
-    yield -1, None, None, obs, orc
-    greens, rng = green_lanes(scn), np.random.RandomState(net.seed)
-    for t in range(net.steps):
-        acts = np.stack([draw_actions(scn, greens, rng, net.p_random, obs[e]) for e in range(E)])
-        pols = np.stack([draw_policy(scn, rng) for e in range(E)]) if scn.agent == 'ma2c' else None
-        res = []
-        for e, o in enumerate(orc):
-            if pols is not None:
-                o.update_fingerprint([pols[e, a, :n] for a, n in enumerate(scn.n_a_ls)])
-            res.append(o.step(list(acts[e])))
-            obs[e] = res[-1][0]
-        yield t, acts, pols, res, orc
-
-
-# ---------------------------------------------------------------------------
 # the kernels around the step: controllers, pressure reward, recording walks, per-instance demand
 # ---------------------------------------------------------------------------
 _aux_scn = {}
@@ -684,7 +607,7 @@ class Aux:
 
 
 # E, steps, seeds and actions of the runs below are run_oracle's (train mode: instance e runs seed net.seed + e); the walks draw their
-# own actions (walk_actions) from RandomState(rng_seed) and run the train-mode seeds seed + e.
+# own actions (uniform_actions) from RandomState(rng_seed) and run the train-mode seeds seed + e.
 AUX = {
     # pressure_kernel against loop_pressure, both measures.  isolated_130: 260 walked lanes (chunk 2); isolated_300: 600 walked lanes
     # (chunk 3), 300 agents and 600 (agent, phase) pairs; grid_x4: 664 walked lanes (chunk 3), 1104 movements (five rounds of zeroing)
@@ -729,34 +652,6 @@ def walk_steps(case):
     return -(-int(scn.episode_length_sec) // int(scn.control_interval_sec)) if case.steps is None else case.steps
 
 
-def walk_actions(scn, rng, E):
-    """One control step's actions of a walk case, int32 [E, A]: agent after agent, E uniform draws among its phases."""
-    act = np.zeros((E, scn.n_agent), np.int32)
-    for a, n in enumerate(scn.n_a_ls):
-        act[:, a] = rng.randint(0, n, E)
-    return act
-
-
-def greedy_rule(tables, ob):
-    """The greedy controller's rule as Scenario.greedy_controller_tables states it, for one agent: tables = (its term rows [GC, GT],
-    its action row [GC], its candidate count), ob its float64 observation.  Per candidate the terms are added in table order, in
-    float64, from 0.0; the first maximum wins.  -> (action, flows)."""
-    term, action, n_cand = tables
-    flows = []
-    for c in range(int(n_cand)):
-        flow = 0.0
-        for j in term[c]:
-            if j < 0:
-                break
-            flow = flow + float(ob[j])
-        flows.append(flow)
-    best = 0
-    for c in range(1, len(flows)):
-        if flows[c] > flows[best]:
-            best = c
-    return int(action[best]), flows
-
-
 # the exhaustive check of greedy_kernel's float32 -> float64 recovery: agent 0 of merge4, every tuple of 0 .. 8 vehicles on its four
 # lanes.  Under the registry's phases the first candidate ('GGGG') holds every lane and always wins, and candidates of two lanes each
 # can only tie on the same two addends; here one lane alone comes first and pairs follow, so that 3 / 5 against 1 / 5 + 2 / 5 -- a tie
@@ -789,47 +684,3 @@ def greedy_exhaustive(norm, clip):
             flows.append(f)
         naive32[i] = action[0][int(np.argmax(flows))]
     return scn, counts, ob32, want, naive64, naive32
-
-
-class WalkOracles:
-    """The oracle's side of a walk case: one snapshot oracle (tests.test_trace_gpu._snapshot_oracle: every lane's vehicles after
-    every simulated second) per watched instance, seed case.seed + e.  A control interval that does not divide the episode runs
-    the last launch past its end, which the device neither traces nor counts: views() cuts the snapshots at the episode's end and
-    answers totals() as of that second."""
-
-    def __init__(self, case):
-        from tests.test_trace_gpu import _snapshot_oracle
-        self.case, self.scn = case, case.scenario()
-        self.T = int(self.scn.episode_length_sec)
-        self.orc = {e: _snapshot_oracle(self.scn, case.seed + e) for e in case.watch}
-        self.at_end = {}
-        for e, o in self.orc.items():
-            def stepper(n=1, _o=o, _e=e, _step=o.ms.step):
-                for _ in range(n):
-                    _step(1)
-                    if len(_o.snaps) + 1 == self.T:         # (the snapshot of this second is appended after the step)
-                        self.at_end[_e] = _o.ms.totals()
-            o.ms.step = stepper
-            o.reset()
-
-    def step(self, acts):
-        for e, o in self.orc.items():
-            o.step(list(acts[e]))
-
-    def views(self):
-        """{e: what tests.test_lane_data_gpu._check reads of an oracle: snaps (seconds 0 .. T - 1) and ms.totals()}."""
-        import types
-        out = {}
-        for e, o in self.orc.items():
-            tot = self.at_end.get(e) if len(o.snaps) >= self.T else o.ms.totals()
-            out[e] = types.SimpleNamespace(snaps=o.snaps[:self.T], ms=types.SimpleNamespace(totals=lambda _t=tot: _t))
-        return out
-
-
-def walk_context(case):
-    """The Krauss walk cases run the oracle's Krauss model (a switch of the oracle library) for the length of the case."""
-    import contextlib
-    if case.scenario().car_following == 'krauss':
-        from tests.test_krauss_gpu import oracle_krauss
-        return oracle_krauss(case.scenario().krauss_sigma)
-    return contextlib.nullcontext()

@@ -2,18 +2,17 @@
 against the CPU oracle: instance e of a handle runs its own veh/h column, its oracle is OracleEnv(replace(scn, flows=flows_e)), and
 observations, rewards and the vehicle state are equal bit for bit -- on every scenario, every workgroup size, the Krauss walk and
 the recording / trace / lane-data walks; the nominal column is the handle's old behaviour; errors change nothing."""
-import dataclasses
-
 import numpy as np
 import pytest
-import torch
 
 from deeprl_signal_control_amd.scenario import DemandSampler, build_large_grid, build_real_net, build_small_grid
+from tests import env_harness as H
+from tests.env_harness import assert_same as _same, demand_parity, episode_outputs as _episode, with_rates
+from tests.env_rules import check_trace, expected_vehicles
 
 pytestmark = pytest.mark.gpu
 
 SCALES = (0.5, 0.75, 1.0, 1.25, 1.5, 2.0)
-STATE_KEYS = ('n', 'x', 'v', 'sf', 'w', 'r')
 
 
 def _columns(scn, E, jitter=0.2, scales=SCALES):
@@ -26,80 +25,6 @@ def _columns(scn, E, jitter=0.2, scales=SCALES):
     return np.stack(rows)
 
 
-def _with_rates(scn, vph):
-    fl = np.array(scn.flows, np.int32)
-    fl[:, 2] = vph
-    return dataclasses.replace(scn, flows=fl)
-
-
-def _oracle(scn, vph, seed, **kw):
-    from oracle.env_oracle import OracleEnv
-    return OracleEnv(_with_rates(scn, vph), seed=seed, **kw)
-
-
-def _expected_vehicles(scn, vph, seconds):
-    """Vehicles the integer rule emits in seconds [0, seconds): element f has emitted ceil(tau vph / 3600) after tau seconds."""
-    b, en = scn.flows[:, 0].astype(np.int64), scn.flows[:, 1].astype(np.int64)
-    tau = np.clip(np.minimum(en, seconds) - b, 0, None)
-    return int(((tau * vph.astype(np.int64) + 3599) // 3600).sum())
-
-
-def _act_pol(scn, rng, E, act, p_change=1.0):
-    """Random fingerprints and random actions (an agent keeps its phase with probability 1 - p_change)."""
-    amax = int(scn.green_tab.shape[1])
-    pol = np.zeros((E, scn.n_agent, amax), np.float32)
-    for a, n in enumerate(scn.n_a_ls):
-        pol[:, a, :n] = rng.dirichlet(np.ones(n), size=E)
-        change = rng.rand(E) < p_change
-        act[change, a] = rng.randint(0, n, int(change.sum()))
-    return pol
-
-
-def _parity(scn, E, steps, seed0, vph, watch=None, rng_seed=0, p_random=0.7, p_change=1.0, env=None):
-    """E instances under vph against the oracles of the watched ones (default: all): obs / reward / global reward / done at every
-    step, the vehicle state and the insertion counters at the end.  Returns (env, oracles)."""
-    from deeprl_signal_control_amd.env import VecTrafficEnv
-    from oracle.env_oracle import greedy_large_grid
-    watch = list(range(E)) if watch is None else list(watch)
-    if env is None:
-        env = VecTrafficEnv(scn, E, seed=seed0)
-        env.set_demand(vph)
-    orc = {e: _oracle(scn, vph[e], seed0 + e) for e in watch}
-    env.reset()
-    np.testing.assert_array_equal(env.demand(), vph)
-    oobs = {e: o.reset() for e, o in orc.items()}
-    rng = np.random.RandomState(rng_seed)
-    act = np.zeros((E, scn.n_agent), np.int32)
-    A = scn.n_agent
-    for t in range(steps):
-        pol = _act_pol(scn, rng, E, act, p_change)
-        if scn.name == 'large_grid' and p_random < 1.0:            # mixed random / greedy, as tests/test_env_gpu.py
-            for e in watch:
-                for a in range(A):
-                    if rng.rand() >= p_random:
-                        act[e, a] = greedy_large_grid(oobs[e][a][:6])
-        if scn.agent == 'ma2c':
-            env.update_fingerprint(torch.from_numpy(pol).cuda())
-        o, r, d, g = env.step(torch.from_numpy(act).cuda())
-        o, r, d, g = o.cpu().numpy(), r.cpu().numpy(), d.cpu().numpy(), g.cpu().numpy()
-        for e in watch:
-            if scn.agent == 'ma2c':
-                orc[e].update_fingerprint([pol[e, a, :n] for a, n in enumerate(scn.n_a_ls)])
-            oo, orr, od, og = orc[e].step(list(act[e]))
-            oobs[e] = oo
-            for a in range(A):
-                np.testing.assert_array_equal(o[e, a, :scn.n_s_ls[a]], oo[a].astype(np.float32), err_msg='t=%d e=%d a=%d' % (t, e, a))
-            np.testing.assert_array_equal(r[e], orr, err_msg='t=%d e=%d' % (t, e))
-            assert g[e] == og and bool(d[e]) == bool(od), (t, e)
-    for e in watch[::max(1, len(watch) // 6)][:6] if len(watch) > 6 else watch:
-        st, sn, tot = env.get_state(e), orc[e].ms.snapshot(), orc[e].ms.totals()
-        for k in STATE_KEYS:
-            np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s e=%d' % (k, e))
-        assert int(st['serial'].sum()) == tot['departed'] and int(st['pending'].sum()) == tot['pending'], e
-        assert int(st['serial'].sum() + st['pending'].sum()) == _expected_vehicles(scn, vph[e], int(st['t'][0])), e
-    return env, orc
-
-
 # ---- 1. parity with the oracle, large_grid MA2C ---------------------------------------------------------------------------
 @pytest.mark.parametrize('E,steps,threads', [(24, 150, '256'), (24, 150, '512'), (24, 150, '1024'), (24, 150, ''), (8, 720, '')])
 def test_large_grid_vs_oracle(E, steps, threads, monkeypatch):
@@ -107,7 +32,7 @@ def test_large_grid_vs_oracle(E, steps, threads, monkeypatch):
         monkeypatch.setenv('TSC_ENV_THREADS', threads)
     scn = build_large_grid('ma2c')
     vph = _columns(scn, E)
-    env, _ = _parity(scn, E, steps, 100, vph, rng_seed=E)
+    env, _ = demand_parity(scn, E, steps, 100, vph, rng_seed=E)
     assert env.mean_live_vehicles() > 50
     env.close()
 
@@ -118,25 +43,20 @@ def test_monaco_vs_oracle(threads, monkeypatch):
     if threads:
         monkeypatch.setenv('TSC_ENV_THREADS', threads)
     scn = build_real_net('ma2c')
-    env, _ = _parity(scn, 12, 400, 300, _columns(scn, 12), rng_seed=4, p_change=0.25)
+    env, _ = demand_parity(scn, 12, 400, 300, _columns(scn, 12), rng_seed=4, p_change=0.25)
     env.close()
 
 
 def test_small_grid_vs_oracle():
     scn = build_small_grid('ma2c')
-    env, _ = _parity(scn, 6, 400, 500, _columns(scn, 6), rng_seed=5, p_change=0.25)
+    env, _ = demand_parity(scn, 6, 400, 500, _columns(scn, 6), rng_seed=5, p_change=0.25)
     env.close()
 
 
 def test_krauss_vs_oracle():
-    from oracle.microsim import lib
     scn = build_large_grid('ma2c', car_following='krauss', krauss_sigma=0.5)
-    L = lib()
-    L.ms_set_krauss(1, 0.5)
-    try:
-        env, _ = _parity(scn, 12, 120, 100, _columns(scn, 12), rng_seed=6)
-    finally:
-        L.ms_set_krauss(0, 0.5)
+    with H.oracle_krauss(0.5):
+        env, _ = demand_parity(scn, 12, 120, 100, _columns(scn, 12), rng_seed=6)
     assert env.car_following() == ('krauss', 0.5)
     env.close()
 
@@ -148,7 +68,7 @@ def test_benchmark_shape_large_grid():
     E = 1024
     watch = sorted([0, E - 1] + [r + 8 * k for r in range(8) for k in (5 + r, 100 + 3 * r)])
     assert len(set(watch)) == 18 and all(sum(e % 8 == r for e in watch[1:-1]) == 2 for r in range(8))
-    env, _ = _parity(scn, E, 120, 100, _columns(scn, E), watch=watch, rng_seed=7, p_random=1.0)
+    env, _ = demand_parity(scn, E, 120, 100, _columns(scn, E), watch=watch, rng_seed=7, p_random=1.0)
     env.close()
 
 
@@ -156,7 +76,7 @@ def test_benchmark_shape_monaco():
     scn = build_real_net('ma2c')
     E = 512
     watch = [0, 73, 138, 203, 268, 333, 398, E - 1]
-    env, _ = _parity(scn, E, 120, 300, _columns(scn, E), watch=watch, rng_seed=8, p_change=0.25)
+    env, _ = demand_parity(scn, E, 120, 300, _columns(scn, E), watch=watch, rng_seed=8, p_change=0.25)
     env.close()
 
 
@@ -175,7 +95,7 @@ def test_vehicle_counts_follow_each_instances_column():
     for e in range(E):
         st = env.get_state(e)
         totals.append(int(st['serial'].sum() + st['pending'].sum()))
-        assert totals[e] == _expected_vehicles(scn, vph[e], scn.episode_length_sec), e
+        assert totals[e] == expected_vehicles(scn, vph[e], scn.episode_length_sec), e
     by_scale = {s: [totals[e] for e in range(E) if SCALES[e % 6] == s] for s in SCALES}
     for lo, hi in zip(SCALES[:-1], SCALES[1:]):                   # jitter 0.2 cannot bridge the gaps between these scales' sums
         assert max(by_scale[lo]) < min(by_scale[hi]), (lo, hi, by_scale)
@@ -183,31 +103,6 @@ def test_vehicle_counts_follow_each_instances_column():
 
 
 # ---- 5. nominal is nominal -----------------------------------------------------------------------------------------------
-def _episode(env, steps, rng_seed, mid=None):
-    """obs / reward per step under a fixed random action sequence (+ the state at the end); mid(t) is called before step t."""
-    scn, E = env.scn, env.E
-    rng = np.random.RandomState(rng_seed)
-    act = np.zeros((E, scn.n_agent), np.int32)
-    out = [env.reset().cpu().numpy().copy()]
-    for t in range(steps):
-        if mid is not None:
-            mid(t)
-        pol = _act_pol(scn, rng, E, act)
-        env.update_fingerprint(torch.from_numpy(pol).cuda())
-        o, r, d, g = env.step(torch.from_numpy(act).cuda())
-        out += [o.cpu().numpy().copy(), r.cpu().numpy().copy(), g.cpu().numpy().copy()]
-    for e in range(E):
-        st = env.get_state(e)
-        out += [st[k] for k in STATE_KEYS + ('pending', 'serial')]
-    return out
-
-
-def _same(a, b):
-    assert len(a) == len(b)
-    for x, y in zip(a, b):
-        np.testing.assert_array_equal(x, y)
-
-
 def test_nominal_is_nominal():
     from deeprl_signal_control_amd.env import VecTrafficEnv
     scn = build_large_grid('ma2c')
@@ -254,7 +149,6 @@ def test_nominal_is_nominal():
 # ---- 6. the recording path -----------------------------------------------------------------------------------------------
 def test_recording_trace_and_lane_data_under_demand():
     from deeprl_signal_control_amd.env import VecTrafficEnv
-    from tests.test_trace_gpu import _check_against_oracle, _snapshot_oracle
     scn = build_large_grid('greedy')
     E, steps, traced, seed0 = 6, 120, [1, 5], 70
     vph = _columns(scn, E)
@@ -265,20 +159,13 @@ def test_recording_trace_and_lane_data_under_demand():
     env.set_lane_data(300)
     orc = []
     for e in range(E):
-        o = _snapshot_oracle(_with_rates(scn, vph[e]), seed0 + e)
+        o = H.snapshot_oracle(with_rates(scn, vph[e]), seed0 + e)
         o.is_record = True
-        o.snaps = []
         orc.append(o)
     env.reset()
-    for o in orc:
-        o.reset()
+    obs = [o.reset() for o in orc]
     rng = np.random.RandomState(9)
-    for t in range(steps):
-        act = torch.from_numpy(rng.randint(0, 5, (E, scn.n_agent)).astype(np.int32)).cuda()
-        env.step(act)
-        a = act.cpu().numpy()
-        for e in range(E):
-            orc[e].step(list(a[e]))
+    H.follow(env, H.oracle_steps(scn, orc, obs, steps, lambda t, obs: (rng.randint(0, 5, (E, scn.n_agent)).astype(np.int32), None)))
     ints, _ = env.read_lane_data()
     from deeprl_signal_control_amd.env import LANEDATA_INTS
     dep = []
@@ -296,7 +183,7 @@ def test_recording_trace_and_lane_data_under_demand():
     assert dep[5] > 2 * dep[0]
     tr = env.collect_trajectories()
     for e in traced:
-        assert _check_against_oracle(scn, tr[e], orc[e].snaps) > 50
+        assert check_trace(scn, tr[e], orc[e].snaps) > 50
     env.close()
 
 

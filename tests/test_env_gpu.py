@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from deeprl_signal_control_amd.scenario import build_large_grid
+from tests import env_harness as H
 
 pytestmark = pytest.mark.gpu
 
@@ -95,37 +96,17 @@ def test_batched_vs_oracle_state(E, steps, p_random, threads, monkeypatch):
     the full vehicle state (positions, speeds, waits, routes) must be identical -- for every workgroup size of the step
     kernel ('' = the library's own choice for this E)."""
     from deeprl_signal_control_amd.env import VecTrafficEnv
-    from oracle.env_oracle import OracleEnv, greedy_large_grid
+    from oracle.env_oracle import OracleEnv
     if threads:
         monkeypatch.setenv('TSC_ENV_THREADS', threads)
     scn = build_large_grid('ma2c')
     env = VecTrafficEnv(scn, E, seed=100)
     orc = [OracleEnv(scn, seed=100 + e) for e in range(E)]
-    obs = env.reset().cpu().numpy()
-    oobs = [o.reset() for o in orc]
+    env.reset()
+    obs = [o.reset() for o in orc]
     rng = np.random.RandomState(E)
-    for t in range(steps):
-        pol = rng.dirichlet(np.ones(5), size=(E, 25)).astype(np.float32)
-        act = np.zeros((E, 25), np.int32)
-        for e in range(E):
-            for a in range(25):
-                act[e, a] = rng.randint(5) if rng.rand() < p_random else greedy_large_grid(oobs[e][a][:6])
-        env.update_fingerprint(torch.from_numpy(pol).cuda())
-        o, r, d, g = env.step(torch.from_numpy(act).cuda())
-        o, r, d, g = o.cpu().numpy(), r.cpu().numpy(), d.cpu().numpy(), g.cpu().numpy()
-        for e in range(E):
-            orc[e].update_fingerprint(list(pol[e]))
-            oo, orr, od, og = orc[e].step(list(act[e]))
-            oobs[e] = oo
-            for a in range(25):
-                np.testing.assert_array_equal(o[e, a, :scn.n_s_ls[a]], oo[a].astype(np.float32),
-                                              err_msg='t=%d e=%d a=%d' % (t, e, a))
-            np.testing.assert_array_equal(r[e], orr, err_msg='t=%d e=%d' % (t, e))
-            assert g[e] == og and bool(d[e]) == bool(od)
-    for e in range(0, E, max(1, E // 6)):
-        st, sn = env.get_state(e), orc[e].ms.snapshot()
-        for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-            np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s e=%d' % (k, e))
+    H.follow(env, H.oracle_steps(scn, orc, obs, steps, lambda t, obs: H.mixed_large_grid(rng, obs, [p_random] * E)),
+             state_at=[steps - 1], state_of=list(range(0, E, max(1, E // 6))))
     assert env.mean_live_vehicles() > 50
     env.close()
 
@@ -166,18 +147,10 @@ def test_helper_threads_equal_plain_walk(monkeypatch):
     oa, ob = a.reset(), b.reset()
     assert torch.equal(oa, ob)
     g = torch.Generator(device='cuda'); g.manual_seed(3)
-    for t in range(400):                                     # random phases: heavy congestion by t = 2000 s
-        act = torch.randint(0, 5, (E, 25), generator=g, device='cuda', dtype=torch.int32)
-        pol = torch.rand(E, 25, 5, generator=g, device='cuda')
-        a.update_fingerprint(pol); b.update_fingerprint(pol)
-        oa, ra, da, ga = a.step(act)
-        ob, rb, db, gb = b.step(act)
-        assert torch.equal(oa, ob) and torch.equal(ra, rb) and torch.equal(ga, gb) and torch.equal(da, db), t
+    # random phases: heavy congestion by t = 2000 s
+    H.lockstep([a, b], 400, lambda t: (torch.randint(0, 5, (E, 25), generator=g, device='cuda', dtype=torch.int32),
+                                       torch.rand(E, 25, 5, generator=g, device='cuda')), state_of=(0, 17, 95))
     assert a.mean_live_vehicles() > 400
-    for e in (0, 17, 95):
-        sa, sb = a.get_state(e), b.get_state(e)
-        for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-            np.testing.assert_array_equal(sa[k], sb[k], err_msg='state %s e=%d' % (k, e))
     a.close(); b.close()
 
 
@@ -199,25 +172,13 @@ def test_flat_phase_super_rounds_at_saturation(kf, spec, threads, monkeypatch):
     env = VecTrafficEnv(scn, E, seed=9)
     orc = [OracleEnv(scn, seed=9 + e) for e in range(E)]
     env.reset()
-    for o in orc:
-        o.reset()
+    obs = [o.reset() for o in orc]
     rng = np.random.RandomState(5)
-    peak = 0.0
-    for t in range(260):
-        act = rng.randint(0, 5, (E, 25)).astype(np.int32)
-        o, r, d, g = env.step(torch.from_numpy(act).cuda())
-        o, r = o.cpu().numpy(), r.cpu().numpy()
-        for e in range(E):
-            oo, orr, _, _ = orc[e].step(list(act[e]))
-            for a in range(25):
-                np.testing.assert_array_equal(o[e, a, :scn.n_s_ls[a]], oo[a].astype(np.float32), err_msg='t=%d e=%d a=%d' % (t, e, a))
-            np.testing.assert_array_equal(r[e], orr, err_msg='t=%d e=%d' % (t, e))
-        peak = max(peak, env.mean_live_vehicles())
+    live = []
+    H.follow(env, H.oracle_steps(scn, orc, obs, 260, lambda t, obs: (rng.randint(0, 5, (E, 25)).astype(np.int32), None)),
+             state_at=[259], after=lambda *_: live.append(env.mean_live_vehicles()))
+    peak = max(live)
     assert peak > 600, peak                      # 256 threads: 3 super-rounds at kF = 1, 2 at kF = 2 (entry lanes cap the inflow)
-    for e in range(E):
-        st, sn = env.get_state(e), orc[e].ms.snapshot()
-        for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-            np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s e=%d' % (k, e))
     env.close()
 
 
@@ -234,13 +195,7 @@ def test_resident_instances_hint_changes_the_launch_shape_not_the_results():
     rng = np.random.RandomState(4)
     for e_ in envs:
         e_.reset()
-    for t in range(40):
-        act = torch.from_numpy(rng.randint(0, 5, (E, 25)).astype(np.int32)).cuda()
-        outs = [e_.step(act) for e_ in envs]
-        assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
-    s0, s1 = envs[0].get_state(5), envs[1].get_state(5)
-    for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-        np.testing.assert_array_equal(s0[k], s1[k])
+    H.lockstep(envs, 40, lambda t: (rng.randint(0, 5, (E, 25)).astype(np.int32), None), state_of=[5])
     for e_ in envs:
         e_.close()
 
@@ -253,7 +208,7 @@ def test_lane_change_rule_vs_oracle(threads, spec, help_, monkeypatch):
     lining up behind the sibling's queue, teleported changers, for every workgroup size, with and without the compile-time
     table dimensions and the flat phase."""
     from deeprl_signal_control_amd.env import VecTrafficEnv
-    from oracle.env_oracle import OracleEnv, greedy_large_grid
+    from oracle.env_oracle import OracleEnv
     monkeypatch.setenv('TSC_ENV_THREADS', threads)
     monkeypatch.setenv('TSC_ENV_SPEC', spec)
     monkeypatch.setenv('TSC_ENV_HELP', help_)
@@ -262,34 +217,12 @@ def test_lane_change_rule_vs_oracle(threads, spec, help_, monkeypatch):
     E = 4
     env = VecTrafficEnv(scn, E, seed=300)
     orc = [OracleEnv(scn, seed=300 + e) for e in range(E)]
-    obs = env.reset().cpu().numpy()
-    oobs = [o.reset() for o in orc]
+    env.reset()
+    obs = [o.reset() for o in orc]
     rng = np.random.RandomState(11)
-    for t in range(720):
-        pol = rng.dirichlet(np.ones(5), size=(E, 25)).astype(np.float32)
-        act = np.zeros((E, 25), np.int32)
-        for e in range(E):
-            for a in range(25):
-                act[e, a] = rng.randint(5) if rng.rand() < 0.1 * e else greedy_large_grid(oobs[e][a][:6])
-        env.update_fingerprint(torch.from_numpy(pol).cuda())
-        o, r, d, g = env.step(torch.from_numpy(act).cuda())
-        o, r, d, g = o.cpu().numpy(), r.cpu().numpy(), d.cpu().numpy(), g.cpu().numpy()
-        for e in range(E):
-            orc[e].update_fingerprint(list(pol[e]))
-            oo, orr, od, og = orc[e].step(list(act[e]))
-            oobs[e] = oo
-            for a in range(25):
-                np.testing.assert_array_equal(o[e, a, :scn.n_s_ls[a]], oo[a].astype(np.float32), err_msg='t=%d e=%d a=%d' % (t, e, a))
-            np.testing.assert_array_equal(r[e], orr, err_msg='t=%d e=%d' % (t, e))
-            assert g[e] == og and bool(d[e]) == bool(od)
-        if t in (299, 719):
-            for e in range(E):
-                st, sn = env.get_state(e), orc[e].ms.snapshot()
-                for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-                    np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s t=%d e=%d' % (k, t, e))
-    arrived, teleported = env.counters()
-    tot = [o.ms.totals() for o in orc]
-    assert [int(x) for x in arrived] == [x['arrived'] for x in tot] and [int(x) for x in teleported] == [x['teleported'] for x in tot]
+    H.follow(env, H.oracle_steps(scn, orc, obs, 720, lambda t, obs: H.mixed_large_grid(rng, obs, [0.1 * e for e in range(E)])),
+             state_at=(299, 719))
+    tot = H.assert_counters_equal(env, orc)
     assert sum(o.ms.lanechange_counts()['changes'] for o in orc) > 2000 and sum(x['teleported'] for x in tot) > 0
     env.close()
 

@@ -11,6 +11,7 @@ import pytest
 
 from deeprl_signal_control_amd.scenario import build_large_grid, build_real_net
 from deeprl_signal_control_amd.trainer import greedy_actions
+from tests.env_rules import check_record_tables as _check
 
 KW = dict(norm_wave=1.0, norm_wait=1.0, clip_wave=1000.0, clip_wait=1000.0, coop_gamma=0.75)
 
@@ -44,22 +45,6 @@ def _run(env, scn):
         if done:
             break
     env.collect_tripinfo()
-
-
-def _check(g, traffic, control, trips):
-    for k in ('episode', 'time_sec', 'number_total_car', 'number_departed_car', 'number_arrived_car'):
-        np.testing.assert_array_equal(np.array([r[k] for r in traffic]), g['traffic_' + k], err_msg=k)
-    for k in ('avg_wait_sec', 'avg_speed_mps', 'std_queue', 'avg_queue'):
-        np.testing.assert_allclose(np.array([r[k] for r in traffic], np.float64), g['traffic_' + k], rtol=1e-12, atol=1e-12, err_msg=k)
-    for k in ('episode', 'time_sec', 'step', 'reward'):
-        np.testing.assert_array_equal(np.array([r[k] for r in control]), g['control_' + k], err_msg=k)
-    assert [r['action'] for r in control] == list(g['control_action'])
-    want = sorted(zip(*(g['trip_' + k] for k in ('arrival_sec', 'id', 'depart_sec', 'duration_sec', 'wait_step', 'wait_sec'))),
-                  key=lambda t: (float(t[0]), t[1]))
-    got = sorted(((r['arrival_sec'], r['id'], r['depart_sec'], r['duration_sec'], r['wait_step'], r['wait_sec']) for r in trips),
-                 key=lambda t: (float(t[0]), t[1]))
-    assert len(got) == len(want) > 100 and got == [tuple(str(x) for x in t) for t in want]
-    assert all(r['episode'] == 1 for r in trips)
 
 
 @pytest.mark.parametrize('name', ['large_grid', 'real_net'])

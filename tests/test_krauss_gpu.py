@@ -3,8 +3,6 @@ Krauss path (ms_set_krauss, MICROSIM_SPEC.md "Krauss car following"): obs, rewar
 every kernel path a Krauss handle can take -- the flat phase at every workgroup size and flat-phase width, the plain walk, the
 recording walk -- and for the scenarios whose vehicles key the dawdling differently (stream != route, drawn routes, merges).
 The oracle's switch is process-wide: every test turns it off again in a `finally`."""
-import contextlib
-import ctypes as C
 import json
 import os
 
@@ -13,27 +11,12 @@ import pytest
 import torch
 
 from deeprl_signal_control_amd.scenario import build_large_grid, build_real_net, build_small_grid
+from tests import env_harness as H
+from tests.env_harness import oracle_krauss
+from tests.env_rules import assert_trips_equal, device_trips
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@contextlib.contextmanager
-def oracle_krauss(sigma):
-    from oracle.microsim import lib
-    L = lib()
-    L.ms_set_krauss(1, float(sigma))
-    try:
-        yield
-    finally:
-        L.ms_set_krauss(0, 0.5)
-
-
-def _random_policy(rng, scn, E):
-    pol = np.zeros((E, scn.n_agent, scn.green_tab.shape[1]), np.float32)
-    for a, n in enumerate(scn.n_a_ls):
-        pol[:, a, :n] = rng.dirichlet(np.ones(n), size=E)
-    return pol
 
 
 def _run_vs_oracle(scn, E, steps, sigma, seed, sample=None, p_change=0.5, rng_seed=0):
@@ -41,35 +24,20 @@ def _run_vs_oracle(scn, E, steps, sigma, seed, sample=None, p_change=0.5, rng_se
     from deeprl_signal_control_amd.env import VecTrafficEnv
     from oracle.env_oracle import OracleEnv
     sample = list(range(E)) if sample is None else list(sample)
-    A = scn.n_agent
     with oracle_krauss(sigma):
         env = VecTrafficEnv(scn, E, seed=seed)
         orc = {e: OracleEnv(scn, seed=seed + e) for e in sample}
         env.reset()
-        for o in orc.values():
-            o.reset()
+        obs = {e: o.reset() for e, o in orc.items()}
         assert env.car_following() == ('krauss', pytest.approx(sigma))
         rng = np.random.RandomState(rng_seed)
-        act = np.zeros((E, A), np.int32)
-        for t in range(steps):
-            pol = _random_policy(rng, scn, E)
-            for a, n in enumerate(scn.n_a_ls):
-                ch = rng.rand(E) < p_change
-                act[ch, a] = rng.randint(0, n, int(ch.sum()))
-            env.update_fingerprint(torch.from_numpy(pol).cuda())
-            o, r, d, g = env.step(torch.from_numpy(act).cuda())
-            o, r, d, g = o.cpu().numpy(), r.cpu().numpy(), d.cpu().numpy(), g.cpu().numpy()
-            for e, oe in orc.items():
-                oe.update_fingerprint([pol[e, a, :n] for a, n in enumerate(scn.n_a_ls)])
-                oo, orr, od, og = oe.step(list(act[e]))
-                for a in range(A):
-                    np.testing.assert_array_equal(o[e, a, :scn.n_s_ls[a]], oo[a].astype(np.float32), err_msg='t=%d e=%d a=%d' % (t, e, a))
-                np.testing.assert_array_equal(r[e], orr, err_msg='t=%d e=%d' % (t, e))
-                assert g[e] == og and bool(d[e]) == bool(od), (t, e)
-        for e, oe in orc.items():
-            st, sn = env.get_state(e), oe.ms.snapshot()
-            for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-                np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s e=%d' % (k, e))
+        act = np.zeros((E, scn.n_agent), np.int32)
+
+        def draw(t, obs):
+            pol = H.agent_policies(scn, rng, E)
+            H.change_actions(scn, rng, act, p_change)
+            return act, pol
+        H.follow(env, H.oracle_steps(scn, orc, obs, steps, draw), state_at=[steps - 1])
         live = env.mean_live_vehicles()
         env.close()
     return live
@@ -121,28 +89,10 @@ def test_krauss_flat_phase_equals_plain_walk(monkeypatch):
     oa, ob = a.reset(), b.reset()
     assert torch.equal(oa, ob)
     g = torch.Generator(device='cuda'); g.manual_seed(3)
-    for t in range(400):
-        act = torch.randint(0, 5, (E, 25), generator=g, device='cuda', dtype=torch.int32)
-        pol = torch.rand(E, 25, 5, generator=g, device='cuda')
-        a.update_fingerprint(pol); b.update_fingerprint(pol)
-        oa, ra, da, ga = a.step(act)
-        ob, rb, db, gb = b.step(act)
-        assert torch.equal(oa, ob) and torch.equal(ra, rb) and torch.equal(ga, gb) and torch.equal(da, db), t
+    H.lockstep([a, b], 400, lambda t: (torch.randint(0, 5, (E, 25), generator=g, device='cuda', dtype=torch.int32),
+                                       torch.rand(E, 25, 5, generator=g, device='cuda')), state_of=(0, 17, 95))
     assert a.mean_live_vehicles() > 400
-    for e in (0, 17, 95):
-        sa, sb = a.get_state(e), b.get_state(e)
-        for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-            np.testing.assert_array_equal(sa[k], sb[k], err_msg='state %s e=%d' % (k, e))
     a.close(); b.close()
-
-
-def _device_trips(env, e):
-    from deeprl_signal_control_amd import _lib
-    cap = 16384
-    buf = np.zeros((cap, 6), np.int32)
-    cnt = C.c_int32()
-    _lib.check(env._L.tsc_env_read_trips(env._h, e, buf.ctypes.data_as(C.c_void_p), cap, C.byref(cnt)))
-    return buf[:min(cnt.value, cap)]
 
 
 def test_recording_under_krauss_trip_table():
@@ -157,22 +107,14 @@ def test_recording_under_krauss_trip_table():
         env.set_record(True)
         orc = [OracleEnv(scn, seed=20 + e, is_record=True) for e in range(E)]
         env.reset()
-        for o in orc:
-            o.reset()
+        obs = [o.reset() for o in orc]
         rng = np.random.RandomState(9)
-        for t in range(360):
-            act = rng.randint(0, 5, (E, 25)).astype(np.int32)
-            _, r, _, g = env.step(torch.from_numpy(act).cuda())
-            g = g.cpu().numpy()
-            for e in range(E):
-                _, _, _, og = orc[e].step(list(act[e]))
-                assert g[e] == og, (t, e)
+        H.follow(env, H.oracle_steps(scn, orc, obs, 360, lambda t, obs: (rng.randint(0, 5, (E, 25)).astype(np.int32), None)))
         for e in range(E):
-            dev = _device_trips(env, e)
+            dev = device_trips(env, e)
             ref = np.array(orc[e].ms.trips(), np.int32).reshape(-1, 6)
             assert len(dev) == len(ref) > 500
-            key = lambda a: a[np.lexsort(a.T[::-1])]
-            np.testing.assert_array_equal(key(dev), key(ref), err_msg='trips e=%d' % e)
+            assert_trips_equal(dev, ref, 'trips e=%d' % e)
             assert len({(int(r_), int(s_)) for r_, s_ in dev[:, :2]}) == len(dev)        # (route, serial) names a vehicle once
         env.close()
 
@@ -191,15 +133,7 @@ def test_explicit_idm_is_the_default():
     assert torch.equal(a.reset(), b.reset())
     assert a.car_following() == b.car_following() == ('idm', 0.0)
     g = torch.Generator(device='cuda'); g.manual_seed(1)
-    for t in range(200):
-        act = torch.randint(0, 5, (E, 25), generator=g, device='cuda', dtype=torch.int32)
-        oa, ra, da, ga = a.step(act)
-        ob, rb, db, gb = b.step(act)
-        assert torch.equal(oa, ob) and torch.equal(ra, rb) and torch.equal(ga, gb) and torch.equal(da, db), t
-    for e in (0, 31):
-        sa, sb = a.get_state(e), b.get_state(e)
-        for k in ('n', 'x', 'v', 'sf', 'w', 'r'):
-            np.testing.assert_array_equal(sa[k], sb[k])
+    H.lockstep([a, b], 200, lambda t: (torch.randint(0, 5, (E, 25), generator=g, device='cuda', dtype=torch.int32), None), state_of=(0, 31))
     a.close(); b.close()
 
 

@@ -9,111 +9,16 @@ import shutil
 import numpy as np
 import pandas as pd
 import pytest
-import torch
 
 from deeprl_signal_control_amd import _lib
 from deeprl_signal_control_amd.scenario import build_large_grid, build_real_net, build_small_grid
-from tests.test_trace_gpu import _actions, _snapshot_oracle
+from tests import env_harness as H
+from tests.env_rules import F, INTS, check_lane_data
 
 pytestmark = pytest.mark.gpu
 
 SCENARIOS = {'large_grid': lambda **kw: build_large_grid('greedy', **kw), 'real_net': lambda **kw: build_real_net('greedy', **kw),
              'small_grid': lambda **kw: build_small_grid('greedy', **kw)}
-INTS = ('sampledSeconds', 'waitingTime', 'departed', 'arrived', 'entered', 'left', 'laneChangedFrom', 'laneChangedTo', 'teleported')
-F = {k: i for i, k in enumerate(INTS)}
-
-
-def _reference(scn, snaps, period):
-    """The lane data of one instance from the oracle's vehicles after every second (snaps[t]: the end of second t), written from
-    the semantics alone: raw per-slot sums ints [n_interval, 9, n_slot] and speed [n_interval, n_slot].  A vehicle's slot is the
-    lane's last piece whose start (float64, cumulated over the pieces before it) is <= x; events compare a vehicle id's slot at
-    the end of t - 1 with its slot at the end of t."""
-    tabs = scn.lane_data_slots()
-    slot0, sumo = tabs['slot0'], tabs['sumo']
-    n_slot, T = int(slot0[-1]), int(scn.episode_length_sec)
-    n_int = -(-T // period)
-    starts = []
-    for ps in scn.lane_pieces:
-        off, st = 0.0, []
-        for _, _, ln in ps:
-            st.append(off)
-            off += ln
-        starts.append(st)
-    sib = None if scn.lane_sib is None else np.asarray(scn.lane_sib)
-    mv_next = np.asarray(scn.mv_next).reshape(scn.n_lane, -1)
-    ints = np.zeros((n_int, len(INTS), n_slot), np.int64)
-    speed = np.zeros((n_int, n_slot), np.float64)
-    halt = np.float32(0.1)
-    prev = {}
-    for t, sn in enumerate(snaps):
-        assert t < T
-        k = t // period
-        lanes = np.repeat(np.arange(scn.n_lane), sn['n'])
-        cur, per_sec = {}, np.zeros(n_slot, np.float64)
-        slots = []
-        for oid, l, x, v, r in zip(sn['id'].tolist(), lanes.tolist(), sn['x'], sn['v'], sn['r'].tolist()):
-            st, j = starts[l], 0
-            while j + 1 < len(st) and float(x) >= st[j + 1]:
-                j += 1
-            s = int(slot0[l]) + j
-            slots.append(s)
-            cur[oid] = (l, s, r)
-            ints[k, F['sampledSeconds'], s] += 1
-            if v < halt:
-                ints[k, F['waitingTime'], s] += 1
-            per_sec[s] += float(v)
-        if len(lanes):                 # the slot's SUMO lane is the one Scenario.sumo_lane_pos (pinned by the FCD tests) names
-            names = np.array(tabs['names'], dtype=object)[sumo[np.array(slots)]]
-            np.testing.assert_array_equal(names, scn.sumo_lane_pos(lanes, sn['x'].astype(np.float64))[0])
-        speed[k] = speed[k] + per_sec
-        for oid, (l, s, r) in cur.items():
-            if oid not in prev:
-                ints[k, F['departed'], s] += 1
-                continue
-            lo, so, _ = prev[oid]
-            if sib is not None and sib[lo] == l:
-                ints[k, F['laneChangedFrom'], so] += 1
-                ints[k, F['laneChangedTo'], s] += 1
-            elif sumo[so] != sumo[s]:
-                ints[k, F['left'], so] += 1
-                ints[k, F['entered'], s] += 1
-        for oid, (lo, so, r) in prev.items():
-            if oid not in cur:
-                ints[k, F['arrived' if mv_next[lo, r] == -1 else 'teleported'], so] += 1
-        prev = cur
-    return ints, speed
-
-
-def _merge_reference(scn, ints, speed):
-    """Per SUMO lane (by name): integer sums and the speed sums added in slot order from 0.0, [n_interval, n_sumo_lane]."""
-    tabs = scn.lane_data_slots()
-    names = tabs['names']
-    out_i = np.zeros((ints.shape[0], len(INTS), len(names)), np.int64)
-    out_s = np.zeros((ints.shape[0], len(names)), np.float64)
-    for s, j in enumerate(tabs['sumo'].tolist()):
-        out_i[:, :, j] += ints[:, :, s]
-        out_s[:, j] = out_s[:, j] + speed[:, s]
-    return out_i, out_s
-
-
-def _check(scn, env, orc, period):
-    ints, speed = env.read_lane_data()
-    cols = env.collect_lane_data()
-    n_sumo = len(scn.lane_data_slots()['names'])
-    for e, o in orc.items():
-        ri, rs = _reference(scn, o.snaps, period)
-        assert ri.sum() > 0
-        np.testing.assert_array_equal(ints[e], ri, err_msg='instance %d' % e)
-        np.testing.assert_array_equal(speed[e].view(np.uint64), rs.view(np.uint64), err_msg='instance %d' % e)
-        mi, ms = _merge_reference(scn, ri, rs)
-        for f, k in enumerate(INTS):
-            np.testing.assert_array_equal(cols[e][k].reshape(-1, n_sumo), mi[:, f, :], err_msg='%s, instance %d' % (k, e))
-        np.testing.assert_array_equal(cols[e]['speed_sum'].reshape(-1, n_sumo).view(np.uint64), ms.view(np.uint64))
-        # the oracle's own counters: the test's classification of the disappearances is the simulator's
-        tot = o.ms.totals()
-        assert ri[:, F['arrived']].sum() == tot['arrived'], (e, tot)
-        assert ri[:, F['teleported']].sum() == tot['teleported'], (e, tot)
-    return {e: {k: int(ints[e, :, f].sum()) for f, k in enumerate(INTS)} for e in orc}
 
 
 def _run(scn, E, steps, instances, policy, period=60, seed=21, rng_seed=0):
@@ -121,18 +26,12 @@ def _run(scn, E, steps, instances, policy, period=60, seed=21, rng_seed=0):
     env = VecTrafficEnv(scn, E, seed=seed)
     env.set_record(True)
     env.set_lane_data(period)
-    orc = {e: _snapshot_oracle(scn, seed + e) for e in instances}
+    orc = {e: H.snapshot_oracle(scn, seed + e) for e in instances}
     env.reset()
-    for o in orc.values():
-        o.reset()
+    obs = {e: o.reset() for e, o in orc.items()}
     rng = np.random.RandomState(rng_seed)
-    for _ in range(steps):
-        act = _actions(env, scn, rng, policy, E)
-        env.step(act)
-        a = act.cpu().numpy()
-        for e, o in orc.items():
-            o.step(list(a[e]))
-    sums = _check(scn, env, orc, period)
+    H.follow(env, H.oracle_steps(scn, orc, obs, steps, lambda t, obs: (H.policy_actions(env, rng, policy), None)))
+    sums = check_lane_data(scn, env, orc, period)
     ints, _ = env.read_lane_data()                                  # (the instances the oracle did not run have sums too)
     assert (ints[:, :, F['sampledSeconds']].sum(axis=(1, 2)) > 0).all()
     env.close()
@@ -153,15 +52,10 @@ def test_lane_data_matches_oracle(name, policy):
 
 @pytest.mark.parametrize('threads', ['256', '1024'])
 def test_lane_data_matches_oracle_krauss(threads, monkeypatch):
-    from oracle.microsim import lib
     monkeypatch.setenv('TSC_ENV_THREADS', threads)
     scn = build_large_grid('greedy', car_following='krauss', krauss_sigma=0.5)
-    L = lib()
-    L.ms_set_krauss(1, 0.5)
-    try:
+    with H.oracle_krauss(0.5):
         sums = _run(scn, 8, 60, list(range(8)), 'random')
-    finally:
-        L.ms_set_krauss(0, 0.5)
     assert min(s['departed'] for s in sums.values()) > 50
 
 
@@ -186,7 +80,7 @@ def test_lane_data_consistency():
     rng = np.random.RandomState(1)
     steps = 120
     for _ in range(steps):
-        env.step(_actions(env, scn, rng, 'random', E))
+        env.step(H.upload(env, H.uniform_actions(scn, rng, E)))
     T = steps * scn.control_interval_sec
     n_int = T // period
     cols = env.collect_lane_data()
@@ -222,7 +116,7 @@ def test_lane_data_consistency():
             np.testing.assert_array_equal(c['sampledSeconds'][k], np.bincount(lane_of[secs], minlength=n_sumo))
     env.reset()
     for _ in range(2):
-        env.step(_actions(env, scn, rng, 'random', E))
+        env.step(H.upload(env, H.uniform_actions(scn, rng, E)))
     cols = env.collect_lane_data()
     for e in range(E):
         s = np.asarray(cols[e]['sampledSeconds']).reshape(-1, n_sumo)
@@ -231,45 +125,18 @@ def test_lane_data_consistency():
     env.close()
 
 
-def _pair(scn, E, seed=5):
-    from deeprl_signal_control_amd.env import VecTrafficEnv
-    envs = []
-    for _ in range(2):
-        env = VecTrafficEnv(scn, E, seed=seed)
-        env.set_record(True)
-        envs.append(env)
-    return envs
-
-
-def _step_both(envs, scn, rng, E, steps):
-    for _ in range(steps):
-        act = np.zeros((E, scn.n_agent), np.int32)
-        for a, n in enumerate(scn.n_a_ls):
-            act[:, a] = rng.randint(0, n, E)
-        outs = [[x.cpu().numpy().copy() for x in env.step(torch.from_numpy(act).cuda())] for env in envs]
-        for x, y in zip(*outs):
-            np.testing.assert_array_equal(x, y)
-
-
-def _tables_equal(a, b):
-    a.collect_tripinfo(); b.collect_tripinfo()
-    for k in ('traffic_data', 'control_data', 'trip_data', 'truncated_trip_data'):
-        assert getattr(a, k) == getattr(b, k), k
-
-
 @pytest.mark.parametrize('with_trace', [False, True])
 def test_lane_data_only_observes(with_trace):
     scn = build_real_net('greedy')
     E = 8
-    measured, plain = _pair(scn, E)
+    measured, plain = H.recording_pair(scn, E)
     if with_trace:
         measured.set_trace([1, 6])
     measured.set_lane_data(300)
     for env in (measured, plain):
         env.reset()
     rng = np.random.RandomState(3)
-    _step_both([measured, plain], scn, rng, E, 80)
-    _tables_equal(measured, plain)
+    H.lockstep_uniform([measured, plain], scn, rng, E, 80, tables=True)
     assert all(np.asarray(c['sampledSeconds']).sum() > 0 for c in measured.collect_lane_data().values())
     if with_trace:
         assert all(len(v['time_sec']) > 0 for v in measured.collect_trajectories().values())
@@ -281,8 +148,7 @@ def test_lane_data_only_observes(with_trace):
     with pytest.raises(RuntimeError, match='no lane data'):
         _lib.check(measured._L.tsc_env_read_lane_data(measured._h, one_i.ctypes.data_as(C.POINTER(C.c_int32)),
                                                       one_d.ctypes.data_as(C.POINTER(C.c_double))))
-    _step_both([measured, plain], scn, rng, E, 20)
-    _tables_equal(measured, plain)
+    H.lockstep_uniform([measured, plain], scn, rng, E, 20, tables=True)
     for env in (measured, plain):
         env.close()
 
@@ -310,12 +176,12 @@ def test_lane_data_refused_rearm_keeps_handle():
     """A re-arming call the library refuses changes nothing: the handle goes on as one that never saw it."""
     scn = build_large_grid('greedy')
     E = 2
-    bad, good = _pair(scn, E)
+    bad, good = H.recording_pair(scn, E)
     for env in (bad, good):
         env.set_lane_data(60)
         env.reset()
     rng = np.random.RandomState(2)
-    _step_both([bad, good], scn, rng, E, 2)                          # the lane data is live when the bad call comes
+    H.lockstep_uniform([bad, good], scn, rng, E, 2)                          # the lane data is live when the bad call comes
     tabs = scn.lane_data_slots()
     ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
     with pytest.raises(RuntimeError, match='bad slot tables'):
@@ -323,7 +189,7 @@ def test_lane_data_refused_rearm_keeps_handle():
                                             tabs['start'].ctypes.data_as(fp), tabs['sumo'].ctypes.data_as(ip)))
     for env in (bad, good):
         env.reset()
-    _step_both([bad, good], scn, rng, E, 4)
+    H.lockstep_uniform([bad, good], scn, rng, E, 4)
     (ints_b, speed_b), (ints_g, speed_g) = bad.read_lane_data(), good.read_lane_data()
     np.testing.assert_array_equal(ints_b, ints_g)
     np.testing.assert_array_equal(speed_b, speed_g)

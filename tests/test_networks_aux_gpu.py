@@ -1,8 +1,8 @@
 """The kernels around the step -- pressure_kernel, pressure_reward_kernel, greedy_kernel, fixed_time_kernel, demand_kernel and the trace
 and lane-data branches of the recording walk (csrc/tsc_env.hip) -- on the synthetic networks of tests/networks.py, against the host
-references the built-in scenarios' tests already use: loop_pressure, trainer.pressure_reward, the greedy rule as
-Scenario.greedy_controller_tables states it, _reference / _check_against_oracle over the oracle's vehicles after every second, _parity
-and _expected_vehicles.  The runs are the rows of networks.AUX; tests/test_networks_aux_host.py states, on the oracle alone, what
+references the built-in scenarios' tests already use (tests/env_rules.py, tests/env_harness.py): loop_pressure, trainer.pressure_reward,
+the greedy rule as Scenario.greedy_controller_tables states it, lane_data_reference / check_trace over the oracle's vehicles after
+every second, demand_parity and expected_vehicles.  The runs are the rows of networks.AUX; tests/test_networks_aux_host.py states, on the oracle alone, what
 each of them reaches (pressure_walk with two and three lanes per thread and a second round of the flat walk, more than 256 agents,
 ties, clipped entries, every lane-data field, the partial last interval, partly covered 4-second words).
 
@@ -17,12 +17,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests import env_harness as H
 from tests import networks as nw
-from tests.test_demand_gpu import STATE_KEYS, _expected_vehicles, _parity, _same, _episode
-from tests.test_lane_data_gpu import _check
-from tests.test_pressure_gpu import hold_state, hold_update, loop_pressure
-from tests.test_pressure_reward_gpu import instance_sum
-from tests.test_trace_gpu import _check_against_oracle
+from tests.env_harness import assert_same as _same, demand_parity as _parity, episode_outputs as _episode
+from tests.env_rules import (check_lane_data, check_trace, expected_vehicles as _expected_vehicles, greedy_rule, hold_state, hold_update,
+                             instance_sum, loop_pressure)
 
 pytestmark = pytest.mark.gpu
 
@@ -36,7 +35,7 @@ def _library_chooses_the_plan(monkeypatch):
 def _device(case, **kw):
     from deeprl_signal_control_amd.env import VecTrafficEnv
     net = case.net()
-    return VecTrafficEnv(case.scenario(), case.E, seed=net.seed, test_seeds=nw.eval_seeds(net, case.E), **kw)
+    return VecTrafficEnv(case.scenario(), case.E, seed=net.seed, test_seeds=H.eval_seeds(net, case.E), **kw)
 
 
 def _follow(case, dev):
@@ -47,8 +46,8 @@ def _follow(case, dev):
             yield t, dev.reset(), res, orc
             continue
         if pols is not None:
-            dev.update_fingerprint(torch.from_numpy(pols).cuda())
-        yield t, dev.step(torch.from_numpy(acts).cuda()), res, orc
+            dev.update_fingerprint(H.upload(dev, pols))
+        yield t, dev.step(H.upload(dev, acts)), res, orc
 
 
 # ---- max-pressure controller ----------------------------------------------------------------------------------------------
@@ -215,7 +214,7 @@ def test_greedy_vs_rule_on_the_oracles_observations(case):
             obs = out if t < 0 else out[0]
             obs64 = res if t < 0 else [r[0] for r in res]
             got = dev.greedy_actions(obs).cpu().numpy()
-            want = np.array([[nw.greedy_rule((term[a], action[a], n_cand[a]), obs64[e][a])[0] for a in range(scn.n_agent)]
+            want = np.array([[greedy_rule((term[a], action[a], n_cand[a]), obs64[e][a])[0] for a in range(scn.n_agent)]
                              for e in range(case.E)], np.int32)
             np.testing.assert_array_equal(got, want, err_msg='t=%d' % t)
     finally:
@@ -276,19 +275,19 @@ def _walk(case, lane_data=True):
         dev.set_trace(case.watch)
         if lane_data:
             dev.set_lane_data(case.period)
-        with nw.walk_context(case):
-            orc = nw.WalkOracles(case)
+        with H.walk_context(case):
+            orc = H.WalkOracles(case)
             dev.reset()
             rng = np.random.RandomState(case.rng_seed)
             for _ in range(nw.walk_steps(case)):
-                acts = nw.walk_actions(scn, rng, case.E)
+                acts = H.uniform_actions(scn, rng, case.E)
                 dev.step(torch.from_numpy(acts).cuda())
                 orc.step(acts)
         views = orc.views()
         tr = dev.collect_trajectories()
         assert sorted(tr) == sorted(case.watch)
-        ids = {e: _check_against_oracle(scn, tr[e], views[e].snaps, by_entry_lane=True) for e in case.watch}
-        sums = _check(scn, dev, views, case.period) if lane_data else None
+        ids = {e: check_trace(scn, tr[e], views[e].snaps, by_entry_lane=True) for e in case.watch}
+        sums = check_lane_data(scn, dev, views, case.period) if lane_data else None
         return ids, sums
     finally:
         dev.close()
@@ -336,17 +335,8 @@ def test_recording_is_refused_on_grid_x4_and_the_handle_goes_on():
                 got = dev.step_plan()
                 assert got['row'] + (got['threads'],) == tuple(nw.NETWORKS['grid_x4'].plan) and got['lds_bytes'] == 157584, got
                 continue
-            o, r, d, g = (x.cpu().numpy() for x in out)
-            for e in range(case.E):
-                oo, orr, od, og = res[e]
-                for a in range(scn.n_agent):
-                    np.testing.assert_array_equal(o[e, a, :scn.n_s_ls[a]], oo[a].astype(np.float32), err_msg='obs t=%d e=%d a=%d' % (t, e, a))
-                np.testing.assert_array_equal(r[e], np.asarray(orr, np.float64), err_msg='reward t=%d e=%d' % (t, e))
-                assert g[e] == og and bool(d[e]) == bool(od), (t, e)
-        for e in range(case.E):
-            st, sn = dev.get_state(e), orc[e].ms.snapshot()
-            for k in STATE_KEYS:
-                np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s e=%d' % (k, e))
+            H.assert_step_equal(scn, t, [x.cpu().numpy() for x in out], res)
+        H.assert_state_equal(dev, orc, range(case.E), t)
     finally:
         dev.close()
 
@@ -365,7 +355,7 @@ def test_demand_windows_vs_oracle_and_per_second_counts():
         np.testing.assert_array_equal(env.demand(), vph)
         rng = np.random.RandomState(12)
         for t in range(case.steps):
-            env.step(torch.from_numpy(nw.walk_actions(scn, rng, case.E)).cuda())
+            env.step(torch.from_numpy(H.uniform_actions(scn, rng, case.E)).cuda())
             for e in range(case.E):
                 st = env.get_state(e)
                 assert int(st['t'][0]) == t + 1

@@ -6,9 +6,9 @@ changed compiler, another seed) fails here, not silently on the GPU.  Every case
 import numpy as np
 import pytest
 
+from tests import env_harness as H
 from tests import networks as nw
-from tests.test_lane_data_gpu import INTS, F, _reference
-from tests.test_pressure_gpu import hold_state, hold_update, loop_pressure
+from tests.env_rules import F, INTS, greedy_rule, hold_state, hold_update, lane_data_reference, loop_pressure
 
 
 # ---- 0. the greedy tables of a scenario with laneless 'G' links ------------------------------------------------------------
@@ -41,8 +41,8 @@ def test_an_empty_candidate_has_flow_zero():
     n_cand, term, action = scn.greedy_controller_tables()
     assert n_cand[0] == 4 and (term[0, 0] == -1).all()
     tab = (term[0], action[0], n_cand[0])
-    assert nw.greedy_rule(tab, np.zeros(4)) == (0, [0.0, 0.0, 0.0, 0.0])
-    assert nw.greedy_rule(tab, np.array([0.0, 0.0, 0.2, 0.0]))[0] == 2
+    assert greedy_rule(tab, np.zeros(4)) == (0, [0.0, 0.0, 0.0, 0.0])
+    assert greedy_rule(tab, np.array([0.0, 0.0, 0.2, 0.0]))[0] == 2
 
 
 # ---- 1. the additions to tests/networks.py ------------------------------------------------------------------------------
@@ -191,7 +191,7 @@ def test_greedy_cases_are_not_vacuous(case):
         obs = res if t < 0 else [r[0] for r in res]
         for e in range(case.E):
             for a in range(scn.n_agent):
-                act, flows = nw.greedy_rule((term[a], action[a], n_cand[a]), obs[e][a])
+                act, flows = greedy_rule((term[a], action[a], n_cand[a]), obs[e][a])
                 ties += int(max(flows) > 0 and sum(f == max(flows) for f in flows) > 1)
                 decisions += 1
                 acts_seen.add(act)
@@ -224,13 +224,13 @@ _walk_sums = {}
 def _walk_reference(case):
     if case.key not in _walk_sums:
         scn = case.scenario()
-        with nw.walk_context(case):
-            orc = nw.WalkOracles(case)
+        with H.walk_context(case):
+            orc = H.WalkOracles(case)
             rng = np.random.RandomState(case.rng_seed)
             for _ in range(nw.walk_steps(case)):
-                orc.step(nw.walk_actions(scn, rng, case.E))
+                orc.step(H.uniform_actions(scn, rng, case.E))
         views = orc.views()
-        _walk_sums[case.key] = {e: _reference(scn, v.snaps, case.period)[0] for e, v in views.items()}, views
+        _walk_sums[case.key] = {e: lane_data_reference(scn, v.snaps, case.period)[0] for e, v in views.items()}, views
     return _walk_sums[case.key]
 
 

@@ -11,12 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests import env_harness as H
 from tests import networks as nw
-from tests.test_eval_outputs import _check as check_record_tables
-from tests.test_krauss_gpu import _device_trips, oracle_krauss
+from tests.env_harness import oracle_krauss
+from tests.env_rules import assert_trips_equal, check_record_tables, device_trips
 
 pytestmark = pytest.mark.gpu
-STATE_KEYS = ('n', 'x', 'v', 'sf', 'w', 'r')
 
 
 def _compare(name, monkeypatch, plan=None, env=None, scn=None, train_mode=True, record=False):
@@ -34,46 +34,33 @@ def _compare(name, monkeypatch, plan=None, env=None, scn=None, train_mode=True, 
     for k, v in dict(net.env, **(env or {})).items():
         monkeypatch.setenv(k, v)
     E, A = net.E, scn.n_agent
-    dev = VecTrafficEnv(scn, E, seed=net.seed, test_seeds=nw.eval_seeds(net))
+    dev = VecTrafficEnv(scn, E, seed=net.seed, test_seeds=H.eval_seeds(net))
     try:
         dev.train_mode = train_mode
         if record:
             dev.set_record(True)
         acc = np.zeros(E)                       # tsc_env_reward_sum: per instance in step order, then over the instances in order
-        for t, acts, pols, res, orc in nw.run_oracle(scn, net, train_mode=train_mode, is_record=record):
-            if t < 0:
-                obs = dev.reset(test_ind=np.arange(E)).cpu().numpy()
-                dev.reward_sum(reset=True)
-                if plan is not None:
-                    got = dev.step_plan()
-                    assert got['row'] + (got['threads'],) == tuple(plan), (got, plan)
-                    assert got['lds_bytes'] <= 160 * 1024
-                for e in range(E):
-                    for a in range(A):
-                        np.testing.assert_array_equal(obs[e, a, :scn.n_s_ls[a]], res[e][a].astype(np.float32), err_msg='reset e=%d a=%d' % (e, a))
-                    assert not obs[e].reshape(A, -1)[np.arange(scn.s_max)[None, :] >= np.array(scn.n_s_ls)[:, None]].any()
-                continue
-            if pols is not None:
-                dev.update_fingerprint(torch.from_numpy(pols).cuda())
-            o, r, d, g = dev.step(torch.from_numpy(acts).cuda())
-            o, r, d, g = o.cpu().numpy(), r.cpu().numpy(), d.cpu().numpy(), g.cpu().numpy()
+        side = H.run_oracle(scn, net, train_mode=train_mode, is_record=record)
+        _, _, _, res, orc = next(side)                              # the oracles' reset
+        obs = dev.reset(test_ind=np.arange(E)).cpu().numpy()
+        dev.reward_sum(reset=True)
+        if plan is not None:
+            got = dev.step_plan()
+            assert got['row'] + (got['threads'],) == tuple(plan), (got, plan)
+            assert got['lds_bytes'] <= 160 * 1024
+        for e in range(E):
+            for a in range(A):
+                np.testing.assert_array_equal(obs[e, a, :scn.n_s_ls[a]], res[e][a].astype(np.float32), err_msg='reset e=%d a=%d' % (e, a))
+            assert not obs[e].reshape(A, -1)[np.arange(scn.s_max)[None, :] >= np.array(scn.n_s_ls)[:, None]].any()
+        last = []
+
+        def after(t, out, res, orc):
             for e in range(E):
-                oo, orr, od, og = res[e]
-                for a in range(A):
-                    np.testing.assert_array_equal(o[e, a, :scn.n_s_ls[a]], oo[a].astype(np.float32), err_msg='obs t=%d e=%d a=%d' % (t, e, a))
-                assert g[e] == og, 'global_reward t=%d e=%d: %r != %r' % (t, e, g[e], og)
-                np.testing.assert_array_equal(r[e], np.asarray(orr, np.float64), err_msg='reward t=%d e=%d' % (t, e))
-                assert bool(d[e]) == bool(od), (t, e)
-                acc[e] += og
-            if t == net.peak or t == net.steps - 1:
-                for e in range(E):
-                    st, sn = dev.get_state(e), orc[e].ms.snapshot()
-                    for k in STATE_KEYS:
-                        np.testing.assert_array_equal(st[k], sn[k], err_msg='state %s t=%d e=%d' % (k, t, e))
-        assert all(bool(x[2]) for x in res)                         # the episode ended inside the run
-        arrived, teleported = dev.counters()
-        tot = [o.ms.totals() for o in orc]
-        assert [int(x) for x in arrived] == [x['arrived'] for x in tot] and [int(x) for x in teleported] == [x['teleported'] for x in tot]
+                acc[e] += res[e][3]
+            last[:] = res
+        H.follow(dev, side, state_at=(net.peak, net.steps - 1), after=after)
+        assert all(bool(x[2]) for x in last)                        # the episode ended inside the run
+        tot = H.assert_counters_equal(dev, orc)
         want = 0.0
         for e in range(E):
             want += acc[e]
@@ -90,9 +77,7 @@ def _compare(name, monkeypatch, plan=None, env=None, scn=None, train_mode=True, 
                 assert len(dev.traffic_data[e]) == net.steps * scn.control_interval_sec
                 assert dev.teleported_trips[e] == getattr(oe, 'teleported_trips', 0)
                 ref = np.array(oe.ms.trips(), np.int32).reshape(-1, 6)
-                got = _device_trips(dev, e)
-                key = lambda a_: a_[np.lexsort(a_.T[::-1])]
-                np.testing.assert_array_equal(key(got), key(ref), err_msg='trip rows e=%d' % e)
+                assert_trips_equal(device_trips(dev, e), ref, 'trip rows e=%d' % e)
         return tot
     finally:
         dev.close()

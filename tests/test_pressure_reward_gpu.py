@@ -19,6 +19,8 @@ from deeprl_signal_control_amd import _lib
 from deeprl_signal_control_amd.env import VecTrafficEnv
 from deeprl_signal_control_amd.scenario import build_scenario
 from deeprl_signal_control_amd.trainer import max_pressure_actions, pressure_reward
+from tests import env_harness as H
+from tests.env_rules import instance_sum
 
 pytestmark = pytest.mark.gpu
 _scn = {}
@@ -33,23 +35,8 @@ def scenario(name, agent='ma2c', **kw):
     return _scn[key]
 
 
-def random_actions(rng, scn, E):
-    return torch.from_numpy(np.stack([rng.randint(0, n, E) for n in scn.n_a_ls], 1).astype(np.int32)).cuda()
-
-
 def walked_live(tb, st):
     return int(st['n'][tb['walk']].sum())
-
-
-def instance_sum(per_step_g):
-    """reward_sum as the library documents it: per instance in step order, then the instances in order."""
-    acc = np.zeros(per_step_g[0].shape, np.float64)
-    for g in per_step_g:
-        acc = acc + g
-    tot = 0.0
-    for v in acc:
-        tot += float(v)
-    return tot
 
 
 # (scenario, agent, scenario keywords, measure, train_mode, control steps, compare every, recording)
@@ -131,8 +118,8 @@ def test_leaves_everything_else_alone():
     scn, _ = scenario('large_grid', 'ma2c', **DENSE)       # objective hybrid: both handles start on the built-in reward
     E = 3
     rng = np.random.RandomState(4)
-    acts = [random_actions(rng, scn, E) for _ in range(20)]
     armed, plain = VecTrafficEnv(scn, E, seed=21), VecTrafficEnv(scn, E, seed=21)
+    acts = [H.upload(armed, H.uniform_actions(scn, rng, E)) for _ in range(20)]
     armed.set_reward_pressure('count')
     for env in (armed, plain):
         env.set_record(True)
