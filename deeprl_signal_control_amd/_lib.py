@@ -44,7 +44,7 @@ _LIB = None
 # every symbol include/tsc.h declares (tests/test_abi.py checks the header against this list)
 SYMBOLS = ['tsc_last_error', 'tsc_version', 'tsc_profile_enable', 'tsc_profile_select', 'tsc_profile_reset', 'tsc_profile_read',
            'tsc_profile_name', 'tsc_env_create', 'tsc_env_destroy', 'tsc_env_set_stream', 'tsc_env_set_resident_instances',
-           'tsc_env_reset', 'tsc_env_set_stream_routes', 'tsc_env_set_demand', 'tsc_env_demand', 'tsc_env_set_greedy', 'tsc_env_greedy_actions', 'tsc_env_set_pressure', 'tsc_env_pressure_actions', 'tsc_env_set_reward_pressure', 'tsc_env_fixed_time_actions', 'tsc_env_set_fingerprint', 'tsc_env_bind_fingerprint', 'tsc_env_reward_sum', 'tsc_env_step', 'tsc_env_step_plan', 'tsc_env_get_state',
+           'tsc_env_reset', 'tsc_env_set_stream_routes', 'tsc_env_set_demand', 'tsc_env_demand', 'tsc_env_set_greedy', 'tsc_env_greedy_actions', 'tsc_env_set_pressure', 'tsc_env_pressure_actions', 'tsc_env_set_actuated', 'tsc_env_actuated_actions', 'tsc_env_actuated_state', 'tsc_env_set_reward_pressure', 'tsc_env_fixed_time_actions', 'tsc_env_set_fingerprint', 'tsc_env_bind_fingerprint', 'tsc_env_reward_sum', 'tsc_env_step', 'tsc_env_step_plan', 'tsc_env_get_state',
            'tsc_env_live_vehicles', 'tsc_env_vehicle_counts', 'tsc_env_set_block_order', 'tsc_env_counters', 'tsc_env_debug_clock', 'tsc_env_live_sum', 'tsc_env_record', 'tsc_env_read_record', 'tsc_env_read_trips', 'tsc_env_trace', 'tsc_env_read_trace', 'tsc_env_lane_data', 'tsc_env_read_lane_data', 'tsc_env_set_car_following', 'tsc_env_car_following',
            'tsc_model_create', 'tsc_model_destroy', 'tsc_model_set_stream', 'tsc_model_layout', 'tsc_model_path', 'tsc_model_plan',
            'tsc_model_set_params', 'tsc_model_reset_opt_state', 'tsc_model_debug_read', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state',
@@ -91,6 +91,9 @@ def lib():
     L.tsc_env_greedy_actions.argtypes = [vp, vp, vp]
     L.tsc_env_set_pressure.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, _ip, _ip, C.c_int32, _ip]
     L.tsc_env_pressure_actions.argtypes = [vp, vp, vp]
+    L.tsc_env_set_actuated.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, _ip, _ip, C.c_int32, _ip]
+    L.tsc_env_actuated_actions.argtypes = [vp, vp, vp]
+    L.tsc_env_actuated_state.argtypes = [vp, _ip, _ip]
     L.tsc_env_set_reward_pressure.argtypes = [vp, C.c_int32, C.c_int32, _ip, _ip]
     L.tsc_env_fixed_time_actions.argtypes = [vp, C.c_int32, vp]
     L.tsc_env_bind_fingerprint.argtypes = [vp, vp]

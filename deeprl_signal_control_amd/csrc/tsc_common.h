@@ -96,7 +96,7 @@ enum KernelId : int {
     KID_RETURNS, KID_HEAD_BWD, KID_LSTM_BWD, KID_DWO_GEMM, KID_DWH_GEMM, KID_DWX_GEMM, KID_DX1_GEMM,
     KID_DW1_GEMM, KID_GRADNORM, KID_RMSPROP, KID_TRANSPOSE, KID_FINGERPRINT, KID_FUSED_FWD,
     KID_IQL_ACT, KID_IQL_GRAD, KID_IQL_REDUCE, KID_IQL_SAMPLE, KID_IQL_ADD, KID_IQL_ADAM, KID_IQL_TARGET,
-    KID_IQL_PER_SAMPLE, KID_IQL_PER_UPDATE, KID_IQL_PER_ADD, KID_IQL_NSTEP, KID_PRESSURE, KID_PRESSURE_REWARD, KID_DEMAND,
+    KID_IQL_PER_SAMPLE, KID_IQL_PER_UPDATE, KID_IQL_PER_ADD, KID_IQL_NSTEP, KID_PRESSURE, KID_PRESSURE_REWARD, KID_ACTUATED, KID_DEMAND,
     KID_GAE, KID_HEAD_BWD_PPO, KID_COUNT
 };
 
@@ -119,7 +119,7 @@ struct ProfScope {
         ProfState &p = prof();
         if (!p.on) return;
         const bool per_step = id == KID_ENV_STEP || id == KID_FUSED_FWD || id == KID_ADD_TRANS || id == KID_FINGERPRINT ||
-                              id == KID_SAMPLE || id == KID_IQL_ACT || id == KID_IQL_ADD || id == KID_IQL_PER_ADD || id == KID_PRESSURE || id == KID_PRESSURE_REWARD;
+                              id == KID_SAMPLE || id == KID_IQL_ACT || id == KID_IQL_ADD || id == KID_IQL_PER_ADD || id == KID_PRESSURE || id == KID_PRESSURE_REWARD || id == KID_ACTUATED;
         if (p.seq[id]++ % (per_step ? p.stride : 1) != 0) return;
         if (!((p.only >> id) & 1ull)) return;
         auto get = [&]() { hipEvent_t e; if (!p.pool.empty()) { e = p.pool.back(); p.pool.pop_back(); } else { (void)hipEventCreate(&e); } return e; };

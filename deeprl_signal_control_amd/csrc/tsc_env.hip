@@ -537,13 +537,15 @@ struct PressDev {
 };
 constexpr int kPressT = 256;       // threads per instance
 
-// The flat walk of pressure_kernel and pressure_reward_kernel (step (a) of pressure_kernel's comment): fills start / down / up for
-// instance e from the live records of the walked lanes; `part` is [kPressT] scan scratch.  Every thread of the workgroup calls it;
-// the sums are complete when it returns (it ends on a barrier).
-__device__ __forceinline__ void pressure_walk(const EnvDev &P, const MovDev &M, int e, int *start, int *down, int *up, int *part) {
-    const int t = threadIdx.x, n_walk = M.n_walk, n_mov = M.n_mov;
-    const bool queue = M.measure == TSC_PRESSURE_QUEUE;
-    const short *__restrict__ walk = M.walk, *__restrict__ mov_of = M.mov_of;
+// The flat walk of the controllers' kernels and the pressure reward (step (a) of pressure_kernel's comment), the one copy: fills
+// start [n_walk + 1] for instance e from the counts of the lanes walk [n_walk], calling at_lane(w, n) once per walked lane (its index
+// into walk, its clamped count), then at_record(w, lane, record) once per live record of those lanes.  `part` is [kPressT] scan
+// scratch.  Every thread of the workgroup calls it; whatever LDS the caller zeroed before the call is zero for every at_record (a
+// barrier lies between), and the callbacks' sums are complete when it returns (it ends on a barrier).
+template <class LaneFn, class RecFn>
+__device__ __forceinline__ void flat_walk(const EnvDev &P, const short *__restrict__ walk, int n_walk, int e, int *start, int *part,
+                                          LaneFn at_lane, RecFn at_record) {
+    const int t = threadIdx.x;
     const int *N = P.N + (size_t)e * P.NLP;
     const float4 *S = P.S + (size_t)e * kCap * P.NLP;
     // counts of this thread's run of walked lanes, their exclusive prefix sum over the workgroup
@@ -566,11 +568,10 @@ __device__ __forceinline__ void pressure_walk(const EnvDev &P, const MovDev &M, 
         int n = N[walk[w]];
         n = n < 0 ? 0 : n > kCap ? kCap : n;
         start[w] = run;
-        down[w] = queue ? 0 : n;               // count: every vehicle of the lane
+        at_lane(w, n);
         run += n;
     }
     if (t == kPressT - 1) start[n_walk] = part[t];
-    for (int m = t; m < n_mov; m += kPressT) up[m] = 0;
     __syncthreads();
     const int total = start[n_walk];
     for (int f = t; f < total; f += kPressT) {
@@ -580,14 +581,31 @@ __device__ __forceinline__ void pressure_walk(const EnvDev &P, const MovDev &M, 
             if (start[mid] <= f) lo = mid; else hi = mid;
         }
         const int lane = walk[lo];
-        const float4 rec = S[vslot(f - start[lo], lane, P.NLP)];
-        if (queue && !(rec.y < kHalt)) continue;
-        const int route = (int)(__float_as_uint(rec.w) >> 16);
-        const int mv = route < P.NR ? mov_of[lane * P.NR + route] : -1;
-        if (mv >= 0) atomicAdd(&up[mv], 1);
-        if (queue) atomicAdd(&down[lo], 1);
+        at_record(lo, lane, S[vslot(f - start[lo], lane, P.NLP)]);
     }
     __syncthreads();
+}
+
+// A record's movement: that of (its lane, the route in the upper half of its last word), -1 = none.
+__device__ __forceinline__ int record_movement(const EnvDev &P, const short *__restrict__ mov_of, int lane, const float4 &rec) {
+    const int route = (int)(__float_as_uint(rec.w) >> 16);
+    return route < P.NR ? mov_of[lane * P.NR + route] : -1;
+}
+
+// flat_walk for pressure_kernel and pressure_reward_kernel: fills start / down / up for instance e from the live records of the
+// walked lanes.
+__device__ __forceinline__ void pressure_walk(const EnvDev &P, const MovDev &M, int e, int *start, int *down, int *up, int *part) {
+    const bool queue = M.measure == TSC_PRESSURE_QUEUE;
+    const short *__restrict__ mov_of = M.mov_of;
+    for (int m = threadIdx.x; m < M.n_mov; m += kPressT) up[m] = 0;
+    flat_walk(P, M.walk, M.n_walk, e, start, part,
+              [=](int w, int n) { down[w] = queue ? 0 : n; },       // count: every vehicle of the lane
+              [=, &P](int w, int lane, const float4 &rec) {
+                  if (queue && !(rec.y < kHalt)) return;
+                  const int mv = record_movement(P, mov_of, lane, rec);
+                  if (mv >= 0) atomicAdd(&up[mv], 1);
+                  if (queue) atomicAdd(&down[w], 1);
+              });
 }
 
 // Max-pressure (Varaiya 2013), the rule of INTEGRATION.md "Baseline controllers": with q(vehicle) = 1 (count) or v < kHalt (queue),
@@ -628,6 +646,108 @@ __global__ void __launch_bounds__(kPressT) pressure_kernel(EnvDev P, PressDev Q,
                 if (prs[a * P.PMAX + p] > prs[a * P.PMAX + arg]) arg = p;
             if (arg != h.x) { h.x = arg; h.y = 1; }
             else h.y = Q.min_green;            // (held long enough: the count need not run on)
+        }
+        *hold = h;
+        action[(size_t)e * P.A + a] = h.x;
+    }
+}
+
+// Tables, parameters and state of the actuated and SOTL controllers (tsc_env_set_actuated), a kernel argument of their own like
+// PressDev and independent of it.  The walk covers the movements' incoming lanes only: no downstream lane is read.
+struct ActDev {
+    int n_mov, n_walk;             // movements; their incoming lanes
+    int rule;                      // TSC_ACTUATED_*
+    int min_green, max_green;      // control steps (max_green: the gap rule's)
+    int theta, mu;                 // SOTL: threshold (vehicles x control steps), the platoon that is not cut
+    const short *walk;             // [n_walk] the incoming lanes, ascending
+    const short *mov_of;           // [NL * NR] movement of (lane, route), -1 = none
+    const float *zone;             // [NL] a vehicle within zone[l] of its lane's end is near (calls)
+    const int *srv_off;            // [A * PMAX + 1] as PressDev's
+    const short *srv;
+    const unsigned *mask;          // [n_mov] bit p: phase p of the movement's agent serves it
+    int *hold;                     // [E][A][2] {cur, age}
+    int *kappa;                    // [E][A][PMAX] SOTL's integrated red-time demand
+};
+
+// Gap-based actuated control and SOTL, the rules of INTEGRATION.md "Baseline controllers".  One workgroup per instance.  (a) The
+// flat walk over the incoming lanes: cnt(movement) = its vehicles, near(movement) = those with float32(lane_len - x) <= zone[lane] --
+// one fp32 subtraction and a compare, nothing the compiler could contract.  (b) One thread per (agent, phase): call = sum of near,
+// dem = sum of cnt over the served movements; under SOTL, in dem's place, red = the sum of cnt over those the agent's current phase
+// does not serve too (phase_mask), and kappa's update with it: every kappa of an agent moves in parallel, not one after the other
+// in its thread.  (c) One thread per agent: the rule, the stores.  Integers but for the compare: the result is exact.  Reads EnvDev, writes only action / counts / D.hold / D.kappa.  One call per control step.
+__global__ void __launch_bounds__(kPressT) actuated_kernel(EnvDev P, ActDev D, int *__restrict__ action, int *__restrict__ counts) {
+    extern __shared__ int asm_[];
+    int *start = asm_;                         // [n_walk + 1] flat index of a walked lane's first record
+    int *cnt = start + D.n_walk + 1;           // [n_mov]
+    int *near = cnt + D.n_mov;                 // [n_mov]
+    int *sums = near + D.n_mov;                // [A * PMAX][3] {call, dem | red, kappa}
+    int *part = sums + 3 * P.A * P.PMAX;       // [kPressT] scan scratch
+    const int e = blockIdx.x, t = threadIdx.x;
+    const bool sotl = D.rule == TSC_ACTUATED_SOTL;
+    const short *__restrict__ mov_of = D.mov_of;
+    const float *__restrict__ zone = D.zone, *__restrict__ lane_len = P.lane_len;
+    for (int m = t; m < 2 * D.n_mov; m += kPressT) cnt[m] = 0;     // (cnt and near)
+    flat_walk(P, D.walk, D.n_walk, e, start, part, [](int, int) {},
+              [=, &P](int, int lane, const float4 &rec) {
+                  const int mv = record_movement(P, mov_of, lane, rec);
+                  if (mv < 0) return;
+                  atomicAdd(&cnt[mv], 1);
+                  if (lane_len[lane] - rec.x <= zone[lane]) atomicAdd(&near[mv], 1);
+              });
+    const int2 *hold_e = (const int2 *)D.hold + (size_t)e * P.A;
+    int *kappa_e = D.kappa + (size_t)e * P.A * P.PMAX;
+    for (int i = t; i < P.A * P.PMAX; i += kPressT) {
+        int call = 0, dem = 0;
+        if (!sotl) {
+            for (int j = D.srv_off[i]; j < D.srv_off[i + 1]; ++j) {
+                const int mv = D.srv[j];
+                call += near[mv];
+                dem += cnt[mv];
+            }
+        } else {
+            const int a = i / P.PMAX, cur = hold_e[a].x;
+            const int k0 = kappa_e[i];
+            for (int j = D.srv_off[i]; j < D.srv_off[i + 1]; ++j) {
+                const int mv = D.srv[j];
+                call += near[mv];
+                dem += (D.mask[mv] >> cur) & 1u ? 0 : cnt[mv];
+            }
+            const int k = i - a * P.PMAX == cur ? 0 : k0 + dem;         // (padded phases serve nothing: theirs stays 0)
+            kappa_e[i] = k; sums[3 * i + 2] = k;
+        }
+        sums[3 * i] = call; sums[3 * i + 1] = dem;             // (padded phases serve nothing: 0)
+        if (counts) {
+            int *c = counts + 2 * ((size_t)e * P.A * P.PMAX + i);
+            c[0] = call; c[1] = dem;
+        }
+    }
+    __syncthreads();
+    for (int a = t; a < P.A; a += kPressT) {
+        int2 *hold = (int2 *)D.hold + (size_t)e * P.A + a;
+        int2 h = *hold;                        // {cur, age}
+        const int n = P.agent_nphase[a];
+        const int *s = sums + 3 * a * P.PMAX;
+        if (!sotl) {
+            if (h.y < D.min_green) h.y += 1;
+            else if (h.y < D.max_green && s[3 * h.x] > 0) h.y += 1;            // the extension
+            else {
+                int q = -1;                    // the first phase after cur, cyclically, with demand
+                for (int d = 1; d < n && q < 0; ++d) {
+                    const int p = h.x + d < n ? h.x + d : h.x + d - n;
+                    if (s[3 * p + 1] > 0) q = p;
+                }
+                if (q < 0) h.y = h.y + 1 < D.max_green ? h.y + 1 : D.max_green;
+                else { h.x = q; h.y = 1; }
+            }
+        } else {
+            int q = -1, best = 0;              // the FIRST maximum of the updated kappa over p != cur
+            for (int p = 0; p < n; ++p) {
+                const int k = s[3 * p + 2];
+                if (p != h.x && (q < 0 || k > best)) { q = p; best = k; }
+            }
+            const int call = s[3 * h.x];
+            if (h.y < D.min_green || (call > 0 && call <= D.mu) || q < 0 || best < D.theta) h.y = h.y < (1 << 30) ? h.y + 1 : 1 << 30;
+            else { h.x = q; h.y = 1; kappa_e[a * P.PMAX + q] = 0; }
         }
         *hold = h;
         action[(size_t)e * P.A + a] = h.x;
@@ -1785,6 +1905,11 @@ struct tsc_env {
     // pressure reward (tsc_env_set_reward_pressure): its tables and accumulator, R.acc null until armed; LDS of pressure_reward_kernel
     PressRewDev R = {};
     size_t smem_prew = 0;
+    // actuated / SOTL controller (tsc_env_set_actuated): its tables and state, D.hold null until armed; LDS of actuated_kernel; the
+    // initial hold state {0, min_green} of every (instance, agent), which arming and tsc_env_reset copy in
+    ActDev D = {};
+    size_t smem_act = 0;
+    std::vector<int> act_init;
 };
 
 // TSC_ENV_THREADS / TSC_ENV_KF (measurement / test knobs) over the library's own choice
@@ -1898,13 +2023,13 @@ const char *tsc_profile_name(int32_t id) {
                                   "returns", "head_bwd", "lstm_bwd", "dwo_gemm", "dwh_gemm", "dwx_gemm", "dx1_gemm",
                                   "dw1_gemm", "grad_norm", "rmsprop", "transpose_wx", "fingerprint", "policy_fwd_fused",
                                   "iql_act", "iql_grad", "iql_reduce", "iql_sample", "iql_add", "iql_adam", "iql_target",
-                                  "iql_per_sample", "iql_per_update", "iql_per_add", "iql_nstep", "pressure", "pressure_reward", "demand",
+                                  "iql_per_sample", "iql_per_update", "iql_per_add", "iql_nstep", "pressure", "pressure_reward", "actuated", "demand",
                                   "gae", "head_bwd_ppo"};
     static_assert(sizeof(names) / sizeof(names[0]) == tsc::KID_COUNT, "one name per kernel id");
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 119; }      // 1.19: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 1.18: tsc_model_plan; 1.17: tsc_iql_set_dueling / tsc_iql_get_dueling; 1.16: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 1.15: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 1.14: tsc_env_set_reward_pressure; 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 120; }      // 1.20: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 1.19: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 1.18: tsc_model_plan; 1.17: tsc_iql_set_dueling / tsc_iql_get_dueling; 1.16: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 1.15: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 1.14: tsc_env_set_reward_pressure; 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_env **out) {
     if (!sc || !out || n_env <= 0) return tsc::fail("tsc_env_create: bad arguments");
@@ -2420,6 +2545,10 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
     }
     if (h->Q.hold)                                     // max-pressure hold: age >= min_green, the first decision is free
         TSC_HIP(hipMemsetAsync(h->Q.hold, 0x7F, sizeof(int) * 2 * (size_t)h->P.E * h->P.A, h->stream));
+    if (h->D.hold) {                                   // actuated / SOTL: cur = 0, age = min_green (the first decision is free), kappa = 0
+        TSC_HIP(hipMemcpyAsync(h->D.hold, h->act_init.data(), sizeof(int) * h->act_init.size(), hipMemcpyHostToDevice, h->stream));
+        TSC_HIP(hipMemsetAsync(h->D.kappa, 0, sizeof(int) * (size_t)h->P.E * h->P.A * h->P.PMAX, h->stream));
+    }
     h->ld_live = h->P.ld_int != nullptr;               // tsc_env_lane_data takes effect here; its sums start over
     if (h->ld_live) {
         const size_t rows = (size_t)h->P.E * h->ld_nint;
@@ -2692,6 +2821,26 @@ static int upload_movements(const char *who, tsc_env *h, int measure, int n_mov,
 }
 static void release_movements(tsc_env *h, const MovDev &M) { h->bufs.release(M.walk); h->bufs.release(M.mov_of); h->bufs.release(M.mov_dn); }
 
+// The range checks and the compiled lists of served [A, PMAX, srv_max] (-1 padded) that tsc_env_set_pressure and tsc_env_set_actuated
+// share: phase (a, p) serves the movements srv[off[a * PMAX + p] .. off[.. + 1]).  Changes nothing of the handle.
+static int compile_served(const char *who, const tsc_env *h, int n_mov, const int32_t *mov, int srv_max, const int32_t *served,
+                          std::vector<int> &off, std::vector<short> &srv) {
+    const EnvDev &P = h->P;
+    srv.clear(); off.assign((size_t)P.A * P.PMAX + 1, 0);
+    for (int a = 0; a < P.A; ++a)
+        for (int p = 0; p < P.PMAX; ++p) {
+            for (int j = 0; j < srv_max; ++j) {
+                const int i = served[((size_t)a * P.PMAX + p) * srv_max + j];
+                if (i < 0) break;
+                if (p >= h->h_nphase[a]) return tsc::fail("%s: agent %d phase %d of %d serves a movement", who, a, p, h->h_nphase[a]);
+                if (i >= n_mov || mov[4 * i] != a) return tsc::fail("%s: agent %d phase %d serves movement %d of %d (or another agent's)", who, a, p, i, n_mov);
+                srv.push_back((short)i);
+            }
+            off[(size_t)a * P.PMAX + p + 1] = (int)srv.size();
+        }
+    return 0;
+}
+
 int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov,
                          int32_t srv_max, const int32_t *served) {
     if (!h || !mov || !lane_route_mov || !served || n_mov < 0 || srv_max <= 0) return tsc::fail("tsc_env_set_pressure: bad arguments");
@@ -2705,18 +2854,8 @@ int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t
     const auto build = [&]() {
         if (upload_movements("tsc_env_set_pressure", h, measure, n_mov, mov, lane_route_mov, N.M, &smem)) return 1;
         std::vector<short> srv;
-        std::vector<int> off((size_t)P.A * P.PMAX + 1, 0);
-        for (int a = 0; a < P.A; ++a)
-            for (int p = 0; p < P.PMAX; ++p) {
-                for (int j = 0; j < srv_max; ++j) {
-                    const int i = served[((size_t)a * P.PMAX + p) * srv_max + j];
-                    if (i < 0) break;
-                    if (p >= h->h_nphase[a]) return tsc::fail("tsc_env_set_pressure: agent %d phase %d of %d serves a movement", a, p, h->h_nphase[a]);
-                    if (i >= n_mov || mov[4 * i] != a) return tsc::fail("tsc_env_set_pressure: agent %d phase %d serves movement %d of %d (or another agent's)", a, p, i, n_mov);
-                    srv.push_back((short)i);
-                }
-                off[(size_t)a * P.PMAX + p + 1] = (int)srv.size();
-            }
+        std::vector<int> off;
+        if (compile_served("tsc_env_set_pressure", h, n_mov, mov, srv_max, served, off, srv)) return 1;
         smem += sizeof(int) * (size_t)P.A * P.PMAX;
         if (smem > 48 * 1024) return tsc::fail("tsc_env_set_pressure: LDS need %zu B > 48 KiB (%d walked lanes, %d movements)", smem, N.M.n_walk, n_mov);
         TSC_HIP(h->bufs.upload(&N.srv_off, off.data(), off.size()));
@@ -2746,6 +2885,93 @@ int tsc_env_pressure_actions(tsc_env *h, int32_t *action_dev, int32_t *pressure_
     tsc::ProfScope ps(tsc::KID_PRESSURE, h->stream);
     hipLaunchKernelGGL(pressure_kernel, dim3(h->P.E), dim3(kPressT), h->smem_press, h->stream, h->P, h->Q, action_dev, pressure_dev);
     TSC_HIP(hipGetLastError());
+    return 0;
+}
+
+int tsc_env_set_actuated(tsc_env *h, int32_t rule, int32_t min_green, int32_t max_green, int32_t theta, int32_t mu, const float *zone_host,
+                         int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov, int32_t srv_max, const int32_t *served) {
+    const char *who = "tsc_env_set_actuated";
+    if (!h || !zone_host || !mov || !lane_route_mov || !served || n_mov < 0 || srv_max <= 0) return tsc::fail("%s: bad arguments", who);
+    if (rule != TSC_ACTUATED_GAP && rule != TSC_ACTUATED_SOTL)
+        return tsc::fail("%s: rule %d is neither TSC_ACTUATED_GAP (0) nor TSC_ACTUATED_SOTL (1)", who, rule);
+    if (min_green < 1) return tsc::fail("%s: min_green %d must be >= 1", who, min_green);
+    if (rule == TSC_ACTUATED_GAP && max_green < min_green) return tsc::fail("%s: max_green %d must be >= min_green %d", who, max_green, min_green);
+    if (rule == TSC_ACTUATED_SOTL && theta < 1) return tsc::fail("%s: theta %d must be >= 1", who, theta);
+    if (rule == TSC_ACTUATED_SOTL && mu < 0) return tsc::fail("%s: mu %d must be >= 0", who, mu);
+    const EnvDev &P = h->P;
+    for (int l = 0; l < P.NL; ++l)
+        if (!(std::isfinite(zone_host[l]) && zone_host[l] > 0.0f)) return tsc::fail("%s: zone of lane %d is %g: must be finite and > 0", who, l, (double)zone_host[l]);
+    if (P.PMAX > 32) return tsc::fail("%s: %d phases per agent: the phase mask holds 32", who, P.PMAX);
+    // every check before anything changes: the movement tables, the served lists, the LDS need
+    std::vector<short> walk_all, mov_of, mov_dn, srv, walk;
+    std::vector<int> off;
+    if (compile_movements(who, P, TSC_PRESSURE_COUNT, n_mov, mov, lane_route_mov, walk_all, mov_of, mov_dn)) return 1;
+    if (compile_served(who, h, n_mov, mov, srv_max, served, off, srv)) return 1;
+    std::vector<char> incoming((size_t)P.NL, 0);
+    for (int i = 0; i < n_mov; ++i) incoming[mov[4 * i + 1]] = 1;
+    for (int l = 0; l < P.NL; ++l)
+        if (incoming[l]) walk.push_back((short)l);
+    std::vector<unsigned> mask((size_t)n_mov, 0u);
+    for (int i = 0; i < P.A * P.PMAX; ++i)
+        for (int j = off[i]; j < off[i + 1]; ++j) mask[srv[j]] |= 1u << (i % P.PMAX);
+    const size_t smem = sizeof(int) * (walk.size() + 1 + 2 * (size_t)n_mov + 3 * (size_t)P.A * P.PMAX + kPressT);
+    if (smem > 48 * 1024) return tsc::fail("%s: LDS need %zu B > 48 KiB (%zu walked lanes, %d movements)", who, smem, walk.size(), n_mov);
+    (void)hipSetDevice(h->device);
+    // Build, then swap: the handle's D changes only when every table of the new one, N, is on the device.
+    ActDev N = {};
+    const auto drop = [h](const ActDev &d) {
+        h->bufs.release(d.walk); h->bufs.release(d.mov_of); h->bufs.release(d.zone); h->bufs.release(d.srv_off); h->bufs.release(d.srv);
+        h->bufs.release(d.mask); h->bufs.release(d.hold); h->bufs.release(d.kappa);
+    };
+    std::vector<int> init(2 * (size_t)P.E * P.A, 0);
+    for (size_t i = 1; i < init.size(); i += 2) init[i] = min_green;
+    const auto build = [&]() {
+        N.n_mov = n_mov; N.n_walk = (int)walk.size(); N.rule = rule; N.min_green = min_green; N.max_green = max_green; N.theta = theta; N.mu = mu;
+        TSC_HIP(h->bufs.upload(&N.walk, walk.data(), walk.size()));
+        TSC_HIP(h->bufs.upload(&N.mov_of, mov_of.data(), mov_of.size()));
+        TSC_HIP(h->bufs.upload(&N.zone, zone_host, (size_t)P.NL));
+        TSC_HIP(h->bufs.upload(&N.srv_off, off.data(), off.size()));
+        TSC_HIP(h->bufs.upload(&N.srv, srv.data(), srv.size()));
+        TSC_HIP(h->bufs.upload(&N.mask, mask.data(), mask.size()));
+        N.hold = h->D.hold; N.kappa = h->D.kappa;              // the state: the handle's from the first arming on
+        if (!N.hold) {
+            TSC_HIP(h->bufs.alloc(&N.hold, 2 * (size_t)P.E * P.A, false));
+            TSC_HIP(h->bufs.alloc(&N.kappa, (size_t)P.E * P.A * P.PMAX, false));
+        }
+        TSC_HIP(hipStreamSynchronize(h->stream));              // a running actuated_kernel may still read the old tables
+        TSC_HIP(hipMemcpy(N.hold, init.data(), sizeof(int) * init.size(), hipMemcpyHostToDevice));    // the next decision is free
+        TSC_HIP(hipMemset(N.kappa, 0, sizeof(int) * (size_t)P.E * P.A * P.PMAX));
+        return 0;
+    };
+    if (build()) {                                             // failed: the handle keeps its tables
+        if (N.hold == h->D.hold) { N.hold = nullptr; N.kappa = nullptr; }     // (an armed handle's state stays its own)
+        drop(N);
+        return 1;
+    }
+    h->D.hold = nullptr; h->D.kappa = nullptr;                 // (N's now)
+    drop(h->D);
+    h->D = N;
+    h->smem_act = smem;
+    h->act_init.swap(init);
+    return 0;
+}
+
+int tsc_env_actuated_actions(tsc_env *h, int32_t *action_dev, int32_t *counts_dev) {
+    if (!h || !action_dev) return tsc::fail("tsc_env_actuated_actions: bad arguments");
+    if (!h->D.hold) return tsc::fail("tsc_env_actuated_actions: no controller tables (tsc_env_set_actuated)");
+    tsc::ProfScope ps(tsc::KID_ACTUATED, h->stream);
+    hipLaunchKernelGGL(actuated_kernel, dim3(h->P.E), dim3(kPressT), h->smem_act, h->stream, h->P, h->D, action_dev, counts_dev);
+    TSC_HIP(hipGetLastError());
+    return 0;
+}
+
+int tsc_env_actuated_state(tsc_env *h, int32_t *hold_host, int32_t *kappa_host) {
+    if (!h || !hold_host) return tsc::fail("tsc_env_actuated_state: bad arguments");
+    if (!h->D.hold) return tsc::fail("tsc_env_actuated_state: no controller tables (tsc_env_set_actuated)");
+    const EnvDev &P = h->P;
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    TSC_HIP(hipMemcpy(hold_host, h->D.hold, sizeof(int) * 2 * (size_t)P.E * P.A, hipMemcpyDeviceToHost));
+    if (kappa_host) TSC_HIP(hipMemcpy(kappa_host, h->D.kappa, sizeof(int) * (size_t)P.E * P.A * P.PMAX, hipMemcpyDeviceToHost));
     return 0;
 }
 

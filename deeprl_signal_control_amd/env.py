@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .scenario import LANE_CAP, OBJECTIVES, PRESSURE_MEASURES, Scenario, build_scenario
+from .scenario import ACTUATED_RULES, LANE_CAP, OBJECTIVES, PRESSURE_MEASURES, Scenario, build_scenario
 
 TRACE_ROW_CAP = 1 << 22           # default trajectory rows per traced instance (64 MiB; large_grid's busiest episodes need ~2 M)
 FCD_COLUMNS = ('episode', 'time_sec', 'id', 'lane', 'pos', 'speed')
@@ -408,6 +408,56 @@ class VecTrafficEnv:
                                                     C.c_void_p(prs.data_ptr()) if return_pressure else None))
         return (out, prs) if return_pressure else out
 
+    def _actuated(self, rule, key, tables_kw, params, out, return_counts):
+        """actuated_actions / sotl_actions: arm (tsc_env_set_actuated) when the rule or a parameter changed, then one call of
+        actuated_kernel.  params: (min_green, max_green, theta, mu)."""
+        if getattr(self, '_actuated_key', None) != key:
+            tabs = self.scn.actuated_tables(rule, **tables_kw)
+            ip = C.POINTER(C.c_int32)
+            mov, lrm, served = (np.ascontiguousarray(tabs[k], np.int32) for k in ('mov', 'lane_route_mov', 'served'))
+            zone = np.ascontiguousarray(tabs['zone'], np.float32)
+            _lib.check(self._L.tsc_env_set_actuated(self._h, ACTUATED_RULES.index(rule), *params, zone.ctypes.data_as(C.POINTER(C.c_float)),
+                                                    len(mov), mov.ctypes.data_as(ip), lrm.ctypes.data_as(ip), served.shape[2],
+                                                    served.ctypes.data_as(ip)))
+            self._actuated_key = key
+        if out is None:
+            out = torch.empty(self.E, self.A, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (self.E, self.A)
+        cnt = torch.empty(self.E, self.A, self.AMAX, 2, dtype=torch.int32, device=self.device) if return_counts else None
+        _lib.check(self._L.tsc_env_actuated_actions(self._h, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(cnt.data_ptr()) if return_counts else None))
+        return (out, cnt) if return_counts else out
+
+    def actuated_actions(self, out=None, min_green=1, max_green=10, gap_sec=3.0, return_counts=False):
+        """The gap-based actuated controller's actions (SUMO's `actuated`) for every instance, from the vehicle state on the device
+        (actuated_kernel, csrc/tsc_env.hip; the rule: INTEGRATION.md "Baseline controllers") -> int32 [E, A]; with return_counts
+        also int32 [E, A, AMAX, 2] = {call, dem} per phase (padded phases 0).  A green is extended while a vehicle is within gap_sec
+        seconds (at the lane's speed limit) of the stop line, between min_green and max_green control steps; phases without demand
+        are skipped.  The defaults are nominal, not tuned: gap_sec is SUMO's max-gap, max_green 50 s at a 5 s control interval.
+        Arms the tables at the first call and again when a parameter changes or sotl_actions ran in between (the handle holds one
+        of the two rules), which resets the state as reset() does.  ONE CALL PER CONTROL STEP: a call advances the state."""
+        kw = actuated_kw(dict(actuated_min_green=min_green, actuated_max_green=max_green, actuated_gap_sec=gap_sec))
+        g, G, gap = kw['actuated_min_green'], kw['actuated_max_green'], kw['actuated_gap_sec']
+        return self._actuated('actuated', ('actuated', g, G, gap), dict(gap_sec=gap), (g, G, 0, 0), out, return_counts)
+
+    def sotl_actions(self, out=None, min_green=2, theta=20, mu=2, omega_m=25.0, return_counts=False):
+        """The self-organising traffic lights' actions (SOTL: Gershenson 2005, Cools et al. 2008) for every instance, as
+        actuated_actions -> int32 [E, A]; with return_counts also int32 [E, A, AMAX, 2] = {call, red} per phase.  A phase is taken
+        when the vehicles it kept waiting at red, summed over the control steps, reach theta, unless 1 .. mu vehicles are within
+        omega_m metres of the stop line of the green phase.  The defaults are nominal, not tuned: of the order Cools et al. use."""
+        kw = actuated_kw(dict(sotl_min_green=min_green, sotl_theta=theta, sotl_mu=mu, sotl_omega=omega_m))
+        g, th, m, om = kw['sotl_min_green'], kw['sotl_theta'], kw['sotl_mu'], kw['sotl_omega']
+        return self._actuated('sotl', ('sotl', g, th, m, om), dict(omega_m=om), (g, g, th, m), out, return_counts)
+
+    def controller_state(self):
+        """The state of the armed actuated / SOTL controller (tsc_env_actuated_state; synchronises): dict of int32 arrays cur [E, A],
+        age [E, A] and kappa [E, A, AMAX] (all 0 under the gap rule)."""
+        hold = np.zeros((self.E, self.A, 2), np.int32)
+        kappa = np.zeros((self.E, self.A, self.AMAX), np.int32)
+        ip = C.POINTER(C.c_int32)
+        _lib.check(self._L.tsc_env_actuated_state(self._h, hold.ctypes.data_as(ip), kappa.ctypes.data_as(ip)))
+        return dict(cur=hold[:, :, 0].copy(), age=hold[:, :, 1].copy(), kappa=kappa)
+
     def set_reward_pressure(self, measure):
         """The pressure reward (tsc_env_set_reward_pressure, pressure_reward_kernel; the rule: INTEGRATION.md "Pressure reward"):
         measure 'count' | 'queue' arms it -- from the next step() on, reward and global_reward are r[a] = -|P[a]| over the state the step
@@ -592,7 +642,7 @@ def car_following_kw(model, sigma=None):
     return kw
 
 
-CONTROLLERS = ('greedy', 'maxpressure', 'fixedtime')     # evaluate --agents names that need no learner (main.py)
+CONTROLLERS = ('greedy', 'maxpressure', 'fixedtime', 'actuated', 'sotl')     # evaluate --agents names that need no learner (main.py)
 
 
 def pressure_kw(measure=None, min_green=None):
@@ -604,13 +654,7 @@ def pressure_kw(measure=None, min_green=None):
 
 
 def _positive_int(key, v):
-    try:
-        n = int(str(v).strip()) if not isinstance(v, (int, np.integer)) else int(v)
-    except ValueError:
-        n = 0
-    if n < 1:
-        raise ValueError('[ENV_CONFIG] %s = %r: must be an integer >= 1' % (key, v))
-    return n
+    return _number(key, v, True, 1, False)
 
 
 def objective_kw(objective=None, measure=None):
@@ -635,6 +679,38 @@ def controller_kw(config):
     kw = pressure_kw(config.get('pressure_measure'), config.get('pressure_min_green'))
     steps = config.get('fixed_time_steps')
     kw['fixed_time_steps'] = _positive_int('fixed_time_steps', 6 if steps is None else steps)
+    return kw
+
+
+def _number(key, v, integer, least, strict):
+    """[ENV_CONFIG] key = v as an int or a finite float, > least (strict) or >= least; refused with the key's name."""
+    try:
+        x = (int(str(v).strip()) if not isinstance(v, (int, np.integer)) else int(v)) if integer else float(v)
+        ok = bool(np.isfinite(x)) and (x > least if strict else x >= least) and (not integer or x <= 1 << 30)   # (int32 on the device)
+    except (TypeError, ValueError):
+        x, ok = None, False
+    if not ok:
+        raise ValueError('[ENV_CONFIG] %s = %r: must be %s %s %g' % (key, v, 'an integer' if integer else 'a finite number',
+                                                                     '>' if strict else '>=', least))
+    return x
+
+
+def actuated_kw(config):
+    """The actuated and SOTL controllers' keys of an [ENV_CONFIG] section (SectionProxy or dict): actuated_min_green = 1,
+    actuated_max_green = 10 (control steps), actuated_gap_sec = 3.0; sotl_min_green = 2, sotl_theta = 20 (vehicles x control steps),
+    sotl_mu = 2, sotl_omega = 25.0 (metres) -> checked values.  The defaults are nominal, not tuned: the gap is SUMO's max-gap, the
+    maximum green 50 s at a 5 s control interval; theta, mu and omega are of the order Cools et al. (2008) use.  Bad values are
+    refused with the key's name."""
+    def val(key, default, integer, least, strict=False):
+        v = config.get(key)
+        return _number(key, default if v is None else v, integer, least, strict)
+    kw = dict(actuated_min_green=val('actuated_min_green', 1, True, 1), actuated_max_green=val('actuated_max_green', 10, True, 1),
+              actuated_gap_sec=val('actuated_gap_sec', 3.0, False, 0, True),
+              sotl_min_green=val('sotl_min_green', 2, True, 1), sotl_theta=val('sotl_theta', 20, True, 1),
+              sotl_mu=val('sotl_mu', 2, True, 0), sotl_omega=val('sotl_omega', 25.0, False, 0, True))
+    if kw['actuated_max_green'] < kw['actuated_min_green']:
+        raise ValueError('[ENV_CONFIG] actuated_max_green = %d: must be >= actuated_min_green = %d'
+                         % (kw['actuated_max_green'], kw['actuated_min_green']))
     return kw
 
 

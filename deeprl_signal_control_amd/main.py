@@ -3,7 +3,7 @@
     python -m deeprl_signal_control_amd.main --base-dir DIR train --config-dir config/config_ma2c_large.ini
                                                                   [--test-mode no_test|in_train_test|after_train_test|all_test]
                                                                   [--envs E]
-    python -m deeprl_signal_control_amd.main --base-dir DIR evaluate --agents ma2c,greedy,maxpressure,fixedtime
+    python -m deeprl_signal_control_amd.main --base-dir DIR evaluate --agents ma2c,greedy,maxpressure,fixedtime,actuated,sotl
                                                                   [--evaluation-policy-type default|stochastic|deterministic]
                                                                   [--evaluation-seeds 10000,20000,...]
                                                                   [--trajectories N] [--lane-data PERIOD]
@@ -24,9 +24,11 @@ scenario.DemandSampler builds it) as one batched episode of seeds x scales insta
 first scale, then the second ... -- and adds a ``demand_scale`` column to every table.  Training draws its demand per episode from
 ``[ENV_CONFIG] demand_scales`` / ``demand_jitter``; the evaluation runs the nominal demand without the flag.
 
-``greedy``, ``maxpressure`` (Varaiya 2013) and ``fixedtime`` are controllers without a learner: ``DIR/<name>/data/*.ini`` supplies the
-config ([ENV_CONFIG] ``pressure_measure = count | queue``, ``pressure_min_green = 1``, ``fixed_time_steps = 6``), no checkpoint is read,
-and ``train`` refuses them.
+``greedy``, ``maxpressure`` (Varaiya 2013), ``fixedtime``, ``actuated`` (SUMO's gap-based actuated control) and ``sotl`` (self-organising
+traffic lights, Gershenson 2005) are controllers without a learner: ``DIR/<name>/data/*.ini`` supplies the config ([ENV_CONFIG]
+``pressure_measure = count | queue``, ``pressure_min_green = 1``, ``fixed_time_steps = 6``; ``actuated_min_green = 1``,
+``actuated_max_green = 10``, ``actuated_gap_sec = 3.0``; ``sotl_min_green = 2``, ``sotl_theta = 20``, ``sotl_mu = 2``, ``sotl_omega = 25.0``
+-- nominal values, not tuned), no checkpoint is read, and ``train`` refuses them.
 
 What differs: ``--envs E`` trains on E parallel env instances per GPU (the reference has one); `total_step`,
 `test_interval`, `log_interval` keep counting control steps of ONE instance, so a run is E times the experience.
@@ -166,6 +168,38 @@ class FixedTimePolicy:
         pass
 
 
+class ActuatedPolicy:
+    """Gap-based actuated control (SUMO's `actuated`) on the device's vehicle state: VecTrafficEnv.actuated_actions ->
+    tsc_env_actuated_actions; [ENV_CONFIG] actuated_min_green / actuated_max_green / actuated_gap_sec.  The observation is not read."""
+    name = 'actuated'
+    n_step = 1
+
+    def __init__(self, env, min_green=1, max_green=10, gap_sec=3.0):
+        self.env, self.min_green, self.max_green, self.gap_sec = env, min_green, max_green, gap_sec
+
+    def forward(self, ob, *_a, **_k):
+        return self.env.actuated_actions(min_green=self.min_green, max_green=self.max_green, gap_sec=self.gap_sec)
+
+    def reset(self):
+        pass
+
+
+class SotlPolicy:
+    """Self-organising traffic lights (Gershenson 2005; Cools et al. 2008) on the device's vehicle state:
+    VecTrafficEnv.sotl_actions -> tsc_env_actuated_actions; [ENV_CONFIG] sotl_min_green / sotl_theta / sotl_mu / sotl_omega."""
+    name = 'sotl'
+    n_step = 1
+
+    def __init__(self, env, min_green=2, theta=20, mu=2, omega_m=25.0):
+        self.env, self.min_green, self.theta, self.mu, self.omega_m = env, min_green, theta, mu, omega_m
+
+    def forward(self, ob, *_a, **_k):
+        return self.env.sotl_actions(min_green=self.min_green, theta=self.theta, mu=self.mu, omega_m=self.omega_m)
+
+    def reset(self):
+        pass
+
+
 A2C_POLICIES = ('lstm', 'fc')
 
 
@@ -256,7 +290,7 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
     """main.py:158-198 + Evaluator.run (utils.py:366-388): all evaluation seeds as ONE batched, recorded episode.  demand_scales:
     every seed under each of these demand scales (instance k * len(seeds) + i runs seed i at scale k); the tables then carry a
     demand_scale column."""
-    from .env import CONTROLLERS, VecTrafficEnv, check_lane_data_period, controller_kw, scenario_from_config
+    from .env import CONTROLLERS, VecTrafficEnv, actuated_kw, check_lane_data_period, controller_kw, scenario_from_config
     from .trainer import VecTrainer
     agent = agent_dir.rstrip('/').split('/')[-1]
     if not os.path.isdir(agent_dir):
@@ -270,6 +304,8 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
     if agent in CONTROLLERS:                  # the controllers share the greedy observation layout (none but greedy reads it)
         config['ENV_CONFIG']['agent'] = 'greedy'
         ctl = controller_kw(config['ENV_CONFIG']) if agent != 'greedy' else {}   # (refusals before any work on the device)
+        if agent in ('actuated', 'sotl'):
+            ctl = actuated_kw(config['ENV_CONFIG'])
     scn, seed, _ = scenario_from_config(config['ENV_CONFIG'])
     lane_data = check_lane_data_period(lane_data, scn.control_interval_sec)     # (before any work on the device)
     n_seed = len(seeds)
@@ -293,6 +329,13 @@ def evaluate_agent(agent_dir, output_dir, seeds, policy_type='default', device=0
     elif agent == 'fixedtime':
         model = FixedTimePolicy(env, ctl['fixed_time_steps'])
         logging.info('Evaluation: fixed-time, %d control steps per phase' % model.steps)
+    elif agent == 'actuated':
+        model = ActuatedPolicy(env, ctl['actuated_min_green'], ctl['actuated_max_green'], ctl['actuated_gap_sec'])
+        logging.info('Evaluation: actuated, green %d to %d control steps, gap %g s' % (model.min_green, model.max_green, model.gap_sec))
+    elif agent == 'sotl':
+        model = SotlPolicy(env, ctl['sotl_min_green'], ctl['sotl_theta'], ctl['sotl_mu'], ctl['sotl_omega'])
+        logging.info('Evaluation: SOTL, min green %d control steps, theta %d, mu %d, omega %g m'
+                     % (model.min_green, model.theta, model.mu, model.omega_m))
     elif agent != 'greedy':
         model = init_model(env, config, 0, E, seed, device)
         if not model.load(agent_dir + '/model/'):

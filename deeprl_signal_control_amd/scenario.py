@@ -48,6 +48,7 @@ NO_LANE = -1
 
 OBJECTIVES = ('queue', 'wait', 'hybrid', 'pressure')      # [ENV_CONFIG] objective: the reference's three and the pressure reward
 PRESSURE_MEASURES = ('count', 'queue')                   # include/tsc.h TSC_PRESSURE_COUNT / TSC_PRESSURE_QUEUE
+ACTUATED_RULES = ('actuated', 'sotl')                    # include/tsc.h TSC_ACTUATED_GAP / TSC_ACTUATED_SOTL
 
 
 @dataclass
@@ -286,6 +287,37 @@ class Scenario:
             raise ValueError('max-pressure tables: %d walked lanes, %d movements and %d (agent, phase) pairs need %d B of LDS, the '
                              'kernel has 48 KiB' % (len(walk), len(mov), A * PMAX, lds))
         return dict(mov=mov, lane_route_mov=lane_route_mov, served=served, n_served=n_served, walk=walk)
+
+    def actuated_tables(self, rule, gap_sec=None, omega_m=None):
+        """The tables of the actuated and SOTL controllers (tsc_env_set_actuated; INTEGRATION.md "Baseline controllers" states the
+        rules): those of pressure_tables and phase_mask u32 [n_mov], bit p set when phase p of the movement's agent serves it; zone
+        f32 [NL], the distance from a lane's end within which a vehicle calls -- rule 'actuated': float32(gap_sec) *
+        float32(lane_vmax[l]), rule 'sotl': float32(omega_m); walk_in i32, the movements' incoming lanes, ascending (the lanes the
+        kernel walks: it reads no downstream lane).  At most 32 phases per agent, and 48 KiB of LDS as in pressure_tables."""
+        if rule not in ACTUATED_RULES:
+            raise ValueError('rule = %r: allowed values are %s' % (rule, ' | '.join(ACTUATED_RULES)))
+        reach = gap_sec if rule == 'actuated' else omega_m
+        if reach is None or not (np.isfinite(float(reach)) and float(reach) > 0.0):
+            raise ValueError('%s = %r: must be a finite number > 0' % ('gap_sec' if rule == 'actuated' else 'omega_m', reach))
+        tabs = self.pressure_tables()
+        A, PMAX = tabs['n_served'].shape
+        if PMAX > 32:
+            raise ValueError('actuated tables: %d phases per agent, the phase mask holds 32' % PMAX)
+        mask = np.zeros(len(tabs['mov']), np.uint32)
+        for a in range(A):
+            for p in range(PMAX):
+                for i in tabs['served'][a, p, :tabs['n_served'][a, p]]:
+                    mask[i] |= np.uint32(1 << p)
+        if rule == 'actuated':
+            zone = np.float32(reach) * np.asarray(self.lane_vmax, np.float32)
+        else:
+            zone = np.full(self.n_lane, np.float32(reach), np.float32)
+        walk_in = np.array(sorted(set(tabs['mov'][:, 1].tolist())), np.int32)
+        lds = 4 * (len(walk_in) + 1 + 2 * len(tabs['mov']) + 3 * A * PMAX + 256)
+        if lds > 48 * 1024:
+            raise ValueError('actuated tables: %d walked lanes, %d movements and %d (agent, phase) pairs need %d B of LDS, the kernel '
+                             'has 48 KiB' % (len(walk_in), len(tabs['mov']), A * PMAX, lds))
+        return dict(tabs, phase_mask=mask, zone=zone.astype(np.float32), walk_in=walk_in)
 
     def streams_ready(self):
         """Fill the optional stream tables (whole-lane insertion window) once streams are declared."""

@@ -200,13 +200,14 @@ class VecTrainer:
         ('default' / 'stochastic') or its argmax ('deterministic').  test_ind: one index, or one per instance.
         Returns (mean, std) of the global reward over the episode's control steps, float64 arrays [E]
         (np.mean / np.std of the reference's `rewards` list, per instance)."""
+        from .env import CONTROLLERS
         env, model = self.env, self.model
         ob = env.reset(test_ind=test_ind)
         done = True                                               # pre-decision: resets the LSTM state
         model.reset()
         rewards = []
         while True:
-            if self.agent in ('greedy', 'maxpressure', 'fixedtime'):     # utils.py:202-203 (controllers: no learner)
+            if self.agent in CONTROLLERS:                        # utils.py:202-203 (controllers: no learner)
                 action = model.forward(ob)
             elif not self.agent.endswith('a2c'):                 # value-based (utils.py:221-226)
                 action, _ = model.forward(ob, stochastic=policy_type == 'stochastic')
@@ -416,6 +417,77 @@ def max_pressure_actions(scn, state, measure='count', return_pressure=False):
                 pressure[a, p] += up[i] - down[tabs['mov'][i, 2]]
     action = np.array([int(np.argmax(pressure[a, :int(scn.agent_nphase[a])])) for a in range(A)], np.int32)
     return (action, pressure) if return_pressure else action
+
+
+def _phase_counts(scn, state, tabs, cur):
+    """call, dem and red(p | cur) int32 [A, PMAX] of the actuated / SOTL rules over one instance's state and
+    Scenario.actuated_tables: per movement the vehicles that take it and those of them with float32(lane_len - x) <= zone."""
+    n = np.asarray(state['n'])
+    x, r = np.asarray(state['x'], np.float32), np.asarray(state['r'])
+    lanes, slots = np.nonzero(np.arange(x.shape[1])[None, :] < n[:, None])
+    mv = tabs['lane_route_mov'][lanes, r[lanes, slots]]
+    near = (np.asarray(scn.lane_len, np.float32)[lanes] - x[lanes, slots]) <= tabs['zone'][lanes]         # float32 - float32
+    n_mov = len(tabs['mov'])
+    cnt = np.bincount(mv[mv >= 0], minlength=n_mov)
+    nr = np.bincount(mv[(mv >= 0) & near], minlength=n_mov)
+    A, PMAX = tabs['n_served'].shape
+    call, dem, red = (np.zeros((A, PMAX), np.int32) for _ in range(3))
+    for a in range(A):
+        for p in range(PMAX):
+            srv = tabs['served'][a, p, :tabs['n_served'][a, p]]
+            call[a, p], dem[a, p] = nr[srv].sum(), cnt[srv].sum()
+            red[a, p] = cnt[srv[(tabs['phase_mask'][srv] >> np.uint32(cur[a])) & np.uint32(1) == 0]].sum()
+    return call, dem, red
+
+
+def actuated_actions(scn, state, cur, age, min_green=1, max_green=10, gap_sec=3.0, return_counts=False):
+    """HOST restatement of the gap-based actuated rule (INTEGRATION.md "Baseline controllers") over one instance's vehicle state, a
+    VecTrafficEnv.get_state / ms.snapshot dict, the controller's state cur and age int [A] BEFORE the call and
+    Scenario.actuated_tables -- what actuated_kernel computes on the device (VecTrafficEnv.actuated_actions, the product path).  For
+    host arrays only: CPU tools and tests.  -> (action, cur, age) after the call, new int32 arrays (action is cur); with
+    return_counts also int32 [A, PMAX, 2] = {call, dem}."""
+    if any(torch.is_tensor(v) for v in list(state.values()) + [cur, age]):
+        raise TypeError('actuated_actions is the host restatement; device state goes through VecTrafficEnv.actuated_actions (HIP)')
+    g, G = int(min_green), int(max_green)
+    tabs = scn.actuated_tables('actuated', gap_sec=gap_sec)
+    cur, age = np.array(cur, np.int32), np.array(age, np.int32)
+    call, dem, _ = _phase_counts(scn, state, tabs, cur)
+    for a in range(scn.n_agent):
+        n, c = int(scn.agent_nphase[a]), int(cur[a])
+        if age[a] < g or (age[a] < G and call[a, c] > 0):
+            age[a] += 1
+            continue
+        order = [(c + d) % n for d in range(1, n)]
+        with_demand = [p for p in order if dem[a, p] > 0]
+        if with_demand:
+            cur[a], age[a] = with_demand[0], 1
+        else:
+            age[a] = min(age[a] + 1, G)
+    out = (cur.copy(), cur, age)
+    return out + (np.stack([call, dem], -1),) if return_counts else out
+
+
+def sotl_actions(scn, state, cur, age, kappa, min_green=2, theta=20, mu=2, omega_m=25.0, return_counts=False):
+    """HOST restatement of the SOTL rule (INTEGRATION.md "Baseline controllers"), as actuated_actions; kappa int [A, PMAX] is the
+    integrated red-time demand before the call.  -> (action, cur, age, kappa) after the call, new int32 arrays; with return_counts
+    also int32 [A, PMAX, 2] = {call, red(p | cur before the call)}."""
+    if any(torch.is_tensor(v) for v in list(state.values()) + [cur, age, kappa]):
+        raise TypeError('sotl_actions is the host restatement; device state goes through VecTrafficEnv.sotl_actions (HIP)')
+    tabs = scn.actuated_tables('sotl', omega_m=omega_m)
+    cur, age, kappa = np.array(cur, np.int32), np.array(age, np.int32), np.array(kappa, np.int32)
+    call, _, red = _phase_counts(scn, state, tabs, cur)
+    for a in range(scn.n_agent):
+        n, c = int(scn.agent_nphase[a]), int(cur[a])
+        kappa[a, :n] += red[a, :n]
+        kappa[a, c] = 0
+        others = np.array([p for p in range(n) if p != c], np.int64)
+        q = int(others[np.argmax(kappa[a, others])]) if len(others) else -1        # (np.argmax: the first maximum)
+        if age[a] >= int(min_green) and not 0 < call[a, c] <= int(mu) and q >= 0 and kappa[a, q] >= int(theta):
+            cur[a], age[a], kappa[a, q] = q, 1, 0
+        else:
+            age[a] = min(age[a] + 1, 1 << 30)
+    out = (cur.copy(), cur, age, kappa)
+    return out + (np.stack([call, red], -1),) if return_counts else out
 
 
 def shape_reward(scn, r, agent_kind=None, train_mode=True):

@@ -100,7 +100,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 120: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -200,6 +200,35 @@ int tsc_env_set_pressure(tsc_env *h, int32_t measure, int32_t min_green, int32_t
  * [E, A]; pressure (nullable) dev int32 [E, A, p_max], padded phases 0.  ONE CALL PER CONTROL STEP: a call advances the hold state
  * (cur, age) whenever min_green > 1.  Changes nothing of the simulation. */
 int tsc_env_pressure_actions(tsc_env *h, int32_t *action_dev, int32_t *pressure_dev);
+/* Gap-based actuated control (SUMO's `actuated`) and self-organising traffic lights (SOTL: Gershenson 2005, Cools et al. 2008); no
+ * reference counterpart; INTEGRATION.md "Baseline controllers" states both rules.  rule = TSC_ACTUATED_GAP | TSC_ACTUATED_SOTL.  mov,
+ * lane_route_mov, srv_max and served are tsc_env_set_pressure's tables; zone_host float32 [n_lane]: a vehicle on lane l with
+ * float32(lane_len[l] - x) <= zone[l] is near the stop line (gap rule: gap seconds x the lane's speed limit; SOTL: omega metres).  Host
+ * pointers, copied.  Per movement i: cnt[i] = the vehicles on its incoming lane whose route takes it, near[i] = those of them that
+ * are near; per phase p: call(p) = sum of near, dem(p) = sum of cnt over the served movements, red(p | cur) = sum of cnt over the
+ * served movements that phase cur does not serve too.  The device keeps cur, age and (SOTL) kappa [p_max] per (instance, agent), all
+ * int32; this call and tsc_env_reset set cur = 0, age = min_green (the first decision is free), kappa = 0.
+ * Gap rule (min_green = g >= 1, max_green = G >= g control steps; theta and mu are not read): age < g: keep, age += 1; else age < G
+ * and call(cur) > 0: keep, age += 1 (the extension); else q = the first of cur + 1, ..., cur + n - 1 (mod n) with dem(q) > 0: none:
+ * keep, age = min(age + 1, G); otherwise cur = q, age = 1.
+ * SOTL (min_green = g >= 1, theta >= 1 vehicles x control steps, mu >= 0; max_green is not read): first kappa[p] += red(p | cur) for
+ * p != cur and kappa[cur] = 0; then age < g: keep, age += 1; else 0 < call(cur) <= mu: keep, age += 1; else q = the FIRST maximum of
+ * kappa[p] over p != cur: kappa[q] >= theta: cur = q, age = 1, kappa[q] = 0; otherwise (or with one phase) keep, age += 1.  age
+ * saturates at 2^30.
+ * Range-checks everything before anything changes (non-zero and tsc_last_error; the handle keeps what it had): a bad rule, min_green
+ * < 1, max_green < min_green (gap rule), theta < 1 or mu < 0 (SOTL), a zone entry that is not finite and > 0, p_max > 32, every table
+ * error tsc_env_set_pressure rejects, more than 48 KiB of LDS.  Synchronises before replacing tables.  Independent of
+ * tsc_env_set_pressure and tsc_env_set_reward_pressure.  A handle that never calls it allocates nothing and launches nothing more. */
+enum { TSC_ACTUATED_GAP = 0, TSC_ACTUATED_SOTL = 1 };
+int tsc_env_set_actuated(tsc_env *h, int32_t rule, int32_t min_green, int32_t max_green, int32_t theta, int32_t mu, const float *zone_host,
+                         int32_t n_mov, const int32_t *mov, const int32_t *lane_route_mov, int32_t srv_max, const int32_t *served);
+/* The armed rule's actions from the vehicle state as it stands (actuated_kernel, one workgroup per instance): action dev int32 [E, A]
+ * = cur after the update; counts (nullable) dev int32 [E, A, p_max, 2] = {call, dem} under the gap rule, {call, red(p | cur before
+ * the update)} under SOTL, padded phases 0.  ONE CALL PER CONTROL STEP: a call advances the state.  Changes nothing of the simulation. */
+int tsc_env_actuated_actions(tsc_env *h, int32_t *action_dev, int32_t *counts_dev);
+/* The controller's state, for tests and checkpoints: hold host int32 [E, A, 2] = {cur, age}, kappa (nullable) host int32 [E, A, p_max]
+ * (all 0 under the gap rule).  Synchronises. */
+int tsc_env_actuated_state(tsc_env *h, int32_t *hold_host, int32_t *kappa_host);
 /* The pressure reward (PressLight / MPLight; no reference counterpart; INTEGRATION.md "Pressure reward" states the rule).  mov and
  * lane_route_mov are tsc_env_set_pressure's (host pointers, int32, copied), up / down and the two measures as there.  While armed,
  * tsc_env_step launches step_kernel exactly as otherwise and then pressure_reward_kernel on the same stream, which OVERWRITES
