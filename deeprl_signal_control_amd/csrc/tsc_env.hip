@@ -844,7 +844,9 @@ __global__ void __launch_bounds__(256) fixed_time_kernel(EnvDev P, int steps, in
 // Register budget: the 256-thread instantiation is capped at 128 VGPRs (4 waves / SIMD).  With 155 VGPRs the
 // grid fits the chip with no slack, and whenever another kernel ran in between (i.e. always, in the training
 // loop) XCD 0 admitted ~30 workgroups one full round late -> 178 us became 316 us per step
-// (tools/bench_env.py, tsc_env_debug_clock).  The cap costs ~120 B of scratch per lane and 8 % in isolation.
+// (tools/bench_env.py, tsc_env_debug_clock).  Since the scalar side stopped spilling into VGPR lanes (below) no instantiation
+// needs scratch under the cap: the benchmarked one takes 88 VGPRs (122 before, two of them full of spilled scalars), the
+// runtime-dimension ones 99 - 128 (128 and 284 - 424 B of scratch before).
 // SPEC 1: the table dimensions of the reference's large_grid are compile-time constants (LDS offsets and index products
 // fold into immediates: the kernel holds > 100 scalar values otherwise and reloads the spilled ones with v_readlane)
 // SPEC = kSpecKrauss (tsc_env_set_car_following): runtime table dimensions and the Krauss car following with SUMO's dawdling
@@ -857,6 +859,35 @@ __global__ void __launch_bounds__(256) fixed_time_kernel(EnvDev P, int steps, in
 // second from its position, and counts the vehicles, the halting ones, the speeds and the events on it; a hand-off carries the
 // vehicle's old slot in the upper half of its outbox target, so that the gathering thread counts `entered` / `laneChangedTo` on
 // its own slot and `left` / `laneChangedFrom` (LDS atomics) on the source's.  The interval's sums stay in LDS for the launch.
+// Scalar registers.  The kernel's arguments are ~100 dwords of kernarg memory, the compiler loads them 8 or 16 dwords at a time at
+// kernel entry, and what the second loop or the epilogue reads of them then stays live -- in whole 16-dword tuples -- across the
+// loop, where 106 SGPRs do not hold it: the surplus lives in VGPR lanes (v_writelane / v_readlane, a VALU slot and wait states
+// each, in a VALU-bound kernel, and the VGPRs count against the 128).  So the prologue alone reads the parameters themselves; the
+// second loop and the epilogue read the kernarg segment again through an opaque copy of its address (step_args: a scalar load
+// where the value is used, served by the scalar cache), values the compiler would compute once in front of the loop and then
+// spill (the `!= 0xFF` masks of the entry-route bytes and their hash products, the lane tests of the flat phase and of publish)
+// are formed from opaque copies inside it, and a specialised row knows its workgroup size at compile time (BD).  Per-second
+// loop of <256, true, false, 2, 1>: 138 v_readlane_b32 and 4482 instructions before, none and 4361 now; no specialised
+// instantiation reloads a scalar inside the loop (tools/kernel_regs.py prints the counts; profiles/env_scalar_bench.json).
+struct StepArgs {                           // the kernarg segment of step_kernel: its parameters in order
+    EnvDev P; const int *action; float *obs; double *reward, *greward; uint8_t *done; int train_mode;
+};
+using StepArgsPtr = const __attribute__((address_space(4))) StepArgs *;
+__device__ __forceinline__ StepArgsPtr step_args() {
+    StepArgsPtr k = (StepArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));             // opaque: what is read through it is loaded behind this point
+    return k;
+}
+// compile-time table dimensions over the runtime ones
+template <int SPEC>
+__device__ __forceinline__ void spec_dims(EnvDev &P) {
+    if constexpr (SPEC > 0) {
+        constexpr SpecDims D = kSpec[SPEC];
+        P.NLP = D.NLP; P.NLA = D.NLA; P.NU = D.NU; P.NR = D.NR; P.A = D.A; P.KMAX = D.KMAX;
+        P.PMAX = D.PMAX; P.LMAX = D.LMAX; P.NBR = D.NBR; P.ctrl = D.ctrl; P.yellow = D.yellow; P.teleport = D.teleport;
+        P.NS = D.NR;                            // the reference's configurations: every route is its own stream
+    }
+}
 template <int MAXT, bool HELP, bool REC = false, int KF = 4, int SPEC = 0>      // REC: evaluation recording (plain walk only); KF: vehicles per thread and super-round of the flat phase
 __global__ void __launch_bounds__(MAXT, MAXT <= 512 ? 4 : 1)      // (HIP: the second figure is wavefronts per SIMD) 128 VGPRs whatever the workgroup size
 step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, double *__restrict__ reward,
@@ -866,18 +897,15 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     constexpr bool TR = SPEC == kSpecTrace || SPEC == kSpecKraussTrace || LD;
     constexpr bool SER = REC || KR;         // R0 (depart | serial << 16) is kept per slot
     static_assert(!TR || (REC && !HELP), "the trace rides on the recording walk");
+    static_assert(offsetof(StepArgs, action) == (sizeof(EnvDev) + 7) / 8 * 8, "StepArgs mirrors the parameter list");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    if constexpr (SPEC > 0) {
-        constexpr SpecDims D = kSpec[SPEC];
-        P.NLP = D.NLP; P.NLA = D.NLA; P.NU = D.NU; P.NR = D.NR; P.A = D.A; P.KMAX = D.KMAX;
-        P.PMAX = D.PMAX; P.LMAX = D.LMAX; P.NBR = D.NBR; P.ctrl = D.ctrl; P.yellow = D.yellow; P.teleport = D.teleport;
-        P.NS = D.NR;                            // the reference's configurations: every route is its own stream
-    }
+    spec_dims<SPEC>(P);
+    const int BD = SPEC > 0 ? MAXT : (int)blockDim.x;       // (plan_step launches a specialised row with exactly its MAXT threads)
     Smem s = carve<KR, LD>(smem_raw, P);
     const int e = P.order ? P.order[blockIdx.x] : (int)blockIdx.x, l = threadIdx.x, NLP = P.NLP, NLA = P.NLA, NR = P.NR, NS = P.NS;
     const bool lane = l < P.NU;             // lanes >= NU are never entered by any route: always empty
     const bool lthr = l < NLA;              // threads >= NLA only help in phase A1 and in the strided loops
-    const bool stamp = P.dbg && blockIdx.x == 0 && threadIdx.x == 0;
+    const bool stamp = blockIdx.x == 0 && threadIdx.x == 0;         // (whether stamps are on is read at each stamp: TSC_STAMP)
     int nstamp = 0;
     // A measurement build (-DTSC_ENV_PHASE_SUMS, tools/build_variant.sh) also lets every workgroup's thread 0 sum its shader-clock
     // cycles per kind of phase (tsc_env_debug_clock enable == 3): bucket 0 prologue + epilogue, 1 head walk, 2 flat phase, 3 gather +
@@ -887,13 +915,13 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     const bool wsum = P.dbg && threadIdx.x == 0;
     long long pacc_[5] = {0, 0, 0, 0, 0}, wprev = 0;
     int wk = 0;
-#define TSC_STAMP() do { if (stamp && nstamp < 62) P.dbg[nstamp++] = clock64();                                        \
+#define TSC_STAMP() do { if (stamp && nstamp < 62) { long long *d_ = step_args()->P.dbg; if (d_) d_[nstamp++] = clock64(); }   \
         if (wsum) { const long long now_ = clock64();                                                                    \
             if (wk > 0) { const int d_ = wk - 1, r_ = (d_ - 1) % 6;                                                       \
                 const int b_ = (d_ == 0 || d_ > 30) ? 0 : (r_ == 0 ? 1 : r_ == 2 ? 2 : r_ == 4 ? 3 : 4); pacc_[b_] += now_ - wprev; } \
             wprev = now_; ++wk; } } while (0)
 #else
-#define TSC_STAMP() do { if (stamp && nstamp < 62) P.dbg[nstamp++] = clock64(); } while (0)
+#define TSC_STAMP() do { if (stamp && nstamp < 62) { long long *d_ = step_args()->P.dbg; if (d_) d_[nstamp++] = clock64(); } } while (0)
 #endif
     TSC_STAMP();
     if (P.dbg && threadIdx.x == 0) P.dbg[64 + 2 * blockIdx.x] = wall_clock64();
@@ -933,12 +961,12 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     }
     // table copies: four (clamped, unconditional) loads in flight per thread and round instead of one
     auto copy_words = [&](uint32_t *dst, const uint32_t *src, int count) {
-        for (int base = l; base < count; base += 4 * (int)blockDim.x) {
+        for (int base = l; base < count; base += 4 * BD) {
             uint32_t w[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const int i = base + u * (int)blockDim.x; w[u] = src[i < count ? i : count - 1]; }
+            for (int u = 0; u < 4; ++u) { const int i = base + u * BD; w[u] = src[i < count ? i : count - 1]; }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { const int i = base + u * (int)blockDim.x; if (i < count) dst[i] = w[u]; }
+            for (int u = 0; u < 4; ++u) { const int i = base + u * BD; if (i < count) dst[i] = w[u]; }
         }
     };
     // Round 6: the first 8 / 4 words per thread of the two tables are REQUESTED here, next to the level-1 loads, and stored behind the
@@ -949,9 +977,9 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     const int n_mv = P.NU * NR, n_zip = (P.NU * NR + 3) / 4;                            // zip padded to 4 B
     uint32_t tw[kTW], tz[kTZ];
 #pragma unroll
-    for (int u = 0; u < kTW; ++u) { const int i = l + u * (int)blockDim.x; tw[u] = ((const uint32_t *)P.mv)[i < n_mv ? i : n_mv - 1]; }
+    for (int u = 0; u < kTW; ++u) { const int i = l + u * BD; tw[u] = ((const uint32_t *)P.mv)[i < n_mv ? i : n_mv - 1]; }
 #pragma unroll
-    for (int u = 0; u < kTZ; ++u) { const int i = l + u * (int)blockDim.x; tz[u] = ((const uint32_t *)P.zip)[i < n_zip ? i : n_zip - 1]; }
+    for (int u = 0; u < kTZ; ++u) { const int i = l + u * BD; tz[u] = ((const uint32_t *)P.zip)[i < n_zip ? i : n_zip - 1]; }
     // level 2 (needs n / act / t), issued before the remaining LDS fills
     float hx = 0, hv = 0, hsf = 0, tx = 0, tv = 0; uint32_t hm = 0;      // head record (slot 0) / tail of my lane, kept in registers
     {
@@ -962,11 +990,11 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         if (n > 0) { hx = a0.x; hv = a0.y; hsf = a0.z; hm = __float_as_uint(a0.w); tx = al.x; tv = al.y; }
     }
 #pragma unroll
-    for (int u = 0; u < kTW; ++u) { const int i = l + u * (int)blockDim.x; if (i < n_mv) ((uint32_t *)s.mv)[i] = tw[u]; }
+    for (int u = 0; u < kTW; ++u) { const int i = l + u * BD; if (i < n_mv) ((uint32_t *)s.mv)[i] = tw[u]; }
 #pragma unroll
-    for (int u = 0; u < kTZ; ++u) { const int i = l + u * (int)blockDim.x; if (i < n_zip) ((uint32_t *)s.zip)[i] = tz[u]; }
-    if (n_mv > kTW * (int)blockDim.x) copy_words((uint32_t *)s.mv + kTW * blockDim.x, (const uint32_t *)P.mv + kTW * blockDim.x, n_mv - kTW * (int)blockDim.x);
-    if (n_zip > kTZ * (int)blockDim.x) copy_words((uint32_t *)s.zip + kTZ * blockDim.x, (const uint32_t *)P.zip + kTZ * blockDim.x, n_zip - kTZ * (int)blockDim.x);
+    for (int u = 0; u < kTZ; ++u) { const int i = l + u * BD; if (i < n_zip) ((uint32_t *)s.zip)[i] = tz[u]; }
+    if (n_mv > kTW * BD) copy_words((uint32_t *)s.mv + kTW * BD, (const uint32_t *)P.mv + kTW * BD, n_mv - kTW * BD);
+    if (n_zip > kTZ * BD) copy_words((uint32_t *)s.zip + kTZ * BD, (const uint32_t *)P.zip + kTZ * BD, n_zip - kTZ * BD);
     // K1: signal FSM (envs/env.py:128-152) -> link chars for the yellow and the green interval
     if (ag) {
         P.prev_action[(size_t)e * P.A + l] = act;
@@ -979,27 +1007,27 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         s.pend[l] = pend0; s.ser[l] = ser0;
         for (int q = 0; q < 8; ++q) s.emit[l * 8 + q] = q < P.ctrl ? emit_tab[(size_t)l * P.emit_len + t + q] : 0;
     }
-    for (int r = blockDim.x + l; r < NS; r += blockDim.x) {              // more streams than threads (tests/test_networks_gpu.py few_threads)
+    for (int r = BD + l; r < NS; r += BD) {              // more streams than threads (tests/test_networks_gpu.py few_threads)
         s.pend[r] = P.pending[(size_t)e * NS + r]; s.ser[r] = P.serial[(size_t)e * NS + r];
         for (int q = 0; q < 8; ++q) s.emit[r * 8 + q] = q < P.ctrl ? emit_tab[(size_t)r * P.emit_len + t + q] : 0;
     }
-    for (int a2 = blockDim.x + l; a2 < P.A; a2 += blockDim.x) {          // more agents than threads (few_threads as well: its live junctions are agents 70 .. 99)
+    for (int a2 = BD + l; a2 < P.A; a2 += BD) {          // more agents than threads (few_threads as well: its live junctions are agents 70 .. 99)
         const int act2 = action[(size_t)e * P.A + a2], prev2 = P.prev_action[(size_t)e * P.A + a2];
         P.prev_action[(size_t)e * P.A + a2] = act2;
         const uint8_t *g = P.green_tab + ((size_t)a2 * P.PMAX + act2) * P.KMAX;
         const uint8_t *y = (prev2 < 0 || prev2 == act2) ? g : P.yellow_tab + (((size_t)a2 * P.PMAX + prev2) * P.PMAX + act2) * P.KMAX;
         for (int k = 0; k < P.KMAX; ++k) { s.link_y[a2 * P.KMAX + k] = y[k]; s.link_g[a2 * P.KMAX + k] = g[k]; }
     }
-    for (int q = l; q < NLA; q += blockDim.x) {
+    for (int q = l; q < NLA; q += BD) {
         const bool in = q < P.NU;
         s.len[q] = in ? P.lane_len[q] : 1.0f; s.node[q] = in ? P.lane_node[q] : -1; s.vmax[q] = in ? P.lane_vmax[q] : 1.0f;
         int sbq = (in && P.lane_sib) ? P.lane_sib[q] : -1;
         s.sib[q] = sbq < P.NU ? sbq : -1;               // (a sibling no route ever reaches has no rows here and is never needed)
     }
-    for (int q = l; q < NLP; q += blockDim.x) { s.wave[q] = 0; s.halt[q] = 0; s.hwait[q] = 0; }
+    for (int q = l; q < NLP; q += BD) { s.wave[q] = 0; s.halt[q] = 0; s.hwait[q] = 0; }
     if constexpr (HELP) {                           // flat-phase marks: all clear (a second sets and clears its own)
         uint32_t *mk = (uint32_t *)s.mark;
-        for (int q = l; q < (NLA * (kCap - 1) + 8) / 4; q += blockDim.x) mk[q] = 0u;
+        for (int q = l; q < (NLA * (kCap - 1) + 8) / 4; q += BD) mk[q] = 0u;
     }
     // publishes a lane's summary for the next second; with HELP also the wave-local inclusive scan of the number
     // of queued vehicles (slots >= 1) that phase A1 distributes over the workgroup
@@ -1009,7 +1037,9 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         if constexpr (HELP) {
             const int inc = wave_scan_add(n > 1 ? n - 1 : 0);
             s.pre[l] = inc;
-            if ((l & 63) == 63) s.wtot[l >> 6] = inc;
+            int l6 = l & 63;
+            asm volatile("" : "+v"(l6));            // (opaque: a mask of this call, not of the launch)
+            if (l6 == 63) s.wtot[l >> 6] = inc;
         }
     };
     publish();
@@ -1033,7 +1063,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
             copy_words((uint32_t *)s.ldsp, (const uint32_t *)ld_gs, 2 * nds);
             copy_words((uint32_t *)s.ldsu, (const uint32_t *)P.ld_sumo, nds);
             copy_words((uint32_t *)s.ldb, (const uint32_t *)P.ld_bound, 4 * P.NU);
-            for (int i = l; i < nds; i += blockDim.x) s.ldsec[i] = 0.0;
+            for (int i = l; i < nds; i += BD) s.ldsec[i] = 0.0;
         }
     }
     // the slot of position x on my lane: the last piece that starts at or before x (the first one for any x before it).  A lane of
@@ -1100,7 +1130,9 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
             if (lthr) {
                 const int c = n > 1 ? n - 1 : 0;
                 int P0 = s.pre[l] - c;
-                for (int w = 0; w < (l >> 6); ++w) P0 += s.wtot[w];
+                int lw = l >> 6;
+                asm volatile("" : "+v"(lw));                // (opaque: the loop's entry test would be a mask held, and spilled, for the launch)
+                for (int w = 0; w < NLA / 64 - 1; ++w) P0 += w < lw ? s.wtot[w] : 0;
                 s.pre[l] = P0;
                 if (c > 0) {
                     s.mark[P0] = (uint8_t)((l & 63) + 1);
@@ -1384,10 +1416,14 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
             for (int w = 0; w < nseg; ++w) total += s.wtot[w];
             constexpr int kF = KF;
             // flat-phase thread index: rotated so that the lane wavefronts (busy with phase H first) own the LAST flat indices
-            const int lf = (int)blockDim.x > NLA ? (l >= NLA ? l - NLA : l + ((int)blockDim.x - NLA)) : l;
-            const int wv = lf >> 6, wl = lf & 63, nwv = (int)blockDim.x >> 6;
+            // (from an opaque copy of the thread index: the phase's lane tests -- first / last lane of a wavefront, first / last thread --
+            //  are masks of this phase, not of the launch)
+            int lo = l;
+            asm volatile("" : "+v"(lo));
+            const int lf = BD > NLA ? (lo >= NLA ? lo - NLA : lo + (BD - NLA)) : lo;
+            const int wv = lf >> 6, wl = lf & 63, nwv = BD >> 6;
             int round = 0;
-            for (int base = 0; base < total; base += kF * (int)blockDim.x, ++round) {
+            for (int base = 0; base < total; base += kF * BD, ++round) {
                 const float carry_round = round > 0 ? s.wtail[((round - 1) & 1) * 16 + nwv - 1] : INFINITY;
                 // A wavefront whose first flat index is past the total has no vehicle in this (last) super-round: it only
                 // keeps the barrier.  The kernel is VALU-issue bound and the four workgroups of a CU share its SIMDs, so the
@@ -1491,7 +1527,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     pfs = TSC_DPP_I(sfl, sfl, kDppWaveShr1, 0xF);     // previous wavefront's tail)
                     if (wl == 63) s.wtail[(round & 1) * 16 + wv] = sv;
                 }
-                if (lf == (int)blockDim.x - 1) { s.hz[2] = x[kF - 1]; s.hz[3] = v[kF - 1]; }
+                if (lf == BD - 1) { s.hz[2] = x[kF - 1]; s.hz[3] = v[kF - 1]; }
                 __syncthreads();
                 if (lf == 0) { s.hz[0] = s.hz[2]; s.hz[1] = s.hz[3]; }      // read by flat thread 0 after the next barrier only
                 const float prev_tail = wv > 0 ? s.wtail[(round & 1) * 16 + wv - 1] : carry_round;
@@ -1514,16 +1550,16 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     stg(S, 4u * ob, make_float4(xn, vv, sf[u], __uint_as_float(nmeta)));
                     if constexpr (KR) stg(R0, ob, sr[u]);
                     if (i == s.n[q] - 1) { s.tx[q] = xn; s.tv[q] = vv; }
-                    if (last && xn >= P.lane_det[q]) { atomicAdd(&s.wave[q], 1); if (vv < kHalt) atomicAdd(&s.halt[q], 1); }
+                    if (last && xn >= step_args()->P.lane_det[q]) { atomicAdd(&s.wave[q], 1); if (vv < kHalt) atomicAdd(&s.halt[q], 1); }
                 }
-                if (base + kF * (int)blockDim.x < total) __syncthreads();     // next super-round reads what this one stored
+                if (base + kF * BD < total) __syncthreads();     // next super-round reads what this one stored
             }
             TSC_STAMP();
             __syncthreads();
             TSC_STAMP();
             {   // this second's marks all lie below `total`: clear them for the next one (which sets its own after the next barrier)
                 uint32_t *mk = (uint32_t *)s.mark;
-                for (int q = l; q < (total + 3) / 4; q += blockDim.x) mk[q] = 0u;
+                for (int q = l; q < (total + 3) / 4; q += BD) mk[q] = 0u;
             }
         }
         // ================= phase B (K3): gather hand-offs from feeder lanes, then demand =========
@@ -1578,9 +1614,11 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     }
                 }
             }
+            uint32_t rlo = myr_lo, rhi = myr_hi;
+            asm volatile("" : "+v"(rlo), "+v"(rhi));            // (opaque: the bytes' tests and hash terms are formed here, every second)
 #pragma unroll
             for (int q = 0; q < kMaxEntry; ++q) {               // my entry routes, ascending (packed: 0xFF ends the list)
-                const int r = (int)(((q < 4 ? myr_lo : myr_hi) >> (8 * (q & 3))) & 0xFFu);
+                const int r = (int)(((q < 4 ? rlo : rhi) >> (8 * (q & 3))) & 0xFFu);
                 if (r == 0xFF) break;
                 int pend = s.pend[r] + (int)s.emit[r * 8 + sub];
                 int ser = s.ser[r];
@@ -1589,9 +1627,10 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     const float xt = n > 0 ? tx : (L + kLen) + kS0;
                     float xmax = (xt - kLen) - kS0;
                     float xlo = kLen;
-                    if (SPEC != 1 && P.sorigin) {                    // the SUMO entry lane is one piece of this (contracted) lane
-                        xlo = P.sorigin[2 * r] + kLen;
-                        const float hi = P.sorigin[2 * r + 1];
+                    const float *const sorigin = SPEC != 1 ? step_args()->P.sorigin : nullptr;
+                    if (SPEC != 1 && sorigin) {                      // the SUMO entry lane is one piece of this (contracted) lane
+                        xlo = sorigin[2 * r] + kLen;
+                        const float hi = sorigin[2 * r + 1];
                         if (xmax > hi) xmax = hi;
                     }
                     if (!(xmax < xlo)) {
@@ -1661,7 +1700,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                 for (int q = 0; q < P.NU; ++q) sp += s.rsp[q];
                 P.rec_speed[row] = sp;
             }
-            for (int p2 = l; p2 < P.A * P.LMAX; p2 += blockDim.x) {
+            for (int p2 = l; p2 < P.A * P.LMAX; p2 += BD) {
                 const int ln = P.agent_lanes[p2];
                 P.rec_queue[row * (P.A * P.LMAX) + p2] = (ln >= 0 && ln < P.NU) ? s.rq[ln] : 0;
             }
@@ -1682,7 +1721,7 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     if (lthr) s.pre[l] += before;
                     __syncthreads();
                     uint4 *rows = P.trace_rows + (size_t)tslot * P.trace_cap;
-                    for (int k = l; k < tot; k += blockDim.x) {
+                    for (int k = l; k < tot; k += BD) {
                         int lo = 0, hi = NLA - 1;            // the lane of row k: the last lane whose first row is <= k
                         while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (s.pre[mid] <= k) lo = mid; else hi = mid - 1; }
                         const unsigned ob = (unsigned)vslot(k - s.pre[lo], lo, NLP) * 4u;
@@ -1704,29 +1743,33 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
         }
     }
 
+    // ---- the epilogue reads its arguments here, behind the loop (see "Scalar registers" above)
+    const StepArgsPtr ka = step_args();
+    const auto &Q = ka->P;
+    const int A_ = SPEC > 0 ? P.A : Q.A, LMAX_ = SPEC > 0 ? P.LMAX : Q.LMAX, PMAX_ = SPEC > 0 ? P.PMAX : Q.PMAX, NBR_ = SPEC > 0 ? P.NBR : Q.NBR;   // (SPEC: constants)
     // ---- K4: detectors (envs/env.py:325-407): wave, halting, wait of the front-most vehicle
     {   // window-mean live vehicles: one atomic per wavefront
         int tot = lane ? n : 0;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) tot += __shfl_down(tot, o, 64);
-        if ((l & 63) == 0 && tot) atomicAdd(&P.live_acc[e], (unsigned long long)tot);
+        if ((l & 63) == 0 && tot) atomicAdd(&Q.live_acc[e], (unsigned long long)tot);
     }
     if (lane) {
-        P.N[(size_t)e * NLP + l] = n;
+        Q.N[(size_t)e * NLP + l] = n;
         // counts were taken while the last simulated second wrote the vehicles; the front-most vehicle is slot 0
         const int hw = (n > 0 && hx >= det && hx > 0.0f) ? (int)(hm & 0xFFFFu) : 0;
         s.wave[l] += d_wave; s.halt[l] += d_halt; s.hwait[l] = hw;       // the flat phase added its vehicles with LDS atomics
     }
-    for (int r = l; r < NS; r += blockDim.x) { P.pending[(size_t)e * NS + r] = s.pend[r]; P.serial[(size_t)e * NS + r] = s.ser[r]; }
-    if (arrived) atomicAdd(&P.arrived[e], (unsigned long long)arrived);
-    if (tele) atomicAdd(&P.teleported[e], (unsigned long long)tele);
+    for (int r = l; r < NS; r += BD) { Q.pending[(size_t)e * NS + r] = s.pend[r]; Q.serial[(size_t)e * NS + r] = s.ser[r]; }
+    if (arrived) atomicAdd(&Q.arrived[e], (unsigned long long)arrived);
+    if (tele) atomicAdd(&Q.teleported[e], (unsigned long long)tele);
     if constexpr (LD) {                 // the interval's sums back (the barrier that ended the last second orders the LDS)
         if (ldon) {
-            for (int i = l; i < kLdInts * nds; i += blockDim.x) ld_gi[i] = s.ldi[i];
-            for (int i = l; i < nds; i += blockDim.x) ld_gs[i] = s.ldsp[i];
+            for (int i = l; i < kLdInts * nds; i += BD) ld_gi[i] = s.ldi[i];
+            for (int i = l; i < nds; i += BD) ld_gs[i] = s.ldsp[i];
         }
     }
-    if (l == 0) { P.tsec[e] = t; done[e] = t >= P.episode ? 1 : 0; }
+    if (l == 0) { Q.tsec[e] = t; ka->done[e] = t >= Q.episode ? 1 : 0; }
     TSC_STAMP();
     __syncthreads();
     TSC_STAMP();
@@ -1734,27 +1777,27 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     // ---- K5: observations.  The float64 normalisation (envs/env.py:439-442, a division) is done once per lane,
     // not once per observation entry; the entries then only gather.  The outbox arrays are dead by now.
     float *o_wave = s.ox, *o_coop = s.ov, *o_wait = s.osf;        // [NLP] each (kMaxCross * NLA >= NLP)
-    int *qacc = (int *)s.om, *wacc = qacc + P.A;                   // per-agent queue / wait sums (integers: exact in any order)
-    for (int q = l; q < NLP; q += blockDim.x) {
-        const double wv = norm_clip((double)s.wave[q], P.norm_wave, P.clip_wave);
+    int *qacc = (int *)s.om, *wacc = qacc + A_;                   // per-agent queue / wait sums (integers: exact in any order)
+    for (int q = l; q < NLP; q += BD) {
+        const double wv = norm_clip((double)s.wave[q], Q.norm_wave, Q.clip_wave);
         o_wave[q] = (float)wv;
-        o_coop[q] = (float)(wv * P.coop_gamma);
-        o_wait[q] = (float)norm_clip((double)s.hwait[q], P.norm_wait, P.clip_wait);
+        o_coop[q] = (float)(wv * Q.coop_gamma);
+        o_wait[q] = (float)norm_clip((double)s.hwait[q], Q.norm_wait, Q.clip_wait);
     }
-    for (int a = l; a < 2 * P.A; a += blockDim.x) qacc[a] = 0;
+    for (int a = l; a < 2 * A_; a += BD) qacc[a] = 0;
     __syncthreads();
     {
-        const int tot = P.A * P.SMAX;
-        const float *fp = (P.fp_bound ? P.fp_bound : P.fp) + (size_t)e * P.A * P.PMAX;
-        float *ob = obs + (size_t)e * tot;
+        const int tot = A_ * Q.SMAX;
+        const float *fp = (Q.fp_bound ? Q.fp_bound : Q.fp) + (size_t)e * A_ * PMAX_;
+        float *ob = ka->obs + (size_t)e * tot;
         constexpr int kOB = 6;                                     // entries per thread and round, loads first
-        for (int base = l; base < tot; base += kOB * (int)blockDim.x) {
+        for (int base = l; base < tot; base += kOB * BD) {
             int ks[kOB];
 #pragma unroll
-            for (int u = 0; u < kOB; ++u) { const int idx = base + u * (int)blockDim.x; ks[u] = P.obs_ks[idx < tot ? idx : tot - 1]; }
+            for (int u = 0; u < kOB; ++u) { const int idx = base + u * BD; ks[u] = Q.obs_ks[idx < tot ? idx : tot - 1]; }
 #pragma unroll
             for (int u = 0; u < kOB; ++u) {
-                const int idx = base + u * (int)blockDim.x;
+                const int idx = base + u * BD;
                 if (idx >= tot) continue;
                 const int kind = ks[u] >> 16, src = ks[u] & 0xFFFF;
                 float o = 0.0f;
@@ -1769,69 +1812,69 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
     TSC_STAMP();
     // ---- K6: reward (envs/env.py:356-367) and shaping (:580,:590-631), float64.  Queue and wait of an agent are
     // sums of small integers: accumulated with LDS atomics over all (agent, lane) pairs in parallel.
-    for (int p2 = l; p2 < P.A * P.LMAX; p2 += blockDim.x) {
-        const int ln = P.agent_lanes[p2];
-        const int a = p2 / P.LMAX;
-        if (ln >= 0 && p2 - a * P.LMAX < P.agent_nlane[a]) {
+    for (int p2 = l; p2 < A_ * LMAX_; p2 += BD) {
+        const int ln = Q.agent_lanes[p2];
+        const int a = p2 / LMAX_;
+        if (ln >= 0 && p2 - a * LMAX_ < Q.agent_nlane[a]) {
             int q = s.halt[ln];
-            if (P.queue_cap >= 0 && q > P.queue_cap) q = P.queue_cap;
+            if (Q.queue_cap >= 0 && q > Q.queue_cap) q = Q.queue_cap;
             atomicAdd(&qacc[a], q);
             atomicAdd(&wacc[a], s.hwait[ln]);
         }
     }
     __syncthreads();
-    for (int a = l; a < P.A; a += blockDim.x) {
+    for (int a = l; a < A_; a += BD) {
         const long long queue = qacc[a];
         const double wsum = (double)wacc[a];
         double r;
-        if (P.objective == TSC_OBJ_QUEUE) r = (double)(-queue);
-        else if (P.objective == TSC_OBJ_WAIT) r = -wsum;
-        else r = (double)(-queue) - P.coef_wait * wsum;
+        if (Q.objective == TSC_OBJ_QUEUE) r = (double)(-queue);
+        else if (Q.objective == TSC_OBJ_WAIT) r = -wsum;
+        else r = (double)(-queue) - Q.coef_wait * wsum;
         s.r[a] = r;
     }
     __syncthreads();
     if (l == 0) {                                   // (np_sum's scratch: the outbox targets, dead since the last second's gather)
-        double g = np_sum(s.r, P.A, (double *)s.oto, s.oto + 2 * kNpSumDepth);
-        s.r[P.A] = g; greward[e] = g; P.reward_acc[e] += g;
+        double g = np_sum(s.r, A_, (double *)s.oto, s.oto + 2 * kNpSumDepth);
+        s.r[A_] = g; ka->greward[e] = g; Q.reward_acc[e] += g;
     }
     __syncthreads();
     // (the loop of shape_rewards, kept in place: calling it here changes the scalar register allocation of the whole kernel)
-    for (int a = l; a < P.A; a += blockDim.x) {
-        const double g = s.r[P.A];
+    for (int a = l; a < A_; a += BD) {
+        const double g = s.r[A_];
         double out;
-        if (!train_mode) {
+        if (!ka->train_mode) {
             out = s.r[a];
-        } else if (P.agent_kind == TSC_AGENT_GREEDY) {
+        } else if (Q.agent_kind == TSC_AGENT_GREEDY) {
             out = g;
-        } else if (P.agent_kind == TSC_AGENT_GLOBAL) {
-            out = P.realnet_scale ? g / (double)(P.A * 20) : g;
+        } else if (Q.agent_kind == TSC_AGENT_GLOBAL) {
+            out = Q.realnet_scale ? g / (double)(A_ * 20) : g;
         } else {
             double cur = s.r[a];
             int deg = 0;
-            for (int j = 0; j < P.NBR; ++j) {
-                const int nb = P.nbr[a * P.NBR + j];
+            for (int j = 0; j < NBR_; ++j) {
+                const int nb = Q.nbr[a * NBR_ + j];
                 if (nb < 0) break;
-                cur += P.coop_gamma * s.r[nb];
+                cur += Q.coop_gamma * s.r[nb];
                 ++deg;
             }
-            out = P.realnet_scale ? cur / (double)((1 + deg) * 20) : cur;
+            out = Q.realnet_scale ? cur / (double)((1 + deg) * 20) : cur;
         }
-        reward[(size_t)e * P.A + a] = out;
+        ka->reward[(size_t)e * A_ + a] = out;
     }
     TSC_STAMP();
 #ifdef TSC_ENV_PHASE_SUMS
     if (wsum) {
 #pragma unroll
-        for (int b_ = 0; b_ < 5; ++b_) P.dbg[64 + 2 * (size_t)P.E + 5 * (size_t)blockIdx.x + b_] = pacc_[b_];
+        for (int b_ = 0; b_ < 5; ++b_) Q.dbg[64 + 2 * (size_t)Q.E + 5 * (size_t)blockIdx.x + b_] = pacc_[b_];
     }
 #endif
-    if (stamp) P.dbg[63] = nstamp;
-    if (P.dbg && threadIdx.x == 0) {
+    if (stamp && Q.dbg) Q.dbg[63] = nstamp;
+    if (Q.dbg && threadIdx.x == 0) {
         unsigned hwid, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         // end time in the low 48 bits, XCC id and HW_ID (cu / se / simd / wave slot) on top
-        P.dbg[64 + 2 * blockIdx.x + 1] = (long long)(wall_clock64() & 0xFFFFFFFFFFFFll) | ((long long)(xcc & 0xF) << 60) | ((long long)(hwid & 0xFFF) << 48);
+        Q.dbg[64 + 2 * blockIdx.x + 1] = (long long)(wall_clock64() & 0xFFFFFFFFFFFFll) | ((long long)(xcc & 0xF) << 60) | ((long long)(hwid & 0xFFF) << 48);
     }
 #undef TSC_STAMP
 }
@@ -2264,7 +2307,9 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     // vehicles per thread and super-round of the flat phase (TSC_ENV_KF = 1 / 2 / 4 for A/B runs).  With runtime dimensions
     // 1 is best (296 M env-steps/s; 2: 294, 4: 284 -- fewer barriers do not pay for the registers); the specialised kernel
     // has the registers for 2 (env step 11.5 -> 10.7 ms per rollout; 4 spills: 11.4; round 5, rule-10 traffic, episode average:
-    // 3 -- 128 VGPRs, 8 spilled dwords, bit-exact -- 94.9 / 95.3 us per control step against 92.7 / 92.8 with 2)
+    // 3 -- 128 VGPRs, 8 spilled dwords, bit-exact -- 94.9 / 95.3 us per control step against 92.7 / 92.8 with 2; again without the
+    // scalar spills -- 99 VGPRs, no scratch, bit-exact -- 81.0 - 81.3 us against 75.6 - 76.1 with 2, five runs each, V = 859: the
+    // third vehicle per thread lengthens every wavefront's chain by more than the rare second super-round costs.  Not built.)
     h->kf = env_kf(h->spec == 1 ? 2 : 1);                    // (Monaco, spec 2: 330 M env-steps/s with 1, 323 M with 2)
     if (h->spec && h->kf == 4) h->spec = 0;                  // (no specialised instantiation of the 4-wide variant)
     // Workgroup size of the specialised kernels: a CU holds 16 wavefronts of this kernel (128 VGPRs), i.e. four workgroups of 256
