@@ -1217,7 +1217,8 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                     }
                     // zipper merge by readiness: of the feeders of tl whose HEAD wants tl, sees an open signal and can reach
                     // its stop line within this second, the one with the smallest rotating rank (t + rank) % count sends
-                    // (large_grid, SPEC 1, has no unsignalised merge: its zip table is all zero, checked at create time)
+                    // (large_grid, SPEC 1, has no unsignalised merge: its zip table is all zero, checked at create time; zippers of
+                    // three and four feeders under signals, next to teleporting heads: tests/test_networks_random_gpu.py)
                     if (SPEC != 1 && can_cross && (z >> 4) > 1) {
                         const uint32_t ups = s.up4[tl];
                         int best = -1, bestp = 1 << 30;
@@ -1593,7 +1594,8 @@ step_kernel(EnvDev P, const int *__restrict__ action, float *__restrict__ obs, d
                         float ax = s.ox[o];
                         const float av = s.ov[o];
                         const uint32_t am = s.om[o];
-                        if (n > 0 && ax > tx - kLen) {                   // arrivals of two feeders in one second
+                        if (n > 0 && ax > tx - kLen) {                   // arrivals of two feeders in one second (yielding feeders of
+                                                                         // one lane: tests/test_networks_random_gpu.py, half of its networks)
                             ax = tx - kLen;
                             if (ax < 0.0f) ax = 0.0f;
                         }

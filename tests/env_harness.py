@@ -304,6 +304,84 @@ def run_oracle(scn, net, on_second=None, train_mode=True, is_record=False, E=Non
     yield from oracle_steps(scn, orc, list(obs), net.steps, draw)
 
 
+def compare_with_oracle(scn, net, monkeypatch, plan=None, env=None, train_mode=True, record=False, label=None, lds_limit=None,
+                        least_trips=101):
+    """The one comparison of tests/test_networks_gpu.py and tests/test_networks_random_gpu.py: VecTrafficEnv(scn, E, seed) against E
+    OracleEnvs over the run of `net` (a networks.Net; run_oracle draws the actions: seeded random choices mixed with a greedy rule on
+    the oracle's observations).  Bit for bit: observations (padded entries zero), local or shaped rewards, global_reward, done, the
+    full vehicle state after the entry's peak step and at the end, counters() and reward_sum(); with record also the per-second
+    record rows, the control rows and the trip log.
+    plan: what step_plan() must report after the first reset (row + threads); lds_limit: the plan is printed and only its LDS need
+    is asserted; env: TSC_ENV_* variables on top of the entry's own; label: put in front of a failure's message (the message itself
+    names the control step, the instance and the first field that differs); least_trips: the fewest finished trips per instance a
+    recorded run must show.  -> the oracles' totals."""
+    from deeprl_signal_control_amd.env import VecTrafficEnv
+    from tests.env_rules import assert_trips_equal, check_record_tables, device_trips
+    for k in ('TSC_ENV_THREADS', 'TSC_ENV_KF', 'TSC_ENV_HELP', 'TSC_ENV_SPEC'):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in dict(net.env, **(env or {})).items():
+        monkeypatch.setenv(k, v)
+    E, A = net.E, scn.n_agent
+    dev = VecTrafficEnv(scn, E, seed=net.seed, test_seeds=eval_seeds(net))
+    try:
+        dev.train_mode = train_mode
+        if record:
+            dev.set_record(True)
+        acc = np.zeros(E)                       # tsc_env_reward_sum: per instance in step order, then over the instances in order
+        side = run_oracle(scn, net, train_mode=train_mode, is_record=record)
+        _, _, _, res, orc = next(side)                              # the oracles' reset
+        obs = dev.reset(test_ind=np.arange(E)).cpu().numpy()
+        dev.reward_sum(reset=True)
+        got = dev.step_plan()
+        if plan is not None:
+            assert got['row'] + (got['threads'],) == tuple(plan), (got, plan)
+            assert got['lds_bytes'] <= 160 * 1024
+        if lds_limit is not None:
+            print('%s: plan %s' % (label, got))
+            assert got['lds_bytes'] <= lds_limit, got
+        lens = np.array([len(x) for x in res[0]])                   # n_s_ls; the greedy controller's observation is its waves alone
+        assert scn.agent == 'greedy' or lens.tolist() == list(scn.n_s_ls)
+        padded = np.arange(scn.s_max)[None, :] >= lens[:, None]
+        for e in range(E):
+            for a in range(A):
+                np.testing.assert_array_equal(obs[e, a, :lens[a]], res[e][a].astype(np.float32), err_msg='reset e=%d a=%d' % (e, a))
+            assert not obs[e].reshape(A, -1)[padded].any()
+        last = []
+
+        def after(t, out, res, orc):
+            for e in range(E):
+                acc[e] += res[e][3]
+                assert not out[0][e].reshape(A, -1)[padded].any(), 'padded obs t=%d e=%d' % (t, e)
+            last[:] = res
+        follow(dev, side, state_at=(net.peak, net.steps - 1), after=after)
+        assert all(bool(x[2]) for x in last)                        # the episode ended inside the run
+        tot = assert_counters_equal(dev, orc)
+        want = 0.0
+        for e in range(E):
+            want += acc[e]
+        assert dev.reward_sum() == want
+        if record:
+            dev.collect_tripinfo()
+            for e, oe in enumerate(orc):
+                oe.collect_tripinfo()
+                gold = {}
+                for kind, rows in (('traffic', oe.traffic_data), ('control', oe.control_data), ('trip', oe.trip_data)):
+                    for k in rows[0]:
+                        gold['%s_%s' % (kind, k)] = np.array([row[k] for row in rows])
+                check_record_tables(gold, dev.traffic_data[e], dev.control_data[e], dev.trip_data[e], least_trips)
+                assert len(dev.traffic_data[e]) == net.steps * scn.control_interval_sec
+                assert dev.teleported_trips[e] == getattr(oe, 'teleported_trips', 0)
+                ref = np.array(oe.ms.trips(), np.int32).reshape(-1, 6)
+                assert_trips_equal(device_trips(dev, e), ref, 'trip rows e=%d' % e)
+        return tot
+    except AssertionError as ex:
+        if label is None:
+            raise
+        raise AssertionError('%s: %s' % (label, ex)) from ex
+    finally:
+        dev.close()
+
+
 # ---- several handles under the same actions ---------------------------------------------------------------------------------------
 def recording_pair(scn, E, seed=5):
     """Two recording handles of the same seeds."""

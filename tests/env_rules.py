@@ -232,10 +232,10 @@ def assert_trips_equal(got, ref, msg=''):
     np.testing.assert_array_equal(key(got), key(ref), err_msg=msg)
 
 
-def check_record_tables(g, traffic, control, trips):
+def check_record_tables(g, traffic, control, trips, least_trips=101):
     """The per-second rows, the control rows and the trip table of a recording env against the arrays g['traffic_*'],
     g['control_*'], g['trip_*'] of a reference: integers and strings exactly, float means to 1e-12 (np.mean's pairwise sum against
-    the per-lane partial sums)."""
+    the per-lane partial sums).  least_trips: the fewest finished trips the run must show (the comparison is not vacuous)."""
     for k in ('episode', 'time_sec', 'number_total_car', 'number_departed_car', 'number_arrived_car'):
         np.testing.assert_array_equal(np.array([r[k] for r in traffic]), g['traffic_' + k], err_msg=k)
     for k in ('avg_wait_sec', 'avg_speed_mps', 'std_queue', 'avg_queue'):
@@ -247,5 +247,5 @@ def check_record_tables(g, traffic, control, trips):
                   key=lambda t: (float(t[0]), t[1]))
     got = sorted(((r['arrival_sec'], r['id'], r['depart_sec'], r['duration_sec'], r['wait_step'], r['wait_sec']) for r in trips),
                  key=lambda t: (float(t[0]), t[1]))
-    assert len(got) == len(want) > 100 and got == [tuple(str(x) for x in t) for t in want]
+    assert len(got) == len(want) >= least_trips and got == [tuple(str(x) for x in t) for t in want]
     assert all(r['episode'] == 1 for r in trips)

@@ -15,7 +15,10 @@ states conditions (the limit is reached, the roads are not empty) about the very
 
 The kernels around the step (controllers, pressure reward, recording walks, per-instance demand) run on the same networks: AUX, at the
 end of this file, lists those runs for tests/test_networks_aux_host.py and tests/test_networks_aux_gpu.py; windows() and split_pieces()
-exist for them."""
+exist for them.
+
+random_network(seed), behind AUX, draws whole networks inside every limit at once -- the seeded sweep of
+tests/test_networks_random_host.py and tests/test_networks_random_gpu.py over RANDOM_SEEDS."""
 import copy
 
 import numpy as np
@@ -684,3 +687,200 @@ def greedy_exhaustive(norm, clip):
             flows.append(f)
         naive32[i] = action[0][int(np.argmax(flows))]
     return scn, counts, ob32, want, naive64, naive32
+
+
+# ---------------------------------------------------------------------------
+# generated networks: the seeded sweep of tests/test_networks_random_host.py / tests/test_networks_random_gpu.py
+# ---------------------------------------------------------------------------
+# Lane lengths in m: float32 values (12, 17, 30, 50, 75, 120, 150, 200) mixed with values float32 cannot hold (15.3, 20.1, 23.4, 24.9,
+# 33.3, 41.7, 49.9, 61.7, 99.9, 187.3, 209.9); ten lie below 50 m (the detector starts at 0), six below 25 m; 209.9 m is just inside
+# the 28 x 7.5 m check_limits accepts, and only lanes from about 175 m up can hold the 25 standing vehicles past the hand-off cap.
+RANDOM_SHORT = (12.0, 15.3, 17.0, 20.1, 23.4, 24.9, 30.0, 33.3, 41.7, 49.9)
+RANDOM_MID = (50.0, 61.7, 75.0, 99.9, 120.0, 150.0)
+RANDOM_LONG = (187.3, 200.0, 209.9)
+RANDOM_VMAX = (5.0, 7.3, 8.33, 11.0, 13.89, 16.7, 20.0, 25.0)           # m/s
+_RANDOM_NET = {}
+
+
+def _random_tables(seed):
+    """The draws of random_network(seed): -> (arguments of compile_network, the run).  One RandomState(seed), consumed in one fixed
+    order; nothing else is random."""
+    rng = np.random.RandomState(seed)
+    pick = lambda seq: seq[int(rng.randint(len(seq)))]
+    A = int(rng.randint(1, 9))
+    merge = 'zipper' if rng.rand() < 0.5 else 'yield'
+    interval = int(rng.randint(1, 9))
+    yellow = int(rng.randint(0, min(3, interval - 1) + 1))
+    steps = int(rng.randint(30, 61))
+    T = steps * interval
+    lanes, routes, entries = [], [[] for _ in range(12)], []       # entries: (entry lane, the routes that begin on it)
+    nlink, linkof = [0] * A, {}
+
+    def lane(kind, node):
+        """A new lane: kind -> the share of short, middle and long lengths."""
+        p = {'main': (0.35, 0.35, 0.30), 'feeder': (0.45, 0.40, 0.15), 'short': (0.8, 0.2, 0.0), 'exit': (0.4, 0.5, 0.1)}[kind]
+        table = (RANDOM_SHORT, RANDOM_MID, RANDOM_LONG)[int(rng.choice(3, p=p))]
+        lanes.append((pick(table), pick(RANDOM_VMAX), node))
+        return len(lanes) - 1
+
+    def link(l, nx):
+        """The signal link of the movement l -> nx (-1: l has no signal): one link per movement, now and then behind a link that no
+        lane uses."""
+        a = lanes[l][2]
+        if a < 0:
+            return -1
+        if (l, nx) not in linkof:
+            if nlink[a] < 10 and rng.rand() < 0.15:
+                nlink[a] += 1
+            linkof[(l, nx)] = nlink[a]
+            nlink[a] += 1
+        return linkof[(l, nx)]
+
+    def path(seq):
+        return [(l, link(l, seq[i + 1]) if i + 1 < len(seq) else -1) for i, l in enumerate(seq)]
+
+    def part(ag, max_lanes):
+        """One connected part over the agents ag: a main road of at least three signalised lanes in a row (route 0), an unsignalised
+        lane inside it, exits where the main road diverges (one lane, several routes, different next lanes and links), feeders that
+        merge into main-road lanes (2 - 4 feeders per lane, the merged lane held back by its own junction) and enter on routes of
+        their own.  Route indices start at 0 in every part."""
+        n, first = len(ag), len(lanes)
+        room = lambda k: len(lanes) - first + k <= max_lanes
+        m = max(n, int(rng.randint(3, 6)))
+        main = [lane('main', ag[i * n // m]) for i in range(m)]
+        if rng.rand() < 0.4:
+            main.insert(int(rng.randint(1, m)), lane('short', -1))
+        main.append(lane('exit', -1))
+        r, starts = 1, [0]
+        exits = {}                                                  # position on the main road -> its exit lane
+        for _ in range(int(rng.randint(0, 3))):
+            i = int(rng.randint(0, len(main) - 1))
+            a = lanes[main[i]][2]
+            if i in exits or not room(1) or r >= 12 or (a >= 0 and nlink[a] > 8):
+                continue
+            exits[i] = lane('exit', -1)
+            routes[r].append(path(main[:i + 1] + [exits[i]]))
+            starts.append(r)
+            r += 1
+        routes[0].append(path(main))
+        entries.append((main[0], starts))
+        for j in range(1, len(main)):
+            if rng.rand() >= 0.55:
+                continue
+            for _ in range(int(rng.choice([1, 2, 3], p=[0.35, 0.3, 0.35]))):
+                a = lanes[main[j - 1]][2]
+                if a < 0 or rng.rand() < 0.15 or nlink[a] > 9:
+                    a = -1
+                if not room(1) or r >= 12:
+                    break
+                f = lane('feeder', a)
+                after = [i for i in exits if i >= j]
+                if after and rng.rand() < 0.4:
+                    i = pick(after)
+                    routes[r].append(path([f] + main[j:i + 1] + [exits[i]]))
+                else:
+                    routes[r].append(path([f] + main[j:]))
+                entries.append((f, [r]))
+                r += 1
+
+    if A >= 4 and rng.rand() < 0.4:                                 # two disjoint parts that share their route indices
+        cut = int(rng.randint(1, A))
+        part(list(range(cut)), 18)
+        part(list(range(cut, A)), 18)
+    else:
+        part(list(range(A)), 36)
+    for _ in range(int(rng.randint(0, 4))):                         # lanes no route uses
+        lane('exit', -1)
+    while routes and not routes[-1]:
+        routes.pop()
+
+    phases = []
+    for a in range(A):
+        used = sorted(k for (l, _), k in linkof.items() if lanes[l][2] == a)
+        nl = min(12, nlink[a] + int(rng.randint(0, 3)))
+        P = int(rng.randint(2, 9))
+        rows = [list(rng.choice(list('Ggr'), size=nl, p=[0.35, 0.15, 0.5])) for _ in range(P)]
+        dead = int(rng.randint(P)) if P >= 3 and rng.rand() < 0.3 else -1          # a phase that opens nothing
+        if dead >= 0:
+            rows[dead] = ['r'] * nl
+        for k in used:                                              # every used link is open in some phase
+            if not any(row[k] in 'Gg' for row in rows):
+                p = int(rng.choice([q for q in range(P) if q != dead]))
+                rows[p][k] = 'G' if rng.rand() < 0.7 else 'g'
+        phases.append([''.join(row) for row in rows])
+
+    streams, flows = [], []
+    heavy = int(rng.randint(len(entries)))
+    for i, (l, starts) in enumerate(entries):
+        ns = int(rng.choice([1, 2, 3, 4, 6, 8], p=[0.35, 0.25, 0.15, 0.1, 0.08, 0.07]))
+        base = float(pick((150, 400, 800, 1400, 2200, 3000)))
+        for q in range(ns):
+            s = len(streams)
+            streams.append((l, int(pick(starts))))
+            for _ in range(int(rng.choice([1, 2, 3], p=[0.6, 0.3, 0.1]))):           # (several elements of a stream may overlap)
+                begin = int(rng.randint(0, max(1, (2 * T) // 3)))
+                kind = rng.rand()
+                end = begin if kind < 0.06 else begin + int(rng.randint(1, T + 1)) if kind < 0.8 else T + int(rng.randint(1, 90))
+                vph = 0 if rng.rand() < 0.05 else int(base * rng.uniform(0.3, 1.2) / np.sqrt(ns))
+                flows.append((begin, end, vph, s))
+            if i == heavy and q == 0:                               # one stream heavy enough to queue
+                flows.append((int(rng.randint(0, 4)), T + int(rng.randint(0, 70)), int(rng.randint(1800, 3001)), s))
+
+    agent = str(rng.choice(['ia2c', 'ma2c', 'greedy'], p=[0.3, 0.45, 0.25]))
+    neighbors = []
+    for a in range(A):
+        others = [b for b in range(A) if b != a]
+        k = int(rng.randint(0, min(4, len(others)) + 1))
+        neighbors.append([int(b) for b in rng.choice(others, size=k, replace=False)] if k else [])
+    env_kw = dict(control_interval_sec=interval, yellow_interval_sec=yellow, episode_length_sec=T,
+                  teleport_sec=int(pick((15, 40, 120, 600))), objective=pick(('queue', 'wait', 'hybrid')),
+                  has_wait_state=bool(rng.rand() < 0.6), queue_cap=int(pick((-1, 3, 10))), coop_gamma=float(pick((0.5, 0.75, 0.9))),
+                  norm_wave=float(pick((1.0, 3.0, 5.0))), clip_wave=float(pick((0.8, 2.0, 30.0))),
+                  norm_wait=float(pick((7.0, 30.0, 100.0))), clip_wait=float(pick((0.5, 2.0, 100.0))),
+                  coef_wait=float(pick((0.05, 0.2, 1.0))))
+    run = dict(E=2, steps=steps, p_random=float(rng.uniform(0.1, 0.9)), seed=30000 + 16 * int(seed),
+               peak=int(rng.randint(steps // 2, steps)), sigma=float(pick((0.0, 0.3, 0.5, 1.0))))
+    args = dict(name='random_%d' % seed, agent=agent, lanes=lanes, routes=routes, phases=phases, neighbors=neighbors, flows=flows,
+                streams=streams, merge=merge, **env_kw)
+    return args, run
+
+
+def random_network(seed):
+    """The Net of a generated network, a pure function of the seed (one np.random.RandomState(seed), no global state; the Net is
+    kept, so that every caller shares one compiled scenario).  The scenario goes through compile_network with check = True: it is one
+    that Scenario.check_limits and tsc_env_create accept, and a draw they refuse is a bug of the generator.
+
+    What is drawn, every axis inside its declared limit:
+    * size: 1 - 8 agents, at most 40 lanes and 12 route indices (two disjoint parts share theirs), 2 - 8 phases and 1 - 12 signal
+      links per agent, some links used by no lane;
+    * lanes: lengths from RANDOM_SHORT / RANDOM_MID / RANDOM_LONG (12 - 209.9 m), speed limits from RANDOM_VMAX (5 - 25 m/s), so
+      that many lanes have a limit above their length (a vehicle may cross the whole lane in one second);
+    * topology: a main road of at least three signalised lanes on one route, an unsignalised lane inside it, exits where a lane
+      diverges (several routes, different next lanes and links), merges of 2 - 4 feeders under the network's one merge kind
+      ('zipper' or 'yield'), merged lanes held back by their own junction, lanes no route uses;
+    * phases: strings over G, g, r; every used link is open in some phase of its agent; some phases open nothing;
+    * demand: 1 - 8 streams per entry lane, 0 - 3000 veh/h, windows that begin and end at any second, overlap, are empty or end past
+      the episode, and one stream heavy enough to queue;
+    * configuration: control interval 1 - 8 s, yellow 0 - min(3, interval - 1) s, teleport after 15 / 40 / 120 / 600 s, agent kind
+      (MA2C and IA2C with neighbour lists of 0 - 4 agents, MA2C with a drawn coop_gamma), objective, has_wait_state, queue_cap,
+      norms, clips and coef_wait;
+    * run: E = 2, 30 - 60 control steps (the episode ends with the last one), 10 - 90 % random actions, peak in the second half;
+      net.sigma is the Krauss sigma of the Krauss variant.
+    Not drawn: two-lane streets (lane_sib, MICROSIM_SPEC.md rule 10) -- compile_network carries no connection-level tables, and
+    grid_x2 / grid_x4 cover rule 10 -- nor per-instance demand, trace and lane data, whose walks run on the hand-made networks."""
+    if seed not in _RANDOM_NET:
+        args, run = _random_tables(seed)
+        net = Net(lambda: compile_network(**_random_tables(seed)[0]), 'generated network, seed %d' % seed, None, run['E'], run['steps'],
+                  run['p_random'], run['seed'], run['peak'], 5.0)
+        net.sigma, net.name = run['sigma'], args['name']
+        _RANDOM_NET[seed] = net
+    return _RANDOM_NET[seed]
+
+
+# The 96 seeds of the sweep, chosen on the host: tests/test_networks_random_host.py states what the sample must reach (coverage
+# quotas over the oracle's runs).  0 - 98 without 22, 26 and 78: in those three no vehicle reaches the end of its route before the
+# episode ends (the used links open late or the only exit is held), a run that compares little.
+RANDOM_SEEDS = [s for s in range(99) if s not in (22, 26, 78)]
+# the 24 networks of the kernel-variant and controller cases: 14 with teleports, 13 with a lane at 25 or more vehicles, 14 zipper and
+# 10 yield networks, every control interval from 1 to 8 s
+RANDOM_VARIANT_SEEDS = RANDOM_SEEDS[:24]

@@ -45,10 +45,10 @@ def assert_state(env, state, msg):
 
 def closed_loop(name, E, steps, rule, prm, state_every=7):
     """The device controller drives `steps` control steps of a handle and its oracles; at every step its actions and counts, and every
-    state_every steps and at the end its state, equal the loop rule over the oracles' snapshots.  -> (the handle, the rule's state,
-    the branches taken, the last counts)."""
+    state_every steps and at the end its state, equal the loop rule over the oracles' snapshots.  name: a registry name (scenario),
+    or (scenario, seed) itself.  -> (the handle, the rule's state, the branches taken, the last counts)."""
     from oracle.env_oracle import OracleEnv
-    scn, seed = scenario(name)
+    scn, seed = scenario(name) if isinstance(name, str) else name
     tb = R.tables(scn, rule, prm)
     env = VecTrafficEnv(scn, E, seed=seed)
     orc = [OracleEnv(scn, seed=seed + e) for e in range(E)]

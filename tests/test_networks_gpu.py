@@ -14,73 +14,17 @@ import torch
 from tests import env_harness as H
 from tests import networks as nw
 from tests.env_harness import oracle_krauss
-from tests.env_rules import assert_trips_equal, check_record_tables, device_trips
 
 pytestmark = pytest.mark.gpu
 
 
 def _compare(name, monkeypatch, plan=None, env=None, scn=None, train_mode=True, record=False):
-    """The one comparison of this module: VecTrafficEnv(scn, E, seed) against E OracleEnvs over the entry's run (networks.run_oracle
-    draws the actions: seeded random choices mixed with a greedy rule on the oracle's observations).  Bit for bit: observations,
-    local or shaped rewards, global_reward, done, the full vehicle state after the entry's peak step and at the end, counters() and
-    reward_sum(); with record also the per-second record rows, the control rows and the trip log.
+    """The one comparison of this module (env_harness.compare_with_oracle) over the registry entry `name`.
     plan: what step_plan() must report after the first reset (row + threads); env: TSC_ENV_* variables on top of the entry's own;
     scn: a variant of the entry's scenario (Krauss: inside oracle_krauss)."""
-    from deeprl_signal_control_amd.env import VecTrafficEnv
     net = nw.NETWORKS[name]
-    scn = net.scenario() if scn is None else scn
-    for k in ('TSC_ENV_THREADS', 'TSC_ENV_KF', 'TSC_ENV_HELP', 'TSC_ENV_SPEC'):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in dict(net.env, **(env or {})).items():
-        monkeypatch.setenv(k, v)
-    E, A = net.E, scn.n_agent
-    dev = VecTrafficEnv(scn, E, seed=net.seed, test_seeds=H.eval_seeds(net))
-    try:
-        dev.train_mode = train_mode
-        if record:
-            dev.set_record(True)
-        acc = np.zeros(E)                       # tsc_env_reward_sum: per instance in step order, then over the instances in order
-        side = H.run_oracle(scn, net, train_mode=train_mode, is_record=record)
-        _, _, _, res, orc = next(side)                              # the oracles' reset
-        obs = dev.reset(test_ind=np.arange(E)).cpu().numpy()
-        dev.reward_sum(reset=True)
-        if plan is not None:
-            got = dev.step_plan()
-            assert got['row'] + (got['threads'],) == tuple(plan), (got, plan)
-            assert got['lds_bytes'] <= 160 * 1024
-        for e in range(E):
-            for a in range(A):
-                np.testing.assert_array_equal(obs[e, a, :scn.n_s_ls[a]], res[e][a].astype(np.float32), err_msg='reset e=%d a=%d' % (e, a))
-            assert not obs[e].reshape(A, -1)[np.arange(scn.s_max)[None, :] >= np.array(scn.n_s_ls)[:, None]].any()
-        last = []
-
-        def after(t, out, res, orc):
-            for e in range(E):
-                acc[e] += res[e][3]
-            last[:] = res
-        H.follow(dev, side, state_at=(net.peak, net.steps - 1), after=after)
-        assert all(bool(x[2]) for x in last)                        # the episode ended inside the run
-        tot = H.assert_counters_equal(dev, orc)
-        want = 0.0
-        for e in range(E):
-            want += acc[e]
-        assert dev.reward_sum() == want
-        if record:
-            dev.collect_tripinfo()
-            for e, oe in enumerate(orc):
-                oe.collect_tripinfo()
-                gold = {}
-                for kind, rows in (('traffic', oe.traffic_data), ('control', oe.control_data), ('trip', oe.trip_data)):
-                    for k in rows[0]:
-                        gold['%s_%s' % (kind, k)] = np.array([row[k] for row in rows])
-                check_record_tables(gold, dev.traffic_data[e], dev.control_data[e], dev.trip_data[e])
-                assert len(dev.traffic_data[e]) == net.steps * scn.control_interval_sec
-                assert dev.teleported_trips[e] == getattr(oe, 'teleported_trips', 0)
-                ref = np.array(oe.ms.trips(), np.int32).reshape(-1, 6)
-                assert_trips_equal(device_trips(dev, e), ref, 'trip rows e=%d' % e)
-        return tot
-    finally:
-        dev.close()
+    return H.compare_with_oracle(net.scenario() if scn is None else scn, net, monkeypatch, plan=plan, env=env, train_mode=train_mode,
+                                 record=record)
 
 
 @pytest.mark.parametrize('name', list(nw.NETWORKS))
