@@ -1923,6 +1923,9 @@ struct tsc_env {
     StepPlan plan;                  // what tsc_env_step launches (plan_step)
     uint32_t *d_seeds;
     std::vector<int> h_mode, h_sroute;      // host copies of the stream tables (tsc_env_set_stream_routes)
+    std::vector<int> h_cand;                // [NS][KC] a stream's candidates: its interval-0 routes up to the first pad, then -1
+    std::vector<int> ir_next;               // [E][NS] the routes the next reset uploads into P.iroute (tsc_env_set_stream_routes)
+    bool ir_dirty = false;
     int *order_buf = nullptr;       // tsc_env_set_block_order
     bool auto_threads;              // the workgroup size follows the number of instances resident on the device (pick_workgroup)
     int kf_default;
@@ -2184,12 +2187,19 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
             const int md = sc->stream_mode[s_];
             if (md < 0 || md > 2) return tsc::fail("tsc_env_create: stream %d has mode %d", s_, md);
             sr[s_] = sc->stream_choice[(size_t)s_ * NI * KC * 2];
-            if (sr[s_] < 0) return tsc::fail("tsc_env_create: stream %d has no route", s_);
+            // a mode-1 stream draws from the table of the second it inserts in: a table that begins with a pad would hand out route -1
+            for (int iv = 0; iv < (md == 1 ? NI : 1); ++iv)
+                if (sc->stream_choice[((size_t)s_ * NI + iv) * KC * 2] < 0)
+                    return tsc::fail("tsc_env_create: stream %d has no route in interval %d", s_, iv);
             if (md != 0 || sr[s_] != s_) identity = false;
             if (sc->stream_origin && sc->stream_origin[s_] != 0.0f) any_origin = true;
             if (sc->stream_limit && sc->stream_limit[s_] < sc->lane_len[stream_entry(s_)]) any_origin = true;
         }
         h->h_mode.assign(sc->stream_mode, sc->stream_mode + NS); h->h_sroute = sr;
+        h->h_cand.assign((size_t)NS * KC, -1);
+        for (int s_ = 0; s_ < NS; ++s_)
+            for (int c = 0; c < KC && sc->stream_choice[((size_t)s_ * NI * KC + c) * 2] >= 0; ++c)
+                h->h_cand[(size_t)s_ * KC + c] = sc->stream_choice[((size_t)s_ * NI * KC + c) * 2];
         if (!identity) {                              // fixed one-to-one streams keep the round-2 fast path (sroute == null)
             TSC_HIP(h->bufs.upload(&P.sroute, sr.data(), NS));
             TSC_HIP(h->bufs.upload(&P.smode, sc->stream_mode, NS));
@@ -2573,6 +2583,10 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev) {
     TSC_HIP(hipMemcpyAsync(h->d_seeds, seeds_host, sizeof(uint32_t) * h->P.E, hipMemcpyHostToDevice, h->stream));
     if (h->P.trace_cnt)                                // tsc_env_trace: cursors and per-second counts start over
         TSC_HIP(hipMemsetAsync(h->P.trace_cnt, 0, sizeof(int) * (size_t)h->n_trace * (h->P.episode + 1), h->stream));
+    if (h->ir_dirty) {                                 // tsc_env_set_stream_routes takes effect here
+        TSC_HIP(hipMemcpyAsync(h->P.iroute, h->ir_next.data(), sizeof(int) * h->ir_next.size(), hipMemcpyHostToDevice, h->stream));
+        h->ir_dirty = false;
+    }
     if (h->dem_dirty) {                                // tsc_env_set_demand takes effect here
         EnvDev &P = h->P;
         if (h->dem_next.empty()) { P.emit_tab = h->emit_shared; P.emit_inst = 0; }
@@ -2736,11 +2750,15 @@ int tsc_env_set_stream_routes(tsc_env *h, const int32_t *routes_host) {
             if (h->h_mode[s_] == 2) {
                 r = routes_host[(size_t)e * P.NS + s_];
                 if (r < 0 || r >= P.NR) return tsc::fail("tsc_env_set_stream_routes: instance %d stream %d: route %d of %d", e, s_, r, P.NR);
+                // only a candidate's lanes were walked for the live-lane prefix: another route may lead onto a lane without a thread
+                bool cand = false;
+                for (int c = 0; c < P.KC && !cand; ++c) cand = h->h_cand[(size_t)s_ * P.KC + c] == r;
+                if (!cand) return tsc::fail("tsc_env_set_stream_routes: instance %d stream %d: route %d is not one of the stream's candidates", e, s_, r);
             }
             ir[(size_t)e * P.NS + s_] = r;
         }
-    TSC_HIP(hipMemcpyAsync(P.iroute, ir.data(), sizeof(int) * ir.size(), hipMemcpyHostToDevice, h->stream));
-    TSC_HIP(hipStreamSynchronize(h->stream));
+    h->ir_next.swap(ir);                         // staged: tsc_env_reset uploads them; a running episode keeps its routes
+    h->ir_dirty = true;
     return 0;
 }
 

@@ -349,6 +349,23 @@ class Scenario:
             raise ValueError('%d routes / %d insertion streams: at most 254 each (route ids and stream lists are bytes on the device): '
                              'let disjoint parts of the network share route indices, merge the flow elements of streams that share '
                              'an entry lane and a route' % (self.n_route, self.n_stream))
+        if self.stream_entry_lane is not None:
+            ch = None if self.stream_choice is None else np.asarray(self.stream_choice)
+            if (self.stream_mode is None or ch is None or ch.ndim != 4 or ch.shape[0] != self.n_stream or ch.shape[1] < 1 or ch.shape[2] < 1
+                    or ch.shape[3] != 2 or len(self.stream_mode) != self.n_stream or self.choice_interval_sec < 1):
+                raise ValueError('incomplete stream tables: declared streams need stream_mode [NS], stream_choice [NS, NI >= 1, KC >= 1, 2] '
+                                 'and choice_interval_sec >= 1')
+            if int(ch[..., 0].max()) >= self.n_route:
+                s_ = int(np.argwhere(ch[..., 0] >= self.n_route)[0][0])
+                raise ValueError('stream %d names route %d of %d' % (s_, int(ch[s_, :, :, 0].max()), self.n_route))
+            for s_, md in enumerate(np.asarray(self.stream_mode).tolist()):
+                if not 0 <= md <= 2:
+                    raise ValueError('stream %d has mode %d: 0 (fixed route), 1 (per-vehicle draw) or 2 (per-episode route)' % (s_, md))
+                # a mode-1 stream draws from the table of the second it inserts in: every one of them must begin with a route
+                for iv in range(ch.shape[1] if md == 1 else 1):
+                    if ch[s_, iv, 0, 0] < 0:
+                        raise ValueError('stream %d has no route in interval %d: a choice table begins with a route, pads (-1) '
+                                         'only end it' % (s_, iv))
         entry = self.route_entry_lane if self.stream_entry_lane is None else self.stream_entry_lane
         per_lane = np.bincount(np.asarray(entry, np.int64)[np.asarray(entry) >= 0], minlength=1)
         if per_lane.max() > MAX_ENTRY:

@@ -143,7 +143,10 @@ int tsc_env_reset(tsc_env *h, const uint32_t *seeds_host, float *obs_dev);
 
 /* Routes of the mode-2 streams for the NEXT reset(): host int32 [E, n_stream] (entries of other streams are ignored) --
  * what gen_rou_file(seed) would write for every instance's episode seed (the caller draws them; env.py does it with
- * numpy's RandomState(seed), the generator the reference's np.random.seed(seed) + np.random.choice uses). */
+ * numpy's RandomState(seed), the generator the reference's np.random.seed(seed) + np.random.choice uses).  The routes are kept
+ * on the host and uploaded by the next tsc_env_reset: a running episode keeps the routes it was reset with.  A route must be one
+ * of its stream's candidates -- stream_choice[s][0][.], up to the first pad -- because only their lanes count as live; any other
+ * route is an error (tsc_last_error names instance, stream and route) and the handle keeps the routes it had. */
 int tsc_env_set_stream_routes(tsc_env *h, const int32_t *routes_host);
 
 /* Per-instance traffic demand.  vph: host int32 [E, n_flow], the veh/h of flow element f for env instance e in place of

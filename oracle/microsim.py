@@ -37,6 +37,7 @@ def lib():
         L.ms_lane_vehicles.argtypes = [C.c_void_p, C.c_int, fp, fp, ip, ip, ip, fp]
         L.ms_time.argtypes = [C.c_void_p]
         L.ms_totals.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.ms_stream_state.argtypes = [C.c_void_p, ip, ip]
         L.ms_check.argtypes = [C.c_void_p]
         L.ms_record.argtypes = [C.c_void_p, C.c_int]
         L.ms_trips.argtypes = [C.c_void_p, ip, C.c_int]
@@ -239,6 +240,13 @@ class MicroSim:
         self.L.ms_totals(self.h, out)
         return dict(live=out[0], departed=out[1], arrived=out[2], sum_trip=out[3], pending=out[4],
                     step_departed=out[5], step_arrived=out[6], teleported=out[7])
+
+    def stream_state(self):
+        """(pending, serial) per insertion stream, int32 [NS] each: what VecTrafficEnv.get_state() calls 'pending' and 'serial'."""
+        ip = C.POINTER(C.c_int32)
+        pend, ser = np.zeros(self.scn.n_stream, np.int32), np.zeros(self.scn.n_stream, np.int32)
+        self.L.ms_stream_state(self.h, pend.ctypes.data_as(ip), ser.ctypes.data_as(ip))
+        return pend, ser
 
     def check(self):
         return self.L.ms_check(self.h)

@@ -18,7 +18,11 @@ end of this file, lists those runs for tests/test_networks_aux_host.py and tests
 exist for them.
 
 random_network(seed), behind AUX, draws whole networks inside every limit at once -- the seeded sweep of
-tests/test_networks_random_host.py and tests/test_networks_random_gpu.py over RANDOM_SEEDS."""
+tests/test_networks_random_host.py and tests/test_networks_random_gpu.py over RANDOM_SEEDS.
+
+The insertion streams -- route modes, choice tables that change in time, insertion windows -- have networks of their own (forks,
+ratios_in_time, sinks, windows_on_lane) and random_stream_network(seed), which redraws the stream tables of random_network(seed):
+tests/test_streams_host.py and tests/test_streams_gpu.py over RANDOM_STREAM_SEEDS."""
 import copy
 
 import numpy as np
@@ -156,7 +160,57 @@ def reachable_prefix(scn):
 # ---------------------------------------------------------------------------
 # a compiler for hand-made networks
 # ---------------------------------------------------------------------------
-def compile_network(name, agent, lanes, routes, phases, neighbors, flows, streams=None, merge='zipper', check=True, **env_kw):
+def stream_hash(seed, stream, serial, k):
+    """The counter-based hash of MICROSIM_SPEC.md rule 6 in Python integers: draw k of the vehicle `serial` of `stream` under the
+    instance's episode seed (k = 0 position, 1 and 2 speed factor, 3 route)."""
+    m = 0xFFFFFFFF
+    h = (seed * 0x9E3779B1 + stream * 0x85EBCA77 + serial * 0xC2B2AE3D + k * 0x27D4EB2F) & m
+    h ^= h >> 16
+    h = h * 0x85EBCA6B & m
+    h ^= h >> 13
+    h = h * 0xC2B2AE35 & m
+    return h ^ h >> 16
+
+
+def route_draw16(seed, stream, serial):
+    """The 16-bit number a mode-1 stream's vehicle compares with the cumulative weights of its table."""
+    return stream_hash(int(seed) & 0xFFFFFFFF, stream, serial, 3) >> 16
+
+
+def table_route(table, u16):
+    """The route a [KC, 2] table of (route, cumulative weight) pairs gives the draw u16: the first pair with u16 < weight; a pad
+    (-1) ends the list, and a draw no weight exceeds takes the last route before it."""
+    rt = int(table[0][0])
+    for r, w in table:
+        if r < 0:
+            break
+        rt = int(r)
+        if u16 < w:
+            break
+    return rt
+
+
+def _stream_tables(streams, lane_len):
+    """The stream tables of compile_network's dict form -> keywords of Scenario.  A tuple (entry lane, route) among dicts is the
+    mode-0 stream with the one choice (route, 65536).  A stream with fewer intervals than the longest repeats its last table."""
+    full = [s if isinstance(s, dict) else dict(lane=s[0], mode=0, choice=[[(s[1], 65536)]]) for s in streams]
+    NS, NI = len(full), max(len(s['choice']) for s in full)
+    KC = max(len(row) for s in full for row in s['choice'])
+    choice = np.zeros((NS, NI, KC, 2), np.int32)
+    choice[..., 0] = -1
+    for i, s in enumerate(full):
+        assert set(s) <= {'lane', 'mode', 'choice', 'origin', 'limit'}, sorted(s)
+        for iv in range(NI):
+            row = s['choice'][min(iv, len(s['choice']) - 1)]
+            choice[i, iv, :len(row)] = np.asarray(row, np.int32).reshape(-1, 2)
+    entry = np.array([s['lane'] for s in full], np.int32)
+    return dict(stream_entry_lane=entry, stream_mode=np.array([s['mode'] for s in full], np.int32), stream_choice=choice,
+                stream_origin=np.array([s.get('origin', 0.0) for s in full], np.float32),
+                stream_limit=np.array([s.get('limit', lane_len[s['lane']]) for s in full], np.float32))
+
+
+def compile_network(name, agent, lanes, routes, phases, neighbors, flows, streams=None, merge='zipper', check=True,
+                    choice_interval_sec=None, **env_kw):
     """A Scenario from a hand-made network.
     lanes: (length m, speed limit m/s, downstream agent or -1) per lane.
     routes: per route index a list of paths; a path is a list of (lane, signal link of the hop that leaves it, -1 = none); the last
@@ -164,7 +218,10 @@ def compile_network(name, agent, lanes, routes, phases, neighbors, flows, stream
         keyed by (lane, route) and a stream names its entry lane -- which keeps n_live_lanes x n_route small with many agents.
     phases: per agent its phase strings (one char per signal link); neighbors: per agent a list of agents.
     flows: (begin, end, veh/h, stream).  streams: (entry lane, route) per insertion stream; None = route r is stream r and enters at
-        the first lane of its only path.
+        the first lane of its only path.  A stream may also be a dict: lane, mode (0 fixed route, 1 a draw per vehicle, 2 a route
+        per instance and episode from the host), choice = per interval a list [(route, cumulative weight of 65536), ...] (padded
+        with (-1, 0) to the longest, the k_choice of the scenario) and, optionally, origin and limit in metres, the stretch of the
+        entry lane the stream inserts on (default: the whole lane).  choice_interval_sec: the length of a choice interval.
     merge: what arbitrates a lane with several feeders -- 'zipper' (mv_zip = rank | count << 8, rank = position among the ascending
         feeders) or 'yield' (the lowest feeder has priority, the others yield to its head).
     Derived: lane_up, the mv_* tables, the agents' lanes (dedup of their links' lanes in link order) and the signal / observation
@@ -226,7 +283,11 @@ def compile_network(name, agent, lanes, routes, phases, neighbors, flows, stream
     obs_kind, obs_src, lens = _obs_table(agent, agent_lanes, nlane, n_a_ls, neighbors, has_wait, max(n_a_ls))
     green, yellow = _signal_tables(phases, kmax)
     stream_kw = {}
-    if streams is not None:
+    if streams is not None and any(isinstance(s, dict) for s in streams):
+        stream_kw = _stream_tables(streams, lane_len)
+        if choice_interval_sec is not None:
+            stream_kw['choice_interval_sec'] = int(choice_interval_sec)
+    elif streams is not None:
         choice = np.zeros((len(streams), 1, 1, 2), np.int32)
         choice[:, 0, 0, 0] = [s[1] for s in streams]
         choice[:, 0, 0, 1] = 65536
@@ -440,6 +501,18 @@ def demand254_columns(scn, E):
     return cols
 
 
+def ratios_columns(scn):
+    """The veh/h columns of the per-instance demand run on ratios_in_time(), int32 [3, n_flow]: the scenario's own, every rate
+    redrawn, and one with the held-back stream (2) at two vehicles a second and stream 3 silent."""
+    nominal = np.asarray(scn.flows)[:, 2].astype(np.int32)
+    cols = np.tile(nominal, (3, 1))
+    cols[1] = np.random.RandomState(78).randint(200, 2500, len(nominal))
+    by_stream = np.asarray(scn.flows)[:, 3]
+    cols[2, by_stream == 2] = 7200
+    cols[2, by_stream == 3] = 0
+    return cols
+
+
 def split_pieces(scn, cuts):
     """A copy of scn whose lanes named in cuts = {lane name: ascending cut positions in m} are made of len(cuts) + 1 SUMO lanes
     '<name>#0', '<name>#1', ... that each begin at 0: lane_pieces only, which the lane data and the trajectories' SUMO positions
@@ -512,7 +585,117 @@ NETWORKS = {
 }
 NETWORKS['windows'] = Net(windows, 'flow windows that begin and end inside a 4-second word of the emission table; 1 s control interval',
                           _NARROW + (256,), 3, 120, 0.3, 510, 60, 8.0)
-RECORDED = ['grid_x4']         # the one plan behind the LDS budget (whether k = 4 fits): as reported by an MI355X handle
+
+
+# ---- insertion streams: route modes, choice tables in time, insertion windows (tests/test_streams_host.py, tests/test_streams_gpu.py)
+FORKS_SEED = 520
+FORKS_EDGE = (6, 0)             # (stream, serial): the vehicle of instance 0 whose draw equals its table's first weight
+
+
+def forks():
+    """One entry lane (0) whose road diverges twice -- route 0: 0 -> 1 -> 2, route 1: 0 -> 3, route 2: 0 -> 1 -> 4 -- and eight
+    mode-1 streams on it (MAX_ENTRY), each with a table of its own (k_choice 6, one interval):
+      0: a first choice of weight 0 (never taken);            1: one choice at 65536 (always taken; a table of one pair);
+      2: weights 1 and 65535;                                 3: a last weight below 65536 (draws past it take the last route);
+      4: a pad in the middle (it ends the list: route 2 behind it is never taken);
+      5: six pairs;                                           7: two pairs;
+      6: a first weight equal to the draw of its own first vehicle in instance 0 (FORKS_EDGE): `draw < weight` is false there
+         and the vehicle takes the second route -- the one vehicle that tells < from <=.
+    All eight emit a vehicle in second 0 and in every 30th second after it, on top of a light steady rate, so that several of them
+    insert in one second on a lane that has drained in between."""
+    lanes = [(150.0, 13.89, 0), (120.0, 13.89, 1), (100.0, 13.89, -1), (80.0, 11.0, -1), (80.0, 11.0, -1)]
+    routes = [[[(0, 0), (1, 0), (2, -1)]], [[(0, 1), (3, -1)]], [[(0, 0), (1, 1), (4, -1)]]]
+    edge = route_draw16(FORKS_SEED, *FORKS_EDGE)
+    tables = [[(1, 0), (0, 65536)],
+              [(2, 65536)],
+              [(0, 1), (1, 65535), (2, 65536)],
+              [(0, 20000), (1, 40000)],
+              [(0, 30000), (-1, 0), (2, 65536)],
+              [(0, 10000), (1, 20000), (2, 30000), (0, 40000), (1, 50000), (2, 65536)],
+              [(1, edge), (2, 65536)],
+              [(2, 16384), (0, 65536)]]
+    streams = [dict(lane=0, mode=1, choice=[t]) for t in tables]
+    flows = [(0, 300, 60 + 5 * s, s) for s in range(8)] + [(b, b + 1, 3600, s) for b in range(30, 300, 30) for s in range(8)]
+    return compile_network('forks', 'ia2c', lanes, routes, [['GG', 'Gr', 'rG'], ['GG', 'rG', 'Gr']], [[1], [0]], flows, streams,
+                           episode_length_sec=300, teleport_sec=120)
+
+
+RATIOS_INTERVAL = 7
+
+
+def ratios_in_time():
+    """Mode-1 streams whose tables change every 7 s, four times (n_interval 4), under a 5 s control interval: the boundaries at 7,
+    14 and 21 s fall inside control steps, and from 28 s on the last table stays in force.  Entry lane 0 diverges like forks():
+    0 -> 1 -> 2 (routes 2 and 5), 0 -> 3 (routes 3 and 6), 0 -> 1 -> 4 (routes 4 and 7); stream 0 draws among 2, 3 and 4, stream 1
+    among 5, 6 and 7.  Routes 4 and 7 appear in the intervals 2 and 3 only, and lane 4 is used by no other route -- the live lanes
+    include it only if the walk reads every interval.  Entry lane 5 is 20.1 m short behind a signal that is red in three of four
+    phases (routes 0 and 8: 5 -> 6, route 1: 5 -> 7): stream 2 emits a vehicle a second for 25 s, so its backlog stands across
+    every boundary, and a vehicle draws from the table of the second it is inserted in.  Stream 3 is a mode-0 stream on the same
+    lane.  No two streams share a route -- the trace knows a vehicle by (route, serial, entry lane) -- and no stream index equals
+    a route the stream can take."""
+    lanes = [(150.0, 13.89, 0), (120.0, 13.89, 1), (100.0, 13.89, -1), (80.0, 11.0, -1), (90.0, 11.0, -1),
+             (20.1, 13.89, 2), (100.0, 13.89, -1), (100.0, 13.89, -1)]
+    main, off, late = [(0, 0), (1, 0), (2, -1)], [(0, 1), (3, -1)], [(0, 0), (1, 1), (4, -1)]
+    routes = [[[(5, 0), (6, -1)]], [[(5, 1), (7, -1)]], [main], [off], [late], [main], [off], [late], [[(5, 0), (6, -1)]]]
+    streams = [
+        dict(lane=0, mode=1, choice=[[(2, 40000), (3, 65536)], [(3, 65536)], [(4, 30000), (2, 65536)], [(2, 20000), (3, 40000), (4, 65536)]]),
+        dict(lane=0, mode=1, choice=[[(6, 65536)], [(5, 65536)], [(5, 50000)], [(7, 65536)]]),
+        dict(lane=5, mode=1, choice=[[(0, 65536)], [(1, 65536)], [(0, 32768), (1, 65536)], [(1, 20000), (0, 65536)]]),
+        (5, 8)]
+    flows = [(0, 60, 1800, 0), (60, 300, 500, 0), (0, 40, 1200, 1), (40, 300, 300, 1), (0, 25, 3600, 2), (100, 300, 300, 2), (30, 300, 200, 3)]
+    return compile_network('ratios_in_time', 'ia2c', lanes, routes, [['GG', 'Gr', 'rG'], ['GG', 'rG', 'Gr'], ['rr', 'rr', 'rr', 'GG']],
+                           [[1], [0], []], flows, streams, choice_interval_sec=RATIOS_INTERVAL, episode_length_sec=300, teleport_sec=120)
+
+
+def sinks(ragged=True):
+    """Mode-2 streams (the route of an instance's episode comes from the host, drawn among the stream's candidates) on two fans:
+    lane 0 -> lanes 1 .. 5 (routes 0 .. 4) and lane 6 -> lanes 7 .. 9 (routes 5 .. 7).  ragged: 5, 3, 2, 1 and 2 candidates (k_choice
+    5, the shorter lists padded), which scenario.draw_stream_routes draws one stream after the other; else two candidates each, its
+    vectorised branch.  A mode-0 and a mode-1 stream sit between them: their entries of the host's route array are ignored."""
+    lanes = [(200.0, 13.89, 0)] + [(80.0 + 5.0 * i, 11.0, -1) for i in range(5)] + [(150.0, 13.89, 1)] + [(90.0, 11.0, -1)] * 3
+    routes = [[[(0, i), (1 + i, -1)]] for i in range(5)] + [[[(6, i), (7 + i, -1)]] for i in range(3)]
+    cands = [[0, 1, 2, 3, 4], [5, 6, 7], [6, 7], [5], [4, 0]] if ragged else [[0, 4], [5, 7], [6, 7], [5, 6], [4, 0]]
+    m2 = [dict(lane=l, mode=2, choice=[[(r, 65536) for r in c]]) for l, c in zip((0, 6, 6, 6, 0), cands)]
+    streams = [m2[0], (0, 2), m2[1], dict(lane=0, mode=1, choice=[[(1, 30000), (3, 65536)]]), m2[2], m2[3], m2[4]]
+    flows = [(0, 300, 300 + 40 * s, s) for s in range(7)]
+    return compile_network('sinks_ragged' if ragged else 'sinks_even', 'ia2c', lanes, routes,
+                           [['GGGGG', 'GGrrr', 'rrGGG', 'GrGrG'], ['GGG', 'Grr', 'rGG']], [[1], [0]], flows, streams,
+                           episode_length_sec=300, teleport_sec=120)
+
+
+WINDOW_FIT = (150.0, 155.0)     # exactly one vehicle length: on an empty lane xlo = 150 + 5 = xmax
+WINDOW_NARROW = (30.0, 34.9)    # less than one: xmax < xlo always
+
+
+def windows_on_lane():
+    """One 200 m entry lane with four streams and their insertion windows: 0: [0, 200] given explicitly; 1: [61.7, 120.1] (no
+    float32 values); 2: WINDOW_FIT, which takes a vehicle only at 155 m and only while no vehicle stands behind 162 m; 3:
+    WINDOW_NARROW, which never inserts -- its backlog grows to the end.  Stream 2's window lies ahead of stream 1's: when both
+    wait, stream 1 inserts first and its vehicle is the tail stream 2 finds.  Streams 0 and 1 pause (0 - 10 s, 120 - 170 s), so
+    that the lane drains and stream 2 finds it empty.  Every stream has a route of its own over the same two lanes (the trace
+    knows a vehicle by (route, serial, entry lane))."""
+    lanes = [(200.0, 13.89, 0), (100.0, 13.89, -1)]
+    windows = [(0.0, 200.0), (61.7, 120.1), WINDOW_FIT, WINDOW_NARROW]
+    streams = [dict(lane=0, mode=0, choice=[[(s, 65536)]], origin=o, limit=hi) for s, (o, hi) in enumerate(windows)]
+    flows = [(10, 120, 400, 0), (170, 300, 400, 0), (20, 120, 400, 1), (170, 300, 300, 1), (0, 300, 240, 2), (0, 300, 360, 3)]
+    return compile_network('windows_on_lane', 'ia2c', lanes, [[[(0, 0), (1, -1)]]] * 4, [['G', 'r']], [[]], flows, streams,
+                           episode_length_sec=300, teleport_sec=120)
+
+
+NETWORKS['forks'] = Net(forks, 'eight mode-1 streams on one lane: every edge of the cumulative-weight lookup', _NARROW + (256,),
+                        3, 60, 0.4, FORKS_SEED, 30, 5.0)
+NETWORKS['ratios_in_time'] = Net(ratios_in_time, 'choice tables that change inside control steps; a backlog across the boundaries',
+                                 _NARROW + (256,), 3, 60, 0.8, 530, 8, 5.0)
+NETWORKS['sinks_ragged'] = Net(sinks, 'mode-2 streams with 1, 2, 3 and 5 candidates between streams of the other modes',
+                               _NARROW + (256,), 3, 60, 0.4, 546, 30, 5.0)
+NETWORKS['windows_on_lane'] = Net(windows_on_lane, 'insertion windows: whole lane, inner, exactly one vehicle, less than one',
+                                  _NARROW + (256,), 3, 60, 0.4, 550, 30, 3.0)
+SINKS_EVEN = Net(lambda: sinks(ragged=False), 'mode-2 streams with two candidates each: the vectorised draw', _NARROW + (256,),
+                 3, 60, 0.4, 546, 30, 5.0)
+STREAM_NETWORKS = ['forks', 'ratios_in_time', 'sinks_ragged', 'windows_on_lane']
+# grid_x4: the one plan behind the LDS budget (whether k = 4 fits); the stream networks: the plan of the generic kernel with the stream
+# tables uploaded.  As reported by an MI355X handle
+RECORDED = ['grid_x4'] + STREAM_NETWORKS
 
 
 def _routes255():
@@ -637,7 +820,10 @@ AUX = {
              Aux('ctrl1', 'ctrl1', 2, None, period=7, watch=[0, 1], seed=24, rng_seed=6),
              Aux('merge4_pieces', 'merge4_zipper', 3, None, period=60, watch=[0, 2], seed=25, rng_seed=7),
              Aux('grid_x2', 'grid_x2', 2, 60, period=60, watch=[1], seed=26, rng_seed=8),
-             Aux('merge4_krauss', 'merge4_zipper', 3, None, period=60, watch=[1, 2], seed=27, rng_seed=9)],
+             Aux('merge4_krauss', 'merge4_zipper', 3, None, period=60, watch=[1, 2], seed=27, rng_seed=9),
+             # the insertion windows and the choice tables in time, vehicle by vehicle (every stream has routes of its own there)
+             Aux('windows_on_lane', 'windows_on_lane', 3, None, period=45, watch=[0, 2], seed=29, rng_seed=11),
+             Aux('ratios_in_time', 'ratios_in_time', 3, None, period=50, watch=[0, 1], seed=30, rng_seed=12)],
     'trace254': Aux('isolated_254', 'isolated_254', 2, 12, watch=[1], seed=28, rng_seed=10),
     # tsc_env_set_demand on windows(): instance e runs column e of windows_columns; isolated_254: demand_kernel on a 254 x 3 grid
     'demand': Aux('windows', 'windows', 4, WINDOWS_EPISODE, seed=600),
@@ -884,3 +1070,94 @@ RANDOM_SEEDS = [s for s in range(99) if s not in (22, 26, 78)]
 # the 24 networks of the kernel-variant and controller cases: 14 with teleports, 13 with a lane at 25 or more vehicles, 14 zipper and
 # 10 yield networks, every control interval from 1 to 8 s
 RANDOM_VARIANT_SEEDS = RANDOM_SEEDS[:24]
+
+
+# ---------------------------------------------------------------------------
+# generated networks with redrawn stream tables: tests/test_streams_host.py / tests/test_streams_gpu.py
+# ---------------------------------------------------------------------------
+_RANDOM_STREAM_NET = {}
+VEH_LEN_M = 5.0                 # MICROSIM_SPEC.md rule 6: a window shorter than one vehicle never inserts
+
+
+def _random_stream_tables(seed):
+    """The arguments of random_network(seed) with the stream tables redrawn from a generator of their own, RandomState(10000 + seed):
+    -> (arguments of compile_network, the run).  Lanes, routes, phases, flows and the configuration are _random_tables' own."""
+    args, run = _random_tables(seed)
+    rng = np.random.RandomState(10_000 + seed)
+    pick = lambda seq: seq[int(rng.randint(len(seq)))]
+    lanes, routes = args['lanes'], args['routes']
+    NI, ilen = int(rng.randint(1, 5)), int(rng.randint(3, 41))
+    streams = []
+    for l, r in args['streams']:
+        starts = [q for q, paths in enumerate(routes) if any(p[0][0] == l for p in paths)]      # the routes that begin on the lane
+        assert r in starts
+        u = rng.rand()
+        mode = 0 if len(starts) < 2 or u >= 0.85 else 1 if u < 0.5 else 2
+        if mode == 1:                           # per interval 1 .. len(starts) + 1 pairs, ascending weights that need not reach 65536
+            choice = []
+            for _ in range(NI):
+                k = int(rng.randint(1, len(starts) + 2))
+                w = sorted(int(x) for x in rng.randint(0, 65537, k))
+                if rng.rand() < 0.5:
+                    w[-1] = 65536
+                choice.append([(int(pick(starts)), x) for x in w])
+        elif mode == 2:
+            choice = [[(int(pick(starts)), 65536) for _ in range(int(rng.randint(1, len(starts) + 2)))]]
+        else:
+            choice = [[(r, 65536)]]
+        s = dict(lane=l, mode=mode, choice=choice)
+        L = lanes[l][0]
+        cuts = [0.0] + [x for x in RANDOM_SHORT + RANDOM_MID + RANDOM_LONG if x <= L]
+        pairs = [(a, b) for a in cuts for b in cuts if b - a >= VEH_LEN_M and (a, b) != (0.0, L)]
+        if rng.rand() < 0.5 and pairs:          # a window inside the lane, at least one vehicle long
+            s['origin'], s['limit'] = pick(pairs)
+        streams.append(s)
+    return dict(args, name='random_stream_%d' % seed, streams=streams, choice_interval_sec=ilen), run
+
+
+def random_stream_network(seed):
+    """random_network(seed) with other stream tables -- the network, the demand, the configuration and the run are the same, a pure
+    function of the seed.  A stream on an entry lane where two or more routes begin is a mode-1 stream (50 %: 1 - 4 intervals of
+    3 - 40 s for the whole scenario, per interval 1 to len(starts) + 1 pairs with ascending weights that reach 65536 half of the
+    time), a mode-2 stream (35 %: 1 to len(starts) + 1 candidates, repeats allowed) or keeps its route; half of all streams
+    insert on a window inside their lane whose ends come from the length tables."""
+    if seed not in _RANDOM_STREAM_NET:
+        args, run = _random_stream_tables(seed)
+        net = Net(lambda: compile_network(**_random_stream_tables(seed)[0]), 'generated network with redrawn stream tables, seed %d' % seed,
+                  None, run['E'], run['steps'], run['p_random'], run['seed'], run['peak'], 5.0)
+        net.sigma, net.name = run['sigma'], args['name']
+        _RANDOM_STREAM_NET[seed] = net
+    return _RANDOM_STREAM_NET[seed]
+
+
+# The 24 seeds of the stream sweep, chosen on the host among RANDOM_SEEDS: few generated networks have an entry lane on which two routes
+# begin, and only those can carry a mode-1 or a mode-2 stream.  tests/test_streams_host.py states what the sample must reach.  The
+# first eight also run under every kernel variant: small networks in which most of the events occur.
+RANDOM_STREAM_SEEDS = [10, 90, 27, 51, 20, 24, 83, 41, 87, 30, 25, 12, 14, 17, 23, 33, 38, 40, 44, 45, 48, 71, 77, 85]
+
+
+def _stream_tables_changed(change, base=ratios_in_time):
+    """ratios_in_time with its stream tables changed in place by change(scn): a scenario for REFUSED (never run)."""
+    scn = copy.copy(base())
+    scn.stream_mode, scn.stream_choice = scn.stream_mode.copy(), scn.stream_choice.copy()
+    change(scn)
+    return scn
+
+
+def _set(scn, field, index, value):
+    getattr(scn, field)[index] = value
+
+
+# the stream tables: the refusals of Scenario.check_limits and of tsc_env_create have the same words
+REFUSED.update({
+    'stream_route9': (lambda: _stream_tables_changed(lambda scn: _set(scn, 'stream_choice', (1, 3, 0, 0), scn.n_route)),
+                      'stream 1 names route 9 of 9', 'stream 1 names route 9 of 9'),
+    'stream_mode3': (lambda: _stream_tables_changed(lambda scn: _set(scn, 'stream_mode', 2, 3)), 'stream 2 has mode 3', 'stream 2 has mode 3'),
+    'stream_no_route': (lambda: _stream_tables_changed(lambda scn: _set(scn, 'stream_choice', (3, 0, 0, 0), -1)),     # (a mode-0 stream)
+                        'stream 3 has no route in interval 0', 'stream 3 has no route in interval 0'),
+    # a mode-1 stream whose table of interval 2 begins with a pad: in that interval the kernel would take route -1
+    'stream_no_route_later': (lambda: _stream_tables_changed(lambda scn: _set(scn, 'stream_choice', (1, 2, 0, 0), -1)),
+                              'stream 1 has no route in interval 2', 'stream 1 has no route in interval 2'),
+    'stream_interval0': (lambda: _stream_tables_changed(lambda scn: setattr(scn, 'choice_interval_sec', 0)),
+                         'incomplete stream tables', 'incomplete stream tables'),
+})
