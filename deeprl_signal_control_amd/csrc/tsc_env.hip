@@ -2143,6 +2143,17 @@ int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_en
     if (sc->lane_sib) {
         for (int l = 0; l < NL; ++l)
             if (sc->lane_sib[l] >= NL || sc->lane_sib[l] == l) return tsc::fail("tsc_env_create: lane %d names sibling lane %d of %d", l, sc->lane_sib[l], NL);
+        // the domain of MICROSIM_SPEC.md rule 10: a changer keeps its position and is gathered before the junction's arrivals
+        for (int l = 0; l < NL; ++l) {
+            const int sb = sc->lane_sib[l];
+            if (sb < 0) continue;
+            if (sc->lane_sib[sb] != l)
+                return tsc::fail("tsc_env_create: lane %d names sibling lane %d, whose sibling is lane %d: lane_sib must be symmetric, name each lane of a two-lane street on the other", l, sb, sc->lane_sib[sb]);
+            if (sc->lane_len[l] != sc->lane_len[sb])
+                return tsc::fail("tsc_env_create: lanes %d and %d are siblings of different length (%g m and %g m): a lane changer keeps its position, give both lanes of a street one length", l, sb, (double)sc->lane_len[l], (double)sc->lane_len[sb]);
+            if (sc->lane_up[(size_t)l * kMaxUp] != sb)
+                return tsc::fail("tsc_env_create: lane %d does not list its sibling lane %d first in lane_up: lane changers are gathered before the junction's arrivals, put the sibling in slot 0", l, sb);
+        }
         TSC_HIP(h->bufs.upload(&P.lane_sib, sc->lane_sib, NL));
     }
     {

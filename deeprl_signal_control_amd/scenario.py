@@ -383,6 +383,20 @@ class Scenario:
                              'lane indices must stay below 255' % self.n_lane)
         if np.asarray(self.lane_up).shape[1] != MAX_UP:
             raise ValueError('lane_up must list %d feeder slots per lane' % MAX_UP)
+        if self.lane_sib is not None:           # the domain of MICROSIM_SPEC.md rule 10
+            sib = np.asarray(self.lane_sib)
+            in_range = not ((sib >= self.n_lane) | (sib == np.arange(self.n_lane))).any()   # (else tsc_env_create names the lane)
+            for l in np.flatnonzero(sib >= 0).tolist() if in_range else []:
+                s_ = int(sib[l])
+                if sib[s_] != l:
+                    raise ValueError('lane %d names sibling lane %d, whose sibling is lane %d: lane_sib must be symmetric, name each '
+                                     'lane of a two-lane street on the other' % (l, s_, int(sib[s_])))
+                if np.float32(self.lane_len[l]) != np.float32(self.lane_len[s_]):
+                    raise ValueError('lanes %d and %d are siblings of different length (%g m and %g m): a lane changer keeps its '
+                                     'position, give both lanes of a street one length' % (l, s_, self.lane_len[l], self.lane_len[s_]))
+                if int(np.asarray(self.lane_up)[l, 0]) != s_:
+                    raise ValueError('lane %d does not list its sibling lane %d first in lane_up: lane changers are gathered before '
+                                     'the junction\'s arrivals, put the sibling in slot 0' % (l, s_))
         if self.control_interval_sec > 8:
             raise ValueError('control_interval_sec %d > 8 unsupported (eight emission and record rows per launch)' % self.control_interval_sec)
         fl = np.asarray(self.flows, np.int64).reshape(-1, 4)

@@ -93,7 +93,9 @@ typedef struct tsc_scenario {
      * envs/env.py:464, with the reference's connection table large_grid/data/build_file.py:107-124): lane_sib[l] = the other lane
      * of lane l's edge or -1; NULL = none.  mv_next then names the lane a junction's CONNECTION enters; a vehicle standing on a
      * lane whose mv_next entry for its route is "not served" (< -1) while lane_sib[l] serves it moves over as a hand-off that keeps
-     * its position (lane_up must list the sibling FIRST: lane changers are gathered before the junction's arrivals). */
+     * its position (lane_up must list the sibling FIRST: lane changers are gathered before the junction's arrivals).  The
+     * relation is symmetric (lane_sib[lane_sib[l]] == l) and both lanes of a street have the same lane_len (the position a changer
+     * keeps is one on the sibling too); tsc_env_create refuses a scenario that breaks one of the three. */
     const int32_t *lane_sib;       /* [n_lane] or NULL */
 } tsc_scenario;
 

@@ -22,7 +22,11 @@ tests/test_networks_random_host.py and tests/test_networks_random_gpu.py over RA
 
 The insertion streams -- route modes, choice tables that change in time, insertion windows -- have networks of their own (forks,
 ratios_in_time, sinks, windows_on_lane) and random_stream_network(seed), which redraws the stream tables of random_network(seed):
-tests/test_streams_host.py and tests/test_streams_gpu.py over RANDOM_STREAM_SEEDS."""
+tests/test_streams_host.py and tests/test_streams_gpu.py over RANDOM_STREAM_SEEDS.
+
+Two-lane streets (MICROSIM_SPEC.md rule 10: lane choice and lane changing) come from compile_network's `siblings` and CHANGE hops:
+random_street_network(seed) turns lanes of random_network(seed) into streets -- tests/test_streets_host.py and
+tests/test_streets_gpu.py over RANDOM_STREET_SEEDS; two_lane() is the hand-made one behind the lane_sib refusals."""
 import copy
 
 import numpy as np
@@ -209,13 +213,23 @@ def _stream_tables(streams, lane_len):
                 stream_limit=np.array([s.get('limit', lane_len[s['lane']]) for s in full], np.float32))
 
 
+CHANGE = -7                     # compile_network: the "link" of a path's hop that is left sideways, for the sibling lane (rule 10)
+
+
 def compile_network(name, agent, lanes, routes, phases, neighbors, flows, streams=None, merge='zipper', check=True,
-                    choice_interval_sec=None, **env_kw):
+                    choice_interval_sec=None, siblings=None, **env_kw):
     """A Scenario from a hand-made network.
     lanes: (length m, speed limit m/s, downstream agent or -1) per lane.
     routes: per route index a list of paths; a path is a list of (lane, signal link of the hop that leaves it, -1 = none); the last
         lane of a path is where the route ends.  Disjoint parts of the network may share a route index -- the movement table is
         keyed by (lane, route) and a stream names its entry lane -- which keeps n_live_lanes x n_route small with many agents.
+    siblings: [(l0, l1), ...], the two lanes of every two-lane street (MICROSIM_SPEC.md rule 10; lane_sib, symmetric).  A hop (l,
+        CHANGE) of a path says that the connection of the hop before it enters l, which does not serve the route: the path's next
+        element is l's sibling, where the vehicle moves over and which carries the route on (its link, its next lane, or the end
+        of the route).  In the tables: mv_next[previous lane][r] = l, mv_next[l][r] stays "not served" (-2), mv_next[sibling][r] is
+        the next lane or -1; lane_up lists a lane's sibling first, then its junction feeders (at most MAX_UP - 1), and the merge
+        tables come from the junction feeders alone.  A stream may also insert on the lane of a street that does not serve its
+        route (it names its entry lane).  None: no lane has a sibling (lane_sib None).
     phases: per agent its phase strings (one char per signal link); neighbors: per agent a list of agents.
     flows: (begin, end, veh/h, stream).  streams: (entry lane, route) per insertion stream; None = route r is stream r and enters at
         the first lane of its only path.  A stream may also be a dict: lane, mode (0 fixed route, 1 a draw per vehicle, 2 a route
@@ -233,10 +247,22 @@ def compile_network(name, agent, lanes, routes, phases, neighbors, flows, stream
     lane_node = np.array([l[2] for l in lanes], np.int32)
     mv_next = np.full((NL, NR), -2, np.int32)
     mv_link = np.full((NL, NR), -1, np.int32)
+    lane_sib = None
+    if siblings is not None:
+        lane_sib = np.full(NL, -1, np.int32)
+        for l0, l1 in siblings:
+            assert l0 != l1 and lane_sib[l0] == lane_sib[l1] == -1, 'lanes %d and %d: a lane has one sibling' % (l0, l1)
+            lane_sib[l0], lane_sib[l1] = l1, l0
+    left = set()                                                    # (lane, route) of the hops that are left sideways
     for r, paths in enumerate(routes):
         for path in paths:
             for i, (l, k) in enumerate(path):
-                assert mv_next[l, r] == -2, 'lane %d appears twice on route %d' % (l, r)
+                assert mv_next[l, r] == -2 and (l, r) not in left, 'lane %d appears twice on route %d' % (l, r)
+                if k == CHANGE:
+                    assert lane_sib is not None and i + 1 < len(path) and path[i + 1][0] == lane_sib[l] and path[i + 1][1] != CHANGE, \
+                        'route %d changes from lane %d to a lane that is not its sibling' % (r, l)
+                    left.add((l, r))
+                    continue
                 mv_next[l, r] = path[i + 1][0] if i + 1 < len(path) else -1
                 if i + 1 < len(path) and lane_node[l] >= 0:
                     mv_link[l, r] = k
@@ -246,8 +272,9 @@ def compile_network(name, agent, lanes, routes, phases, neighbors, flows, stream
     mv_prio = np.zeros((NL, NR), np.int32)
     for l2 in range(NL):
         ups = sorted({int(l) for l in np.nonzero((mv_next == l2).any(axis=1))[0]})
-        assert len(ups) <= MAX_UP, 'lane %d has %d feeders' % (l2, len(ups))
-        lane_up[l2, :len(ups)] = ups
+        slots = ups if lane_sib is None or lane_sib[l2] < 0 else [int(lane_sib[l2])] + ups      # lane changers are gathered first
+        assert len(slots) <= MAX_UP, 'lane %d has %d feeders' % (l2, len(slots))
+        lane_up[l2, :len(slots)] = slots
         if len(ups) > 1:
             for rank, l in enumerate(ups):
                 into = mv_next[l] == l2
@@ -296,7 +323,7 @@ def compile_network(name, agent, lanes, routes, phases, neighbors, flows, stream
         name=name, agent=agent, node_names=['n%d' % a for a in range(A)], n_agent=A,
         lane_names=['l%d' % l for l in range(NL)], lane_len=lane_len, lane_vmax=lane_vmax, lane_node=lane_node,
         lane_det_start=np.where(lane_node >= 0, np.maximum(lane_len - DET_LEN, 0.0), 0.0).astype(np.float32), lane_up=lane_up,
-        n_route=NR, mv_next=mv_next, mv_link=mv_link, mv_yield=mv_yield, mv_prio=mv_prio, mv_zip=mv_zip,
+        lane_sib=lane_sib, n_route=NR, mv_next=mv_next, mv_link=mv_link, mv_yield=mv_yield, mv_prio=mv_prio, mv_zip=mv_zip,
         route_entry_lane=np.array([paths[0][0][0] if paths else 0 for paths in routes], np.int32),
         route_names=[('r%d' % r, 'r%d' % r) for r in range(NR)],
         agent_lanes=agent_lanes, agent_nlane=np.array(nlane, np.int32), agent_nlink=np.array([len(p[0]) for p in phases], np.int32),
@@ -1052,8 +1079,9 @@ def random_network(seed):
       norms, clips and coef_wait;
     * run: E = 2, 30 - 60 control steps (the episode ends with the last one), 10 - 90 % random actions, peak in the second half;
       net.sigma is the Krauss sigma of the Krauss variant.
-    Not drawn: two-lane streets (lane_sib, MICROSIM_SPEC.md rule 10) -- compile_network carries no connection-level tables, and
-    grid_x2 / grid_x4 cover rule 10 -- nor per-instance demand, trace and lane data, whose walks run on the hand-made networks."""
+    Not drawn: two-lane streets (lane_sib, MICROSIM_SPEC.md rule 10) -- random_street_network(seed) adds them to the same
+    networks from a generator of its own -- nor per-instance demand, trace and lane data, whose walks run on the hand-made networks
+    and on street_walks()."""
     if seed not in _RANDOM_NET:
         args, run = _random_tables(seed)
         net = Net(lambda: compile_network(**_random_tables(seed)[0]), 'generated network, seed %d' % seed, None, run['E'], run['steps'],
@@ -1136,6 +1164,262 @@ def random_stream_network(seed):
 RANDOM_STREAM_SEEDS = [10, 90, 27, 51, 20, 24, 83, 41, 87, 30, 25, 12, 14, 17, 23, 33, 38, 40, 44, 45, 48, 71, 77, 85]
 
 
+# ---------------------------------------------------------------------------
+# generated networks with two-lane streets (MICROSIM_SPEC.md rule 10): tests/test_streets_host.py / tests/test_streets_gpu.py
+# ---------------------------------------------------------------------------
+_RANDOM_STREET_NET = {}
+STREET_MAX_LANES = 40
+STREET_MAX_LINKS = 12
+HEAVY_WINDOW = (12.0, 17.0)     # m: x <= 12 on the twin, x >= 17 + 5 on the serving lane, and 22 - 5 - 12 >= the standstill gap of 2
+ROOM_LEN_M = 187.3              # the shortest length of RANDOM_LONG: 26 standing vehicles, more than the CAP - 8 = 20 of the room test
+
+
+def _random_street_tables(seed):
+    """The arguments of random_network(seed) with some lanes turned into two-lane streets, from a generator of its own,
+    RandomState(20000 + seed), consumed in one fixed order: -> (arguments of compile_network, the run).  A street is a lane of
+    _random_tables and a twin of the same length and downstream agent behind the last lane; per route through it a draw says which
+    of the two the connection enters and which one serves the next hop."""
+    args, run = _random_tables(seed)
+    rng = np.random.RandomState(20_000 + seed)
+    pick = lambda seq: seq[int(rng.randint(len(seq)))]
+    lanes = list(args['lanes'])
+    routes = [[list(p) for p in paths] for paths in args['routes']]
+    phases = [list(p) for p in args['phases']]
+    streams, flows = list(args['streams']), list(args['flows'])
+    T = int(args['episode_length_sec'])
+    n_old = len(lanes)
+
+    uses = {}                                                       # lane -> [(route, path index)] of the paths through it
+    for r, paths in enumerate(routes):
+        for pi, path in enumerate(paths):
+            for l, _ in path:
+                uses.setdefault(l, []).append((r, pi))
+    at = lambda path, l: [x[0] for x in path].index(l)
+    hops = lambda: [(path, j) for paths in routes for path in paths for j in range(len(path))]
+    # the junction feeders of a lane and the lanes its connections enter, as the paths stand now (a CHANGE hop hands over sideways)
+    feeders = lambda l: {path[j - 1][0] for path, j in hops() if path[j][0] == l and j > 0 and path[j - 1][1] != CHANGE}
+    nexts = lambda l: {path[j + 1][0] for path, j in hops() if path[j][0] == l and j + 1 < len(path) and path[j][1] != CHANGE}
+    paired = lambda l: any(l in pair for pair in siblings)
+    entry_lanes = {l for l, _ in streams}
+    ends = {path[-1][0] for paths in routes for path in paths}
+    chosen, siblings, twin_link = [], [], {}
+    behind = []                                                     # the streams that insert on the heavy street's twin
+
+    def fits(l):
+        a = lanes[l][2]
+        return (l in uses and l not in chosen and len(feeders(l)) <= MAX_UP - 1 and len(lanes) < STREET_MAX_LANES
+                and all(len(feeders(nx)) + 1 + paired(nx) <= MAX_UP for nx in nexts(l))        # (the twin feeds them too)
+                and (a < 0 or len(phases[a][0]) + len(nexts(l)) <= STREET_MAX_LINKS))
+
+    def twin(l):
+        """The second lane of the street of lane l: the same length and downstream agent, half of the time another speed limit."""
+        length, vmax, node = lanes[l]
+        lanes.append((length, vmax if rng.rand() < 0.5 else pick(RANDOM_VMAX), node))
+        chosen.append(l)
+        siblings.append((l, len(lanes) - 1))
+        return len(lanes) - 1
+
+    def link(l2, nx):
+        """The signal link of the twin's movement l2 -> nx: a link of its own behind the agent's last one, open in some phase."""
+        a = lanes[l2][2]
+        if a < 0 or nx is None:
+            return -1
+        if (l2, nx) not in twin_link:
+            twin_link[(l2, nx)] = len(phases[a][0])
+            col = list(rng.choice(list('Ggr'), size=len(phases[a]), p=[0.35, 0.15, 0.5]))
+            if not any(c in 'Gg' for c in col):
+                col[int(rng.randint(len(col)))] = 'G'
+            phases[a] = [p + c for p, c in zip(phases[a], col)]
+        return twin_link[(l2, nx)]
+
+    def connect(l, l2, r, pi, mode):
+        """Route r's hop over the street (l, l2) -- 'stay': enters l, which serves it; 'change': enters l, l2 serves it; 'twin':
+        enters l2, which serves it; 'back': enters l2, l serves it."""
+        path = routes[r][pi]
+        i = at(path, l)
+        k = path[i][1]
+        nx = path[i + 1][0] if i + 1 < len(path) else None
+        hop = {'stay': [(l, k)], 'change': [(l, CHANGE), (l2, link(l2, nx))], 'twin': [(l2, link(l2, nx))],
+               'back': [(l2, CHANGE), (l, k)]}[mode]
+        path[i:i + 1] = hop
+
+    # the designated heavy street: the entry lane of the heaviest stream, made long enough to hold more than CAP - 8 vehicles; the
+    # heavy stream inserts on the lane that serves it, the lane's other streams mostly on the other one (one is added if there is
+    # none).  The streams of the twin insert within HEAVY_WINDOW[0] m, those of the serving lane beyond HEAVY_WINDOW[1] m (`windows`,
+    # written into the stream tables at the end): a vehicle inserted on the twin stands behind the serving lane's tail by more
+    # than the gap test asks, so that what keeps it out is the serving lane's count alone
+    windows = {}
+    load = [sum(max(0, min(e, T) - b) * v for b, e, v, s_ in flows if s_ == s) for s in range(len(streams))]
+    hs = int(np.argmax(load))
+    lh = streams[hs][0]
+    if fits(lh):
+        if lanes[lh][0] < ROOM_LEN_M:
+            lanes[lh] = (pick(RANDOM_LONG),) + tuple(lanes[lh][1:])
+        l2 = twin(lh)
+        for s, (l, r) in enumerate(streams):
+            if l == lh and s != hs and rng.rand() < 0.7:
+                streams[s] = (l2, r)
+                behind.append(s)
+        if not behind:
+            streams.append((l2, streams[hs][1]))
+            flows.append((int(rng.randint(0, 10)), T + int(rng.randint(0, 30)), int(rng.randint(400, 1201)), len(streams) - 1))
+            behind.append(len(streams) - 1)
+        windows = {s: (0.0, HEAVY_WINDOW[0]) if s in behind else (HEAVY_WINDOW[1], lanes[lh][0])
+                   for s, (l, _) in enumerate(streams) if l in (lh, l2)}
+
+    # one street per kind (when the network has a lane of the kind and the draw says so), then up to two more
+    kinds = [
+        ('entry', 0.6, lambda l: l in entry_lanes),
+        ('merge', 0.75, lambda l: len(feeders(l)) >= 2),
+        ('fast', 0.9, lambda l: lanes[l][1] > lanes[l][0]),
+        ('short', 0.75, lambda l: lanes[l][0] < 50.0),
+        ('unsignalised', 0.7, lambda l: lanes[l][2] < 0 and l not in ends),
+        ('end', 1.0, lambda l: l in ends and len(uses[l]) == max(len(uses[x]) for x in ends)),
+        ('any', 0.5, lambda l: True), ('any', 0.5, lambda l: True)]
+    for kind, p, is_kind in kinds:
+        cand = [l for l in range(n_old) if fits(l) and is_kind(l)]
+        if rng.rand() >= p or not cand:
+            continue
+        l = pick(cand)
+        l2 = twin(l)
+        if rng.rand() < 0.12:                                       # a second lane that no route uses
+            continue
+        inner = [(r, pi) for r, pi in uses[l] if at(routes[r][pi], l) > 0]
+        first = [(r, pi) for r, pi in uses[l] if at(routes[r][pi], l) == 0]
+        modes = [str(rng.choice(['stay', 'change', 'twin', 'back'], p=[0.25, 0.35, 0.15, 0.25])) for _ in inner]
+        if kind == 'end':                                           # both lanes carry traffic that leaves at speed
+            modes = [('stay', 'change', 'twin', 'back')[j % 4] for j in range(len(inner))]
+        moved = any(m in ('change', 'back') for m in modes)
+        for r, pi in first:                                         # a route that begins on the street: one lane serves it (the
+            serve = l if rng.rand() < 0.6 else l2                   # path names that one), its streams insert on either
+            if serve == l2:
+                connect(l, l2, r, pi, 'twin')
+            for s in [s for s, (le, rs) in enumerate(streams) if le == l and rs == r]:
+                on_wrong = bool(rng.rand() < 0.5) or not moved
+                streams[s] = ((l2 if serve == l else l) if on_wrong else serve, r)
+                moved |= on_wrong
+        if not moved and inner:                                     # every street that routes use carries a change
+            modes[0] = 'change' if modes[0] == 'stay' else 'back'
+        for (r, pi), mode in zip(inner, modes):
+            connect(l, l2, r, pi, mode)
+    for s, (lo, hi) in windows.items():
+        l, r = streams[s]
+        streams[s] = dict(lane=l, mode=0, choice=[[(r, 65536)]], origin=lo, limit=hi)
+    return dict(args, name='random_street_%d' % seed, lanes=lanes, routes=routes, phases=phases, streams=streams, flows=flows,
+                siblings=siblings), run
+
+
+def random_street_network(seed):
+    """random_network(seed) with two-lane streets (MICROSIM_SPEC.md rule 10) -- the lanes, routes, phases, demand, configuration and
+    run of _random_tables(seed), a pure function of the seed.  Drawn, inside the declared limits (at most 40 lanes, 12 links per
+    agent and MAX_UP lane_up slots, the sibling among them):
+    * which lanes become streets: the entry lane of the heaviest stream, made at least 187.3 m long (the heavy stream inserts on
+      the lane that serves it and fills it past the CAP - 8 vehicles of the room test, other streams insert on the lane beside it);
+      then, each with its own probability and where the network has one, another entry lane, a merge target with two or three
+      junction feeders, a lane whose speed limit exceeds its length, a lane shorter than 50 m, an unsignalised lane, the lane on
+      which the most routes end (always: its routes take the four connection kinds in turn, so that both lanes carry traffic that
+      leaves at speed and a changer behind a vehicle that has just left finds the sibling's tail moving a few metres ahead -- what
+      makes the clamp behind that tail bind), and up to two more of any kind;
+    * the twin: the same length and downstream agent, another speed limit half of the time;
+    * per route through a street which lane the connection enters and which serves the next hop -- stay, change, enter the twin,
+      or enter the twin and change back, so that streets carry changes in both directions, routes end on the sibling, and the twin
+      of a merge target is a merge target itself; per stream on an entry street the lane it inserts on; every street that routes
+      use carries a change; one street in eight has a twin that no route uses (it lies beyond the live prefix);
+    * signals: every movement of a twin has a signal link of its own behind the agent's last one, open in some phase."""
+    if seed not in _RANDOM_STREET_NET:
+        args, run = _random_street_tables(seed)
+        net = Net(lambda: compile_network(**_random_street_tables(seed)[0]), 'generated network with two-lane streets, seed %d' % seed,
+                  None, run['E'], run['steps'], run['p_random'], run['seed'], run['peak'], 5.0)
+        net.sigma, net.name = run['sigma'], args['name']
+        _RANDOM_STREET_NET[seed] = net
+    return _RANDOM_STREET_NET[seed]
+
+
+# The 48 seeds of the street sweep, chosen on the host: 0 - 49 without 22 (no vehicle is inserted before the episode ends: no lane
+# change, no arrival) and 26 (no vehicle reaches the end of its route) -- the seeds RANDOM_SEEDS leaves out for the same reason.
+# tests/test_streets_host.py states what the sample must reach (floors over the oracle's runs).
+RANDOM_STREET_SEEDS = [s for s in range(50) if s not in (22, 26)]
+# the 16 networks of the kernel-variant, controller, trace and lane-data cases
+RANDOM_STREET_VARIANT_SEEDS = RANDOM_STREET_SEEDS[:16]
+
+
+# Cut positions in m, none of them a float32 value
+STREET_CUTS = (13.3, 20.1, 33.3, 61.7, 90.9, 120.1, 150.7)
+
+
+def street_walk_scenario(seed, krauss=False):
+    """random_street_network(seed) for the trace and lane-data walk.  The trace knows a vehicle by (route, serial, entry lane) and
+    serials count per stream: the streams that share an entry lane and a route become one (their flow elements add up on the
+    first).  The longest street is in pieces: the lane with the lower index in four (or as many as STREET_CUTS allows below its
+    length, at least two), its sibling in two or three at other positions.  krauss: under Krauss with the network's sigma."""
+    args, run = _random_street_tables(seed)
+    lane_route = lambda s: (s['lane'], s['choice'][0][0][0]) if isinstance(s, dict) else tuple(s)
+    first, streams, renum = {}, [], []
+    for s in args['streams']:
+        key = lane_route(s)
+        if key not in first:
+            first[key] = len(streams)
+            streams.append(s)
+        renum.append(first[key])
+    flows = [(b, e, v, renum[s]) for b, e, v, s in args['flows']]
+    scn = compile_network(**dict(args, name='random_street_%d_walk' % seed, streams=streams, flows=flows))
+    sib = np.asarray(scn.lane_sib)
+    l = max((l for l in range(scn.n_lane) if sib[l] > l), key=lambda l: (float(scn.lane_len[l]), -l))
+    below = [c for c in STREET_CUTS if c < float(scn.lane_len[l]) - 1.0]
+    assert len(below) >= 2, (seed, scn.lane_len[l])
+    scn = split_pieces(scn, {scn.lane_names[l]: below[:3], scn.lane_names[sib[l]]: below[1:3] if len(below) > 2 else below[1:]})
+    if krauss:
+        scn.car_following, scn.krauss_sigma = 'krauss', run['sigma']
+    return scn
+
+
+class StreetWalk(Aux):
+    """A walk case (AUX['walk']) over street_walk_scenario(seed)."""
+
+    def __init__(self, seed, krauss, period_steps):
+        net = random_street_network(seed)
+        scn = street_walk_scenario(seed, krauss)
+        Aux.__init__(self, 'street_%d%s' % (seed, '_krauss' if krauss else ''), None, net.E, None, watch=[0, 1], seed=net.seed,
+                     rng_seed=700 + seed, period=period_steps * int(scn.control_interval_sec))
+        self._scn = scn
+
+    def scenario(self):
+        return self._scn
+
+
+_STREET_WALKS = []
+
+
+def street_walks():
+    """The six walk cases of the street sweep, built once: six of RANDOM_STREET_VARIANT_SEEDS (episodes of 52 to 228 s; zipper and
+    yield; room refusals in 3, 11 and 15, teleports in 4 and 8), two of them under Krauss with sigma 1.0.  The lane-data period is a
+    number of control steps that does not divide the episode: the last interval is a partial one."""
+    if not _STREET_WALKS:
+        _STREET_WALKS.extend(StreetWalk(seed, krauss, steps) for seed, krauss, steps in
+                             ((2, False, 20), (3, True, 11), (4, False, 9), (8, True, 17), (11, False, 12), (15, False, 7)))
+    return _STREET_WALKS
+
+
+def wrong_lane_pairs(scn):
+    """(lane, route) pairs of signalised lanes that do not serve the route while their sibling does."""
+    sib, nxt = np.asarray(scn.lane_sib), np.asarray(scn.mv_next)
+    return [(l, r) for l in range(scn.n_lane) if sib[l] >= 0 and scn.lane_node[l] >= 0 for r in range(scn.n_route)
+            if nxt[l, r] < -1 and nxt[sib[l], r] >= -1]
+
+
+def walk_lane_changes(case):
+    """{watched instance: the lane changes the oracle counts (ms.lanechange_counts) over the walk of `case`}: the oracle's side of
+    the walk alone, under the walk's own actions."""
+    from tests import env_harness as H
+    scn = case.scenario()
+    with H.walk_context(case):
+        orc = H.WalkOracles(case)
+        rng = np.random.RandomState(case.rng_seed)
+        for _ in range(walk_steps(case)):
+            orc.step(H.uniform_actions(scn, rng, case.E))
+    return {e: int(o.ms.lanechange_counts()['changes']) for e, o in orc.orc.items()}
+
+
 def _stream_tables_changed(change, base=ratios_in_time):
     """ratios_in_time with its stream tables changed in place by change(scn): a scenario for REFUSED (never run)."""
     scn = copy.copy(base())
@@ -1160,4 +1444,38 @@ REFUSED.update({
                               'stream 1 has no route in interval 2', 'stream 1 has no route in interval 2'),
     'stream_interval0': (lambda: _stream_tables_changed(lambda scn: setattr(scn, 'choice_interval_sec', 0)),
                          'incomplete stream tables', 'incomplete stream tables'),
+})
+
+
+def two_lane():
+    """An entry lane (0) into a two-lane street (1, 2) with one exit (3): route 0 stays on lane 1, route 1 enters lane 1 and moves
+    over to lane 2.  The smallest network with a sibling that is also fed by a junction: lane_up[1] = (2, 0)."""
+    lanes = [(100.0, 13.89, 0), (150.0, 13.89, 1), (150.0, 13.89, 1), (100.0, 13.89, -1)]
+    routes = [[[(0, 0), (1, 0), (3, -1)]], [[(0, 0), (1, CHANGE), (2, 1), (3, -1)]]]
+    return compile_network('two_lane', 'ia2c', lanes, routes, [['G', 'r'], ['GG', 'Gr', 'rG']], [[1], [0]],
+                           [(0, 300, 500, 0), (0, 300, 500, 1)], siblings=[(1, 2)], episode_length_sec=300, teleport_sec=120)
+
+
+def _two_lane_changed(change):
+    """two_lane with its street tables changed in place by change(scn, l, s), l a street lane with a junction feeder and s its
+    sibling: a scenario for REFUSED (never run)."""
+    scn = copy.copy(two_lane())
+    scn.lane_sib, scn.lane_len, scn.lane_up = scn.lane_sib.copy(), scn.lane_len.copy(), scn.lane_up.copy()
+    l = int(np.flatnonzero((scn.lane_sib >= 0) & (scn.lane_up[:, 1] >= 0))[0])
+    change(scn, l, int(scn.lane_sib[l]))
+    return scn
+
+
+def _swap_first_two(scn, l, s):
+    scn.lane_up[l, :2] = scn.lane_up[l, 1::-1]
+
+
+# the domain of lane_sib (MICROSIM_SPEC.md rule 10): the refusals of Scenario.check_limits and of tsc_env_create have the same words
+REFUSED.update({
+    'sib_one_way': (lambda: _two_lane_changed(lambda scn, l, s: _set(scn, 'lane_sib', s, -1)),
+                    'names sibling lane [0-9]+, whose sibling is lane -1', 'names sibling lane [0-9]+, whose sibling is lane -1'),
+    'sib_length': (lambda: _two_lane_changed(lambda scn, l, s: _set(scn, 'lane_len', s, 149.0)),
+                   'are siblings of different length', 'are siblings of different length'),
+    'sib_not_first': (lambda: _two_lane_changed(_swap_first_two), 'does not list its sibling lane [0-9]+ first in lane_up',
+                      'does not list its sibling lane [0-9]+ first in lane_up'),
 })

@@ -36,8 +36,10 @@ VARIANTS = {
 }
 
 
-def _compare(seed, monkeypatch, variant=None):
-    net = nw.random_network(seed)
+def _compare(seed, monkeypatch, variant=None, network=nw.random_network):
+    """One generated network (network(seed): random_network, or random_street_network for tests/test_streets_gpu.py) against the
+    oracle under the library's own plan or a kernel variant."""
+    net = network(seed)
     scn = net.scenario()
     label = 'seed %d%s' % (seed, ' (%s)' % variant if variant else '')
     kw = dict(VARIANTS[variant]) if variant else {}
@@ -74,21 +76,21 @@ def _named(seed, what, call):
         raise AssertionError('seed %d (%s): %s' % (seed, what, ex)) from ex
 
 
-def _handle_and_oracles(seed):
+def _handle_and_oracles(seed, network=nw.random_network):
     from deeprl_signal_control_amd.env import VecTrafficEnv
     from oracle.env_oracle import OracleEnv
-    net = nw.random_network(seed)
+    net = network(seed)
     scn = net.scenario()
     env = VecTrafficEnv(scn, net.E, seed=net.seed)
     orc = [OracleEnv(scn, seed=net.seed + e) for e in range(net.E)]
     return net, scn, env, orc
 
 
-def _greedy_loop(seed):
+def _greedy_loop(seed, network=nw.random_network):
     """greedy_kernel on the handle's observations chooses; its actions equal trainer.greedy_actions on the oracles' observations
     after the reset and every control step, and handle and oracles stay bit-equal under them."""
     from deeprl_signal_control_amd.trainer import greedy_actions
-    net, scn, env, orc = _handle_and_oracles(seed)
+    net, scn, env, orc = _handle_and_oracles(seed, network)
     try:
         env.reset()
         obs = [o.reset() for o in orc]
@@ -107,10 +109,10 @@ def _greedy_loop(seed):
         env.close()
 
 
-def _pressure_loop(seed, measure, min_green):
+def _pressure_loop(seed, measure, min_green, network=nw.random_network):
     """pressure_kernel chooses: at every step the full pressure array and the action equal the loop rule over the oracles' state and
     the hold bookkeeping of tests/test_pressure_gpu.py's test_hold (the action is the held phase)."""
-    net, scn, env, orc = _handle_and_oracles(seed)
+    net, scn, env, orc = _handle_and_oracles(seed, network)
     tb = scn.pressure_tables()
     try:
         env.reset()

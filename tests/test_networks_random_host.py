@@ -164,6 +164,10 @@ def test_every_network_is_inside_the_declared_limits():
         for a in range(scn.n_agent):            # every used link is open in some phase of its agent
             for k in {int(x) for x in scn.mv_link[scn.lane_node == a].ravel() if x >= 0}:
                 assert any(p[k] in 'Gg' for p in scn.phases[a]), (seed, a, k)
+    # the counterpart: every network of the street sweep has two-lane streets (its own limits: tests/test_streets_host.py)
+    for seed in nw.RANDOM_STREET_SEEDS:
+        scn = nw.random_street_network(seed).scenario()
+        assert scn.lane_sib is not None and (scn.lane_sib >= 0).sum() >= 2 and scn.n_lane <= 40, seed
 
 
 def test_every_episode_ends_inside_its_run_and_few_runs_are_degenerate():
