@@ -22,13 +22,14 @@
 //                     grouped GEMMs + lstm_fwd + head_fwd: training-shape re-forward)
 //   update .......... head_bwd (persistent, loss gradient + dH + dWo | dbo) -> lstm_bwd2 (Wh^T stationary in registers,
 //                     dc in registers / dh through LDS over the n_step time steps, next step's inputs in flight under the
-//                     MFMAs) -> dwxh (dWx | dWh | dbl, whole tower output in accumulators) -> dx1w1_kernel2 (dX1 in
+//                     MFMAs) -> dwxh (dWx | dWh | dbl, whole tower output in accumulators; dwxh_split_kernel: bf16 MFMAs on
+//                     three-way split f32 operands, dwxh_kernel: exact f32 behind TSC_DW_SPLIT=0) -> dx1w1_kernel2 (dX1 in
 //                     registers, chained into dW1 | db1) -> grad_norm -> rmsprop; the FcACPolicy update: head_bwd ->
 //                     fc_bwd_kernel (dWfc | dbfc | dW1 | db1 in one pass over the X1 / Hh rows its rollout forward cached;
 //                     the grouped split-K GEMMs of tsc_gemm.h behind TSC_UNFUSED_DX and for other shapes)
 // Which of these a handle runs is decided once, in tsc_model_create: its Plan (forward kernel, the three one-pass update
 // kernels, split counts) follows from the shapes, the LDS and workspace fits and the knobs of INTEGRATION.md section 5, which
-// are read there and nowhere else.  The forward and the update only switch on the plan; tsc_model_plan / tsc_model_path report it.  The fused
+// are read there and nowhere else.  The forward and the update only switch on the plan; tsc_model_plan / tsc_model_path / tsc_model_dw_split report it.  The fused
 // kernels exist for the hidden widths of with_fused_width, and each launch derives its template argument from H.
 // Where a kernel's sizes live: next to the kernel, as constexpr functions of its shape -- <kernel>_lds (dynamic LDS, bytes),
 // <kernel>_ws_floats (a split's partial in the split-K workspace) -- written in the constants the kernel carves its pointers by,
@@ -2056,6 +2057,246 @@ dwxh_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const fl
     if (kh == 0) w[(long long)NT * 32 * kG4 + col0 + li] = bsum;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same product on the bf16 matrix cores at f32 accuracy ("BF16x6").  v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16
+// rate, and dwxh_kernel sits at 75 - 81 % of that f32 peak.  Here every f32 operand is cut into three bf16 pieces of 8
+// mantissa bits, x = p1 + p2 + p3 with p1 = bf16(x), p2 = bf16(x - p1), p3 = bf16((x - p1) - p2) (round to nearest even; exact
+// for every normal f32 whose smallest piece does not underflow), and six of the nine piece products are summed into the SAME
+// f32 accumulators by v_mfma_f32_32x32x16_bf16, smallest terms first: a3 b1, a1 b3, a2 b2, a2 b1, a1 b2, a1 b1.  Each bf16 x bf16
+// product is exact in f32, the three dropped terms are <= 2^-24 relative, so the error is the f32 accumulation's as before.
+// Six 32-cycle MFMAs cover 16 rows where eight 64-cycle ones did: 192 against 512 cycles per tile.
+// Contract, grid, workspace records and flush are dwxh_kernel's (dwxh_reduce_kernel adds either kernel's partials).  What differs:
+//   * the contraction step is 16 rows: lane (r = lane & 31, h = lane >> 5) holds A[feature r][rows 8h .. 8h+7] and
+//     B[rows 8h .. 8h+7][column r], eight consecutive rows of one column;
+//   * dZ (B): eight coalesced dword loads per lane and step, one step ahead as before, cut into pieces in registers (about 50
+//     VALU instructions per wave and step); bsum adds the f32 values, rows in the order 8h + j (dwxh_kernel: 2 ks + h), so dbl
+//     agrees with dwxh_kernel's to rounding and not bit for bit;
+//   * [X1 | h_prev] (A) is cut ONCE per workgroup, by the staging thread that holds the float4, and lives in LDS as three
+//     row-major bf16 planes per 16-row sub-chunk, [piece][8-row group][32-feature tile][8 rows x 64 B], written with one 8-byte
+//     store per piece.  The 16-byte chunk of 8 features `ch` of row `row` sits at 64 (row & 7) + 16 (ch ^ ((row >> 2) & 3)) of its
+//     512-byte subtile; the MFMA fragments come back k-major through ds_read_b64_tr_b16 (two per piece and tile: rows 8h .. 8h+3
+//     and 8h+4 .. 8h+7), conflict-free by the bank rule (32 lanes x 8 B on 64 distinct banks).  That read needs EXEC all ones: no
+//     early return, no lane-dependent branch around it (has1 / has2 / lead are wave-uniform), tails clamp instead of branching;
+//   * 6 B per element: a ring of FOUR sub-chunks (two buffers of 32 rows, 108 KiB at NT = 9), one barrier per 32 rows; sub-chunk
+//     c's staging writes c + 2 and requests c + 3.
+// Option (i) of the two LDS images considered; (ii) (k-pair-major, plain 16-byte reads) puts the four 32-bit stores of a staging
+// thread on one bank.
+// Budgets: LDS 4 x 3 x 1024 NT bytes (NT = 9: 110 592); registers at NT = 9 / 8 / 7 / 6: 233 / 218 / 202 / 177 VGPRs, no scratch (the
+// split's bounds and the loop counters are forced into scalar registers, the clamped fetches recompute their lane values from an opaque
+// tid: without either the unclamped loop spilled at NT = 9).  Fragment reads are pinned two gaps ahead of their MFMA with
+// sched_group_barrier; left to itself the scheduler issued a tile's six reads right in front of its MFMAs.
+// Measured: profiles/dwxh_split_bench.json (accuracy against float64 beside dwxh_kernel's, kernel and iteration times).
+// ------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef s16x4 __attribute__((address_space(3))) *lds_s16x4_p;
+
+constexpr int kDsKi = 32;                 // rows per LDS buffer of dwxh_split_kernel (interval between two barriers)
+template <int NT> constexpr size_t dwxh_split_plane() { return sizeof(__bf16) * kDwKc * NT * 32; }        // one piece of a sub-chunk
+template <int NT> constexpr size_t dwxh_split_lds() { return 3 * dwxh_split_plane<NT>() * (2 * kDsKi / kDwKc); }
+// byte offset of features f .. f + 3 (f % 4 == 0) of row rr (0 .. 15) inside a piece's plane of a sub-chunk
+__device__ __forceinline__ constexpr unsigned dwxh_split_off(int NT, int rr, int f) {
+    return ((rr >> 3) * NT + (f >> 5)) * 512 + 64 * (rr & 7) + 16 * (((f >> 3) & 3) ^ ((rr >> 2) & 3)) + 2 * (f & 7);
+}
+
+template <int NT>
+__global__ void __launch_bounds__(512, 1)
+dwxh_split_kernel(const float *__restrict__ X1, const float *__restrict__ Hp, const float *__restrict__ dZ, long long N, int G,
+                  int S, long long rows_per_split, float *__restrict__ ws) {
+    constexpr int HT = NT - 2, H = 32 * HT, KC = kDwKc;
+    constexpr int XQ = H / 4, NX = KC * XQ;                     // float4s of a sub-chunk's X1 rows (its h_prev rows: 256)
+    constexpr unsigned PL = (unsigned)dwxh_split_plane<NT>(), SUB = 3 * PL;
+    static_assert(NX >= 512 && NX <= 1024 && NX % 64 == 0 && KC * (kL / 4) == 256, "staging slots");
+    static_assert(2 * PL + (NT - 1) * 512 < 65536, "a fragment read's immediate offset");
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];     // [4 sub-chunks][3 pieces][PL]
+    const int g = blockIdx.x % G, sp = blockIdx.x / G;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, kh = lane >> 5;
+    const int col0 = 32 * wave;
+    // (the split's bounds and the loop counters in scalar registers: as 64-bit lane values they cost the unclamped loop four VGPRs)
+    const auto uniform = [](long long v) {
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+        return (long long)(((unsigned long long)hi << 32) | lo);
+    };
+    const long long n0 = uniform((long long)sp * rows_per_split);
+    const long long n1 = uniform(n0 + rows_per_split > N ? N : n0 + rows_per_split);
+    const int R = __builtin_amdgcn_readfirstlane((int)(n1 - n0));       // (a split is far below 2^31 rows)
+    const float *x1 = X1 + (long long)g * N * H, *hp = Hp + (long long)g * N * kL;
+    const float *dz = dZ + (long long)g * N * kG4;
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    float bsum = 0.f;
+    // staging slots of a thread: dwxh_kernel's (see there)
+    const bool has1 = wave < (NX - 512) / 64, has2 = wave >= 4;
+    struct Slots { int r0, c0, r1, c1, r2, c2; };
+    auto slots = [&](int t) {
+        const int i1 = has1 ? t + 512 : t, i2 = t & 255;
+        return Slots{t / XQ, 4 * (t % XQ), i1 / XQ, 4 * (i1 % XQ), i2 >> 4, 4 * (i2 & 15)};
+    };
+    const Slots sl = slots(tid);
+    const unsigned o0 = sl.r0 * H + sl.c0, o1 = sl.r1 * H + sl.c1, o2 = sl.r2 * kL + sl.c2;          // source, floats past the sub-chunk's first row
+    const unsigned l0 = dwxh_split_off(NT, sl.r0, sl.c0), l1 = dwxh_split_off(NT, sl.r1, sl.c1),
+                   l2 = dwxh_split_off(NT, sl.r2, H + sl.c2);                                         // LDS, bytes past the sub-chunk's piece 0
+    // Fragment reads: the 16-lane group lane >> 4 = 2 kh + (li >> 4) takes the 4-row x 16-feature blocks at rows 8 kh + 4 s
+    // (s = 0, 1), features 16 (li >> 4) ..; its lane 4q + p supplies the address of row q, features 4p .. 4p + 3 of the block.
+    const int rq = (lane >> 2) & 3, rp = lane & 3, rc = 2 * ((lane >> 4) & 1) + (rp >> 1);
+    const unsigned rb0 = kh * NT * 512 + 64 * rq + 16 * (rc ^ (2 * kh)) + 8 * (rp & 1),
+                   rb1 = kh * NT * 512 + 64 * (4 + rq) + 16 * (rc ^ (2 * kh + 1)) + 8 * (rp & 1);
+    const unsigned zb = 8 * kh * kG4 + col0 + li;
+    f32x4 g0, g1, g2;
+    bf16x8 b1, b2, b3;
+    float bnxt[8];
+    using Clamp = std::true_type;
+    using Plain = std::false_type;
+    auto fetch_a = [&](auto cl, long long c) {
+        if constexpr (decltype(cl)::value) {
+            int t = tid;
+            asm volatile("" : "+v"(t));
+            const Slots q = slots(t);
+            auto rowc = [&](long long r) { return r < n1 ? r : n1 - 1; };
+            const long long b = n0 + KC * c;
+            g0 = *reinterpret_cast<const f32x4 *>(x1 + rowc(b + q.r0) * H + q.c0);
+            if (has1) g1 = *reinterpret_cast<const f32x4 *>(x1 + rowc(b + q.r1) * H + q.c1);
+            if (has2) g2 = *reinterpret_cast<const f32x4 *>(hp + rowc(b + q.r2) * kL + q.c2);
+        } else {
+            const gfloat_p xs = uniform_ptr(x1 + (n0 + KC * c) * H), hs = uniform_ptr(hp + (n0 + KC * c) * kL);
+            g0 = *(gfloat4_p)(xs + o0);
+            if (has1) g1 = *(gfloat4_p)(xs + o1);
+            if (has2) g2 = *(gfloat4_p)(hs + o2);
+        }
+    };
+    // a float4 of four features of one row -> its three pieces, one 8-byte store per plane
+    auto put = [&](char *d, const f32x4 &v) {
+        bf16x4 p1, p2, p3;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            p1[e] = (__bf16)v[e];
+            const float r1 = v[e] - (float)p1[e];
+            p2[e] = (__bf16)r1;
+            p3[e] = (__bf16)(r1 - (float)p2[e]);
+        }
+        *reinterpret_cast<bf16x4 *>(d) = p1;
+        *reinterpret_cast<bf16x4 *>(d + PL) = p2;
+        *reinterpret_cast<bf16x4 *>(d + 2 * PL) = p3;
+    };
+    auto commit_a = [&](long long c) {
+        char *d = smem_raw + (unsigned)(c & 3) * SUB;
+        put(d + l0, g0);
+        if (has1) put(d + l1, g1);
+        if (has2) put(d + l2, g2);
+    };
+    // dZ rows 8 kh + j of sub-chunk c, column col0 + li; Clamp: rows past the split contribute zero
+    auto fetch_b = [&](auto cl, long long c) {
+        if constexpr (decltype(cl)::value) {
+            int t = tid;                                        // (opaque, as in fetch_a)
+            asm volatile("" : "+v"(t));
+            const long long row0 = n0 + KC * c + 8 * ((t >> 5) & 1);
+            const float *zc = dz + col0 + (t & 31);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const long long row = row0 + j;
+                const float z = zc[(row < n1 ? row : n1 - 1) * kG4];
+                bnxt[j] = row < n1 ? z : 0.f;
+            }
+        } else {
+            const gfloat_p zs = uniform_ptr(dz + (n0 + KC * c) * kG4);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) bnxt[j] = (zs + j * kG4)[zb];
+        }
+    };
+    // bnxt -> the operand pieces of the next step; dbl sums the f32 values
+    auto split_b = [&]() {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            bsum += bnxt[j];
+            b1[j] = (__bf16)bnxt[j];
+            const float r1 = bnxt[j] - (float)b1[j];
+            b2[j] = (__bf16)r1;
+            b3[j] = (__bf16)(r1 - (float)b2[j]);
+        }
+    };
+    // waves w and w + 4 share a SIMD and run out of phase between two barriers, as in dwxh_kernel
+    const bool lead = wave < 4;
+    // sub-chunk c: dZ of c + 1 requested, then the MFMAs of its 16 rows (LDS slot c & 3); staged before or after them: A rows of
+    // c + 2 into the other buffer (nobody reads it before the next barrier), A rows of c + 3 into the registers
+    auto sub = [&](auto cl, long long c) {
+        auto stage = [&]() { commit_a(c + 2); fetch_a(cl, c + 3); };
+        fetch_b(cl, c + 1);
+        if (lead) stage();
+        const char *a = smem_raw + (unsigned)(c & 3) * SUB;
+        const lds_s16x4_p a0 = (lds_s16x4_p)(a + rb0), a1 = (lds_s16x4_p)(a + rb1);
+        __builtin_amdgcn_sched_barrier(0);
+        // Fragment reads run ahead of the MFMAs that use them, two in a gap between MFMAs: a tile's a3 is last used by its first
+        // MFMA and a2 by its fourth, so the next tile's a3 and a2 are read into the same registers right after those; only a1
+        // (used last, needed second) has two sets.
+        auto frag = [&](int t, int p) {
+            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(a0 + (p * PL + t * 512) / 8);
+            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(a1 + (p * PL + t * 512) / 8);
+            return __builtin_bit_cast(bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        };
+        bf16x8 p1[2], p2, p3;
+        p3 = frag(0, 2); p1[0] = frag(0, 0); p2 = frag(0, 1);
+        __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);              // (the groups below then take the NEXT tile's reads)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const bool more = t + 1 < NT;
+            const bf16x8 c1 = p1[t & 1];
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p3, b1, acc[t], 0, 0, 0);
+            if (more) p3 = frag(t + 1, 2);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, b3, acc[t], 0, 0, 0);
+            if (more) p1[(t + 1) & 1] = frag(t + 1, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p2, b2, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p2, b1, acc[t], 0, 0, 0);
+            if (more) p2 = frag(t + 1, 1);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, b2, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, b1, acc[t], 0, 0, 0);
+            if (more) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA a3 b1
+                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // LDS reads: the next a3
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // a1 b3
+                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // the next a1
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);      // a2 b2, a2 b1
+                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // the next a2
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);      // a1 b2, a1 b1
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (!lead) stage();
+        split_b();
+    };
+    if (R > 0) {
+        for (int c = 0; c < 2; ++c) { fetch_a(Clamp{}, c); commit_a(c); }
+        fetch_a(Clamp{}, 2); fetch_b(Clamp{}, 0);
+        split_b();
+        __syncthreads();
+        int c = 0;
+        // full intervals: nothing they touch (MFMA rows of c, c + 1, dZ up to c + 2, A rows up to c + 4) reaches past the split
+        for (; KC * (c + 5) <= R; c += 2) {
+            sub(Plain{}, c); sub(Plain{}, c + 1);
+            __syncthreads();
+        }
+        // tail: the same schedule with clamped rows, until the split's rows are used up
+        for (; KC * c < R; ++c) {
+            sub(Clamp{}, c);
+            if (c & 1) __syncthreads();
+        }
+    }
+    float *w = ws + ((long long)sp * G + g) * dwxh_ws_floats(H);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            w[(long long)row * kG4 + col0 + li] = acc[t][r];
+        }
+    bsum += __shfl_xor(bsum, 32, 64);
+    if (kh == 0) w[(long long)NT * 32 * kG4 + col0 + li] = bsum;
+}
+
 // grads[g][oWx .. oWx + (H+64+1)*256) = sum over splits, in split order
 __global__ void dwxh_reduce_kernel(const float *__restrict__ ws, int G, int S, long long per, float *__restrict__ grads,
                                    long long stride, long long off) {
@@ -2568,7 +2809,8 @@ template <class F> bool with_fused_width(int H, F &&f) { return with_width(Fused
 // by construction, so tsc_model_create has no runtime test (and no failure path) for them; it compares the others (Tile, Ws, FcThread:
 // any H, SMAX) with kLdsMax where it picks the forward.
 template <int... W> constexpr bool fused_kernels_fit(Widths<W...>) {
-    return ((policy_fwd_fc_mfma_lds(W) <= kLdsMax && dwxh_lds<(W + kL) / 32>() <= kLdsMax && fc_bwd_lds(W) <= kLdsMax) && ...);
+    return ((policy_fwd_fc_mfma_lds(W) <= kLdsMax && dwxh_lds<(W + kL) / 32>() <= kLdsMax && dwxh_split_lds<(W + kL) / 32>() <= kLdsMax &&
+             fc_bwd_lds(W) <= kLdsMax) && ...);
 }
 static_assert(fused_kernels_fit(FusedWidths{}) && dx1w1_lds() <= kLdsMax && lstm_fwd_lds() <= kLdsMax && lstm_bwd2_lds() <= kLdsMax,
               "a kernel's dynamic LDS exceeds the workgroup's");
@@ -2587,6 +2829,7 @@ inline bool fills_cache(Fwd f) { return f == Fwd::Tile || f == Fwd::Ws || f == F
 struct Plan {
     Fwd fwd;
     bool dwxh;      // LSTM: dWx | dWh | dbl in one pass (dwxh_kernel<(H + kL) / 32>), else two grouped GEMMs
+    bool dw_split;  // ... on the bf16 matrix cores with three-way split operands (dwxh_split_kernel), else dwxh_kernel's exact f32
     bool dx1w1;     // LSTM: dX1 in registers, dW1 | db1 in the same pass (dx1w1_kernel2<H / 16>), else two grouped GEMMs
     bool fc_bwd;    // FcACPolicy: dWfc | dbfc | dW1 | db1 in one pass, dX1 in registers (fc_bwd_kernel<H / 16>)
     int s_fwd;      // Ws: workgroups per tower
@@ -2763,6 +3006,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
         P.fwd = !tile ? Fwd::Dense
               : wide && policy_fwd_ws_lds(L.H, L.SMAX) <= kLdsMax && !(fwd_ws && fwd_ws[0] == '0') ? Fwd::Ws : Fwd::Tile;
         P.dwxh = wide && !env_int("TSC_UNFUSED_DW", 0) && ws_fits(dwxh_ws_floats(L.H));
+        P.dw_split = P.dwxh && env_int("TSC_DW_SPLIT", 1) != 0;
         P.dx1w1 = wide && narrow_obs && !unfused_dx && ws_fits(w1_ws_floats(L.H));
     } else {
         // policy_fwd_fc_mfma_kernel fits every fused width (114 KiB of LDS at H = 224); the per-thread kernel does not fit at
@@ -2805,7 +3049,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
         constexpr int H = decltype(w)::value;
         if (P.fwd == Fwd::Ws) allow_lds((const void *)policy_fwd_ws_kernel<(H + kL) / 2>);
         if (P.fwd == Fwd::FcMfma) allow_lds((const void *)policy_fwd_fc_mfma_kernel<H / 32>);
-        if (P.dwxh) allow_lds((const void *)dwxh_kernel<(H + kL) / 32>);
+        if (P.dwxh) allow_lds(P.dw_split ? (const void *)dwxh_split_kernel<(H + kL) / 32> : (const void *)dwxh_kernel<(H + kL) / 32>);
         if (P.dx1w1) allow_lds((const void *)dx1w1_kernel2<H / 16>);
         if (P.fc_bwd) allow_lds((const void *)fc_bwd_kernel<H / 16>);
     });
@@ -2887,6 +3131,12 @@ int tsc_model_path(tsc_model *m, int32_t out[2]) {
     const Fwd f = m->plan.fwd;
     out[0] = !fc ? -1 : f == Fwd::FcMfma ? 2 : f == Fwd::FcThread ? 1 : 0;
     out[1] = !fc ? -1 : m->plan.fc_bwd ? 1 : 0;
+    return 0;
+}
+
+int tsc_model_dw_split(tsc_model *m, int32_t *out) {
+    if (!m || !out) return tsc::fail("tsc_model_dw_split: bad arguments");
+    *out = m->plan.dw_split;
     return 0;
 }
 
@@ -3073,21 +3323,32 @@ int tsc_model_rollout_slot(tsc_model *m, int32_t t, void *ptrs[6]) {
 
 // The one-pass weight-gradient launches of the update (dwxh, dx1w1 / fc_bwd): the kernel over S x G workgroups of
 // split_rows(N, S, its quantum) rows each, then its reduce pass, under their two profile ids.
+// (both kernels take the same splits: partials, and so the reduce, do not depend on which one ran)
+static void launch_dwxh_pass(int H, bool split, const float *X1, const float *Hp, const float *dZ, long long N, int G, int S, float *ws,
+                             long long *dbg, hipStream_t st) {
+    with_fused_width(H, [&](auto w) {
+        constexpr int NT = (decltype(w)::value + kL) / 32;
+        if (split)
+            hipLaunchKernelGGL(dwxh_split_kernel<NT>, dim3((unsigned)(S * G)), dim3(512), dwxh_split_lds<NT>(), st, X1, Hp, dZ, N, G, S,
+                               split_rows(N, S, kDwK), ws);
+        else
+            hipLaunchKernelGGL(dwxh_kernel<NT>, dim3((unsigned)(S * G)), dim3(512), dwxh_lds<NT>(), st, X1, Hp, dZ, N, G, S,
+                               split_rows(N, S, kDwK), ws, dbg);
+    });
+}
+static void launch_dwxh_reduce(int H, const float *ws, int G, int S, float *grads, long long stride, long long off, hipStream_t st) {
+    const long long per = dwxh_ws_floats(H);
+    hipLaunchKernelGGL(dwxh_reduce_kernel, dim3((unsigned)((per * G + 255) / 256)), dim3(256), 0, st, ws, G, S, per, grads, stride, off);
+}
 static void launch_dwxh(tsc_model *m, long long N) {        // LSTM: dWx | dWh | dbl
     const Layout &L = m->lay;
     const int G = L.G, S = m->plan.s_upd;
-    const long long per = dwxh_ws_floats(L.H);
     {
         tsc::ProfScope ps(tsc::KID_DWX_GEMM, m->stream);
-        with_fused_width(L.H, [&](auto w) {
-            constexpr int NT = (decltype(w)::value + kL) / 32;
-            hipLaunchKernelGGL(dwxh_kernel<NT>, dim3((unsigned)(S * G)), dim3(512), dwxh_lds<NT>(), m->stream, m->X1, m->Hp, m->Z, N, G, S,
-                               split_rows(N, S, kDwK), m->ws, m->dbg);
-        });
+        launch_dwxh_pass(L.H, m->plan.dw_split, m->X1, m->Hp, m->Z, N, G, S, m->ws, m->dbg, m->stream);
     }
     tsc::ProfScope ps(tsc::KID_DWH_GEMM, m->stream);
-    hipLaunchKernelGGL(dwxh_reduce_kernel, dim3((unsigned)((per * G + 255) / 256)), dim3(256), 0, m->stream, m->ws, G, S, per, m->grads,
-                       L.stride, L.oWx);
+    launch_dwxh_reduce(L.H, m->ws, G, S, m->grads, L.stride, L.oWx, m->stream);
 }
 
 // dX1 stays in registers, dW1 | db1 come out of the same pass.  LSTM: dx1w1_kernel2 over the gate gradients in Z; FcACPolicy:
@@ -3351,6 +3612,26 @@ int tsc_gemm_grouped_f32(int32_t form, int32_t epi, int32_t groups, int32_t M, i
     tsc::plan_splitk(a, groups, form != 0 ? splitk_ws : nullptr, splitk_wsc, (size_t)ws_floats, (size_t)wsc_floats);
     tsc::launch_gemm_dyn(form != 0, epi, a, groups, (hipStream_t)hip_stream);
     TSC_HIP(hipGetLastError());
+    return 0;
+}
+
+int tsc_dwxh_f32(int32_t H, int64_t N, int32_t G, int32_t S, const float *X1, const float *Hp, const float *dZ, float *out, int32_t split) {
+    if (!X1 || !Hp || !dZ || !out || N < 1 || G < 1 || S < 1) return tsc::fail("tsc_dwxh_f32: bad arguments");
+    if (!with_fused_width(H, [](auto) {})) return tsc::fail("tsc_dwxh_f32: no kernel for H = %d", H);
+    hipError_t attr = hipSuccess;
+    with_fused_width(H, [&](auto w) {
+        constexpr int NT = (decltype(w)::value + kL) / 32;
+        attr = hipFuncSetAttribute(split ? (const void *)dwxh_split_kernel<NT> : (const void *)dwxh_kernel<NT>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
+    });
+    TSC_HIP(attr);
+    tsc::DeviceBufs bufs;
+    float *ws = nullptr;
+    TSC_HIP(bufs.alloc(&ws, (size_t)S * G * dwxh_ws_floats(H), false));
+    launch_dwxh_pass(H, split != 0, X1, Hp, dZ, N, G, S, ws, nullptr, nullptr);
+    launch_dwxh_reduce(H, ws, G, S, out, dwxh_ws_floats(H), 0, nullptr);
+    TSC_HIP(hipGetLastError());
+    TSC_HIP(hipDeviceSynchronize());
     return 0;
 }
 

@@ -4,7 +4,8 @@
     python tools/bench_update.py [--envs 1024] [--agent ma2c] [--policy lstm] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]]
 --algo ppo times `--ppo-epochs` epochs per rollout and also prints the wall time (stream-synchronised, profiling off) of an epoch-0
 update and of a later epoch (re-forward + update); --algo a2c prints the wall time of its one update the same way.
-Environment knobs of the library (TSC_UNFUSED_DW, TSC_UNFUSED_DX) select kernel variants for A/B runs.
+Environment knobs of the library (TSC_DW_SPLIT, TSC_UNFUSED_DW, TSC_UNFUSED_DX; INTEGRATION.md section 5) select kernel variants for A/B runs;
+the dwxh stamps are dwxh_kernel's (TSC_DW_SPLIT=0): dwxh_split_kernel carries none.
 --stamps (a library built with TSC_BUILD_DEFS=-DTSC_UPD_STAMPS=1): shader-clock stamps of workgroup 0, waves 0 and 4 (the two
 wavefronts of one SIMD), in one step of dwxh_kernel (16 rows: sub-chunk 11, the last of its 64-row interval) and of dx1w1_kernel2
 (32 rows: chunk 5) -- step start, first MFMA, last MFMA, staging done, barrier passed -- printed as cycles per segment, each
