@@ -46,11 +46,11 @@ SYMBOLS = ['tsc_last_error', 'tsc_version', 'tsc_profile_enable', 'tsc_profile_s
            'tsc_profile_name', 'tsc_env_create', 'tsc_env_destroy', 'tsc_env_set_stream', 'tsc_env_set_resident_instances',
            'tsc_env_reset', 'tsc_env_set_stream_routes', 'tsc_env_set_demand', 'tsc_env_demand', 'tsc_env_set_greedy', 'tsc_env_greedy_actions', 'tsc_env_set_pressure', 'tsc_env_pressure_actions', 'tsc_env_set_actuated', 'tsc_env_actuated_actions', 'tsc_env_actuated_state', 'tsc_env_set_reward_pressure', 'tsc_env_fixed_time_actions', 'tsc_env_set_fingerprint', 'tsc_env_bind_fingerprint', 'tsc_env_reward_sum', 'tsc_env_step', 'tsc_env_step_plan', 'tsc_env_get_state',
            'tsc_env_live_vehicles', 'tsc_env_vehicle_counts', 'tsc_env_set_block_order', 'tsc_env_counters', 'tsc_env_debug_clock', 'tsc_env_live_sum', 'tsc_env_record', 'tsc_env_read_record', 'tsc_env_read_trips', 'tsc_env_trace', 'tsc_env_read_trace', 'tsc_env_lane_data', 'tsc_env_read_lane_data', 'tsc_env_set_car_following', 'tsc_env_car_following',
-           'tsc_model_create', 'tsc_model_destroy', 'tsc_model_set_stream', 'tsc_model_layout', 'tsc_model_path', 'tsc_model_plan', 'tsc_model_dw_split',
+           'tsc_model_create', 'tsc_model_destroy', 'tsc_model_set_stream', 'tsc_model_layout', 'tsc_model_path', 'tsc_model_plan', 'tsc_model_dw_split', 'tsc_model_dx_split',
            'tsc_model_set_params', 'tsc_model_reset_opt_state', 'tsc_model_debug_read', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state',
            'tsc_model_reset', 'tsc_model_forward', 'tsc_model_forward_sample', 'tsc_model_sample', 'tsc_model_add_transition',
            'tsc_model_rollout_slot', 'tsc_model_compute_grads', 'tsc_model_grad_buffer', 'tsc_model_apply_grads', 'tsc_model_compute_grads_ppo', 'tsc_model_apply_grads_ex', 'tsc_model_ppo_stats', 'tsc_model_get_returns', 'tsc_model_debug_clock',
-           'tsc_gemm_grouped_f32', 'tsc_dwxh_f32',
+           'tsc_gemm_grouped_f32', 'tsc_dwxh_f32', 'tsc_dx1w1_f32',
            'tsc_iql_create', 'tsc_iql_destroy', 'tsc_iql_set_stream', 'tsc_iql_layout', 'tsc_iql_set_params', 'tsc_iql_get_params',
            'tsc_iql_get_opt_state', 'tsc_iql_set_opt_state', 'tsc_iql_forward', 'tsc_iql_add_transition', 'tsc_iql_replay_size',
            'tsc_iql_compute_grads', 'tsc_iql_compute_grads_at', 'tsc_iql_grad_buffer', 'tsc_iql_apply_grads', 'tsc_iql_debug_batch', 'tsc_iql_path', 'tsc_iql_debug_clock',

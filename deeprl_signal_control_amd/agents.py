@@ -260,6 +260,7 @@ def _setup_lib(L):
     L.tsc_model_path.argtypes = [vp, C.POINTER(C.c_int32)]
     L.tsc_model_plan.argtypes = [vp, C.POINTER(C.c_int32)]
     L.tsc_model_dw_split.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_model_dx_split.argtypes = [vp, C.POINTER(C.c_int32)]
     for f in ('tsc_model_set_params', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state'):
         getattr(L, f).argtypes = [vp, vp]
     L.tsc_model_reset_opt_state.argtypes = [vp]
@@ -281,6 +282,7 @@ def _setup_lib(L):
     L.tsc_gemm_grouped_f32.argtypes = [C.c_int32] * 6 + [vp, C.c_int64, C.c_int32, vp, C.c_int64, C.c_int32,
                                                         vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, C.c_int64, vp, C.c_int64, vp]
     L.tsc_dwxh_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32]
+    L.tsc_dx1w1_f32.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int32]
     L._model_ready = True
 
 
@@ -344,6 +346,9 @@ class VecA2C:
         dws = C.c_int32()
         _lib.check(L.tsc_model_dw_split(h, C.byref(dws)))
         self.dw_split = int(dws.value)          # dwxh on the bf16 matrix cores (three-way split operands); 0: exact f32 (TSC_DW_SPLIT=0)
+        dxs = C.c_int32()
+        _lib.check(L.tsc_model_dx_split(h, C.byref(dxs)))
+        self.dx_split = int(dxs.value)          # dX1 of dx1w1 on the bf16 matrix cores (three-way split operands); 0: exact f32 (TSC_DX_SPLIT=0)
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream(self.device)
             _lib.check(L.tsc_model_set_stream(h, C.c_void_p(self.stream.cuda_stream)))

@@ -23,7 +23,7 @@
 //   update .......... head_bwd (persistent, loss gradient + dH + dWo | dbo) -> lstm_bwd2 (Wh^T stationary in registers,
 //                     dc in registers / dh through LDS over the n_step time steps, next step's inputs in flight under the
 //                     MFMAs) -> dwxh (dWx | dWh | dbl, whole tower output in accumulators; dwxh_split_kernel: bf16 MFMAs on
-//                     three-way split f32 operands, dwxh_kernel: exact f32 behind TSC_DW_SPLIT=0) -> dx1w1_kernel2 (dX1 in
+//                     three-way split f32 operands, dwxh_kernel: exact f32 behind TSC_DW_SPLIT=0) -> dx1w1_split_kernel / dx1w1_kernel2 (TSC_DX_SPLIT=0) (dX1 in
 //                     registers, chained into dW1 | db1) -> grad_norm -> rmsprop; the FcACPolicy update: head_bwd ->
 //                     fc_bwd_kernel (dWfc | dbfc | dW1 | db1 in one pass over the X1 / Hh rows its rollout forward cached;
 //                     the grouped split-K GEMMs of tsc_gemm.h behind TSC_UNFUSED_DX and for other shapes)
@@ -2575,6 +2575,291 @@ dx1w1_kernel2(const float *__restrict__ dZ, const float *__restrict__ X1, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// dx1w1_kernel2 with the dX1 = dZ Wx^T product on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16), both f32 operands cut into
+// three bf16 pieces with p1 + p2 + p3 == x EXACTLY and six piece products per tile into the same f32 accumulator, smallest first
+// (a3 b1, a1 b3, a2 b2, a2 b1, a1 b2, a1 b1), as in dwxh_split_kernel.  Same contract as dx1w1_kernel2: arguments, grid, splits with
+// the 32-row quantum, the record w1_flush writes; the relu mask, the row clamp, the obs^T dX1 tail (f32, w1_tail) are its own.
+//   * Wx^T (B) stays stationary as f32, 64 registers per column unit, loaded exactly as dx1w1_kernel2 loads it: three bf16 planes of a
+//     tower (344 KB) fit neither the CU's registers nor its LDS.  The eight registers bw[8 s .. 8 s + 7] of K-step s are cut right
+//     before the MFMAs that use them, by TRUNCATION: p1 = the high half of x (one byte permute packs two), p2 = the high half of
+//     x - p1, p3 = the high half of (x - p1) - p2; every subtraction is exact and 8 + 8 + 8 bits hold the 24-bit significand (44 VALU
+//     instructions per fragment; tests/test_dx1w1_split_host.py restates it).  The mask and the permute selector come out of scalar
+//     registers made opaque at every K-step, or the loop-invariant pieces (192 registers per wave) are hoisted out of the chunk loop,
+//     or to the head of the unit, and spilled; made opaque themselves, the weight registers were copied (another 128).
+//   * The contraction index is permuted so that those eight registers ARE the B fragment: element e of lane group kq in K-step s is
+//     k = 32 s + 16 (e >> 2) + 4 kq + (e & 3).
+//   * dZ (A) is cut once per chunk by the staging thread that holds the float4 (round-to-nearest pieces, dwxh_split_kernel's put)
+//     and lives in LDS as three planes [row tile 2][K-step 8][kq 4][row 16][8 bf16 in the order above]: the fragment of lane
+//     (row n, kq) is ONE ds_read_b128 at 16 lane + a constant, and any 16 lanes with distinct n cover the 64 banks once whatever
+//     their kq, so the four lane groups of the read are conflict-free without padding or swizzle.  A staging thread takes the four
+//     float4s of row 8 (wave & 3) + (lane >> 3) at 16-byte columns (lane & 7) + 8 (wave >> 2) + 16 q: 128-byte lines per eight lanes
+//     from HBM, and ds_write_b64 on all 32 banks four lanes deep (the minimum for 512 bytes).
+// Loop boundaries: dx1w1_kernel2's (plain chunks while the successor is whole, then clamped ones).
+// LDS 2 x 3 x 16 KiB + the obs chunks = 115 712 bytes.  Measured: profiles/dx1w1_split_bench.json.
+// ------------------------------------------------------------------------------------------------
+constexpr unsigned kDxPlane = 2 * 8 * 4 * 16 * 16;          // bytes of one piece of a 32-row dZ chunk
+constexpr size_t dx1w1_split_lds() { return 2 * 3 * (size_t)kDxPlane + sizeof(float) * 2 * kW1Chunk * kObLd; }        // Az | Ob
+
+// bw[8 s .. 8 s + 7] -> the three B fragments of K-step s.  perm(y, x, SEL) = high half of x | high half of y << 16; HI and SEL
+// pass through an opaque scalar register (see the kernel's header)
+__device__ __forceinline__ void dx_cut8(const float (&bw)[64], int s, bf16x8 &b1, bf16x8 &b2, bf16x8 &b3) {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    unsigned HI = 0xffff0000u, SEL = 0x07060302u;
+    asm volatile("" : "+s"(HI), "+s"(SEL));
+    u32x4 w1, w2, w3;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float x = bw[8 * s + 2 * e], y = bw[8 * s + 2 * e + 1];
+        const unsigned ux = __float_as_uint(x), uy = __float_as_uint(y);
+        w1[e] = __builtin_amdgcn_perm(uy, ux, SEL);
+        const float rx = x - __uint_as_float(ux & HI), ry = y - __uint_as_float(uy & HI);
+        const unsigned vx = __float_as_uint(rx), vy = __float_as_uint(ry);
+        w2[e] = __builtin_amdgcn_perm(vy, vx, SEL);
+        const float tx = rx - __uint_as_float(vx & HI), ty = ry - __uint_as_float(vy & HI);
+        w3[e] = __builtin_amdgcn_perm(__float_as_uint(ty), __float_as_uint(tx), SEL);
+    }
+    b1 = __builtin_bit_cast(bf16x8, w1);
+    b2 = __builtin_bit_cast(bf16x8, w2);
+    b3 = __builtin_bit_cast(bf16x8, w3);
+}
+
+template <int NCU>   // H / 16
+__global__ void __launch_bounds__(512, 1)
+dx1w1_split_kernel(const float *__restrict__ dZ, const float *__restrict__ X1, const float *__restrict__ WxT,
+                   const float *__restrict__ obs, long long N, int G, int S, long long rows_per_split, int A, int SMAX,
+                   float *__restrict__ ws, const int *__restrict__ ftm, long long *dbg) {
+    constexpr int H = 16 * NCU, NHU = 2 * NCU;                  // half units (column unit x row tile) per chunk
+    constexpr int CHI = (NHU + 7) / 8, CLO = NHU / 8;           // tiles of waves 0..3 / 4..7
+    constexpr unsigned PL = kDxPlane, BUF = 3 * PL;
+    static_assert(NHU % 8 == 0 || NHU % 8 == 4, "H must be a multiple of 32");
+    static_assert(2 * PL + 8192 + 7 * 1024 < 65536, "a fragment read's immediate offset");
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    char *Az = smem_raw;                                        // [2][3 pieces][PL]
+    float *Ob = (float *)(smem_raw + 2 * BUF);                  // [2][32][kObLd]
+    const int g = blockIdx.x % G, sp = blockIdx.x / G, a = g >> 1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), n = lane & 15, kq = lane >> 4;
+    const long long n0 = (long long)sp * rows_per_split;
+    long long n1 = n0 + rows_per_split;
+    if (n1 > N) n1 = N;
+    const float *dz = dZ + (long long)g * N * kG4, *x1 = X1 + (long long)g * N * H;
+    const long long AS = (long long)A * SMAX;
+    const int sq = SMAX >> 2;
+    float *w = ws + ((long long)sp * G + g) * w1_ws_floats(H);
+    // this wave's half units [st, st + cnt): unit = h >> 1, row tile = h & 1 (dx1w1_kernel2's deal)
+    const int st = wave < 4 ? wave * CHI : 4 * CHI + (wave - 4) * CLO, cnt = wave < 4 ? CHI : CLO;
+    const int U0 = st >> 1;
+    const bool a00 = 2 * U0 >= st, a01 = 2 * U0 + 1 < st + cnt, a10 = 2 * U0 + 2 < st + cnt, a11 = 2 * U0 + 3 < st + cnt;
+    const int U1 = U0 + 1 < NCU ? U0 + 1 : NCU - 1;             // clamped when the second slot is unused
+    const int col0 = 16 * U0 + n, col1 = 16 * U1 + n;
+    const int fm0 = ftm[a * NCU + U0], fm1 = ftm[a * NCU + U1];
+    // stationary B operands: bwX[4 j + c] = Wx^T[k = 16 j + 4 kq + c][col]; K-step s takes j = 2 s, 2 s + 1
+    float bw0[64], bw1[64];
+    {
+        const float *src = WxT + (long long)g * kG4 * H + (long long)(4 * kq) * H;
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                bw0[4 * j + c] = src[(long long)(16 * j + c) * H + col0];
+                bw1[4 * j + c] = src[(long long)(16 * j + c) * H + col1];
+            }
+    }
+    f32x4 accW[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int ft = 0; ft < 4; ++ft) accW[u][ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum0 = 0.f, bsum1 = 0.f;
+    // staging: thread -> four dZ float4s of chunk row zrow (16-byte columns zc0 + 16 q: K-steps (wave >> 2) + 2 q) and one obs float4
+    struct Stg { int zrow, zc0, orow, oc; };
+    auto stg = [](int t) { return Stg{8 * ((t >> 6) & 3) + ((t >> 3) & 7), (t & 7) + 8 * (t >> 8), t >> 4, t & 15}; };
+    // (the clamped chunks and the flush recompute their lane values from an opaque tid: shared with the plain loop's they stay in
+    // registers across it, and the kernel spills)
+    auto opaque_tid = [&]() { int t = tid; asm volatile("" : "+v"(t)); return t; };
+    const int zrow = stg(tid).zrow, zc0 = stg(tid).zc0, orow = stg(tid).orow, oc = stg(tid).oc;
+    f32x4 s0, s1, s2, s3, so;
+    using Clamp = std::true_type;
+    using Plain = std::false_type;
+    const unsigned zo = zrow * kG4 + 4 * zc0, oo = (unsigned)orow * (unsigned)AS + 4 * (oc < sq ? oc : 0);
+    // LDS byte of the first float4's four values inside a piece's plane; the q-th: + 2048 q
+    const unsigned zl = (zrow >> 4) * 8192 + (wave >> 2) * 1024 + (lane & 3) * 256 + (zrow & 15) * 16 + ((lane >> 2) & 1) * 8;
+    const bool ob_ok = oc < sq;
+    // the chunk at row0 in two halves (a wave with two column units holds one half at a time): A = the first two float4s of dZ,
+    // B = the other two and the obs float4
+    auto fetchA = [&](auto cl, long long row0) {
+        if constexpr (decltype(cl)::value) {
+            const Stg q = stg(opaque_tid());
+            const long long r = row0 + q.zrow;
+            const float *zs = dz + (r < n1 ? r : n1 - 1) * kG4 + 4 * q.zc0;
+            s0 = *reinterpret_cast<const f32x4 *>(zs);
+            s1 = *reinterpret_cast<const f32x4 *>(zs + 64);
+        } else {
+            const gfloat_p zs = uniform_ptr(dz + row0 * kG4);
+            s0 = *(gfloat4_p)(zs + zo);
+            s1 = *(gfloat4_p)(zs + 64 + zo);
+        }
+    };
+    auto fetchB = [&](auto cl, long long row0) {
+        if constexpr (decltype(cl)::value) {
+            auto rowc = [&](long long r) { return r < n1 ? r : n1 - 1; };
+            const Stg q = stg(opaque_tid());
+            const float *zs = dz + rowc(row0 + q.zrow) * kG4 + 4 * q.zc0;
+            s2 = *reinterpret_cast<const f32x4 *>(zs + 128);
+            s3 = *reinterpret_cast<const f32x4 *>(zs + 192);
+            const f32x4 o = *reinterpret_cast<const f32x4 *>(obs + rowc(row0 + q.orow) * AS + (long long)a * SMAX + 4 * (q.oc < sq ? q.oc : 0));
+            so = q.oc < sq ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+            const gfloat_p zs = uniform_ptr(dz + row0 * kG4), os = uniform_ptr(obs + row0 * AS + (long long)a * SMAX);
+            s2 = *(gfloat4_p)(zs + 128 + zo);
+            s3 = *(gfloat4_p)(zs + 192 + zo);
+            const f32x4 o = *(gfloat4_p)(os + oo);
+            so = ob_ok ? o : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    // a float4 of four k of one row -> its three pieces, one 8-byte store per plane
+    auto cut = [&](char *d, const f32x4 &v) {
+        bf16x4 p1, p2, p3;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            p1[e] = (__bf16)v[e];
+            const float r1 = v[e] - (float)p1[e];
+            p2[e] = (__bf16)r1;
+            p3[e] = (__bf16)(r1 - (float)p2[e]);
+        }
+        *reinterpret_cast<bf16x4 *>(d) = p1;
+        *reinterpret_cast<bf16x4 *>(d + PL) = p2;
+        *reinterpret_cast<bf16x4 *>(d + 2 * PL) = p3;
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto putA = [&](int buf) {
+        char *d = Az + (unsigned)buf * BUF + zl;
+        cut(d, s0);
+        cut(d + 2048, s1);
+    };
+    auto putB = [&](int buf) {
+        char *d = Az + (unsigned)buf * BUF + zl;
+        cut(d + 4096, s2);
+        cut(d + 6144, s3);
+        *reinterpret_cast<f32x4 *>(Ob + ((long long)buf * 32 + orow) * kObLd + 4 * oc) = so;
+    };
+#ifdef TSC_UPD_STAMPS
+    // (dbg[16 .. 31], dx1w1_kernel2's slots and its stamps 0 .. 4; 5 / 6: the first unit's MFMAs / its tail done)
+    long long *stp = dbg && blockIdx.x == 0 && (tid == 0 || tid == 256) ? dbg + 16 + (tid >> 8) * 8 : nullptr;
+#define USTAMP(k) do { if (stp && row == n0 + 5 * 32) stp[k] = clock64(); } while (0)
+#else
+#define USTAMP(k) do { } while (0)
+#endif
+    // one column unit of the chunk in LDS buffer `buf`: both / one of its row tiles
+    auto unit = [&](auto cl, int buf, long long row, const float (&bw)[64], int ub, bool r0, bool r1, f32x4 (&aw)[4], float &bs, int fm,
+                    bool first) __attribute__((always_inline)) {
+        constexpr bool clamp = decltype(cl)::value;
+        // relu mask rows 16 r + 4 kq + i of column col: requested first, consumed after the MFMAs
+        float xm0[4], xm1[4];
+        int zq = 0;
+        asm volatile("" : "+v"(zq));
+        if constexpr (clamp) {
+            const int t = opaque_tid(), col = ub + (t & 15);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                long long ra = row + 4 * ((t >> 4) & 3) + i, rb = ra + 16;
+                if (ra >= n1) ra = n1 - 1;
+                if (rb >= n1) rb = n1 - 1;
+                xm0[i] = x1[ra * H + col];
+                xm1[i] = x1[rb * H + col];
+            }
+        } else {
+            const gfloat_p xs = uniform_ptr(x1 + row * H);
+            const unsigned xo = (unsigned)(4 * kq * H + ub + n + zq);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                xm0[i] = (xs + i * H)[xo];
+                xm1[i] = (xs + (16 + i) * H)[xo];
+            }
+        }
+        f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = f32x4{0.f, 0.f, 0.f, 0.f};
+        const char *ab = Az + (unsigned)buf * BUF + 16 * lane;
+        auto frag = [&](int r, int s, int p) { return *reinterpret_cast<const bf16x8 *>(ab + p * PL + r * 8192 + s * 1024); };
+        // one K-step of one row tile: the six piece products, smallest first, into the tile's accumulator
+        auto step = [&](int r, int s, const bf16x8 &b1, const bf16x8 &b2, const bf16x8 &b3, f32x4 &c) __attribute__((always_inline)) {
+            const bf16x8 p3 = frag(r, s, 2), p1 = frag(r, s, 0), p2 = frag(r, s, 1);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p3, b1, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p1, b3, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p2, b2, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p2, b1, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p1, b2, c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(p1, b1, c, 0, 0, 0);
+        };
+        if (r0 && r1) {
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                bf16x8 b1, b2, b3;
+                dx_cut8(bw, s, b1, b2, b3);
+                __builtin_amdgcn_sched_barrier(0);
+                step(0, s, b1, b2, b3, c0);
+                __builtin_amdgcn_sched_barrier(0);
+                step(1, s, b1, b2, b3, c1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            const int r = r0 ? 0 : 1;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                bf16x8 b1, b2, b3;
+                dx_cut8(bw, s, b1, b2, b3);
+                __builtin_amdgcn_sched_barrier(0);
+                step(r, s, b1, b2, b3, c0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (!r0) { c1 = c0; }
+        }
+        if (first) USTAMP(5);
+        auto tail = [&](int r, const f32x4 &c, const float (&xm)[4]) { w1_tail<clamp>(Ob, buf, r, kq, n, c, xm, row, n1, fm, aw, bs); };
+        if (r0) tail(0, c0, xm0);
+        if (r1) tail(1, c1, xm1);
+        if (first) USTAMP(6);
+    };
+    // The next chunk goes into the other LDS buffer, which nobody reads before the barrier.  A wave with two column units requests
+    // half A before its first unit and writes it after that unit, then the same with half B around the second (the five staging
+    // float4s at once do not fit beside 128 weight registers); a wave with one unit requests both halves before it.
+    const bool two = a10 || a11;
+    auto chunk = [&](auto cl, int buf, long long row) __attribute__((always_inline)) {
+        USTAMP(0);
+        fetchA(cl, row + 32);
+        if (!two) fetchB(cl, row + 32);
+        USTAMP(1);
+        if (a00 || a01) unit(cl, buf, row, bw0, 16 * U0, a00, a01, accW[0], bsum0, fm0, true);
+        if (two) {
+            putA(buf ^ 1);
+            fetchB(cl, row + 32);
+            unit(cl, buf, row, bw1, 16 * U1, a10, a11, accW[1], bsum1, fm1, false);
+        }
+        USTAMP(2);
+        if (!two) putA(buf ^ 1);
+        putB(buf ^ 1);
+        USTAMP(3);
+        __syncthreads();
+        USTAMP(4);
+    };
+    if (n0 < n1) {
+        fetchA(Clamp{}, n0);
+        fetchB(Clamp{}, n0);
+        putA(0);
+        putB(0);
+        __syncthreads();
+        int buf = 0;
+        long long row = n0;
+        // full chunks whose successor is full too: no row compare, clamp or select anywhere in the loop
+        for (; row + 2 * kW1Chunk <= n1; row += kW1Chunk, buf ^= 1) chunk(Plain{}, buf, row);
+        for (; row < n1; row += kW1Chunk, buf ^= 1) chunk(Clamp{}, buf, row);
+    }
+#undef USTAMP
+    const int tf = opaque_tid();
+    auto flush = [&](const f32x4 (&aw)[4], float bs, int col, bool r0, bool r1) { w1_flush<H>(w, (tf >> 4) & 3, aw, bs, col, r0, r1); };
+    if (a00 || a01) flush(accW[0], bsum0, 16 * U0 + (tf & 15), a00, a01);
+    if (a10 || a11) flush(accW[1], bsum1, 16 * U1 + (tf & 15), a10, a11);
+}
+
+// ------------------------------------------------------------------------------------------------
 // FcACPolicy (agents/policies.py:214-256; BASELINE configs[1]): both layers' weight gradients of one tower in ONE pass over
 // the n-step batch.  The second layer is fc(H -> 64) + relu, so its pre-activation gradient dZ [N][64] is what head_bwd
 // leaves in dH (relu' of the 64 units folded in); then
@@ -2812,7 +3097,7 @@ template <int... W> constexpr bool fused_kernels_fit(Widths<W...>) {
     return ((policy_fwd_fc_mfma_lds(W) <= kLdsMax && dwxh_lds<(W + kL) / 32>() <= kLdsMax && dwxh_split_lds<(W + kL) / 32>() <= kLdsMax &&
              fc_bwd_lds(W) <= kLdsMax) && ...);
 }
-static_assert(fused_kernels_fit(FusedWidths{}) && dx1w1_lds() <= kLdsMax && lstm_fwd_lds() <= kLdsMax && lstm_bwd2_lds() <= kLdsMax,
+static_assert(fused_kernels_fit(FusedWidths{}) && dx1w1_lds() <= kLdsMax && dx1w1_split_lds() <= kLdsMax && lstm_fwd_lds() <= kLdsMax && lstm_bwd2_lds() <= kLdsMax,
               "a kernel's dynamic LDS exceeds the workgroup's");
 
 // Which kernels a handle runs: decided once in tsc_model_create from its shapes and the knobs.
@@ -2831,6 +3116,7 @@ struct Plan {
     bool dwxh;      // LSTM: dWx | dWh | dbl in one pass (dwxh_kernel<(H + kL) / 32>), else two grouped GEMMs
     bool dw_split;  // ... on the bf16 matrix cores with three-way split operands (dwxh_split_kernel), else dwxh_kernel's exact f32
     bool dx1w1;     // LSTM: dX1 in registers, dW1 | db1 in the same pass (dx1w1_kernel2<H / 16>), else two grouped GEMMs
+    bool dx_split;  // ... its dX1 product on the bf16 matrix cores with three-way split operands (dx1w1_split_kernel<H / 16>)
     bool fc_bwd;    // FcACPolicy: dWfc | dbfc | dW1 | db1 in one pass, dX1 in registers (fc_bwd_kernel<H / 16>)
     int s_fwd;      // Ws: workgroups per tower
     int s_upd;      // dwxh / dx1w1 / fc_bwd: row splits per tower (~ one workgroup per CU)
@@ -3008,6 +3294,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
         P.dwxh = wide && !env_int("TSC_UNFUSED_DW", 0) && ws_fits(dwxh_ws_floats(L.H));
         P.dw_split = P.dwxh && env_int("TSC_DW_SPLIT", 1) != 0;
         P.dx1w1 = wide && narrow_obs && !unfused_dx && ws_fits(w1_ws_floats(L.H));
+        P.dx_split = P.dx1w1 && env_int("TSC_DX_SPLIT", 1) != 0;
     } else {
         // policy_fwd_fc_mfma_kernel fits every fused width (114 KiB of LDS at H = 224); the per-thread kernel does not fit at
         // H = 224 (161 KiB), so MA2C-FC on large_grid with TSC_FC_MFMA=0 takes the dense GEMMs + head_fwd_kernel
@@ -3050,7 +3337,7 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
         if (P.fwd == Fwd::Ws) allow_lds((const void *)policy_fwd_ws_kernel<(H + kL) / 2>);
         if (P.fwd == Fwd::FcMfma) allow_lds((const void *)policy_fwd_fc_mfma_kernel<H / 32>);
         if (P.dwxh) allow_lds(P.dw_split ? (const void *)dwxh_split_kernel<(H + kL) / 32> : (const void *)dwxh_kernel<(H + kL) / 32>);
-        if (P.dx1w1) allow_lds((const void *)dx1w1_kernel2<H / 16>);
+        if (P.dx1w1) allow_lds(P.dx_split ? (const void *)dx1w1_split_kernel<H / 16> : (const void *)dx1w1_kernel2<H / 16>);
         if (P.fc_bwd) allow_lds((const void *)fc_bwd_kernel<H / 16>);
     });
     TSC_HIP(attr);
@@ -3137,6 +3424,12 @@ int tsc_model_path(tsc_model *m, int32_t out[2]) {
 int tsc_model_dw_split(tsc_model *m, int32_t *out) {
     if (!m || !out) return tsc::fail("tsc_model_dw_split: bad arguments");
     *out = m->plan.dw_split;
+    return 0;
+}
+
+int tsc_model_dx_split(tsc_model *m, int32_t *out) {
+    if (!m || !out) return tsc::fail("tsc_model_dx_split: bad arguments");
+    *out = m->plan.dx_split;
     return 0;
 }
 
@@ -3353,21 +3646,33 @@ static void launch_dwxh(tsc_model *m, long long N) {        // LSTM: dWx | dWh |
 
 // dX1 stays in registers, dW1 | db1 come out of the same pass.  LSTM: dx1w1_kernel2 over the gate gradients in Z; FcACPolicy:
 // fc_bwd_kernel over dZ in dHh, which adds dWfc | dbfc (perF floats of every split's record).
+static void launch_dx1w1_pass(int H, bool split, const float *dZ, const float *X1, const float *WxT, const float *obs, long long N, int G,
+                              int S, int A, int SMAX, float *ws, const int *ftm, long long *dbg, hipStream_t st) {
+    const long long rps = split_rows(N, S, kW1Chunk);
+    with_fused_width(H, [&](auto w) {
+        constexpr int NCU = decltype(w)::value / 16;
+        if (split)
+            hipLaunchKernelGGL(dx1w1_split_kernel<NCU>, dim3((unsigned)(S * G)), dim3(512), dx1w1_split_lds(), st, dZ, X1, WxT, obs, N, G, S, rps,
+                               A, SMAX, ws, ftm, dbg);
+        else
+            hipLaunchKernelGGL(dx1w1_kernel2<NCU>, dim3((unsigned)(S * G)), dim3(512), dx1w1_lds(), st, dZ, X1, WxT, obs, N, G, S, rps, A, SMAX,
+                               ws, ftm, dbg);
+    });
+}
 static void launch_w1(tsc_model *m, long long N) {
     const Layout &L = m->lay;
     const int G = L.G, S = m->plan.s_upd;
     const long long rps = split_rows(N, S, kW1Chunk), perF = L.fc ? fc2_ws_floats(L.H) : 0;
     {
         tsc::ProfScope ps(tsc::KID_DX1_GEMM, m->stream);
-        with_fused_width(L.H, [&](auto w) {
-            constexpr int H = decltype(w)::value;
-            if (L.fc)
+        if (L.fc)
+            with_fused_width(L.H, [&](auto w) {
+                constexpr int H = decltype(w)::value;
                 hipLaunchKernelGGL(fc_bwd_kernel<H / 16>, dim3((unsigned)(S * G)), dim3(512), fc_bwd_lds(H), m->stream, m->dHh, m->X1, m->WxT,
                                    m->r_obs, N, G, S, rps, L.A, L.SMAX, m->ws, m->ftmask);
-            else
-                hipLaunchKernelGGL(dx1w1_kernel2<H / 16>, dim3((unsigned)(S * G)), dim3(512), dx1w1_lds(), m->stream, m->Z, m->X1, m->WxT,
-                                   m->r_obs, N, G, S, rps, L.A, L.SMAX, m->ws, m->ftmask, m->dbg);
-        });
+            });
+        else
+            launch_dx1w1_pass(L.H, m->plan.dx_split, m->Z, m->X1, m->WxT, m->r_obs, N, G, S, L.A, L.SMAX, m->ws, m->ftmask, m->dbg, m->stream);
     }
     tsc::ProfScope ps(tsc::KID_DW1_GEMM, m->stream);
     const long long tot = ((long long)(L.SMAX + 1) * L.H + perF) * G;
@@ -3630,6 +3935,38 @@ int tsc_dwxh_f32(int32_t H, int64_t N, int32_t G, int32_t S, const float *X1, co
     TSC_HIP(bufs.alloc(&ws, (size_t)S * G * dwxh_ws_floats(H), false));
     launch_dwxh_pass(H, split != 0, X1, Hp, dZ, N, G, S, ws, nullptr, nullptr);
     launch_dwxh_reduce(H, ws, G, S, out, dwxh_ws_floats(H), 0, nullptr);
+    TSC_HIP(hipGetLastError());
+    TSC_HIP(hipDeviceSynchronize());
+    return 0;
+}
+
+// Test entry: the first-layer pass of the LSTM update (dx1w1_split_kernel or dx1w1_kernel2, then w1_reduce_kernel) on caller-supplied
+// device tensors.  dZ [G][N][256], X1 [G][N][H], Wx [G][H][256], obs [N][G / 2][SMAX], ftm [G / 2][H / 16], rowrange [G / 2][SMAX][2];
+// out [G][SMAX + 1][H] = dW1 | db1.  Synchronises.
+int tsc_dx1w1_f32(int32_t H, int64_t N, int32_t G, int32_t S, int32_t SMAX, const float *dZ, const float *X1, const float *Wx,
+                  const float *obs, const int32_t *ftm, const int16_t *rowrange, float *out, int32_t split) {
+    if (!dZ || !X1 || !Wx || !obs || !ftm || !rowrange || !out || N < 1 || G < 2 || G % 2 || S < 1)
+        return tsc::fail("tsc_dx1w1_f32: bad arguments");
+    if (SMAX < 4 || SMAX > 64 || SMAX % 4) return tsc::fail("tsc_dx1w1_f32: SMAX must be a multiple of 4 in [4, 64]");
+    if (!with_fused_width(H, [](auto) {})) return tsc::fail("tsc_dx1w1_f32: no kernel for H = %d", H);
+    hipError_t attr = hipSuccess;
+    with_fused_width(H, [&](auto w) {
+        constexpr int NCU = decltype(w)::value / 16;
+        attr = hipFuncSetAttribute(split ? (const void *)dx1w1_split_kernel<NCU> : (const void *)dx1w1_kernel2<NCU>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
+    });
+    TSC_HIP(attr);
+    tsc::DeviceBufs bufs;
+    float *ws = nullptr, *WxT = nullptr;
+    TSC_HIP(bufs.alloc(&ws, (size_t)S * G * w1_ws_floats(H), false));
+    TSC_HIP(bufs.alloc(&WxT, (size_t)G * H * kG4, false));
+    Layout lay{};
+    lay.G = G; lay.H = H; lay.NZ = kG4; lay.stride = (long long)H * kG4; lay.oWx = 0;
+    hipLaunchKernelGGL(transpose_wx_kernel, dim3((unsigned)(((long long)G * H * kG4 + 255) / 256)), dim3(256), 0, nullptr, Wx, lay, WxT);
+    launch_dx1w1_pass(H, split != 0, dZ, X1, WxT, obs, N, G, S, G / 2, SMAX, ws, ftm, nullptr, nullptr);
+    const long long per = (long long)(SMAX + 1) * H;
+    hipLaunchKernelGGL(w1_reduce_kernel, dim3((unsigned)((per * G + 255) / 256)), dim3(256), 0, nullptr, ws, G, S, H, SMAX, 0LL, rowrange, out,
+                       per, 0LL, (long long)SMAX * H, 0LL);
     TSC_HIP(hipGetLastError());
     TSC_HIP(hipDeviceSynchronize());
     return 0;

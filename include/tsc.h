@@ -102,7 +102,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 121: tsc_model_dw_split / tsc_dwxh_f32; 120: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 122: tsc_model_dx_split / tsc_dx1w1_f32; 121: tsc_model_dw_split / tsc_dwxh_f32; 120: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -390,6 +390,10 @@ int tsc_model_plan(tsc_model *m, int32_t out[6]);
  * every f32 operand cut into three bf16 pieces, six products: f32 accuracy, not bit-equal to the f32 kernel), 0 for the exact-f32
  * dwxh_kernel (TSC_DW_SPLIT=0 in the environment) or when dwxh is 0. */
 int tsc_model_dw_split(tsc_model *m, int32_t *out);
+/* Which kernel the one-pass first-layer update of the LSTM policy (plan field dx1w1) runs: *out = 1 for dx1w1_split_kernel (the
+ * dX1 = dZ Wx^T product on the bf16 matrix cores, both operands cut into three bf16 pieces, six products: f32 accuracy, not
+ * bit-equal), 0 for the exact-f32 dx1w1_kernel2 (TSC_DX_SPLIT=0 in the environment) or when dx1w1 is 0.  (tsc_version 122) */
+int tsc_model_dx_split(tsc_model *m, int32_t *out);
 int tsc_model_set_params(tsc_model *m, const float *params_host);     /* optimizer state untouched */
 int tsc_model_reset_opt_state(tsc_model *m);                         /* RMSProp ms <- 1 (TF1 slot init) */
 int tsc_model_get_params(tsc_model *m, float *params_host);
@@ -666,6 +670,15 @@ int tsc_gemm_grouped_f32(int32_t form, int32_t epi, int32_t groups, int32_t M, i
  * order.  H is one of 128 / 160 / 192 / 224.  split != 0 runs dwxh_split_kernel, 0 the exact-f32 dwxh_kernel.  Synchronises. */
 int tsc_dwxh_f32(int32_t H, int64_t N, int32_t G, int32_t S, const float *X1, const float *Hp, const float *dZ, float *out,
                  int32_t split);
+
+/* Test hook: the first-layer pass of the LSTM update on caller-supplied DEVICE inputs.  dZ [G][N][256], X1 [G][N][H] (the relu
+ * mask: X1 > 0), Wx [G][H][256], obs [N][G / 2][SMAX] (towers 2a and 2a + 1 read agent a), ftm [G / 2][H / 16] (bit t: feature
+ * tile t of dW1 has a structural non-zero in the column unit), rowrange [G / 2][SMAX][2] (hidden columns [lo, hi) an obs row
+ * feeds) -> out [G][SMAX + 1][H] = dW1 = obs^T dX1 inside the structure | db1 = colsum(dX1), dX1 = (dZ Wx^T) * [X1 > 0], over S
+ * row splits added in split order.  H is one of 128 / 160 / 192 / 224, SMAX a multiple of 4 up to 64, G even.  split != 0 runs
+ * dx1w1_split_kernel, 0 the exact-f32 dx1w1_kernel2.  Synchronises.  (tsc_version 122) */
+int tsc_dx1w1_f32(int32_t H, int64_t N, int32_t G, int32_t S, int32_t SMAX, const float *dZ, const float *X1, const float *Wx,
+                  const float *obs, const int32_t *ftm, const int16_t *rowrange, float *out, int32_t split);
 
 #ifdef __cplusplus
 }

@@ -4,8 +4,9 @@
     python tools/bench_update.py [--envs 1024] [--agent ma2c] [--policy lstm] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]]
 --algo ppo times `--ppo-epochs` epochs per rollout and also prints the wall time (stream-synchronised, profiling off) of an epoch-0
 update and of a later epoch (re-forward + update); --algo a2c prints the wall time of its one update the same way.
-Environment knobs of the library (TSC_DW_SPLIT, TSC_UNFUSED_DW, TSC_UNFUSED_DX; INTEGRATION.md section 5) select kernel variants for A/B runs;
-the dwxh stamps are dwxh_kernel's (TSC_DW_SPLIT=0): dwxh_split_kernel carries none.
+Environment knobs of the library (TSC_DW_SPLIT, TSC_DX_SPLIT, TSC_UNFUSED_DW, TSC_UNFUSED_DX) select kernel variants
+for A/B runs; --json reports the choice (dw_split, dx_split).  The dwxh stamps are dwxh_kernel's (TSC_DW_SPLIT=0): dwxh_split_kernel carries
+none; the dx1w1 stamps are taken by whichever of dx1w1_split_kernel / dx1w1_kernel2 runs.
 --stamps (a library built with TSC_BUILD_DEFS=-DTSC_UPD_STAMPS=1): shader-clock stamps of workgroup 0, waves 0 and 4 (the two
 wavefronts of one SIMD), in one step of dwxh_kernel (16 rows: sub-chunk 11, the last of its 64-row interval) and of dx1w1_kernel2
 (32 rows: chunk 5) -- step start, first MFMA, last MFMA, staging done, barrier passed -- printed as cycles per segment, each
@@ -122,7 +123,7 @@ def main():
         print('wall: %s update, epoch %d: %s ms (median %.3f)' % (args.algo, k, ' '.join('%.3f' % x for x in w), float(np.median(w))))
     if args.json:
         print(json.dumps(dict(algo=args.algo, envs=args.envs, agent=args.agent, scenario=args.scenario, n_step=T, wall_ms_per_epoch=wall,
-                              kernel_ms_per_update=kern)))
+                              kernel_ms_per_update=kern, dw_split=getattr(m, 'dw_split', None), dx_split=getattr(m, 'dx_split', None))))
 
 
 if __name__ == '__main__':
