@@ -48,6 +48,7 @@ SYMBOLS = ['tsc_last_error', 'tsc_version', 'tsc_profile_enable', 'tsc_profile_s
            'tsc_env_live_vehicles', 'tsc_env_vehicle_counts', 'tsc_env_set_block_order', 'tsc_env_counters', 'tsc_env_debug_clock', 'tsc_env_live_sum', 'tsc_env_record', 'tsc_env_read_record', 'tsc_env_read_trips', 'tsc_env_trace', 'tsc_env_read_trace', 'tsc_env_lane_data', 'tsc_env_read_lane_data', 'tsc_env_set_car_following', 'tsc_env_car_following',
            'tsc_model_create', 'tsc_model_destroy', 'tsc_model_set_stream', 'tsc_model_layout', 'tsc_model_path', 'tsc_model_plan', 'tsc_model_dw_split', 'tsc_model_dx_split',
            'tsc_model_set_params', 'tsc_model_reset_opt_state', 'tsc_model_debug_read', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state',
+           'tsc_model_set_sharing', 'tsc_model_get_sharing', 'tsc_model_share_grads',
            'tsc_model_reset', 'tsc_model_forward', 'tsc_model_forward_sample', 'tsc_model_sample', 'tsc_model_add_transition',
            'tsc_model_rollout_slot', 'tsc_model_compute_grads', 'tsc_model_grad_buffer', 'tsc_model_apply_grads', 'tsc_model_compute_grads_ppo', 'tsc_model_apply_grads_ex', 'tsc_model_ppo_stats', 'tsc_model_get_returns', 'tsc_model_debug_clock',
            'tsc_gemm_grouped_f32', 'tsc_dwxh_f32', 'tsc_dx1w1_f32',

@@ -28,6 +28,29 @@ A2C_DEFAULTS = dict(rmsp_alpha=0.99, rmsp_epsilon=1e-5, max_grad_norm=40.0, gamm
 PPO_DEFAULTS = dict(algo='a2c', ppo_epochs=4, ppo_clip=0.2, gae_lambda=0.95)
 
 
+# Opt-in parameter sharing (no reference counterpart; INTEGRATION.md "Parameter sharing"): `share_params = 1` ties the agents with equal
+# (n_wave, n_wait, n_fp, n_a) to one set of weights, trained on the mean of the members' gradients; 0, the default, is the reference's
+# one pair of towers per intersection.
+SHARE_DEFAULTS = dict(share_params=0)
+
+
+def check_share_config(cfg):
+    """Validate the [MODEL_CONFIG] key of SHARE_DEFAULTS in a coerced config; returns 0 or 1."""
+    v = cfg['share_params']
+    if not isinstance(v, int) or isinstance(v, bool) or v not in (0, 1):
+        raise ValueError('MODEL_CONFIG share_params = %r: expected 0 or 1' % (v,))
+    return int(v)
+
+
+def share_classes(n_wave_ls, n_w_ls, n_f_ls, n_a_ls):
+    """Parameter-sharing classes: agents with equal (n_wave, n_wait, n_fp, n_a) form one.  -> class id per agent, the id being the
+    class's lowest member index (an agent alone in its class gets its own index)."""
+    first, out = {}, []
+    for a, key in enumerate(zip(n_wave_ls, n_w_ls, n_f_ls, n_a_ls)):
+        out.append(first.setdefault(tuple(int(x) for x in key), a))
+    return out
+
+
 def check_algo_config(cfg):
     """Validate the [MODEL_CONFIG] keys of PPO_DEFAULTS in a coerced config; returns (algo, epochs, clip, lambda)."""
     algo = str(cfg['algo']).strip().lower()
@@ -264,6 +287,9 @@ def _setup_lib(L):
     for f in ('tsc_model_set_params', 'tsc_model_get_params', 'tsc_model_get_opt_state', 'tsc_model_set_opt_state'):
         getattr(L, f).argtypes = [vp, vp]
     L.tsc_model_reset_opt_state.argtypes = [vp]
+    L.tsc_model_set_sharing.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_model_get_sharing.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_model_share_grads.argtypes = [vp]
     L.tsc_model_debug_read.argtypes = [vp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, vp]
     L.tsc_model_reset.argtypes = [vp]
     L.tsc_model_forward.argtypes = [vp, vp, vp, vp, vp, C.c_int32]
@@ -293,8 +319,10 @@ class VecA2C:
                  total_step=0, device=0, seed=None, name='ma2c', process_group=None, policy='lstm', replica=0):
         if not torch.cuda.is_available():
             raise RuntimeError('VecA2C needs a GPU (MI355X); there is no CPU fallback')
-        cfg = coerce_config(model_config, {**A2C_DEFAULTS, **PPO_DEFAULTS})
+        cfg = coerce_config(model_config, {**A2C_DEFAULTS, **PPO_DEFAULTS, **SHARE_DEFAULTS})
         self.algo, self.ppo_epochs, self.ppo_clip, self.gae_lambda = check_algo_config(cfg)
+        share_params = check_share_config(cfg)
+        self.share = None                       # share_params = 1: the class id of every agent (share_classes), armed below
         self.n_epoch = self.ppo_epochs if self.algo == 'ppo' else 1       # updates per rollout
         self.cfg, self.name = cfg, name
         self.policy = policy                    # 'lstm' (what the reference instantiates) or 'fc' (FcACPolicy; MA2C: FPFcACPolicy)
@@ -369,6 +397,8 @@ class VecA2C:
         self.base_seed, self.replica = (0 if seed is None else int(seed)), int(replica)
         self.sample_seed = replica_sample_seed(self.base_seed, self.rank, replica)
         self.init_params(seed)
+        if share_params:                        # the lowest member's orthogonal draw becomes its class's
+            self.set_sharing(share_classes(self.n_wave_ls, self.n_w_ls, self.n_f_ls, self.n_a_ls))
         self.sync_replicas()
 
     # ---- parameters -----------------------------------------------------------------------
@@ -391,9 +421,39 @@ class VecA2C:
 
     def init_params(self, seed=None):
         rng = np.random.RandomState(seed) if seed is not None else np.random
-        self.set_tower_params(init_tower_params(self.n_wave_ls, self.n_w_ls, self.n_f_ls, self.n_a_ls, self.n_fc, self.Lh,
-                                                self.policy, rng))
+        towers = init_tower_params(self.n_wave_ls, self.n_w_ls, self.n_f_ls, self.n_a_ls, self.n_fc, self.Lh, self.policy, rng)
+        if self.share is not None:              # sharing armed: every member takes the draw of its class's lowest member
+            towers = [towers[2 * self.share[g // 2] + g % 2] for g in range(len(towers))]
+        self.set_tower_params(towers)
         _lib.check(self._L.tsc_model_reset_opt_state(self._h))      # TF1 RMSProp slot init: ms = 1
+
+    # ---- parameter sharing (include/tsc.h tsc_model_set_sharing) ----------------------------------
+    def set_sharing(self, class_of):
+        """Arm parameter sharing over the classes `class_of` (a class id in [0, A) per agent; None disarms): the lowest member's
+        parameters and RMSProp accumulator become its class's, and every later update applies the class-mean gradient."""
+        if class_of is None:
+            _lib.check(self._L.tsc_model_set_sharing(self._h, None))
+            self.share = None
+            return
+        ids = np.ascontiguousarray(class_of, np.int32)
+        assert ids.shape == (self.n_agent,), 'one class id per agent'
+        _lib.check(self._L.tsc_model_set_sharing(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.share = [int(x) for x in ids]
+
+    def get_sharing(self):
+        """The class ids the handle holds (every agent its own class when disarmed)."""
+        out = np.zeros(self.n_agent, np.int32)
+        _lib.check(self._L.tsc_model_get_sharing(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return [int(x) for x in out]
+
+    def share_sizes(self):
+        """Member counts of the parameter-sharing classes, largest first ([1] * n_agent when disarmed)."""
+        ids = self.share if self.share is not None else list(range(self.n_agent))
+        return sorted((ids.count(c) for c in set(ids)), reverse=True)
+
+    def share_grads(self):
+        """The class-mean reduce alone on the gradient buffer (parity hook; apply_grads runs it itself).  No-op when disarmed."""
+        _lib.check(self._L.tsc_model_share_grads(self._h))
 
     def sync_replicas(self, src=0):
         """Data-parallel replicas must start identical (only gradients are exchanged afterwards): broadcast the flat
@@ -604,7 +664,7 @@ class VecA2C:
                  ms=self.get_flat('ms'), layout=np.array(self.layout.as_tuple() + (self.s_max,), np.int64),
                  dims=np.array([self.n_wave_ls, self.n_w_ls, self.n_f_ls, self.n_a_ls], np.int64),
                  counters=np.array([self.sample_step, self.base_seed, self.lr_scheduler.n, self.beta_scheduler.n], np.int64),
-                 format=np.int64(CKPT_FORMAT))
+                 format=np.int64(CKPT_FORMAT), share=np.array(self.get_sharing(), np.int64))
 
     def load(self, model_dir, checkpoint=None):
         save_file, save_step = None, 0
@@ -630,6 +690,13 @@ class VecA2C:
                 ('dims' in z.files and not np.array_equal(z['dims'], dims)):
             raise ValueError('checkpoint %s does not fit this model (layout %r vs %r, %d vs %d parameters)'
                              % (save_file, tuple(int(x) for x in z['layout']), want, p.size, self.n_param))
+        if self.share is not None:              # a shared model takes a file whose class members agree, and no other
+            for what, flat in (('parameters', p), ('RMSProp accumulators', ms)):
+                rows = flat.reshape(self.n_agent, -1)
+                for a, c in enumerate(self.share):
+                    if rows[a].tobytes() != rows[c].tobytes():
+                        raise ValueError('checkpoint %s does not fit this model (share_params = 1: the %s of agents %d and %d, '
+                                         'members of one class, differ in the file)' % (save_file, what, c, a))
         _lib.check(self._L.tsc_model_set_params(self._h, p.ctypes.data_as(C.c_void_p)))
         _lib.check(self._L.tsc_model_set_opt_state(self._h, ms.ctypes.data_as(C.c_void_p)))
         if 'counters' in z.files:            # action-RNG stream and lr / beta schedules resume where they stopped; the checkpoint holds

@@ -40,6 +40,7 @@
 #include "../../include/tsc.h"
 
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -1808,6 +1809,26 @@ __global__ void grad_norm_fold_kernel(const double *part, int A, double *norm2) 
     norm2[a] = s;
 }
 
+// Parameter sharing (tsc_model_set_sharing): every member of a class takes the class mean of the members' gradient slices, in place.
+// Grid (ceil(per_agent / 4 / 256), classes with >= 2 members); a thread owns one 16-byte column of four floats: it loads the column
+// of every member (members[off[c] .. off[c + 1]), ascending agent indices), adds in float64 in that order, multiplies by the float64
+// inv_k[c] = 1 / k, rounds once to float32 and stores the result to every member.  It reads all of its inputs before it writes
+// any, and no other thread touches them: no atomics, no LDS, deterministic.  per_agent % 4 == 0 (checked when sharing is armed).
+__global__ void __launch_bounds__(256) share_reduce_kernel(float *__restrict__ grads, long long per_agent, const int *__restrict__ members,
+                                                           const int *__restrict__ off, const double *__restrict__ inv_k) {
+    const long long i = 4 * ((long long)blockIdx.x * 256 + threadIdx.x);
+    if (i >= per_agent) return;
+    const int c = blockIdx.y, lo = off[c], hi = off[c + 1];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int j = lo; j < hi; ++j) {
+        const float4 v = *(const float4 *)(grads + (long long)members[j] * per_agent + i);
+        s0 += (double)v.x; s1 += (double)v.y; s2 += (double)v.z; s3 += (double)v.w;
+    }
+    const double ik = inv_k[c];
+    const float4 r = make_float4((float)(s0 * ik), (float)(s1 * ik), (float)(s2 * ik), (float)(s3 * ik));
+    for (int j = lo; j < hi; ++j) *(float4 *)(grads + (long long)members[j] * per_agent + i) = r;
+}
+
 // TF1 RMSPropOptimizer (momentum 0, not centred): ms = a ms + (1-a) g^2 ; w -= lr g / sqrt(ms + eps)
 __global__ void rmsprop_kernel(float *w, float *ms, const float *grad, long long per_agent, long long total,
                                const double *norm2, float gscale, float clip, float lr, float alpha, float eps) {
@@ -3155,6 +3176,12 @@ struct tsc_model {
     int cached_next;            // next rollout slot whose activations the fused forward will cache; T = all cached
     long long *dbg;
     long long nparam;
+    // parameter sharing (tsc_model_set_sharing)
+    std::vector<int32_t> dims;          // [A][4] n_wave, n_wait, n_fp, n_act as given to create
+    std::vector<int32_t> share_class;   // [A] the caller's class ids; empty: disarmed
+    std::vector<std::vector<int>> share_lists;  // classes with >= 2 members, ascending agent indices
+    int *share_members, *share_off;     // device: the lists back to back, [n_lists + 1] offsets into them
+    double *share_invk;                 // device: [n_lists] 1 / members
 };
 
 namespace {
@@ -3185,6 +3212,29 @@ int dense_forward(tsc_model *m, const float *obs, long long rows, float *X1, flo
              nullptr, 0))
         return 1;
     return 0;
+}
+
+// Parameter sharing armed: a host buffer in the parameter layout must hold bit-identical slices for the members of a class.
+// Returns 0, or 1 with the first differing pair named (what = the calling function).
+int share_check_host(const tsc_model *m, const float *h, const char *what) {
+    const long long per_agent = 2 * m->lay.stride;
+    for (const std::vector<int> &cls : m->share_lists)
+        for (size_t j = 1; j < cls.size(); ++j) {
+            const float *p0 = h + cls[0] * per_agent, *p1 = h + cls[j] * per_agent;
+            if (memcmp(p0, p1, sizeof(float) * per_agent) == 0) continue;
+            long long i = 0;
+            while (memcmp(p0 + i, p1 + i, sizeof(float)) == 0) ++i;
+            return tsc::fail("%s: parameter sharing is armed and agents %d and %d of one class differ (first at offset %lld of the agent's "
+                             "slice: %.9g vs %.9g)", what, cls[0], cls[j], i, (double)p0[i], (double)p1[i]);
+        }
+    return 0;
+}
+
+void launch_share_reduce(tsc_model *m) {
+    if (m->share_lists.empty()) return;
+    const long long per_agent = 2 * m->lay.stride;
+    hipLaunchKernelGGL(share_reduce_kernel, dim3((unsigned)((per_agent / 4 + 255) / 256), (unsigned)m->share_lists.size()), dim3(256), 0,
+                       m->stream, m->grads, per_agent, m->share_members, m->share_off, m->share_invk);
 }
 
 }  // namespace
@@ -3253,6 +3303,12 @@ int tsc_model_create(const tsc_model_cfg *cfg, int32_t n_env, int32_t device, ts
         TSC_HIP(m->bufs.upload(&m->ftmask, fm.data(), fm.size()));
     }
     TSC_HIP(m->bufs.upload(&m->n_act, cfg->n_act, L.A));
+    m->dims.resize((size_t)L.A * 4);
+    for (int a = 0; a < L.A; ++a) {
+        const int32_t d[4] = {cfg->n_wave[a], cfg->n_wait[a], cfg->n_fp[a], cfg->n_act[a]};
+        for (int k = 0; k < 4; ++k) m->dims[(size_t)a * 4 + k] = d[k];
+    }
+    m->share_members = m->share_off = nullptr; m->share_invk = nullptr;
     const long long E = n_env, T = m->T, N = E * T, G = L.G, A = L.A;
     TSC_HIP(m->bufs.alloc(&m->params, m->nparam, true)); TSC_HIP(m->bufs.alloc(&m->grads, m->nparam, true)); TSC_HIP(m->bufs.alloc(&m->ms, m->nparam, true));
     TSC_HIP(m->bufs.alloc(&m->WxT, G * L.H * kG4, true));
@@ -3370,6 +3426,7 @@ int tsc_model_layout(tsc_model *m, int64_t out[12]) {
 
 int tsc_model_set_params(tsc_model *m, const float *h) {
     if (!m || !h) return tsc::fail("tsc_model_set_params: bad arguments");
+    if (share_check_host(m, h, "tsc_model_set_params")) return 1;
     m->cached_next = -1;                              // activations cached under the old parameters are stale
     m->ppo_ready = 0;                                 // ... and so is logp_old: a PPO epoch > 0 needs a new epoch 0
     m->wg_dirty = 1;
@@ -3398,8 +3455,87 @@ int tsc_model_get_opt_state(tsc_model *m, float *h) {
 }
 int tsc_model_set_opt_state(tsc_model *m, const float *h) {
     if (!m || !h) return tsc::fail("tsc_model_set_opt_state: bad arguments");
+    if (share_check_host(m, h, "tsc_model_set_opt_state")) return 1;
     TSC_HIP(hipStreamSynchronize(m->stream));
     TSC_HIP(hipMemcpy(m->ms, h, sizeof(float) * m->nparam, hipMemcpyHostToDevice));
+    return 0;
+}
+
+int tsc_model_set_sharing(tsc_model *m, const int32_t *class_of) {
+    if (!m) return tsc::fail("null handle");
+    const Layout &L = m->lay;
+    const auto drop = [m]() {
+        m->bufs.release(m->share_members); m->bufs.release(m->share_off); m->bufs.release(m->share_invk);
+        m->share_members = m->share_off = nullptr; m->share_invk = nullptr;
+        m->share_class.clear(); m->share_lists.clear();
+    };
+    if (!class_of) {                                  // disarm: parameters and accumulators stay as they are
+        TSC_HIP(hipStreamSynchronize(m->stream));
+        drop();
+        return 0;
+    }
+    const long long per_agent = 2 * L.stride;
+    if (per_agent % 4) return tsc::fail("tsc_model_set_sharing: an agent's slice of %lld floats is not a multiple of 4", per_agent);
+    std::string bad;
+    for (int a = 0; a < L.A; ++a)
+        if (class_of[a] < 0 || class_of[a] >= L.A) bad += (bad.empty() ? "" : ", ") + std::to_string(a) + " (id " + std::to_string(class_of[a]) + ")";
+    if (!bad.empty()) return tsc::fail("tsc_model_set_sharing: class id outside [0, %d) for agent(s) %s", L.A, bad.c_str());
+    std::vector<std::vector<int>> by_id(L.A);
+    for (int a = 0; a < L.A; ++a) by_id[class_of[a]].push_back(a);          // ascending agent indices
+    std::vector<std::vector<int>> lists;
+    for (const std::vector<int> &cls : by_id) {
+        for (size_t j = 1; j < cls.size(); ++j) {
+            const int32_t *d0 = &m->dims[(size_t)cls[0] * 4], *d1 = &m->dims[(size_t)cls[j] * 4];
+            if (memcmp(d0, d1, sizeof(int32_t) * 4))
+                return tsc::fail("tsc_model_set_sharing: agents %d and %d of class %d have unequal (n_wave, n_wait, n_fp, n_act): "
+                                 "(%d, %d, %d, %d) vs (%d, %d, %d, %d)", cls[0], cls[j], class_of[cls[0]], d0[0], d0[1], d0[2], d0[3],
+                                 d1[0], d1[1], d1[2], d1[3]);
+        }
+        if (cls.size() >= 2) lists.push_back(cls);
+    }
+    if (lists.size() > 65535) return tsc::fail("tsc_model_set_sharing: %zu classes of two or more agents, at most 65535", lists.size());
+    std::vector<int> members, off(1, 0);
+    std::vector<double> invk;
+    for (const std::vector<int> &cls : lists) {
+        members.insert(members.end(), cls.begin(), cls.end());
+        off.push_back((int)members.size());
+        invk.push_back(1.0 / (double)cls.size());
+    }
+    TSC_HIP(hipStreamSynchronize(m->stream));
+    int *d_members = nullptr, *d_off = nullptr;
+    double *d_invk = nullptr;
+    hipError_t e = m->bufs.upload(&d_members, members.data(), members.size());
+    if (e == hipSuccess) e = m->bufs.upload(&d_off, off.data(), off.size());
+    if (e == hipSuccess) e = m->bufs.upload(&d_invk, invk.data(), invk.size());
+    // the lowest member's parameters and accumulator become the class's
+    for (const std::vector<int> &cls : lists)
+        for (size_t j = 1; j < cls.size() && e == hipSuccess; ++j)
+            for (float *buf : {m->params, m->ms})
+                if (e == hipSuccess)
+                    e = hipMemcpy(buf + cls[j] * per_agent, buf + cls[0] * per_agent, sizeof(float) * per_agent, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);       // the copies ran on the null stream: done before the handle's stream goes on
+    if (e != hipSuccess) {
+        m->bufs.release(d_members); m->bufs.release(d_off); m->bufs.release(d_invk);
+        TSC_HIP(e);
+    }
+    drop();
+    m->share_members = d_members; m->share_off = d_off; m->share_invk = d_invk;
+    m->share_class.assign(class_of, class_of + L.A);
+    m->share_lists = std::move(lists);
+    m->cached_next = -1; m->ppo_ready = 0; m->wg_dirty = 1;       // as tsc_model_set_params: the parameters changed
+    return 0;
+}
+
+int tsc_model_get_sharing(tsc_model *m, int32_t *class_of) {
+    if (!m || !class_of) return tsc::fail("tsc_model_get_sharing: bad arguments");
+    for (int a = 0; a < m->lay.A; ++a) class_of[a] = m->share_class.empty() ? a : m->share_class[a];
+    return 0;
+}
+
+int tsc_model_share_grads(tsc_model *m) {
+    if (!m) return tsc::fail("null handle");
+    launch_share_reduce(m);
+    TSC_HIP(hipGetLastError());
     return 0;
 }
 
@@ -3828,6 +3964,7 @@ int tsc_model_apply_grads_ex(tsc_model *m, double lr, double grad_scale, double 
     const long long per_agent = 2 * L.stride;
     hipStream_t st = m->stream;
     tsc::ProfScope ps10(tsc::KID_GRADNORM, m->stream);
+    launch_share_reduce(m);                       // parameter sharing armed: class members take the class-mean gradient first
     hipLaunchKernelGGL(grad_norm_kernel, dim3(L.A, kNormParts), dim3(256), 0, st, m->grads, per_agent, grad_scale, m->norm_part);
     hipLaunchKernelGGL(grad_norm_fold_kernel, dim3((L.A + 63) / 64), dim3(64), 0, st, m->norm_part, L.A, m->norm2);
     ps10.stop();

@@ -264,6 +264,10 @@ def train(args):
         logging.info('Training: dueling head, Q = V + A - mean(A)')
     if getattr(model, 'return_steps', 1) > 1:
         logging.info('Training: %d-step returns' % model.return_steps)
+    if getattr(model, 'share', None) is not None:
+        sizes = model.share_sizes()
+        logging.info('Training: parameter sharing, %d agents in %d classes of %s members'
+                     % (model.n_agent, len(sizes), ' + '.join(str(n) for n in sizes)))
     trainer = VecTrainer(env, model, counter, log_rewards=True)
     data = trainer.run_training(run_test=in_test, output_path=dirs['data'])
     if post_test:                                               # Tester.run_offline (utils.py:324-338)

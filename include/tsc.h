@@ -102,7 +102,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 122: tsc_model_dx_split / tsc_dx1w1_f32; 121: tsc_model_dw_split / tsc_dwxh_f32; 120: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 123: tsc_model_set_sharing / tsc_model_get_sharing / tsc_model_share_grads; 122: tsc_model_dx_split / tsc_dx1w1_f32; 121: tsc_model_dw_split / tsc_dwxh_f32; 120: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -399,6 +399,24 @@ int tsc_model_reset_opt_state(tsc_model *m);                         /* RMSProp 
 int tsc_model_get_params(tsc_model *m, float *params_host);
 int tsc_model_get_opt_state(tsc_model *m, float *ms_host);
 int tsc_model_set_opt_state(tsc_model *m, const float *ms_host);
+
+/* Parameter sharing across like-shaped agents (opt-in; no reference counterpart; INTEGRATION.md "Parameter sharing").  class_of_host
+ * [A]: class ids in [0, A); agents with the same id form a class and must have equal (n_wave, n_wait, n_fp, n_act), so that their
+ * towers have the same layout inside `stride`.  Refused (tsc_last_error names the agents, nothing changes): an id out of range, two
+ * agents of one class with unequal dims.  On arming, the lowest-index member's parameters and RMSProp accumulator are copied to the
+ * other members (device to device), with the side effects of tsc_model_set_params.  From then on tsc_model_apply_grads(_ex) first
+ * replaces every member's gradient slice [a * 2 stride, (a + 1) * 2 stride) by the class mean (share_reduce_kernel: float64 sums in
+ * ascending member order, times the float64 1 / k, one rounding to float32) and then runs the unchanged update: the members see the
+ * same gradient, norm, parameters and accumulator and stay bit-identical; stats[:, 3] is the class's norm for every member.  Classes
+ * of one agent are never read or written.  While armed, tsc_model_set_params / tsc_model_set_opt_state refuse a host buffer in which
+ * two members of a class differ (the first differing pair is named).  class_of_host = null disarms and leaves the parameters as they
+ * are.  Synchronises.  (tsc_version 123) */
+int tsc_model_set_sharing(tsc_model *m, const int32_t *class_of_host);
+/* The class ids tsc_model_set_sharing was given; a disarmed handle reports every agent in its own class (class_of_host[a] = a). */
+int tsc_model_get_sharing(tsc_model *m, int32_t *class_of_host);
+/* Parity hook: the class-mean reduce alone, on the gradient buffer (tsc_model_grad_buffer), on the handle's stream.  A no-op when
+ * disarmed. */
+int tsc_model_share_grads(tsc_model *m);
 
 /* IA2C.reset (agents/models.py:218-220): zero the forward and backward LSTM states. */
 int tsc_model_reset(tsc_model *m);

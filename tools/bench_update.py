@@ -1,11 +1,12 @@
 #!/usr/bin/env python
 """Time the A2C update's kernels alone (no simulator): fill one rollout of the benchmark shape through the fused forward
 (random observations, E env instances, T = n_step), then run compute_grads `--reps` times with HIP-event timing on.
-    python tools/bench_update.py [--envs 1024] [--agent ma2c] [--policy lstm] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]]
+    python tools/bench_update.py [--envs 1024] [--agent ma2c] [--policy lstm] [--reps 3] [--algo ppo [--ppo-epochs 2] [--json]] [--share-params]
 --algo ppo times `--ppo-epochs` epochs per rollout and also prints the wall time (stream-synchronised, profiling off) of an epoch-0
 update and of a later epoch (re-forward + update); --algo a2c prints the wall time of its one update the same way.
 Environment knobs of the library (TSC_DW_SPLIT, TSC_DX_SPLIT, TSC_UNFUSED_DW, TSC_UNFUSED_DX) select kernel variants
-for A/B runs; --json reports the choice (dw_split, dx_split).  The dwxh stamps are dwxh_kernel's (TSC_DW_SPLIT=0): dwxh_split_kernel carries
+for A/B runs; --json reports the choice (dw_split, dx_split).  --share-params arms parameter sharing ([MODEL_CONFIG] share_params = 1): the class-mean
+reduce runs inside the grad_norm scope, so that line's difference to an unarmed run is its cost.  The dwxh stamps are dwxh_kernel's (TSC_DW_SPLIT=0): dwxh_split_kernel carries
 none; the dx1w1 stamps are taken by whichever of dx1w1_split_kernel / dx1w1_kernel2 runs.
 --stamps (a library built with TSC_BUILD_DEFS=-DTSC_UPD_STAMPS=1): shader-clock stamps of workgroup 0, waves 0 and 4 (the two
 wavefronts of one SIMD), in one step of dwxh_kernel (16 rows: sub-chunk 11, the last of its 64-row interval) and of dx1w1_kernel2
@@ -31,6 +32,7 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--algo', default='a2c', choices=['a2c', 'ppo'])
     ap.add_argument('--ppo-epochs', type=int, default=2)
+    ap.add_argument('--share-params', action='store_true', help='[MODEL_CONFIG] share_params = 1: agents of equal shape share one set of weights')
     ap.add_argument('--stamps', action='store_true', help='per-step cycle split of dwxh / dx1w1 (needs a -DTSC_UPD_STAMPS=1 build)')
     ap.add_argument('--json', action='store_true', help='one JSON line with the wall times (ms) of the updates, per epoch index, and the kernel times at full precision')
     args = ap.parse_args()
@@ -40,7 +42,8 @@ def main():
     scn = build_scenario(args.scenario, args.agent)
     T = 120 if args.scenario == 'large_grid' else 40
     m = VecA2C(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, scn.n_f_ls, args.envs, scn.s_max, int(scn.green_tab.shape[1]),
-               dict(batch_size=T, **(dict(algo='ppo', ppo_epochs=args.ppo_epochs) if args.algo == 'ppo' else {})), device=0, seed=0,
+               dict(batch_size=T, **(dict(algo='ppo', ppo_epochs=args.ppo_epochs) if args.algo == 'ppo' else {}),
+                    **(dict(share_params=1) if args.share_params else {})), device=0, seed=0,
                name=args.agent, policy=args.policy)
     sl = m.rollout_slots()
     g = torch.Generator(device='cuda'); g.manual_seed(0)
@@ -123,7 +126,8 @@ def main():
         print('wall: %s update, epoch %d: %s ms (median %.3f)' % (args.algo, k, ' '.join('%.3f' % x for x in w), float(np.median(w))))
     if args.json:
         print(json.dumps(dict(algo=args.algo, envs=args.envs, agent=args.agent, scenario=args.scenario, n_step=T, wall_ms_per_epoch=wall,
-                              kernel_ms_per_update=kern, dw_split=getattr(m, 'dw_split', None), dx_split=getattr(m, 'dx_split', None))))
+                              kernel_ms_per_update=kern, dw_split=getattr(m, 'dw_split', None), dx_split=getattr(m, 'dx_split', None),
+                              share_sizes=m.share_sizes() if getattr(m, 'share', None) is not None else None)))
 
 
 if __name__ == '__main__':

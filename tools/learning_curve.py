@@ -24,7 +24,7 @@ import torch                # noqa: E402
 
 
 def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, log=None, policy='lstm', scn_kw=None, test_seeds=None,
-        algo='a2c', ppo_epochs=None, ppo_clip=None, gae_lambda=None, q_kw=None):
+        algo='a2c', ppo_epochs=None, ppo_clip=None, gae_lambda=None, q_kw=None, share_params=0):
     from deeprl_signal_control_amd.agents import VecA2C
     from deeprl_signal_control_amd.env import VecTrafficEnv
     from deeprl_signal_control_amd.scenario import build_scenario
@@ -38,6 +38,8 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
         mcfg['lr_init'] = lr
     # the update rule ([MODEL_CONFIG] algo and its keys; unset ones keep agents.PPO_DEFAULTS)
     mcfg.update({k: v for k, v in dict(algo=algo, ppo_epochs=ppo_epochs, ppo_clip=ppo_clip, gae_lambda=gae_lambda).items() if v is not None})
+    if share_params:                    # [MODEL_CONFIG] share_params = 1: one set of weights per class of like-shaped agents (A2C agents)
+        mcfg['share_params'] = 1
     env = VecTrafficEnv(scn, n_env, device=0, seed=seed0, **({'test_seeds': tuple(test_seeds)} if test_seeds else {}))
     is_q = agent in ('iqld', 'iqll')
     if is_q:
@@ -97,7 +99,8 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
     run.algo_in_force = dict({k: model.cfg[k] for k in ('prioritized_replay', 'per_alpha', 'per_beta', 'per_eps')} if model.prioritized_replay else {},
                              **({'dueling': model.dueling} if model.dueling else {}),
                              **({'return_steps': model.return_steps} if model.return_steps > 1 else {}),
-                             **({'target_update': model.target_update, 'double_q': model.double_q} if model.target_update else {})) if is_q else dict(algo=model.algo, ppo_epochs=model.n_epoch, ppo_clip=model.ppo_clip, gae_lambda=model.gae_lambda)
+                             **({'target_update': model.target_update, 'double_q': model.double_q} if model.target_update else {})) if is_q else dict(algo=model.algo, ppo_epochs=model.n_epoch, ppo_clip=model.ppo_clip, gae_lambda=model.gae_lambda,
+        **({'share_params': 1, 'share_sizes': model.share_sizes()} if model.share is not None else {}))
     env.close(); model.close()
     return rows, ev
 
@@ -116,6 +119,7 @@ def main():
     ap.add_argument('--ppo-epochs', type=int, default=None, help='algo ppo: epochs per rollout (default 4)')
     ap.add_argument('--ppo-clip', type=float, default=None, help='algo ppo: clip range of the probability ratio (default 0.2)')
     ap.add_argument('--gae-lambda', type=float, default=None, help='algo ppo: GAE lambda (default 0.95)')
+    ap.add_argument('--share-params', action='store_true', help='the A2C agents: [MODEL_CONFIG] share_params = 1 (agents of equal shape share one set of weights)')
     ap.add_argument('--objective', default=None, choices=['queue', 'wait', 'hybrid', 'pressure'],
                     help='[ENV_CONFIG] objective of the scenario (default: the scenario\'s own); pressure = the pressure reward, whose '
                          'levels are not comparable with the others\'')
@@ -136,7 +140,7 @@ def main():
                                    double_q=1 if args.double_q else None, return_steps=args.return_steps).items() if v is not None}
     rows, ev = run(args.episodes, args.envs, args.scenario, args.agent, lr=args.lr, log=print, policy=args.policy, scn_kw=kw,
                    test_seeds=[int(x) for x in args.test_seeds.split(',')] if args.test_seeds else None,
-                   algo=args.algo, ppo_epochs=args.ppo_epochs, ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, q_kw=q_kw)
+                   algo=args.algo, ppo_epochs=args.ppo_epochs, ppo_clip=args.ppo_clip, gae_lambda=args.gae_lambda, q_kw=q_kw, share_params=int(args.share_params))
     first, last = np.mean([r['avg_reward'] for r in rows[:5]]), np.mean([r['avg_reward'] for r in rows[-5:]])
     out = dict(scenario=args.scenario, agent=args.agent, policy=args.policy, **run.algo_in_force, envs=args.envs, episodes=args.episodes, scenario_options=kw,
                control_steps_per_episode=rows[0]['step'], first5_mean=first, last5_mean=last, rows=rows, evaluation=ev,
