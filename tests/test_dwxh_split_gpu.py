@@ -14,13 +14,28 @@ half of the rows cancelling in pairs (row n + N / 4 repeats row n with the oppos
 Bound (the project's, for BOTH kernels): |out - ref64| <= 2e-5 * max|ref64| per tensor (dWx, dWh, dbl).  Outputs of all-zero columns
 are exactly zero.  dbl: the split kernel adds a lane's dZ rows in the order 8h + j where dwxh_kernel adds 2 ks + h, so dbl is NOT
 bit-equal between the two and is held to the same bound.  One Inf in dZ leaves every output of its gate column non-finite.
-No tighter split-versus-f32 threshold is asserted: the figures are printed (max and mean of |err| / max|ref64| of both kernels and
-their ratio) and recorded in profiles/dwxh_split_bench.json under `accuracy`."""
+That bound alone cannot see the loss of one third-order piece product (2^-16 of a term; tests/test_split_mutants_host.py shows every
+such mutant of the host restatement meeting it).  Two things pin the six-product arithmetic:
+  * test_exact_probes_come_back_bit_for_bit: inputs whose six piece products sum exactly in any order, one product per output entry,
+    both kernels np.array_equal to one expected array (tests/split_harness.py; the host test counts what the ownership maps own);
+  * in test_both_kernels_match_float64 the split kernel's max error is held to a multiple of the f32 kernel's on the same case, per
+    tensor: split_harness.RATIO, each threshold the geometric mean of the real kernels' largest ratio (measured here over all widths
+    and sizes) and the weakest restated mutant's, with a factor 2 on each side.  dWx, dWh on kinds a and d (thresholds 7.3 .. 10.3;
+    real kernels <= 2.27, mutants >= 31) and dWx on kind c (3.46; 1.69 / 7.1).  Not adopted, the gap being under 4: dWh on kind c
+    (1.78 / 6.5) and the mean on kind c for both tensors (1.37 / 5.0) -- every cut of this kernel rounds to nearest, so on all-positive
+    input a lost product is no bias.  Kind b has no ratio criterion (the f32 kernel is at times unusually good on heavy tails) and
+    stays under the 2e-5 bound; dbl holds no piece product.  The figures are printed and recorded in profiles/dwxh_split_bench.json
+    under `accuracy`.
+test_split_path_equals_exact_f32_path keeps the bound 2e-5 max|g|: normalised per tower by the largest entry of Wx | Wh | bl the real
+paths differ by up to 4.6e-7 (large_grid) and 1.3e-6 (real_net), and the weakest mutant restated on the rows the update read (towers
+0, 1, 6, 7) by 1.5e-6 and 1.6e-6 -- gaps of 3.2 and 1.2, no room for a threshold at these small batches."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
+
+from tests import split_harness as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -100,11 +115,35 @@ def test_both_kernels_match_float64(H, N):
             assert np.isfinite(outs[split]).all()
             for (mx, _), name in zip(errs[split], ('dWx', 'dWh', 'dbl')):
                 assert mx <= BOUND, (H, N, kind, name, 'split' if split else 'f32', mx)
+        named = [dict(zip(('dWx', 'dWh', 'dbl'), errs[split])) for split in (1, 0)]
+        assert kind == 'b' or sh.accuracy_criteria('dwxh', kind)
+        assert not sh.accuracy_failures('dwxh', kind, *named), (H, N, kind, sh.accuracy_failures('dwxh', kind, *named))
         if kind == 'd':
             for split in (1, 0):
                 o = outs[split]
                 assert (o[:, 0:H:7] == 0).all() and (o[:, H + 5] == 0).all() and (o[:, :, 3::11] == 0).all(), (H, N, split)
                 assert (ref[:, 0:H:7] == 0).all() and (ref[:, :, 3::11] == 0).all()
+
+
+@pytest.mark.parametrize('N', SIZES)
+@pytest.mark.parametrize('H', WIDTHS)
+def test_exact_probes_come_back_bit_for_bit(H, N):
+    """tests/split_harness.dwxh_probe: every entry of dWx | dWh is ONE product whose six piece products sum exactly, in any order, to the
+    f32 product -- the expected array is the same for both kernels and np.array_equal is the assertion.  Features nobody owns are
+    exactly zero.  dbl is a plain f32 row sum of dZ, not exact under this construction: it keeps the bound."""
+    for q0, boundary, seed in sh.probe_calls('dwxh', H, N):
+        X1, Hp, dZ, exp, owner = sh.dwxh_probe(H, N, G, S, q0, boundary, seed)
+        assert (owner < 0).any() and (exp[owner >= 0] != 0).all()
+        dev = _device([X1, Hp, dZ])
+        dbl = dZ.astype(np.float64).sum(1)
+        for split in (1, 0):
+            o = _run(H, N, *dev, split)
+            bad = np.argwhere(o[:, :H + L] != exp)
+            assert len(bad) == 0, (H, N, q0, boundary, 'split' if split else 'f32', len(bad), bad[0], owner[bad[0][0], bad[0][1]],
+                                   float(o[tuple(bad[0])]), float(exp[tuple(bad[0])]))
+            assert np.array_equal(o[:, :H + L], exp)
+            assert (o[:, :H + L][owner < 0] == 0).all()
+            assert np.abs(o[:, H + L] - dbl).max() <= BOUND * np.abs(dbl).max(), (H, N, q0, split)
 
 
 @pytest.mark.parametrize('H', WIDTHS)

@@ -7,7 +7,10 @@
   * Schedule.  Ring of four sub-chunks, a barrier every two: each sub-chunk's MFMAs read the slot that holds exactly its rows, no slot
     is written between the barriers around a read of it, unclamped loads stay inside the split, every row is consumed once.
   * Split.  p1 = bf16(x), p2 = bf16(x - p1), p3 = bf16((x - p1) - p2), round to nearest even: p1 + p2 + p3 == x exactly.
-It also counts what the shapes of tests/test_dwxh_split_gpu.py drive."""
+It also counts what the shapes of tests/test_dwxh_split_gpu.py drive.
+What is NOT pinned here is which piece products reach the accumulator: tests/split_harness.py restates that (the six products, mutants
+that lose or misplace one), tests/test_split_mutants_host.py holds the mutant table, and the exact probes of the GPU test pin it bit
+for bit on the kernel."""
 import numpy as np
 import torch
 

@@ -19,13 +19,30 @@ first half of the rows cancelling in pairs (row n + N / 4 repeats row n with the
 Bound (the project's, for BOTH kernels): |out - ref64| <= 2e-5 * max|ref64| per tensor (dW1, db1).  Entries outside the block structure,
 feature tiles without a structural non-zero and all-zero columns are exactly zero.  One Inf and one NaN in dZ of tower 1, in rows whose X1
 is positive throughout, leave every db1 entry and every dW1 entry inside the structure of that tower non-finite, and tower 0 finite.
-No tighter split-versus-f32 threshold is asserted: the figures are printed (max and mean of |err| / max|ref64| of both kernels and their
-ratio) and recorded in profiles/dx1w1_split_bench.json under `accuracy`."""
+That bound alone cannot see the loss of one third-order piece product (2^-16 of a term; tests/test_split_mutants_host.py shows every
+such mutant of the host restatement meeting it in at least 19 of 20 cases).  Two things pin the six-product arithmetic:
+  * test_exact_probes_come_back_bit_for_bit: inputs whose six piece products sum exactly in any order, one product per output entry,
+    both kernels np.array_equal to one expected array (tests/split_harness.py; the host test counts what the ownership maps own);
+  * in test_both_kernels_match_float64 the split kernel's error is held to a multiple of the f32 kernel's on the same case, per tensor:
+    split_harness.RATIO (max) and MEAN_C (mean, all-positive kind c), each threshold the geometric mean of the real kernels' largest
+    ratio (measured here over all widths and sizes) and the weakest restated mutant's, with a factor 2 on each side.  Max on kinds a
+    and d for dW1 and db1 (thresholds 3.45 .. 3.77; real kernels <= 1.63, mutants >= 8.7).  Mean on kind c (13.4 / 14.3; real kernels
+    <= 1.08, mutants >= 174): it claims only the mutants that lose a product of Wx's third piece, the operand dx_cut8 TRUNCATES, whose
+    remainders all have one sign.  Not adopted: the max on kind c and the mean on kind c over all third-order mutants (gap 0.2 / 0.3)
+    -- dZ is rounded to nearest, so a lost a3 product is no bias there and lies below the f32 kernel's own error.  Kind b has no ratio
+    criterion: the f32 kernel is at times unusually good on heavy tails (37 x on one case, `finding` of the profile) and b stays under
+    the 2e-5 bound only.  The figures are printed and recorded in profiles/dx1w1_split_bench.json under `accuracy`.
+test_split_path_differs_from_the_exact_path_only_in_w1_b1 keeps the bound 2e-5 max|g|: normalised per tower by the largest entry of
+W1 | b1 the real paths differ by up to 3.8e-7 (large_grid) and 6.5e-7 (real_net), and the weakest mutant restated on the rows the
+update read (dZ and X1 from the activation cache, Wx from the parameters, the obs fed in; towers 0, 1, 6, 7) by 1.2e-6 and 1.6e-6 --
+gaps of 3.1 and 2.5, no room for a threshold at these small batches."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
+
+from tests import split_harness as sh
 
 pytestmark = pytest.mark.gpu
 
@@ -129,8 +146,30 @@ def test_both_kernels_match_float64(H, N):
             assert (o[:, :SMAX][:, ~mask] == 0).all(), (H, N, kind, split)          # outside the structure, empty feature tiles
             if kind == 'd':
                 assert (o[:, :, ::7] == 0).all() and (o[:, :, 5] == 0).all(), (H, N, split)
+        named = [dict(zip(('dW1', 'db1'), errs[split])) for split in (1, 0)]
+        assert kind == 'b' or sh.accuracy_criteria('dx1w1', kind)
+        assert not sh.accuracy_failures('dx1w1', kind, *named), (H, N, kind, sh.accuracy_failures('dx1w1', kind, *named))
         if kind == 'd':
             assert (ref[:, :, ::7] == 0).all() and (ref[:, :, 5] == 0).all()
+
+
+@pytest.mark.parametrize('N', SIZES)
+@pytest.mark.parametrize('H', WIDTHS)
+def test_exact_probes_come_back_bit_for_bit(H, N):
+    """tests/split_harness.dx1w1_probe: every column of dX1 has ONE row that passes the relu mask, and that entry is ONE product whose
+    six piece products sum exactly, in any order, to the f32 product; obs entries are powers of two.  db1 and every dW1 entry are
+    single exact values, the same for both kernels: np.array_equal is the assertion, zeros outside the structure included."""
+    rr, ftm, mask = _structure(H)
+    for q0, boundary, seed in sh.probe_calls('dx1w1', H, N):
+        dZ, X1, Wx, obs, exp, owner, ks = sh.dx1w1_probe(H, N, G, S, q0, boundary, seed)
+        assert (exp[:, SMAX] != 0).all() and (exp[:, :SMAX][:, mask] != 0).all() and (exp[:, :SMAX][:, ~mask] == 0).all()
+        dev = _device([dZ, X1, Wx, obs, ftm, rr])
+        for split in (1, 0):
+            o = _run(H, N, dev, split)
+            bad = np.argwhere(o != exp)
+            assert len(bad) == 0, (H, N, q0, boundary, 'split' if split else 'f32', len(bad), bad[0], owner[bad[0][0], bad[0][2]],
+                                   ks[bad[0][0], bad[0][2]], float(o[tuple(bad[0])]), float(exp[tuple(bad[0])]))
+            assert np.array_equal(o, exp)
 
 
 @pytest.mark.parametrize('H', WIDTHS)

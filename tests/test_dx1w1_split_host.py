@@ -9,7 +9,10 @@ dZ chunk with the permuted contraction index, and the chunk loop.  No GPU.
     tile a plane exactly once; the fragment lane (n, kq) reads with ONE 16-byte read at 16 lane + a constant holds, in element order,
     exactly the k of the weight registers bw[8 s + e] = Wx^T[16 (2 s + (e >> 2)) + 4 kq + (e & 3)] that form its B fragment; each of
     the four 16-lane groups of a ds_read_b128 touches 64 distinct banks, and a wave's ds_write_b64 puts four lanes on every bank.
-  * Loop.  Chunks of 32 rows, unclamped while the successor is whole; it also counts what the shapes of tests/test_dx1w1_split_gpu.py drive."""
+  * Loop.  Chunks of 32 rows, unclamped while the successor is whole; it also counts what the shapes of tests/test_dx1w1_split_gpu.py drive.
+What is NOT pinned here is which piece products reach the accumulator: tests/split_harness.py restates that (this cut for Wx, the
+rounding cut for dZ, the six products, mutants that lose or misplace one), tests/test_split_mutants_host.py holds the mutant table, and
+the exact probes of the GPU test pin it bit for bit on the kernel."""
 import numpy as np
 
 PL = 2 * 8 * 4 * 16 * 16
