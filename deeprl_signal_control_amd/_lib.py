@@ -58,7 +58,8 @@ SYMBOLS = ['tsc_last_error', 'tsc_version', 'tsc_profile_enable', 'tsc_profile_s
            'tsc_iql_set_target', 'tsc_iql_sync_target', 'tsc_iql_set_target_params', 'tsc_iql_get_target_params', 'tsc_iql_debug_targets',
            'tsc_iql_set_per', 'tsc_iql_set_per_beta', 'tsc_iql_get_priorities', 'tsc_iql_set_priorities', 'tsc_iql_debug_per',
            'tsc_iql_set_dueling', 'tsc_iql_get_dueling',
-           'tsc_iql_set_return_steps', 'tsc_iql_get_return_steps', 'tsc_iql_debug_nstep']
+           'tsc_iql_set_return_steps', 'tsc_iql_get_return_steps', 'tsc_iql_debug_nstep',
+           'tsc_iql_set_sharing', 'tsc_iql_get_sharing', 'tsc_iql_share_grads']
 
 
 def lib():

@@ -2077,7 +2077,7 @@ const char *tsc_profile_name(int32_t id) {
     return (id >= 0 && id < tsc::KID_COUNT) ? names[id] : "";
 }
 
-int tsc_version(void) { return 123; }      // 1.21: tsc_model_dw_split / tsc_dwxh_f32; 1.20: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 1.19: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 1.18: tsc_model_plan; 1.17: tsc_iql_set_dueling / tsc_iql_get_dueling; 1.16: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 1.15: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 1.14: tsc_env_set_reward_pressure; 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
+int tsc_version(void) { return 124; }      // 1.24: tsc_iql_set_sharing / tsc_iql_get_sharing / tsc_iql_share_grads; 1.23: tsc_model_set_sharing / tsc_model_get_sharing / tsc_model_share_grads; 1.22: tsc_model_dx_split / tsc_dx1w1_f32; 1.21: tsc_model_dw_split / tsc_dwxh_f32; 1.20: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 1.19: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 1.18: tsc_model_plan; 1.17: tsc_iql_set_dueling / tsc_iql_get_dueling; 1.16: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 1.15: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 1.14: tsc_env_set_reward_pressure; 1.13: tsc_env_step_plan; 1.12: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 1.11: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 1.10: tsc_env_set_demand / tsc_env_demand; 1.09: tsc_env_lane_data / tsc_env_read_lane_data; 1.08: tsc_env_trace / tsc_env_read_trace; 1.07: tsc_env_set_car_following / tsc_env_car_following; 1.06: tsc_model_path; 1.05: round 5 (tsc_env_set_greedy / tsc_env_greedy_actions); 1.04: tsc_env_counters, negative arrival = truncated trip
 
 int tsc_env_create(const tsc_scenario *sc, int32_t n_env, int32_t device, tsc_env **out) {
     if (!sc || !out || n_env <= 0) return tsc::fail("tsc_env_create: bad arguments");

@@ -20,11 +20,13 @@
 // tsc_gemm.h (groups = agents); the element-wise pieces (sampling, gather, TD target, Adam) are small HBM-bound kernels.
 #include "tsc_common.h"
 #include "tsc_gemm.h"
+#include "tsc_share.h"
 #include "../../include/tsc.h"
 
 #include <cassert>
 #include <cmath>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 namespace {
@@ -603,6 +605,12 @@ struct tsc_iql {
     float *ns_ret = nullptr, *ns_disc = nullptr;
     bool ns_valid = false;        // a compute_grads ran on the handle while return_steps > 1
     std::vector<int> n_act_host;
+    // parameter sharing (tsc_iql_set_sharing)
+    std::vector<int32_t> dims;          // [A][3] n_wave, n_wait, n_act as given to create
+    std::vector<int32_t> share_class;   // [A] the caller's class ids; empty: disarmed
+    std::vector<std::vector<int>> share_lists;  // classes with >= 2 members, ascending agent indices
+    int *share_members = nullptr, *share_off = nullptr;     // device: the lists back to back, [n_lists + 1] offsets into them
+    double *share_invk = nullptr;       // device: [n_lists] 1 / members
 };
 
 namespace {
@@ -666,6 +674,30 @@ void duel_combine(tsc_iql *h, float *Q, long long rows) {
 
 size_t per_sample_lds(const tsc_iql *h) { return sizeof(float) * kPerWaves * per_wave_floats((int)h->cap); }
 
+// Parameter sharing armed: a host buffer in the parameter layout must hold bit-identical slices for the members of a class.
+// Returns 0, or 1 with the first differing pair named (what = the calling function and, where it takes several, the buffer).
+int share_check_host(const tsc_iql *h, const float *p, const char *what) {
+    const long long per_agent = h->lay.stride;
+    for (const std::vector<int> &cls : h->share_lists)
+        for (size_t j = 1; j < cls.size(); ++j) {
+            const float *p0 = p + cls[0] * per_agent, *p1 = p + cls[j] * per_agent;
+            if (memcmp(p0, p1, sizeof(float) * per_agent) == 0) continue;
+            long long i = 0;
+            while (memcmp(p0 + i, p1 + i, sizeof(float)) == 0) ++i;
+            return tsc::fail("%s: parameter sharing is armed and agents %d and %d of one class differ (first at offset %lld of the agent's "
+                             "slice: %.9g vs %.9g)", what, cls[0], cls[j], i, (double)p0[i], (double)p1[i]);
+        }
+    return 0;
+}
+
+// parameter sharing armed: every class member's gradient slice <- the class mean (share_reduce_kernel, tsc_share.h)
+void launch_share_reduce(tsc_iql *h) {
+    if (h->share_lists.empty()) return;
+    const long long per_agent = h->lay.stride;
+    hipLaunchKernelGGL(share_reduce_kernel, dim3((unsigned)((per_agent / 4 + 255) / 256), (unsigned)h->share_lists.size()), dim3(256), 0,
+                       h->stream, h->grads, per_agent, h->share_members, h->share_off, h->share_invk);
+}
+
 }  // namespace
 
 extern "C" {
@@ -711,6 +743,10 @@ int tsc_iql_create(const tsc_iql_cfg *cfg, int32_t n_env, int32_t device, tsc_iq
     TSC_HIP(h->bufs.upload(&h->rowrange, rr.data(), rr.size()));
     TSC_HIP(h->bufs.upload(&h->n_act, cfg->n_act, L.A));
     h->n_act_host.assign(cfg->n_act, cfg->n_act + L.A);
+    h->dims.resize((size_t)L.A * 3);
+    for (int a = 0; a < L.A; ++a) {
+        h->dims[(size_t)a * 3] = cfg->n_wave[a]; h->dims[(size_t)a * 3 + 1] = cfg->n_wait[a]; h->dims[(size_t)a * 3 + 2] = cfg->n_act[a];
+    }
     const long long E = n_env, A = L.A, R = E * h->B, per = A * L.SMAX;
     TSC_HIP(h->bufs.alloc(&h->params, h->nparam, true)); TSC_HIP(h->bufs.alloc(&h->grads, h->nparam, true));
     TSC_HIP(h->bufs.alloc(&h->m1, h->nparam, true)); TSC_HIP(h->bufs.alloc(&h->m2, h->nparam, true));
@@ -792,6 +828,7 @@ int tsc_iql_layout(tsc_iql *h, int64_t out[12]) {
 
 int tsc_iql_set_params(tsc_iql *h, const float *p) {
     if (!h || !p) return tsc::fail("tsc_iql_set_params: bad arguments");
+    if (share_check_host(h, p, "tsc_iql_set_params")) return 1;
     TSC_HIP(hipStreamSynchronize(h->stream));
     TSC_HIP(hipMemcpy(h->params, p, sizeof(float) * h->nparam, hipMemcpyHostToDevice));
     return 0;
@@ -812,6 +849,7 @@ int tsc_iql_get_opt_state(tsc_iql *h, float *m, float *v, int64_t *t) {
 }
 int tsc_iql_set_opt_state(tsc_iql *h, const float *m, const float *v, int64_t t) {
     if (!h || !m || !v || t < 0) return tsc::fail("tsc_iql_set_opt_state: bad arguments");
+    if (share_check_host(h, m, "tsc_iql_set_opt_state (first moments)") || share_check_host(h, v, "tsc_iql_set_opt_state (second moments)")) return 1;
     TSC_HIP(hipStreamSynchronize(h->stream));
     TSC_HIP(hipMemcpy(h->m1, m, sizeof(float) * h->nparam, hipMemcpyHostToDevice));
     TSC_HIP(hipMemcpy(h->m2, v, sizeof(float) * h->nparam, hipMemcpyHostToDevice));
@@ -1039,6 +1077,7 @@ int tsc_iql_apply_grads(tsc_iql *h, double lr, double grad_scale, double *stats_
     const QLayout &L = h->lay;
     hipStream_t st = h->stream;
     tsc::ProfScope ps(tsc::KID_IQL_ADAM, st);          // norm + Adam
+    launch_share_reduce(h);                            // parameter sharing armed: class members take the class-mean gradient first
     hipLaunchKernelGGL(iql_norm_kernel, dim3(L.A * kNormSlices), dim3(256), 0, st, h->grads, L.stride, grad_scale, h->norm2);
     h->adam_t += 1;
     const double lr_t = lr * sqrt(1.0 - pow(0.999, (double)h->adam_t)) / (1.0 - pow(0.9, (double)h->adam_t));
@@ -1057,6 +1096,83 @@ int tsc_iql_apply_grads(tsc_iql *h, double lr, double grad_scale, double *stats_
             for (int k = 0; k < kNormSlices; ++k) n2[a] += n2p[(size_t)a * kNormSlices + k];
         for (int a = 0; a < L.A; ++a) { stats_host[a * 2] = s[a * 2]; stats_host[a * 2 + 1] = sqrt(n2[a]); }
     }
+    return 0;
+}
+
+int tsc_iql_set_sharing(tsc_iql *h, const int32_t *class_of) {
+    if (!h) return tsc::fail("null handle");
+    const QLayout &L = h->lay;
+    const auto drop = [h]() {
+        h->bufs.release(h->share_members); h->bufs.release(h->share_off); h->bufs.release(h->share_invk);
+        h->share_members = h->share_off = nullptr; h->share_invk = nullptr;
+        h->share_class.clear(); h->share_lists.clear();
+    };
+    TSC_HIP(hipSetDevice(h->device));
+    if (!class_of) {                                  // disarm: parameters, moments and the frozen copy stay as they are
+        TSC_HIP(hipStreamSynchronize(h->stream));
+        drop();
+        return 0;
+    }
+    const long long per_agent = L.stride;
+    if (per_agent % 4) return tsc::fail("tsc_iql_set_sharing: an agent's slice of %lld floats is not a multiple of 4", per_agent);
+    std::string bad;
+    for (int a = 0; a < L.A; ++a)
+        if (class_of[a] < 0 || class_of[a] >= L.A) bad += (bad.empty() ? "" : ", ") + std::to_string(a) + " (id " + std::to_string(class_of[a]) + ")";
+    if (!bad.empty()) return tsc::fail("tsc_iql_set_sharing: class id outside [0, %d) for agent(s) %s", L.A, bad.c_str());
+    std::vector<std::vector<int>> by_id(L.A);
+    for (int a = 0; a < L.A; ++a) by_id[class_of[a]].push_back(a);          // ascending agent indices
+    std::vector<std::vector<int>> lists;
+    for (const std::vector<int> &cls : by_id) {
+        for (size_t j = 1; j < cls.size(); ++j) {
+            const int32_t *d0 = &h->dims[(size_t)cls[0] * 3], *d1 = &h->dims[(size_t)cls[j] * 3];
+            if (memcmp(d0, d1, sizeof(int32_t) * 3))
+                return tsc::fail("tsc_iql_set_sharing: agents %d and %d of class %d have unequal (n_wave, n_wait, n_act): "
+                                 "(%d, %d, %d) vs (%d, %d, %d)", cls[0], cls[j], class_of[cls[0]], d0[0], d0[1], d0[2], d1[0], d1[1], d1[2]);
+        }
+        if (cls.size() >= 2) lists.push_back(cls);
+    }
+    if (lists.size() > 65535) return tsc::fail("tsc_iql_set_sharing: %zu classes of two or more agents, at most 65535", lists.size());
+    std::vector<int> members, off(1, 0);
+    std::vector<double> invk;
+    for (const std::vector<int> &cls : lists) {
+        members.insert(members.end(), cls.begin(), cls.end());
+        off.push_back((int)members.size());
+        invk.push_back(1.0 / (double)cls.size());
+    }
+    TSC_HIP(hipStreamSynchronize(h->stream));
+    int *d_members = nullptr, *d_off = nullptr;
+    double *d_invk = nullptr;
+    hipError_t e = h->bufs.upload(&d_members, members.data(), members.size());
+    if (e == hipSuccess) e = h->bufs.upload(&d_off, off.data(), off.size());
+    if (e == hipSuccess) e = h->bufs.upload(&d_invk, invk.data(), invk.size());
+    // the lowest member's parameters, Adam moments and (target network armed) frozen copy become the class's
+    for (const std::vector<int> &cls : lists)
+        for (size_t j = 1; j < cls.size() && e == hipSuccess; ++j)
+            for (float *buf : {h->params, h->m1, h->m2, h->tgt_period ? h->tparams : (float *)nullptr})
+                if (buf && e == hipSuccess)
+                    e = hipMemcpy(buf + cls[j] * per_agent, buf + cls[0] * per_agent, sizeof(float) * per_agent, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);       // the copies ran on the null stream: done before the handle's stream goes on
+    if (e != hipSuccess) {
+        h->bufs.release(d_members); h->bufs.release(d_off); h->bufs.release(d_invk);
+        TSC_HIP(e);
+    }
+    drop();
+    h->share_members = d_members; h->share_off = d_off; h->share_invk = d_invk;
+    h->share_class.assign(class_of, class_of + L.A);
+    h->share_lists = std::move(lists);
+    return 0;
+}
+
+int tsc_iql_get_sharing(tsc_iql *h, int32_t *class_of) {
+    if (!h || !class_of) return tsc::fail("tsc_iql_get_sharing: bad arguments");
+    for (int a = 0; a < h->lay.A; ++a) class_of[a] = h->share_class.empty() ? a : h->share_class[a];
+    return 0;
+}
+
+int tsc_iql_share_grads(tsc_iql *h) {
+    if (!h) return tsc::fail("null handle");
+    launch_share_reduce(h);
+    TSC_HIP(hipGetLastError());
     return 0;
 }
 
@@ -1105,6 +1221,7 @@ int tsc_iql_sync_target(tsc_iql *h) {
 int tsc_iql_set_target_params(tsc_iql *h, const float *p) {
     if (!h || !p) return tsc::fail("tsc_iql_set_target_params: bad arguments");
     if (!h->tgt_period) return tsc::fail("tsc_iql_set_target_params: no target network (tsc_iql_set_target)");
+    if (share_check_host(h, p, "tsc_iql_set_target_params")) return 1;
     TSC_HIP(hipStreamSynchronize(h->stream));
     TSC_HIP(hipMemcpy(h->tparams, p, sizeof(float) * h->nparam, hipMemcpyHostToDevice));
     return 0;

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .agents import CKPT_FORMAT, resume_sample_seed, Scheduler, allreduce_grads_, coerce_config, ortho_init, replica_sample_seed
+from .agents import (CKPT_FORMAT, SHARE_DEFAULTS, resume_sample_seed, Scheduler, allreduce_grads_, check_share_config, coerce_config, ortho_init,
+                     replica_sample_seed, share_classes)
 
 IQL_DEFAULTS = dict(max_grad_norm=40.0, gamma=0.99, lr_init=1e-4, lr_decay='constant', lr_min=0.0, epsilon_init=1.0,
                     epsilon_min=0.01, epsilon_decay='linear', epsilon_ratio=0.5, num_fc=128, num_h=64, batch_size=20,
@@ -138,6 +139,9 @@ def _setup_lib(L):
     L.tsc_iql_set_return_steps.argtypes = [vp, C.c_int32]
     L.tsc_iql_get_return_steps.argtypes = [vp, C.POINTER(C.c_int32)]
     L.tsc_iql_debug_nstep.argtypes = [vp, vp, vp, vp, vp]
+    L.tsc_iql_set_sharing.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_iql_get_sharing.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.tsc_iql_share_grads.argtypes = [vp]
     L._iql_ready = True
 
 
@@ -245,11 +249,9 @@ class VecIQL:
 
     def __init__(self, n_s_ls, n_a_ls, n_w_ls, n_env, s_max, a_max, model_config=None, total_step=0, device=0, seed=None,
                  model_type='dqn', process_group=None, replica=0):
-        if not torch.cuda.is_available():
-            raise RuntimeError('VecIQL needs a GPU (MI355X); there is no CPU fallback')
         if model_type not in ('dqn', 'lr'):
             raise ValueError("model_type must be 'dqn' or 'lr' (agents/models.py:298-307)")
-        cfg = coerce_config(model_config, IQL_DEFAULTS)
+        cfg = coerce_config(model_config, {**IQL_DEFAULTS, **SHARE_DEFAULTS})
         self.cfg, self.name, self.model_type = cfg, 'iql', model_type
         self.target_update, self.double_q = target_config(cfg)
         self.prioritized_replay, self.per_alpha, self.per_beta, self.per_eps = per_config(cfg)
@@ -258,6 +260,10 @@ class VecIQL:
         self.return_steps = return_steps_config({'return_steps': given.get('return_steps', cfg['return_steps'])})
         if self.dueling and model_type != 'dqn':
             raise ValueError("dueling = 1 needs model_type 'dqn': a linear Q with a value column spans the same functions")
+        share_params = check_share_config(cfg)
+        self.share = None           # share_params = 1: the class id of every agent (agents.share_classes), armed below
+        if not torch.cuda.is_available():       # (behind the config checks, which need no device)
+            raise RuntimeError('VecIQL needs a GPU (MI355X); there is no CPU fallback')
         self.per_n = 0              # environment steps the beta schedule has counted (backward calls x batch_size, like lr_scheduler.n)
         self.n_agent, self.E = len(n_s_ls), int(n_env)
         self.n_s_ls, self.n_a_ls, self.n_w_ls = list(n_s_ls), list(n_a_ls), list(n_w_ls)
@@ -315,6 +321,8 @@ class VecIQL:
         if self.return_steps > 1:   # (no checkpoint key: the parameters mean the same under every horizon)
             _lib.check(L.tsc_iql_set_return_steps(h, self.return_steps))
         self.init_params(seed)
+        if share_params:            # the lowest member's orthogonal draw becomes its class's (theta- with it: arming copies the frozen copy too)
+            self.set_sharing(share_classes(self.n_wave_ls, self.n_w_ls, [0] * self.n_agent, self.n_a_ls))
         if self.world > 1:
             t = torch.from_numpy(self.get_flat()).to(self.device)
             dist.broadcast(t, src=0, group=self.pg)
@@ -338,11 +346,43 @@ class VecIQL:
     # ---- parameters -------------------------------------------------------------------------------------------
     def init_params(self, seed=None):
         rng = np.random.RandomState(seed) if seed is not None else np.random
-        self.set_agent_params(init_agent_params(self.layout, rng))
+        agents = init_agent_params(self.layout, rng)
+        if self.share is not None:  # sharing armed: every member takes the draw of its class's lowest member
+            low = {}
+            agents = [agents[low.setdefault(c, a)] for a, c in enumerate(self.share)]
+        self.set_agent_params(agents)
         z = np.zeros(self.n_param, np.float32)
         _lib.check(self._L.tsc_iql_set_opt_state(self._h, z.ctypes.data_as(C.c_void_p), z.ctypes.data_as(C.c_void_p), 0))
         if self.target_update:
             self.sync_target()
+
+    # ---- parameter sharing (share_params = 1; include/tsc.h tsc_iql_set_sharing) ----------------------------------
+    def set_sharing(self, class_of):
+        """Arm parameter sharing over the classes `class_of` (a class id in [0, A) per agent; None disarms): the lowest member's
+        parameters, Adam moments and frozen copy become its class's, and every later update applies the class-mean gradient."""
+        if class_of is None:
+            _lib.check(self._L.tsc_iql_set_sharing(self._h, None))
+            self.share = None
+            return
+        ids = np.ascontiguousarray(class_of, np.int32)
+        assert ids.shape == (self.n_agent,), 'one class id per agent'
+        _lib.check(self._L.tsc_iql_set_sharing(self._h, ids.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.share = [int(x) for x in ids]
+
+    def get_sharing(self):
+        """The class ids the handle holds (every agent its own class when disarmed)."""
+        out = np.zeros(self.n_agent, np.int32)
+        _lib.check(self._L.tsc_iql_get_sharing(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return [int(x) for x in out]
+
+    def share_sizes(self):
+        """Member counts of the parameter-sharing classes, largest first ([1] * n_agent when disarmed)."""
+        ids = self.share if self.share is not None else list(range(self.n_agent))
+        return sorted((ids.count(c) for c in set(ids)), reverse=True)
+
+    def share_grads(self):
+        """The class-mean reduce alone on the gradient buffer (parity hook; apply_grads runs it itself).  No-op when disarmed."""
+        _lib.check(self._L.tsc_iql_share_grads(self._h))
 
     # ---- target network (target_update > 0; include/tsc.h tsc_iql_set_target) ------------------------------------
     def sync_target(self):
@@ -493,6 +533,8 @@ class VecIQL:
             extra['per_n'] = np.int64(self.per_n)
         if self.dueling:                # same layout, another function of it
             extra['dueling'] = np.int64(1)
+        if self.share is not None:      # the classes (an unshared model reads the file as ordinary parameters)
+            extra['share'] = np.array(self.get_sharing(), np.int64)
         np.savez(os.path.join(model_dir, 'checkpoint-%d.npz' % int(global_step)), params=self.get_flat(), adam_m=m, adam_v=v,
                  layout=np.array(self.layout.as_tuple() + (self.s_max,), np.int64),
                  counters=np.array([t, self.act_step, self.update_step, self.base_seed, self.lr_scheduler.n, self.eps_scheduler.n], np.int64),
@@ -518,13 +560,25 @@ class VecIQL:
         file_dueling = int(z['dueling']) if 'dueling' in z.files else 0
         if file_dueling != self.dueling:        # column 7 of the head is the value stream in one and unused in the other
             raise ValueError('checkpoint %s was written with dueling = %d, this model has dueling = %d' % (save_file, file_dueling, self.dueling))
+        m, v = np.ascontiguousarray(z['adam_m'], np.float32), np.ascontiguousarray(z['adam_v'], np.float32)
+        if self.share is not None:              # a shared model takes a file whose class members agree, and no other (whatever its `share` key says)
+            tgt = z['target'] if self.target_update and 'target' in z.files and z['target'].size == self.n_param else None
+            for what, flat in (('parameters', z['params']), ('first Adam moments', m), ('second Adam moments', v), ('target parameters', tgt)):
+                if flat is None:
+                    continue
+                rows = np.ascontiguousarray(flat, np.float32).reshape(self.n_agent, -1)
+                low = {}
+                for a, c in enumerate(self.share):
+                    b = low.setdefault(c, a)
+                    if rows[a].tobytes() != rows[b].tobytes():
+                        raise ValueError('checkpoint %s does not fit this model (share_params = 1: the %s of agents %d and %d, '
+                                         'members of one class, differ in the file)' % (save_file, what, b, a))
         self.set_flat(z['params'])
         if self.target_update:                  # a file written without a target network: theta- <- theta
             if 'target' in z.files and z['target'].size == self.n_param:
                 self.set_target_flat(z['target'])
             else:
                 self.sync_target()
-        m, v = np.ascontiguousarray(z['adam_m'], np.float32), np.ascontiguousarray(z['adam_v'], np.float32)
         c = [int(x) for x in z['counters']]
         _lib.check(self._L.tsc_iql_set_opt_state(self._h, m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), c[0]))
         self.act_step, self.update_step = c[1], c[2]
@@ -590,6 +644,13 @@ class IQL:
 
     def sync_target(self):
         self.vec.sync_target()
+
+    def share_sizes(self):
+        return self.vec.share_sizes()
+
+    @property
+    def share(self):
+        return self.vec.share
 
     def get_target_flat(self):
         return self.vec.get_target_flat()

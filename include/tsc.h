@@ -102,7 +102,7 @@ typedef struct tsc_scenario {
 typedef struct tsc_env tsc_env;
 
 const char *tsc_last_error(void);
-int tsc_version(void);            /* 100 * major + minor; 123: tsc_model_set_sharing / tsc_model_get_sharing / tsc_model_share_grads; 122: tsc_model_dx_split / tsc_dx1w1_f32; 121: tsc_model_dw_split / tsc_dwxh_f32; 120: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
+int tsc_version(void);            /* 100 * major + minor; 124: tsc_iql_set_sharing / tsc_iql_get_sharing / tsc_iql_share_grads; 123: tsc_model_set_sharing / tsc_model_get_sharing / tsc_model_share_grads; 122: tsc_model_dx_split / tsc_dx1w1_f32; 121: tsc_model_dw_split / tsc_dwxh_f32; 120: tsc_env_set_actuated / tsc_env_actuated_actions / tsc_env_actuated_state; 119: tsc_iql_set_return_steps / tsc_iql_get_return_steps / tsc_iql_debug_nstep; 118: tsc_model_plan; 117: tsc_iql_set_dueling / tsc_iql_get_dueling; 116: tsc_iql_set_per / tsc_iql_set_per_beta / tsc_iql_get_priorities / tsc_iql_set_priorities / tsc_iql_debug_per; 115: tsc_iql_set_target / tsc_iql_sync_target / tsc_iql_set_target_params / tsc_iql_get_target_params / tsc_iql_debug_targets; 114: tsc_env_set_reward_pressure; 113: tsc_env_step_plan; 112: tsc_env_set_pressure / tsc_env_pressure_actions / tsc_env_fixed_time_actions; 111: tsc_model_compute_grads_ppo / tsc_model_apply_grads_ex / tsc_model_ppo_stats; 110: tsc_env_set_demand / tsc_env_demand; 109: tsc_env_lane_data / tsc_env_read_lane_data; 108: tsc_env_trace / tsc_env_read_trace; 107: tsc_env_set_car_following / tsc_env_car_following; 106: tsc_model_path; 105: tsc_env_set_greedy / tsc_env_greedy_actions; 104: tsc_env_counters, truncated trips flagged in tsc_env_read_trips */
 
 /* Per-kernel timing with HIP events on the launch stream (bench.py's live roofline figure; the
  * reference has no equivalent).  Off by default; read() synchronises the recorded events.
@@ -664,6 +664,28 @@ int tsc_iql_get_return_steps(tsc_iql *h, int32_t *n);
  * [E][A][batch_size] (the layout of tsc_iql_debug_batch) and G, gamma^k, k [A][E * batch_size].  Refused before the first such step.
  * Synchronises. */
 int tsc_iql_debug_nstep(tsc_iql *h, int32_t *slot_host, float *ret_host, float *disc_host, int32_t *k_host);
+/* Parameter sharing across like-shaped agents (opt-in; no reference counterpart; INTEGRATION.md "Parameter sharing"; the Q-learners'
+ * twin of tsc_model_set_sharing).  class_of_host [A]: class ids in [0, A); agents with the same id form a class and must have equal
+ * (n_wave, n_wait, n_act), so that their rows of the [A][stride] layout have the same layout, rowrange mask and action count.  Refused
+ * (tsc_last_error names the agents, nothing changes): an id out of range, two agents of one class with unequal dims, a stride that is
+ * no multiple of 4.  On arming, the lowest-index member's parameters, both Adam moments and -- where a target network is armed -- the
+ * frozen copy are copied to the other members (device to device), with the side effects of tsc_iql_set_params; the Adam step count is
+ * the handle's already.  From then on tsc_iql_apply_grads first replaces every member's gradient slice [a * stride, (a + 1) * stride)
+ * by the class mean (share_reduce_kernel: float64 sums in ascending member order, times the float64 1 / k, one rounding to float32;
+ * inside the iql_adam profile scope, behind the caller's all-reduce) and then runs the unchanged norm + clip + Adam: the members see
+ * the same gradient, norm, parameters and moments and stay bit-identical; stats[a][1] is the class's norm for every member, stats[a][0]
+ * stays the member's own loss.  The rings, the draw, the priorities and their write-back, the n-step windows and the forward stay per
+ * agent.  Classes of one agent are never read or written.  While armed, tsc_iql_set_params, tsc_iql_set_opt_state and
+ * tsc_iql_set_target_params refuse a host buffer in which two members of a class differ (the first differing pair is named; nothing
+ * is uploaded); tsc_iql_set_target / tsc_iql_sync_target copy theta and so keep the members equal by themselves.  The order of arming
+ * relative to tsc_iql_set_target, tsc_iql_set_per, tsc_iql_set_dueling and tsc_iql_set_return_steps does not matter.  class_of_host =
+ * null disarms and leaves everything as it is.  Synchronises.  (tsc_version 124) */
+int tsc_iql_set_sharing(tsc_iql *h, const int32_t *class_of_host);
+/* The class ids tsc_iql_set_sharing was given; a disarmed handle reports every agent in its own class (class_of_host[a] = a). */
+int tsc_iql_get_sharing(tsc_iql *h, int32_t *class_of_host);
+/* Parity hook: the class-mean reduce alone, on the gradient buffer (tsc_iql_grad_buffer), on the handle's stream.  A no-op when
+ * disarmed. */
+int tsc_iql_share_grads(tsc_iql *h);
 /* Measurement hook of the fused learner (tools/bench_iql.py --stamps): enable != 0 allocates the stamp buffer; the next
  * tsc_iql_compute_grads then records, for every workgroup, its start / end on the 100-MHz wall clock ([64 + 2 b],
  * [64 + 2 b + 1]) and -- in a measurement build with -DTSC_IQL_STAMPS (tools/build_variant.sh; the stamps' branches are kept

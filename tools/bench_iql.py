@@ -3,7 +3,7 @@
 (tsc_iql_compute_grads: sample + fused gradient + reduce) and the acting forward, with HIP events on the launch stream.
 
     python tools/bench_iql.py [--envs 1024] [--reps 50] [--scenario large_grid] [--model-type dqn|lr] [--target-update N [--double-q]] [--per]
-                              [--dueling] [--return-steps N]
+                              [--dueling] [--return-steps N] [--share-params]
 
 --model-type lr times IQL-LR, which always runs the grouped-GEMM path (gather, GEMMs, iql_td_kernel).  IQL-DNN runs the fused kernels at
 the widths they are built for; TSC_IQL_FUSED=0 in the environment selects the grouped path for it too ("fused" in the output line says
@@ -14,7 +14,8 @@ row set).  --per arms prioritized replay (the proportional sampler in place of t
 two-launch gradient with importance weights, the priority write-back and, on add_transition, the fill at the ring's maximum; the rings are
 filled to their capacity then, the sampler's full read).  --dueling arms the dueling head (always the two-launch gradient, its own
 instantiations of the act, target and gradient kernels).  --return-steps N arms multi-step returns (the window pre-pass iql_nstep behind the
-draw, always the two-launch gradient, the target kernel's instantiations with the rows' return and discount).  --split adds the per-kernel split of the minibatch step ("kernel_us": iql_target / iql_grad / ..., each measured in a
+draw, always the two-launch gradient, the target kernel's instantiations with the rows' return and discount).  --share-params arms
+parameter sharing (share_reduce_kernel in front of the norm, inside the iql_adam scope: compare that id of --split with and without).  --split adds the per-kernel split of the minibatch step ("kernel_us": iql_target / iql_grad / ..., each measured in a
 pass of its own with only its launches bracketed: 5 x reps more minibatch steps).  --stamps reads the gradient kernel's workgroups
 and, on an armed handle, the target kernel's as well ("target_wg_us").
 """
@@ -40,6 +41,7 @@ def main():
     ap.add_argument('--per', action='store_true', help='[MODEL_CONFIG] prioritized_replay = 1')
     ap.add_argument('--dueling', action='store_true', help='[MODEL_CONFIG] dueling = 1')
     ap.add_argument('--return-steps', type=int, default=1, help='[MODEL_CONFIG] return_steps (multi-step returns; 1: the one-step target)')
+    ap.add_argument('--share-params', action='store_true', help='[MODEL_CONFIG] share_params = 1 (one Q-network per class of like-shaped agents)')
     ap.add_argument('--split', action='store_true', help='per-kernel split of the minibatch step (one more pass of --reps steps per kernel)')
     ap.add_argument('--stamps', action='store_true', help='phase stamps of workgroup 0 and the start / end of every workgroup (tsc_iql_debug_clock)')
     args = ap.parse_args()
@@ -50,7 +52,8 @@ def main():
     E, A = args.envs, scn.n_agent
     m = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, E, scn.s_max, int(scn.green_tab.shape[1]),
                dict(batch_size=20, buffer_size=1000, reward_norm=3000.0, target_update=args.target_update, double_q=int(args.double_q),
-                    prioritized_replay=int(args.per), dueling=int(args.dueling), return_steps=args.return_steps),
+                    prioritized_replay=int(args.per), dueling=int(args.dueling), return_steps=args.return_steps,
+                    share_params=int(args.share_params)),
                total_step=10 ** 6, seed=0, model_type=args.model_type)
     g = torch.Generator(device='cuda'); g.manual_seed(0)
     mask = torch.zeros(A, scn.s_max, device='cuda')
@@ -83,6 +86,7 @@ def main():
         _lib.check(m._L.tsc_iql_compute_grads(m._h, 7, step[0]))
         step[0] += 1
     out = {'model_type': args.model_type, 'fused': m.fused, 'E': E, 'target_update': m.target_update, 'double_q': m.double_q, 'prioritized_replay': m.prioritized_replay, 'dueling': m.dueling, 'return_steps': m.return_steps,
+           'share_params': int(m.share is not None), 'share_sizes': m.share_sizes(),
            'replay_size': m.replay_size()[0], 'compute_grads_us': timed(grads, args.reps),
            'forward_us': timed(lambda: m.forward(obs, mode='explore'), args.reps),
            'minibatch_step_us': timed(lambda: m.minibatch_step(1e-4), args.reps)}

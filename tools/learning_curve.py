@@ -38,7 +38,7 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
         mcfg['lr_init'] = lr
     # the update rule ([MODEL_CONFIG] algo and its keys; unset ones keep agents.PPO_DEFAULTS)
     mcfg.update({k: v for k, v in dict(algo=algo, ppo_epochs=ppo_epochs, ppo_clip=ppo_clip, gae_lambda=gae_lambda).items() if v is not None})
-    if share_params:                    # [MODEL_CONFIG] share_params = 1: one set of weights per class of like-shaped agents (A2C agents)
+    if share_params:                    # [MODEL_CONFIG] share_params = 1: one set of weights per class of like-shaped agents (A2C agents; the Q-learners below)
         mcfg['share_params'] = 1
     env = VecTrafficEnv(scn, n_env, device=0, seed=seed0, **({'test_seeds': tuple(test_seeds)} if test_seeds else {}))
     is_q = agent in ('iqld', 'iqll')
@@ -48,6 +48,8 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
         qcfg = dict(batch_size=20, buffer_size=1000, reward_norm=3000.0 if scenario == 'large_grid' else 1.0)
         if lr is not None:
             qcfg['lr_init'] = lr
+        if share_params:
+            qcfg['share_params'] = 1
         qcfg.update(q_kw or {})         # opt-in keys of the Q-learners ([MODEL_CONFIG] prioritized_replay, per_alpha, per_beta, dueling, target_update, double_q, return_steps)
         model = VecIQL(scn.n_s_ls, scn.n_a_ls, scn.n_w_ls, n_env, scn.s_max, int(scn.green_tab.shape[1]), qcfg,
                        total_step=episodes * int(env.T), device=0, seed=seed, model_type='dqn' if agent == 'iqld' else 'lr')
@@ -99,7 +101,8 @@ def run(episodes, n_env, scenario='large_grid', agent='ma2c', seed=0, lr=None, l
     run.algo_in_force = dict({k: model.cfg[k] for k in ('prioritized_replay', 'per_alpha', 'per_beta', 'per_eps')} if model.prioritized_replay else {},
                              **({'dueling': model.dueling} if model.dueling else {}),
                              **({'return_steps': model.return_steps} if model.return_steps > 1 else {}),
-                             **({'target_update': model.target_update, 'double_q': model.double_q} if model.target_update else {})) if is_q else dict(algo=model.algo, ppo_epochs=model.n_epoch, ppo_clip=model.ppo_clip, gae_lambda=model.gae_lambda,
+                             **({'target_update': model.target_update, 'double_q': model.double_q} if model.target_update else {}),
+                             **({'share_params': 1, 'share_sizes': model.share_sizes()} if model.share is not None else {})) if is_q else dict(algo=model.algo, ppo_epochs=model.n_epoch, ppo_clip=model.ppo_clip, gae_lambda=model.gae_lambda,
         **({'share_params': 1, 'share_sizes': model.share_sizes()} if model.share is not None else {}))
     env.close(); model.close()
     return rows, ev
@@ -119,7 +122,7 @@ def main():
     ap.add_argument('--ppo-epochs', type=int, default=None, help='algo ppo: epochs per rollout (default 4)')
     ap.add_argument('--ppo-clip', type=float, default=None, help='algo ppo: clip range of the probability ratio (default 0.2)')
     ap.add_argument('--gae-lambda', type=float, default=None, help='algo ppo: GAE lambda (default 0.95)')
-    ap.add_argument('--share-params', action='store_true', help='the A2C agents: [MODEL_CONFIG] share_params = 1 (agents of equal shape share one set of weights)')
+    ap.add_argument('--share-params', action='store_true', help='the A2C agents and the Q-learners (iqld / iqll): [MODEL_CONFIG] share_params = 1 (agents of equal shape share one set of weights)')
     ap.add_argument('--objective', default=None, choices=['queue', 'wait', 'hybrid', 'pressure'],
                     help='[ENV_CONFIG] objective of the scenario (default: the scenario\'s own); pressure = the pressure reward, whose '
                          'levels are not comparable with the others\'')
